@@ -24,6 +24,10 @@ contiguous blocks over the ranks (overlapnet_amd.distributed.shard_bounds), feat
 (SURVEY.md 8d), one RCCL gather of (overlap, yaw) to rank 0 per step; value = pool_total * steps / elapsed.
 `--pool-total 0` gives the weak-scaling variant (P candidates per rank).  Prints ONE JSON line on rank 0.
 
+`--steps K` is the number of timed steps and `ms_per_step` in the line is the time of one.  `--dump-outputs DIR` writes what the last
+timed step returned (`overlap.npy`, `yaw.npy`: one entry per candidate of the sweep, in pool order); the inputs are seeded, so two
+runs with the same arguments -- of two builds, say -- can be compared output for output.
+
 `--rehearsal` (or OVN_BENCH_REHEARSAL=1) with N > 1: the SAME command path -- launcher, one rank per "GPU", shard bounds, per-step
 gather to rank 0, every rank's self-check, rank-0-only JSON -- with all N ranks on ONE device and gloo / host tensors in the
 collectives (RCCL refuses two ranks on one device); rank 0 then evaluates the whole pool in one process and requires the gathered
@@ -259,6 +263,38 @@ def relaunch_env(env):
     return e
 
 
+def refuse(msg, rank, world):
+    """Exit with `msg` on stderr.  Under the launcher the first rank to exit gets the others killed, so every rank says why first
+    and they leave together (a host barrier, bounded in time)."""
+    print(msg, file=sys.stderr, flush=True)
+    if world > 1:
+        sys.stdout.flush()
+        os.dup2(2, 1)                       # gloo's connection banner goes to C stdout; stdout is reserved for the JSON line
+        try:
+            import datetime
+            os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+            dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=60))
+            dist.barrier()
+            dist.destroy_process_group()
+        except Exception:
+            pass
+    raise SystemExit(1)
+
+
+def dump_outputs(out_dir, arrays, limit_bytes=64 << 20):
+    """Write host copies of result tensors as out_dir/<name>.npy: float32 stays float32, everything else becomes float64."""
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a if a.dtype == np.float32 else a.astype(np.float64)
+    total = sum(a.nbytes for a in host.values())
+    if total > limit_bytes:
+        raise SystemExit("bench.py --dump-outputs: %d bytes exceed the %d-byte limit" % (total, limit_bytes))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def timed(step, warmup, steps, eng, use_dist, dev, side_eng=None):
     """W untimed warm-up steps, then exactly K steps bracketed by barrier + synchronize on both sides; max over ranks.
     Returns (elapsed_s, per-kernel HIP-event profile, last step result).  `side_eng`: a second library context whose kernels
@@ -404,6 +440,9 @@ def main():
     ap.add_argument("--traffic", default="measure", choices=["measure", "committed", "none"],
                     help="roofline.traffic: two rocprofv3 PMC passes over a short run of this program (default, N = 1 warm mode; falls back "
                          "to the newest committed profile), the committed profile, or nothing")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned -- (overlap, yaw) of every pair of the sweep, in pool "
+                         "order -- as DIR/overlap.npy (float32) and DIR/yaw.npy (float64); rank 0 only")
     ap.add_argument("--accuracy-pairs", type=int, default=12, help="pairs checked against a LIVE fp64 oracle when no committed "
                                                                   "oracle outputs exist for the configuration (untimed)")
     args = ap.parse_args()
@@ -422,10 +461,10 @@ def main():
     rehearsal = bool(args.rehearsal and world > 1)
     if rehearsal:
         if visible < 1:
-            raise SystemExit("bench.py --rehearsal: needs one GPU, none visible (rank %d)" % rank)
+            refuse("bench.py --rehearsal: needs one GPU, none visible (rank %d)" % rank, rank, world)
         local_rank = 0                      # every rank on the ONE device
     elif visible < max(world, 1) or local_rank >= visible:
-        raise SystemExit("bench.py: %d GPUs needed, %d visible (rank %d)" % (world, visible, rank))
+        refuse("bench.py: %d GPUs needed, %d visible (rank %d)" % (world, visible, rank), rank, world)
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
     use_dist = world > 1 or args.force_dist
@@ -603,6 +642,8 @@ def main():
             walks.append(st["k_walk_frac"])
     walk_frac = (sum(walks) / len(walks)) if walks else 1.0
     elapsed, prof, res = timed(step, args.warmup, args.steps, eng, use_dist, dev, side_eng=qa.side if qa is not None else None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"overlap": res[0], "yaw": res[1]})
     if args.mode == "warm":
         # query 0 in a step of its own (untimed): what the accuracy block below and the same-results checks compare.  Serial order:
         # the same kernels and bits as the streamed order (tests/test_gpu_parity.py::test_query_ahead_*; `warm_serial.same_results`)

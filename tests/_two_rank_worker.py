@@ -146,7 +146,7 @@ def infer_api(work):
 
 
 def infer_demo3(work):
-    """the reference's REAL caller at world 8 -- the calls its own demo3_lcd.py made on a 259-frame run (recorded in
+    """the reference's REAL caller on several ranks -- the calls its own demo3_lcd.py made on a 259-frame run (recorded in
     tests/golden/demo_transcript.json: `infer_multiple(frame, gated reference list)`, windows of consecutive frame ids, 83 non-empty
     lists) replayed through `Infer(config, rank=, world=)` on every rank; every 7th non-empty query goes through `infer_best_match`
     instead.  Rank 0 replays the same calls on the unsharded object and compares every return value; every rank reports the pairs it

@@ -21,7 +21,8 @@ import h5py
 import numpy as np
 
 here = os.path.dirname(os.path.abspath(__file__))
-rng = np.random.default_rng(20260924)
+FULL_SEED = 20260924
+rng = np.random.default_rng(FULL_SEED)
 
 
 def keras_like(path, shapes, weightless, optimizer=True):
@@ -141,7 +142,7 @@ weightless = ["input_1", "input_2", "reshape_1", "reshape_2", "lambda_1", "lambd
 if "--full-only" not in sys.argv:
     write_fixtures()
 
-if len(sys.argv) > 1:  # optional: a full-size model_geo-shaped file for a local timing / equality check (not committed)
+if len(sys.argv) > 1:  # a full-size model_geo-shaped file (not committed; with --skeleton, what test_hdf5_lite rebuilds it from is)
     full = {
         "s_conv1": (5, 15, 4, 16), "s_conv2": (3, 15, 16, 32), "s_conv3": (3, 15, 32, 64), "s_conv3a": (3, 12, 64, 64),
         "s_conv4": (2, 9, 64, 128), "s_conv5": (1, 9, 128, 128), "s_conv6": (1, 9, 128, 128), "s_conv7": (1, 9, 128, 128),
@@ -150,4 +151,26 @@ if len(sys.argv) > 1:  # optional: a full-size model_geo-shaped file for a local
     }
     e = keras_like(sys.argv[1], full, weightless)
     np.savez(sys.argv[1] + ".expected.npz", **e)
+    if "--skeleton" in sys.argv:
+        # hdf5_full_skeleton.npz (committed): the full-size file minus its 7 MB of random data.  Every byte h5py wrote except the
+        # contiguous data blocks, which are zeroed, plus each block's offset and shape in the order `rng` drew them: the test
+        # refills them from default_rng(FULL_SEED) and checks the sha256 of the whole file before reading it
+        import hashlib
+        raw = open(sys.argv[1], "rb").read()
+        paths = ["model_weights/%s/%s/%s:0" % (k.split("/")[0], k.split("/")[0], k.split("/")[1]) for k in e]
+        paths.append("optimizer_weights/training/Adagrad/Variable:0")
+        skel = np.frombuffer(raw, np.uint8).copy()
+        offsets, shapes, ndims = [], [], []
+        with h5py.File(sys.argv[1], "r") as f:
+            for p in paths:
+                d = f[p]
+                off = d.id.get_offset()
+                skel[off:off + d.id.get_storage_size()] = 0
+                offsets.append(off)
+                shapes.append(list(d.shape) + [1] * (4 - d.ndim))      # padded to 4-D; `ndims` says how many are real
+                ndims.append(d.ndim)
+        np.savez_compressed(os.path.join(here, "hdf5_full_skeleton.npz"), skeleton=skel, sha256=np.array(hashlib.sha256(raw).hexdigest()),
+                            paths=np.array(paths), offsets=np.array(offsets, np.int64), shapes=np.array(shapes, np.int64),
+                            ndims=np.array(ndims, np.int64),
+                            seed=np.int64(FULL_SEED))
 print("ok")

@@ -83,10 +83,11 @@ def test_sharded_infer_equals_the_unsharded_object(tmp_path, fixture_npz):
     assert len(r["best"]) == frames // 5 and any(b[0] is not None for b in r["best"])
 
 
-def test_eight_ranks_replay_the_recorded_demo3_run(tmp_path, fixture_npz):
-    """Rehearsal of the multi-GPU form of the reference's real caller: EIGHT ranks (one GPU, gloo / host collectives --
-    RCCL refuses two ranks on one device; no N > 1 RCCL run exists) replay the 259 `infer_multiple` calls the reference's own
-    demo3_lcd.py made (gated windows of consecutive frame ids, tests/golden/demo_transcript.json) through `Infer(config, rank=, world=8)`,
+def test_four_ranks_replay_the_recorded_demo3_run(tmp_path, fixture_npz):
+    """Rehearsal of the multi-GPU form of the reference's real caller: FOUR ranks (one GPU, gloo / host collectives --
+    RCCL refuses two ranks on one device; no N > 1 RCCL run exists; with the test process at most five processes hold the GPU) replay
+    the 259 `infer_multiple` calls the reference's own demo3_lcd.py made (gated windows of consecutive frame ids,
+    tests/golden/demo_transcript.json) through `Infer(config, rank=, world=4)`,
     some of them as `infer_best_match`: every return value equals the unsharded object's, every scored pair ran on its owner's cache
     rows, and the work shares of THIS run stay within the bound DESIGN.md section 7 quotes for the skewed block-cyclic ownership."""
     from tools import synthetic as S
@@ -102,7 +103,7 @@ def test_eight_ranks_replay_the_recorded_demo3_run(tmp_path, fixture_npz):
            "use_depth": True, "use_normals": True, "use_class_probabilities": False, "use_class_probabilities_pca": False,
            "use_intensity": False, "batch_size": 16, "pretrained_weightsfilename": "", "_frames": frames}
     json.dump(cfg, open(tmp_path / "config.json", "w"))
-    r = _run_two("infer_demo3", tmp_path, timeout=900, world=8)
+    r = _run_two("infer_demo3", tmp_path, timeout=900, world=4)
     assert r["calls"] == 259 and r["nonempty"] == 83 and r["best_calls"] >= 10 and r["mismatch"] == [], r
     st = r["stats"]
     assert sum(s["frames_cached"] for s in st) == 259 and max(s["frames_cached"] for s in st) - min(s["frames_cached"] for s in st) <= 3, st
@@ -111,4 +112,4 @@ def test_eight_ranks_replay_the_recorded_demo3_run(tmp_path, fixture_npz):
     assert scored.sum() == 1460 and list(scored.astype(int)) == r["owner_work"], (scored, r["owner_work"])
     # work-weighted imbalance of the whole run (max / mean share over the ranks) and the worst single query against its even share
     assert scored.max() / scored.mean() <= 1.31, scored
-    assert r["worst_single_query_share"] <= 4.0, r["worst_single_query_share"]      # (a 2-element list on 8 ranks: 1 of 0.25)
+    assert r["worst_single_query_share"] <= 2.0, r["worst_single_query_share"]      # (a 2-element list on 4 ranks: 1 of 0.5)

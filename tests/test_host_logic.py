@@ -103,9 +103,8 @@ def test_error_statistics(tmp_path):
 
 def test_pair_reader_both_layouts_and_test_run(tmp_path):
     """load_pairs against files written the way demo4 writes them (demo4_gen_gt_files.py:97-109) and in the old
-    single-array layout, cross-checked with the reference's own reader when the reference tree is present."""
+    single-array layout, cross-checked with what the reference's own reader returned for the same files."""
     import os
-    import sys
     rng = np.random.default_rng(3)
     n = 7
     arr = np.zeros((n, 4))
@@ -122,16 +121,11 @@ def test_pair_reader_both_layouts_and_test_run(tmp_path):
     f1, f2, d1, d2, ov, ori = E.load_pairs([new, old])
     assert f1[:n] == ["000005"] * n and f2[:n] == ["%06d" % v for v in arr[:, 1]] and d1[:n] == ["07"] * n
     assert d1[n:] == [""] * n and np.array_equal(ov, np.tile(arr[:, 2], 2)) and np.array_equal(ori, np.tile(arr[:, 3], 2))
-    ref_dir = "/root/reference/src/two_heads"
-    if os.path.isdir(ref_dir):                      # same answer as the reference's reader
-        sys.path.insert(0, ref_dir)
-        try:
-            from overlap_orientation_npz_file2string_string_nparray import overlap_orientation_npz_file2string_string_nparray as ref
-        finally:
-            sys.path.pop(0)
-        r = ref([new, old], shuffle=False)
-        assert list(r[0]) == f1 and list(r[1]) == f2 and list(r[2]) == d1 and list(r[3]) == d2
-        assert np.array_equal(r[4], ov) and np.array_equal(r[5], ori)
+    # same answer as the reference's reader on these two files (tests/golden/make_pair_reader_golden.py ran it)
+    with np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pair_reader.npz")) as r:
+        assert np.array_equal(r["input"], arr)
+        assert list(r["imgf1"]) == f1 and list(r["imgf2"]) == f2 and list(r["dir1"]) == d1 and list(r["dir2"]) == d2
+        assert np.array_equal(r["overlap"], ov) and np.array_equal(r["orientation"], ori)
 
     class FakeInfer:            # records the pair roles run_test asks for
         def infer_multiple_vs_multiple(self, names, first, second):

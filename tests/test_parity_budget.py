@@ -36,9 +36,16 @@ def test_budget_golden_equals_live_oracle_on_sample(name):
     qf = O.leg_forward(quers[idx] if quers.shape[0] > 1 else quers, w, CFG, np.float64)
     if qf.shape[0] == 1:
         qf = np.repeat(qf, len(idx), axis=0)
-    ov, yaw, lg, _ = O.heads_forward(fv, qf, w)
+    ov, yaw, lg, corr = O.heads_forward(fv, qf, w)
     np.testing.assert_allclose(ov, g[name + "/overlap"][idx], rtol=0, atol=1e-12)
-    assert np.array_equal(yaw, g[name + "/yaw"][idx])
+    # yaw: the same bin wherever the oracle's maximum is clear.  Where the golden's top two correlation values lie within 1e-5 (the
+    # GPU test's near-tie threshold; an invalid query's flat correlation is one) the first maximum is picked by the last bits of the
+    # host's float64 sums -- there the golden's bin must be a maximum of the live correlation to within that gap
+    g_yaw = g[name + "/yaw"][idx]
+    tie = g[name + "/corr_top2_gap"][idx] < 1e-5
+    assert np.array_equal(yaw[~tie], g_yaw[~tie])
+    for k in np.nonzero(tie)[0]:
+        assert corr[k].max() - corr[k][180 - g_yaw[k]] < 1e-5, (k, yaw[k], g_yaw[k])
     if name == "gain_2":     # the last-layer gain scales the feature volumes exactly
         fv1 = O.leg_forward(cands[idx], S.make_trained_like_weights(4), CFG, np.float64)
         np.testing.assert_allclose(fv, 2.0 * fv1, rtol=1e-6, atol=1e-9)      # (weights are rounded to float32 after the scaling)
