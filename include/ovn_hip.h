@@ -39,7 +39,7 @@ typedef struct ovn_ctx ovn_ctx;
 #define OVN_ERR_STATE 3    /* call order (weights missing ...)  */
 
 /* ABI version of this header; bumped on any signature change. */
-#define OVN_ABI_VERSION 6
+#define OVN_ABI_VERSION 7
 int ovn_abi_version(void);
 
 /* Last error message of the calling thread ("" if none). */
@@ -220,11 +220,16 @@ int ovn_gt_overlap_counts(ovn_ctx* ctx, const float* ref_ranges_dev, const float
                           int proj_w, int32_t* counts_dev, void* stream);
 
 /* Arithmetic of the Delta head's contractions (c_conv1, c_conv2, c_conv3) and of ovn_spectrum's DFT; storage and accumulation
- * are fp32 either way:
+ * are fp32 in every mode:
  *   0 = fp32 matrix cores (v_mfma_f32_16x16x4_f32; bit-for-bit an fp32 FMA chain),
  *   1 = scaled 3-term fp16 split on the fp16 matrix cores (x * 2^k = hi + lo, a*w ~ ah*wh + al*wh + ah*wl; 2^-21 per operand)
  *       -- the default, measured as accurate as mode 0; both modes are held to |d overlap| <= 1e-4 against the fp64 oracle on
- *       every pair of the benchmark sweep by the parity tests. */
+ *       every pair of the benchmark sweep by the parity tests,
+ *   2 = bf16x3: DeltaLayer + c_conv1 and c_conv2 on the bf16 matrix cores with the exact 3-term bf16 split of every fp32 operand
+ *       (x = hi + mid + lo by truncation, a*w ~ the six terms down to 2^-24 relative: fp32's own rounding level); the linear terms
+ *       of the min form in fp32, c_conv3, Dense and the DFT as in mode 0.  A pair with a negative value is shifted (l + c, r + c
+ *       rounded once in fp32, the same class of error as mode 0's l - r).  Delta cache rows are ignored, as in mode 0.
+ * Any other value: OVN_ERR_ARG. */
 int ovn_set_head_precision(ovn_ctx* ctx, int mode);
 
 /* Arithmetic of the leg convolutions, same two modes as ovn_set_head_precision (default 1). */

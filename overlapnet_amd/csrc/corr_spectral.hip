@@ -410,7 +410,7 @@ int ovn_spectral_prepare(ovn_ctx* ctx, hipStream_t stream) {
 }
 
 int ovn_spectrum_forward(ovn_ctx* ctx, const float* feats, int n, float* spectra, hipStream_t stream) {
-  if (ctx->head_mode != 0) {   // f16x3 arithmetic (default)
+  if (ctx->head_mode == 1) {   // f16x3 arithmetic (default); the fp32 and bf16x3 modes take the fp32 transform
     int rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(dft_f16x3_kernel<3>), DFT_LDS);
     if (rc) return rc;
     rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(dft_f16x3_kernel<1>), DFT_LDS);

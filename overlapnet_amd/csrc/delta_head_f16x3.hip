@@ -18,7 +18,7 @@
 //   * the l' and r' terms are LINEAR, and so is c_conv1 itself (activation='linear', generateNet.py:96-99), so they are
 //     pushed through c_conv2 and added to its output per pair:
 //       o2pre[ib][jb][p] = b2[p] + TT[ib][p] + AA[jb][p] - 2 sum_{di,o} M[15 ib + di][jb][o] W2[di][o][p]
-//       M[i][jb][o]  = sum_{dj,c} min(l'[i][c], r'[15 jb + dj][c]) W1[dj][c][o]          <- delta_c1_f16x3_kernel (99.4 % of the work)
+//       M[i][jb][o]  = sum_{dj,c} min(l'[i][c], r'[15 jb + dj][c]) W1[dj][c][o]          <- delta_c1_kernel (99.4 % of the work)
 //       TT[ib][p]    = sum_{di,o} (b1[o] + sum_c l'[15 ib + di][c] Ws[c][o]) W2[di][o][p]  <- prepare kernel (Ws = W1 summed over its taps)
 //       AA[jb][p]    = sum_o (sum_{dj,c} r'[15 jb + dj][c] W1[dj][c][o]) W2s[o][p]        <- a2 + prepare kernels (W2s = W2 summed over its taps)
 //   Numerics: the three terms are ~1.5x larger than their sum, so the fp32 accumulation error is that of an fp32 evaluation
@@ -26,11 +26,11 @@
 //
 // Three kernels per call (plus delta_a2_kernel for the right volumes):
 //   delta_prepare_split_kernel  per pair: value range -> shift and scales, both volumes packed into the word streams below, TT, AA
-//   delta_c1_f16x3_kernel       the min-term contraction; NO epilogue phase: it stores -2 M (scaled, fp32) and goes on with the
+//   delta_c1_kernel       the min-term contraction; NO epilogue phase: it stores -2 M (scaled, fp32) and goes on with the
 //                               next rows; registers hold the 96 accumulators, the pass's L words and the operand fragments, and
 //                               every operand stream (W1 window, packed R words, packed L slices) arrives by LDS-DMA
 //                               (global_load_lds_dwordx4): no staging registers, no ds_write pass, no exposed global-load latency
-//   delta_c2_f16x3_kernel       c_conv2 as a streaming GEMM over the (n 576) x 960 matrix of -2 M rows (2.2 MB per pair through HBM)
+//   delta_c2_kernel       c_conv2 as a streaming GEMM over the (n 576) x 960 matrix of -2 M rows (2.2 MB per pair through HBM)
 // The one-kernel predecessor (o1 image in LDS, c_conv2 as an epilogue phase of every pass: 5.56 ms per 1024 pairs against
 // 4.2 + 0.6 + 0.21 here; its epilogue phase cost 0.93 ms for 0.25 ms of MFMAs, exposed L loads 0.43, W1 register staging 0.35)
 // is in the history (tools/experiments/delta_head_f16x3_fused.hip up to the round-3 tree, commit 170ae22).
@@ -48,6 +48,7 @@
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
@@ -145,6 +146,96 @@ __device__ __forceinline__ void make_a(const u32x4& l0, const u32x4& l1, const u
   al = __builtin_bit_cast(f16x8, q);
 }
 
+// bf16 fragments of 8 fp32 words by truncation, x = hi + mid + lo EXACTLY for every sign and every x >= 2^-110 or so:
+// hi = bits & 0xffff0000, r1 = x - hi (exact), mid = bits(r1) & 0xffff0000, lo = r1 - mid (exact, at most 8 significant bits, so its
+// upper half IS bf16(lo)).  Two VALU per term and element, the halves gathered by v_perm_b32 (element k <- word k of w0, w1).
+__device__ __forceinline__ void split3_words(const unsigned (&w)[8], bf16x8& a0, bf16x8& a1, bf16x8& a2) {
+  u32x4 p0, p1, p2;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const unsigned x0 = w[2 * p], x1 = w[2 * p + 1];
+    const unsigned r0 = __float_as_uint(__uint_as_float(x0) - __uint_as_float(x0 & 0xffff0000u));
+    const unsigned r1 = __float_as_uint(__uint_as_float(x1) - __uint_as_float(x1 & 0xffff0000u));
+    const unsigned q0 = __float_as_uint(__uint_as_float(r0) - __uint_as_float(r0 & 0xffff0000u));
+    const unsigned q1 = __float_as_uint(__uint_as_float(r1) - __uint_as_float(r1 & 0xffff0000u));
+    p0[p] = __builtin_amdgcn_perm(x1, x0, 0x07060302u);
+    p1[p] = __builtin_amdgcn_perm(r1, r0, 0x07060302u);
+    p2[p] = __builtin_amdgcn_perm(q1, q0, 0x07060302u);
+  }
+  a0 = __builtin_bit_cast(bf16x8, p0);
+  a1 = __builtin_bit_cast(bf16x8, p1);
+  a2 = __builtin_bit_cast(bf16x8, p2);
+}
+
+// Operand arithmetic of the contraction (delta_c1_kernel) and c_conv2 (delta_c2_kernel): how an operand becomes matrix-core fragments
+// (PLANES of them per operand) and which fragment products every accumulator sums, in the order term 0 .. TERMS - 1.
+struct ArithF16x3 {   // scaled fp16 hi + lo: a w ~ ah wh + al wh + ah wl (fp16 MFMA)
+  typedef f16x8 frag;
+  static constexpr int PLANES = 2, TERMS = 3;
+  static constexpr int BSETS = 2;   // W1 fragments of the contraction double-buffered per MFMA step
+  static constexpr int MAX_RT = 2;  // row tiles per pass of a sweep's contraction kernel
+  static constexpr int ta(int t) { return t == 1 ? 1 : 0; }
+  static constexpr int tb(int t) { return t == 2 ? 1 : 0; }
+  static __device__ __forceinline__ f32x4 mma(const frag& a, const frag& b, const f32x4& c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+  }
+  // A fragments of min(l, r) from packed words (P(x) = fp16_rtz(x) << 16 | fp16_rne(x - hi), see pack_pair)
+  static __device__ __forceinline__ void min_a(const u32x4& l0, const u32x4& l1, const u32x4& r0, const u32x4& r1, frag (&a)[PLANES]) {
+    make_a(l0, l1, r0, r1, a[0], a[1]);
+  }
+  // 8 fp32 values of an A row (already scaled)
+  static __device__ __forceinline__ void split8(const f32x4& x0, const f32x4& x1, float one, frag (&a)[PLANES]) {
+    unsigned h0, h1, h2, h3, l0, l1, l2, l3;
+    split_pair(x0[0], x0[1], one, h0, l0);
+    split_pair(x0[2], x0[3], one, h1, l1);
+    split_pair(x1[0], x1[1], one, h2, l2);
+    split_pair(x1[2], x1[3], one, h3, l3);
+    a[0] = __builtin_bit_cast(f16x8, (u32x4){h0, h1, h2, h3});
+    a[1] = __builtin_bit_cast(f16x8, (u32x4){l0, l1, l2, l3});
+  }
+};
+
+struct ArithBF16x3 {   // exact 3-term bf16 split, no scales: a w ~ a0 w0 + a0 w1 + a1 w0 + a0 w2 + a1 w1 + a2 w0 (bf16 MFMA)
+  typedef bf16x8 frag;
+  static constexpr int PLANES = 3, TERMS = 6;
+  static constexpr int BSETS = 1;   // one set of the three planes, requested behind the MFMAs of a step's last slot
+  static constexpr int MAX_RT = 1;  // one row tile per pass: at two, the 96 accumulators and 3 planes spill (144 B / lane)
+  static constexpr int ta(int t) { return t == 2 || t == 4 ? 1 : (t == 5 ? 2 : 0); }
+  static constexpr int tb(int t) { return t == 1 || t == 4 ? 1 : (t == 3 ? 2 : 0); }
+  static __device__ __forceinline__ f32x4 mma(const frag& a, const frag& b, const f32x4& c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+  }
+  // A fragments of min(l, r) from raw fp32 words: for x >= 0 the bit pattern orders like x, so min_u32 IS the fp32 minimum
+  static __device__ __forceinline__ void min_a(const u32x4& l0, const u32x4& l1, const u32x4& r0, const u32x4& r1, frag (&a)[PLANES]) {
+    unsigned m[8];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      m[e] = min(l0[e], r0[e]);
+      m[4 + e] = min(l1[e], r1[e]);
+    }
+    split3_words(m, a[0], a[1], a[2]);
+  }
+  static __device__ __forceinline__ void split8(const f32x4& x0, const f32x4& x1, float, frag (&a)[PLANES]) {
+    unsigned m[8];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      m[e] = __float_as_uint(x0[e]);
+      m[4 + e] = __float_as_uint(x1[e]);
+    }
+    split3_words(m, a[0], a[1], a[2]);
+  }
+};
+
+// one fp32 weight -> its three bf16 planes (the split of split3_words)
+__device__ __forceinline__ void split3_f32(float x, __bf16& hi, __bf16& mid, __bf16& lo) {
+  const unsigned u = __float_as_uint(x);
+  const unsigned r = __float_as_uint(x - __uint_as_float(u & 0xffff0000u));
+  const unsigned q = __float_as_uint(__uint_as_float(r) - __uint_as_float(r & 0xffff0000u));
+  hi = __builtin_bit_cast(__bf16, (unsigned short)(u >> 16));
+  mid = __builtin_bit_cast(__bf16, (unsigned short)(r >> 16));
+  lo = __builtin_bit_cast(__bf16, (unsigned short)(q >> 16));
+}
+
 // out[0] = max |w|, out[1] = max over columns n of sum_k |w[k][n]| for a row-major [K][N] matrix; one workgroup.
 __global__ __launch_bounds__(256) void delta_wstats_kernel(const float* __restrict__ w, int K, int N, float* __restrict__ out) {
   __shared__ float red[256];
@@ -234,6 +325,32 @@ __global__ void delta_prep_w2_f16_kernel(const float* __restrict__ w2, _Float16*
     const size_t base = (((size_t)ks * 8 + nt) * 2) * 512 + lane * 8 + e;
     w2p[base] = hi;
     w2p[base + 512] = lo;
+  }
+}
+
+// bf16x3 planes of c_conv1 / c_conv2 in the fragment orders above with a third plane: W1b[u][nt(4)][pl(3)][lane][8],
+// W2b[ks][nt(8)][pl(3)][lane][8] (no scales: bf16 has the exponent range of fp32)
+__global__ void delta_prep_w1_bf16x3_kernel(const float* __restrict__ w1, __bf16* __restrict__ w1b) {
+  const int total = S * 4 * 4 * 64 * 8;
+  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
+    const int e = idx & 7, lane = (idx >> 3) & 63, nt = (idx >> 9) & 3, u = idx >> 11;
+    const int s = u / S, dj = u - s * S;
+    const int c = 32 * (lane >> 4) + 8 * s + e, o = 16 * nt + (lane & 15);
+    const size_t base = (((size_t)u * 4 + nt) * 3) * 512 + lane * 8 + e;
+    split3_f32(w1[(dj * FC + c) * O1 + o], w1b[base], w1b[base + 512], w1b[base + 1024]);
+  }
+}
+
+__global__ void delta_prep_w2_bf16x3_kernel(const float* __restrict__ w2, __bf16* __restrict__ w2b) {
+  const int total = (K2 / 32) * 8 * 64 * 8;
+  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
+    const int e = idx & 7, lane = (idx >> 3) & 63, nt = (idx >> 9) & 7, ks = idx >> 12;
+    const int kp = 32 * ks + 8 * (lane >> 4) + e;
+    const int m = kp & 63;
+    const int k = (kp & ~63) + 16 * (m & 3) + (m >> 2);
+    const int p = 16 * nt + (lane & 15);
+    const size_t base = (((size_t)ks * 8 + nt) * 3) * 512 + lane * 8 + e;
+    split3_f32(w2[k * O2 + p], w2b[base], w2b[base + 512], w2b[base + 1024]);
   }
 }
 
@@ -989,6 +1106,177 @@ __global__ __launch_bounds__(512) void delta_query_kernel(const float* __restric
   }
 }
 
+// ---- bf16x3 mode: the preparation of a pair --------------------------------------------------------------------------------------
+// No scales and no packing: the contraction reads the fp32 words of l' = l + c and r' = r + c themselves (c = -min(0, smallest value of
+// the pair), rounded once in fp32 when c != 0; `+ c` also turns a -0 into +0, whose word would otherwise order above every positive
+// one).  R words of one column group's chunk stay contiguous: pr[jb][slice][tap][g][8] with entry e = channel 32 g + 8 slice + e.
+__device__ __forceinline__ void store_rwords_f32(const float* __restrict__ Rf, float c, unsigned* __restrict__ Pr, int tid, int nthreads) {
+  for (int i8 = tid; i8 < OVN_FEAT_ELEMS / 8; i8 += nthreads) {
+    const int jrow = i8 >> 4, sc = (i8 >> 2) & 3, gq = i8 & 3;
+    const int jb = jrow / S, dj = jrow - jb * S;
+    const float* src = Rf + (size_t)jrow * FC + 32 * gq + 8 * sc;
+    const f32x4 v0 = *reinterpret_cast<const f32x4*>(src), v1 = *reinterpret_cast<const f32x4*>(src + 4);
+    u32x4 w0, w1;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      w0[e] = __float_as_uint(v0[e] + c);
+      w1[e] = __float_as_uint(v1[e] + c);
+    }
+    unsigned* dst = Pr + ((jb * 4 + sc) * S + dj) * 32 + gq * 8;
+    *reinterpret_cast<u32x4*>(dst) = w0;
+    *reinterpret_cast<u32x4*>(dst + 4) = w1;
+  }
+}
+
+// the query's words of a 1-vs-N sweep (shift 0), shared by every pair that needs no shift
+__global__ __launch_bounds__(512) void delta_qwords_bf16x3_kernel(const float* __restrict__ feats_r, unsigned* __restrict__ qwords) {
+  store_rwords_f32(feats_r, 0.0f, qwords, blockIdx.x * 512 + threadIdx.x, gridDim.x * 512);
+}
+
+constexpr size_t PREP_B3_LDS = ((size_t)FW * O1 + (size_t)G * O1 + 2 * NWAVE) * sizeof(float);
+
+// Per pair: the shift, the word streams (pl channel-major [c][360]; pr per pair unless the query's shared words serve), and the linear
+// terms in fp32: T = b1 + l' Ws on the fp32 matrix cores into LDS, TT + b2 = T W2 + b2 on the fp32 matrix cores, AA = (A2 + c w1col) W2s
+// by FMAs as in delta_prepare_split_kernel.  scales = {1, -2, 1, 1}: the contraction stores -2 M, c_conv2 needs no rescaling.
+__global__ __launch_bounds__(512) void delta_prepare_bf16x3_kernel(
+    const float* __restrict__ feats_l, const int32_t* __restrict__ lidx, const float* __restrict__ feats_r,
+    const int32_t* __restrict__ ridx, const float* __restrict__ w1sum, const float* __restrict__ w1col, const float* __restrict__ b1,
+    const float* __restrict__ a2raw, const float* __restrict__ w2raw, const float* __restrict__ w2sum, const float* __restrict__ b2,
+    f32x4* __restrict__ scales, unsigned* __restrict__ o2max, unsigned* __restrict__ pl, unsigned* __restrict__ pr,
+    const unsigned* __restrict__ qwords, float* __restrict__ lin, DeltaDesc* __restrict__ desc) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char psm[];
+  float* Tl = reinterpret_cast<float*>(psm);   // T [360][64] = [ib][di * 64 + o]: row ib of c_conv2's A matrix
+  float* A2l = Tl + FW * O1;                   // [24][64]
+  float* red = A2l + G * O1;                   // [NWAVE]
+  const int pair = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lrow = lane & 15, g = lane >> 4;
+  const float* Lf = feats_l + (long long)(lidx ? lidx[pair] : pair) * OVN_FEAT_ELEMS;
+  const float* Rf = feats_r + (long long)(ridx ? ridx[pair] : 0) * OVN_FEAT_ELEMS;
+  float mn = 0.0f;
+  for (int i = tid; i < OVN_FEAT_ELEMS / 4; i += 512) {
+    const f32x4 a = reinterpret_cast<const f32x4*>(Lf)[i], b = reinterpret_cast<const f32x4*>(Rf)[i];
+    mn = fminf(mn, fminf(fminf(fminf(a[0], a[1]), fminf(a[2], a[3])), fminf(fminf(b[0], b[1]), fminf(b[2], b[3]))));
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) mn = fminf(mn, __shfl_down(mn, off, 64));
+  if (lane == 0) red[wave] = mn;
+  __syncthreads();
+  mn = red[0];
+#pragma unroll
+  for (int w = 1; w < NWAVE; ++w) mn = fminf(mn, red[w]);
+  const float c = mn < 0.0f ? -mn : 0.0f;
+  const bool own_r = ridx != nullptr || c != 0.0f || qwords == nullptr;
+  unsigned* Pl = pl + (size_t)pair * OVN_FEAT_ELEMS;
+  unsigned* Pr = own_r ? pr + (size_t)pair * OVN_FEAT_ELEMS : nullptr;
+  float* lp = lin + (size_t)pair * LIN_ELEMS;
+  if (tid == 0) {
+    scales[2 * pair] = (f32x4){1.0f, -2.0f, 1.0f, 1.0f};
+    scales[2 * pair + 1] = (f32x4){0.0f, c, 0.0f, 0.0f};
+    o2max[pair] = 0u;
+    DeltaDesc d;
+    d.pl = Pl;
+    d.pr = own_r ? Pr : qwords;
+    d.tt = lp;
+    d.aa = lp + G * O2;
+    desc[pair] = d;
+  }
+  // words: L channel-major (coalesced stores, gathered loads from L2), R in walk order
+  for (int idx = tid; idx < OVN_FEAT_ELEMS; idx += 512) {
+    const int ch = idx / FW, i = idx - ch * FW;
+    Pl[idx] = __float_as_uint(Lf[(size_t)i * FC + ch] + c);
+  }
+  if (own_r) store_rwords_f32(Rf, c, Pr, tid, 512);
+  // A2[jb][o] (true units) of this pair
+#pragma unroll
+  for (int u = 0; u < 3; ++u) {
+    const int i = tid + 512 * u;
+    const float* src = a2raw + (size_t)(ridx ? pair : 0) * A2_KSPLIT * A2_ELEMS;
+    float v = src[i];
+#pragma unroll
+    for (int k = 1; k < A2_KSPLIT; ++k) v += src[(size_t)k * A2_ELEMS + i];
+    A2l[i] = v + c * w1col[i & (O1 - 1)];
+  }
+  // T = b1 + l' Ws: 23 row tiles x 4 n-tiles of 16 x 16, wave = task; k = 16 j + 4 g + e, chain e (as ovn_delta_a2_task)
+  for (int task = wave; task < 23 * 4; task += NWAVE) {
+    const int tile = task >> 2, nt = task & 3;
+    const int i = 16 * tile + lrow;
+    const float* arow = Lf + (size_t)(i < FW ? i : FW - 1) * FC + 4 * g;
+    const float* bcol = w1sum + (size_t)(4 * g) * O1 + 16 * nt + lrow;
+    f32x4 acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    f32x4 av[FC / 16];
+    float bv[FC / 16][4];
+#pragma unroll
+    for (int j = 0; j < FC / 16; ++j) {
+      av[j] = *reinterpret_cast<const f32x4*>(arow + 16 * j);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) bv[j][e] = bcol[(size_t)(16 * j + e) * O1];
+    }
+#pragma unroll
+    for (int j = 0; j < FC / 16; ++j)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[e] = __builtin_amdgcn_mfma_f32_16x16x4f32(i < FW ? av[j][e] + c : 0.0f, bv[j][e], acc[e], 0, 0, 0);
+    const f32x4 sum = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+    const float bb = b1[16 * nt + lrow];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = 16 * tile + 4 * g + r;
+      if (row < FW) Tl[row * O1 + 16 * nt + lrow] = sum[r] + bb;
+    }
+  }
+  __syncthreads();
+  // TT + b2 = T W2 + b2: 2 m-tiles (ib) x 8 n-tiles (p), wave = n-tile, both m-tiles; k = 16 j + 4 g + e, chain e
+  {
+    const int nt = wave;
+    const int ib1 = 16 + lrow < G ? 16 + lrow : G - 1;
+    const float* a0 = Tl + lrow * K2 + 4 * g;
+    const float* a1 = Tl + ib1 * K2 + 4 * g;
+    const float* bcol = w2raw + (size_t)(4 * g) * O2 + 16 * nt + lrow;
+    f32x4 acc[2][4] = {};
+    constexpr int JB = 6;   // k-groups of 16 per batch of weight loads
+#pragma unroll 1
+    for (int j0 = 0; j0 < K2 / 16; j0 += JB) {
+      float bv[JB][4];
+#pragma unroll
+      for (int j = 0; j < JB; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) bv[j][e] = bcol[(size_t)(16 * (j0 + j) + e) * O2];
+#pragma unroll
+      for (int j = 0; j < JB; ++j) {
+        const f32x4 x0 = *reinterpret_cast<const f32x4*>(a0 + 16 * (j0 + j)), x1 = *reinterpret_cast<const f32x4*>(a1 + 16 * (j0 + j));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          acc[0][e] = __builtin_amdgcn_mfma_f32_16x16x4f32(x0[e], bv[j][e], acc[0][e], 0, 0, 0);
+          acc[1][e] = __builtin_amdgcn_mfma_f32_16x16x4f32(x1[e], bv[j][e], acc[1][e], 0, 0, 0);
+        }
+      }
+    }
+    const float bb = b2[16 * nt + lrow];
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) {
+      const f32x4 sum = (acc[mt][0] + acc[mt][1]) + (acc[mt][2] + acc[mt][3]);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int ib = 16 * mt + 4 * g + r;
+        if (ib < G) lp[ib * O2 + 16 * nt + lrow] = sum[r] + bb;
+      }
+    }
+  }
+  // AA[jb][p] = sum_o A2[jb][o] W2s[o][p]
+  {
+    const int p = tid & (O2 - 1), jb0 = 6 * (tid >> 7);
+    float wcol[O1];
+#pragma unroll
+    for (int o = 0; o < O1; ++o) wcol[o] = w2sum[o * O2 + p];
+    float sacc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int o = 0; o < O1; ++o)
+#pragma unroll
+      for (int j = 0; j < 6; ++j) sacc[j] = fmaf(A2l[(jb0 + j) * O1 + o], wcol[o], sacc[j]);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) lp[G * O2 + (jb0 + j) * O2 + p] = sacc[j];
+  }
+}
+
 // W2s[o][p] = sum_di W2[di][o][p] (fp64 accumulation, rounded once)
 __global__ __launch_bounds__(256) void delta_w2sum_kernel(const float* __restrict__ w2, float* __restrict__ w2sum) {
   const int idx = blockIdx.x * 256 + threadIdx.x;
@@ -1025,23 +1313,30 @@ constexpr int T_LBLK = 8 * 32 + 16;                       // words of one L bloc
 constexpr int T_LSL_WORDS = 4 * T_LBLK;                   // one L slice (32 positions x 32 rows): 4,352 B
 constexpr int T_TAIL_ROW0 = (FW / 16) * 16;               // 352: first row of the short pass
 static_assert(FW - T_TAIL_ROW0 == 8 && G % 3 == 0 && G / 3 == NWAVE, "pass geometry");
-// SPC = MFMA steps (taps) per chunk: W1 fragments SPC x 8 KB + R words [jb(24)][tap(SPC)][g(4)][8] = SPC x 3 KB per chunk
-constexpr size_t t_lds_bytes(int spc) { return 2 * (size_t)spc * STEP_BYTES + 2 * (size_t)G * spc * 32 * 4 + 2 * (size_t)T_LSL_WORDS * 4; }
+// SPC = MFMA steps (taps) per chunk: W1 fragments SPC x 8 KB (bf16x3: 12 KB) + R words [jb(24)][tap(SPC)][g(4)][8] = SPC x 3 KB per chunk
+constexpr size_t t_lds_bytes(int spc, int planes = 2) {
+  return 2 * (size_t)spc * planes * (STEP_BYTES / 2) + 2 * (size_t)G * spc * 32 * 4 + 2 * (size_t)T_LSL_WORDS * 4;
+}
 
-template <int RT, int T_SPC>
-__global__ __launch_bounds__(512) void delta_c1_f16x3_kernel(const DeltaDesc* __restrict__ desc, const _Float16* __restrict__ w1p,
-                                                             const f32x4* __restrict__ scales, float* __restrict__ o1raw, int rot,
-                                                             int nsplit, int pair0, const int32_t* __restrict__ lidx,
-                                                             const unsigned* __restrict__ live, const _Float16* __restrict__ w1c) {
+// AR = ArithF16x3 (packed words, scaled fp16 hi/lo) or ArithBF16x3 (raw fp32 words of the volumes, three bf16 planes of W1: 1.5x the
+// W1 window, twice the MFMAs; no compaction, so `live` is NULL).  Same walk, same DMA streams, same output rows.
+template <class AR, int RT, int T_SPC>
+__global__ __launch_bounds__(512) void delta_c1_kernel(const DeltaDesc* __restrict__ desc, const void* __restrict__ w1p,
+                                                       const f32x4* __restrict__ scales, float* __restrict__ o1raw, int rot,
+                                                       int nsplit, int pair0, const int32_t* __restrict__ lidx,
+                                                       const unsigned* __restrict__ live, const void* __restrict__ w1c) {
+  typedef typename AR::frag frag;
+  constexpr int NPL = AR::PLANES;
+  constexpr int STEPB = NPL * (STEP_BYTES / 2);  // W1 fragments of one MFMA step: [nt(4)][plane][lane(64)][16 B]
   constexpr int NFULL = RT ? (FW / 16) / RT : 0; // full passes: 11 (RT 2) / 22 (RT 1); RT 0: none -- EVERY pass is a short one
   constexpr int NPASS = RT ? NFULL + 1 : FW / 8; // + the short pass over rows 352 .. 359 (RT 0: 45 passes of 8 rows)
-  constexpr int T_CHB = T_SPC * STEP_BYTES;      // W1 fragments of a chunk
+  constexpr int T_CHB = T_SPC * STEPB;           // W1 fragments of a chunk
   constexpr int T_CPS = S / T_SPC;               // chunks per channel slice
   constexpr int T_RCH_WORDS = G * T_SPC * 32;    // R words of a chunk
-  constexpr int PFN = T_CHB / (512 * 16);        // W1 DMA instructions per lane and chunk
+  constexpr int PFN = (T_CHB / 16 + 511) / 512;  // W1 DMA instructions per lane and chunk (bf16x3: the last one partial, whole waves)
   constexpr int RPJ = T_SPC * 8;                 // 16-byte pieces of an R chunk per column group
   constexpr int RFN = (G * RPJ + 511) / 512;     // R DMA instructions per lane and chunk (the last one partial, whole waves)
-  static_assert(S % T_SPC == 0 && T_CHB % (512 * 16) == 0 && T_SPC == 3 && (G * RPJ) % 64 == 0, "bad chunking (the packed slice has 3, 6 or 9 steps)");
+  static_assert(S % T_SPC == 0 && (T_CHB / 16) % 64 == 0 && T_SPC == 3 && (G * RPJ) % 64 == 0, "bad chunking (the packed slice has 3, 6 or 9 steps)");
   __shared__ __attribute__((aligned(16))) unsigned char chan_s[CHAN_BYTES];
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   unsigned char* wst = smem_raw;                                                   // [2][T_CHB]
@@ -1089,6 +1384,7 @@ __global__ __launch_bounds__(512) void delta_c1_f16x3_kernel(const DeltaDesc* __
 
 #define OVN_DMA_W(CH, BUF)                                                                        \
   _Pragma("unroll") for (int q = 0; q < PFN; ++q)                                                 \
+    if (T_CHB % (512 * 16) == 0 || q * 512 + wave * 64 < T_CHB / 16)                              \
       glds16(w1bytes + (size_t)(CH) * T_CHB + (q * 512 + tid) * 16, wst + (BUF) * T_CHB + (q * 512 + wave * 64) * 16);
   // piece idx = q 512 + tid of an R chunk: column group idx / RPJ, 16 bytes idx % RPJ of its T_SPC taps (contiguous in the packed volume)
 #define OVN_DMA_R(SL, C5, BUF)                                                                    \
@@ -1180,13 +1476,12 @@ __global__ __launch_bounds__(512) void delta_c1_f16x3_kernel(const DeltaDesc* __
           const unsigned char* wcur = wst + cur * T_CHB;
           const unsigned* rcur = rbuf + cur * T_RCH_WORDS;
           u32x4 rw[NJ][2];
-          f16x8 bh[2][4], bl[2][4];
-          f16x8 ah[2], al[2];
+          frag b[AR::BSETS][NPL][4];
+          frag a[2][NPL];
 #define OVN_READ_B(SET, H)                                                                          \
-  _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) {                                                \
-    bh[SET][nt] = *reinterpret_cast<const f16x8*>(wcur + (H) * STEP_BYTES + ((nt * 2 + 0) * 64 + lane) * 16); \
-    bl[SET][nt] = *reinterpret_cast<const f16x8*>(wcur + (H) * STEP_BYTES + ((nt * 2 + 1) * 64 + lane) * 16); \
-  }
+  _Pragma("unroll") for (int nt = 0; nt < 4; ++nt)                                                  \
+    _Pragma("unroll") for (int pl = 0; pl < NPL; ++pl)                                              \
+      b[SET][pl][nt] = *reinterpret_cast<const frag*>(wcur + (H) * STEPB + ((nt * NPL + pl) * 64 + lane) * 16);
 #define OVN_READ_R(J, H)                                                                            \
   {                                                                                                 \
     rw[J][0] = *reinterpret_cast<const u32x4*>(rcur + rofs[J] + (H) * 32);                           \
@@ -1196,29 +1491,27 @@ __global__ __launch_bounds__(512) void delta_c1_f16x3_kernel(const DeltaDesc* __
           // forms the operands of slot q + 1 (16 VALU) next to the 12 MFMAs of slot q, requests a column group's R words of the next
           // step once its last tile of this step has taken them, and the next step's W1 fragments at the first slot of a step.
           // Unfenced, the scheduler hoists every operand formation and fragment read of a step to its top: 344 spilled registers.
+          // (BSETS = 1: the next step's W1 fragments are requested behind the MFMAs of the step's last slot instead.)
           constexpr int NS = NT * NJ;
           OVN_READ_B(0, 0)
 #pragma unroll
           for (int j = 0; j < NJ; ++j) OVN_READ_R(j, 0)
-          make_a(la[0][0], la[0][1], rw[0][0], rw[0][1], ah[0], al[0]);
+          AR::min_a(la[0][0], la[0][1], rw[0][0], rw[0][1], a[0]);
 #pragma unroll
           for (int q = 0; q < T_SPC * NS; ++q) {
             const int h = q / NS, k = q - NS * h, t = k / NJ, j = k - NJ * t;
             __builtin_amdgcn_sched_barrier(0);
-            if (k == 0 && h + 1 < T_SPC) OVN_READ_B((h + 1) & 1, h + 1)
+            if (AR::BSETS == 2 && k == 0 && h + 1 < T_SPC) OVN_READ_B((h + 1) % AR::BSETS, h + 1)
             if (t == NT - 1 && h + 1 < T_SPC) OVN_READ_R(j, h + 1)
             if (q + 1 < T_SPC * NS) {
               const int k1 = (q + 1) % NS, t1 = k1 / NJ, j1 = k1 - NJ * t1;
-              make_a(la[t1][0], la[t1][1], rw[j1][0], rw[j1][1], ah[(q + 1) & 1], al[(q + 1) & 1]);
+              AR::min_a(la[t1][0], la[t1][1], rw[j1][0], rw[j1][1], a[(q + 1) & 1]);
             }
-            {
 #pragma unroll
-              for (int nt = 0; nt < 4; ++nt) acc[j][t][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[q & 1], bh[h & 1][nt], acc[j][t][nt], 0, 0, 0);
+            for (int tm = 0; tm < AR::TERMS; ++tm)
 #pragma unroll
-              for (int nt = 0; nt < 4; ++nt) acc[j][t][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[q & 1], bh[h & 1][nt], acc[j][t][nt], 0, 0, 0);
-#pragma unroll
-              for (int nt = 0; nt < 4; ++nt) acc[j][t][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[q & 1], bl[h & 1][nt], acc[j][t][nt], 0, 0, 0);
-            }
+              for (int nt = 0; nt < 4; ++nt) acc[j][t][nt] = AR::mma(a[q & 1][AR::ta(tm)], b[h % AR::BSETS][AR::tb(tm)][nt], acc[j][t][nt]);
+            if (AR::BSETS == 1 && k == NS - 1 && h + 1 < T_SPC) OVN_READ_B(0, h + 1)
           }
           __builtin_amdgcn_sched_barrier(0);
 #undef OVN_READ_B
@@ -1229,7 +1522,7 @@ __global__ __launch_bounds__(512) void delta_c1_f16x3_kernel(const DeltaDesc* __
       }
       lcur ^= 1;
     }
-    // -2 M s1r -> o1raw in the streaming order of delta_c2_f16x3_kernel: [tile of 192 rows = (pair, jb / 8)][k-step 2 di + (o' >> 5)]
+    // -2 M s1r -> o1raw in the streaming order of delta_c2_kernel: [tile of 192 rows = (pair, jb / 8)][k-step 2 di + (o' >> 5)]
     // [row = (jb % 8) 24 + ib][o' & 31], o' = 4 lrow + nt: 16 bytes per lane.  The stores drain behind the next pass's first chunk.
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -1281,11 +1574,16 @@ __global__ __launch_bounds__(512) void delta_c1_f16x3_kernel(const DeltaDesc* __
 // <1, 6, 3> serves a handful of pairs (9 workgroups per pair, acc 32 registers): with nothing else on the CU, a step costs
 // the memory round trip of the operands it waits for, so they travel 5 (A) and 3 (W2) steps ahead -- 44 -> ~17 us for one pair
 // (the single-pair latency of demo2 / gated demo3 queries).  Same per-accumulator order (k-step, hi hi / lo hi / hi lo): same bits.
-template <int MT, int ASLOTS, int WSETS>
-__global__ __launch_bounds__(256, 2) void delta_c2_f16x3_kernel(const float* __restrict__ o1raw, const _Float16* __restrict__ w2p,
-                                                                         const DeltaDesc* __restrict__ desc, const f32x4* __restrict__ scales,
-                                                                         float* __restrict__ o2, unsigned* __restrict__ o2max, float one) {
-  __shared__ __attribute__((aligned(16))) unsigned char wb[2][16384];
+// AR: the arithmetic (ArithF16x3: W2 slabs of 16 KB, A rows split into scaled fp16 hi / lo; ArithBF16x3: 24 KB slabs of three bf16
+// planes, A rows split into three bf16 terms, unscaled).
+template <class AR, int MT, int ASLOTS, int WSETS>
+__global__ __launch_bounds__(256, 2) void delta_c2_kernel(const float* __restrict__ o1raw, const void* __restrict__ w2p,
+                                                          const DeltaDesc* __restrict__ desc, const f32x4* __restrict__ scales,
+                                                          float* __restrict__ o2, unsigned* __restrict__ o2max, float one) {
+  typedef typename AR::frag frag;
+  constexpr int NPL = AR::PLANES;
+  constexpr int SLAB = NPL * 8192;   // W2 fragments of one k-step: [nt(8)][plane][lane(64)][16 B]
+  __shared__ __attribute__((aligned(16))) unsigned char wb[2][SLAB];
   constexpr int NKS = K2 / 32;   // 30
   constexpr int WG_ROWS = 64 * MT;
   static_assert(C2_TILE_ROWS % WG_ROWS == 0 && 6 % ASLOTS == 0 && 6 % WSETS == 0 && NKS % 6 == 0 && ASLOTS >= 2, "bad c_conv2 tiling");
@@ -1300,16 +1598,16 @@ __global__ __launch_bounds__(256, 2) void delta_c2_f16x3_kernel(const float* __r
   const unsigned char* w2bytes = reinterpret_cast<const unsigned char*>(w2p) + tid * 16;
 
   f32x4 araw[ASLOTS][MT][2];   // [k-step mod ASLOTS][m-tile][half]
-  f32x4 wr[WSETS][4];          // [k-step mod WSETS]
+  f32x4 wr[WSETS][2 * NPL];    // [k-step mod WSETS]
 #define OVN_LOAD_A(SLOT, KS)                                                                 \
   _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) {                                        \
     araw[SLOT][mt][0] = *reinterpret_cast<const f32x4*>(abase + (KS) * (C2_TILE_ROWS * 32) + mt * 512);       \
     araw[SLOT][mt][1] = *reinterpret_cast<const f32x4*>(abase + (KS) * (C2_TILE_ROWS * 32) + mt * 512 + 4);   \
   }
 #define OVN_LOAD_W(SET, KS) \
-  _Pragma("unroll") for (int q = 0; q < 4; ++q) wr[SET][q] = *reinterpret_cast<const f32x4*>(w2bytes + (size_t)(KS) * 16384 + q * 4096);
+  _Pragma("unroll") for (int q = 0; q < 2 * NPL; ++q) wr[SET][q] = *reinterpret_cast<const f32x4*>(w2bytes + (size_t)(KS) * SLAB + q * 4096);
 #define OVN_STORE_W(SET, BUF) \
-  _Pragma("unroll") for (int q = 0; q < 4; ++q) *reinterpret_cast<f32x4*>(&wb[BUF][q * 4096 + tid * 16]) = wr[SET][q];
+  _Pragma("unroll") for (int q = 0; q < 2 * NPL; ++q) *reinterpret_cast<f32x4*>(&wb[BUF][q * 4096 + tid * 16]) = wr[SET][q];
 
   f32x4 acc[MT][8];
 #pragma unroll
@@ -1332,26 +1630,17 @@ __global__ __launch_bounds__(256, 2) void delta_c2_f16x3_kernel(const float* __r
     if ((KS) + WSETS < NKS) OVN_LOAD_W((J) % WSETS, (KS) + WSETS)                                                 \
     if ((KS) + ASLOTS - 1 < NKS) OVN_LOAD_A(((J) + ASLOTS - 1) % ASLOTS, (KS) + ASLOTS - 1)                       \
     __builtin_amdgcn_sched_barrier(0);   /* the scheduler otherwise sinks the loads next to their first use */      \
-    f16x8 ah[MT], al[MT];                                                                                         \
-    _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) {                                                           \
-      unsigned h0, h1, h2, h3, l0, l1, l2, l3;                                                                    \
-      split_pair(araw[(J) % ASLOTS][mt][0][0], araw[(J) % ASLOTS][mt][0][1], one, h0, l0);                        \
-      split_pair(araw[(J) % ASLOTS][mt][0][2], araw[(J) % ASLOTS][mt][0][3], one, h1, l1);                        \
-      split_pair(araw[(J) % ASLOTS][mt][1][0], araw[(J) % ASLOTS][mt][1][1], one, h2, l2);                        \
-      split_pair(araw[(J) % ASLOTS][mt][1][2], araw[(J) % ASLOTS][mt][1][3], one, h3, l3);                        \
-      ah[mt] = __builtin_bit_cast(f16x8, (u32x4){h0, h1, h2, h3});                                                \
-      al[mt] = __builtin_bit_cast(f16x8, (u32x4){l0, l1, l2, l3});                                                \
-    }                                                                                                             \
+    frag af[MT][NPL];                                                                                             \
+    _Pragma("unroll") for (int mt = 0; mt < MT; ++mt)                                                             \
+      AR::split8(araw[(J) % ASLOTS][mt][0], araw[(J) % ASLOTS][mt][1], one, af[mt]);                              \
     const unsigned char* wcur = &wb[(J) & 1][lane * 16];                                                          \
     _Pragma("unroll") for (int nt = 0; nt < 8; ++nt) {                                                            \
-      const f16x8 bh = *reinterpret_cast<const f16x8*>(wcur + (nt * 2) * 1024);                                   \
-      const f16x8 bl = *reinterpret_cast<const f16x8*>(wcur + (nt * 2 + 1) * 1024);                               \
-      _Pragma("unroll") for (int mt = 0; mt < MT; ++mt)                                                           \
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[mt], bh, acc[mt][nt], 0, 0, 0);                 \
-      _Pragma("unroll") for (int mt = 0; mt < MT; ++mt)                                                           \
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[mt], bh, acc[mt][nt], 0, 0, 0);                 \
-      _Pragma("unroll") for (int mt = 0; mt < MT; ++mt)                                                           \
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[mt], bl, acc[mt][nt], 0, 0, 0);                 \
+      frag bf[NPL];                                                                                               \
+      _Pragma("unroll") for (int pl = 0; pl < NPL; ++pl)                                                          \
+        bf[pl] = *reinterpret_cast<const frag*>(wcur + (nt * NPL + pl) * 1024);                                   \
+      _Pragma("unroll") for (int tm = 0; tm < AR::TERMS; ++tm)                                                    \
+        _Pragma("unroll") for (int mt = 0; mt < MT; ++mt)                                                         \
+          acc[mt][nt] = AR::mma(af[mt][AR::ta(tm)], bf[AR::tb(tm)], acc[mt][nt]);                                 \
     }                                                                                                             \
     if ((KS) + 1 < NKS) OVN_STORE_W(((J) + 1) % WSETS, ((J) + 1) & 1)                                             \
     __syncthreads();                                                                                              \
@@ -1438,6 +1727,44 @@ static int pick_nsplit(int n) {
   return 1;
 }
 
+// the contraction kernel for n pairs split nsplit ways (pick_nsplit): 45 / 23 = 8-row / one-row-tile passes, one per workgroup; the
+// passes of a pair are independent, so any split (and RT 0 / 1 / 2) gives the same bits
+template <class AR>
+static int launch_c1(int n, int nsplit, const DeltaDesc* desc, const void* w1, const f32x4* scales, float* o1raw, int pair0,
+                     const int32_t* lidx, const unsigned* live, const void* w1c, hipStream_t stream) {
+  const size_t lds = t_lds_bytes(3, AR::PLANES);
+  int rc = OVN_OK;
+  if (nsplit == 45) {   // up to five pairs: 8-row passes, one per workgroup
+    rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_c1_kernel<AR, 0, 3>), lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL((delta_c1_kernel<AR, 0, 3>), dim3(n * nsplit), dim3(512), lds, stream, desc, w1, scales, o1raw, 1, nsplit, pair0, lidx, live, w1c);
+    return OVN_OK;
+  }
+  if constexpr (AR::MAX_RT >= 2) {
+    if (nsplit != 23) {
+      rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_c1_kernel<AR, 2, 3>), lds);
+      if (rc) return rc;
+      hipLaunchKernelGGL((delta_c1_kernel<AR, 2, 3>), dim3(n * nsplit), dim3(512), lds, stream, desc, w1, scales, o1raw, 1, nsplit, pair0, lidx, live, w1c);
+      return OVN_OK;
+    }
+  }
+  // one row tile per pass (22 + 1 passes): a handful of pairs, one pass per workgroup (nsplit 23) -- or every sweep when MAX_RT = 1
+  rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_c1_kernel<AR, 1, 3>), lds);
+  if (rc) return rc;
+  hipLaunchKernelGGL((delta_c1_kernel<AR, 1, 3>), dim3(n * nsplit), dim3(512), lds, stream, desc, w1, scales, o1raw, 1, nsplit, pair0, lidx, live, w1c);
+  return OVN_OK;
+}
+
+template <class AR>
+static void launch_c2(int n, const float* o1raw, const void* w2, const DeltaDesc* desc, const f32x4* scales, float* o2, unsigned* o2max,
+                      hipStream_t stream) {
+  const int total_rows = n * G * G;
+  if (n <= 28)   // 9 workgroups of 64 rows per pair, operands several k-steps ahead (a handful of pairs: latency, not throughput)
+    hipLaunchKernelGGL((delta_c2_kernel<AR, 1, 6, 3>), dim3(total_rows / 64), dim3(256), 0, stream, o1raw, w2, desc, scales, o2, o2max, 1.0f);
+  else
+    hipLaunchKernelGGL((delta_c2_kernel<AR, 3, 3, 1>), dim3(total_rows / C2_TILE_ROWS), dim3(256), 0, stream, o1raw, w2, desc, scales, o2, o2max, 1.0f);
+}
+
 // a2 + prepare (profile class delta_prep), c_conv1 contraction (delta_c12), c_conv2 GEMM (delta_c2)
 // where ovn_delta_c12_f16x3_forward keeps A2raw inside its scratch (the yaw launch of a small sweep fills it: a2_done)
 float* ovn_delta_f16x3_a2raw(void* scratch, int n) {
@@ -1501,32 +1828,61 @@ int ovn_delta_c12_f16x3_forward(ovn_ctx* ctx, const float* feats_l, const int32_
   }
   {
     OvnProfScope ps(ctx, OVN_K_DELTA, stream);
-    if (nsplit == 45) {   // up to five pairs: 8-row passes, one per workgroup
-      rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_c1_f16x3_kernel<0, 3>), t_lds_bytes(3));
-      if (rc) return rc;
-      hipLaunchKernelGGL((delta_c1_f16x3_kernel<0, 3>), dim3(n * nsplit), dim3(512), t_lds_bytes(3), stream, desc,
-                         reinterpret_cast<const _Float16*>(ctx->w1p_h), scales, o1raw, 1, nsplit, pair0, lidx, live, w1c);
-    } else if (nsplit == 23) {   // a handful of pairs: one row tile per pass, one pass per workgroup
-      rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_c1_f16x3_kernel<1, 3>), t_lds_bytes(3));
-      if (rc) return rc;
-      hipLaunchKernelGGL((delta_c1_f16x3_kernel<1, 3>), dim3(n * nsplit), dim3(512), t_lds_bytes(3), stream, desc,
-                         reinterpret_cast<const _Float16*>(ctx->w1p_h), scales, o1raw, 1, nsplit, pair0, lidx, live, w1c);
-    } else {
-      rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_c1_f16x3_kernel<2, 3>), t_lds_bytes(3));
-      if (rc) return rc;
-      hipLaunchKernelGGL((delta_c1_f16x3_kernel<2, 3>), dim3(n * nsplit), dim3(512), t_lds_bytes(3), stream, desc,
-                         reinterpret_cast<const _Float16*>(ctx->w1p_h), scales, o1raw, 1, nsplit, pair0, lidx, live, w1c);
-    }
+    rc = launch_c1<ArithF16x3>(n, nsplit, desc, ctx->w1p_h, scales, o1raw, pair0, lidx, live, w1c, stream);
+    if (rc) return rc;
   }
   {
     OvnProfScope ps(ctx, OVN_K_DELTA_C2, stream);
-    const int total_rows = n * G * G;
-    if (n <= 28)   // 9 workgroups of 64 rows per pair, operands several k-steps ahead (a handful of pairs: latency, not throughput)
-      hipLaunchKernelGGL((delta_c2_f16x3_kernel<1, 6, 3>), dim3(total_rows / 64), dim3(256), 0, stream, o1raw,
-                         reinterpret_cast<const _Float16*>(ctx->w2p_h), desc, scales, o2, o2max, 1.0f);
-    else
-      hipLaunchKernelGGL((delta_c2_f16x3_kernel<3, 3, 1>), dim3(total_rows / C2_TILE_ROWS), dim3(256), 0, stream, o1raw,
-                         reinterpret_cast<const _Float16*>(ctx->w2p_h), desc, scales, o2, o2max, 1.0f);
+    launch_c2<ArithF16x3>(n, o1raw, ctx->w2p_h, desc, scales, o2, o2max, stream);
+  }
+  OVN_HIP_CHECK(hipGetLastError());
+  return OVN_OK;
+}
+
+// bf16x3 mode (ovn_set_head_precision 2): same scratch layout as the f16x3 path (its query block holds the query's shared words), same
+// launch structure and profile classes; dense walk of all 128 channels, no Delta cache rows.
+int ovn_delta_c12_bf16x3_forward(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx,
+                                 int n, void* scratch, float* o2, hipStream_t stream, int pair0, bool a2_done) {
+  int rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_prepare_bf16x3_kernel), PREP_B3_LDS);
+  if (rc) return rc;
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  char* p = static_cast<char*>(scratch);
+  f32x4* scales = reinterpret_cast<f32x4*>(p);
+  p += al((size_t)n * 8 * sizeof(float));
+  unsigned* o2max = reinterpret_cast<unsigned*>(p);
+  p += al((size_t)n * sizeof(unsigned));
+  unsigned* pl = reinterpret_cast<unsigned*>(p);
+  p += al((size_t)n * OVN_FEAT_ELEMS * sizeof(unsigned));
+  unsigned* pr = reinterpret_cast<unsigned*>(p);
+  p += al((size_t)n * OVN_FEAT_ELEMS * sizeof(unsigned));
+  float* lin = reinterpret_cast<float*>(p);
+  p += al((size_t)n * LIN_ELEMS * sizeof(float));
+  float* a2raw = reinterpret_cast<float*>(p);
+  p += al((size_t)(ridx ? n : 1) * A2_KSPLIT * A2_ELEMS * sizeof(float));
+  float* o1raw = reinterpret_cast<float*>(p);
+  p += al((size_t)n * O1RAW_ELEMS * sizeof(float));
+  DeltaDesc* desc = reinterpret_cast<DeltaDesc*>(p);
+  p += al((size_t)n * sizeof(DeltaDesc));
+  unsigned* qwords = ridx ? nullptr : reinterpret_cast<unsigned*>(p);   // QBLOCK_WORDS >= one volume of words
+  static_assert(QBLOCK_WORDS >= (size_t)OVN_FEAT_ELEMS, "query block too small for the shared words");
+  ctx->dbg_live = nullptr;   // every pair walks all 128 channels
+  const int nsplit = pick_nsplit(n);
+  {
+    OvnProfScope ps(ctx, OVN_K_DELTA_PREP, stream);
+    if (!a2_done)
+      hipLaunchKernelGGL(delta_a2_kernel, dim3(ridx ? n : 1, A2_KSPLIT), dim3(512), 0, stream, feats_r, ridx, ctx->w1raw, a2raw);
+    if (qwords) hipLaunchKernelGGL(delta_qwords_bf16x3_kernel, dim3(12), dim3(512), 0, stream, feats_r, qwords);
+    hipLaunchKernelGGL(delta_prepare_bf16x3_kernel, dim3(n), dim3(512), PREP_B3_LDS, stream, feats_l, lidx, feats_r, ridx, ctx->w1sum,
+                       ctx->w1col, ctx->b1, a2raw, ctx->w2raw, ctx->w2sum, ctx->c2.bias, scales, o2max, pl, pr, qwords, lin, desc);
+  }
+  {
+    OvnProfScope ps(ctx, OVN_K_DELTA, stream);
+    rc = launch_c1<ArithBF16x3>(n, nsplit, desc, ctx->w1p_b3, scales, o1raw, pair0, lidx, nullptr, nullptr, stream);
+    if (rc) return rc;
+  }
+  {
+    OvnProfScope ps(ctx, OVN_K_DELTA_C2, stream);
+    launch_c2<ArithBF16x3>(n, o1raw, ctx->w2p_b3, desc, scales, o2, o2max, stream);
   }
   OVN_HIP_CHECK(hipGetLastError());
   return OVN_OK;
@@ -1614,6 +1970,13 @@ int ovn_delta_prepare_f16x3(ovn_ctx* ctx, const float* c1_kernel_dev, const floa
                      reinterpret_cast<_Float16*>(ctx->w1p_h), hs->sw1);
   hipLaunchKernelGGL(delta_prep_w2_f16_kernel, dim3(240), dim3(256), 0, stream, c2_kernel_dev,
                      reinterpret_cast<_Float16*>(ctx->w2p_h), hs->sw2);
+  // bf16x3 mode: three bf16 planes of c_conv1 / c_conv2, c_conv2 as registered (B operand of TT)
+  OVN_HIP_CHECK(hipMalloc(&ctx->w1p_b3, (size_t)S * FC * O1 * 3 * sizeof(__bf16)));
+  OVN_HIP_CHECK(hipMalloc(&ctx->w2p_b3, (size_t)K2 * O2 * 3 * sizeof(__bf16)));
+  OVN_HIP_CHECK(hipMalloc((void**)&ctx->w2raw, (size_t)K2 * O2 * sizeof(float)));
+  hipLaunchKernelGGL(delta_prep_w1_bf16x3_kernel, dim3(240), dim3(256), 0, stream, c1_kernel_dev, reinterpret_cast<__bf16*>(ctx->w1p_b3));
+  hipLaunchKernelGGL(delta_prep_w2_bf16x3_kernel, dim3(240), dim3(256), 0, stream, c2_kernel_dev, reinterpret_cast<__bf16*>(ctx->w2p_b3));
+  OVN_HIP_CHECK(hipMemcpyAsync(ctx->w2raw, c2_kernel_dev, (size_t)K2 * O2 * sizeof(float), hipMemcpyDeviceToDevice, stream));
   OVN_HIP_CHECK(hipGetLastError());
   return OVN_OK;
 }

@@ -44,6 +44,7 @@ int ovn_ws_reserve(ovn_ctx* ctx, size_t bytes, hipStream_t stream) {
     ctx->dbg_partial = nullptr;
     ctx->dbg_o2max = nullptr;
     ctx->dbg_n = 0;
+    ctx->dbg_live = nullptr;
   }
   const size_t want = bytes + bytes / 8;  // a little headroom so near-equal requests do not thrash
   OVN_HIP_CHECK(hipMalloc(&ctx->ws, want));
@@ -110,6 +111,9 @@ int ovn_destroy(ovn_ctx* ctx) {
   if (ctx->w1col) (void)hipFree(ctx->w1col);
   if (ctx->wsp_h) (void)hipFree(ctx->wsp_h);
   if (ctx->w2sum) (void)hipFree(ctx->w2sum);
+  if (ctx->w1p_b3) (void)hipFree(ctx->w1p_b3);
+  if (ctx->w2p_b3) (void)hipFree(ctx->w2p_b3);
+  if (ctx->w2raw) (void)hipFree(ctx->w2raw);
   if (ctx->ws) (void)hipFree(ctx->ws);
   if (ctx->actmax) (void)hipFree(ctx->actmax);
   if (ctx->c3_arrived) (void)hipFree(ctx->c3_arrived);
@@ -172,8 +176,11 @@ int ovn_set_head_weights(ovn_ctx* ctx, const float* c1k, const float* c1b, const
     if (ctx->w1col) (void)hipFree(ctx->w1col);
     if (ctx->wsp_h) (void)hipFree(ctx->wsp_h);
       if (ctx->w2sum) (void)hipFree(ctx->w2sum);
-    ctx->w1p_h = ctx->w2p_h = ctx->wsp_h = nullptr;
-    ctx->w1raw = ctx->w1sum = ctx->w1col = ctx->w2sum = nullptr;
+    if (ctx->w1p_b3) (void)hipFree(ctx->w1p_b3);
+    if (ctx->w2p_b3) (void)hipFree(ctx->w2p_b3);
+    if (ctx->w2raw) (void)hipFree(ctx->w2raw);
+    ctx->w1p_h = ctx->w2p_h = ctx->wsp_h = ctx->w1p_b3 = ctx->w2p_b3 = nullptr;
+    ctx->w1raw = ctx->w1sum = ctx->w1col = ctx->w2sum = ctx->w2raw = nullptr;
     ctx->w1p = ctx->b1 = ctx->wd = ctx->bd = nullptr;
     ctx->head_set = false;
   }
@@ -433,6 +440,7 @@ struct OvnFork {   // fork on construction-time request, join (on every exit pat
 static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r,
                           const int32_t* ridx, int64_t n, float* overlap, float* logit, int32_t* yaw, float* corr,
                           int corr_mode, const float* spec_l, const float* spec_r, const float* dcache_l, hipStream_t stream) {
+  ctx->dbg_live = nullptr;   // ovn_head_walk_stats describes THIS call (a sweep that compacts sets it again)
   if (ctx->head_s != OVN_S) {   // general conv1size: fp32 generality path, chunked so that the scratch stays near 2 GB
     const size_t pb = ovn_delta_generic_pair_bytes(ctx->head_g);
     int64_t chunk = (int64_t)((2ull << 30) / pb);
@@ -467,13 +475,16 @@ static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lid
   }
   const size_t o2_elems = (size_t)OVN_G * OVN_G * OVN_C2_OUT;   // 24*24*128 per pair
   const size_t o3_elems = (size_t)OVN_DENSE_IN;                 // 22*22*256 per pair
-  const bool fused = (ctx->head_mode != 0);
+  // head modes: 0 = fp32 (one kernel for DeltaLayer + c_conv1 + c_conv2, generic c_conv3, Dense); 1 = f16x3 (prepare / contraction /
+  // c_conv2 kernels, fused c_conv3 + Dense); 2 = bf16x3 (the same three Delta kernels with the exact bf16 split, generic fp32 c_conv3, Dense)
+  const bool fused = (ctx->head_mode == 1);
+  const bool split = (ctx->head_mode != 0);                     // the two-kernel Delta path with its per-pair scratch
   const int64_t chunk = ctx->head_chunk;                        // pairs per pass over the scratch (f16x3: 3.2 MB per pair)
   const int64_t cmax = n < chunk ? n : chunk;
-  // sub-chunks: only the f16x3 kernels are split (the fp32 mode is one long kernel per chunk and keeps the round-2 structure)
-  int64_t sub = (fused && ctx->head_sub > 0 && ctx->head_sub < cmax) ? ctx->head_sub : cmax;
+  // sub-chunks: only the f16x3 / bf16x3 kernels are split (the fp32 mode is one long kernel per chunk and keeps the round-2 structure)
+  int64_t sub = (split && ctx->head_sub > 0 && ctx->head_sub < cmax) ? ctx->head_sub : cmax;
   const int nsub_max = (int)((cmax + sub - 1) / sub);
-  const int nstreams = (fused && nsub_max > 1 && ctx->head_streams > 1) ? 2 : 1;
+  const int nstreams = (split && nsub_max > 1 && ctx->head_streams > 1) ? 2 : 1;
   auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const size_t o2_bytes = al((size_t)cmax * o2_elems * sizeof(float));
   // second scratch region: o3 (n,22,22,256) in fp32 mode; in f16x3 mode c_conv3 and the Dense layer are one kernel and only
@@ -481,7 +492,7 @@ static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lid
   const size_t o3_bytes = fused ? al((size_t)cmax * OVN_DENSE_PARTIALS * sizeof(float)) : al((size_t)cmax * o3_elems * sizeof(float));
   // f16x3 mode: per-pair scales, packed volumes, linear terms and the c_conv1 rows between the two Delta kernels (2.9 MB per pair),
   // one self-contained block per sub-chunk
-  const size_t sc_sub = fused ? al(ovn_delta_f16x3_scratch_bytes((int)sub, ridx != nullptr)) : 0;
+  const size_t sc_sub = split ? al(ovn_delta_f16x3_scratch_bytes((int)sub, ridx != nullptr)) : 0;
   int rc = ovn_ws_reserve(ctx, o2_bytes + o3_bytes + sc_sub * nsub_max, stream);
   if (rc) return rc;
   if (fused && ctx->c3_arrived_n < chunk) {   // arrival counters of the fused c_conv3 + Dense kernel, one per pair of a chunk (sized
@@ -512,7 +523,7 @@ static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lid
     }
     OvnProfScope ps(ctx, OVN_K_CORR_SPECTRAL, ys);
     // a small 1-vs-N sweep in one sub-chunk: the query's right-volume term of the Delta head rides in the yaw launch (csrc/delta_a2.h)
-    a2_in_yaw = fused && ridx == nullptr && n <= OVN_A2_IN_YAW_MAX_PAIRS && n <= chunk && ys == stream && nsub_max == 1 && ctx->head_s == OVN_S;
+    a2_in_yaw = split && ridx == nullptr && n <= OVN_A2_IN_YAW_MAX_PAIRS && n <= chunk && ys == stream && nsub_max == 1 && ctx->head_s == OVN_S;
     rc = ovn_corr_spectral_forward(ctx, spec_l, lidx, spec_r, ridx, (int)n, yaw, corr, ys, a2_in_yaw ? feats_r : nullptr,
                                    a2_in_yaw ? ovn_delta_f16x3_a2raw(dscratch, (int)n) : nullptr);
     if (rc) return rc;
@@ -552,7 +563,10 @@ static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lid
         }
       } else {
         float* o3s = o3 + (size_t)q0 * o3_elems;
-        {
+        if (split) {   // bf16x3: times its prepare kernels, the contraction kernel and c_conv2 separately
+          rc = ovn_delta_c12_bf16x3_forward(ctx, fl, li, feats_r, ri, np, dscratch + (size_t)j * sc_sub, o2s, st, (int)(p0 & 0x3fffffff),
+                                            a2_in_yaw);
+        } else {
           OvnProfScope ps(ctx, OVN_K_DELTA, st);
           rc = ovn_delta_c12_forward(ctx, fl, li, feats_r, ri, np, o2s, st);
         }
@@ -591,7 +605,7 @@ int ovn_heads_spectral(ovn_ctx* ctx, const float* feats_l, const float* spec_l, 
   OVN_REQUIRE(feats_l && feats_r && spec_l && spec_r && overlap && yaw, OVN_ERR_ARG, "ovn_heads_spectral: NULL buffer");
   OVN_ON_DEVICE(ctx->device);
   return delta_head_run(ctx, feats_l, lidx, feats_r, ridx, n, overlap, logit, yaw, corr, 2, spec_l, spec_r,
-                        ctx->head_mode != 0 ? dcache_l : nullptr, (hipStream_t)stream_);
+                        ctx->head_mode == 1 ? dcache_l : nullptr, (hipStream_t)stream_);   // (rows serve the f16x3 mode only)
 }
 
 int ovn_delta_head(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx,
@@ -717,7 +731,7 @@ int ovn_gt_overlap_counts(ovn_ctx* ctx, const float* ref_ranges_dev, const float
 
 int ovn_set_head_precision(ovn_ctx* ctx, int mode) {
   OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_set_head_precision: ctx is NULL");
-  OVN_REQUIRE(mode == 0 || mode == 1, OVN_ERR_ARG, "ovn_set_head_precision: mode %d (0 = fp32 MFMA, 1 = f16x3 MFMA)", mode);
+  OVN_REQUIRE(mode >= 0 && mode <= 2, OVN_ERR_ARG, "ovn_set_head_precision: mode %d (0 = fp32 MFMA, 1 = f16x3 MFMA, 2 = bf16x3 MFMA)", mode);
   ctx->head_mode = mode;
   return OVN_OK;
 }

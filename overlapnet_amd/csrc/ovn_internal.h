@@ -161,12 +161,16 @@ struct ovn_ctx {
   float* w1col = nullptr;  // [64] column sums of the c_conv1 kernel (shift term)
   void* wsp_h = nullptr;   // w1sum as scaled hi/lo fp16 fragments
   float* w2sum = nullptr;  // c_conv2 kernel summed over its 15 taps, [64][128]: the right-volume linear term pushed through c_conv2
+  void* w1p_b3 = nullptr;  // c_conv1 / c_conv2 as three bf16 planes in the fragment orders of the f16x3 path (bf16x3 head mode)
+  void* w2p_b3 = nullptr;
+  float* w2raw = nullptr;  // c_conv2 kernel as registered, [960][128] (k = di * 64 + o): B operand of TT in bf16x3 mode
   OvnHeadScales hs;
   int leg_mode = 1;        // 0 = fp32 MFMA (conv_f32.hip), 1 = scaled 3-term fp16 split on the fp16 MFMA (conv_f16x3.hip)
   int head_compact = 1;    // ovn_set_head_compaction: 1 = 1-vs-N sweeps drop the query's dead channels from the Delta contraction (exact)
   int proj_trig = 0;       // ovn_set_projection_trig: 0 = NumPy-on-AVX512 (SVML) float32 angles, 1 = correctly rounded float32 angles
   unsigned* actmax = nullptr;   // [layer][scan of the slice][OVN_ACTMAX_STRIDE] float bits of max |layer input| of that scan (f16x3 scales)
-  int head_mode = 1;       // 0 = fp32 MFMA (exact fp32), 1 = scaled 3-term fp16 split on the fp16 MFMA (default)
+  int head_mode = 1;       // 0 = fp32 MFMA (exact fp32), 1 = scaled 3-term fp16 split on the fp16 MFMA (default),
+                           // 2 = exact 3-term bf16 split on the bf16 MFMA (operands at least as wide as fp32)
   float* wd = nullptr;   // dense kernel [123904]
   float* bd = nullptr;   // dense bias [1]
   // spectral correlation head: constant twiddle layers (corr_spectral.hip)
@@ -202,7 +206,8 @@ struct ovn_ctx {
   int64_t dbg_n = 0;
   unsigned* c3_arrived = nullptr;       // arrival counters of c3_dense_kernel, one per pair of a chunk, zero between launches
   int64_t c3_arrived_n = 0;
-  const unsigned* dbg_live = nullptr;   // live-channel list of the most recent f16x3 Delta sweep (NULL: it walked all 128 channels)
+  const unsigned* dbg_live = nullptr;   // live-channel list of the most recent Delta sweep (NULL: it walked all 128 channels; reset
+                                        // by every head call and with the scratch it points into)
 };
 
 // kernel classes reported by ovn_profile_end
@@ -263,6 +268,9 @@ int ovn_delta_c12_f16x3_forward(ovn_ctx* ctx, const float* feats_l, const int32_
                                 const float* dcache_l = nullptr,   // Delta cache rows of the left pool (ovn_delta_cache), 1-vs-N only
                                 bool a2_done = false);   // A2raw of the (single) right volume is already in the scratch (ovn_delta_f16x3_a2raw)
 float* ovn_delta_f16x3_a2raw(void* scratch, int n);
+// bf16x3 head mode: the same two-kernel path with the exact bf16 split (delta_head_f16x3.hip); same scratch size and A2raw location
+int ovn_delta_c12_bf16x3_forward(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx,
+                                 int n, void* scratch, float* o2, hipStream_t stream, int pair0, bool a2_done);
 int ovn_delta_cache_forward(ovn_ctx* ctx, const float* feats, int n, float* cache, hipStream_t stream);
 int ovn_delta_walk_stats(ovn_ctx* ctx, int32_t* out16, hipStream_t stream);
 

@@ -251,7 +251,8 @@ class OvnEngine:
 
     @property
     def has_delta_cache(self) -> bool:
-        return self.conv1size == 15
+        # the bf16x3 head mode reads no Delta cache rows, so none are built for it
+        return self.conv1size == 15 and self.head_precision != "bf16x3"
 
     def delta_cache(self, feats: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """feature volumes (n,360,128) -> Delta cache rows (n, 49216): the candidate-side half of the Delta head's preparation
@@ -467,8 +468,9 @@ class OvnEngine:
     def set_head_precision(self, mode: str) -> None:
         """Arithmetic of the Delta-head contractions (fp32 storage and accumulation in both modes):
         'f16x3' (default) = scaled 3-term fp16 split on the fp16 matrix cores (22 significand bits per operand: the error of an
-        fp32 evaluation), 'f32' = fp32 matrix cores (bit-for-bit an fp32 FMA chain, 1/16 of the rate)."""
-        table = {"f32": 0, "f16x3": 1}
+        fp32 evaluation), 'f32' = fp32 matrix cores (bit-for-bit an fp32 FMA chain, 1/16 of the rate), 'bf16x3' = exact 3-term bf16
+        split on the bf16 matrix cores (operands at least as wide as fp32: 24 significand bits; include/ovn_hip.h)."""
+        table = {"f32": 0, "f16x3": 1, "bf16x3": 2}
         if mode not in table:
             raise ValueError("head precision must be one of %s" % sorted(table))
         _lib.check(self.lib.ovn_set_head_precision(self._h, table[mode]), "ovn_set_head_precision")

@@ -10,7 +10,8 @@ types and error behaviour; the Keras/TensorFlow models behind it are replaced by
   * arithmetic: fp32 storage and accumulation everywhere; the contractions run on the fp16 matrix cores with a scaled
     3-term split ("f16x3": 22 significand bits per operand -- measured against an fp64 evaluation this is as accurate as
     running every contraction in fp32, profiles/r2_parity_1024.json).  `config['precision'] = 'f32'` (optional key, absent
-    from the reference's network.yml) selects bit-for-bit fp32 FMA chains on the fp32 matrix cores at ~1/3 of the speed;
+    from the reference's network.yml) selects bit-for-bit fp32 FMA chains on the fp32 matrix cores at ~1/3 of the speed, and
+    'bf16x3' the fp32 leg with the exact 3-term bf16 split in the Delta head (fp32-wide operands, include/ovn_hip.h);
   * `pretrained_weightsfilename` may name a native `.npz` (keys `<layer>/kernel|bias`) besides the
     Keras HDF5 file (read by the built-in `hdf5_lite` parser);
   * `infer_best_match` (extension): `infer_multiple` + demo3's decision taken on the GPU;
@@ -268,9 +269,10 @@ class Infer():
     self.leg = self.engine    # reference: keras.Model (infer.py:101)
     self.head = self.engine   # reference: keras.Model (infer.py:111)
     self.precision = config.get('precision', 'f16x3')   # extension key, see the module docstring
-    if self.precision not in ('f16x3', 'f32'):
-      raise Exception("config['precision'] must be 'f16x3' or 'f32'")
-    self.engine.set_leg_precision(self.precision)
+    if self.precision not in ('f16x3', 'f32', 'bf16x3'):
+      raise Exception("config['precision'] must be 'f16x3', 'f32' or 'bf16x3'")
+    # bf16x3: the head's bf16x3 mode with the fp32 leg (the only leg arithmetic at least as wide as fp32)
+    self.engine.set_leg_precision('f32' if self.precision == 'bf16x3' else self.precision)
     self.engine.set_head_precision(self.precision)
     self.engine.set_projection_trig(self._projection_trig)
 
