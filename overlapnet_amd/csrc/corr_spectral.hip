@@ -268,7 +268,15 @@ __global__ __launch_bounds__(512) void dft_f16x3_kernel(const float* __restrict_
   m = red[0];
 #pragma unroll
   for (int w = 1; w < 8; ++w) m = fmaxf(m, red[w]);
-  const float sx = ovn_pow2_scale_for(m);
+  // power-of-two scale 2^kx that brings the largest |value| into [2^13, 2^14), applied with ldexp and NOT clamped at 2^+-100
+  // like ovn_pow2_scale_for.  With the clamp, a volume whose largest value is below 2^-86 (subnormals) stayed below the fp16 range
+  // and came out as an all-zero spectrum (yaw 180), and one above 2^114 overflowed fp16.  Between the two the scale is the
+  // clamped one and ldexp gives the bits of the power-of-two multiply (apart from subnormal spectrum values)
+  int kx = 0;
+  if (m > 0.0f && m < 3.0e38f) {
+    (void)frexpf(m, &kx);
+    kx = 14 - kx;
+  }
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
     const int item = tid + 512 * k;
@@ -279,7 +287,7 @@ __global__ __launch_bounds__(512) void dft_f16x3_kernel(const float* __restrict_
         unsigned hw[4], lw[4];
 #pragma unroll
         for (int j = 0; j < 8; j += 2) {
-          const float x0 = v[k][j][e] * sx, x1 = v[k][j + 1][e] * sx;
+          const float x0 = ldexpf(v[k][j][e], kx), x1 = ldexpf(v[k][j + 1][e], kx);
           const f16x2 hp = __builtin_bit_cast(f16x2, __builtin_amdgcn_cvt_pkrtz(x0, x1));
           f16x2 lp;
           lp[0] = (_Float16)__builtin_fmaf(x0, one, -(float)hp[0]);
@@ -335,7 +343,7 @@ __global__ __launch_bounds__(512) void dft_f16x3_kernel(const float* __restrict_
   }
 #undef DFT_LOAD_B
   // C/D layout: lane holds column lrow of its n-tile, rows (channels) 4g .. 4g+3 of each m-tile
-  const float inv = 1.0f / (sx * sT);
+  const float inv = 1.0f / sT;
   float* out = spectra + (size_t)scan * OVN_SPEC_ELEMS + (size_t)(DFT_CH * half) * SW;
 #pragma unroll
   for (int j = 0; j < NTW; ++j) {
@@ -344,7 +352,7 @@ __global__ __launch_bounds__(512) void dft_f16x3_kernel(const float* __restrict_
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) out[(size_t)(16 * mt + 4 * g + r) * SW + col] = acc[mt][j][r] * inv;
+        for (int r = 0; r < 4; ++r) out[(size_t)(16 * mt + 4 * g + r) * SW + col] = ldexpf(acc[mt][j][r] * inv, -kx);
     }
   }
 }
