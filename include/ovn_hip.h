@@ -39,7 +39,7 @@ typedef struct ovn_ctx ovn_ctx;
 #define OVN_ERR_STATE 3    /* call order (weights missing ...)  */
 
 /* ABI version of this header; bumped on any signature change. */
-#define OVN_ABI_VERSION 7
+#define OVN_ABI_VERSION 8
 int ovn_abi_version(void);
 
 /* Last error message of the calling thread ("" if none). */
@@ -112,8 +112,8 @@ int ovn_heads(ovn_ctx* ctx, const float* feats_l_dev, const int32_t* lidx_dev, c
 int ovn_delta_head(ovn_ctx* ctx, const float* feats_l_dev, const int32_t* lidx_dev, const float* feats_r_dev,
                    const int32_t* ridx_dev, int64_t n, float* overlap_dev, float* logit_dev, void* stream);
 
-/* Correlation (yaw) head alone (NormalizedCorrelation2D.py:43-109 with normalize='none'); same
- * indexing convention as ovn_heads. */
+/* Correlation (yaw) head alone (NormalizedCorrelation2D.py:43-109 with the normalisation of ovn_set_corr_normalization, 'none' by
+ * default); same indexing convention as ovn_heads.  Both volumes are normalised on the fly. */
 int ovn_corr_head(ovn_ctx* ctx, const float* feats_l_dev, const int32_t* lidx_dev, const float* feats_r_dev,
                   const int32_t* ridx_dev, int64_t n, int32_t* yaw_dev, float* corr_dev, void* stream);
 
@@ -136,6 +136,20 @@ int ovn_corr_head_spectral(ovn_ctx* ctx, const float* spec_l_dev, const int32_t*
  * Valid for the head weights registered when it was built (f16x3 head mode; the fp32 mode ignores it). */
 #define OVN_DELTA_CACHE_ELEMS 49216
 int ovn_delta_cache(ovn_ctx* ctx, const float* feats_dev, int64_t n, float* cache_dev, void* stream);
+
+/* Normalisation of the correlation head's inputs, NormalizedCorrelation2D(normalize=...) (NormalizedCorrelation2D.py:23-73):
+ *   0 none (default; what generateCorrelationHead builds, generateNet.py:343), 1 euclidean (the layer's own default:
+ *   x / sqrt(max(sum x^2, 1e-12))), 2 scaling ((x - min) / (max - min + 1e-6)), 3 standardization (y = x - mean + 1e-5,
+ *   y / sqrt(max(sum y^2, 1e-12))), each per (volume, channel) over the 360 columns; any other value: OVN_ERR_ARG.
+ * Statistics in fp64 in one fixed order, each element evaluated in fp64 and rounded once to fp32: a volume's normalised values do not
+ * depend on the call, the batch or the pair.  The Delta head reads the raw volumes in every mode (so do Delta cache rows).
+ *   ovn_corr_head, ovn_heads (no spectra)   normalise both volumes on the fly; corr_dev is the normalised correlation.
+ *   ovn_spectrum                            writes the spectrum of the NORMALISED volume: a cached spectrum is valid for the mode
+ *                                           it was built under (the same rule as Delta cache rows and head weights).
+ *   ovn_corr_head_spectral, ovn_heads_spectral   consume such spectra unchanged.
+ * Mode 0 runs the kernels of ABI 7 unchanged, with the same launches and bits. */
+int ovn_set_corr_normalization(ovn_ctx* ctx, int mode);
+int ovn_get_corr_normalization(ovn_ctx* ctx, int* mode);
 
 /* Both heads of a sweep whose candidates have their spectra (and optionally their Delta cache rows, dcache_l_dev, may be NULL) cached
  * next to their feature volumes: what `Infer.infer_multiple` runs per query.  Same outputs and indexing as ovn_heads (one index

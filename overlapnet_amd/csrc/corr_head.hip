@@ -10,6 +10,9 @@
 // diagonals, corr[k] += G[(k + j + 180) mod 360, j].  Thread k owns corr[k]; panels and the columns
 // inside a panel are added in a fixed order, so the result (and the argmax) is deterministic.
 // One workgroup (8 waves) = one pair; the candidate feature volume is read from HBM exactly once.
+// With a normalisation mode (ovn_set_corr_normalization) the NORM instantiation first derives both volumes' per-channel affine forms
+// (ovn_corr_norm_affine, two more reads of each volume from L2) and normalises every operand as it is loaded; mode 0 launches the
+// unchanged NORM = false kernel.
 #include "ovn_internal.h"
 
 namespace {
@@ -18,11 +21,12 @@ constexpr int FW = OVN_FEAT_W;
 constexpr int FC = OVN_FEAT_C;
 constexpr int GS_STRIDE = 17;  // floats per Gram row in LDS (16 + 1: column reads hit distinct banks)
 
+template <bool NORM>
 __global__ __launch_bounds__(512) void corr_head_kernel(const float* __restrict__ feats_l,
                                                         const int32_t* __restrict__ lidx,
                                                         const float* __restrict__ feats_r,
                                                         const int32_t* __restrict__ ridx, int32_t* __restrict__ yaw,
-                                                        float* __restrict__ corr) {
+                                                        float* __restrict__ corr, int norm_mode) {
   __shared__ float gs[FW * GS_STRIDE];
   __shared__ float red_v[8];
   __shared__ int red_i[8];
@@ -37,6 +41,28 @@ __global__ __launch_bounds__(512) void corr_head_kernel(const float* __restrict_
   const float* L = feats_l + (long long)(lidx ? lidx[pair] : pair) * OVN_FEAT_ELEMS;
   const float* R = feats_r + (long long)(ridx ? ridx[pair] : 0) * OVN_FEAT_ELEMS;
 
+  // normalisation: affine forms of both volumes (NORM only; the LDS below exists in that instantiation alone)
+  double* aff = nullptr;   // [0][c]: m, [1][c]: s of L; [2][c], [3][c] of R
+  double na = 0.0;
+  if constexpr (NORM) {
+    __shared__ OvnNormLds<FC> nl;
+    __shared__ double aff_s[4][FC];
+    ovn_corr_norm_affine<FC>(L, norm_mode, nl);
+    if (tid < FC) {
+      aff_s[0][tid] = nl.m[tid];
+      aff_s[1][tid] = nl.s[tid];
+    }
+    __syncthreads();
+    ovn_corr_norm_affine<FC>(R, norm_mode, nl);
+    if (tid < FC) {
+      aff_s[2][tid] = nl.m[tid];
+      aff_s[3][tid] = nl.s[tid];
+    }
+    __syncthreads();
+    aff = &aff_s[0][0];
+    na = ovn_corr_norm_add(norm_mode);
+  }
+
   // A operand: rows i = 48*wave + 16*t + lrow, channels 32g..32g+31 (same slice as the Delta kernel)
   f32x4 lreg[3][8];
 #pragma unroll
@@ -46,6 +72,16 @@ __global__ __launch_bounds__(512) void corr_head_kernel(const float* __restrict_
     for (int q = 0; q < 8; ++q)
       lreg[t][q] = (i < FW) ? *reinterpret_cast<const f32x4*>(L + i * FC + 32 * g + 4 * q)
                             : (f32x4){0.f, 0.f, 0.f, 0.f};
+    if constexpr (NORM) {
+      if (i < FW)
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int c = 32 * g + 4 * q + e;
+            lreg[t][q][e] = ovn_corr_norm_apply(lreg[t][q][e], aff[c], na, aff[FC + c]);
+          }
+    }
   }
 
   float partial = 0.f;
@@ -56,6 +92,15 @@ __global__ __launch_bounds__(512) void corr_head_kernel(const float* __restrict_
     f32x4 rreg[8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) rreg[q] = *reinterpret_cast<const f32x4*>(R + j * FC + 32 * g + 4 * q);
+    if constexpr (NORM) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int c = 32 * g + 4 * q + e;
+          rreg[q][e] = ovn_corr_norm_apply(rreg[q][e], aff[2 * FC + c], na, aff[3 * FC + c]);
+        }
+    }
 
     f32x4 acc[3];
 #pragma unroll
@@ -125,8 +170,11 @@ __global__ __launch_bounds__(512) void corr_head_kernel(const float* __restrict_
 }  // namespace
 
 int ovn_corr_forward(const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx, int n,
-                     int32_t* yaw, float* corr, hipStream_t stream) {
-  hipLaunchKernelGGL(corr_head_kernel, dim3(n), dim3(512), 0, stream, feats_l, lidx, feats_r, ridx, yaw, corr);
+                     int32_t* yaw, float* corr, hipStream_t stream, int norm_mode) {
+  if (norm_mode == 0)
+    hipLaunchKernelGGL(corr_head_kernel<false>, dim3(n), dim3(512), 0, stream, feats_l, lidx, feats_r, ridx, yaw, corr, 0);
+  else
+    hipLaunchKernelGGL(corr_head_kernel<true>, dim3(n), dim3(512), 0, stream, feats_l, lidx, feats_r, ridx, yaw, corr, norm_mode);
   OVN_HIP_CHECK(hipGetLastError());
   return OVN_OK;
 }

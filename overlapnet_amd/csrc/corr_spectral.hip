@@ -228,9 +228,11 @@ constexpr size_t DFT_LDS = 2 * (size_t)DFT_CH * DFT_LD * sizeof(_Float16) + 64;
 
 // NTW n-tiles per wave: 3 (one workgroup covers all 24 n-tiles) or 1 (three workgroups per slab, blockIdx.y: a handful of scans
 // then still fills 6 x as many CUs; the slab staging is repeated, the K loop is a third as long)
-template <int NTW>
+// NORM (ovn_set_corr_normalization != 0): the slab's 64 channels are normalised in registers before the scale is taken
+// (ovn_corr_norm_affine, its LDS borrowed from the hi image before that is written); NORM = false is the kernel of mode 0, unchanged.
+template <int NTW, bool NORM>
 __global__ __launch_bounds__(512) void dft_f16x3_kernel(const float* __restrict__ feats, const _Float16* __restrict__ tw,
-                                                       float sT, float one, float* __restrict__ spectra) {
+                                                       float sT, float one, float* __restrict__ spectra, int norm_mode) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
   _Float16* ah = reinterpret_cast<_Float16*>(dsm);
   _Float16* al = ah + DFT_CH * DFT_LD;
@@ -251,6 +253,22 @@ __global__ __launch_bounds__(512) void dft_f16x3_kernel(const float* __restrict_
     const int cq = item & 15, ib = (item < NITEM) ? (item >> 4) : 0;
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[k][j] = *reinterpret_cast<const f32x4*>(X + (size_t)(8 * ib + j) * FC + 4 * cq);
+  }
+  if constexpr (NORM) {
+    static_assert(sizeof(OvnNormLds<DFT_CH>) <= DFT_CH * DFT_LD * sizeof(_Float16), "normalisation LDS must fit in the hi image");
+    OvnNormLds<DFT_CH>& nl = *reinterpret_cast<OvnNormLds<DFT_CH>*>(dsm);
+    ovn_corr_norm_affine<DFT_CH>(X, norm_mode, nl);
+    const double na = ovn_corr_norm_add(norm_mode);
+    const int cq = tid & 15;   // (item & 15 for both items of the thread)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const double mc = nl.m[4 * cq + e], sc = nl.s[4 * cq + e];
+#pragma unroll
+      for (int k = 0; k < 2; ++k)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[k][j][e] = ovn_corr_norm_apply(v[k][j][e], mc, na, sc);
+    }
+    __syncthreads();   // every thread has read its affine forms before the hi image's padding is zeroed below
   }
 #pragma unroll
   for (int k = 0; k < 2; ++k)
@@ -417,24 +435,76 @@ int ovn_spectral_prepare(ovn_ctx* ctx, hipStream_t stream) {
   return OVN_OK;
 }
 
-int ovn_spectrum_forward(ovn_ctx* ctx, const float* feats, int n, float* spectra, hipStream_t stream) {
-  if (ctx->head_mode == 1) {   // f16x3 arithmetic (default); the fp32 and bf16x3 modes take the fp32 transform
-    int rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(dft_f16x3_kernel<3>), DFT_LDS);
-    if (rc) return rc;
-    rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(dft_f16x3_kernel<1>), DFT_LDS);
-    if (rc) return rc;
-    if (n <= 64)   // up to 128 slabs: three workgroups per slab
-      hipLaunchKernelGGL(dft_f16x3_kernel<1>, dim3(2 * n, 3), dim3(512), DFT_LDS, stream, feats,
-                         reinterpret_cast<const _Float16*>(ctx->dft.wp_h), ctx->dft.sw_h, 1.0f, spectra);
-    else
-      hipLaunchKernelGGL(dft_f16x3_kernel<3>, dim3(2 * n), dim3(512), DFT_LDS, stream, feats,
-                         reinterpret_cast<const _Float16*>(ctx->dft.wp_h), ctx->dft.sw_h, 1.0f, spectra);
-    OVN_HIP_CHECK(hipGetLastError());
-    return OVN_OK;
+namespace {
+
+template <bool NORM>
+int launch_dft_f16x3(ovn_ctx* ctx, const float* feats, int n, float* spectra, hipStream_t stream) {
+  int rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(dft_f16x3_kernel<3, NORM>), DFT_LDS);
+  if (rc) return rc;
+  rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(dft_f16x3_kernel<1, NORM>), DFT_LDS);
+  if (rc) return rc;
+  if (n <= 64)   // up to 128 slabs: three workgroups per slab
+    hipLaunchKernelGGL((dft_f16x3_kernel<1, NORM>), dim3(2 * n, 3), dim3(512), DFT_LDS, stream, feats,
+                       reinterpret_cast<const _Float16*>(ctx->dft.wp_h), ctx->dft.sw_h, 1.0f, spectra, ctx->corr_norm);
+  else
+    hipLaunchKernelGGL((dft_f16x3_kernel<3, NORM>), dim3(2 * n), dim3(512), DFT_LDS, stream, feats,
+                       reinterpret_cast<const _Float16*>(ctx->dft.wp_h), ctx->dft.sw_h, 1.0f, spectra, ctx->corr_norm);
+  OVN_HIP_CHECK(hipGetLastError());
+  return OVN_OK;
+}
+
+// Standalone normalisation of whole feature volumes (the fp32 transform's input): one workgroup per volume, the same affine forms
+// as every other route (ovn_corr_norm_affine)
+__global__ __launch_bounds__(512) void corr_normalize_kernel(const float* __restrict__ feats, float* __restrict__ out, int mode) {
+  __shared__ OvnNormLds<FC> nl;
+  const float* X = feats + (size_t)blockIdx.x * OVN_FEAT_ELEMS;
+  float* Y = out + (size_t)blockIdx.x * OVN_FEAT_ELEMS;
+  ovn_corr_norm_affine<FC>(X, mode, nl);
+  const double na = ovn_corr_norm_add(mode);
+  const int c4 = threadIdx.x & 31;   // channels 4 c4 .. 4 c4 + 3, rows threadIdx.x / 32 + 16 r
+  double m[4], sc[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    m[e] = nl.m[4 * c4 + e];
+    sc[e] = nl.s[4 * c4 + e];
   }
+  for (int i = threadIdx.x >> 5; i < FW; i += 16) {
+    f32x4 x = *reinterpret_cast<const f32x4*>(X + (size_t)i * FC + 4 * c4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) x[e] = ovn_corr_norm_apply(x[e], m[e], na, sc[e]);
+    *reinterpret_cast<f32x4*>(Y + (size_t)i * FC + 4 * c4) = x;
+  }
+}
+
+constexpr int NORM_SLICE = 256;   // volumes per pass of the standalone normalisation over its buffer (47 MB)
+
+}  // namespace
+
+int ovn_spectrum_forward(ovn_ctx* ctx, const float* feats, int n, float* spectra, hipStream_t stream) {
+  if (ctx->head_mode == 1)   // f16x3 arithmetic (default): normalisation (if any) fused into the transform
+    return ctx->corr_norm ? launch_dft_f16x3<true>(ctx, feats, n, spectra, stream) : launch_dft_f16x3<false>(ctx, feats, n, spectra, stream);
+  // the fp32 and bf16x3 modes take the fp32 transform
   int oh = 0, ow = 0;
   // input viewed as (n, H=360, W=128, C=1): out (n, 1, 128, 368) = spectra (n, 128, 368)
-  return ovn_conv_forward(ctx->dft, feats, n, FW, FC, spectra, &oh, &ow, stream);
+  if (ctx->corr_norm == 0) return ovn_conv_forward(ctx->dft, feats, n, FW, FC, spectra, &oh, &ow, stream);
+  const int64_t slice = n < NORM_SLICE ? n : NORM_SLICE;
+  if (ctx->norm_buf_n < slice) {
+    OVN_HIP_CHECK(hipStreamSynchronize(stream));   // earlier launches may still read the old buffer
+    if (ctx->norm_buf) (void)hipFree(ctx->norm_buf);
+    ctx->norm_buf = nullptr;
+    ctx->norm_buf_n = 0;
+    OVN_HIP_CHECK(hipMalloc((void**)&ctx->norm_buf, (size_t)slice * OVN_FEAT_ELEMS * sizeof(float)));
+    ctx->norm_buf_n = slice;
+  }
+  for (int s0 = 0; s0 < n; s0 += (int)slice) {
+    const int k = (n - s0 < slice) ? (n - s0) : (int)slice;
+    hipLaunchKernelGGL(corr_normalize_kernel, dim3(k), dim3(512), 0, stream, feats + (size_t)s0 * OVN_FEAT_ELEMS, ctx->norm_buf,
+                       ctx->corr_norm);
+    OVN_HIP_CHECK(hipGetLastError());
+    const int rc = ovn_conv_forward(ctx->dft, ctx->norm_buf, k, FW, FC, spectra + (size_t)s0 * OVN_SPEC_ELEMS, &oh, &ow, stream);
+    if (rc) return rc;
+  }
+  return OVN_OK;
 }
 
 int ovn_corr_spectral_forward(ovn_ctx* ctx, const float* spec_l, const int32_t* lidx, const float* spec_r,

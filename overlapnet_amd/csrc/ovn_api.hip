@@ -115,6 +115,7 @@ int ovn_destroy(ovn_ctx* ctx) {
   if (ctx->w2p_b3) (void)hipFree(ctx->w2p_b3);
   if (ctx->w2raw) (void)hipFree(ctx->w2raw);
   if (ctx->ws) (void)hipFree(ctx->ws);
+  if (ctx->norm_buf) (void)hipFree(ctx->norm_buf);
   if (ctx->actmax) (void)hipFree(ctx->actmax);
   if (ctx->c3_arrived) (void)hipFree(ctx->c3_arrived);
   if (ctx->aux_ready) {
@@ -351,7 +352,7 @@ int ovn_corr_head(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const
   OVN_REQUIRE(feats_l && feats_r && yaw, OVN_ERR_ARG, "ovn_corr_head: NULL buffer");
   OVN_ON_DEVICE(ctx->device);
   OvnProfScope ps(ctx, OVN_K_CORR, (hipStream_t)stream);
-  return ovn_corr_forward(feats_l, lidx, feats_r, ridx, (int)n, yaw, corr, (hipStream_t)stream);
+  return ovn_corr_forward(feats_l, lidx, feats_r, ridx, (int)n, yaw, corr, (hipStream_t)stream, ctx->corr_norm);
 }
 
 int ovn_spectrum(ovn_ctx* ctx, const float* feats_dev, int64_t n, float* spectra_dev, void* stream) {
@@ -464,7 +465,7 @@ static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lid
       const int32_t* ri = ridx ? ridx + p0 : nullptr;
       if (corr_mode == 1) {
         OvnProfScope ps(ctx, OVN_K_CORR, stream);
-        rc = ovn_corr_forward(fl, li, feats_r, ri, np, yaw + p0, corr ? corr + (size_t)p0 * OVN_FEAT_W : nullptr, stream);
+        rc = ovn_corr_forward(fl, li, feats_r, ri, np, yaw + p0, corr ? corr + (size_t)p0 * OVN_FEAT_W : nullptr, stream, ctx->corr_norm);
         if (rc) return rc;
       }
       OvnProfScope ps(ctx, OVN_K_DELTA, stream);
@@ -533,7 +534,8 @@ static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lid
     if (corr_mode == 1) {
       OvnProfScope ps(ctx, OVN_K_CORR, stream);
       rc = ovn_corr_forward(lidx ? feats_l : feats_l + (size_t)c0 * OVN_FEAT_ELEMS, lidx ? lidx + c0 : nullptr, feats_r,
-                            ridx ? ridx + c0 : nullptr, (int)cn, yaw + c0, corr ? corr + (size_t)c0 * OVN_FEAT_W : nullptr, stream);
+                            ridx ? ridx + c0 : nullptr, (int)cn, yaw + c0, corr ? corr + (size_t)c0 * OVN_FEAT_W : nullptr, stream,
+                            ctx->corr_norm);
       if (rc) return rc;
     }
     int j = 0;
@@ -733,6 +735,20 @@ int ovn_set_head_precision(ovn_ctx* ctx, int mode) {
   OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_set_head_precision: ctx is NULL");
   OVN_REQUIRE(mode >= 0 && mode <= 2, OVN_ERR_ARG, "ovn_set_head_precision: mode %d (0 = fp32 MFMA, 1 = f16x3 MFMA, 2 = bf16x3 MFMA)", mode);
   ctx->head_mode = mode;
+  return OVN_OK;
+}
+
+int ovn_set_corr_normalization(ovn_ctx* ctx, int mode) {
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_set_corr_normalization: ctx is NULL");
+  OVN_REQUIRE(mode >= 0 && mode <= 3, OVN_ERR_ARG,
+              "ovn_set_corr_normalization: mode %d (0 = none, 1 = euclidean, 2 = scaling, 3 = standardization)", mode);
+  ctx->corr_norm = mode;
+  return OVN_OK;
+}
+
+int ovn_get_corr_normalization(ovn_ctx* ctx, int* mode) {
+  OVN_REQUIRE(ctx != nullptr && mode != nullptr, OVN_ERR_ARG, "ovn_get_corr_normalization: NULL argument");
+  *mode = ctx->corr_norm;
   return OVN_OK;
 }
 

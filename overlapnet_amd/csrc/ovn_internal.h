@@ -111,6 +111,96 @@ __device__ __forceinline__ void ovn_fold_absmax_wg(float vmax, unsigned* word, f
 }
 #endif
 
+// ---- normalisation of the correlation head's inputs (NormalizedCorrelation2D normalize=..., ovn_set_corr_normalization) ----------
+// Per (volume, channel), over the 360 columns:
+//   1 euclidean        x' = x / sqrt(max(sum x^2, 1e-12))
+//   2 scaling          x' = (x - min x) / (max x - min x + 1e-6)
+//   3 standardization  y = (x - mean x) + 1e-5, x' = y / sqrt(max(sum y^2, 1e-12))
+// all of the form x' = RN32(((x - m) + a) s) with the per-channel m, s and the mode's constant a in fp64; each element is evaluated
+// in fp64 and rounded ONCE to fp32.  The statistics are fp64 sums in ONE fixed order: per channel 15 blocks of 24 consecutive
+// columns, each summed in column order, then the 15 block sums in block order.  Every route (direct head, fused DFT, standalone
+// pass) calls ovn_corr_norm_affine, so a volume's normalised values do not depend on the batch, the pair, the launch or the rank.
+constexpr int OVN_NORM_BLK = 24;                          // columns per partial sum
+constexpr int OVN_NORM_NB = OVN_FEAT_W / OVN_NORM_BLK;    // 15 partial sums per channel
+static_assert(OVN_NORM_NB * OVN_NORM_BLK == OVN_FEAT_W, "normalisation blocks must tile the 360 columns");
+
+template <int NCH>
+struct OvnNormLds {       // LDS of ovn_corr_norm_affine for NCH channels (NCH = 128: 32 KB)
+  double part[OVN_NORM_NB][NCH];
+  float mn[OVN_NORM_NB][NCH], mx[OVN_NORM_NB][NCH];
+  double m[NCH], s[NCH];  // the affine form: x' = RN32(((x - m) + a) s)
+};
+
+__host__ __device__ inline double ovn_corr_norm_add(int mode) { return mode == 3 ? 1e-5 : 0.0; }
+
+#ifdef __HIPCC__
+__device__ __forceinline__ float ovn_corr_norm_apply(float x, double m, double a, double s) {
+  return (float)((((double)x - m) + a) * s);
+}
+
+// Affine form of channels c0 .. c0 + NCH - 1 of one (360, 128) feature volume (X = volume + c0) for mode 1..3 into L.m / L.s.
+// Every thread of the (1-D) workgroup must call it; it ends with a barrier, after which L.m / L.s are valid.
+template <int NCH>
+__device__ void ovn_corr_norm_affine(const float* __restrict__ X, int mode, OvnNormLds<NCH>& L) {
+  const int tid = threadIdx.x, nt = blockDim.x;
+  for (int t = tid; t < OVN_NORM_NB * NCH; t += nt) {   // pass 1: block sums, minima, maxima
+    const int c = t % NCH, b = t / NCH;
+    const float* p = X + (size_t)(b * OVN_NORM_BLK) * OVN_FEAT_C + c;
+    double sm = 0.0;
+    float lo = INFINITY, hi = -INFINITY;
+#pragma unroll 8
+    for (int i = 0; i < OVN_NORM_BLK; ++i) {
+      const float v = p[(size_t)i * OVN_FEAT_C];
+      sm += (double)v;
+      lo = fminf(lo, v);
+      hi = fmaxf(hi, v);
+    }
+    L.part[b][c] = sm;
+    L.mn[b][c] = lo;
+    L.mx[b][c] = hi;
+  }
+  __syncthreads();
+  if (tid < NCH) {
+    double sm = 0.0;
+    float lo = INFINITY, hi = -INFINITY;
+    for (int b = 0; b < OVN_NORM_NB; ++b) {
+      sm += L.part[b][tid];
+      lo = fminf(lo, L.mn[b][tid]);
+      hi = fmaxf(hi, L.mx[b][tid]);
+    }
+    if (mode == 2) {
+      L.m[tid] = (double)lo;
+      L.s[tid] = 1.0 / (((double)hi - (double)lo) + 1e-6);
+    } else {
+      L.m[tid] = (mode == 3) ? sm / (double)OVN_FEAT_W : 0.0;
+      L.s[tid] = 0.0;
+    }
+  }
+  __syncthreads();
+  if (mode == 2) return;
+  const double a = ovn_corr_norm_add(mode);
+  for (int t = tid; t < OVN_NORM_NB * NCH; t += nt) {   // pass 2 (euclidean, standardization): block sums of y^2
+    const int c = t % NCH, b = t / NCH;
+    const float* p = X + (size_t)(b * OVN_NORM_BLK) * OVN_FEAT_C + c;
+    const double m = L.m[c];
+    double q = 0.0;
+#pragma unroll 8
+    for (int i = 0; i < OVN_NORM_BLK; ++i) {
+      const double y = ((double)p[(size_t)i * OVN_FEAT_C] - m) + a;
+      q = __builtin_fma(y, y, q);
+    }
+    L.part[b][c] = q;
+  }
+  __syncthreads();
+  if (tid < NCH) {
+    double q = 0.0;
+    for (int b = 0; b < OVN_NORM_NB; ++b) q += L.part[b][tid];
+    L.s[tid] = 1.0 / sqrt(q > 1e-12 ? q : 1e-12);
+  }
+  __syncthreads();
+}
+#endif
+
 // static scales / norms of the Delta-head weights (delta_head_f16x3.hip)
 struct OvnHeadScales {
   float sw1 = 1.f, sw2 = 1.f;     // power-of-two scales of the c_conv1 / c_conv2 kernels
@@ -176,6 +266,9 @@ struct ovn_ctx {
   // spectral correlation head: constant twiddle layers (corr_spectral.hip)
   OvnConvLayer dft;        // forward transform as a conv layer (fp32 mode) + its fp16 hi/lo fragments (dft_f16x3_kernel)
   double* tw64 = nullptr;  // [2][360] cos / sin (2 pi m / 360) in fp64: start values of the inverse transform (spectral_corr_kernel)
+  int corr_norm = 0;       // ovn_set_corr_normalization: 0 none, 1 euclidean, 2 scaling, 3 standardization
+  float* norm_buf = nullptr;   // normalised feature volumes of ovn_spectrum's fp32 transform (modes != 0 with head_mode != 1)
+  int64_t norm_buf_n = 0;      // ... volumes it holds
   // optional RCCL communicator of the sharded sweep (comm.hip)
   void* comm = nullptr;
   int comm_rank = 0, comm_world = 1;
@@ -280,8 +373,9 @@ int ovn_delta_generic_forward(const ovn_ctx* ctx, const float* feats_l, const in
                               const int32_t* ridx, int n, void* scratch, float* overlap, float* logit, hipStream_t stream);
 
 // corr_head.hip
+// norm_mode: ovn_set_corr_normalization (0 = none: the kernel of ABI 7, unchanged; else both volumes normalised on load)
 int ovn_corr_forward(const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx,
-                     int n, int32_t* yaw, float* corr, hipStream_t stream);
+                     int n, int32_t* yaw, float* corr, hipStream_t stream, int norm_mode);
 
 // corr_spectral.hip
 int ovn_spectral_prepare(ovn_ctx* ctx, hipStream_t stream);

@@ -60,6 +60,7 @@ class OvnEngine:
         self.leg_precision = "f16x3"
         self.projection_trig = "numpy_avx512"
         self.head_compaction = True
+        self.negate_diffs = False            # deltaLayer_negateDiffs of the registered weights (load_weights)
         self.conv1size = 15
         self.check_device_indices = False    # opt-in range check of pair-index tensors that already live on the device (_idx)
 
@@ -87,8 +88,13 @@ class OvnEngine:
 
     # -- weights ------------------------------------------------------------------------------------
     def load_weights(self, weights: Dict[str, np.ndarray], model_cfg: Optional[dict] = None) -> None:
-        """Register leg + head weights given by Keras layer name (reference infer.py:117-120)."""
+        """Register leg + head weights given by Keras layer name (reference infer.py:117-120).  The optional model keys
+        `correlationHead_normalize` (set_corr_normalization; a missing key leaves the mode as it is) and `deltaLayer_negateDiffs`
+        (DeltaLayer(negateDiffs=True), generateNet.py:56-57: -|l - r|) are honoured here (weights.head_options).  c_conv1 is
+        linear, so sum(-|d| w) + b = sum(|d| (-w)) + b with every product and partial sum equal up to sign: negated differences are
+        registered as the negated c_conv1 kernel, exactly, in every head arithmetic."""
         cfg = model_cfg or {}
+        norm, negate = W.head_options(cfg)
         W.check_weights(weights, self.in_c, cfg)
         self.conv1size = int(cfg.get("conv1NetworkHead_conv1size", 15))     # generateNet.py:88-89
         with self._dev():
@@ -107,11 +113,15 @@ class OvnEngine:
             names = ["c_conv1", "c_conv2", "c_conv3", "overlap_output"]
             ts = []
             for n in names:
-                ts.append(torch.from_numpy(np.ascontiguousarray(weights[n + "/kernel"], np.float32)).to(self.device))
+                k = np.ascontiguousarray(weights[n + "/kernel"], np.float32)
+                ts.append(torch.from_numpy(-k if (negate and n == "c_conv1") else k).to(self.device))
                 ts.append(torch.from_numpy(np.ascontiguousarray(weights[n + "/bias"], np.float32)).to(self.device))
             _lib.check(self.lib.ovn_set_head_weights(self._h, *[_ptr(t) for t in ts], st), "ovn_set_head_weights")
             self._head_ready = True
+            self.negate_diffs = negate
             torch.cuda.synchronize(self.device)
+        if "correlationHead_normalize" in cfg:
+            self.set_corr_normalization(norm)
 
     # -- leg ----------------------------------------------------------------------------------------
     def leg(self, images: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -476,6 +486,22 @@ class OvnEngine:
         _lib.check(self.lib.ovn_set_head_precision(self._h, table[mode]), "ovn_set_head_precision")
         self.head_precision = mode
 
+    def set_corr_normalization(self, mode: str) -> None:
+        """Normalisation of the correlation head's inputs, NormalizedCorrelation2D(normalize=mode): 'none' (default, what
+        generateCorrelationHead builds), 'euclidean', 'scaling' or 'standardization' -- per (volume, channel) over the 360 columns,
+        statistics in fp64, each element rounded once to fp32 (include/ovn_hip.h: ovn_set_corr_normalization).  Spectra from
+        `spectrum` are valid for the mode they were built under; the Delta head is not affected."""
+        if not isinstance(mode, str) or mode not in W.CORR_NORMALIZE_MODES:
+            raise ValueError("correlation normalisation must be one of %s" % sorted(W.CORR_NORMALIZE_MODES))
+        _lib.check(self.lib.ovn_set_corr_normalization(self._h, W.CORR_NORMALIZE_MODES[mode]), "ovn_set_corr_normalization")
+
+    @property
+    def corr_normalization(self) -> str:
+        """The normalisation mode the library context holds (ovn_get_corr_normalization)."""
+        m = C.c_int(-1)
+        _lib.check(self.lib.ovn_get_corr_normalization(self._h, C.byref(m)), "ovn_get_corr_normalization")
+        return {v: k for k, v in W.CORR_NORMALIZE_MODES.items()}[m.value]
+
     def set_head_compaction(self, on: bool) -> None:
         """1-vs-N sweeps drop the query's dead feature channels (zero in all 360 columns) from the Delta head's contraction (default on;
         exact -- include/ovn_hip.h: ovn_set_head_compaction).  Off: every pair walks all 128 channels, as indexed pairs always do."""
@@ -568,6 +594,7 @@ class QueryAhead:
         self.side.set_leg_precision(engine.leg_precision)
         self.side.set_head_precision(engine.head_precision)       # the spectrum kernel follows the head arithmetic
         self.side.set_projection_trig(engine.projection_trig)     # (the look-ahead of Infer projects raw scans in this context)
+        self.side.set_corr_normalization(engine.corr_normalization)   # the query spectrum is that of the normalised volume
         dev = engine.device
         with torch.cuda.device(dev):
             self.stream = torch.cuda.Stream(device=dev)
@@ -607,6 +634,8 @@ class QueryAhead:
             self.side.set_head_precision(self.main.head_precision)
         if self.side.projection_trig != self.main.projection_trig:
             self.side.set_projection_trig(self.main.projection_trig)
+        if self.side.corr_normalization != self.main.corr_normalization:
+            self.side.set_corr_normalization(self.main.corr_normalization)
         if wait_current:
             self.stream.wait_stream(torch.cuda.current_stream(self.main.device))   # the image belongs to the caller's stream
         if self._released[slot] is not None:

@@ -12,6 +12,10 @@ types and error behaviour; the Keras/TensorFlow models behind it are replaced by
     running every contraction in fp32, profiles/r2_parity_1024.json).  `config['precision'] = 'f32'` (optional key, absent
     from the reference's network.yml) selects bit-for-bit fp32 FMA chains on the fp32 matrix cores at ~1/3 of the speed, and
     'bf16x3' the fp32 leg with the exact 3-term bf16 split in the Delta head (fp32-wide operands, include/ovn_hip.h);
+  * `config['model']['correlationHead_normalize']` ('none' default | 'euclidean' | 'scaling' | 'standardization': the modes of
+    NormalizedCorrelation2D, compared by value -- the reference's `is` test would turn a YAML string into 'none') and
+    `config['model']['deltaLayer_negateDiffs']` (bool, default False: DeltaLayer(negateDiffs=True)) build the heads a model was
+    trained with; both keys are optional extensions, any other value raises ValueError before a GPU is touched;
   * `pretrained_weightsfilename` may name a native `.npz` (keys `<layer>/kernel|bias`) besides the
     Keras HDF5 file (read by the built-in `hdf5_lite` parser);
   * `infer_best_match` (extension): `infer_multiple` + demo3's decision taken on the GPU;
@@ -260,10 +264,15 @@ class Infer():
     if self.network_output_size != FEAT_W:
       raise OvnError("leg_output_width=%s: the HIP heads are built for 360" % self.network_output_size)
 
+    # optional head keys (extensions, absent from the reference's network.yml): checked here, before any GPU work, so that a config
+    # the heads cannot honour fails loudly instead of being ignored (weights.head_options)
+    corr_normalize, negate_diffs = W.head_options(model_cfg)
     self._model_cfg = {
       'strides_layer1': model_cfg.get('strides_layer1', (2, 2)),
       'additional_unsymmetric_layer3a': model_cfg.get('additional_unsymmetric_layer3a', False),
       'conv1NetworkHead_conv1size': model_cfg.get('conv1NetworkHead_conv1size', 15),
+      'correlationHead_normalize': corr_normalize,
+      'deltaLayer_negateDiffs': negate_diffs,
     }
     self.engine = OvnEngine(self.inputShape[0], self.inputShape[1], self.inputShape[2], device=device)
     self.leg = self.engine    # reference: keras.Model (infer.py:101)

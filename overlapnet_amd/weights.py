@@ -138,6 +138,27 @@ def synthetic_weights(in_channels: int, model_cfg: dict | None = None, seed: int
     return out
 
 
+# NormalizedCorrelation2D(normalize=...) (NormalizedCorrelation2D.py:23-73) -> ovn_set_corr_normalization's mode
+CORR_NORMALIZE_MODES = {"none": 0, "euclidean": 1, "scaling": 2, "standardization": 3}
+
+
+def head_options(model_cfg: dict | None = None) -> Tuple[str, bool]:
+    """The two optional head keys of config['model'] (absent from the reference's network.yml; a missing key keeps the behaviour of
+    generateNet.py:56-57,343): `correlationHead_normalize` ('none' | 'euclidean' | 'scaling' | 'standardization', default 'none') and
+    `deltaLayer_negateDiffs` (bool, default False).  Raises ValueError on anything else.  The mode string is compared by VALUE: the
+    reference's `self.use_norm is 'euclidean'` is an identity test that only holds for interned literals (a value read from YAML
+    silently gives 'none'); the intended meaning is the string's value."""
+    cfg = model_cfg or {}
+    norm = cfg.get("correlationHead_normalize", "none")
+    if not isinstance(norm, str) or norm not in CORR_NORMALIZE_MODES:
+        raise ValueError("config['model']['correlationHead_normalize'] must be one of %s, got %r"
+                         % (sorted(CORR_NORMALIZE_MODES), norm))
+    neg = cfg.get("deltaLayer_negateDiffs", False)
+    if not isinstance(neg, (bool, np.bool_)):
+        raise ValueError("config['model']['deltaLayer_negateDiffs'] must be a bool, got %r" % (neg,))
+    return norm, bool(neg)
+
+
 def check_weights(weights: Dict[str, np.ndarray], in_channels: int, model_cfg: dict | None = None) -> None:
     exp = expected_shapes(in_channels, model_cfg)
     for k, shp in exp.items():

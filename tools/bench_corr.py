@@ -2,7 +2,8 @@
 """Correlation (yaw) head alone: direct form vs spectral form, 1-vs-N sweep over cached candidates.
 Reports pairs/s and the algorithmic HBM rate (184,328 B per pair; the spectral form
 actually streams 188,416 B of spectrum per pair) against the 8 TB/s HBM3E peak.
-    python tools/bench_corr.py [--n 16384] [--iters 20]
+    python tools/bench_corr.py [--n 16384] [--iters 20] [--normalize none|euclidean|scaling|standardization] [--precision f16x3|f32|bf16x3]
+--normalize: the correlation head's input normalisation (OvnEngine.set_corr_normalization); spectra are built under it.
 """
 import argparse
 import json
@@ -18,9 +19,13 @@ from overlapnet_amd.engine import OvnEngine  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--n", type=int, default=16384)
 ap.add_argument("--iters", type=int, default=20)
+ap.add_argument("--normalize", default="none", choices=["none", "euclidean", "scaling", "standardization"])
+ap.add_argument("--precision", default="f16x3", choices=["f16x3", "f32", "bf16x3"])
 a = ap.parse_args()
 torch.cuda.set_device(0)
 eng = OvnEngine(64, 900, 4)
+eng.set_corr_normalization(a.normalize)
+eng.set_head_precision(a.precision)       # the spectrum's transform follows the head arithmetic
 g = torch.Generator(device="cuda").manual_seed(1234)
 feats = torch.relu(torch.randn((a.n, 360, 128), device="cuda", generator=g) + 0.1).contiguous()
 query = feats[7:8].contiguous()
@@ -51,7 +56,7 @@ yd = eng.corr_head(feats, query)["yaw"]
 ys = eng.corr_head_spectral(spec, qspec)["yaw"]
 mism = torch.nonzero(yd != ys).flatten().cpu().numpy()
 out["yaw_mismatches_direct_vs_spectral"] = int(mism.size)
-if mism.size:  # adjudicate with the fp64 oracle: are these genuine near-ties?
+if mism.size and a.normalize == "none":  # adjudicate with the fp64 oracle: are these genuine near-ties?
     from oracle import overlapnet_oracle as O
     idx = mism[:16]
     fl = feats[idx].cpu().numpy().reshape(-1, 1, 360, 128).astype(np.float64)
@@ -63,4 +68,6 @@ if mism.size:  # adjudicate with the fp64 oracle: are these genuine near-ties?
     out["mismatch_direct_matches_oracle"] = int(np.sum(yd[idx].cpu().numpy() == oy))
     out["mismatch_spectral_matches_oracle"] = int(np.sum(ys[idx].cpu().numpy() == oy))
 out["n"] = a.n
+out["normalize"] = a.normalize
+out["precision"] = a.precision
 print(json.dumps(out))
