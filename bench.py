@@ -12,27 +12,34 @@ when they were the current frame, infer.py:184-185).
 N = 1 (default): P = 1024 candidates, C = 4 = BASELINE.json configs[1] ("batched 1-vs-1024 pairs, 64x900 depth+normals").
 `value` is that warm sweep for a STREAM of queries: every step enqueues one query leg and one 1024-pair head sweep, the leg (and
 spectrum) of query k + 1 on a second context / stream beside the head kernels of query k (overlapnet_amd.engine.QueryAhead;
-`--serial-query` puts the leg in front of its own heads on one stream instead).  The same run then measures, each in its own
-timed region and reported as sub-records of the ONE JSON line: `warm_serial` (that one-stream order), `fp32_mode` (every contraction on the fp32 matrix cores), `cold` (candidate legs inside the step),
-`fullstack` (raw clouds -> projection -> legs -> heads), `corr_head` (the HBM-bound correlation head alone at N = 1024 and
-16384), `infer_api` (BASELINE configs[2]: the 1101-frame loop-closure sweep through `Infer.infer_multiple`), `latency` (one query
-against N = 1 [configs[0]], 16, 100, 256 candidates), and the accuracy of the timed configuration over ALL pairs against the
-committed fp64-oracle outputs.
+`--serial-query` puts the leg in front of its own heads on one stream instead).
+
+A plain run does what that headline figure needs and no more: it sets up, warms up, times the K steps, writes `--dump-outputs` and
+prints the line, whose `kernels` and `roofline` come from the HIP events of the timed steps themselves.  `--full` adds everything
+else, after the timed steps: each in its own timed region and reported as sub-records of the ONE JSON line, `warm_serial` (that
+one-stream order), `dense_walk` (no dead-channel compaction), `trained_like` (the second weight set), `fp32_mode` (every
+contraction on the fp32 matrix cores), `cold` (candidate legs inside the step), `fullstack` (raw clouds -> projection -> legs ->
+heads), `corr_head` (the HBM-bound correlation head alone at N = 1024 and 16384), `infer_api` (BASELINE configs[2]: the 1101-frame
+loop-closure sweep through `Infer.infer_multiple`), `latency` (one query against N = 1 [configs[0]], 16, 100, 256 candidates); the
+K walk of every query of the stream; the accuracy of the timed configuration over ALL pairs against the committed fp64-oracle
+outputs; the dominant kernel's HBM traffic (two rocprofv3 PMC passes over a plain run of this program); and the CPU baselines.
+`--no-extras`, `--no-walk-stats`, `--no-cpu-baseline` and `--traffic` narrow a `--full` run.
 
 N > 1: BASELINE.json configs[3], STRONG scaling: one 1-vs-100000 synthetic candidate pool (`--pool-total`) sharded in
 contiguous blocks over the ranks (overlapnet_amd.distributed.shard_bounds), feature volumes generated on the device
 (SURVEY.md 8d), one RCCL gather of (overlap, yaw) to rank 0 per step; value = pool_total * steps / elapsed.
-`--pool-total 0` gives the weak-scaling variant (P candidates per rank).  Prints ONE JSON line on rank 0.
+`--pool-total 0` gives the weak-scaling variant (P candidates per rank).  Prints ONE JSON line on rank 0.  With `--full` every rank
+re-evaluates windows of its block without the Delta cache rows and rank 0 checks a few pairs against a live fp64 oracle.
 
 `--steps K` is the number of timed steps and `ms_per_step` in the line is the time of one.  `--dump-outputs DIR` writes what the last
 timed step returned (`overlap.npy`, `yaw.npy`: one entry per candidate of the sweep, in pool order); the inputs are seeded, so two
 runs with the same arguments -- of two builds, say -- can be compared output for output.
 
-`--rehearsal` (or OVN_BENCH_REHEARSAL=1) with N > 1: the SAME command path -- launcher, one rank per "GPU", shard bounds, per-step
-gather to rank 0, every rank's self-check, rank-0-only JSON -- with all N ranks on ONE device and gloo / host tensors in the
-collectives (RCCL refuses two ranks on one device); rank 0 then evaluates the whole pool in one process and requires the gathered
-(overlap, yaw) to be `torch.equal` to it.  The line is marked `"rehearsal": true` and carries no pairs/s (`value` is null): N
-processes time-sharing one GPU say nothing about scaling.
+`--rehearsal` (or OVN_BENCH_REHEARSAL=1) with N > 1, a check run that always makes the checks of `--full`: the SAME command path --
+launcher, one rank per "GPU", shard bounds, per-step gather to rank 0, every rank's self-check, rank-0-only JSON -- with all N ranks
+on ONE device and gloo / host tensors in the collectives (RCCL refuses two ranks on one device); rank 0 then evaluates the whole
+pool in one process and requires the gathered (overlap, yaw) to be `torch.equal` to it.  The line is marked `"rehearsal": true`
+and carries no pairs/s (`value` is null): N processes time-sharing one GPU say nothing about scaling.
 """
 import argparse
 import json
@@ -121,7 +128,7 @@ def _measured_traffic(kernel_prefix: str, extra_args, timeout_s: float = 150.0):
         for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
             out_dir = os.path.join(tmp, ctr)
             cmd = [exe, "--kernel-trace", "--pmc", ctr, "-d", out_dir, "-o", "bench", "--", sys.executable, os.path.abspath(__file__),
-                   "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--no-walk-stats", "--traffic", "none"] + list(extra_args)
+                   "--steps", "3", "--warmup", "1"] + list(extra_args)     # a plain run: its last launches are the timed steps'
             env = dict(os.environ, TMPDIR="/tmp")
             try:
                 p = subprocess.Popen(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True)
@@ -160,7 +167,7 @@ def rocprof_traffic(kernel_prefix: str, mode: str, extra_args):
     """-> (bytes per launch or None, where the figure comes from).  mode: 'measure' (PMC passes now, committed profile if they
     fail), 'committed', 'none'."""
     if mode == "none":
-        return None, "not collected (--traffic none)"
+        return None, "not collected (--traffic none, the default without --full)"
     if mode == "measure":
         b, info = _measured_traffic(kernel_prefix, extra_args)
         if b is not None:
@@ -429,22 +436,25 @@ def main():
     ap.add_argument("--no-delta-cache", action="store_true", help="warm sweep without the candidates' Delta cache rows (round-2 behaviour)")
     ap.add_argument("--no-compaction", action="store_true",
                     help="walk all 128 feature channels in the Delta contraction even where the query's are dead (ovn_set_head_compaction 0)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, measure and check everything else in the same run: the sub-records, the K walk "
+                         "of each query, accuracy against the fp64 oracle, the HBM traffic passes and the CPU baselines (module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--serial-query", action="store_true", help="warm mode: the query leg on the heads' stream, in front of them (no QueryAhead)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the fp32_mode / cold / fullstack / corr_head sub-records")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the sub-records (warm_serial, fp32_mode, cold, fullstack, ...)")
     ap.add_argument("--no-walk-stats", action="store_true",
-                    help="skip the untimed 32-pair sweeps that read the K walk of each query of the stream back (profiling runs: every "
-                         "launch of the trace is then a full sweep)")
+                    help="--full: skip the untimed 32-pair sweeps that read the K walk of each query of the stream back (profiling runs: "
+                         "every launch of the trace is then a full sweep)")
     ap.add_argument("--rehearsal", action="store_true", default=os.environ.get("OVN_BENCH_REHEARSAL", "") == "1",
                     help="N > 1 ranks on ONE device, gloo / host collectives: rehearses the driver's multi-GPU command path (no pairs/s claim)")
-    ap.add_argument("--traffic", default="measure", choices=["measure", "committed", "none"],
-                    help="roofline.traffic: two rocprofv3 PMC passes over a short run of this program (default, N = 1 warm mode; falls back "
-                         "to the newest committed profile), the committed profile, or nothing")
+    ap.add_argument("--traffic", default=None, choices=["measure", "committed", "none"],
+                    help="roofline.traffic: two rocprofv3 PMC passes over a short run of this program (default with --full, N = 1 warm "
+                         "mode; falls back to the newest committed profile), the committed profile, or nothing (default without --full)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last one returned -- (overlap, yaw) of every pair of the sweep, in pool "
                          "order -- as DIR/overlap.npy (float32) and DIR/yaw.npy (float64); rank 0 only")
-    ap.add_argument("--accuracy-pairs", type=int, default=12, help="pairs checked against a LIVE fp64 oracle when no committed "
-                                                                  "oracle outputs exist for the configuration (untimed)")
+    ap.add_argument("--accuracy-pairs", type=int, default=12, help="--full: pairs checked against a LIVE fp64 oracle when no "
+                                                                  "committed oracle outputs exist for the configuration (untimed)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -459,6 +469,8 @@ def main():
         raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
     visible = torch.cuda.device_count()
     rehearsal = bool(args.rehearsal and world > 1)
+    # the untimed checks of the results (query 0 again, shard windows, oracle accuracy): --full, and a rehearsal, which is a check run
+    checks = args.full or rehearsal
     if rehearsal:
         if visible < 1:
             refuse("bench.py --rehearsal: needs one GPU, none visible (rank %d)" % rank, rank, world)
@@ -532,7 +544,7 @@ def main():
             n = min(4096, P - s)
             cands[s:s + n] = torch.relu(torch.randn((n, 360, 128), device=dev, generator=g) + 0.1)
     else:
-        keep_imgs = (args.mode == "cold") or (world == 1 and not args.no_extras)
+        keep_imgs = (args.mode == "cold") or (world == 1 and args.full and not args.no_extras)
         if keep_imgs:   # P candidate images + one slot for the query image at the end (the cold step's leg input, resident in HBM)
             all_imgs = torch.empty((P + 1, 64, 900, C), dtype=torch.float32, device=dev)
             pool_imgs = all_imgs[:P]
@@ -632,7 +644,7 @@ def main():
     # (BEFORE the timed region -- the launches after it stay full-size sweeps, which the traffic passes read --
     #  read back from the library after an untimed sweep per query: ovn_head_walk_stats -- the slices every wave of the contraction kernel walks)
     live_counts, walks = [], []
-    if args.mode == "warm" and args.head_precision == "f16x3" and spectral and P > 0 and not args.no_walk_stats:
+    if args.full and args.mode == "warm" and args.head_precision == "f16x3" and spectral and P > 0 and not args.no_walk_stats:
         n_w = min(P, 32)
         for qi in query_ring:
             fq = eng.leg(qi)
@@ -640,15 +652,20 @@ def main():
             st = eng.head_walk_stats()
             live_counts.append(st["live_channels"])
             walks.append(st["k_walk_frac"])
-    walk_frac = (sum(walks) / len(walks)) if walks else 1.0
+    if walks:
+        walk_frac = sum(walks) / len(walks)
+    elif args.head_precision != "f16x3" or args.no_compaction:
+        walk_frac = 1.0                 # every pair walks all 128 channels
+    else:
+        walk_frac = None                # compaction on, the walk not read back
     elapsed, prof, res = timed(step, args.warmup, args.steps, eng, use_dist, dev, side_eng=qa.side if qa is not None else None)
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, {"overlap": res[0], "yaw": res[1]})
-    if args.mode == "warm":
+    streamed_same = None
+    if checks and args.mode == "warm":
         # query 0 in a step of its own (untimed): what the accuracy block below and the same-results checks compare.  Serial order:
         # the same kernels and bits as the streamed order (tests/test_gpu_parity.py::test_query_ahead_*; `warm_serial.same_results`)
         res = step_warm_serial(query_img)
-        streamed_same = None
         if qa is not None:      # ... and once more through the streamed path: must be the same bits
             qa.take()           # (the query in flight since the last timed step)
             qa.submit(query_img)
@@ -672,7 +689,7 @@ def main():
     # ---- sharded pool: EVERY rank re-evaluates three windows of its block WITHOUT the Delta cache rows (same bits required; windows
     #      beyond the first 1024-pair chunk where the block is long enough) and rank 0 collects the verdicts ----
     shard_check = None
-    if strong and args.mode == "warm" and spectral:
+    if checks and strong and args.mode == "warm" and spectral:
         own = eng.heads(cands, query_fv, spec_l=cand_spec, spec_r=query_spec, dcache_l=cand_dc)   # query 0 (left by the untimed step)
         wins = sorted({max(0, min(P - 64, s0)) for s0 in (0, 1024 + 37, P - 64)}) if P > 0 else []
         same = True
@@ -707,7 +724,10 @@ def main():
         launch_pairs = P * args.steps / d_n
     kname, peak, kprefix, flop_per_pair, rl_note = HEAD_KERNEL[args.head_precision]
     achieved = flop_per_pair * launch_pairs / (avg_ms * 1e-3) / 1e12 if d_n else 0.0
-    mfma_per_alg = (3.0 * walk_frac) if args.head_precision == "f16x3" else 1.0
+    if args.head_precision != "f16x3":
+        mfma_per_alg = 1.0
+    else:
+        mfma_per_alg = (3.0 * walk_frac) if walk_frac is not None else None
     if strong:
         workload = ("1-vs-%d synthetic candidate pool sharded over %d rank(s) in contiguous blocks (BASELINE configs[3]; warm: 1 query "
                     "leg per rank + %d head pairs per step in total), feature volumes generated on the device, 64x900x%d query"
@@ -734,13 +754,14 @@ def main():
                    "query_leg": ("step k + 1's query leg + spectrum on a second context / stream beside step k's head kernels "
                                  "(engine.QueryAhead; one leg and one head sweep enqueued per step)" if qa is not None
                                  else "on the heads' stream, in front of them"),
-                   "collective": "RCCL gather of (overlap,yaw) to rank 0 per step" if use_dist else "none"},
+                   "collective": "RCCL gather of (overlap,yaw) to rank 0 per step" if use_dist else "none",
+                   "full": args.full},
         "roofline": {"bound": "mfma", "kernel": kname, "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
                      "frac": achieved / peak, "traffic": None,
                      "flop_per_launch": flop_per_pair * launch_pairs, "pairs_per_launch": launch_pairs,
                      "avg_launch_ms": avg_ms,
                      "mfma_flops_per_algorithmic_flop": mfma_per_alg,
-                     "frac_executed": mfma_per_alg * achieved / peak,
+                     "frac_executed": mfma_per_alg * achieved / peak if mfma_per_alg is not None else None,
                      "query_live_channels": (sum(live_counts) / len(live_counts)) if live_counts else None,
                      "k_walk_frac": walk_frac,
                      "k_walk_by_query": {"live_channels": live_counts, "k_walk_frac": walks,
@@ -788,14 +809,14 @@ def main():
         out["value"] = None
         del pool_all, full
 
-    # ---- accuracy part of the metric ("overlap MAE vs ref"), untimed ----
+    # ---- accuracy part of the metric ("overlap MAE vs ref"), untimed; every branch is a check ----
     ov = res[0].float().cpu().numpy()
     yw = res[1].cpu().numpy()
-    golden_ok = (not strong and args.mode != "fullstack" and P == 1024 and C == 4 and world == 1
+    golden_ok = (checks and not strong and args.mode != "fullstack" and P == 1024 and C == 4 and world == 1
                  and os.path.isfile(os.path.join(ROOT, "tests", "golden", "parity_sweep_glorot.npz")))
     if golden_ok:
         out.update(golden_accuracy(ov[:P], yw[:P]))
-    elif strong and shard_check is not None:
+    elif checks and strong and shard_check is not None:
         # sharded pool (no committed oracle outputs): the verdicts of EVERY rank's self-check (above), and a live fp64 oracle on a few
         # pairs of rank 0's block
         fvq = query_fv                          # query 0, left there by the untimed step above
@@ -815,7 +836,7 @@ def main():
             out["yaw_exact_rate"] = float(np.mean(yw[s0:s0 + k] == o_yaw))
             out["accuracy_pairs"] = int(k)
             out["accuracy_scope"] = "feature volumes -> heads vs fp64 oracle, pairs %d.. of rank 0's block" % s0
-    elif args.accuracy_pairs > 0 and not strong:
+    elif checks and args.accuracy_pairs > 0 and not strong:
         from oracle import overlapnet_oracle as O
         k = min(args.accuracy_pairs, P)
         if raw is not None:
@@ -840,8 +861,8 @@ def main():
         out["yaw_exact_rate"] = float(np.mean(yw[:k] == o_yaw))
         out["accuracy_pairs"] = int(k)
 
-    # ---- sub-records: every other number DESIGN.md quotes, measured in this same run (N = 1 only) ----
-    if world == 1 and not strong and not args.no_extras and args.mode == "warm":
+    # ---- sub-records: every other number DESIGN.md quotes, measured in this same run (--full, N = 1 only) ----
+    if world == 1 and not strong and args.full and not args.no_extras and args.mode == "warm":
         sub_steps = max(args.steps, 20)
         # (0) the same warm step with the query leg IN FRONT of its heads on one stream (no QueryAhead)
         if qa is not None:
@@ -1000,9 +1021,10 @@ def main():
                        "query of a stream whose next leg runs beside the current heads (QueryAhead), decision still read every query")
         out["latency"] = lat
     # ---- HBM traffic of the dominant kernel: measured now (two rocprofv3 PMC passes over a short run of this program) when this is the
-    #      default single-GPU warm configuration, else the newest committed profile; never silently ----
-    traffic_mode = args.traffic if (world == 1 and not strong and args.mode == "warm" and not args.no_extras) else \
-        ("none" if args.traffic == "none" else "committed")
+    #      default single-GPU warm configuration, else the newest committed profile; never silently; a plain run collects none ----
+    traffic = args.traffic or ("measure" if args.full else "none")
+    traffic_mode = traffic if (world == 1 and not strong and args.mode == "warm" and not args.no_extras) else \
+        ("none" if traffic == "none" else "committed")
     pass_args = ["--pool", str(P), "--channels", str(C), "--head-precision", args.head_precision, "--corr", args.corr] + \
         (["--no-compaction"] if args.no_compaction else [])
     t_bytes, t_src = rocprof_traffic(kprefix, traffic_mode, pass_args)
@@ -1058,7 +1080,7 @@ def main():
         if "overlap_maxerr_vs_oracle" in out["trained_like"]:
             rl["overlap_maxerr_vs_oracle_trained_like"] = out["trained_like"]["overlap_maxerr_vs_oracle"]
     rl["traffic_from"] = (t_src.get("source") or "none") if isinstance(t_src, dict) else str(t_src)
-    if args.head_precision == "f16x3":
+    if mfma_per_alg is not None and args.head_precision == "f16x3":
         # executed MFMA rate against what a bare MFMA loop sustains on real operands (a committed measurement, not this run's)
         rl["executed_frac_of_sustained_mfma_rate"] = mfma_per_alg * rl0["achieved"] / SUSTAINED_16BIT_MFMA_TFLOPS
     rl["avg_launch_ms"] = rl0["avg_launch_ms"]
@@ -1092,7 +1114,7 @@ def main():
     if "trained_like" in out:
         out["value_trained_like"] = out["trained_like"]["compacted"]["value"]
         out["value_trained_like_dense_walk"] = out["trained_like"]["dense_walk"]["value"]
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(C, P)
         if not args.no_extras:
             # the preprocessing half of BASELINE configs[4] on the same host, next to `fullstack`'s projection

@@ -4,7 +4,7 @@
 The step starts from RAW clouds (tools/synthetic.fullstack_cloud: the shipped scans rotated about z): projection + normals +
 channel stacking + leg + both heads.  The oracle starts from the same clouds with its own restatement of every stage
 (range_projection with the restated NumPy float32 angles, gen_normal_map, fp64 leg and heads).  Query = cloud 1024 (the
-candidate pool of the benchmark is clouds 0..1023).  bench.py compares its fullstack results with this file in the default run;
+candidate pool of the benchmark is clouds 0..1023).  bench.py --full compares its fullstack results with this file;
 tests/test_parity_sweep.py re-runs the oracle on a sample and requires equality with the file.
 
     python tests/golden/make_fullstack_golden.py [--pairs 64]

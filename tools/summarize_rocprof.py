@@ -41,10 +41,10 @@ def main():
     for name, calls, tot, avg, pct in rows:
         out["kernels"].append({"name": short(name), "calls": calls, "total_us": tot, "avg_us": avg, "pct": pct})
         lines.append("| `%s` | %d | %.1f | %.2f | %.2f |" % (short(name), calls, tot, avg, pct))
-    # the timed launches only: bench.py ran 2 warm-up + 5 timed steps (+ 2 untimed sweeps of query 0 afterwards, without the next
-    # query's leg on the side stream), so dispatches 2 .. 6 of the head kernels are the ones its own HIP-event timer brackets (the
-    # first launches run on cold caches and pull the plain average up)
-    lines += ["", "| kernel | avg us over the 5 timed dispatches (2 warm-up launches before, 2 untimed after) | bench.py event timer in this profiled run |", "|---|---|---|"]
+    # the timed launches only: bench.py ran 2 warm-up + 5 timed steps (a plain run: no untimed sweeps after them), so dispatches
+    # 2 .. 6 of the head kernels are the ones its own HIP-event timer brackets (the first launches run on cold caches and pull the
+    # plain average up)
+    lines += ["", "| kernel | avg us over the 5 timed dispatches (2 warm-up launches before) | bench.py event timer in this profiled run |", "|---|---|---|"]
     ev = None
     logp = os.path.join(src, "stats.log")
     if os.path.isfile(logp):
