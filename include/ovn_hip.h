@@ -39,7 +39,7 @@ typedef struct ovn_ctx ovn_ctx;
 #define OVN_ERR_STATE 3    /* call order (weights missing ...)  */
 
 /* ABI version of this header; bumped on any signature change. */
-#define OVN_ABI_VERSION 8
+#define OVN_ABI_VERSION 9
 int ovn_abi_version(void);
 
 /* Last error message of the calling thread ("" if none). */
@@ -70,13 +70,24 @@ int ovn_set_head_weights(ovn_ctx* ctx, const float* c1_kernel_dev, const float* 
 /* Head geometry: `conv1NetworkHead_conv1size` of the reference's network.yml (generateNet.py:88-99: the 1 x s / s x 1 kernels and
  * strides of c_conv1 / c_conv2; default 15, which the shipped configuration uses).  Call BEFORE ovn_set_head_weights when the
  * model was built with another value: c_conv1 is then (1, s, 128, 64), c_conv2 (s, 1, 64, 128) and the Dense kernel has
- * (360 // s - 2)^2 * 256 inputs.  The MFMA-tiled Delta kernels (both arithmetic modes) serve s = 15; any other s runs a general fp32
+ * (feat_w // s - 2)^2 * 256 inputs (feat_w = 360 before ovn_finalize).  The MFMA-tiled Delta kernels (both arithmetic modes) serve s = 15; any other s runs a general fp32
  * path (DeltaLayer + c_conv1 as plain FMAs without materialising the difference tensor, c_conv2 / c_conv3 through the generic fp32
  * convolution) -- correct to the same tolerance, an order of magnitude slower, no Delta cache. */
 int ovn_set_head_geometry(ovn_ctx* ctx, int conv1size);
 
-/* Validate the registered leg chain: output must be 1 x feat_w x 128 (1 x 360 x 128 in the reference).
- * Writes the leg output width to *feat_w. */
+/* Validate the registered leg chain: output must be 1 x feat_w x 128 with OVN_FEAT_W_MIN <= feat_w <= OVN_FEAT_W_MAX
+ * (1 x 360 x 128 in the reference's shipped configuration; the reference derives the width from `inputShape`, `strides_layer1`
+ * and `additional_unsymmetric_layer3a`, generateNet.py:143-146).  Writes the leg output width to *feat_w.
+ *
+ * Width rule.  Every feature volume a context reads or writes is feat_w x 128 floats, corr vectors are feat_w floats, and the Delta
+ * head has G = feat_w // conv1size column groups (at least 3) and a Dense kernel of (G - 2)^2 * 256 inputs.  At feat_w = 360 every
+ * route of this header is available.  At any other width the heads run exact fp32 on the fp32 MFMA in every head precision mode
+ * (ovn_set_head_precision is accepted and has no effect there: the split-operand kernels are tiled to 24 groups of 15 and to the
+ * 360-point DFT), and the 360-only entry points ovn_spectrum, ovn_corr_head_spectral, ovn_heads_spectral and ovn_delta_cache
+ * return OVN_ERR_ARG.  If ovn_set_head_weights ran first, finalize also requires feat_w // conv1size to match the Dense kernel
+ * registered there. */
+#define OVN_FEAT_W_MIN 45
+#define OVN_FEAT_W_MAX 512
 int ovn_finalize(ovn_ctx* ctx, int* feat_w);
 
 /* Leg: images_dev (n, in_h, in_w, in_c) -> features_dev (n, feat_w, 128).

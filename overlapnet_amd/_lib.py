@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OVN_LIB") or os.path.join(_HERE, "libovn_hip.so")
 CSRC_DIR = os.path.join(_HERE, "csrc")
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 _f32p = C.POINTER(C.c_float)
 _i32p = C.POINTER(C.c_int32)

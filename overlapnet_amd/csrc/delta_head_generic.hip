@@ -1,4 +1,5 @@
-// DeltaLayer + c_conv1 for ANY conv1NetworkHead_conv1size s (generateNet.py:15-61, :88-99), fp32, for gfx950.
+// DeltaLayer + c_conv1 for ANY conv1NetworkHead_conv1size s (generateNet.py:15-61, :88-99), fp32, for gfx950, at the context's feature
+// width W (360 in the shipped configuration; the 360 below stands for W).
 //
 // The shipped network.yml leaves the key at its default (15), and the two fast Delta paths (delta_head_f16x3.hip, delta_head.hip)
 // are tiled around it: 24 column groups of 15.  The reference builds the head for any s (Conv2D(64, (1, s), strides (1, s)) on the
@@ -16,7 +17,6 @@
 
 namespace {
 
-constexpr int FW = OVN_FEAT_W;    // 360
 constexpr int FC = OVN_FEAT_C;    // 128
 constexpr int O1 = OVN_C1_OUT;    // 64
 constexpr int IB = 64;            // rows i per workgroup
@@ -25,7 +25,7 @@ constexpr int RPT = 16;           // rows per thread
 __global__ __launch_bounds__(256) void delta_c1_generic_kernel(const float* __restrict__ feats_l, const int32_t* __restrict__ lidx,
                                                                const float* __restrict__ feats_r, const int32_t* __restrict__ ridx,
                                                                const float* __restrict__ w1, const float* __restrict__ b1, int s, int G,
-                                                               float* __restrict__ out1) {
+                                                               int FW, float* __restrict__ out1) {
   extern __shared__ __attribute__((aligned(16))) float gsm[];
   float* ll = gsm;                  // [IB][128]
   float* rl = gsm + IB * FC;        // [s][128]
@@ -38,8 +38,8 @@ __global__ __launch_bounds__(256) void delta_c1_generic_kernel(const float* __re
   const int tid = threadIdx.x;
   const int o = tid & (O1 - 1);
   const int ig = tid >> 6;
-  const float* L = feats_l + (long long)(lidx ? lidx[pair] : pair) * OVN_FEAT_ELEMS;
-  const float* R = feats_r + (long long)(ridx ? ridx[pair] : 0) * OVN_FEAT_ELEMS;
+  const float* L = feats_l + (long long)(lidx ? lidx[pair] : pair) * FW * FC;
+  const float* R = feats_r + (long long)(ridx ? ridx[pair] : 0) * FW * FC;
   const int i0 = iblk * IB;
   for (int e = tid; e < IB * FC / 4; e += 256) {
     const int row = e / (FC / 4);
@@ -108,16 +108,18 @@ __global__ __launch_bounds__(256) void dense_sigmoid_any_kernel(const float* __r
 
 }  // namespace
 
-// Bytes of scratch per pair of the general path: out1 (360, G, 64) | o2 (G, G, 128) | o3 (G - 2, G - 2, 256), each 256-byte aligned
-size_t ovn_delta_generic_pair_bytes(int G) {
+// Bytes of scratch per pair of the general path: out1 (W, G, 64) | o2 (G, G, 128) | o3 (G - 2, G - 2, 256), each 256-byte aligned
+size_t ovn_delta_generic_pair_bytes(int FW, int G) {
   auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
   return al((size_t)FW * G * O1 * 4) + al((size_t)G * G * OVN_C2_OUT * 4) + al((size_t)(G - 2) * (G - 2) * OVN_C3_OUT * 4);
 }
 
-// The whole Delta head for n pairs at conv1size s = ctx->head_s (any value with 360 // s >= 3); scratch: n * pair_bytes
+// The whole Delta head for n pairs at conv1size s = ctx->head_s (any value with W // s >= 3) and feature width W = ctx->feat_w (360
+// before ovn_finalize); scratch: n * pair_bytes
 int ovn_delta_generic_forward(const ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r,
                               const int32_t* ridx, int n, void* scratch, float* overlap, float* logit, hipStream_t stream) {
   const int s = ctx->head_s, G = ctx->head_g;
+  const int FW = ctx->finalized ? ctx->feat_w : OVN_FEAT_W;
   auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
   float* out1 = static_cast<float*>(scratch);
   float* o2 = reinterpret_cast<float*>(static_cast<char*>(scratch) + al((size_t)n * FW * G * O1 * 4));
@@ -127,15 +129,19 @@ int ovn_delta_generic_forward(const ovn_ctx* ctx, const float* feats_l, const in
   if (rc) return rc;
   const int nib = (FW + IB - 1) / IB;
   hipLaunchKernelGGL(delta_c1_generic_kernel, dim3((unsigned)(nib * G * n)), dim3(256), lds, stream, feats_l, lidx, feats_r, ridx,
-                     ctx->w1raw, ctx->b1, s, G, out1);
+                     ctx->w1raw, ctx->b1, s, G, FW, out1);
   OVN_HIP_CHECK(hipGetLastError());
   int oh = 0, ow = 0;
-  rc = ovn_conv_forward(ctx->c2, out1, n, FW, G, o2, &oh, &ow, stream);          // (n, 360, G, 64) -> (n, G, G, 128), s x 1 / stride (s, 1)
+  rc = ovn_conv_forward(ctx->c2, out1, n, FW, G, o2, &oh, &ow, stream);          // (n, W, G, 64) -> (n, G, G, 128), s x 1 / stride (s, 1)
   if (rc) return rc;
   OVN_REQUIRE(oh == G && ow == G, OVN_ERR_STATE, "general Delta head: c_conv2 produced %dx%d, expected %dx%d", oh, ow, G, G);
   rc = ovn_conv_forward(ctx->c3, o2, n, G, G, o3, &oh, &ow, stream);              // -> (n, G - 2, G - 2, 256)
   if (rc) return rc;
-  const long long dense_in = (long long)(G - 2) * (G - 2) * OVN_C3_OUT;
+  return ovn_dense_sigmoid_any_forward(ctx, o3, n, (long long)(G - 2) * (G - 2) * OVN_C3_OUT, overlap, logit, stream);
+}
+
+int ovn_dense_sigmoid_any_forward(const ovn_ctx* ctx, const float* o3, int n, long long dense_in, float* overlap, float* logit,
+                                  hipStream_t stream) {
   hipLaunchKernelGGL(dense_sigmoid_any_kernel, dim3(n), dim3(256), 0, stream, o3, ctx->wd, ctx->bd, dense_in, overlap, logit);
   OVN_HIP_CHECK(hipGetLastError());
   return OVN_OK;

@@ -52,6 +52,10 @@ int ovn_ws_reserve(ovn_ctx* ctx, size_t bytes, hipStream_t stream) {
   return OVN_OK;
 }
 
+// Width of the context's feature volumes: the leg's output once finalized, the reference's 360 before (a context that registers head
+// weights without a leg keeps the behaviour it always had)
+static int ctx_feat_w(const ovn_ctx* ctx) { return ctx->finalized ? ctx->feat_w : OVN_FEAT_W; }
+
 extern "C" {
 
 int ovn_abi_version(void) { return OVN_ABI_VERSION; }
@@ -185,7 +189,9 @@ int ovn_set_head_weights(ovn_ctx* ctx, const float* c1k, const float* c1b, const
     ctx->w1p = ctx->b1 = ctx->wd = ctx->bd = nullptr;
     ctx->head_set = false;
   }
+  ctx->head_g = ctx_feat_w(ctx) / ctx->head_s;   // G of the Dense kernel registered below
   const int hs = ctx->head_s, hg = ctx->head_g;
+  OVN_REQUIRE(hg >= 3, OVN_ERR_ARG, "ovn_set_head_weights: conv1size %d leaves %d column groups, c_conv3 needs 3", hs, hg);
   const bool general = (hs != OVN_S);   // any other conv1size: general fp32 path (delta_head_generic.hip), no fast-path operands
   int rc = OVN_OK;
   if (!general) {
@@ -249,8 +255,12 @@ int ovn_finalize(ovn_ctx* ctx, int* feat_w) {
     w = (w - l.kw) / l.sw + 1;
     c = l.cout;
   }
-  OVN_REQUIRE(h == 1 && w == OVN_FEAT_W && c == OVN_FEAT_C, OVN_ERR_ARG,
-              "ovn_finalize: leg produces %dx%dx%d, the heads need 1x%dx%d", h, w, c, OVN_FEAT_W, OVN_FEAT_C);
+  OVN_REQUIRE(h == 1 && w >= OVN_FEAT_W_MIN && w <= OVN_FEAT_W_MAX && c == OVN_FEAT_C, OVN_ERR_ARG,
+              "ovn_finalize: leg produces %dx%dx%d, the heads need 1 x W x %d with %d <= W <= %d", h, w, c, OVN_FEAT_C, OVN_FEAT_W_MIN,
+              OVN_FEAT_W_MAX);
+  OVN_REQUIRE(!ctx->head_set || w / ctx->head_s == ctx->head_g, OVN_ERR_STATE,
+              "ovn_finalize: leg width %d gives %d column groups, the head weights were registered for %d", w, w / ctx->head_s,
+              ctx->head_g);
   ctx->feat_w = w;
   ctx->finalized = true;
   if (feat_w) *feat_w = w;
@@ -286,6 +296,7 @@ int ovn_leg(ovn_ctx* ctx, const float* images_dev, int64_t n, float* features_de
   if (rc) return rc;
   float* buf[2] = {reinterpret_cast<float*>(ctx->ws), reinterpret_cast<float*>(static_cast<char*>(ctx->ws) + buf_bytes)};
   const size_t in_elems = (size_t)ctx->in_h * ctx->in_w * ctx->in_c;
+  const size_t feat_elems = (size_t)ctx->feat_w * OVN_FEAT_C;
   OVN_REQUIRE(ctx->leg.size() + 1 <= OVN_ACTMAX_SLOTS, OVN_ERR_STATE, "ovn_leg: too many leg layers");
   const size_t actmax_bytes = (size_t)OVN_ACTMAX_SLOTS * OVN_LEG_SLICE * OVN_ACTMAX_STRIDE * sizeof(unsigned);
   if (ctx->leg_mode != 0 && !ctx->actmax) OVN_HIP_CHECK(hipMalloc((void**)&ctx->actmax, actmax_bytes));
@@ -308,7 +319,7 @@ int ovn_leg(ovn_ctx* ctx, const float* images_dev, int64_t n, float* features_de
     }
     for (size_t li = 0; li < ctx->leg.size(); ++li) {
       const bool last = (li + 1 == ctx->leg.size());
-      float* dst = last ? features_dev + (size_t)s0 * OVN_FEAT_ELEMS : buf[li & 1];
+      float* dst = last ? features_dev + (size_t)s0 * feat_elems : buf[li & 1];
       int oh = 0, ow = 0;
       // f16x3, C = 4: s_conv1 + s_conv2 as one kernel (the activation between them never leaves the CU)
       if (ctx->leg_mode != 0 && li == 0 && (reinterpret_cast<uintptr_t>(cur) & 15) == 0 && ovn_leg_front_matches(ctx, li, h, w)) {
@@ -325,7 +336,7 @@ int ovn_leg(ovn_ctx* ctx, const float* images_dev, int64_t n, float* features_de
       // f16x3: the six 1 x KW layers at the end run as one kernel with the activations kept in LDS
       if (ctx->leg_mode != 0 && ovn_leg_tail_matches(ctx, li, h, w)) {
         OvnProfScope ps(ctx, OVN_K_LEG, stream);
-        rc = ovn_leg_tail_forward(ctx, li, cur, nb, w, features_dev + (size_t)s0 * OVN_FEAT_ELEMS, stream);
+        rc = ovn_leg_tail_forward(ctx, li, cur, nb, w, features_dev + (size_t)s0 * feat_elems, stream);
         if (rc) return rc;
         break;
       }
@@ -352,11 +363,15 @@ int ovn_corr_head(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const
   OVN_REQUIRE(feats_l && feats_r && yaw, OVN_ERR_ARG, "ovn_corr_head: NULL buffer");
   OVN_ON_DEVICE(ctx->device);
   OvnProfScope ps(ctx, OVN_K_CORR, (hipStream_t)stream);
+  if (ctx_feat_w(ctx) != OVN_FEAT_W)
+    return ovn_corr_w_forward(feats_l, lidx, feats_r, ridx, (int)n, ctx_feat_w(ctx), yaw, corr, (hipStream_t)stream, ctx->corr_norm);
   return ovn_corr_forward(feats_l, lidx, feats_r, ridx, (int)n, yaw, corr, (hipStream_t)stream, ctx->corr_norm);
 }
 
 int ovn_spectrum(ovn_ctx* ctx, const float* feats_dev, int64_t n, float* spectra_dev, void* stream) {
   OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_spectrum: ctx is NULL");
+  OVN_REQUIRE(ctx_feat_w(ctx) == OVN_FEAT_W, OVN_ERR_ARG,
+              "ovn_spectrum: the spectral correlation head needs 360-column feature volumes (the leg produces %d)", ctx_feat_w(ctx));
   OVN_REQUIRE(n >= 0 && n < (1ll << 24), OVN_ERR_ARG, "ovn_spectrum: bad n");
   if (n == 0) return OVN_OK;
   OVN_REQUIRE(feats_dev && spectra_dev, OVN_ERR_ARG, "ovn_spectrum: NULL buffer");
@@ -368,6 +383,8 @@ int ovn_spectrum(ovn_ctx* ctx, const float* feats_dev, int64_t n, float* spectra
 int ovn_corr_head_spectral(ovn_ctx* ctx, const float* spec_l, const int32_t* lidx, const float* spec_r,
                            const int32_t* ridx, int64_t n, int32_t* yaw, float* corr, void* stream) {
   OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_corr_head_spectral: ctx is NULL");
+  OVN_REQUIRE(ctx_feat_w(ctx) == OVN_FEAT_W, OVN_ERR_ARG,
+              "ovn_corr_head_spectral: the spectral correlation head needs 360-column feature volumes (the leg produces %d)", ctx_feat_w(ctx));
   OVN_REQUIRE(n >= 0 && n < (1ll << 31), OVN_ERR_ARG, "ovn_corr_head_spectral: bad n");
   if (n == 0) return OVN_OK;
   OVN_REQUIRE(spec_l && spec_r && yaw, OVN_ERR_ARG, "ovn_corr_head_spectral: NULL buffer");
@@ -442,10 +459,17 @@ static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lid
                           const int32_t* ridx, int64_t n, float* overlap, float* logit, int32_t* yaw, float* corr,
                           int corr_mode, const float* spec_l, const float* spec_r, const float* dcache_l, hipStream_t stream) {
   ctx->dbg_live = nullptr;   // ovn_head_walk_stats describes THIS call (a sweep that compacts sets it again)
-  if (ctx->head_s != OVN_S) {   // general conv1size: fp32 generality path, chunked so that the scratch stays near 2 GB
-    const size_t pb = ovn_delta_generic_pair_bytes(ctx->head_g);
+  const int fw = ctx_feat_w(ctx);
+  const size_t feat_elems = (size_t)fw * OVN_FEAT_C;
+  // general conv1size, or a feature width other than 360: fp32 paths (every head mode), chunked so that the scratch stays near 2 GB.
+  // At W != 360 with conv1size 15 the Delta head is the fused MFMA kernel of delta_head_w.hip, and the chunk honours head_chunk.
+  if (ctx->head_s != OVN_S || fw != OVN_FEAT_W) {
+    OVN_REQUIRE(corr_mode != 2 || fw == OVN_FEAT_W, OVN_ERR_ARG, "spectral correlation head at feature width %d", fw);
+    const bool wide = (ctx->head_s == OVN_S);
+    const size_t pb = wide ? ovn_delta_w_pair_bytes(ctx->head_g) : ovn_delta_generic_pair_bytes(fw, ctx->head_g);
     int64_t chunk = (int64_t)((2ull << 30) / pb);
     chunk = chunk < 1 ? 1 : (chunk > 1024 ? 1024 : chunk);
+    if (fw != OVN_FEAT_W && ctx->head_chunk < chunk) chunk = ctx->head_chunk;
     const int64_t cmax = n < chunk ? n : chunk;
     int rc = ovn_ws_reserve(ctx, (size_t)cmax * pb + 1024, stream);
     if (rc) return rc;
@@ -460,16 +484,22 @@ static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lid
     }
     for (int64_t p0 = 0; p0 < n; p0 += chunk) {
       const int np = (int)((n - p0 < chunk) ? (n - p0) : chunk);
-      const float* fl = lidx ? feats_l : feats_l + (size_t)p0 * OVN_FEAT_ELEMS;
+      const float* fl = lidx ? feats_l : feats_l + (size_t)p0 * feat_elems;
       const int32_t* li = lidx ? lidx + p0 : nullptr;
       const int32_t* ri = ridx ? ridx + p0 : nullptr;
       if (corr_mode == 1) {
         OvnProfScope ps(ctx, OVN_K_CORR, stream);
-        rc = ovn_corr_forward(fl, li, feats_r, ri, np, yaw + p0, corr ? corr + (size_t)p0 * OVN_FEAT_W : nullptr, stream, ctx->corr_norm);
+        float* cp = corr ? corr + (size_t)p0 * fw : nullptr;
+        rc = (fw == OVN_FEAT_W) ? ovn_corr_forward(fl, li, feats_r, ri, np, yaw + p0, cp, stream, ctx->corr_norm)
+                                : ovn_corr_w_forward(fl, li, feats_r, ri, np, fw, yaw + p0, cp, stream, ctx->corr_norm);
         if (rc) return rc;
       }
-      OvnProfScope ps(ctx, OVN_K_DELTA, stream);
-      rc = ovn_delta_generic_forward(ctx, fl, li, feats_r, ri, np, ctx->ws, overlap + p0, logit ? logit + p0 : nullptr, stream);
+      if (wide) {   // times its Delta, c_conv3 and Dense kernels separately
+        rc = ovn_delta_w_forward(ctx, fl, li, feats_r, ri, np, ctx->ws, overlap + p0, logit ? logit + p0 : nullptr, stream);
+      } else {
+        OvnProfScope ps(ctx, OVN_K_DELTA, stream);
+        rc = ovn_delta_generic_forward(ctx, fl, li, feats_r, ri, np, ctx->ws, overlap + p0, logit ? logit + p0 : nullptr, stream);
+      }
       if (rc) return rc;
     }
     return OVN_OK;
@@ -533,8 +563,8 @@ static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lid
     const int64_t cn = (n - c0 < chunk) ? (n - c0) : chunk;
     if (corr_mode == 1) {
       OvnProfScope ps(ctx, OVN_K_CORR, stream);
-      rc = ovn_corr_forward(lidx ? feats_l : feats_l + (size_t)c0 * OVN_FEAT_ELEMS, lidx ? lidx + c0 : nullptr, feats_r,
-                            ridx ? ridx + c0 : nullptr, (int)cn, yaw + c0, corr ? corr + (size_t)c0 * OVN_FEAT_W : nullptr, stream,
+      rc = ovn_corr_forward(lidx ? feats_l : feats_l + (size_t)c0 * feat_elems, lidx ? lidx + c0 : nullptr, feats_r,
+                            ridx ? ridx + c0 : nullptr, (int)cn, yaw + c0, corr ? corr + (size_t)c0 * fw : nullptr, stream,
                             ctx->corr_norm);
       if (rc) return rc;
     }
@@ -547,7 +577,7 @@ static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lid
         rc = fk.side(0, &st);
         if (rc) return rc;
       }
-      const float* fl = lidx ? feats_l : feats_l + (size_t)p0 * OVN_FEAT_ELEMS;
+      const float* fl = lidx ? feats_l : feats_l + (size_t)p0 * feat_elems;
       const int32_t* li = lidx ? lidx + p0 : nullptr;
       const int32_t* ri = ridx ? ridx + p0 : nullptr;
       float* o2s = o2 + (size_t)q0 * o2_elems;
@@ -602,6 +632,8 @@ int ovn_heads_spectral(ovn_ctx* ctx, const float* feats_l, const float* spec_l, 
                        const float* feats_r, const float* spec_r, const int32_t* ridx, int64_t n, float* overlap, int32_t* yaw,
                        float* logit, float* corr, void* stream_) {
   OVN_REQUIRE(ctx && ctx->head_set, OVN_ERR_STATE, "ovn_heads_spectral: head weights not set");
+  OVN_REQUIRE(ctx_feat_w(ctx) == OVN_FEAT_W, OVN_ERR_ARG,
+              "ovn_heads_spectral: the spectral correlation head needs 360-column feature volumes (the leg produces %d)", ctx_feat_w(ctx));
   OVN_REQUIRE(n >= 0 && n < (1ll << 31), OVN_ERR_ARG, "ovn_heads_spectral: bad n");
   if (n == 0) return OVN_OK;
   OVN_REQUIRE(feats_l && feats_r && spec_l && spec_r && overlap && yaw, OVN_ERR_ARG, "ovn_heads_spectral: NULL buffer");
@@ -622,6 +654,8 @@ int ovn_delta_head(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, cons
 
 int ovn_delta_cache(ovn_ctx* ctx, const float* feats_dev, int64_t n, float* cache_dev, void* stream) {
   OVN_REQUIRE(ctx && ctx->head_set, OVN_ERR_STATE, "ovn_delta_cache: head weights not set");
+  OVN_REQUIRE(ctx_feat_w(ctx) == OVN_FEAT_W, OVN_ERR_ARG,
+              "ovn_delta_cache: Delta cache rows exist for 360-column feature volumes only (the leg produces %d)", ctx_feat_w(ctx));
   OVN_REQUIRE(n >= 0 && n < (1ll << 24), OVN_ERR_ARG, "ovn_delta_cache: bad n");
   if (n == 0) return OVN_OK;
   OVN_REQUIRE(feats_dev && cache_dev, OVN_ERR_ARG, "ovn_delta_cache: NULL buffer");
@@ -635,10 +669,11 @@ int ovn_delta_cache(ovn_ctx* ctx, const float* feats_dev, int64_t n, float* cach
 int ovn_set_head_geometry(ovn_ctx* ctx, int conv1size) {
   OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_set_head_geometry: ctx is NULL");
   OVN_REQUIRE(!ctx->head_set, OVN_ERR_STATE, "ovn_set_head_geometry: call it before ovn_set_head_weights");
-  OVN_REQUIRE(conv1size >= 1 && OVN_FEAT_W / conv1size >= 3, OVN_ERR_ARG,
-              "ovn_set_head_geometry: conv1size %d leaves fewer than 3 x 3 groups of the 360 columns for c_conv3", conv1size);
+  const int fw = ctx_feat_w(ctx);
+  OVN_REQUIRE(conv1size >= 1 && fw / conv1size >= 3, OVN_ERR_ARG,
+              "ovn_set_head_geometry: conv1size %d leaves fewer than 3 x 3 groups of the %d columns for c_conv3", conv1size, fw);
   ctx->head_s = conv1size;
-  ctx->head_g = OVN_FEAT_W / conv1size;
+  ctx->head_g = fw / conv1size;
   return OVN_OK;
 }
 

@@ -62,6 +62,8 @@ struct OvnDeviceGuard {
 constexpr int OVN_FEAT_W = 360;   // leg_output_width, config/network.yml:77
 constexpr int OVN_FEAT_C = 128;   // s_conv10 filters, generateNet.py:214
 constexpr int OVN_FEAT_ELEMS = OVN_FEAT_W * OVN_FEAT_C;
+// any other leg output width W in [OVN_FEAT_W_MIN, OVN_FEAT_W_MAX] (include/ovn_hip.h) runs the runtime-W fp32 heads
+// (delta_head_w.hip, corr_head_w.hip, delta_head_generic.hip); every feature volume is ctx->feat_w * 128 floats
 constexpr int OVN_S = 15;         // conv1NetworkHead_conv1size default, generateNet.py:88-89
 constexpr int OVN_G = OVN_FEAT_W / OVN_S;            // 24
 constexpr int OVN_C1_OUT = 64;    // c_conv1 filters
@@ -367,8 +369,21 @@ int ovn_delta_c12_bf16x3_forward(ovn_ctx* ctx, const float* feats_l, const int32
 int ovn_delta_cache_forward(ovn_ctx* ctx, const float* feats, int n, float* cache, hipStream_t stream);
 int ovn_delta_walk_stats(ovn_ctx* ctx, int32_t* out16, hipStream_t stream);
 
-// delta_head_generic.hip: the Delta head for any conv1size (fp32, generality path)
-size_t ovn_delta_generic_pair_bytes(int G);
+// delta_head_generic.hip: the Delta head for any conv1size (fp32, generality path) at feature width ctx->feat_w
+size_t ovn_delta_generic_pair_bytes(int W, int G);
+// Dense(1) + sigmoid over dense_in floats per pair (fixed reduction order)
+int ovn_dense_sigmoid_any_forward(const ovn_ctx* ctx, const float* o3, int n, long long dense_in, float* overlap, float* logit,
+                                  hipStream_t stream);
+
+// delta_head_w.hip: the Delta head at a feature width W != 360 with conv1size 15 (fused fp32 MFMA DeltaLayer + c_conv1 + c_conv2,
+// generic c_conv3, Dense); scratch: n * ovn_delta_w_pair_bytes(G) + 256 bytes
+size_t ovn_delta_w_pair_bytes(int G);
+int ovn_delta_w_forward(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx, int n,
+                        void* scratch, float* overlap, float* logit, hipStream_t stream);
+
+// corr_head_w.hip: the direct correlation head at a feature width W != 360 (fp32 MFMA, all normalisation modes)
+int ovn_corr_w_forward(const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx, int n, int W,
+                       int32_t* yaw, float* corr, hipStream_t stream, int norm_mode);
 int ovn_delta_generic_forward(const ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r,
                               const int32_t* ridx, int n, void* scratch, float* overlap, float* logit, hipStream_t stream);
 

@@ -15,7 +15,7 @@ import torch
 from . import _lib
 from . import weights as W
 
-FEAT_W = 360
+FEAT_W = 360         # the reference's leg output width; an engine's own width is OvnEngine.feat_w (weights.feature_width)
 FEAT_C = 128
 
 
@@ -95,7 +95,11 @@ class OvnEngine:
         registered as the negated c_conv1 kernel, exactly, in every head arithmetic."""
         cfg = model_cfg or {}
         norm, negate = W.head_options(cfg)
-        W.check_weights(weights, self.in_c, cfg)
+        try:     # the Dense kernel is sized by the width this leg produces (ovn_finalize refuses a geometry the heads cannot run)
+            hf, fw, _ = W.leg_output_shape(self.in_h, self.in_w, W.leg_layers(self.in_c, cfg))
+        except ValueError:
+            hf, fw = 1, FEAT_W
+        W.check_weights(weights, self.in_c, cfg, fw if hf == 1 else FEAT_W)
         self.conv1size = int(cfg.get("conv1NetworkHead_conv1size", 15))     # generateNet.py:88-89
         with self._dev():
             st = self._stream()
@@ -125,7 +129,7 @@ class OvnEngine:
 
     # -- leg ----------------------------------------------------------------------------------------
     def leg(self, images: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """images (n, H, W, C) float32 on this device -> feature volumes (n, 360, 128)."""
+        """images (n, H, W, C) float32 on this device -> feature volumes (n, feat_w, 128)."""
         if not self._leg_ready:
             raise _lib.OvnError("leg weights not loaded")
         if images.device != self.device or images.dtype != torch.float32 or not images.is_contiguous():
@@ -140,11 +144,21 @@ class OvnEngine:
         return out
 
     # -- heads --------------------------------------------------------------------------------------
+    @property
+    def _fw(self) -> int:
+        """Width of this engine's feature volumes: the leg's output once the weights are loaded, 360 before."""
+        return self.feat_w or FEAT_W
+
+    @property
+    def has_spectrum(self) -> bool:
+        """The spectral correlation head (`spectrum`, `corr_head_spectral`, spec_l / spec_r of `heads`) runs 360-column volumes only."""
+        return self._fw == FEAT_W
+
     def _check_feats(self, t: torch.Tensor, what: str) -> None:
         if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous():
             raise _lib.OvnError("%s must be a contiguous float32 tensor on %s" % (what, self.device))
-        if t.numel() % (FEAT_W * FEAT_C) != 0:
-            raise _lib.OvnError("%s is not a stack of 360x128 feature volumes" % what)
+        if t.numel() % (self._fw * FEAT_C) != 0:
+            raise _lib.OvnError("%s is not a stack of %dx128 feature volumes" % (what, self._fw))
 
     def _idx(self, idx, n: Optional[int], bound: Optional[int] = None, what: str = "pair index") -> Optional[torch.Tensor]:
         """Index list -> int32 device tensor.  Host lists / arrays are range-checked ON THE HOST before the upload (no device
@@ -196,13 +210,14 @@ class OvnEngine:
         lidx None -> p, ridx None -> 0 (1-vs-N: feats_r holds the single query).
         spec_l / spec_r: cached spectra (`spectrum`) -> the HBM-bound spectral yaw head; dcache_l: the left pool's Delta cache rows
         (`delta_cache`), used by 1-vs-N sweeps -- same results with or without it.
-        Returns dict of device tensors: overlap (n) f32, yaw (n) i32 [, logit (n), corr (n,360)]."""
+        Returns dict of device tensors: overlap (n) f32, yaw (n) i32 [, logit (n), corr (n, feat_w)].  At feat_w != 360 there are no
+        spectra or Delta cache rows: spec_l / spec_r raise."""
         if not self._head_ready:
             raise _lib.OvnError("head weights not loaded")
         self._check_feats(feats_l, "feats_l")
         self._check_feats(feats_r, "feats_r")
-        nl = feats_l.numel() // (FEAT_W * FEAT_C)
-        nr = feats_r.numel() // (FEAT_W * FEAT_C)
+        nl = feats_l.numel() // (self._fw * FEAT_C)
+        nr = feats_r.numel() // (self._fw * FEAT_C)
         li, ri, n = self._pairs(nl, nr, lidx, ridx, n)
         overlap = torch.empty(n, dtype=torch.float32, device=self.device)
         logit = torch.empty(n, dtype=torch.float32, device=self.device) if want_logit else None
@@ -210,6 +225,8 @@ class OvnEngine:
             # cached spectra given: Delta head on the features, correlation head in its HBM-bound spectral form
             if spec_l is None or spec_r is None:
                 raise _lib.OvnError("spec_l and spec_r must be given together")
+            if not self.has_spectrum:
+                raise _lib.OvnError("spectra exist for 360-column feature volumes only (this leg produces %d)" % self._fw)
             for t, what in ((spec_l, "spec_l"), (spec_r, "spec_r")):
                 if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous():
                     raise _lib.OvnError("%s must be a contiguous float32 tensor on %s" % (what, self.device))
@@ -233,7 +250,7 @@ class OvnEngine:
                 out["corr"] = corr
             return out
         yaw = torch.empty(n, dtype=torch.int32, device=self.device)
-        corr = torch.empty((n, FEAT_W), dtype=torch.float32, device=self.device) if want_corr else None
+        corr = torch.empty((n, self._fw), dtype=torch.float32, device=self.device) if want_corr else None
         with self._dev():
             _lib.check(self.lib.ovn_heads(self._h, _ptr(feats_l), _ptr(li), _ptr(feats_r), _ptr(ri), n, _ptr(overlap),
                                           _ptr(yaw), _ptr(logit), _ptr(corr), self._stream()), "ovn_heads")
@@ -248,9 +265,9 @@ class OvnEngine:
                   want_corr: bool = False):
         self._check_feats(feats_l, "feats_l")
         self._check_feats(feats_r, "feats_r")
-        li, ri, n = self._pairs(feats_l.numel() // (FEAT_W * FEAT_C), feats_r.numel() // (FEAT_W * FEAT_C), lidx, ridx, n)
+        li, ri, n = self._pairs(feats_l.numel() // (self._fw * FEAT_C), feats_r.numel() // (self._fw * FEAT_C), lidx, ridx, n)
         yaw = torch.empty(n, dtype=torch.int32, device=self.device)
-        corr = torch.empty((n, FEAT_W), dtype=torch.float32, device=self.device) if want_corr else None
+        corr = torch.empty((n, self._fw), dtype=torch.float32, device=self.device) if want_corr else None
         with self._dev():
             _lib.check(self.lib.ovn_corr_head(self._h, _ptr(feats_l), _ptr(li), _ptr(feats_r), _ptr(ri), n, _ptr(yaw),
                                               _ptr(corr), self._stream()), "ovn_corr_head")
@@ -261,8 +278,8 @@ class OvnEngine:
 
     @property
     def has_delta_cache(self) -> bool:
-        # the bf16x3 head mode reads no Delta cache rows, so none are built for it
-        return self.conv1size == 15 and self.head_precision != "bf16x3"
+        # the bf16x3 head mode reads no Delta cache rows, so none are built for it; nor are they at a feature width other than 360
+        return self.conv1size == 15 and self.head_precision != "bf16x3" and self._fw == FEAT_W
 
     def delta_cache(self, feats: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """feature volumes (n,360,128) -> Delta cache rows (n, 49216): the candidate-side half of the Delta head's preparation
@@ -270,9 +287,9 @@ class OvnEngine:
         if not self._head_ready:
             raise _lib.OvnError("head weights not loaded")
         if not self.has_delta_cache:
-            raise _lib.OvnError("the Delta cache exists for conv1NetworkHead_conv1size=15 only")
+            raise _lib.OvnError("the Delta cache exists for conv1NetworkHead_conv1size=15 and 360-column feature volumes only")
         self._check_feats(feats, "feats")
-        n = feats.numel() // (FEAT_W * FEAT_C)
+        n = feats.numel() // (self._fw * FEAT_C)
         if out is None:
             out = torch.empty((n, self.DELTA_CACHE_ELEMS), dtype=torch.float32, device=self.device)
         with self._dev():
@@ -280,7 +297,9 @@ class OvnEngine:
         return out
 
     def spectrum(self, feats: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """feature volumes (n,360,128) -> cached spectra (n,128,368) for the spectral correlation head."""
+        """feature volumes (n,360,128) -> cached spectra (n,128,368) for the spectral correlation head (360 columns only)."""
+        if not self.has_spectrum:
+            raise _lib.OvnError("spectra exist for 360-column feature volumes only (this leg produces %d)" % self._fw)
         self._check_feats(feats, "feats")
         n = feats.numel() // (FEAT_W * FEAT_C)
         if out is None:
@@ -291,7 +310,9 @@ class OvnEngine:
 
     def corr_head_spectral(self, spec_l: torch.Tensor, spec_r: torch.Tensor, lidx=None, ridx=None,
                            n: Optional[int] = None, want_corr: bool = False):
-        """Correlation head on cached spectra: dict(yaw (n) i32 [, corr (n,360)])."""
+        """Correlation head on cached spectra: dict(yaw (n) i32 [, corr (n,360)]); 360-column feature volumes only."""
+        if not self.has_spectrum:
+            raise _lib.OvnError("spectra exist for 360-column feature volumes only (this leg produces %d)" % self._fw)
         for t, what in ((spec_l, "spec_l"), (spec_r, "spec_r")):
             if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous():
                 raise _lib.OvnError("%s must be a contiguous float32 tensor on %s" % (what, self.device))
@@ -479,7 +500,10 @@ class OvnEngine:
         """Arithmetic of the Delta-head contractions (fp32 storage and accumulation in both modes):
         'f16x3' (default) = scaled 3-term fp16 split on the fp16 matrix cores (22 significand bits per operand: the error of an
         fp32 evaluation), 'f32' = fp32 matrix cores (bit-for-bit an fp32 FMA chain, 1/16 of the rate), 'bf16x3' = exact 3-term bf16
-        split on the bf16 matrix cores (operands at least as wide as fp32: 24 significand bits; include/ovn_hip.h)."""
+        split on the bf16 matrix cores (operands at least as wide as fp32: 24 significand bits; include/ovn_hip.h).
+        At a feature width other than 360 every mode runs the exact fp32 heads (delta_head_w.hip / corr_head_w.hip): the
+        split-operand kernels are tiled to 24 column groups of 15 and to the 360-point DFT, and fp32 is the reference's own
+        arithmetic.  The mode is still recorded (and the leg follows its own precision setting)."""
         table = {"f32": 0, "f16x3": 1, "bf16x3": 2}
         if mode not in table:
             raise ValueError("head precision must be one of %s" % sorted(table))
@@ -598,8 +622,10 @@ class QueryAhead:
         dev = engine.device
         with torch.cuda.device(dev):
             self.stream = torch.cuda.Stream(device=dev)
-            self._fv = [torch.empty((1, FEAT_W, FEAT_C), dtype=torch.float32, device=dev) for _ in range(2)]
-            self._spec = [torch.empty((1, FEAT_C, engine.SPEC_W), dtype=torch.float32, device=dev) for _ in range(2)]
+            self._fv = [torch.empty((1, self.side.feat_w, FEAT_C), dtype=torch.float32, device=dev) for _ in range(2)]
+            # no spectrum at a feature width other than 360: take() hands out (volume, None), the look-ahead is the leg alone
+            self._spec = [torch.empty((1, FEAT_C, engine.SPEC_W), dtype=torch.float32, device=dev) if self.side.has_spectrum else None
+                          for _ in range(2)]
             self._dc = ([torch.empty((1, engine.DELTA_CACHE_ELEMS), dtype=torch.float32, device=dev) for _ in range(2)]
                         if with_delta_cache and engine.has_delta_cache else None)
             self._ready = [torch.cuda.Event(), torch.cuda.Event()]
@@ -642,7 +668,8 @@ class QueryAhead:
             self.stream.wait_event(self._released[slot])     # the heads that read this slot two queries ago are done with it
         with torch.cuda.stream(self.stream):
             self.side.leg(image, out=self._fv[slot])
-            self.side.spectrum(self._fv[slot], out=self._spec[slot])
+            if self._spec[slot] is not None:
+                self.side.spectrum(self._fv[slot], out=self._spec[slot])
             self._has_dc[slot] = self._dc is not None and bool(with_delta)
             if self._has_dc[slot]:
                 self.side.delta_cache(self._fv[slot], out=self._dc[slot])
@@ -651,7 +678,7 @@ class QueryAhead:
         self._submitted += 1
 
     def take(self) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(feature volume (1, 360, 128), spectrum) of the oldest submitted query; the CURRENT stream waits for them, the host does
+        """(feature volume (1, W, 128), spectrum or None at W != 360) of the oldest submitted query; the CURRENT stream waits for them, the host does
         not.  Readers of the pair must be enqueued on the current stream before the next submit() / take() call (class docstring)."""
         if self._taken >= self._submitted:
             raise _lib.OvnError("QueryAhead.take: nothing submitted")

@@ -45,7 +45,8 @@ _VALID_LEGS = ("360OutputkLegs", "360OutputkLegsFixed")       # generateNet.py:1
 
 class FeatureVolumeCache(object):
   """`Infer.feature_volumes`: behaves like the reference's Python list of (1, 360, 128) arrays (infer.py:114,185), but the
-  volumes live in HBM (together with their spectra) and are copied to the host one at a time when indexed."""
+  volumes live in HBM (together with their spectra) and are copied to the host one at a time when indexed.  At a leg output width
+  W != 360 the volumes are (1, W, 128) and the cache holds them alone: the spectra and Delta cache rows exist at 360 only."""
 
   def __init__(self, engine, min_capacity=1024, with_delta_cache=True):
     """min_capacity: smallest allocation (volumes) on first use -- 1024 (580 MB with the spectra and the Delta cache rows) for the persistent cache of
@@ -64,18 +65,27 @@ class FeatureVolumeCache(object):
   def _with_dc(self) -> bool:      # (the engine learns its head geometry when the weights are loaded, after this object is built)
     return self._want_dc and self._engine.has_delta_cache
 
+  @property
+  def spectral(self) -> bool:      # spectra are cached next to the volumes (feature width 360)
+    return self._engine.has_spectrum
+
+  @property
+  def _w(self) -> int:
+    return self._engine.feat_w or FEAT_W
+
   # -- device side ---------------------------------------------------------------------------------
   def _grow(self, need: int) -> None:
     if self._fv is not None and need <= self._fv.shape[0]:
       return
     cap = max(self._min_capacity, need if self._fv is None else 2 * need)
     dev = self._engine.device
-    nf = torch.empty((cap, FEAT_W, FEAT_C), dtype=torch.float32, device=dev)
-    ns = torch.empty((cap, FEAT_C, self._engine.SPEC_W), dtype=torch.float32, device=dev)
+    nf = torch.empty((cap, self._w, FEAT_C), dtype=torch.float32, device=dev)
+    ns = torch.empty((cap if self.spectral else 0, FEAT_C, self._engine.SPEC_W), dtype=torch.float32, device=dev)
     nd = torch.empty((cap if self._with_dc else 0, self._engine.DELTA_CACHE_ELEMS), dtype=torch.float32, device=dev)
     if self._n:
       nf[:self._n].copy_(self._fv[:self._n])
-      ns[:self._n].copy_(self._spec[:self._n])
+      if self.spectral:
+        ns[:self._n].copy_(self._spec[:self._n])
       if self._with_dc:
         nd[:self._n].copy_(self._dc[:self._n])
     self._fv, self._spec, self._dc = nf, ns, nd
@@ -90,7 +100,9 @@ class FeatureVolumeCache(object):
     slot = int(slot)
     self._grow(max(self._n, slot + k))
     self._fv[slot:slot + k].copy_(fv)
-    if spec is not None:
+    if not self.spectral:
+      pass
+    elif spec is not None:
       self._spec[slot:slot + k].copy_(spec)
     else:
       self._engine.spectrum(self._fv[slot:slot + k], out=self._spec[slot:slot + k])
@@ -113,7 +125,8 @@ class FeatureVolumeCache(object):
     self._grow(max(self._n, int(slots.max()) + 1))
     idx = torch.from_numpy(slots).to(fv.device)
     self._fv.index_copy_(0, idx, fv)
-    self._spec.index_copy_(0, idx, self._engine.spectrum(fv))
+    if self.spectral:
+      self._spec.index_copy_(0, idx, self._engine.spectrum(fv))
     if self._with_dc:
       self._dc.index_copy_(0, idx, self._engine.delta_cache(fv))
     self._n = max(self._n, int(slots.max()) + 1)
@@ -124,10 +137,13 @@ class FeatureVolumeCache(object):
 
   @property
   def device_features(self) -> torch.Tensor:
-    return self._fv[:self._n] if self._fv is not None else torch.empty((0, FEAT_W, FEAT_C), device=self._engine.device)
+    return self._fv[:self._n] if self._fv is not None else torch.empty((0, self._w, FEAT_C), device=self._engine.device)
 
   @property
-  def device_spectra(self) -> torch.Tensor:
+  def device_spectra(self) -> Optional[torch.Tensor]:
+    """Cached spectra of the volumes, or None at a feature width other than 360 (no spectral correlation head there)."""
+    if not self.spectral:
+      return None
     return self._spec[:self._n] if self._spec is not None else torch.empty((0, FEAT_C, self._engine.SPEC_W), device=self._engine.device)
 
   @property
@@ -143,11 +159,11 @@ class FeatureVolumeCache(object):
 
   @property
   def shape(self):
-    return (self._n, 1, FEAT_W, FEAT_C)
+    return (self._n, 1, self._w, FEAT_C)
 
   def _one(self, i):
     a = self._fv[i].cpu().numpy()
-    return a.reshape(1, FEAT_W, FEAT_C)
+    return a.reshape(1, self._w, FEAT_C)
 
   def __getitem__(self, i):
     if isinstance(i, slice):
@@ -164,12 +180,12 @@ class FeatureVolumeCache(object):
       yield self._one(i)
 
   def __array__(self, dtype=None, copy=None):
-    a = self.device_features.cpu().numpy().reshape(self._n, 1, FEAT_W, FEAT_C)
+    a = self.device_features.cpu().numpy().reshape(self._n, 1, self._w, FEAT_C)
     return a.astype(dtype) if dtype is not None else a
 
   def append(self, volume) -> None:
-    """list.append of a host (1, 360, 128) volume, as a caller of the reference could do."""
-    v = torch.from_numpy(np.ascontiguousarray(volume, np.float32).reshape(1, FEAT_W, FEAT_C)).to(self._engine.device)
+    """list.append of a host (1, W, 128) volume, as a caller of the reference could do."""
+    v = torch.from_numpy(np.ascontiguousarray(volume, np.float32).reshape(1, self._w, FEAT_C)).to(self._engine.device)
     self.extend_device(v)
 
 _VALID_OVERLAP_HEADS = ("DeltaLayerConv1NetworkHead",)         # generateNet.py:64
@@ -261,8 +277,6 @@ class Infer():
                         (orientation_head, _VALID_ORIENTATION_HEADS)):
       if name not in valid:
         raise AttributeError("module 'generateNet' has no attribute 'generate%s'" % name)
-    if self.network_output_size != FEAT_W:
-      raise OvnError("leg_output_width=%s: the HIP heads are built for 360" % self.network_output_size)
 
     # optional head keys (extensions, absent from the reference's network.yml): checked here, before any GPU work, so that a config
     # the heads cannot honour fails loudly instead of being ignored (weights.head_options)
@@ -274,6 +288,12 @@ class Infer():
       'correlationHead_normalize': corr_normalize,
       'deltaLayer_negateDiffs': negate_diffs,
     }
+    # feature geometry from inputShape + the leg's model keys, before any GPU work (ValueError with the shapes otherwise)
+    self.feat_w = W.feature_width(self.inputShape[0], self.inputShape[1], self.inputShape[2], self._model_cfg,
+                                  self.network_output_size)
+    if self._world > 1 and self.feat_w != FEAT_W:
+      raise ValueError('Infer(world=%d): the sharded sweep runs 360-column feature volumes only, this leg produces %d'
+                       % (self._world, self.feat_w))
     self.engine = OvnEngine(self.inputShape[0], self.inputShape[1], self.inputShape[2], device=device)
     self.leg = self.engine    # reference: keras.Model (infer.py:101)
     self.head = self.engine   # reference: keras.Model (infer.py:111)
@@ -295,7 +315,7 @@ class Infer():
       w = W.load_weights_file(pretrained_weightsfilename)
     else:
       print('Pre-trained weights was not found in:', pretrained_weightsfilename)
-      w = W.keras_default_init(self.no_input_channels, self._model_cfg, seed)
+      w = W.keras_default_init(self.no_input_channels, self._model_cfg, seed, self.feat_w)
     self.engine.load_weights(w, self._model_cfg)
     self._weights = w           # kept for the second context of the streaming path (_start_ahead)
     self._qa = None
@@ -337,10 +357,11 @@ class Infer():
         # sweeps refuse it until the cache is reset from a list (`infer.feature_volumes = []` or the volumes of frames 0 .. n-1)
         self._n_frames = -1
       return
-    vols = np.asarray(value, dtype=np.float32) if len(value) else np.zeros((0, FEAT_W, FEAT_C), np.float32)
-    if vols.size % (FEAT_W * FEAT_C):
-      raise ValueError('feature volumes must have shape (n, 1, %d, %d)' % (FEAT_W, FEAT_C))
-    vols = np.ascontiguousarray(vols).reshape(-1, FEAT_W, FEAT_C)
+    fw = self.feat_w
+    vols = np.asarray(value, dtype=np.float32) if len(value) else np.zeros((0, fw, FEAT_C), np.float32)
+    if vols.size % (fw * FEAT_C):
+      raise ValueError('feature volumes must have shape (n, 1, %d, %d)' % (fw, FEAT_C))
+    vols = np.ascontiguousarray(vols).reshape(-1, fw, FEAT_C)
     self._drop_ahead()
     self._n_frames = vols.shape[0]          # sharded mode: the list holds the volumes of frames 0 .. n-1; the next frame is n
     cache = FeatureVolumeCache(self.engine)
@@ -488,7 +509,7 @@ class Infer():
   def _leg_device(self, filenames: Sequence[str]) -> torch.Tensor:
     """leg over `filenames`, batched like predict_generator (batch_size scans per launch group)."""
     n = len(filenames)
-    out = torch.empty((n, FEAT_W, FEAT_C), dtype=torch.float32, device=self.engine.device)
+    out = torch.empty((n, self.feat_w, FEAT_C), dtype=torch.float32, device=self.engine.device)
     bs = max(1, int(self.batch_size))
     for s in range(0, n, bs):
       k = min(bs, n - s)
@@ -498,9 +519,9 @@ class Infer():
 
   def create_feature_volumes(self, filenames):
     """ create feature volumes, thus execute the leg (infer.py:240-265).
-        Returns a n x 1 x 360 x 128 numpy array. """
+        Returns a n x 1 x W x 128 numpy array (W = 360 in the shipped configuration). """
     fv = self._leg_device(list(filenames))
-    return fv.cpu().numpy().reshape(len(filenames), 1, FEAT_W, FEAT_C)
+    return fv.cpu().numpy().reshape(len(filenames), 1, self.feat_w, FEAT_C)
 
   # ------------------------------------------------------------------------------------------------
   def _heads_device(self, cache: FeatureVolumeCache, pair_indizes: np.ndarray):
@@ -509,7 +530,7 @@ class Infer():
     indices are range-checked on the host (no device synchronisation before the launches).  When every pair has the
     same right-hand volume (the 1-vs-N sweep of `infer_multiple`) the library's 1-vs-N form is used: no right index
     array, and the query's linear term is evaluated once instead of per pair."""
-    feats, spec = cache.device_features, cache.device_spectra
+    feats, spec = cache.device_features, cache.device_spectra     # spec None at a feature width != 360: the direct yaw head
     right = pair_indizes[:, 1]
     left = pair_indizes[:, 0]
     if len(left) and left[0] == 0 and np.array_equal(left, np.arange(len(left))):
@@ -518,8 +539,8 @@ class Infer():
       q = int(right[0])
       if not 0 <= q < len(cache):
         raise IndexError('index %d is out of bounds for axis 0 with size %d' % (q, len(cache)))
-      return self.engine.heads(feats, feats[q:q + 1], lidx=left, n=len(right), spec_l=spec, spec_r=spec[q:q + 1],
-                               dcache_l=cache.device_delta_cache)
+      return self.engine.heads(feats, feats[q:q + 1], lidx=left, n=len(right), spec_l=spec,
+                               spec_r=None if spec is None else spec[q:q + 1], dcache_l=cache.device_delta_cache)
     return self.engine.heads(feats, feats, lidx=left, ridx=right, n=len(right), spec_l=spec, spec_r=spec)
 
   def _run_heads(self, cache: FeatureVolumeCache, pair_indizes: np.ndarray, ahead=None):

@@ -18,6 +18,8 @@ from typing import Dict, List, NamedTuple, Sequence, Tuple
 
 import numpy as np
 
+from ._lib import OvnError
+
 
 class ConvSpec(NamedTuple):
     name: str
@@ -72,6 +74,35 @@ def leg_output_shape(h: int, w: int, layers: Sequence[ConvSpec]) -> Tuple[int, i
     return h, w, c
 
 
+# feature widths the heads run (include/ovn_hip.h: OVN_FEAT_W_MIN / OVN_FEAT_W_MAX): G = W // 15 >= 3 column groups for c_conv3,
+# and the runtime-W kernels' LDS stays within 160 KB up to 512
+FEAT_W_MIN = 45
+FEAT_W_MAX = 512
+
+
+class FeatureGeometryError(ValueError, OvnError):
+    """A leg geometry the heads cannot run.  A ValueError (the configuration is wrong) raised before any GPU work, and an OvnError:
+    the library's ovn_finalize refuses the same shapes with one, so callers that caught it keep working."""
+
+
+def feature_width(in_h: int, in_w: int, in_channels: int, model_cfg: dict | None = None,
+                  leg_output_width: int | None = None) -> int:
+    """The feature width W the leg produces from an (in_h, in_w, in_channels) input under the model keys `strides_layer1` /
+    `additional_unsymmetric_layer3a` (Keras derives every shape from `inputShape`, generateNet.py:143-146, 161-214).  Raises
+    FeatureGeometryError (a ValueError), with the shapes in the message, unless the feature volume is 1 x W x 128 with FEAT_W_MIN <= W <= FEAT_W_MAX, and when
+    `leg_output_width` (config['model']['leg_output_width'], the reference's yaw label width, com_overlap_yaw.py:25) is given and
+    differs from W."""
+    hf, wf, cf = leg_output_shape(int(in_h), int(in_w), leg_layers(in_channels, model_cfg))
+    what = "input %dx%dx%d -> leg output %dx%dx%d" % (in_h, in_w, in_channels, hf, wf, cf)
+    if hf != 1:
+        raise FeatureGeometryError("%s: the heads need a feature volume of height 1 (the correlation head reshapes it to (W, 1))" % what)
+    if not FEAT_W_MIN <= wf <= FEAT_W_MAX:
+        raise FeatureGeometryError("%s: the heads run feature widths %d..%d" % (what, FEAT_W_MIN, FEAT_W_MAX))
+    if leg_output_width is not None and int(leg_output_width) != wf:
+        raise FeatureGeometryError("%s: config['model']['leg_output_width'] is %s, the leg produces %d" % (what, leg_output_width, wf))
+    return wf
+
+
 def head_layers(feat_channels: int = 128, conv1size: int = 15) -> List[ConvSpec]:
     """Delta head convolutions (reference `generateNet.py:96-110`). c_conv1 is *linear*."""
     s = int(conv1size)
@@ -110,26 +141,26 @@ def _glorot_uniform(rng: np.random.Generator, shape: Tuple[int, ...]) -> np.ndar
     return rng.uniform(-lim, lim, size=shape).astype(np.float32)
 
 
-def keras_default_init(in_channels: int, model_cfg: dict | None = None, seed: int = 0) -> Dict[str, np.ndarray]:
+def keras_default_init(in_channels: int, model_cfg: dict | None = None, seed: int = 0, feat_w: int = 360) -> Dict[str, np.ndarray]:
     """What the reference is left with when `pretrained_weightsfilename` is empty
-    (`infer.py:121-122`): Keras default init = Glorot-uniform kernels, zero biases."""
+    (`infer.py:121-122`): Keras default init = Glorot-uniform kernels, zero biases.  feat_w: the leg output width (Dense shape)."""
     rng = np.random.default_rng(seed)
     out = {}
-    for k, shp in expected_shapes(in_channels, model_cfg).items():
+    for k, shp in expected_shapes(in_channels, model_cfg, feat_w).items():
         out[k] = _glorot_uniform(rng, shp) if k.endswith("/kernel") else np.zeros(shp, np.float32)
     return out
 
 
 def synthetic_weights(in_channels: int, model_cfg: dict | None = None, seed: int = 0,
                       kernel_gain: float = 1.0, bias_scale: float = 0.05,
-                      gains: Dict[str, float] | None = None) -> Dict[str, np.ndarray]:
+                      gains: Dict[str, float] | None = None, feat_w: int = 360) -> Dict[str, np.ndarray]:
     """Seeded synthetic weights for parity tests and the benchmark (no trained weights ship with the
     reference: `.gitignore:9`). Glorot-uniform kernels scaled by `kernel_gain` (per-layer overrides
-    in `gains`), and small NON-zero biases so that the bias path of every kernel is exercised."""
+    in `gains`), and small NON-zero biases so that the bias path of every kernel is exercised.  feat_w: the leg output width."""
     rng = np.random.default_rng(seed)
     out = {}
     g = gains or {}
-    for k, shp in expected_shapes(in_channels, model_cfg).items():
+    for k, shp in expected_shapes(in_channels, model_cfg, feat_w).items():
         layer = k.split("/")[0]
         if k.endswith("/kernel"):
             out[k] = (_glorot_uniform(rng, shp) * np.float32(g.get(layer, kernel_gain))).astype(np.float32)
@@ -159,8 +190,8 @@ def head_options(model_cfg: dict | None = None) -> Tuple[str, bool]:
     return norm, bool(neg)
 
 
-def check_weights(weights: Dict[str, np.ndarray], in_channels: int, model_cfg: dict | None = None) -> None:
-    exp = expected_shapes(in_channels, model_cfg)
+def check_weights(weights: Dict[str, np.ndarray], in_channels: int, model_cfg: dict | None = None, feat_w: int = 360) -> None:
+    exp = expected_shapes(in_channels, model_cfg, feat_w)
     for k, shp in exp.items():
         if k not in weights:
             raise KeyError("weight '%s' missing" % k)

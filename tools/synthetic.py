@@ -50,12 +50,12 @@ def flags_of(channels: int) -> Tuple[bool, bool, bool]:
     return table[channels]
 
 
-def make_test_weights(channels: int = 4, seed: int = 0, model_cfg: Optional[dict] = None) -> Dict[str, np.ndarray]:
-    """Non-degenerate seeded weights (Glorot-uniform scaled per layer, non-zero biases)."""
+def make_test_weights(channels: int = 4, seed: int = 0, model_cfg: Optional[dict] = None, feat_w: int = 360) -> Dict[str, np.ndarray]:
+    """Non-degenerate seeded weights (Glorot-uniform scaled per layer, non-zero biases); feat_w: leg output width (Dense shape)."""
     cfg = model_cfg or REFERENCE_MODEL_CFG
     gains = {l.name: _LEG_GAIN for l in W.leg_layers(channels, cfg)}
     gains["overlap_output"] = _DENSE_GAIN
-    w = W.synthetic_weights(channels, cfg, seed=seed, kernel_gain=1.0, bias_scale=0.05, gains=gains)
+    w = W.synthetic_weights(channels, cfg, seed=seed, kernel_gain=1.0, bias_scale=0.05, gains=gains, feat_w=feat_w)
     w["overlap_output/bias"] = np.array([_DENSE_BIAS.get(channels, 2.0)], np.float32)
     return w
 
