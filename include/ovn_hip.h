@@ -39,7 +39,7 @@ typedef struct ovn_ctx ovn_ctx;
 #define OVN_ERR_STATE 3    /* call order (weights missing ...)  */
 
 /* ABI version of this header; bumped on any signature change. */
-#define OVN_ABI_VERSION 9
+#define OVN_ABI_VERSION 10
 int ovn_abi_version(void);
 
 /* Last error message of the calling thread ("" if none). */
@@ -202,6 +202,21 @@ int ovn_get_head_pipeline(ovn_ctx* ctx, int64_t* chunk_pairs, int64_t* sub_chunk
  * Ranks of a sharded sweep exchange these 16-byte records instead of N scores (overlapnet_amd/distributed.py). */
 int ovn_best_match(ovn_ctx* ctx, const float* overlap_dev, const int32_t* yaw_dev, const int32_t* ids_dev, int64_t n,
                    float threshold, int64_t index_offset, int32_t* out_dev, void* stream);
+
+/* The k best candidates of a 1-vs-N sweep, ranked on the device: what a back end checks geometrically before it accepts a loop
+ * closure, and what recall@k needs.  Arguments as for ovn_best_match; yaw_dev and ids_dev may be NULL.
+ *   k        1 .. OVN_TOP_K_MAX
+ *   out_dev  k x 4 int32, 16-byte aligned: record i = { id, float bits of overlap, yaw, 1 if overlap > threshold else 0 } of the
+ *            i-th best candidate, in ovn_best_match's format; each record is written with one 16-byte store
+ * Order: overlap descending; equal overlaps by position ascending (the index into overlap_dev, before ids_dev / index_offset
+ * apply: np.argmax's first maximum comes first); -0.0 and +0.0 are equal (a record keeps its element's own bits); +inf ranks
+ * first, -inf last; NaN is never selected.  With fewer than k non-NaN scores the remaining records are { -1, 0, 0, 0 } (all of
+ * them when n == 0).  The result is the same on every call, and for k == 1 it is bit for bit the record of ovn_best_match.
+ * Returns OVN_ERR_ARG for k outside 1..OVN_TOP_K_MAX, n outside [0, 2^31), index_offset + n >= 2^31, a NULL buffer
+ * (overlap_dev may be NULL only when n == 0) or a misaligned out_dev.  One workgroup, one launch, no scratch. */
+#define OVN_TOP_K_MAX 1024
+int ovn_top_k(ovn_ctx* ctx, const float* overlap_dev, const int32_t* yaw_dev, const int32_t* ids_dev, int64_t n, int k,
+              float threshold, int64_t index_offset, int32_t* out_dev, void* stream);
 
 /* Spherical projection + normals for a batch of scans (src/utils/utils.py:59-134 range_projection and
  * :137-186 gen_normal_map; the drivers gen_depth_data.py:24-46 etc. loop over files and call these).

@@ -708,6 +708,18 @@ int ovn_best_match(ovn_ctx* ctx, const float* overlap, const int32_t* yaw, const
   return ovn_best_match_forward(overlap, yaw, ids, (int)n, threshold, (int)index_offset, out, (hipStream_t)stream);
 }
 
+int ovn_top_k(ovn_ctx* ctx, const float* overlap, const int32_t* yaw, const int32_t* ids, int64_t n, int k, float threshold,
+              int64_t index_offset, int32_t* out, void* stream) {
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_top_k: ctx is NULL");
+  OVN_REQUIRE(k >= 1 && k <= OVN_TOP_K_MAX, OVN_ERR_ARG, "ovn_top_k: k must be in 1..OVN_TOP_K_MAX (1024)");
+  OVN_REQUIRE(n >= 0 && n < (1ll << 31), OVN_ERR_ARG, "ovn_top_k: bad n");
+  OVN_REQUIRE(index_offset >= 0 && index_offset + n < (1ll << 31), OVN_ERR_ARG, "ovn_top_k: bad index_offset");
+  OVN_REQUIRE(out != nullptr && (n == 0 || overlap != nullptr), OVN_ERR_ARG, "ovn_top_k: NULL buffer");
+  OVN_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0, OVN_ERR_ARG, "ovn_top_k: out_dev is not 16-byte aligned");
+  OVN_ON_DEVICE(ctx->device);
+  return ovn_top_k_forward(overlap, yaw, ids, (int)n, k, threshold, (int)index_offset, out, (hipStream_t)stream);
+}
+
 int ovn_project(ovn_ctx* ctx, const float* points_dev, const int64_t* offsets_dev, int n_scans,
                 int64_t max_points_per_scan, int proj_h, int proj_w, double fov_up_deg, double fov_down_deg,
                 double max_range, float* range_dev, float* vertex_dev, float* intensity_dev, int32_t* idx_dev,

@@ -200,6 +200,22 @@ def merge_matches_by_position(records) -> "torch.Tensor":
     return best[1].clone()
 
 
+def merge_top_k_by_position(records, k: int) -> "torch.Tensor":
+    """Global top-k of per-rank top-k lists ((world, k, 4) int32 records of `OvnEngine.top_k`) whose id field is the POSITION of the
+    candidate in the caller's reference list (shares of a list under `frame_owner`): the k-record analogue of
+    `merge_matches_by_position`, in the same order as the kernel -- overlap descending, lower position first on ties, -0 == +0.
+    Rows with id < 0 are empty.  Returns (k, 4) int32, padded with {-1, 0, 0, 0}."""
+    rec = torch.as_tensor(records).reshape(-1, 4).to(torch.int32).cpu().numpy()
+    rec = rec[rec[:, 0] >= 0]
+    ov = rec[:, 1].copy().view(np.float32)
+    rec, ov = rec[~np.isnan(ov)], ov[~np.isnan(ov)]
+    by_pos = np.argsort(rec[:, 0], kind="stable")
+    order = by_pos[np.argsort(-(ov[by_pos] + np.float32(0)), kind="stable")][:int(k)]      # (+0: -0 -> +0, then equal)
+    out = np.tile(np.array([-1, 0, 0, 0], np.int32), (int(k), 1))
+    out[:len(order)] = rec[order]
+    return torch.from_numpy(out)
+
+
 def allgather_records(record: torch.Tensor, group=None) -> torch.Tensor:
     """(world, 4) int32: every rank's 16-byte best-match record.  The `found` field (word 3) of a rank whose local work failed
     carries a negative status instead (see `Infer._infer_best_match_sharded`): every rank sees it in the same payload."""

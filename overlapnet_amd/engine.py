@@ -7,7 +7,7 @@ math or to the CPU oracle.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -400,6 +400,28 @@ class OvnEngine:
                 return view.copy()            # (a NumPy record: `decode_match` takes it as it is)
         return out
 
+    def top_k(self, overlap: torch.Tensor, yaw: Optional[torch.Tensor] = None, k: int = 5, threshold: float = 0.3,
+              ids: Optional[torch.Tensor] = None, index_offset: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The k best candidates of a 1-vs-N sweep, ranked on the device (`ovn_top_k`): a (k, 4) int32 device tensor of
+        best-match records, best first -- overlap descending, equal overlaps by position ascending, -0 == +0, NaN never selected,
+        {-1, 0, 0, 0} past the last non-NaN score.  k = 1 gives `best_match`'s record bit for bit.  Decode with `decode_top_k`.
+        `out` (optional): a contiguous int32 device tensor of k x 4 elements, 16-byte aligned (the library checks)."""
+        n = int(overlap.numel())
+        for t, what, dt in ((overlap, "overlap", torch.float32), (yaw, "yaw", torch.int32), (ids, "ids", torch.int32)):
+            if t is None:
+                continue
+            if t.device != self.device or t.dtype != dt or not t.is_contiguous() or t.numel() != n:
+                raise _lib.OvnError("%s must be a contiguous %s tensor of %d elements on %s" % (what, dt, n, self.device))
+        k = int(k)
+        if out is None:
+            out = torch.empty((max(k, 0), 4), dtype=torch.int32, device=self.device)
+        elif out.device != self.device or out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != 4 * k:
+            raise _lib.OvnError("out must be a contiguous int32 tensor of %d elements on %s" % (4 * k, self.device))
+        with self._dev():
+            _lib.check(self.lib.ovn_top_k(self._h, _ptr(overlap), _ptr(yaw), _ptr(ids), n, k, float(threshold), int(index_offset),
+                                          _ptr(out), self._stream()), "ovn_top_k")
+        return out
+
     # -- preprocessing ------------------------------------------------------------------------------
     def project(self, points: torch.Tensor, offsets: torch.Tensor, max_points: int, proj_h: int = 64,
                 proj_w: int = 900, fov_up: float = 3.0, fov_down: float = -25.0, max_range: float = 50.0,
@@ -709,3 +731,10 @@ def decode_match(record) -> Optional[Tuple[int, float, int]]:
     if r[3] == 0 or r[0] < 0:
         return None
     return int(r[0]), float(r[1:2].view(np.float32)[0]), int(r[2])
+
+
+def decode_top_k(records) -> List[Tuple[int, float, int, bool]]:
+    """[(candidate id, overlap, yaw, overlap > threshold)] from top-k records, best first; the {-1, 0, 0, 0} rows are dropped."""
+    r = np.asarray(records.cpu() if hasattr(records, "cpu") else records, dtype=np.int32).reshape(-1, 4)
+    ov = r[:, 1].copy().view(np.float32)
+    return [(int(r[i, 0]), float(ov[i]), int(r[i, 2]), bool(r[i, 3] > 0)) for i in range(len(r)) if r[i, 0] >= 0]

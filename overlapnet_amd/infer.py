@@ -18,7 +18,8 @@ types and error behaviour; the Keras/TensorFlow models behind it are replaced by
     trained with; both keys are optional extensions, any other value raises ValueError before a GPU is touched;
   * `pretrained_weightsfilename` may name a native `.npz` (keys `<layer>/kernel|bias`) besides the
     Keras HDF5 file (read by the built-in `hdf5_lite` parser);
-  * `infer_best_match` (extension): `infer_multiple` + demo3's decision taken on the GPU;
+  * `infer_best_match` (extension): `infer_multiple` + demo3's decision taken on the GPU; `infer_top_k` (extension): the k best
+    candidates, ranked on the GPU;
   * `config['scan_folder']` (extension key): read the RAW scans `<scan_folder>/<frame>.bin` and project them on the GPU
     (`ovn_project`: range image + normals + intensity straight into the stacked leg input) instead of reading demo1's `.npy`
     files -- demo1 + demo2/demo3 in one object (BASELINE configs[4]); same bits as the `.npy` route on files written by
@@ -39,6 +40,8 @@ import torch
 from . import weights as W
 from ._lib import OvnError
 from .engine import FEAT_C, FEAT_W, OvnEngine
+
+TOP_K_MAX = 1024      # OVN_TOP_K_MAX of include/ovn_hip.h
 
 _VALID_LEGS = ("360OutputkLegs", "360OutputkLegsFixed")       # generateNet.py:119,222
 
@@ -805,6 +808,71 @@ class Infer():
     if got is None:
       return None
     return int(ref[got[0]]), got[1], got[2]
+
+  def _infer_top_k_sharded(self, current_frame_id, reference_frame_id, k, overlap_thres):
+    """Each rank ranks the references it owns (ids = their positions in the list); ONE all-gather of k x 16 B per rank, merged in
+    the kernel's order; a rank whose local work failed marks word 3 of its first record < 0, as `_infer_best_match_sharded` does."""
+    from . import distributed as D
+    from .engine import decode_top_k
+    fid = self._check_sharded_frame(current_frame_id)
+    ref, owner, mine = self._sharded_refs(reference_frame_id)
+    dev = self.engine.device
+    thr = float('-inf') if overlap_thres is None else overlap_thres
+    err, rec = None, None
+    try:
+      q_fv, q_spec = self._query_frame_sharded(fid)
+      if len(ref):
+        r = self._local_heads_sharded(ref, mine, q_fv, q_spec)
+        if r is not None:
+          pos = torch.from_numpy(np.nonzero(mine)[0].astype(np.int32)).to(dev)
+          rec = self.engine.top_k(r["overlap"], r["yaw"], k, thr, ids=pos)
+    except Exception as e:                    # noqa: BLE001
+      err = e
+    if len(ref) == 0:
+      self._agree_frame_cached(err)
+      if err is None:
+        self._start_ahead(current_frame_id)
+      return []
+    if err is not None or rec is None:
+      rec = torch.tensor([[-1, 0, 0, 0]] * k, dtype=torch.int32, device=dev)
+      if err is not None:
+        rec[0, 3] = -1                        # word 3 < 0: this rank failed
+    if err is None:
+      self._start_ahead(current_frame_id)
+    recs = D.allgather_records(rec, self._group).reshape(-1, k, 4)
+    self._frame_done((recs[:, 0, 3] < 0).numpy(), err)
+    got = decode_top_k(D.merge_top_k_by_position(recs, k))
+    return [(int(ref[p]), ov, yw) for p, ov, yw, above in got if overlap_thres is None or above]
+
+  def infer_top_k(self, current_frame_id, reference_frame_id, k=5, overlap_thres=0.3):
+    """ Addition to the reference API: the k best loop-closure candidates of `infer_multiple`'s sweep, ranked on the GPU
+        (`ovn_top_k`), so only k records cross PCIe instead of N scores -- what a back end checks geometrically before it accepts
+        a loop closure, and what recall@k needs.  Returns up to k (reference frame id, overlap, yaw), best first: overlap
+        descending, equal overlaps in list order, NaN never; only overlaps > `overlap_thres` (None keeps every score).  Caches
+        the current frame like `infer_multiple`; an empty reference list returns [].  k = 1 gives `[infer_best_match(...)]`
+        (or [] where that is None). """
+    from .engine import decode_top_k
+    k = int(k)
+    if not 1 <= k <= TOP_K_MAX:
+      raise ValueError('k must be in 1..%d, got %d' % (TOP_K_MAX, k))
+    if self._world > 1:
+      return self._infer_top_k_sharded(current_frame_id, reference_frame_id, k, overlap_thres)
+    self._cache_frame(str(current_frame_id).zfill(6))
+    if len(reference_frame_id) == 0:
+      return []
+    ref = np.asarray(reference_frame_id, dtype=np.int64).reshape(-1)
+    n = len(self.feature_volumes)
+    if ref.min() < 0 or max(int(ref.max()), int(current_frame_id)) >= n:
+      raise IndexError('index %d is out of bounds for axis 0 with size %d' % (int(ref.max()), n))
+    pair_indizes = np.zeros((len(ref), 2), dtype=np.int64)
+    pair_indizes[:, 0] = ref
+    pair_indizes[:, 1] = int(current_frame_id)
+    r = self._heads_device(self.feature_volumes, pair_indizes)
+    ids = torch.from_numpy(ref.astype(np.int32)).to(self.engine.device)
+    thr = float('-inf') if overlap_thres is None else overlap_thres
+    rec = self.engine.top_k(r["overlap"], r["yaw"], k, thr, ids=ids)
+    self._start_ahead(current_frame_id)     # next frame's files, copy and leg in the shadow of the kernels just enqueued
+    return [(i, ov, yw) for i, ov, yw, above in decode_top_k(rec) if overlap_thres is None or above]
 
   def infer_multiple(self, current_frame_id, reference_frame_id):
     """ Loop closing: current frame vs old frames (infer.py:162-203).  The current frame's feature

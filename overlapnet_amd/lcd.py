@@ -11,7 +11,7 @@ make_lcd_golden.py) for three synthetic trajectories, and requires equality (tes
 """
 from __future__ import annotations
 
-from typing import Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -67,6 +67,24 @@ def decide(reference_idx: Sequence[int], overlaps, yaws, overlap_thres: float = 
     if overlaps[k] > overlap_thres:
         return int(np.asarray(reference_idx)[k]), float(overlaps[k]), int(yaws[k])
     return None
+
+
+def decide_top_k(reference_idx: Sequence[int], overlaps, yaws, k: int = 5,
+                 overlap_thres: Optional[float] = 0.3) -> List[Tuple[int, float, int]]:
+    """Up to k (frame id, overlap, yaw), best first -- the ranked form of `decide`: overlap descending, equal overlaps in list
+    order (np.argmax's first maximum comes first), -0 == +0, NaN dropped; only overlaps > `overlap_thres` (None keeps every
+    non-NaN score).  The threshold is compared in the overlaps' own precision (float32 for the library's outputs), as on the GPU.
+    The host statement of `Infer.infer_top_k` / `ovn_top_k`."""
+    ov = np.atleast_1d(np.asarray(overlaps))
+    yaws = np.atleast_1d(np.asarray(yaws))
+    ref = np.asarray(reference_idx).reshape(-1)
+    if len(ref) == 0 or ov.size == 0:
+        return []
+    pos = np.nonzero(~np.isnan(ov))[0]
+    order = pos[np.argsort(-(ov[pos] + ov.dtype.type(0)), kind="stable")][:max(int(k), 0)]    # (+0: -0 -> +0, then equal)
+    if overlap_thres is not None:
+        order = order[ov[order] > np.asarray(overlap_thres, dtype=ov.dtype)]
+    return [(int(ref[i]), float(ov[i]), int(yaws[i])) for i in order]
 
 
 def detect(infer, idx: int, traj_xy: np.ndarray, traj_length: np.ndarray, ellipse, **gate_kw):
