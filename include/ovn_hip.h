@@ -39,7 +39,7 @@ typedef struct ovn_ctx ovn_ctx;
 #define OVN_ERR_STATE 3    /* call order (weights missing ...)  */
 
 /* ABI version of this header; bumped on any signature change. */
-#define OVN_ABI_VERSION 10
+#define OVN_ABI_VERSION 11
 int ovn_abi_version(void);
 
 /* Last error message of the calling thread ("" if none). */
@@ -173,6 +173,36 @@ int ovn_heads_spectral(ovn_ctx* ctx, const float* feats_l_dev, const float* spec
                        const int32_t* lidx_dev, const float* feats_r_dev, const float* spec_r_dev, const int32_t* ridx_dev, int64_t n,
                        float* overlap_dev, int32_t* yaw_dev, float* logit_dev, float* corr_dev, void* stream);
 
+/* Both heads on a batch of B loop-closure queries, each with its own candidate list (a SEGMENT), in one call: the offline form of
+ * B calls of ovn_heads_spectral (or ovn_heads, without spectra) in their 1-vs-N form.  The batch is stored like a CSR matrix:
+ *   seg_offsets  HOST array, B + 1 int64: seg_offsets[0] == 0, non-decreasing, seg_offsets[B] == n; segment b is the pairs
+ *                [seg_offsets[b], seg_offsets[b + 1]) (empty segments are allowed)
+ *   query_idx    HOST array, B int32 >= 0: segment b's query is feats_q_dev[query_idx[b]] (spec_q_dev alike)
+ *   cand_idx_dev DEVICE array, n int32: pair p's candidate is feats_pool_dev[cand_idx[p]] (spec_pool_dev, dcache_pool_dev alike)
+ * Pair p of segment b = (left = pool[cand_idx[p]], right = queries[query_idx[b]]): candidate -> head-left, query -> head-right, the
+ * orientation of Infer.infer_multiple.  The two pools may be the same tensors.  spec_pool_dev / spec_q_dev: both or neither (360
+ * columns only); dcache_pool_dev may be NULL.  Outputs are flat (n), in pair order, as in ovn_heads.
+ * Contract: pair p gets the bits ovn_heads_spectral (ovn_heads without spectra) returns for it when segment b is run alone in its
+ * 1-vs-N form -- lidx = cand_idx[seg_offsets[b] ..], ridx NULL, feats_r = the query -- with the same pools, settings and precision mode.
+ * Route: in the f16x3 mode at W = 360 with conv1size 15 and compaction on, the batch runs in passes of at most the head chunk
+ * (ovn_set_head_pipeline) and OVN_SEG_PASS_MAX segments.  A pass computes each segment's query state once, in one launch per kernel
+ * for all its segments (A2, the query block, the live-channel list, the W1 fragments gathered for it); the prepare and contraction
+ * kernels find a pair's through its segment.  All segments of a pass share one kernel chain.  Every other mode and geometry, and
+ * f16x3 with compaction off (its 1-vs-N walk is the indexed walk), runs one indexed pass over all pairs.  The per-pair query and
+ * segment indices come from one small kernel over the staged table.
+ * Argument errors return OVN_ERR_ARG before any launch: B outside [0, 2^31), bad offsets, n != seg_offsets[B], a negative
+ * query_idx, spec_* given alone, misaligned pointers (4 bytes; dcache_pool_dev 16).  The library does not range-check the device
+ * array cand_idx_dev or query_idx's upper end against the pools (as with lidx / ridx of ovn_heads): the caller does.
+ * n == 0 is a no-op.  Workspace (ovn_workspace_bytes): that of a head call over one chunk, plus 2 MB of query state per segment of a
+ * pass (at most OVN_SEG_PASS_MAX x 2 MB), plus a context-owned table of 8 (B + 1) + 4 B + 8 n bytes on the device and 8 (B + 1) + 4 B
+ * in pinned host memory.  The host arrays may be reused as soon as the call returns.  Successive segmented calls may use different
+ * streams: each waits for the previous one's kernels before it rewrites the table. */
+int ovn_heads_segments(ovn_ctx* ctx, const float* feats_pool_dev, const float* spec_pool_dev, const float* dcache_pool_dev,
+                       const int32_t* cand_idx_dev, const float* feats_q_dev, const float* spec_q_dev, const int32_t* query_idx,
+                       const int64_t* seg_offsets, int64_t B, int64_t n, float* overlap_dev, int32_t* yaw_dev, float* logit_dev,
+                       float* corr_dev, void* stream);
+#define OVN_SEG_PASS_MAX 128
+
 /* Launch structure of the head calls (the reference's counterpart is `batch_size`, network.yml:41, which sets how many pairs one
  * predict step materialises):
  *   chunk_pairs          pairs per pass over the context's scratch (default 1024).  The f16x3 Delta path needs 2.9 MB of scratch
@@ -217,6 +247,17 @@ int ovn_best_match(ovn_ctx* ctx, const float* overlap_dev, const int32_t* yaw_de
 #define OVN_TOP_K_MAX 1024
 int ovn_top_k(ovn_ctx* ctx, const float* overlap_dev, const int32_t* yaw_dev, const int32_t* ids_dev, int64_t n, int k,
               float threshold, int64_t index_offset, int32_t* out_dev, void* stream);
+
+/* ovn_top_k of every segment of a batch (ovn_heads_segments' layout), one workgroup per segment, in one launch, no scratch.
+ *   seg_offsets  HOST array, B + 1 int64, as in ovn_heads_segments (n = seg_offsets[B] scores in overlap_dev / yaw_dev / ids_dev)
+ *   out_dev      B x k x 4 int32, 16-byte aligned: segment b's k records at out_dev + 4 k b
+ * Segment b's records are bit for bit those of ovn_top_k on its slice (overlap_dev + seg_offsets[b], yaw_dev / ids_dev sliced the
+ * same way, index_offset 0): a NULL ids_dev means the position inside the segment; k = 1 is ovn_best_match's record; an empty
+ * segment gives k records { -1, 0, 0, 0 }.  A segment costs the time ovn_top_k takes on it.  OVN_ERR_ARG for k outside
+ * 1..OVN_TOP_K_MAX, bad offsets, a NULL or misaligned buffer.  B == 0 is a no-op.  Workspace: the context's segment table
+ * (8 (B + 1) bytes, see ovn_heads_segments). */
+int ovn_top_k_segments(ovn_ctx* ctx, const float* overlap_dev, const int32_t* yaw_dev, const int32_t* ids_dev,
+                       const int64_t* seg_offsets, int64_t B, int k, float threshold, int32_t* out_dev, void* stream);
 
 /* Spherical projection + normals for a batch of scans (src/utils/utils.py:59-134 range_projection and
  * :137-186 gen_normal_map; the drivers gen_depth_data.py:24-46 etc. loop over files and call these).

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OVN_LIB") or os.path.join(_HERE, "libovn_hip.so")
 CSRC_DIR = os.path.join(_HERE, "csrc")
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 _f32p = C.POINTER(C.c_float)
 _i32p = C.POINTER(C.c_int32)
@@ -42,6 +42,9 @@ SIGNATURES = {
     "ovn_get_head_pipeline": (C.c_int, [_vp, _i64p, _i64p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ovn_best_match": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_float, C.c_int64, _vp, _vp]),
     "ovn_top_k": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int, C.c_float, C.c_int64, _vp, _vp]),
+    "ovn_heads_segments": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32p, _i64p, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp,
+                                     _vp]),
+    "ovn_top_k_segments": (C.c_int, [_vp, _vp, _vp, _vp, _i64p, C.c_int64, C.c_int, C.c_float, _vp, _vp]),
     "ovn_project": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double,
                               C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     "ovn_normals": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),

@@ -417,6 +417,7 @@ constexpr size_t QBLOCK_WORDS = (size_t)QV * OVN_FEAT_ELEMS + G * O2 + 4;
 // -- and any pair that needs a shift (negative values: r' = r + c has no zeros) -- walks exactly the K of rounds 2-4.
 constexpr int NPAIR = G / 2;               // column-group pairs (the passes of the contraction kernel)
 constexpr int LIVE_WORDS = 4 + FC / 4 + 4; // {largest slice count, live channels, 0, 0} | 128 channel bytes: position 32 s + 8 g + e of the
+constexpr size_t W1C_HALFS = (size_t)S * FC * O1 * 2;   // W1 fragments gathered for a query's live list (hi + lo), at most all 128 channels
                                            // compacted walk | slices to walk for column groups 2 p, 2 p + 1 (12 bytes, + 4 of padding)
 constexpr int CHAN_BYTES = FC + 16;        // the table in LDS: channel bytes + per-pair slice counts + the packed last slice (below)
 // The LAST slice of a compacted walk, when it holds n <= 16 live channels, is packed TAP-MAJOR: a step then carries T = 32 / n taps of
@@ -618,7 +619,9 @@ __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
 // sweeps) checks exactly that condition per pair and, when it holds, only writes the pair's scales and its operand descriptor
 // (cache row + the query's shared block); otherwise it prepares the pair in scratch as before.  Both routes give the same bits:
 // the scales are functions of the power-of-two bucket of the pair's largest value, never of the value itself.
-template <bool BUILD>
+// SEG (ovn_heads_segments): pair p belongs to segment pseg[p]; its query's state (a2raw, query block, live list) is entry pseg[p] - seg0
+// of the pass's arrays, ridx[p] is its query's index in feats_r.
+template <bool BUILD, bool SEG = false>
 __global__ __launch_bounds__(512) void delta_prepare_split_kernel(
     const float* __restrict__ feats_l, const int32_t* __restrict__ lidx, const float* __restrict__ feats_r,
     const int32_t* __restrict__ ridx, const _Float16* __restrict__ wsp, const float* __restrict__ w1col,
@@ -626,7 +629,7 @@ __global__ __launch_bounds__(512) void delta_prepare_split_kernel(
     const float* __restrict__ w2sum, const float* __restrict__ b2, float sw1, float sw2, float sws, float w1_colsum, float b1_absmax,
     float one, f32x4* __restrict__ scales, unsigned* __restrict__ o2max, unsigned* __restrict__ pl, unsigned* __restrict__ pr,
     float* __restrict__ lin, DeltaDesc* __restrict__ desc, const float* __restrict__ dcache, const unsigned* __restrict__ qblock,
-    float* __restrict__ cache_out, const unsigned* __restrict__ live) {
+    float* __restrict__ cache_out, const unsigned* __restrict__ live, const int32_t* __restrict__ pseg = nullptr, int seg0 = 0) {
   extern __shared__ __attribute__((aligned(16))) unsigned char psm[];
   __shared__ __attribute__((aligned(16))) unsigned char chan_p[CHAN_BYTES];
   // T image, scaled fp16 hi / lo: T[15 ib + di][o] at [ib][di * 64 + 4 (o & 15) + (o >> 4)] (the K order of W2p)
@@ -640,6 +643,12 @@ __global__ __launch_bounds__(512) void delta_prepare_split_kernel(
   const int lane = tid & 63, wave = tid >> 6;
   const int lrow = lane & 15, g = lane >> 4;
   const long long cand = lidx ? lidx[pair] : pair;
+  if constexpr (SEG) {   // workgroup-uniform
+    const int sg = pseg[pair] - seg0;
+    qblock += (size_t)sg * QBLOCK_WORDS;
+    live += (size_t)sg * LIVE_WORDS;
+    a2raw += (size_t)sg * A2_KSPLIT * A2_ELEMS;
+  }
   if (!BUILD && dcache) {   // workgroup-uniform: is the candidate's cache row valid for this query?
     const float* row = dcache + cand * OVN_DELTA_CACHE_ELEMS;
     const float* qm = reinterpret_cast<const float*>(qblock + (size_t)QV * OVN_FEAT_ELEMS + G * O2);
@@ -695,7 +704,7 @@ __global__ __launch_bounds__(512) void delta_prepare_split_kernel(
   for (int q = 0; q < 4; ++q) wsv[q] = reinterpret_cast<const f32x4*>(wsp)[tid + 512 * q];
   float a2v[3][A2_KSPLIT] = {};
   if (!BUILD) {
-    const float* src = a2raw + (size_t)(ridx ? pair : 0) * A2_KSPLIT * A2_ELEMS;
+    const float* src = a2raw + (size_t)((!SEG && ridx) ? pair : 0) * A2_KSPLIT * A2_ELEMS;
 #pragma unroll
     for (int u = 0; u < 3; ++u)
 #pragma unroll
@@ -952,10 +961,23 @@ __global__ __launch_bounds__(512) void delta_prepare_split_kernel(
 // The query's side of a cached 1-vs-N sweep, once per call: workgroup v packs the query's words at scale sa_q / 2^v (the version a
 // candidate whose own scale is that much coarser pairs with); workgroup 0 also leaves AA = (R W1) W2s and {max R, min R}.
 // Same arithmetic, in the same order, as the R / AA parts of delta_prepare_split_kernel with shift c = 0.
+// SEG (ovn_heads_segments): blockIdx.y = segment seg0 + y of a pass; its query is feats_r[qidx[seg0 + y]], its state (a2raw, the query
+// block, the live list, the gathered W1 fragments) the y-th of each array.  An empty segment has nothing to prepare.
+template <bool SEG>
 __global__ __launch_bounds__(512) void delta_query_kernel(const float* __restrict__ feats_r, const float* __restrict__ a2raw,
                                                           const float* __restrict__ w2sum, unsigned* __restrict__ qblock,
                                                           unsigned* __restrict__ live_out, const _Float16* __restrict__ w1p,
-                                                          _Float16* __restrict__ w1c) {
+                                                          _Float16* __restrict__ w1c, const int32_t* __restrict__ qidx,
+                                                          const int64_t* __restrict__ offs, int seg0) {
+  if constexpr (SEG) {
+    const int y = blockIdx.y, b = seg0 + y;
+    if (offs[b + 1] == offs[b]) return;
+    feats_r += (size_t)qidx[b] * OVN_FEAT_ELEMS;
+    a2raw += (size_t)y * A2_KSPLIT * A2_ELEMS;
+    qblock += (size_t)y * QBLOCK_WORDS;
+    live_out += (size_t)y * LIVE_WORDS;
+    w1c += (size_t)y * W1C_HALFS;
+  }
   __shared__ float red[2 * NWAVE];
   __shared__ float A2l[G * O1];
   __shared__ int alive2[NPAIR][FC];
@@ -1320,11 +1342,13 @@ constexpr size_t t_lds_bytes(int spc, int planes = 2) {
 
 // AR = ArithF16x3 (packed words, scaled fp16 hi/lo) or ArithBF16x3 (raw fp32 words of the volumes, three bf16 planes of W1: 1.5x the
 // W1 window, twice the MFMAs; no compaction, so `live` is NULL).  Same walk, same DMA streams, same output rows.
-template <class AR, int RT, int T_SPC>
+// SEG (ovn_heads_segments): the pair's live list and gathered W1 fragments are entry pseg[pair] - seg0 of the pass's arrays.
+template <class AR, int RT, int T_SPC, bool SEG = false>
 __global__ __launch_bounds__(512) void delta_c1_kernel(const DeltaDesc* __restrict__ desc, const void* __restrict__ w1p,
                                                        const f32x4* __restrict__ scales, float* __restrict__ o1raw, int rot,
                                                        int nsplit, int pair0, const int32_t* __restrict__ lidx,
-                                                       const unsigned* __restrict__ live, const void* __restrict__ w1c) {
+                                                       const unsigned* __restrict__ live, const void* __restrict__ w1c,
+                                                       const int32_t* __restrict__ pseg = nullptr, int seg0 = 0) {
   typedef typename AR::frag frag;
   constexpr int NPL = AR::PLANES;
   constexpr int STEPB = NPL * (STEP_BYTES / 2);  // W1 fragments of one MFMA step: [nt(4)][plane][lane(64)][16 B]
@@ -1345,6 +1369,11 @@ __global__ __launch_bounds__(512) void delta_c1_kernel(const DeltaDesc* __restri
 
   const int pair = blockIdx.x / nsplit;
   const int part = blockIdx.x - pair * nsplit;
+  if constexpr (SEG) {   // workgroup-uniform
+    const int sg = __builtin_amdgcn_readfirstlane(pseg[pair] - seg0);
+    live += (size_t)sg * LIVE_WORDS;
+    w1c = reinterpret_cast<const _Float16*>(w1c) + (size_t)sg * W1C_HALFS;
+  }
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1710,6 +1739,13 @@ size_t ovn_delta_f16x3_scratch_bytes(int n, bool per_pair_right) {
          al(LIVE_WORDS * sizeof(unsigned)) + al((size_t)S * FC * O1 * 2 * sizeof(_Float16));
 }
 
+// per-segment query state of a segmented pass: A2raw, query block, live list, gathered W1 fragments per segment
+size_t ovn_delta_f16x3_seg_bytes(int nseg) {
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  return al((size_t)nseg * A2_KSPLIT * A2_ELEMS * sizeof(float)) + al((size_t)nseg * QBLOCK_WORDS * sizeof(unsigned)) +
+         al((size_t)nseg * LIVE_WORDS * sizeof(unsigned)) + al((size_t)nseg * W1C_HALFS * sizeof(_Float16));
+}
+
 static int pick_nsplit(int n) {
   // divisors of the 12 passes (11 of two row tiles + the short one): time ~ rounds of workgroups over the 256 CUs x 1/d of a pair's
   // work; the smallest d within 5 % of the best (big sweeps keep d = 1: one workgroup per pair).  d = 23 (ONE row tile per pass, 22 + 1
@@ -1729,30 +1765,39 @@ static int pick_nsplit(int n) {
 
 // the contraction kernel for n pairs split nsplit ways (pick_nsplit): 45 / 23 = 8-row / one-row-tile passes, one per workgroup; the
 // passes of a pair are independent, so any split (and RT 0 / 1 / 2) gives the same bits
-template <class AR>
-static int launch_c1(int n, int nsplit, const DeltaDesc* desc, const void* w1, const f32x4* scales, float* o1raw, int pair0,
-                     const int32_t* lidx, const unsigned* live, const void* w1c, hipStream_t stream) {
+template <class AR, bool SEG>
+static int launch_c1_t(int n, int nsplit, const DeltaDesc* desc, const void* w1, const f32x4* scales, float* o1raw, int pair0,
+                       const int32_t* lidx, const unsigned* live, const void* w1c, hipStream_t stream, const int32_t* pseg, int seg0) {
   const size_t lds = t_lds_bytes(3, AR::PLANES);
   int rc = OVN_OK;
   if (nsplit == 45) {   // up to five pairs: 8-row passes, one per workgroup
-    rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_c1_kernel<AR, 0, 3>), lds);
+    rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_c1_kernel<AR, 0, 3, SEG>), lds);
     if (rc) return rc;
-    hipLaunchKernelGGL((delta_c1_kernel<AR, 0, 3>), dim3(n * nsplit), dim3(512), lds, stream, desc, w1, scales, o1raw, 1, nsplit, pair0, lidx, live, w1c);
+    hipLaunchKernelGGL((delta_c1_kernel<AR, 0, 3, SEG>), dim3(n * nsplit), dim3(512), lds, stream, desc, w1, scales, o1raw, 1, nsplit, pair0,
+                       lidx, live, w1c, pseg, seg0);
     return OVN_OK;
   }
   if constexpr (AR::MAX_RT >= 2) {
     if (nsplit != 23) {
-      rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_c1_kernel<AR, 2, 3>), lds);
+      rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_c1_kernel<AR, 2, 3, SEG>), lds);
       if (rc) return rc;
-      hipLaunchKernelGGL((delta_c1_kernel<AR, 2, 3>), dim3(n * nsplit), dim3(512), lds, stream, desc, w1, scales, o1raw, 1, nsplit, pair0, lidx, live, w1c);
+      hipLaunchKernelGGL((delta_c1_kernel<AR, 2, 3, SEG>), dim3(n * nsplit), dim3(512), lds, stream, desc, w1, scales, o1raw, 1, nsplit,
+                         pair0, lidx, live, w1c, pseg, seg0);
       return OVN_OK;
     }
   }
   // one row tile per pass (22 + 1 passes): a handful of pairs, one pass per workgroup (nsplit 23) -- or every sweep when MAX_RT = 1
-  rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_c1_kernel<AR, 1, 3>), lds);
+  rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_c1_kernel<AR, 1, 3, SEG>), lds);
   if (rc) return rc;
-  hipLaunchKernelGGL((delta_c1_kernel<AR, 1, 3>), dim3(n * nsplit), dim3(512), lds, stream, desc, w1, scales, o1raw, 1, nsplit, pair0, lidx, live, w1c);
+  hipLaunchKernelGGL((delta_c1_kernel<AR, 1, 3, SEG>), dim3(n * nsplit), dim3(512), lds, stream, desc, w1, scales, o1raw, 1, nsplit, pair0,
+                     lidx, live, w1c, pseg, seg0);
   return OVN_OK;
+}
+
+template <class AR>
+static int launch_c1(int n, int nsplit, const DeltaDesc* desc, const void* w1, const f32x4* scales, float* o1raw, int pair0,
+                     const int32_t* lidx, const unsigned* live, const void* w1c, hipStream_t stream) {
+  return launch_c1_t<AR, false>(n, nsplit, desc, w1, scales, o1raw, pair0, lidx, live, w1c, stream, nullptr, 0);
 }
 
 template <class AR>
@@ -1775,11 +1820,72 @@ float* ovn_delta_f16x3_a2raw(void* scratch, int n) {
   return reinterpret_cast<float*>(p);
 }
 
+// Segmented pass (ovn_heads_segments, compaction on): the pairs of several segments, pair p = (feats_l[lidx[p]], feats_r[ridx[p]]) in
+// segment seg.pseg[p].  Each segment's query state -- A2, the query block, the live list and the W1 fragments gathered for it -- is
+// computed ONCE, for all segments of the pass in one launch each; the prepare and contraction kernels find a pair's through pseg.
+// Every pair then runs exactly what its segment's 1-vs-N sweep runs for it (same scales, same compacted K walk rotated by the
+// candidate's slot, same cache-row rule): the same bits.
+static int delta_c12_f16x3_segments(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx,
+                                    int n, void* scratch, unsigned** o2max_out, float* o2, hipStream_t stream, const float* dcache_l,
+                                    const OvnSegPass& seg) {
+  int rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_prepare_split_kernel<false, true>), PREP_SPLIT_LDS);
+  if (rc) return rc;
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  char* p = static_cast<char*>(scratch);
+  f32x4* scales = reinterpret_cast<f32x4*>(p);
+  p += al((size_t)n * 8 * sizeof(float));
+  unsigned* o2max = reinterpret_cast<unsigned*>(p);
+  p += al((size_t)n * sizeof(unsigned));
+  unsigned* pl = reinterpret_cast<unsigned*>(p);
+  p += al((size_t)n * OVN_FEAT_ELEMS * sizeof(unsigned));
+  unsigned* pr = reinterpret_cast<unsigned*>(p);
+  p += al((size_t)n * OVN_FEAT_ELEMS * sizeof(unsigned));
+  float* lin = reinterpret_cast<float*>(p);
+  p += al((size_t)n * LIN_ELEMS * sizeof(float));
+  float* o1raw = reinterpret_cast<float*>(p);
+  p += al((size_t)n * O1RAW_ELEMS * sizeof(float));
+  DeltaDesc* desc = reinterpret_cast<DeltaDesc*>(p);
+  char* q = static_cast<char*>(seg.scratch);   // ovn_delta_f16x3_seg_bytes(seg.nseg)
+  float* a2raw = reinterpret_cast<float*>(q);
+  q += al((size_t)seg.nseg * A2_KSPLIT * A2_ELEMS * sizeof(float));
+  unsigned* qblock = reinterpret_cast<unsigned*>(q);
+  q += al((size_t)seg.nseg * QBLOCK_WORDS * sizeof(unsigned));
+  unsigned* live = reinterpret_cast<unsigned*>(q);
+  q += al((size_t)seg.nseg * LIVE_WORDS * sizeof(unsigned));
+  _Float16* w1c = reinterpret_cast<_Float16*>(q);
+  ctx->dbg_live = nullptr;   // (ovn_head_walk_stats describes 1-vs-N sweeps)
+  *o2max_out = o2max;
+  const int nsplit = pick_nsplit(n);
+  {
+    OvnProfScope ps(ctx, OVN_K_DELTA_PREP, stream);
+    hipLaunchKernelGGL(delta_a2_kernel, dim3(seg.nseg, A2_KSPLIT), dim3(512), 0, stream, feats_r, seg.qidx + seg.seg0, ctx->w1raw, a2raw);
+    hipLaunchKernelGGL(delta_query_kernel<true>, dim3(QV + QGW, seg.nseg), dim3(512), 0, stream, feats_r, a2raw, ctx->w2sum, qblock, live,
+                       reinterpret_cast<const _Float16*>(ctx->w1p_h), w1c, seg.qidx, seg.offs, seg.seg0);
+    hipLaunchKernelGGL((delta_prepare_split_kernel<false, true>), dim3(n), dim3(512), PREP_SPLIT_LDS, stream, feats_l, lidx, feats_r, ridx,
+                       reinterpret_cast<const _Float16*>(ctx->wsp_h), ctx->w1col, ctx->b1, a2raw,
+                       reinterpret_cast<const _Float16*>(ctx->w2p_h), ctx->w2sum, ctx->c2.bias, ctx->hs.sw1, ctx->hs.sw2, ctx->hs.sws,
+                       ctx->hs.w1_colsum, ctx->hs.b1_absmax, 1.0f, scales, o2max, pl, pr, lin, desc, dcache_l, qblock, (float*)nullptr, live,
+                       seg.pseg, seg.seg0);
+  }
+  {
+    OvnProfScope ps(ctx, OVN_K_DELTA, stream);
+    rc = launch_c1_t<ArithF16x3, true>(n, nsplit, desc, ctx->w1p_h, scales, o1raw, 0, lidx, live, w1c, stream, seg.pseg, seg.seg0);
+    if (rc) return rc;
+  }
+  {
+    OvnProfScope ps(ctx, OVN_K_DELTA_C2, stream);
+    launch_c2<ArithF16x3>(n, o1raw, ctx->w2p_h, desc, scales, o2, o2max, stream);
+  }
+  OVN_HIP_CHECK(hipGetLastError());
+  return OVN_OK;
+}
+
 int ovn_delta_c12_f16x3_forward(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r,
                                 const int32_t* ridx, int n, void* scratch, unsigned** o2max_out, float* o2, hipStream_t stream,
-                                int pair0, const float* dcache_l, bool a2_done) {
+                                int pair0, const float* dcache_l, bool a2_done, const OvnSegPass* seg) {
   int rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_prepare_split_kernel<false>), PREP_SPLIT_LDS);
   if (rc) return rc;
+  if (seg) return delta_c12_f16x3_segments(ctx, feats_l, lidx, feats_r, ridx, n, scratch, o2max_out, o2, stream, dcache_l, *seg);
   if (ridx) dcache_l = nullptr;   // the cache serves the 1-vs-N form (one query against many cached candidates)
   auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
   char* p = static_cast<char*>(scratch);
@@ -1815,8 +1921,9 @@ int ovn_delta_c12_f16x3_forward(ovn_ctx* ctx, const float* feats_l, const int32_
     if (!a2_done)
       hipLaunchKernelGGL(delta_a2_kernel, dim3(ridx ? n : 1, A2_KSPLIT), dim3(512), 0, stream, feats_r, ridx, ctx->w1raw, a2raw);
     if (dcache_l) {   // the query kernel also builds the live-channel list and gathers the W1 fragments for it
-      hipLaunchKernelGGL(delta_query_kernel, dim3(live ? QV + QGW : QV), dim3(512), 0, stream, feats_r, a2raw, ctx->w2sum, qblock, live ? live_buf : nullptr,
-                         reinterpret_cast<const _Float16*>(ctx->w1p_h), w1c);
+      hipLaunchKernelGGL(delta_query_kernel<false>, dim3(live ? QV + QGW : QV), dim3(512), 0, stream, feats_r, a2raw, ctx->w2sum, qblock,
+                         live ? live_buf : nullptr, reinterpret_cast<const _Float16*>(ctx->w1p_h), w1c, (const int32_t*)nullptr,
+                         (const int64_t*)nullptr, 0);
     } else if (live) {
       hipLaunchKernelGGL(delta_live_kernel, dim3(1), dim3(512), 0, stream, feats_r, live_buf);
       hipLaunchKernelGGL(delta_w1c_kernel, dim3(240), dim3(256), 0, stream, reinterpret_cast<const _Float16*>(ctx->w1p_h), live, w1c);

@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include "ovn_internal.h"
 
 int ovn_allow_dynamic_lds(const void* kernel, size_t bytes) {
@@ -122,6 +123,10 @@ int ovn_destroy(ovn_ctx* ctx) {
   if (ctx->norm_buf) (void)hipFree(ctx->norm_buf);
   if (ctx->actmax) (void)hipFree(ctx->actmax);
   if (ctx->c3_arrived) (void)hipFree(ctx->c3_arrived);
+  if (ctx->seg_dev) (void)hipFree(ctx->seg_dev);
+  if (ctx->seg_host) (void)hipHostFree(ctx->seg_host);
+  if (ctx->seg_ev) (void)hipEventDestroy(ctx->seg_ev);
+  if (ctx->seg_done) (void)hipEventDestroy(ctx->seg_done);
   if (ctx->aux_ready) {
     for (int i = 0; i < 2; ++i) {
       (void)hipStreamDestroy(ctx->aux[i]);
@@ -457,7 +462,8 @@ struct OvnFork {   // fork on construction-time request, join (on every exit pat
 // stream j % streams, so a region is only ever reused in stream order).
 static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r,
                           const int32_t* ridx, int64_t n, float* overlap, float* logit, int32_t* yaw, float* corr,
-                          int corr_mode, const float* spec_l, const float* spec_r, const float* dcache_l, hipStream_t stream) {
+                          int corr_mode, const float* spec_l, const float* spec_r, const float* dcache_l, hipStream_t stream,
+                          const OvnSegPass* seg = nullptr) {   // seg: a pass of ovn_heads_segments (f16x3 fused path only)
   ctx->dbg_live = nullptr;   // ovn_head_walk_stats describes THIS call (a sweep that compacts sets it again)
   const int fw = ctx_feat_w(ctx);
   const size_t feat_elems = (size_t)fw * OVN_FEAT_C;
@@ -513,7 +519,8 @@ static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lid
   const int64_t chunk = ctx->head_chunk;                        // pairs per pass over the scratch (f16x3: 3.2 MB per pair)
   const int64_t cmax = n < chunk ? n : chunk;
   // sub-chunks: only the f16x3 / bf16x3 kernels are split (the fp32 mode is one long kernel per chunk and keeps the round-2 structure)
-  int64_t sub = (split && ctx->head_sub > 0 && ctx->head_sub < cmax) ? ctx->head_sub : cmax;
+  // (a segmented pass keeps one sub-chunk: its per-segment query state is shared by all of its pairs)
+  int64_t sub = (split && !seg && ctx->head_sub > 0 && ctx->head_sub < cmax) ? ctx->head_sub : cmax;
   const int nsub_max = (int)((cmax + sub - 1) / sub);
   const int nstreams = (split && nsub_max > 1 && ctx->head_streams > 1) ? 2 : 1;
   auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
@@ -524,7 +531,8 @@ static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lid
   // f16x3 mode: per-pair scales, packed volumes, linear terms and the c_conv1 rows between the two Delta kernels (2.9 MB per pair),
   // one self-contained block per sub-chunk
   const size_t sc_sub = split ? al(ovn_delta_f16x3_scratch_bytes((int)sub, ridx != nullptr)) : 0;
-  int rc = ovn_ws_reserve(ctx, o2_bytes + o3_bytes + sc_sub * nsub_max, stream);
+  const size_t seg_bytes = seg ? al(ovn_delta_f16x3_seg_bytes(seg->nseg)) : 0;
+  int rc = ovn_ws_reserve(ctx, o2_bytes + o3_bytes + sc_sub * nsub_max + seg_bytes, stream);
   if (rc) return rc;
   if (fused && ctx->c3_arrived_n < chunk) {   // arrival counters of the fused c_conv3 + Dense kernel, one per pair of a chunk (sized
     OVN_HIP_CHECK(hipStreamSynchronize(stream));   // by the chunk, not by this call: a growing sweep must not re-allocate): zeroed
@@ -584,9 +592,16 @@ static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lid
       if (fused) {   // times its prepare kernels, the contraction kernel and c_conv2 separately
         unsigned* o2max = nullptr;
         float* part = o3 + (size_t)q0 * OVN_DENSE_PARTIALS;
+        OvnSegPass sp{};
+        if (seg) {
+          sp = *seg;
+          sp.pseg += p0;
+          sp.scratch = dscratch + sc_sub * nsub_max;
+        }
         rc = ovn_delta_c12_f16x3_forward(ctx, fl, li, feats_r, ri, np, dscratch + (size_t)j * sc_sub, &o2max, o2s, st, (int)(p0 & 0x3fffffff),
                                           // a cache row belongs to a CANDIDATE: without an index list it moves with the feature pointer
-                                          dcache_l ? (lidx ? dcache_l : dcache_l + (size_t)p0 * OVN_DELTA_CACHE_ELEMS) : nullptr, a2_in_yaw);
+                                          dcache_l ? (lidx ? dcache_l : dcache_l + (size_t)p0 * OVN_DELTA_CACHE_ELEMS) : nullptr, a2_in_yaw,
+                                          seg ? &sp : nullptr);
         if (rc) return rc;
         if (p0 == 0) ctx->dbg_o2max = o2max;
         {   // c_conv3 + Flatten + Dense + sigmoid: one launch (the pair's last workgroup finishes it)
@@ -718,6 +733,153 @@ int ovn_top_k(ovn_ctx* ctx, const float* overlap, const int32_t* yaw, const int3
   OVN_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0, OVN_ERR_ARG, "ovn_top_k: out_dev is not 16-byte aligned");
   OVN_ON_DEVICE(ctx->device);
   return ovn_top_k_forward(overlap, yaw, ids, (int)n, k, threshold, (int)index_offset, out, (hipStream_t)stream);
+}
+
+// ---- segmented batches ---------------------------------------------------------------------------------------------------------
+// The host segment table (offsets, and the query of every segment when it is given) is validated, staged in a context-owned pinned
+// buffer and copied to seg_dev on `stream`; `extra` more bytes of device space follow it (the indexed route's right index).  The
+// pinned buffer is rewritten only after the previous call's copy has left it (seg_ev).
+static const char* seg_offsets_error(const int64_t* offs, int64_t B, int64_t* n_out) {
+  if (B < 0 || B >= (1ll << 31)) return "B outside [0, 2^31)";
+  if (!offs) return "seg_offsets is NULL";
+  if (offs[0] != 0) return "seg_offsets[0] != 0";
+  for (int64_t b = 0; b < B; ++b)
+    if (offs[b + 1] < offs[b]) return "seg_offsets decrease";
+  if (offs[B] >= (1ll << 31)) return "more than 2^31 - 1 pairs";
+  *n_out = offs[B];
+  return nullptr;
+}
+
+static int seg_stage(ovn_ctx* ctx, const int64_t* offs, const int32_t* qidx, int64_t B, size_t extra, hipStream_t stream,
+                     int64_t** offs_dev, int32_t** qidx_dev, void** extra_dev) {
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t ob = al((size_t)(B + 1) * sizeof(int64_t)), qb = qidx ? al((size_t)B * sizeof(int32_t)) : 0;
+  const size_t need = ob + qb + al(extra);
+  if (!ctx->seg_ev) {
+    OVN_HIP_CHECK(hipEventCreateWithFlags(&ctx->seg_ev, hipEventDisableTiming));
+    OVN_HIP_CHECK(hipEventCreateWithFlags(&ctx->seg_done, hipEventDisableTiming));
+  }
+  if (ctx->seg_ev_pending) {
+    OVN_HIP_CHECK(hipEventSynchronize(ctx->seg_ev));              // the previous table has left the pinned buffer
+    OVN_HIP_CHECK(hipStreamWaitEvent(stream, ctx->seg_done, 0));  // and its kernels are done with seg_dev, whatever their stream
+    ctx->seg_ev_pending = false;
+  }
+  if (need > ctx->seg_cap) {
+    OVN_HIP_CHECK(hipStreamSynchronize(stream));       // earlier launches may still read the old device table
+    if (ctx->seg_dev) (void)hipFree(ctx->seg_dev);
+    if (ctx->seg_host) (void)hipHostFree(ctx->seg_host);
+    ctx->seg_dev = ctx->seg_host = nullptr;
+    ctx->seg_cap = 0;
+    const size_t want = need + need / 2;
+    OVN_HIP_CHECK(hipMalloc(&ctx->seg_dev, want));
+    OVN_HIP_CHECK(hipHostMalloc(&ctx->seg_host, want, hipHostMallocDefault));
+    ctx->seg_cap = want;
+  }
+  char* h = static_cast<char*>(ctx->seg_host);
+  memcpy(h, offs, (size_t)(B + 1) * sizeof(int64_t));
+  if (qidx) memcpy(h + ob, qidx, (size_t)B * sizeof(int32_t));
+  OVN_HIP_CHECK(hipMemcpyAsync(ctx->seg_dev, h, ob + qb, hipMemcpyHostToDevice, stream));
+  OVN_HIP_CHECK(hipEventRecord(ctx->seg_ev, stream));
+  ctx->seg_ev_pending = true;
+  char* d = static_cast<char*>(ctx->seg_dev);
+  *offs_dev = reinterpret_cast<int64_t*>(d);
+  if (qidx_dev) *qidx_dev = qidx ? reinterpret_cast<int32_t*>(d + ob) : nullptr;
+  if (extra_dev) *extra_dev = d + ob + qb;
+  return OVN_OK;
+}
+
+// the last kernel of a segmented call that reads seg_dev has been enqueued on `stream`
+static int seg_release(ovn_ctx* ctx, hipStream_t stream) {
+  OVN_HIP_CHECK(hipEventRecord(ctx->seg_done, stream));
+  return OVN_OK;
+}
+
+static bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+
+int ovn_heads_segments(ovn_ctx* ctx, const float* feats_pool, const float* spec_pool, const float* dcache_pool,
+                       const int32_t* cand_idx, const float* feats_q, const float* spec_q, const int32_t* query_idx,
+                       const int64_t* seg_offsets, int64_t B, int64_t n, float* overlap, int32_t* yaw, float* logit, float* corr,
+                       void* stream_) {
+  OVN_REQUIRE(ctx && ctx->head_set, OVN_ERR_STATE, "ovn_heads_segments: head weights not set");
+  int64_t total = 0;
+  const char* bad = seg_offsets_error(seg_offsets, B, &total);
+  OVN_REQUIRE(bad == nullptr, OVN_ERR_ARG, "ovn_heads_segments: %s", bad);
+  OVN_REQUIRE(n == total, OVN_ERR_ARG, "ovn_heads_segments: n = %lld but seg_offsets[B] = %lld", (long long)n, (long long)total);
+  OVN_REQUIRE(B == 0 || query_idx != nullptr, OVN_ERR_ARG, "ovn_heads_segments: query_idx is NULL");
+  for (int64_t b = 0; b < B; ++b)
+    OVN_REQUIRE(query_idx[b] >= 0, OVN_ERR_ARG, "ovn_heads_segments: query_idx[%lld] = %d < 0", (long long)b, query_idx[b]);
+  if (n == 0) return OVN_OK;
+  OVN_REQUIRE(feats_pool && feats_q && cand_idx && overlap && yaw, OVN_ERR_ARG, "ovn_heads_segments: NULL buffer");
+  OVN_REQUIRE((spec_pool == nullptr) == (spec_q == nullptr), OVN_ERR_ARG, "ovn_heads_segments: spec_pool and spec_q go together");
+  const int fw = ctx_feat_w(ctx);
+  OVN_REQUIRE(spec_pool == nullptr || fw == OVN_FEAT_W, OVN_ERR_ARG,
+              "ovn_heads_segments: the spectral correlation head needs 360-column feature volumes (the leg produces %d)", fw);
+  OVN_REQUIRE(!misaligned(feats_pool, 4) && !misaligned(feats_q, 4) && !misaligned(cand_idx, 4) && !misaligned(overlap, 4) &&
+                  !misaligned(yaw, 4) && !misaligned(logit, 4) && !misaligned(corr, 4) && !misaligned(spec_pool, 4) &&
+                  !misaligned(spec_q, 4) && !misaligned(dcache_pool, 16),
+              OVN_ERR_ARG, "ovn_heads_segments: misaligned buffer (4 bytes; dcache_pool 16 bytes)");
+  OVN_ON_DEVICE(ctx->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  const bool spectral = spec_pool != nullptr;
+  const int corr_mode = spectral ? 2 : 1;
+  // f16x3 at W = 360 with conv1size 15 and compaction on: segmented passes (each segment's query state once, its compacted K walk and
+  // the Delta cache rows, as in its 1-vs-N sweep).  Every other mode and geometry -- and f16x3 with compaction off, whose 1-vs-N walk
+  // is the 128-channel walk of an indexed pair -- is the same per pair in the indexed form: one indexed pass over all pairs.
+  const bool segmented = ctx->head_mode == 1 && fw == OVN_FEAT_W && ctx->head_s == OVN_S && ctx->head_compact;
+  int64_t* offs_dev = nullptr;
+  int32_t* qidx_dev = nullptr;
+  void* rbuf = nullptr;
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t rbytes = al((size_t)n * sizeof(int32_t));
+  int rc = seg_stage(ctx, seg_offsets, query_idx, B, rbytes * (segmented ? 2 : 1), stream, &offs_dev, &qidx_dev, &rbuf);
+  if (rc) return rc;
+  int32_t* ridx = static_cast<int32_t*>(rbuf);
+  int32_t* pseg = segmented ? reinterpret_cast<int32_t*>(static_cast<char*>(rbuf) + rbytes) : nullptr;
+  {
+    OvnProfScope ps(ctx, OVN_K_DELTA_PREP, stream);
+    rc = ovn_segment_ridx_forward(offs_dev, qidx_dev, (int)B, (int)n, ridx, pseg, stream);
+    if (rc) return rc;
+  }
+  if (!segmented) {
+    rc = delta_head_run(ctx, feats_pool, cand_idx, feats_q, ridx, n, overlap, logit, yaw, corr, corr_mode, spec_pool, spec_q, nullptr, stream);
+    return rc ? rc : seg_release(ctx, stream);
+  }
+  // passes of at most head_chunk pairs and OVN_SEG_PASS_MAX segments (a segment may straddle two passes: its state is computed in both)
+  const float* dc = spectral ? dcache_pool : nullptr;   // (rows serve ovn_heads_spectral's sweeps)
+  const int64_t* o = seg_offsets;
+  auto seg_of = [&](int64_t p) { return (int64_t)(std::upper_bound(o, o + B + 1, p) - o) - 1; };   // the segment holding pair p
+  for (int64_t p0 = 0; p0 < n;) {
+    const int64_t b0 = seg_of(p0);
+    int64_t p1 = std::min(n, p0 + ctx->head_chunk);
+    if (seg_of(p1 - 1) - b0 + 1 > OVN_SEG_PASS_MAX) p1 = o[b0 + OVN_SEG_PASS_MAX];
+    const int64_t np = p1 - p0;
+    OvnSegPass sp{pseg + p0, qidx_dev, offs_dev, (int)b0, (int)(seg_of(p1 - 1) - b0 + 1), nullptr};
+    rc = delta_head_run(ctx, feats_pool, cand_idx + p0, feats_q, ridx + p0, np, overlap + p0, logit ? logit + p0 : nullptr, yaw + p0,
+                        corr ? corr + (size_t)p0 * fw : nullptr, corr_mode, spec_pool, spec_q, dc, stream, &sp);
+    if (rc) return rc;
+    p0 = p1;
+  }
+  return seg_release(ctx, stream);
+}
+
+int ovn_top_k_segments(ovn_ctx* ctx, const float* overlap, const int32_t* yaw, const int32_t* ids, const int64_t* seg_offsets,
+                       int64_t B, int k, float threshold, int32_t* out, void* stream) {
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_top_k_segments: ctx is NULL");
+  OVN_REQUIRE(k >= 1 && k <= OVN_TOP_K_MAX, OVN_ERR_ARG, "ovn_top_k_segments: k must be in 1..OVN_TOP_K_MAX (1024)");
+  int64_t n = 0;
+  const char* bad = seg_offsets_error(seg_offsets, B, &n);
+  OVN_REQUIRE(bad == nullptr, OVN_ERR_ARG, "ovn_top_k_segments: %s", bad);
+  if (B == 0) return OVN_OK;
+  OVN_REQUIRE(out != nullptr && (n == 0 || overlap != nullptr), OVN_ERR_ARG, "ovn_top_k_segments: NULL buffer");
+  OVN_REQUIRE(!misaligned(out, 16), OVN_ERR_ARG, "ovn_top_k_segments: out_dev is not 16-byte aligned");
+  OVN_REQUIRE(!misaligned(overlap, 4) && !misaligned(yaw, 4) && !misaligned(ids, 4), OVN_ERR_ARG,
+              "ovn_top_k_segments: misaligned buffer");
+  OVN_ON_DEVICE(ctx->device);
+  int64_t* offs_dev = nullptr;
+  int rc = seg_stage(ctx, seg_offsets, nullptr, B, 0, (hipStream_t)stream, &offs_dev, nullptr, nullptr);
+  if (rc) return rc;
+  rc = ovn_top_k_segments_forward(overlap, yaw, ids, offs_dev, (int)B, k, threshold, out, (hipStream_t)stream);
+  return rc ? rc : seg_release(ctx, (hipStream_t)stream);
 }
 
 int ovn_project(ovn_ctx* ctx, const float* points_dev, const int64_t* offsets_dev, int n_scans,

@@ -303,6 +303,14 @@ struct ovn_ctx {
   int64_t c3_arrived_n = 0;
   const unsigned* dbg_live = nullptr;   // live-channel list of the most recent Delta sweep (NULL: it walked all 128 channels; reset
                                         // by every head call and with the scratch it points into)
+  // segmented batches (ovn_heads_segments / ovn_top_k_segments): the host segment table staged in pinned memory and copied to
+  // seg_dev = [seg_offsets int64 (B + 1) | query_idx int32 (B) | per-pair right index int32 (n)]; seg_ev orders the reuse of seg_host
+  void* seg_host = nullptr;
+  void* seg_dev = nullptr;
+  size_t seg_cap = 0;
+  hipEvent_t seg_ev = nullptr;        // the table left seg_host
+  hipEvent_t seg_done = nullptr;      // the kernels of the last segmented call have read seg_dev
+  bool seg_ev_pending = false;
 };
 
 // kernel classes reported by ovn_profile_end
@@ -357,11 +365,23 @@ int ovn_dense_sigmoid_forward(const ovn_ctx* ctx, const float* o3, int n, float*
 int ovn_delta_prepare_f16x3(ovn_ctx* ctx, const float* c1_kernel_dev, const float* c1_bias_dev, const float* c2_kernel_dev,
                             hipStream_t stream);
 size_t ovn_delta_f16x3_scratch_bytes(int n, bool per_pair_right);
+// A pass of ovn_heads_segments over the pairs of segments seg0 .. seg0 + nseg - 1 (f16x3, compaction on): pseg = the pass's first
+// pair's entry of the per-pair segment index, qidx / offs = the whole batch's query indices and offsets (device), scratch =
+// ovn_delta_f16x3_seg_bytes(nseg) bytes for the per-segment query state.  ridx must hold each pair's query index.
+struct OvnSegPass {
+  const int32_t* pseg;
+  const int32_t* qidx;
+  const int64_t* offs;
+  int seg0, nseg;
+  void* scratch;
+};
+size_t ovn_delta_f16x3_seg_bytes(int nseg);
 int ovn_delta_c12_f16x3_forward(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r,
                                 const int32_t* ridx, int n, void* scratch, unsigned** o2max_out, float* o2, hipStream_t stream,
                                 int pair0 = 0,    // pair0: index of the call's first pair in the sweep (rotation of the K walks)
                                 const float* dcache_l = nullptr,   // Delta cache rows of the left pool (ovn_delta_cache), 1-vs-N only
-                                bool a2_done = false);   // A2raw of the (single) right volume is already in the scratch (ovn_delta_f16x3_a2raw)
+                                bool a2_done = false,    // A2raw of the (single) right volume is already in the scratch (ovn_delta_f16x3_a2raw)
+                                const struct OvnSegPass* seg = nullptr);   // a segmented pass (ovn_heads_segments), see below
 float* ovn_delta_f16x3_a2raw(void* scratch, int n);
 // bf16x3 head mode: the same two-kernel path with the exact bf16 split (delta_head_f16x3.hip); same scratch size and A2raw location
 int ovn_delta_c12_bf16x3_forward(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx,
@@ -425,6 +445,12 @@ int ovn_best_match_forward(const float* overlap, const int32_t* yaw, const int32
 // top_k.hip
 int ovn_top_k_forward(const float* overlap, const int32_t* yaw, const int32_t* ids, int n, int k, float threshold,
                       int index_offset, int32_t* out, hipStream_t stream);
+// one workgroup per segment b: ovn_top_k_forward on overlap[offs[b] .. offs[b + 1]) (yaw / ids sliced alike) -> out + 4 k b
+int ovn_top_k_segments_forward(const float* overlap, const int32_t* yaw, const int32_t* ids, const int64_t* offs_dev, int B, int k,
+                               float threshold, int32_t* out, hipStream_t stream);
+// ridx[p] = qidx[b] and pseg[p] = b (pseg may be NULL) for offs[b] <= p < offs[b + 1]: the per-pair query and segment of a batch
+int ovn_segment_ridx_forward(const int64_t* offs_dev, const int32_t* qidx_dev, int B, int n, int32_t* ridx, int32_t* pseg,
+                             hipStream_t stream);
 // a2_feats_r / a2raw non-NULL (small 1-vs-N sweeps): the launch also computes A2raw of that right volume (delta_a2.h) in extra workgroups
 int ovn_corr_spectral_forward(ovn_ctx* ctx, const float* spec_l, const int32_t* lidx, const float* spec_r,
                               const int32_t* ridx, int n, int32_t* yaw, float* corr, hipStream_t stream,

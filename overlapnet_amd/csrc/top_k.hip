@@ -66,9 +66,24 @@ __device__ __forceinline__ void for_each_score(const float* __restrict__ overlap
   for (int i = tail + threadIdx.x; i < n; i += TK_THREADS) f(i, p[i]);
 }
 
+// SEG = false: ovn_top_k, one workgroup on overlap[0, n).  SEG = true: ovn_top_k_segments, workgroup b on segment b =
+// [offs[b], offs[b + 1]) of overlap / yaw / ids (positions and records relative to the segment), records to out + 4 k b; n and
+// index_offset are ignored.  The rest of the kernel is the same code: a segment gets the records of ovn_top_k on its slice.
+template <bool SEG>
 __global__ __launch_bounds__(TK_THREADS) void top_k_kernel(const float* __restrict__ overlap, const int32_t* __restrict__ yaw,
                                                            const int32_t* __restrict__ ids, int n, int k, float threshold,
-                                                           int index_offset, int32_t* __restrict__ out) {
+                                                           int index_offset, int32_t* __restrict__ out,
+                                                           const int64_t* __restrict__ offs) {
+  if constexpr (SEG) {
+    const int64_t b = blockIdx.x;
+    const int64_t base = offs[b];
+    n = (int)(offs[b + 1] - base);
+    overlap += base;
+    if (yaw) yaw += base;
+    if (ids) ids += base;
+    out += (size_t)b * k * 4;
+    index_offset = 0;
+  }
   __shared__ uint32_t hist[TK_BINS * TK_COPIES];     // 32 KB: hist[bin * 32 + copy]
   __shared__ uint32_t merged[TK_BINS];
   __shared__ uint64_t keys[OVN_TOP_K_MAX];           // 8 KB
@@ -220,7 +235,45 @@ __global__ __launch_bounds__(TK_THREADS) void top_k_kernel(const float* __restri
 
 int ovn_top_k_forward(const float* overlap, const int32_t* yaw, const int32_t* ids, int n, int k, float threshold,
                       int index_offset, int32_t* out, hipStream_t stream) {
-  hipLaunchKernelGGL(top_k_kernel, dim3(1), dim3(TK_THREADS), 0, stream, overlap, yaw, ids, n, k, threshold, index_offset, out);
+  hipLaunchKernelGGL(top_k_kernel<false>, dim3(1), dim3(TK_THREADS), 0, stream, overlap, yaw, ids, n, k, threshold, index_offset, out,
+                     nullptr);
+  OVN_HIP_CHECK(hipGetLastError());
+  return OVN_OK;
+}
+
+int ovn_top_k_segments_forward(const float* overlap, const int32_t* yaw, const int32_t* ids, const int64_t* offs_dev, int B, int k,
+                               float threshold, int32_t* out, hipStream_t stream) {
+  if (B == 0) return OVN_OK;
+  hipLaunchKernelGGL(top_k_kernel<true>, dim3(B), dim3(TK_THREADS), 0, stream, overlap, yaw, ids, 0, k, threshold, 0, out, offs_dev);
+  OVN_HIP_CHECK(hipGetLastError());
+  return OVN_OK;
+}
+
+namespace {
+
+// ridx[p] = qidx[b] and pseg[p] = b, with b the last segment whose offset is <= p (the segment holding pair p: empty segments before
+// it share its offset and come first).  One thread per pair, a binary search over the B + 1 offsets.
+__global__ __launch_bounds__(256) void segment_ridx_kernel(const int64_t* __restrict__ offs, const int32_t* __restrict__ qidx, int B,
+                                                           int n, int32_t* __restrict__ ridx, int32_t* __restrict__ pseg) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= n) return;
+  int lo = 0, hi = B;   // offs[lo] <= p < offs[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (offs[mid] <= p) lo = mid;
+    else hi = mid;
+  }
+  ridx[p] = qidx[lo];
+  if (pseg) pseg[p] = lo;
+}
+
+}  // namespace
+
+int ovn_segment_ridx_forward(const int64_t* offs_dev, const int32_t* qidx_dev, int B, int n, int32_t* ridx, int32_t* pseg,
+                             hipStream_t stream) {
+  if (n == 0) return OVN_OK;
+  const unsigned blocks = (unsigned)(((int64_t)n + 255) / 256);
+  hipLaunchKernelGGL(segment_ridx_kernel, dim3(blocks), dim3(256), 0, stream, offs_dev, qidx_dev, B, n, ridx, pseg);
   OVN_HIP_CHECK(hipGetLastError());
   return OVN_OK;
 }

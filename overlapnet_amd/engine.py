@@ -261,6 +261,56 @@ class OvnEngine:
             out["corr"] = corr
         return out
 
+    def heads_segments(self, feats_pool: torch.Tensor, feats_q: torch.Tensor, cand_idx, query_idx, seg_offsets,
+                       spec_pool: Optional[torch.Tensor] = None, spec_q: Optional[torch.Tensor] = None,
+                       dcache_pool: Optional[torch.Tensor] = None, want_logit: bool = False, want_corr: bool = False):
+        """Both heads on a batch of B loop-closure queries in one call (`ovn_heads_segments`): segment b is the pairs
+        [seg_offsets[b], seg_offsets[b + 1]), pair p = (left = feats_pool[cand_idx[p]], right = feats_q[query_idx[b]]) -- the 1-vs-N
+        orientation of `Infer.infer_multiple`.  Pair p gets exactly the bits `heads` gives it when segment b runs alone in its 1-vs-N
+        form (`heads(feats_pool, feats_q[q:q + 1], lidx=cand_idx[segment], spec_l=spec_pool, spec_r=spec_q[q:q + 1],
+        dcache_l=dcache_pool)`).  seg_offsets / query_idx are host data (lists, arrays or tensors), checked here; cand_idx is
+        range-checked on the host unless it is already a device tensor (see `_idx`).  spec_pool / spec_q: both or neither.
+        Returns dict of flat device tensors in pair order: overlap (n) f32, yaw (n) i32 [, logit (n), corr (n, feat_w)]."""
+        if not self._head_ready:
+            raise _lib.OvnError("head weights not loaded")
+        self._check_feats(feats_pool, "feats_pool")
+        self._check_feats(feats_q, "feats_q")
+        npool = feats_pool.numel() // (self._fw * FEAT_C)
+        nq = feats_q.numel() // (self._fw * FEAT_C)
+        offs, q = segment_table(seg_offsets, query_idx, nq)
+        n = int(offs[-1])
+        ci = self._idx(cand_idx, n, npool, "candidate index")
+        if (spec_pool is None) != (spec_q is None):
+            raise _lib.OvnError("spec_pool and spec_q must be given together")
+        if spec_pool is not None:
+            if not self.has_spectrum:
+                raise _lib.OvnError("spectra exist for 360-column feature volumes only (this leg produces %d)" % self._fw)
+            for t, what, m in ((spec_pool, "spec_pool", npool), (spec_q, "spec_q", nq)):
+                if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous():
+                    raise _lib.OvnError("%s must be a contiguous float32 tensor on %s" % (what, self.device))
+                if t.numel() != m * FEAT_C * self.SPEC_W:
+                    raise _lib.OvnError("%s must hold one 128x368 spectrum per feature volume" % what)
+        if dcache_pool is not None:
+            if dcache_pool.device != self.device or dcache_pool.dtype != torch.float32 or not dcache_pool.is_contiguous():
+                raise _lib.OvnError("dcache_pool must be a contiguous float32 tensor on %s" % self.device)
+            if dcache_pool.numel() != npool * self.DELTA_CACHE_ELEMS:
+                raise _lib.OvnError("dcache_pool must hold one Delta cache row per pool volume")
+        overlap = torch.empty(n, dtype=torch.float32, device=self.device)
+        yaw = torch.empty(n, dtype=torch.int32, device=self.device)
+        logit = torch.empty(n, dtype=torch.float32, device=self.device) if want_logit else None
+        corr = torch.empty((n, self._fw), dtype=torch.float32, device=self.device) if want_corr else None
+        with self._dev():
+            _lib.check(self.lib.ovn_heads_segments(
+                self._h, _ptr(feats_pool), _ptr(spec_pool), _ptr(dcache_pool), _ptr(ci), _ptr(feats_q), _ptr(spec_q),
+                q.ctypes.data_as(C.POINTER(C.c_int32)), offs.ctypes.data_as(C.POINTER(C.c_int64)), len(q), n, _ptr(overlap),
+                _ptr(yaw), _ptr(logit), _ptr(corr), self._stream()), "ovn_heads_segments")
+        out = {"overlap": overlap, "yaw": yaw}
+        if want_logit:
+            out["logit"] = logit
+        if want_corr:
+            out["corr"] = corr
+        return out
+
     def corr_head(self, feats_l: torch.Tensor, feats_r: torch.Tensor, lidx=None, ridx=None, n: Optional[int] = None,
                   want_corr: bool = False):
         self._check_feats(feats_l, "feats_l")
@@ -420,6 +470,29 @@ class OvnEngine:
         with self._dev():
             _lib.check(self.lib.ovn_top_k(self._h, _ptr(overlap), _ptr(yaw), _ptr(ids), n, k, float(threshold), int(index_offset),
                                           _ptr(out), self._stream()), "ovn_top_k")
+        return out
+
+    def top_k_segments(self, overlap: torch.Tensor, seg_offsets, yaw: Optional[torch.Tensor] = None, k: int = 5,
+                       threshold: float = 0.3, ids: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`top_k` of every segment of a `heads_segments` batch in one launch (`ovn_top_k_segments`): a (B, k, 4) int32 device
+        tensor; segment b's k records are bit for bit `top_k(overlap[o0:o1], yaw[o0:o1], k, threshold, ids=ids[o0:o1])` (ids None:
+        the position inside the segment); an empty segment gives k records {-1, 0, 0, 0}.  seg_offsets: host data, checked here."""
+        offs, _ = segment_table(seg_offsets, None, None)
+        k = check_top_k(k)
+        n, B = int(offs[-1]), len(offs) - 1
+        for t, what, dt in ((overlap, "overlap", torch.float32), (yaw, "yaw", torch.int32), (ids, "ids", torch.int32)):
+            if t is None:
+                continue
+            if t.device != self.device or t.dtype != dt or not t.is_contiguous() or t.numel() != n:
+                raise _lib.OvnError("%s must be a contiguous %s tensor of %d elements on %s" % (what, dt, n, self.device))
+        if out is None:
+            out = torch.empty((B, k, 4), dtype=torch.int32, device=self.device)
+        elif out.device != self.device or out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != 4 * k * B:
+            raise _lib.OvnError("out must be a contiguous int32 tensor of %d elements on %s" % (4 * k * B, self.device))
+        with self._dev():
+            _lib.check(self.lib.ovn_top_k_segments(self._h, _ptr(overlap), _ptr(yaw), _ptr(ids),
+                                                   offs.ctypes.data_as(C.POINTER(C.c_int64)), B, k, float(threshold), _ptr(out),
+                                                   self._stream()), "ovn_top_k_segments")
         return out
 
     # -- preprocessing ------------------------------------------------------------------------------
@@ -721,6 +794,42 @@ class QueryAhead:
     def close(self) -> None:
         self.stream.synchronize()
         self.side.close()
+
+
+def segment_table(seg_offsets, query_idx, n_queries: Optional[int]) -> Tuple[np.ndarray, np.ndarray]:
+    """Host check of a segmented batch's table (`heads_segments`, `top_k_segments`): (offsets int64 (B + 1), query_idx int32 (B)).
+    Raises ValueError for offsets that do not start at 0 or decrease, IndexError for a query index outside [0, n_queries).  No GPU."""
+    def host(a):
+        return a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    o = host(seg_offsets).reshape(-1)
+    if o.size == 0 or (o.size and not np.issubdtype(o.dtype, np.integer)):
+        raise ValueError("seg_offsets must be B + 1 >= 1 integers")
+    o = np.ascontiguousarray(o, dtype=np.int64)
+    if o[0] != 0:
+        raise ValueError("seg_offsets[0] must be 0, got %d" % int(o[0]))
+    if np.any(np.diff(o) < 0):
+        raise ValueError("seg_offsets must be non-decreasing")
+    if int(o[-1]) >= 1 << 31:
+        raise ValueError("more than 2^31 - 1 pairs in one batch")
+    if query_idx is None:
+        return o, np.zeros(0, np.int32)
+    q = host(query_idx).reshape(-1)
+    if q.size != o.size - 1:
+        raise ValueError("query_idx has %d entries for %d segments" % (q.size, o.size - 1))
+    if q.size and not np.issubdtype(q.dtype, np.integer):
+        raise IndexError("query_idx holds non-integer values")
+    q = q.astype(np.int64)
+    if q.size and (int(q.min()) < 0 or (n_queries is not None and int(q.max()) >= n_queries)):
+        raise IndexError("query index out of range: [%d, %d] not within [0, %s)" % (int(q.min()), int(q.max()), n_queries))
+    return o, np.ascontiguousarray(q, dtype=np.int32)
+
+
+def check_top_k(k) -> int:
+    """k of the top-k calls: an integer in 1..OVN_TOP_K_MAX (1024), else ValueError."""
+    k = int(k)
+    if not 1 <= k <= 1024:
+        raise ValueError("k must be in 1..1024, got %d" % k)
+    return k
 
 
 def decode_match(record) -> Optional[Tuple[int, float, int]]:

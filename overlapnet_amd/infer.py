@@ -916,6 +916,95 @@ class Infer():
     self._start_ahead(current_frame_id)     # next frame's files, copy and leg in the shadow of the kernels just enqueued
     return decode_match(rec)
 
+  # ---- offline batches: many queries against the cached frames in one pass (extension) ----------------------------------------
+  def cache_frames(self, n):
+    """ Addition to the reference API: feed frames len(feature_volumes) .. n - 1 through the leg, in batches of `batch_size`, into
+        the device cache with their spectra and Delta cache rows -- what `infer_multiple` would have cached feeding them one by one,
+        bit for bit (a scan's feature volume does not depend on the batch).  Prepares the `*_batch` calls on a recorded drive. """
+    if self._world > 1:
+      raise Exception('Infer.cache_frames: not available on a sharded Infer (world %d)' % self._world)
+    n = int(n)
+    start = len(self.feature_volumes)
+    if n <= start:
+      return
+    self._drop_ahead()
+    self._ahead = None
+    bs = max(1, int(self.batch_size))
+    for s in range(start, n, bs):
+      names = [str(i).zfill(6) for i in range(s, min(n, s + bs))]
+      self.feature_volumes.extend_device(self._leg_device(names))
+
+  def _segments(self, current_ids, reference_lists, what):
+    """Host checks of a batch call, before any GPU work -> (query ids int64 (B), candidate ids int64 (n), offsets int64 (B + 1))."""
+    if self._world > 1:
+      raise Exception('Infer.%s: batches are not sharded; use a single-rank Infer (world %d)' % (what, self._world))
+    q = np.asarray(current_ids, dtype=np.int64).reshape(-1)
+    lists = [np.asarray(r, dtype=np.int64).reshape(-1) for r in reference_lists]
+    if len(lists) != len(q):
+      raise ValueError('Infer.%s: %d query ids but %d reference lists' % (what, len(q), len(lists)))
+    offs = np.zeros(len(lists) + 1, dtype=np.int64)
+    if lists:
+      offs[1:] = np.cumsum([len(r) for r in lists])
+    cand = np.concatenate(lists) if lists else np.zeros(0, np.int64)
+    n = len(self.feature_volumes)
+    for ids in (q, cand):
+      if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= n):
+        bad = int(ids.min()) if int(ids.min()) < 0 else int(ids.max())
+        raise IndexError('index %d is out of bounds for axis 0 with size %d (cache the frames first: cache_frames)' % (bad, n))
+    return q, cand, offs
+
+  def _heads_batch(self, q, cand, offs):
+    cache = self.feature_volumes
+    feats, spec = cache.device_features, cache.device_spectra
+    ci = torch.from_numpy(cand.astype(np.int32)).to(self.engine.device)
+    r = self.engine.heads_segments(feats, feats, ci, q, offs, spec_pool=spec, spec_q=spec, dcache_pool=cache.device_delta_cache)
+    return r, ci
+
+  def infer_multiple_batch(self, current_ids, reference_lists):
+    """ Addition to the reference API: `infer_multiple` for B queries at once, all frames already cached (`cache_frames`).
+        Returns a list with, per query, exactly what `infer_multiple(current_ids[b], reference_lists[b])` returns on the same cache
+        ((overlap, yaw) or None for an empty list).  One head pass over all pairs and ONE device-to-host copy; caches nothing. """
+    q, cand, offs = self._segments(current_ids, reference_lists, 'infer_multiple_batch')
+    if len(cand) == 0:
+      return [None] * len(q)
+    r, _ = self._heads_batch(q, cand, offs)
+    res = torch.stack([r["overlap"].view(torch.int32), r["yaw"]]).cpu().numpy()      # ONE device-to-host copy for all queries
+    out = []
+    for b in range(len(q)):
+      o0, o1 = int(offs[b]), int(offs[b + 1])
+      if o0 == o1:
+        out.append(None)
+        continue
+      out.append((res[0, o0:o1].view(np.float32).reshape(-1, 1).squeeze(), res[1, o0:o1].astype(np.int64)))
+    return out
+
+  def infer_best_match_batch(self, current_ids, reference_lists, overlap_thres=0.3):
+    """ Addition to the reference API: `infer_best_match` for B queries at once, all frames already cached (`cache_frames`): one
+        head pass, one launch of B decisions on the GPU (`top_k_segments` with k = 1, `best_match`'s record) and ONE copy of B
+        16-byte records.  Returns a list of (reference frame id, overlap, yaw) or None, per query. """
+    from .engine import decode_match
+    q, cand, offs = self._segments(current_ids, reference_lists, 'infer_best_match_batch')
+    if len(cand) == 0:
+      return [None] * len(q)
+    r, ci = self._heads_batch(q, cand, offs)
+    rec = self.engine.top_k_segments(r["overlap"], offs, r["yaw"], 1, overlap_thres, ids=ci).cpu().numpy()
+    return [decode_match(rec[b, 0]) for b in range(len(q))]
+
+  def infer_top_k_batch(self, current_ids, reference_lists, k=5, overlap_thres=0.3):
+    """ Addition to the reference API: `infer_top_k` for B queries at once, all frames already cached (`cache_frames`): one head
+        pass, one launch of B rankings and ONE copy of B x k records.  Returns a list of what `infer_top_k` returns, per query. """
+    from .engine import decode_top_k
+    k = int(k)
+    if not 1 <= k <= TOP_K_MAX:
+      raise ValueError('k must be in 1..%d, got %d' % (TOP_K_MAX, k))
+    q, cand, offs = self._segments(current_ids, reference_lists, 'infer_top_k_batch')
+    if len(cand) == 0:
+      return [[] for _ in range(len(q))]
+    r, ci = self._heads_batch(q, cand, offs)
+    thr = float('-inf') if overlap_thres is None else overlap_thres
+    rec = self.engine.top_k_segments(r["overlap"], offs, r["yaw"], k, thr, ids=ci).cpu().numpy()
+    return [[(i, ov, yw) for i, ov, yw, above in decode_top_k(rec[b]) if overlap_thres is None or above] for b in range(len(q))]
+
   def infer_multiple_vs_multiple(self, file_names, first_idxs, second_idxs):
     """ Multiple pairs (infer.py:205-238): pair i = (file_names[first_idxs[i]], file_names[second_idxs[i]]);
         second -> head-left, first -> head-right.  Replaces the feature-volume cache. """

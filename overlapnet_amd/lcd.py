@@ -98,3 +98,16 @@ def detect(infer, idx: int, traj_xy: np.ndarray, traj_length: np.ndarray, ellips
     if res is None:
         return None
     return decide(ref, res[0], res[1], overlap_thres)
+
+
+def detect_offline(infer, frames: Sequence[int], traj_xy: np.ndarray, traj_length: np.ndarray, ellipse, **gate_kw):
+    """`detect` over a recorded drive in one pass: caches frames up to max(frames) (`infer.cache_frames`), gates every frame with
+    `gate_candidates`, then takes all decisions in ONE `infer.infer_best_match_batch`.  Returns the list a loop of `detect` over the
+    same frames (fed in order, starting from an empty cache) returns: (frame id, overlap, yaw) or None per frame."""
+    overlap_thres = gate_kw.pop("overlap_thres", 0.3)
+    frames = [int(f) for f in frames]
+    if not frames:
+        return []
+    refs = [list(gate_candidates(f, traj_xy, traj_length, ellipse, **gate_kw)) for f in frames]
+    infer.cache_frames(max(frames) + 1)
+    return infer.infer_best_match_batch(frames, refs, overlap_thres)
