@@ -343,8 +343,10 @@ int ovn_profile_end(ovn_ctx* ctx, double* ms_by_kind, int64_t* launches_by_kind)
 /* Test hook: run registered leg layer `layer` alone on in_dev (nb,h,w,cin) -> out_dev (nb,oh,ow,cout). */
 int ovn_debug_conv(ovn_ctx* ctx, int layer, const float* in_dev, int nb, int h, int w, float* out_dev, void* stream);
 
-/* Test hook: copy the c_conv2 (n,24,24,128) and c_conv3 (n,22,22,256) activations that the most recent
+/* Test hook: copy the c_conv2 (n,G,G,128) and c_conv3 (n,G-2,G-2,256) activations that the most recent
  * ovn_heads call left in scratch (its first chunk / sub-chunk, n <= min(pairs, chunk_pairs, sub_chunk_pairs)); either output may be NULL.
+ * G = feat_w // 15: 24 at feat_w = 360.  At any other feat_w (conv1size 15) only a call that ran as ONE chunk keeps them (n <= its
+ * pair count); after a call of several chunks, and on the general conv1size path, the hook returns OVN_ERR_STATE.
  * (generateNet.py:102-110 intermediates; the reference exposes them as Keras layer outputs.) */
 int ovn_debug_head_activations(ovn_ctx* ctx, int64_t n, float* o2_dev, float* o3_dev, void* stream);
 

@@ -74,30 +74,46 @@ def _w(weights, name):
 
 
 def min_form_parts(l: np.ndarray, r: np.ndarray, weights, s: int = 15):
-    """The three terms of c_conv1 in min form, fp64: (lin_l (360, G, 64), lin_r (G, 64), M (360, G, 64), c) with
+    """The three terms of c_conv1 in min form, fp64: (lin_l (W, G, 64), lin_r (G, 64), M (W, G, 64), c) with
     o1 = b1 + lin_l + lin_r - 2 M.  lin_l[i, jb] = sum_{dj,c} l'[i, c] W1[dj, c], lin_r[jb] = sum_{dj,c} r'[s jb + dj, c] W1[dj, c],
-    M[i, jb] = sum_{dj,c} min(l'[i, c], r'[s jb + dj, c]) W1[dj, c]."""
+    M[i, jb] = sum_{dj,c} min(l'[i, c], r'[s jb + dj, c]) W1[dj, c].  W = l.shape[0], G = W // s."""
     l = np.asarray(l, np.float64)
     r = np.asarray(r, np.float64)
-    g = 360 // s
+    wd = l.shape[0]
+    g = wd // s
     c = -min(0.0, float(l.min()), float(r.min()))
     lp, rp = l + c, r + c
     w1 = _w(weights, "c_conv1/kernel").reshape(s, 128, 64)
     lin_l = np.repeat((lp @ w1.sum(axis=0))[:, None, :], g, axis=1)
     lin_r = rp[:g * s].reshape(g, s * 128) @ w1.reshape(s * 128, 64)
-    mn = np.minimum(lp[:, None, :], rp[None, :g * s, :])                      # (360, g s, 128)
-    M = mn.reshape(360 * g, s * 128) @ w1.reshape(s * 128, 64)
-    return lin_l, lin_r, M.reshape(360, g, 64), c
+    mn = np.minimum(lp[:, None, :], rp[None, :g * s, :])                      # (W, g s, 128)
+    M = mn.reshape(wd * g, s * 128) @ w1.reshape(s * 128, 64)
+    return lin_l, lin_r, M.reshape(wd, g, 64), c
 
 
-def _c1(x_ij, w1, s):
-    """sum_{dj,c} x[i, s jb + dj, c] w1[dj, c, o] for x (360, >= G s, 128)."""
-    g = 360 // s
-    return (x_ij[:, :g * s].reshape(360 * g, s * 128) @ w1.reshape(s * 128, 64)).reshape(360, g, 64)
+def _c1(x_ij, w1, s, width=None):
+    """sum_{dj,c} x[i, s jb + dj, c] w1[dj, c, o] for x (n, >= G s, 128); G = width // s, width = n by default (the volume's W)."""
+    n = x_ij.shape[0]
+    g = (width or n) // s
+    return (x_ij[:, :g * s].reshape(n * g, s * 128) @ w1.reshape(s * 128, 64)).reshape(n, g, 64)
+
+
+def _c1_abs_rows(l64, r64, w1, s, rows=32):
+    """c_conv1 on |l - r| without its bias and the root-sum-square of its terms, (W, G, 64) each, `rows` rows of l at a time: the
+    abs form of `head_pair` at a width other than 360, whose (W, W, 128) intermediates would take ~270 MB each at W = 512."""
+    wd = l64.shape[0]
+    g = wd // s
+    w1sq = np.square(w1)
+    val, var = np.empty((wd, g, 64)), np.empty((wd, g, 64))
+    for i0 in range(0, wd, rows):
+        d = np.abs(l64[i0:i0 + rows, None, :] - r64[None, :g * s, :])
+        val[i0:i0 + rows] = _c1(d, w1, s, wd)
+        var[i0:i0 + rows] = _c1(np.square(d), w1sq, s, wd)
+    return val, np.sqrt(var)
 
 
 def head_tail(o1: np.ndarray, weights, s: int = 15, wf=None, relu: bool = True):
-    """c_conv2 (+ ReLU), c_conv3 (+ ReLU), Dense on a c_conv1 output (360, G, 64).  `wf`: applied to every weight and bias first
+    """c_conv2 (+ ReLU), c_conv3 (+ ReLU), Dense on a c_conv1 output (W, G, 64).  `wf`: applied to every weight and bias first
     (np.abs: the magnitude chain; np.square: the variance chain), relu=False for those.  Returns (o2 (G, G, 128), o3 (G-2, G-2, 256),
     logit)."""
     f = wf or (lambda a: a)
@@ -128,13 +144,25 @@ def _conv3(o2, w3, b3):
 
 
 def head_pair(l: np.ndarray, r: np.ndarray, weights, s: int = 15, o1: Optional[np.ndarray] = None) -> dict:
-    """fp64 values of every Delta-head stage of the pair (l, r), each (360, 128), plus what `head_bounds` needs: the sizes of the
+    """fp64 values of every Delta-head stage of the pair (l, r), each (W, 128), plus what `head_bounds` needs: the sizes of the
     c_conv1 terms in both forms.  `o1`: a (possibly perturbed) c_conv1 output to push through the rest instead of the exact one
-    (the fault models of the tests)."""
+    (the fault models of the tests).  At W != 360 every head mode runs the exact fp32 kernels (|l - r| formed exactly): only the
+    abs form is kept, computed a few rows at a time."""
     l64 = np.asarray(l, np.float64)
     r64 = np.asarray(r, np.float64)
     w1 = _w(weights, "c_conv1/kernel").reshape(s, 128, 64)
     b1 = _w(weights, "c_conv1/bias")
+    if l64.shape[0] != 360:
+        c1v, rms_abs = _c1_abs_rows(l64, r64, w1, s)
+        o1x = b1 + c1v
+        if o1 is None:
+            o1 = o1x
+        o2, o3, logit = head_tail(o1, weights, s)
+        overlap = 1.0 / (1.0 + math.exp(-logit)) if logit > -700 else 0.0
+        c = -min(0.0, float(l64.min()), float(r64.min()))
+        span = float(max(l64.max() + c, r64.max() + c, 0.0))
+        return {"o1": o1, "o2": o2, "o3": o3, "logit": logit, "overlap": overlap, "s": s, "span": span,
+                "c1": {"abs": (np.abs(b1) + np.abs(c1v), rms_abs)}}
     diff = np.abs(l64[:, None, :] - r64[None, :, :])
     o1x = b1 + _c1(diff, w1, s)
     if o1 is None:
@@ -181,6 +209,8 @@ def head_bounds(h: dict, weights, mode: str) -> dict:
     sq = np.square
     w2, w3 = _w(weights, "c_conv2/kernel"), _w(weights, "c_conv3/kernel")
     wd = _w(weights, "overlap_output/kernel").reshape(-1)
+    if HEAD_FORM[mode] not in h["c1"]:
+        raise ValueError("head mode %s at a feature width other than 360: every head mode runs the fp32 kernels there ('f32')" % mode)
     val1, rms1 = h["c1"][HEAD_FORM[mode]]
     a1 = np.abs(_w(weights, "c_conv1/kernel")).reshape(-1, 64).sum(axis=0)
     a2 = np.abs(w2).reshape(-1, 128).sum(axis=0)
@@ -202,9 +232,10 @@ def head_bounds(h: dict, weights, mode: str) -> dict:
 
 
 def corr_pair(l: np.ndarray, r: np.ndarray) -> dict:
-    """Correlation vector of the pair (360,) with its elementwise bounds in both forms.
-      direct    one fp32 contraction of 360 x 128 products (corr_head.hip): SAFETY (u rms + sqrt(n) u (|v| + rms)) per shift, plus
-                the subnormal floor of n fp32 products.
+    """Correlation vector of the pair (W,), W = l.shape[0], with its elementwise bounds in both forms:
+        corr[k] = sum_j sum_c l[(k + j + W // 2) mod W, c] r[j, c]
+      direct    one fp32 contraction of W x 128 products (corr_head.hip, corr_head_w.hip): SAFETY (u rms + sqrt(n) u (|v| + rms))
+                per shift, plus the subnormal floor of n fp32 products.
       spectral  corr_spectral.hip: each spectrum X^[f, c] = sum_i x[i, c] e^(-2 pi i f i / 360) is a 360-term contraction split on
                 the fp16 matrix cores, its operands scaled by 2^k from the scan's largest |value| (unclamped: dft_f16x3_kernel);
                 the spectral product C^[f] = sum_c L^ conj(R^) is summed over 128 channels in fp32; the inverse transform is
@@ -212,15 +243,19 @@ def corr_pair(l: np.ndarray, r: np.ndarray) -> dict:
                     sigma_X[f, c] = u_prod ||x_c||_2 + sqrt(360) u (|X^| + ||x_c||_2) + sqrt(360) 4 2^-25 / scale + U_SUB
                     sigma_C[f]^2  = sum_c (|R^|^2 sigma_L^2 + |L^|^2 sigma_R^2) + (sqrt(128) u (|C^| + rms_C))^2
                 and the inverse transform (1 / 360) sum_f C^[f] e^(...) carries sqrt(2 sum_f sigma_C^2) / 360 to every shift (f and
-                360 - f are conjugates: their errors add coherently)."""
+                360 - f are conjugates: their errors add coherently).  360 columns only (the spectral route refuses other widths):
+                at W != 360 the result has no 'spectral' entry."""
     l64 = np.asarray(l, np.float64)
     r64 = np.asarray(r, np.float64)
-    jj = np.arange(360)
-    idx = (np.arange(360)[:, None] + jj[None, :] + 180) % 360
+    wd = l64.shape[0]
+    jj = np.arange(wd)
+    idx = (np.arange(wd)[:, None] + jj[None, :] + wd // 2) % wd
     corr = (l64 @ r64.T)[idx, jj[None, :]].sum(axis=1)
     rms = np.sqrt((np.square(l64) @ np.square(r64).T)[idx, jj[None, :]].sum(axis=1))
-    n = 360 * 128
+    n = wd * 128
     direct = SAFETY * _sigma("f32", n, corr, rms) + n * U_SUB + U_SUB
+    if wd != 360:
+        return {"corr": corr, "direct": direct}
     L, R = np.fft.fft(l64, axis=0), np.fft.fft(r64, axis=0)                  # (360 f, 128 c)
 
     def sig_x(X, x):
@@ -298,18 +333,18 @@ def leg_with_bounds(images_nhwc: np.ndarray, weights, modes=("f16x3", "f32"), mo
 # Feature volumes on the value edges of the Delta head's fast paths (shared by the CPU fault-power test and the GPU tests)
 # --------------------------------------------------------------------------------------------------------------------------------
 
-def _relu_vol(rng, k=1, mean=0.2):
-    return np.maximum(rng.normal(mean, 1.0, size=(k, 360, 128)), 0).astype(np.float32)
+def _relu_vol(rng, k=1, mean=0.2, width=360):
+    return np.maximum(rng.normal(mean, 1.0, size=(k, width, 128)), 0).astype(np.float32)
 
 
-def value_edge_sets(seed: int = 0) -> Dict[str, np.ndarray]:
-    """name -> (k, 360, 128) float32 volumes.  Volume 0 is the query of the 1-vs-N routes, all of them its candidates (the
+def value_edge_sets(seed: int = 0, width: int = 360) -> Dict[str, np.ndarray]:
+    """name -> (k, width, 128) float32 volumes.  Volume 0 is the query of the 1-vs-N routes, all of them its candidates (the
     single_column and pow2_edge sets are also swept with other queries: their edges are properties of the query)."""
     rng = np.random.default_rng(seed)
     f32 = np.float32
     out = {}
     # -0.0: scattered through query and candidates, an all -0.0 volume, -0.0 as a volume's minimum (no negative value anywhere)
-    v = _relu_vol(rng, 4)
+    v = _relu_vol(rng, 4, width=width)
     for i in (0, 1):
         z = v[i] == 0
         v[i][z & (rng.random(z.shape) < 0.5)] = f32(-0.0)
@@ -317,22 +352,22 @@ def value_edge_sets(seed: int = 0) -> Dict[str, np.ndarray]:
     v[3][v[3] == 0] = f32(-0.0)
     out["neg_zero"] = v
     # subnormals: a volume of subnormals only, subnormals in place of the zeros of O(1) volumes
-    v = _relu_vol(rng, 4)
-    v[1] = (rng.random((360, 128)) * 1e-39).astype(f32)
+    v = _relu_vol(rng, 4, width=width)
+    v[1] = (rng.random((width, 128)) * 1e-39).astype(f32)
     for i in (0, 2):
         z = v[i] == 0
         v[i][z] = (rng.random(int(z.sum())) * 1e-38).astype(f32)
     out["subnormal"] = v
     # one value of -1e-30 in the query (shift on, no compaction), and in a candidate
-    v = _relu_vol(rng, 3)
+    v = _relu_vol(rng, 3, width=width)
     v[0][:, 100:] = 0
     v[0, 17, 5] = f32(-1e-30)
-    v[2, 200, 60] = f32(-1e-30)
+    v[2, 200 * width // 360, 60] = f32(-1e-30)
     out["tiny_negative"] = v
     # largest values at exactly 2^k and one ulp around it: volumes 0, 1, 2 (4, 4 - ulp, 4 + ulp) each serve as the query of a
     # sweep over all six (tests/test_gpu_error_bounds.py), so the query's own bucket and the candidates' buckets meet in both
     # orders: both sides of the cache-row validity rule and of the scale bucket edge
-    base = _relu_vol(rng, 6)
+    base = _relu_vol(rng, 6, width=width)
     tops = [f32(4.0), np.nextafter(f32(4.0), f32(0)), np.nextafter(f32(4.0), f32(8)), f32(4.0), np.nextafter(f32(4.0), f32(8)),
             np.nextafter(f32(4.0), f32(0))]
     for i, t in enumerate(tops):
@@ -340,24 +375,24 @@ def value_edge_sets(seed: int = 0) -> Dict[str, np.ndarray]:
         base[i, 11 + i, 7 * i] = t
     out["pow2_edge"] = base
     # channels alive in exactly one query column (O(1) value), live counts 97, 111, 112, 113 -> packed last slices of 1, 15, 16, 17
-    q = np.zeros((5, 360, 128), f32)
+    q = np.zeros((5, width, 128), f32)
     perm = rng.permutation(128)
     for i, live in enumerate((97, 111, 112, 113)):
         ch = perm[:live]
-        q[i][:, ch] = np.maximum(rng.normal(0.2, 1.0, size=(360, live)), 0)
+        q[i][:, ch] = np.maximum(rng.normal(0.2, 1.0, size=(width, live)), 0)
         q[i][:, ch[:8]] = 0
-        q[i][rng.integers(0, 360, 8), ch[:8]] = f32(1.0)          # alive in one column each
-    q[4] = _relu_vol(rng)[0]
+        q[i][rng.integers(0, width, 8), ch[:8]] = f32(1.0)          # alive in one column each
+    q[4] = _relu_vol(rng, width=width)[0]
     out["single_column"] = q
     # exact ties: duplicated columns, and the query among its own candidates
-    v = _relu_vol(rng, 3)
-    v[0][180:] = v[0][:180]
+    v = _relu_vol(rng, 3, width=width)
+    v[0][width - width // 2:] = v[0][:width // 2]
     v[1] = v[0]
     v[2][:, :64] = v[0][:, :64]
     out["ties"] = v
     # wide ranges in one volume, and large spans
-    v = _relu_vol(rng, 4)
-    v[0] *= np.where(rng.random((360, 128)) < 0.5, f32(1e-6), f32(1e4)).astype(f32)
+    v = _relu_vol(rng, 4, width=width)
+    v[0] *= np.where(rng.random((width, 128)) < 0.5, f32(1e-6), f32(1e4)).astype(f32)
     v[2] *= f32(1e20)
     v[3] *= f32(1e30)
     v[3][:, 64:] = 0

@@ -508,6 +508,12 @@ static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lid
       }
       if (rc) return rc;
     }
+    if (wide && n > 0 && n <= chunk) {   // one chunk: its o2 / o3 regions (ovn_delta_w_forward) hold every pair for the test hook
+      const size_t o2w = (size_t)n * ctx->head_g * ctx->head_g * OVN_C2_OUT * sizeof(float);
+      ctx->dbg_o2 = static_cast<const float*>(ctx->ws);
+      ctx->dbg_o3 = reinterpret_cast<const float*>(static_cast<const char*>(ctx->ws) + ((o2w + 255) & ~(size_t)255));
+      ctx->dbg_n = n;
+    }
     return OVN_OK;
   }
   const size_t o2_elems = (size_t)OVN_G * OVN_G * OVN_C2_OUT;   // 24*24*128 per pair
@@ -1039,12 +1045,13 @@ int ovn_debug_head_activations(ovn_ctx* ctx, int64_t n, float* o2_dev, float* o3
   OVN_REQUIRE(ctx && ctx->dbg_o2 && n >= 0 && n <= ctx->dbg_n, OVN_ERR_STATE,
               "ovn_debug_head_activations: call right after ovn_heads with n <= its (first-chunk) pair count");
   OVN_ON_DEVICE(ctx->device);
+  const size_t g = (size_t)ctx->head_g;   // 24 at W = 360; W // 15 on the width path (delta_head_w.hip)
   if (o2_dev)
-    OVN_HIP_CHECK(hipMemcpyAsync(o2_dev, ctx->dbg_o2, (size_t)n * OVN_G * OVN_G * OVN_C2_OUT * sizeof(float),
+    OVN_HIP_CHECK(hipMemcpyAsync(o2_dev, ctx->dbg_o2, (size_t)n * g * g * OVN_C2_OUT * sizeof(float),
                                  hipMemcpyDeviceToDevice, (hipStream_t)stream));
   if (o3_dev && ctx->dbg_o3)
-    OVN_HIP_CHECK(hipMemcpyAsync(o3_dev, ctx->dbg_o3, (size_t)n * OVN_DENSE_IN * sizeof(float), hipMemcpyDeviceToDevice,
-                                 (hipStream_t)stream));
+    OVN_HIP_CHECK(hipMemcpyAsync(o3_dev, ctx->dbg_o3, (size_t)n * (g - 2) * (g - 2) * OVN_C3_OUT * sizeof(float),
+                                 hipMemcpyDeviceToDevice, (hipStream_t)stream));
   else if (o3_dev)  // f16x3 mode: o3 never left the fused kernel -- run it again on the o2 still in scratch, with o3 output
     return ovn_c3_dense_forward(ctx, ctx->dbg_o2, ctx->dbg_o2max, (int)n, ctx->dbg_partial, o3_dev, nullptr, nullptr, nullptr, (hipStream_t)stream);
   return OVN_OK;

@@ -572,9 +572,11 @@ class OvnEngine:
         return yaw, pitch, pix
 
     def debug_head_activations(self, n: int):
-        """(o2 (n,24,24,128), o3 (n,22,22,256)) left in scratch by the last heads() call -- test hook."""
-        o2 = torch.empty((n, 24, 24, 128), dtype=torch.float32, device=self.device)
-        o3 = torch.empty((n, 22, 22, 256), dtype=torch.float32, device=self.device)
+        """(o2 (n,G,G,128), o3 (n,G-2,G-2,256)), G = feat_w // 15, left in scratch by the last heads() call -- test hook.
+        At feat_w != 360 only a heads() call that ran as one chunk keeps them."""
+        g = self._fw // 15
+        o2 = torch.empty((n, g, g, 128), dtype=torch.float32, device=self.device)
+        o3 = torch.empty((n, g - 2, g - 2, 256), dtype=torch.float32, device=self.device)
         with self._dev():
             _lib.check(self.lib.ovn_debug_head_activations(self._h, n, _ptr(o2), _ptr(o3), self._stream()),
                        "ovn_debug_head_activations")

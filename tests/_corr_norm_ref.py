@@ -2,7 +2,8 @@
 the normalised correlation vector -- test infrastructure shared by tests/test_corr_normalize.py (CPU) and
 tests/test_gpu_corr_normalize.py.
 
-A feature volume is (360, 128); Keras normalises over axis 2 of (1, 1, 360, 128), the 360 columns, per channel:
+A feature volume is (W, 128), W = 360 for the reference leg; Keras normalises over axis 2 of (1, 1, W, 128), the W columns, per
+channel:
     none             x
     euclidean        x / sqrt(max(sum x^2, 1e-12))                        (K.l2_normalize, epsilon 1e-12)
     scaling          (x - min x) / (max x - min x + 1e-6)
@@ -18,7 +19,7 @@ MODES = ("none", "euclidean", "scaling", "standardization")
 
 
 def affine64(v, mode):
-    """(m, a, s) per channel, fp64, so that x' = ((x - m) + a) s; v (..., 360, 128)."""
+    """(m, a, s) per channel, fp64, so that x' = ((x - m) + a) s; v (..., W, 128)."""
     x = np.asarray(v, np.float64)
     zero = np.zeros(x.shape[:-2] + (1, x.shape[-1]))
     if mode == "none":
@@ -55,15 +56,16 @@ def normalize32(v, mode):
 
 
 def _wrapped(a, b):
-    """sum_j sum_c a[(k + j + 180) mod 360, c] b[j, c] for k = 0..359 (the correlation's shift structure), fp64."""
-    jj = np.arange(360)
-    idx = (np.arange(360)[:, None] + jj[None, :] + 180) % 360
+    """sum_j sum_c a[(k + j + W // 2) mod W, c] b[j, c] for k = 0..W-1 (the correlation's shift structure), fp64; W = a.shape[0]."""
+    wd = np.shape(a)[0]
+    jj = np.arange(wd)
+    idx = (np.arange(wd)[:, None] + jj[None, :] + wd // 2) % wd
     return (np.asarray(a, np.float64) @ np.asarray(b, np.float64).T)[idx, jj[None, :]].sum(axis=1)
 
 
 def norm_sigma(v, mode):
     """Elementwise error of the stored normalised value against the fp64 truth: one fp32 rounding (u |x'|) plus the fp64 error of the
-    statistics carried by s (a few hundred fp64 roundings of |x| in the sums: 2^-44 s max|x|), plus the subnormal floor."""
+    statistics carried by s (at most 512 fp64 roundings of |x| in the sums: 2^-44 s max|x|), plus the subnormal floor."""
     if mode == "none":
         return np.zeros(np.shape(v))
     x = np.asarray(v, np.float64)
@@ -73,18 +75,21 @@ def norm_sigma(v, mode):
 
 
 def corr_norm_pair(l, r, mode):
-    """{'corr': fp64 normalised correlation (360,), 'direct' / 'spectral': elementwise bounds}.
+    """{'corr': fp64 normalised correlation (W,), 'direct' / 'spectral': elementwise bounds ('spectral' at W = 360 only).
 
     The bound is E.corr_pair's on the fp64-normalised volumes (the correlation kernels' own arithmetic on those operands) plus the
     normalisation's rounding carried through the correlation: with stored values l' + dl, r' + dr the correlation moves by
     sum (l' dr + dl r') + O(d^2); the elementwise errors are independent roundings, so per shift they add in quadrature:
-        sigma_k^2 = sum_j sum_c (l'[(k+j+180) mod 360, c]^2 sigma_r[j, c]^2 + sigma_l[(k+j+180) mod 360, c]^2 r'[j, c]^2)
+        sigma_k^2 = sum_j sum_c (l'[(k+j+W//2) mod W, c]^2 sigma_r[j, c]^2 + sigma_l[(k+j+W//2) mod W, c]^2 r'[j, c]^2)
     and the bound adds SAFETY sigma_k (SAFETY = 6, as everywhere in oracle/error_bounds.py)."""
     ln, rn = normalize64(l, mode), normalize64(r, mode)
     c = E.corr_pair(ln, rn)
     sl, sr = norm_sigma(l, mode), norm_sigma(r, mode)
     carried = E.SAFETY * np.sqrt(_wrapped(np.square(ln), np.square(sr)) + _wrapped(np.square(sl), np.square(rn)))
-    return {"corr": c["corr"], "direct": c["direct"] + carried, "spectral": c["spectral"] + carried}
+    out = {"corr": c["corr"], "direct": c["direct"] + carried}
+    if "spectral" in c:
+        out["spectral"] = c["spectral"] + carried
+    return out
 
 
 def yaw_ok(gpu_corr_row, gpu_bin, ref_corr, bound):
@@ -98,24 +103,25 @@ def yaw_ok(gpu_corr_row, gpu_bin, ref_corr, bound):
     return ref_corr[int(gpu_bin)] >= srt[-1] - 2 * b
 
 
-def edge_volume(seed=0):
-    """(360, 128) float32: random ReLU channels and dead channels next to the edge channels of every mode -- all zero, constant,
+def edge_volume(seed=0, width=360):
+    """(width, 128) float32: random ReLU channels and dead channels next to the edge channels of every mode -- all zero, constant,
     one non-zero column, negative values, 2^100, 2^-100, subnormals, a small-range channel (the +1e-6 / +1e-5 constants matter)
     and a large near-constant one."""
     rng = np.random.default_rng(seed)
-    v = np.maximum(rng.normal(0.2, 1.0, size=(360, 128)), 0).astype(np.float32)
+    wd = width
+    v = np.maximum(rng.normal(0.2, 1.0, size=(wd, 128)), 0).astype(np.float32)
     v[:, 0:8] = 0                                                            # dead
     v[:, 8] = np.float32(3.25)                                               # constant
     v[:, 9] = 0
-    v[int(rng.integers(360)), 9] = np.float32(2.5)                           # one non-zero column
-    v[:, 10] = rng.normal(0.0, 1.0, 360).astype(np.float32)                 # negative values
-    v[:, 11] = -np.abs(rng.normal(0.0, 1.0, 360)).astype(np.float32)
-    v[:, 12] = (np.float32(2.0 ** 100) * rng.random(360)).astype(np.float32)
-    v[:, 13] = (np.float32(2.0 ** -100) * rng.random(360)).astype(np.float32)
-    v[:, 14] = (rng.random(360) * 1e-39).astype(np.float32)                 # subnormal
-    v[:, 15] = (rng.random(360) * 3e-7).astype(np.float32)                  # range below the +1e-6 of 'scaling'
-    v[:, 16] = (rng.random(360) * 2e-6).astype(np.float32)                  # values below the +1e-5 of 'standardization'
-    v[:, 17] = np.float32(1000.0) + (rng.random(360) * 0.01).astype(np.float32)   # large, near-constant
+    v[int(rng.integers(wd)), 9] = np.float32(2.5)                           # one non-zero column
+    v[:, 10] = rng.normal(0.0, 1.0, wd).astype(np.float32)                 # negative values
+    v[:, 11] = -np.abs(rng.normal(0.0, 1.0, wd)).astype(np.float32)
+    v[:, 12] = (np.float32(2.0 ** 100) * rng.random(wd)).astype(np.float32)
+    v[:, 13] = (np.float32(2.0 ** -100) * rng.random(wd)).astype(np.float32)
+    v[:, 14] = (rng.random(wd) * 1e-39).astype(np.float32)                 # subnormal
+    v[:, 15] = (rng.random(wd) * 3e-7).astype(np.float32)                  # range below the +1e-6 of 'scaling'
+    v[:, 16] = (rng.random(wd) * 2e-6).astype(np.float32)                  # values below the +1e-5 of 'standardization'
+    v[:, 17] = np.float32(1000.0) + (rng.random(wd) * 0.01).astype(np.float32)   # large, near-constant
     return v
 
 
@@ -124,7 +130,7 @@ def rolled(v, s):
     return np.roll(np.asarray(v), s, axis=0)
 
 
-def known_bin(s):
-    """The correlation bin at which r = rolled(l, s) peaks: corr[k] pairs l[(k + j + 180) mod 360] with r[j] = l[j - s], so the
-    peak is where k + 180 = -s (mod 360)."""
-    return (-s - 180) % 360
+def known_bin(s, W=360):
+    """The correlation bin at which r = rolled(l, s) peaks: corr[k] pairs l[(k + j + W // 2) mod W] with r[j] = l[j - s], so the
+    peak is where k + W // 2 = -s (mod W)."""
+    return (-s - W // 2) % W
