@@ -274,6 +274,28 @@ int ovn_project(ovn_ctx* ctx, const float* points_dev, const int64_t* offsets_de
                 int32_t* idx_dev, float* normal_dev, float* stacked_dev, int use_depth, int use_normals,
                 int use_intensity, void* stream);
 
+/* ovn_project plus the class probabilities of the semantic model (use_class_probabilities: gen_semantic_data.py:33-46 and
+ * ImagePairOverlapOrientationSequence.py:165-195), from the raw scans in one launch sequence.
+ *   probs_dev     (offsets[n_scans], n_classes) float32: one row per point, rows in the order and with the offsets of points_dev;
+ *                 may be NULL when neither semantic_dev nor a stacked output with use_semantic is requested
+ *   n_classes     1 .. OVN_SEMANTIC_CLASSES_MAX (RangeNet++: 20)
+ *   semantic_dev  (n,H,W,n_classes) or NULL: probs[sem_idx] at every pixel with a point, -1 elsewhere
+ *   sem_idx_dev   (n,H,W) int32 or NULL: the reference's proj_idx with max_range = inf -- the winner's index among the points with
+ *                 depth > 0 and finite.  As in the reference it addresses the UNFILTERED probability rows: a scan with zero-depth or
+ *                 NaN points ahead of the winner reads a shifted row (the semantic .npy files a model was trained on were made so)
+ *   stacked_dev   (n,H,W,C), C = use_depth + 3 use_normals + n_classes use_semantic + use_intensity: depth | normals |
+ *                 probabilities | intensity, the reference's channel order
+ * range / vertex / intensity / idx / normal are bit for bit what ovn_project writes at the same max_range, and so are the
+ * depth / normal / intensity channels of stacked_dev.  One scatter serves both views: a pixel's nearest point under the semantic
+ * filter is its nearest cue point when its depth is < max_range, and otherwise the pixel has no cue point.  OVN_ERR_ARG for
+ * n_classes outside 1..OVN_SEMANTIC_CLASSES_MAX, a NULL probs_dev with a probability output, more than 65535 scans. */
+#define OVN_SEMANTIC_CLASSES_MAX 64
+int ovn_project_semantic(ovn_ctx* ctx, const float* points_dev, const int64_t* offsets_dev, int n_scans,
+                         int64_t max_points_per_scan, int proj_h, int proj_w, double fov_up_deg, double fov_down_deg,
+                         double max_range, const float* probs_dev, int n_classes, float* range_dev, float* vertex_dev,
+                         float* intensity_dev, int32_t* idx_dev, float* normal_dev, float* semantic_dev, int32_t* sem_idx_dev,
+                         float* stacked_dev, int use_depth, int use_normals, int use_semantic, int use_intensity, void* stream);
+
 /* Normal map alone from given range (n,H,W) and vertex (n,H,W,4) images -> normal (n,H,W,3)
  * (src/utils/utils.py:137-186 gen_normal_map). */
 int ovn_normals(ovn_ctx* ctx, const float* range_dev, const float* vertex_dev, int n_scans, int proj_h, int proj_w,

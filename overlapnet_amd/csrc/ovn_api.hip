@@ -902,6 +902,26 @@ int ovn_project(ovn_ctx* ctx, const float* points_dev, const int64_t* offsets_de
                              stacked_dev, use_depth, use_normals, use_intensity, (hipStream_t)stream);
 }
 
+int ovn_project_semantic(ovn_ctx* ctx, const float* points_dev, const int64_t* offsets_dev, int n_scans,
+                         int64_t max_points_per_scan, int proj_h, int proj_w, double fov_up_deg, double fov_down_deg,
+                         double max_range, const float* probs_dev, int n_classes, float* range_dev, float* vertex_dev,
+                         float* intensity_dev, int32_t* idx_dev, float* normal_dev, float* semantic_dev, int32_t* sem_idx_dev,
+                         float* stacked_dev, int use_depth, int use_normals, int use_semantic, int use_intensity, void* stream) {
+  OVN_REQUIRE(n_classes >= 1 && n_classes <= OVN_SEMANTIC_CLASSES_MAX, OVN_ERR_ARG,
+              "ovn_project_semantic: n_classes %d outside 1..%d", n_classes, OVN_SEMANTIC_CLASSES_MAX);
+  OVN_REQUIRE(probs_dev || !(semantic_dev || (stacked_dev && use_semantic)), OVN_ERR_ARG,
+              "ovn_project_semantic: probabilities requested but probs is NULL");
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_project_semantic: ctx is NULL");
+  OVN_REQUIRE(n_scans == 0 || (points_dev || max_points_per_scan == 0), OVN_ERR_ARG, "ovn_project_semantic: points is NULL");
+  OVN_REQUIRE(n_scans == 0 || offsets_dev, OVN_ERR_ARG, "ovn_project_semantic: offsets is NULL");
+  OVN_ON_DEVICE(ctx->device);
+  OvnProfScope ps(ctx, OVN_K_PROJ, (hipStream_t)stream);
+  return ovn_project_semantic_forward(ctx, points_dev, offsets_dev, n_scans, max_points_per_scan, proj_h, proj_w, fov_up_deg,
+                                      fov_down_deg, max_range, probs_dev, n_classes, range_dev, vertex_dev, intensity_dev, idx_dev,
+                                      normal_dev, semantic_dev, sem_idx_dev, stacked_dev, use_depth, use_normals, use_semantic,
+                                      use_intensity, (hipStream_t)stream);
+}
+
 int ovn_projection_angles(ovn_ctx* ctx, const float* points_dev, int64_t n_points, int proj_h, int proj_w, double fov_up_deg,
                           double fov_down_deg, double max_range, float* yaw_dev, float* pitch_dev, int32_t* pixel_dev,
                           void* stream) {

@@ -463,6 +463,11 @@ int ovn_project_forward(ovn_ctx* ctx, const float* points, const int64_t* offset
                         float* normal, float* stacked, int use_depth, int use_normals, int use_intensity,
                         hipStream_t stream);
 
+int ovn_project_semantic_forward(ovn_ctx* ctx, const float* points, const int64_t* offsets, int n_scans, int64_t max_points, int H,
+                                 int W, double fov_up_deg, double fov_down_deg, double max_range, const float* probs, int n_classes,
+                                 float* range, float* vertex, float* intensity, int32_t* idx, float* normal, float* semantic,
+                                 int32_t* sem_idx, float* stacked, int use_depth, int use_normals, int use_semantic, int use_intensity,
+                                 hipStream_t stream);
 int ovn_projection_angles_forward(const float* points, int64_t n, int H, int W, double fov_up_deg, double fov_down_deg,
                                   double max_range, float* yaw, float* pitch, int32_t* pixel, hipStream_t stream, int trig = 0);
 int ovn_normals_forward(const float* range, const float* vertex, int n_scans, int H, int W, float* normal,

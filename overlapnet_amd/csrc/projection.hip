@@ -21,6 +21,8 @@
 #include "ovn_internal.h"
 #include "svml_f32.h"
 
+#include <cstring>
+
 namespace {
 
 constexpr unsigned long long EMPTY_KEY = 0xFFFFFFFFFFFFFFFFull;
@@ -395,6 +397,299 @@ int ovn_project_forward(ovn_ctx* ctx, const float* points, const int64_t* offset
   hipLaunchKernelGGL(proj_resolve_kernel, dim3(gblocks), dim3(256), 0, stream, points, reinterpret_cast<const long long*>(offsets),
                      keys, local_idx, block_cnt, blocks_per_scan, (long long)max_points, H, W, n_scans, range, vertex, intensity, idx,
                      normal, stacked, use_depth, use_normals, use_intensity, C);
+  OVN_HIP_CHECK(hipGetLastError());
+  return OVN_OK;
+}
+
+// ---- ovn_project_semantic: the cue images of ovn_project plus the reference's projected class probabilities ----------------------
+// gen_semantic_data.py:33-46 projects with max_range = inf and gathers probs[proj_idx], proj_idx counted after ITS filter
+// (depth > 0, finite).  The cue points (depth > 0, depth < max_range) are a subset of those, and the key orders by depth first:
+// a pixel's semantic winner is its cue winner when its depth is < max_range, and otherwise the pixel holds no cue point at all
+// (ties resolve the same way in both views: lower point index).  So ONE scatter under the semantic filter gives both views; the
+// resolve treats a key whose depth is >= max_range as empty for every cue (the pixel and both neighbours of its normal).
+namespace {
+
+typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));   // dword-aligned: gfx950 issues it as one dwordx4 access
+
+constexpr int MASK_WORDS = PB / 64;   // keep-mask words per scatter block
+
+// grid = (blocks_per_scan, n_scans); gm.max_range = +inf (the semantic filter).  Besides the keys: one keep mask per 64 points and
+// per view (bit i of word w = point 64 w + i kept; view 0 semantic, view 1 cue) and each block's kept count per view.  A point's
+// index among the kept points of its scan is then its block's exclusive prefix + the kept bits below it (kept_rank).
+__global__ __launch_bounds__(PB) void proj_sem_scatter_kernel(const float* __restrict__ points, const long long* __restrict__ offsets,
+                                                              ProjGeom gm, float cue_max_range, unsigned long long* __restrict__ keys,
+                                                              unsigned long long* __restrict__ masks, int* __restrict__ block_cnt,
+                                                              int blocks_per_scan, int n_scans) {
+  __shared__ int wave_cnt[2][PB / 64];
+  const int scan = blockIdx.y;
+  const long long beg = offsets[scan];
+  const long long npts = offsets[scan + 1] - beg;
+  const long long p = (long long)blockIdx.x * PB + threadIdx.x;
+  bool keep = false;
+  float depth = 0.f;
+  int pix = 0;
+  if (p < npts) {
+    const f32x4 pt = *reinterpret_cast<const f32x4*>(points + (beg + p) * 4);
+    float yaw, pitch;
+    keep = point_to_pixel(pt[0], pt[1], pt[2], gm, depth, yaw, pitch, pix);
+  }
+  const int lane = threadIdx.x & 63;
+  {
+    // runs of lanes with the same pixel issue one atomicMin per four lanes, as in proj_scatter_kernel
+    unsigned long long key = ((unsigned long long)__float_as_uint(depth) << 32) | (unsigned long long)(unsigned)p;
+    const int ppix = __shfl_up(pix, 1, 64);
+    const int pkeep = __shfl_up((int)keep, 1, 64);
+    const bool head = keep && (lane == 0 || !pkeep || ppix != pix);
+    const unsigned long long hm = __ballot(head);
+    const unsigned long long le = hm & (lane == 63 ? ~0ull : ((2ull << lane) - 1ull));
+    const int hpos = le ? 63 - __clzll((long long)le) : -1;
+    const int run = keep ? hpos : -2 - lane;
+#pragma unroll
+    for (int d = 1; d <= 2; d <<= 1) {
+      const unsigned long long kd = __shfl_down(key, d, 64);
+      const int rd = __shfl_down(run, d, 64);
+      if (lane + d < 64 && rd == run && kd < key) key = kd;
+    }
+    if (keep && ((lane - hpos) & 3) == 0) atomicMin(&keys[(long long)scan * gm.H * gm.W + pix], key);
+  }
+  if (masks) {
+    const unsigned long long ms = __ballot(keep);
+    const unsigned long long mc = __ballot(keep && depth < cue_max_range);   // utils.py:76-77 at the caller's max_range
+    const int wave = threadIdx.x >> 6;
+    const long long wps = (long long)blocks_per_scan * MASK_WORDS;
+    if (lane == 0) {
+      masks[(long long)scan * wps + blockIdx.x * MASK_WORDS + wave] = ms;
+      masks[((long long)n_scans + scan) * wps + blockIdx.x * MASK_WORDS + wave] = mc;
+      wave_cnt[0][wave] = __popcll(ms);
+      wave_cnt[1][wave] = __popcll(mc);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+      int tot = 0;
+      for (int w = 0; w < PB / 64; ++w) tot += wave_cnt[threadIdx.x][w];
+      block_cnt[((long long)threadIdx.x * n_scans + scan) * blocks_per_scan + blockIdx.x] = tot;
+    }
+  }
+}
+
+// index of scan-local point p among the kept points of its scan (utils.py:117-118) from one view's masks / block prefixes
+__device__ __forceinline__ int kept_rank(const unsigned long long* __restrict__ m, const int* __restrict__ bpref, long long p) {
+  const long long w = p >> 6;
+  const long long b = p / PB;
+  int r = bpref[b];
+  for (long long j = b * MASK_WORDS; j < w; ++j) r += __popcll(m[j]);
+  return r + __popcll(m[w] & ((1ull << (p & 63)) - 1ull));
+}
+
+// n floats of a register array to a dword-aligned row: dwordx4 stores, then the remainder
+template <int N>
+__device__ __forceinline__ void store_row(float* __restrict__ o, const float* r) {
+#pragma unroll
+  for (int i = 0; i + 4 <= N; i += 4) *reinterpret_cast<f32x4u*>(o + i) = (f32x4u){r[i], r[i + 1], r[i + 2], r[i + 3]};
+#pragma unroll
+  for (int i = N & ~3; i < N; ++i) o[i] = r[i];
+}
+
+// One thread per pixel, tiles and XCD grouping as proj_resolve_kernel.  NC > 0: n_classes == NC known at compile time, the winner's
+// probability row read with dwordx4 loads into registers and the semantic / stacked rows written with dwordx4 stores (stacked at
+// depth | normals | probabilities [| intensity] as one register row); NC == 0: any n_classes, one float at a time.
+template <int NC>
+__global__ __launch_bounds__(256) void proj_sem_resolve_kernel(
+    const float* __restrict__ points, const long long* __restrict__ offsets, const unsigned long long* __restrict__ keys,
+    const unsigned long long* __restrict__ masks, const int* __restrict__ block_pref, int blocks_per_scan, int H, int W, int n_scans,
+    unsigned long long cue_lim, const float* __restrict__ probs, int n_classes, float* __restrict__ range, float* __restrict__ vertex,
+    float* __restrict__ intensity, int32_t* __restrict__ idx, float* __restrict__ normal, float* __restrict__ semantic,
+    int32_t* __restrict__ sem_idx, float* __restrict__ stacked, int cues) {
+  // cues: bit 0 depth, 1 normals, 2 probabilities, 3 intensity
+  const int nc = NC > 0 ? NC : n_classes;
+  const bool use_depth = cues & 1, use_normals = cues & 2, use_semantic = cues & 4, use_intensity = cues & 8;
+  const int C = (int)use_depth + 3 * (int)use_normals + nc * (int)use_semantic + (int)use_intensity;
+  const int HW = H * W;
+  const bool want_n = (normal != nullptr) || (stacked != nullptr && use_normals);
+  const bool want_p = (semantic != nullptr) || (stacked != nullptr && use_semantic);
+  const bool want_srank = want_p || sem_idx != nullptr;
+  const long long wps = (long long)blocks_per_scan * MASK_WORDS;
+  constexpr int TR = 8, TC = 32;
+  const int tiles_x = (W + TC - 1) / TC, tiles_y = (H + TR - 1) / TR;
+  const int tps = tiles_y * tiles_x;
+  const long long n_tiles = (long long)((n_scans + 7) / 8) * 8 * tps;
+  const int ty = threadIdx.x / TC, tx = threadIdx.x - ty * TC;
+  const long long tile = blockIdx.x;   // one tile per workgroup: the grid-stride loop of proj_resolve_kernel spilled SGPRs here
+  if (tile >= n_tiles) return;
+  const long long k = tile >> 3;
+  const int scan = (int)(tile & 7) + 8 * (int)(k / tps);
+  if (scan >= n_scans) return;
+  const int tin = (int)(k % tps);
+  const int tyi = tin / tiles_x;
+  const int py = tyi * TR + ty, px = (tin - tyi * tiles_x) * TC + tx;
+  if (py >= H || px >= W) return;
+  const int pix = py * W + px;
+  const long long sbase = (long long)scan * HW;
+  const long long q = sbase + pix;
+  const float* pts = points + offsets[scan] * 4;
+  const unsigned long long key = keys[q];
+  const long long p = (long long)(key & 0xFFFFFFFFull);
+  f32x4 v = {-1.f, -1.f, -1.f, -1.f};
+  float d = -1.f, it = -1.f, nx = -1.f, ny = -1.f, nz = -1.f;
+  int id = -1, sid = -1;
+  if (key < cue_lim) {   // the semantic winner is the cue winner (depth < max_range)
+    const f32x4 pt = *reinterpret_cast<const f32x4*>(pts + p * 4);
+    d = __uint_as_float((unsigned)(key >> 32));
+    it = pt[3];
+    v = (f32x4){pt[0], pt[1], pt[2], 1.0f};
+    if (idx) id = kept_rank(masks + ((long long)n_scans + scan) * wps, block_pref + ((long long)n_scans + scan) * blocks_per_scan, p);
+    if (want_n && py < H - 1) {
+      const int xr = (px + 1 >= W) ? (px + 1 - W) : (px + 1);   // wrap(), utils.py:178-186
+      const unsigned long long ku = keys[sbase + (long long)py * W + xr];
+      const unsigned long long kv = keys[sbase + (long long)(py + 1) * W + px];
+      if (ku < cue_lim && kv < cue_lim) {                       // both neighbours hold a cue point
+        const f32x4 pu = *reinterpret_cast<const f32x4*>(pts + (long long)(ku & 0xFFFFFFFFull) * 4);
+        const f32x4 pv = *reinterpret_cast<const f32x4*>(pts + (long long)(kv & 0xFFFFFFFFull) * 4);
+        normal_of(pt, pu, pv, nx, ny, nz);
+      }
+    }
+  }
+  // the reference's proj_idx under the semantic filter; it addresses the UNFILTERED probability rows (gen_semantic_data.py:44)
+  if (want_srank && key != EMPTY_KEY)
+    sid = kept_rank(masks + (long long)scan * wps, block_pref + (long long)scan * blocks_per_scan, p);
+  const float* prow = (want_p && sid >= 0) ? probs + (offsets[scan] + sid) * (long long)nc : nullptr;
+  if (range) range[q] = d;
+  if (vertex) *reinterpret_cast<f32x4*>(vertex + q * 4) = v;
+  if (intensity) intensity[q] = it;
+  if (idx) idx[q] = id;
+  if (sem_idx) sem_idx[q] = sid;
+  if (normal) {
+    normal[q * 3 + 0] = nx;
+    normal[q * 3 + 1] = ny;
+    normal[q * 3 + 2] = nz;
+  }
+  if constexpr (NC > 0) {
+    float pr[NC];
+    if (want_p) {
+      if (prow) {
+#pragma unroll
+        for (int c = 0; c < NC; c += 4) {   // NC % 4 == 0, the row 16-byte aligned (the host checks)
+          const f32x4 t = *reinterpret_cast<const f32x4*>(prow + c);
+          pr[c] = t[0];
+          pr[c + 1] = t[1];
+          pr[c + 2] = t[2];
+          pr[c + 3] = t[3];
+        }
+      } else {
+#pragma unroll
+        for (int c = 0; c < NC; ++c) pr[c] = -1.f;
+      }
+    }
+    if (semantic) store_row<NC>(semantic + q * NC, pr);
+    if (stacked && use_depth && use_normals && use_semantic) {   // the semantic model's own input: C = 4 + NC (+ 1)
+      float r[NC + 5];
+      r[0] = d;
+      r[1] = nx;
+      r[2] = ny;
+      r[3] = nz;
+#pragma unroll
+      for (int c = 0; c < NC; ++c) r[4 + c] = pr[c];
+      r[NC + 4] = it;
+      if (use_intensity) store_row<NC + 5>(stacked + q * C, r);
+      else store_row<NC + 4>(stacked + q * C, r);
+    } else if (stacked) {
+      float* o = stacked + q * C;
+      int c = 0;
+      if (use_depth) o[c++] = d;
+      if (use_normals) {
+        o[c++] = nx;
+        o[c++] = ny;
+        o[c++] = nz;
+      }
+      if (use_semantic) {
+#pragma unroll
+        for (int j = 0; j < NC; ++j) o[c++] = pr[j];
+      }
+      if (use_intensity) o[c++] = it;
+    }
+  } else {
+    if (semantic) {
+      float* o = semantic + q * nc;
+      for (int j = 0; j < nc; ++j) o[j] = prow ? prow[j] : -1.f;
+    }
+    if (stacked) {
+      float* o = stacked + q * C;
+      int c = 0;
+      if (use_depth) o[c++] = d;
+      if (use_normals) {
+        o[c++] = nx;
+        o[c++] = ny;
+        o[c++] = nz;
+      }
+      if (use_semantic)
+        for (int j = 0; j < nc; ++j) o[c++] = prow ? prow[j] : -1.f;
+      if (use_intensity) o[c++] = it;
+    }
+  }
+}
+
+}  // namespace
+
+int ovn_project_semantic_forward(ovn_ctx* ctx, const float* points, const int64_t* offsets, int n_scans, int64_t max_points, int H,
+                                 int W, double fov_up_deg, double fov_down_deg, double max_range, const float* probs, int n_classes,
+                                 float* range, float* vertex, float* intensity, int32_t* idx, float* normal, float* semantic,
+                                 int32_t* sem_idx, float* stacked, int use_depth, int use_normals, int use_semantic, int use_intensity,
+                                 hipStream_t stream) {
+  OVN_REQUIRE(n_scans >= 0 && H > 0 && W > 0 && max_points >= 0, OVN_ERR_ARG, "ovn_project_semantic: bad sizes");
+  OVN_REQUIRE(max_points < (1ll << 32), OVN_ERR_ARG, "ovn_project_semantic: more than 2^32 points per scan");
+  OVN_REQUIRE(n_scans <= 65535, OVN_ERR_ARG, "ovn_project_semantic: at most 65535 scans per call");
+  const int C = (use_depth ? 1 : 0) + (use_normals ? 3 : 0) + (use_semantic ? n_classes : 0) + (use_intensity ? 1 : 0);
+  OVN_REQUIRE(!stacked || C > 0, OVN_ERR_ARG, "ovn_project_semantic: stacked output requested with no channel enabled");
+  const bool want_p = semantic || (stacked && use_semantic);
+  if (n_scans == 0) return OVN_OK;
+
+  const ProjGeom gm = make_geom(H, W, fov_up_deg, fov_down_deg, INFINITY, ctx->proj_trig);   // gen_semantic_data.py:39
+  const float cue_max = (float)max_range;                                                      // utils.py:76-77 (ProjGeom's cast)
+  // key < cue_lim  <=>  key != EMPTY and depth < cue_max (depth > 0: float bits order like the floats; NaN / <= 0 keeps nothing)
+  uint32_t cue_bits = 0;
+  std::memcpy(&cue_bits, &cue_max, 4);
+  const unsigned long long cue_lim = cue_max > 0.f ? ((unsigned long long)cue_bits << 32) : 0ull;
+
+  const long long HW = (long long)H * W;
+  const long long npix = HW * n_scans;
+  const int blocks_per_scan = (int)((max_points + PB - 1) / PB) > 0 ? (int)((max_points + PB - 1) / PB) : 1;
+  const bool ranks = idx || sem_idx || want_p;
+  size_t off = 0;
+  auto carve = [&](size_t bytes) {
+    size_t o = off;
+    off += (bytes + 255) & ~(size_t)255;
+    return o;
+  };
+  const size_t o_keys = carve((size_t)npix * 8);
+  const size_t o_mask = ranks ? carve((size_t)2 * n_scans * blocks_per_scan * MASK_WORDS * 8) : 0;
+  const size_t o_bcnt = ranks ? carve((size_t)2 * n_scans * blocks_per_scan * 4) : 0;
+  int rc = ovn_ws_reserve(ctx, off, stream);
+  if (rc) return rc;
+  char* ws = static_cast<char*>(ctx->ws);
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(ws + o_keys);
+  unsigned long long* masks = ranks ? reinterpret_cast<unsigned long long*>(ws + o_mask) : nullptr;
+  int* block_cnt = ranks ? reinterpret_cast<int*>(ws + o_bcnt) : nullptr;
+  const long long* offs = reinterpret_cast<const long long*>(offsets);
+
+  hipLaunchKernelGGL(proj_clear_kernel, dim3(1024), dim3(256), 0, stream, keys, npix);
+  if (max_points > 0) {
+    hipLaunchKernelGGL(proj_sem_scatter_kernel, dim3(blocks_per_scan, n_scans), dim3(PB), 0, stream, points, offs, gm, cue_max, keys,
+                       masks, block_cnt, blocks_per_scan, n_scans);
+    if (ranks) hipLaunchKernelGGL(proj_block_scan_kernel, dim3(2 * n_scans), dim3(64), 0, stream, block_cnt, blocks_per_scan);
+  }
+  const long long n_tiles = (long long)((n_scans + 7) / 8) * 8 * ((H + 7) / 8) * ((W + 31) / 32);
+  OVN_REQUIRE(n_tiles < (1ll << 31), OVN_ERR_ARG, "ovn_project_semantic: image batch too large");
+  const int gblocks = (int)n_tiles;
+  const int cues = (use_depth ? 1 : 0) | (use_normals ? 2 : 0) | (use_semantic ? 4 : 0) | (use_intensity ? 8 : 0);
+  const bool vec = n_classes == 20 && (reinterpret_cast<uintptr_t>(probs) & 15) == 0;
+  if (vec)
+    hipLaunchKernelGGL(proj_sem_resolve_kernel<20>, dim3(gblocks), dim3(256), 0, stream, points, offs, keys, masks, block_cnt,
+                       blocks_per_scan, H, W, n_scans, cue_lim, probs, n_classes, range, vertex, intensity, idx, normal, semantic,
+                       sem_idx, stacked, cues);
+  else
+    hipLaunchKernelGGL(proj_sem_resolve_kernel<0>, dim3(gblocks), dim3(256), 0, stream, points, offs, keys, masks, block_cnt,
+                       blocks_per_scan, H, W, n_scans, cue_lim, probs, n_classes, range, vertex, intensity, idx, normal, semantic,
+                       sem_idx, stacked, cues);
   OVN_HIP_CHECK(hipGetLastError());
   return OVN_OK;
 }

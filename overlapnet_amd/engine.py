@@ -17,6 +17,7 @@ from . import weights as W
 
 FEAT_W = 360         # the reference's leg output width; an engine's own width is OvnEngine.feat_w (weights.feature_width)
 FEAT_C = 128
+SEMANTIC_CLASSES_MAX = 64   # OVN_SEMANTIC_CLASSES_MAX of include/ovn_hip.h
 
 
 class _NoContext(object):
@@ -498,17 +499,27 @@ class OvnEngine:
     # -- preprocessing ------------------------------------------------------------------------------
     def project(self, points: torch.Tensor, offsets: torch.Tensor, max_points: int, proj_h: int = 64,
                 proj_w: int = 900, fov_up: float = 3.0, fov_down: float = -25.0, max_range: float = 50.0,
-                want: Sequence[str] = ("range", "normal", "intensity"), stacked_flags: Optional[Tuple[bool, bool, bool]] = None,
-                stacked_out: Optional[torch.Tensor] = None):
+                want: Sequence[str] = ("range", "normal", "intensity"), stacked_flags: Optional[Tuple[bool, ...]] = None,
+                stacked_out: Optional[torch.Tensor] = None, probs: Optional[torch.Tensor] = None, n_classes: int = 20,
+                n_points: Optional[int] = None):
         """Batch spherical projection.  points: (total,4) f32 device tensor of concatenated scans,
         offsets: (n_scans+1) int64 device tensor (absolute positions in `points`: a slice of a longer offsets tensor projects
         that range of scans).  `want` selects outputs among range, vertex, intensity, idx, normal;
         stacked_flags=(use_depth,use_normals,use_intensity) additionally assembles the (n,H,W,C) leg input (into `stacked_out`
-        when given).  Returns a dict of device tensors."""
+        when given).  Returns a dict of device tensors.
+        probs: (offsets[-1], n_classes) f32 device tensor of per-point class probabilities (the semantic model's input,
+        gen_semantic_data.py:33-46) -- routes the call to ovn_project_semantic: `want` may then also name "semantic"
+        (n,H,W,n_classes: the probabilities of each pixel's point under max_range = inf, -1 elsewhere) and "sem_idx" (that
+        point's proj_idx, which indexes the unfiltered rows as in the reference), stacked_flags is
+        (use_depth, use_normals, use_semantic, use_intensity) in the reference's channel order, and every other output is bit
+        for bit the one of the call without probs.  n_points: offsets[-1] when the caller knows it (else read from the device)."""
         if points.device != self.device or points.dtype != torch.float32 or not points.is_contiguous():
             raise _lib.OvnError("points must be a contiguous float32 tensor on %s" % self.device)
         if offsets.device != self.device or offsets.dtype != torch.int64:
             raise _lib.OvnError("offsets must be an int64 tensor on %s" % self.device)
+        if probs is not None:
+            return self._project_semantic(points, offsets, max_points, proj_h, proj_w, fov_up, fov_down, max_range, want,
+                                          stacked_flags, stacked_out, probs, n_classes, n_points)
         n = offsets.numel() - 1
         dev = self.device
         out = {}
@@ -536,6 +547,56 @@ class OvnEngine:
                                             _ptr(itn), _ptr(idx), _ptr(nrm), _ptr(stk), ud, un, ui, self._stream()),
                        "ovn_project")
         for k, v in (("range", rng), ("vertex", vtx), ("intensity", itn), ("idx", idx), ("normal", nrm), ("stacked", stk)):
+            if v is not None:
+                out[k] = v
+        return out
+
+    def _project_semantic(self, points, offsets, max_points, proj_h, proj_w, fov_up, fov_down, max_range, want, stacked_flags,
+                          stacked_out, probs, n_classes, n_points):
+        n_classes = int(n_classes)
+        if not 1 <= n_classes <= SEMANTIC_CLASSES_MAX:
+            raise _lib.OvnError("n_classes must be in 1..%d, got %d" % (SEMANTIC_CLASSES_MAX, n_classes))
+        total = int(offsets[-1].item()) if n_points is None else int(n_points)
+        if (probs.device != self.device or probs.dtype != torch.float32 or not probs.is_contiguous()
+                or tuple(probs.shape) != (total, n_classes)):
+            raise _lib.OvnError("probs must be a contiguous float32 (%d, %d) tensor on %s (one row per point), got %s %s %s"
+                                % (total, n_classes, self.device, tuple(probs.shape), probs.dtype, probs.device))
+        if probs.numel() == 0:      # no points at all: nothing is read, but the library wants a buffer for a probability output
+            probs = torch.empty((1, n_classes), dtype=torch.float32, device=self.device)
+        n = offsets.numel() - 1
+        dev = self.device
+        mk = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)
+        rng = mk(n, proj_h, proj_w) if "range" in want else None
+        vtx = mk(n, proj_h, proj_w, 4) if "vertex" in want else None
+        itn = mk(n, proj_h, proj_w) if "intensity" in want else None
+        idx = mk(n, proj_h, proj_w, dt=torch.int32) if "idx" in want else None
+        nrm = mk(n, proj_h, proj_w, 3) if "normal" in want else None
+        sem = mk(n, proj_h, proj_w, n_classes) if "semantic" in want else None
+        sid = mk(n, proj_h, proj_w, dt=torch.int32) if "sem_idx" in want else None
+        stk = None
+        ud = un = us = ui = 0
+        if stacked_flags is not None:
+            if len(stacked_flags) != 4:
+                raise _lib.OvnError("with probs, stacked_flags is (use_depth, use_normals, use_semantic, use_intensity)")
+            ud, un, us, ui = (int(bool(v)) for v in stacked_flags)
+            c = ud + 3 * un + n_classes * us + ui
+            if stacked_out is not None:
+                if (stacked_out.device != self.device or stacked_out.dtype != torch.float32 or not stacked_out.is_contiguous()
+                        or tuple(stacked_out.shape) != (n, proj_h, proj_w, c)):
+                    raise _lib.OvnError("stacked_out must be a contiguous float32 (%d,%d,%d,%d) tensor on %s"
+                                        % (n, proj_h, proj_w, c, self.device))
+                stk = stacked_out
+            else:
+                stk = mk(n, proj_h, proj_w, c)
+        with self._dev():
+            _lib.check(self.lib.ovn_project_semantic(self._h, _ptr(points), _ptr(offsets), n, int(max_points), proj_h, proj_w,
+                                                     float(fov_up), float(fov_down), float(max_range), _ptr(probs), n_classes,
+                                                     _ptr(rng), _ptr(vtx), _ptr(itn), _ptr(idx), _ptr(nrm), _ptr(sem), _ptr(sid),
+                                                     _ptr(stk), ud, un, us, ui, self._stream()),
+                       "ovn_project_semantic")
+        out = {}
+        for k, v in (("range", rng), ("vertex", vtx), ("intensity", itn), ("idx", idx), ("normal", nrm), ("semantic", sem),
+                     ("sem_idx", sid), ("stacked", stk)):
             if v is not None:
                 out[k] = v
         return out

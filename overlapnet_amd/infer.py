@@ -27,6 +27,9 @@ types and error behaviour; the Keras/TensorFlow models behind it are replaced by
     AVX512_SKX x86-64 host (float32 `arctan2` / `arcsin` = Intel SVML, bit for bit); `config['projection_trig'] = 'rounded'`
     selects the correctly rounded float32 angles instead (what NumPy's libm fallback gives on AVX2-only / aarch64 hosts: a point
     moves to the neighbouring pixel about once per 200 k points);
+  * `config['semantic_folder']` (extension key, with `scan_folder` and use_class_probabilities): the semantic model from raw scans --
+    per-point RangeNet++ probabilities `<semantic_folder>/<frame>.label` (raw float32 (N, 20)) projected beside the scan
+    (`ovn_project_semantic`), the bits of gen_semantic_data's `.npy` files;
   * `self.leg` / `self.head` are the native engine, not keras.Model objects.
 """
 from __future__ import annotations
@@ -42,6 +45,7 @@ from ._lib import OvnError
 from .engine import FEAT_C, FEAT_W, OvnEngine
 
 TOP_K_MAX = 1024      # OVN_TOP_K_MAX of include/ovn_hip.h
+_SEMANTIC_CLASSES = 20   # RangeNet++ class probabilities per point (gen_semantic_data.py:33) and per pixel (infer.py:70-73)
 
 _VALID_LEGS = ("360OutputkLegs", "360OutputkLegsFixed")       # generateNet.py:119,222
 
@@ -232,8 +236,17 @@ class Infer():
     self.sharded_stats = {'frames_cached': 0, 'pairs_scored': 0, 'pairs_on_cache_rows': 0, 'ahead_delta_rows': 0}
     self._scan_folder = config.get('scan_folder') or None
     self._projection_trig = config.get('projection_trig', 'numpy_avx512')     # extension key, with 'scan_folder' (engine.set_projection_trig)
+    # extension key, with 'scan_folder' and use_class_probabilities: per-point RangeNet++ probabilities <semantic_folder>/<frame>.label
+    # (raw float32 (N, 20), gen_semantic_data.py:33), projected beside the scan on the GPU (ovn_project_semantic)
+    self._semantic_folder = config.get('semantic_folder') or None
+    if self._semantic_folder is not None and (self._scan_folder is None or not config.get('use_class_probabilities', False)):
+      raise ValueError("config['semantic_folder'] is read only with config['scan_folder'] and use_class_probabilities: True")
     if self._scan_folder is not None and config['use_class_probabilities']:
-      raise Exception("config['scan_folder']: the semantic channels come from RangeNet++ .npy files, not from the raw scans")
+      if self._semantic_folder is None:
+        raise Exception("config['scan_folder']: the semantic channels come from RangeNet++ .npy files, not from the raw scans")
+      if config.get('use_class_probabilities_pca', False):
+        raise ValueError("config['scan_folder']: use_class_probabilities_pca has no producer from raw scans (only the 20 class "
+                         "probabilities of config['semantic_folder'])")
     self._stream_ahead = bool(config.get('stream_ahead', True))
     self.network_output_size = config['model']['leg_output_width']      # infer.py:31
     self.seq = config['infer_seqs']                                     # infer.py:32
@@ -461,10 +474,16 @@ class Infer():
   def _scan_path(self, name: str) -> str:
     return os.path.join(self._scan_folder, name + '.bin')
 
+  def _label_path(self, name: str) -> str:
+    return os.path.join(self._semantic_folder, name + '.label')
+
   def _inputs_from_scans(self, filenames: Sequence[str], engine=None) -> torch.Tensor:
     """(n,h,w,C) leg input from the RAW scans (gen_depth_data.py:31-32 reads them the same way): one batched `ovn_project`
     (utils.py:59-186 on the GPU) writes depth | normals | intensity in the reference's channel order straight into the stacked
-    tensor.  `engine`: the context whose scratch the projection uses (the look-ahead passes its second context)."""
+    tensor.  With config['semantic_folder'] every scan's .label file is read too (into pinned memory, copied asynchronously) and
+    `ovn_project_semantic` adds the 20 class probabilities between the normals and the intensity -- the .npy route's
+    probability/ images as gen_semantic_data writes them.  Every file is read and checked before any GPU work.
+    `engine`: the context whose scratch the projection uses (the look-ahead passes its second context)."""
     eng = engine or self.engine
     pts, offs = [], [0]
     for name in filenames:
@@ -476,11 +495,41 @@ class Infer():
       p = p.reshape((-1, 4))
       pts.append(p)
       offs.append(offs[-1] + p.shape[0])
+    probs = None
+    if self._semantic_folder is not None:
+      row = 4 * _SEMANTIC_CLASSES
+      labels = []
+      for i, name in enumerate(filenames):
+        f = self._label_path(name)
+        try:
+          size = os.stat(f).st_size
+        except OSError:
+          raise Exception('Could not read semantic file %s' % f)
+        if size != row * pts[i].shape[0]:
+          rows = '%d' % (size // row) if size % row == 0 else '%.2f' % (size / row)
+          raise Exception('semantic file %s holds %s rows of %d class probabilities, its scan %d points'
+                          % (f, rows, _SEMANTIC_CLASSES, pts[i].shape[0]))
+        labels.append(f)
+      probs = torch.empty((offs[-1], _SEMANTIC_CLASSES), dtype=torch.float32, pin_memory=True)
+      hv = probs.numpy()
+      for i, f in enumerate(labels):
+        try:
+          with open(f, 'rb') as fh:
+            ok = fh.readinto(memoryview(hv[offs[i]:offs[i + 1]]).cast('B')) == row * pts[i].shape[0]
+        except OSError:
+          ok = False
+        if not ok:
+          raise Exception('Could not read semantic file %s' % f)
     flat = np.concatenate(pts, axis=0) if offs[-1] else np.zeros((1, 4), np.float32)
     dev = eng.device
     pd = torch.from_numpy(np.ascontiguousarray(flat)).to(dev, non_blocking=False)
     od = torch.tensor(offs, dtype=torch.int64, device=dev)
     h, w, c = self.inputShape
+    if probs is not None:
+      r = eng.project(pd, od, max(p.shape[0] for p in pts) if pts else 0, h, w, want=(),
+                      stacked_flags=(bool(self.use_depth), bool(self.use_normals), True, bool(self.use_intensity)),
+                      probs=probs.to(dev, non_blocking=True), n_classes=_SEMANTIC_CLASSES, n_points=offs[-1])
+      return r["stacked"]
     r = eng.project(pd, od, max(p.shape[0] for p in pts) if pts else 0, h, w, want=(),
                     stacked_flags=(bool(self.use_depth), bool(self.use_normals), bool(self.use_intensity)))
     return r["stacked"]
@@ -620,11 +669,15 @@ class Infer():
     ahead is adopted only if the files are still the ones it read (live preprocessing may rewrite frame i + 1 between two calls;
     `self.seq` / `self.datasetpath` may change).  None if a file is missing."""
     if self._scan_folder is not None:
-      try:
-        a = os.stat(self._scan_path(name))
-      except OSError:
-        return None
-      return (self._scan_folder, self.seq, name, ((a.st_mtime_ns, a.st_size),))
+      paths = [self._scan_path(name)] + ([self._label_path(name)] if self._semantic_folder is not None else [])
+      st = []
+      for f in paths:
+        try:
+          a = os.stat(f)
+        except OSError:
+          return None
+        st.append((a.st_mtime_ns, a.st_size))
+      return (self._scan_folder, self.seq, name, tuple(st))
     root = os.path.join(self.datasetpath, self.seq)
     st = []
     for sub, k, label in self._cue_files():

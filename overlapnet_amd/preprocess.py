@@ -34,8 +34,10 @@ def load_files(folder):
 
 def project_scans(scans: Sequence[np.ndarray], engine: Optional[OvnEngine] = None, proj_H=64, proj_W=900,
                   fov_up=3.0, fov_down=-25.0, max_range=50, want=("range", "normal", "intensity"),
-                  stacked_flags: Optional[Tuple[bool, bool, bool]] = None):
-    """Project a list of (N_i,4) float32 scans in ONE batched launch sequence; returns device tensors."""
+                  stacked_flags: Optional[Tuple[bool, ...]] = None, probs: Optional[Sequence[np.ndarray]] = None,
+                  n_classes: int = 20):
+    """Project a list of (N_i,4) float32 scans in ONE batched launch sequence; returns device tensors.
+    probs: one (N_i, n_classes) float32 array per scan -- the semantic projection (OvnEngine.project's `probs`)."""
     eng = engine or _get_engine()
     counts = [int(np.asarray(s).reshape(-1, 4).shape[0]) for s in scans]
     offsets = np.zeros(len(scans) + 1, dtype=np.int64)
@@ -48,8 +50,15 @@ def project_scans(scans: Sequence[np.ndarray], engine: Optional[OvnEngine] = Non
     if pts.numel() == 0:
         pts = torch.zeros((1, 4), dtype=torch.float32, device=eng.device)
     off = torch.from_numpy(offsets).to(eng.device)
+    pr = None
+    if probs is not None:
+        rows = [np.asarray(p, np.float32).reshape(-1, n_classes) for p in probs]
+        if [r.shape[0] for r in rows] != counts:
+            raise ValueError("probs: %s rows for scans of %s points" % ([r.shape[0] for r in rows], counts))
+        pr = torch.from_numpy(np.ascontiguousarray(np.concatenate(rows, axis=0) if rows else
+                                                   np.zeros((0, n_classes), np.float32))).to(eng.device)
     return eng.project(pts, off, max(counts) if counts else 0, proj_H, proj_W, fov_up, fov_down, max_range,
-                       want=want, stacked_flags=stacked_flags)
+                       want=want, stacked_flags=stacked_flags, probs=pr, n_classes=n_classes, n_points=int(offsets[-1]))
 
 
 def range_projection(current_vertex, fov_up=3.0, fov_down=-25.0, proj_H=64, proj_W=900, max_range=50):
@@ -114,7 +123,9 @@ def gen_semantic_data(semantic_folder, scan_folder, dst_folder, proj_H=64, proj_
     """ (64,900,20) projected class probabilities -> dst_folder/semantic/<scan name>.npy (gen_semantic_data.py:11-57).
         Raw inputs: per-point float32 (N,20) probability files, one per scan, in sorted order.  The correspondences are
         the projection's `proj_idx` with max_range = inf (gen_semantic_data.py:39); like the reference, that index (taken
-        after the depth > 0 filter) addresses the unfiltered probability array. """
+        after the depth > 0 filter) addresses the unfiltered probability array.  Projection and gather run on the GPU
+        (ovn_project_semantic), 64 scans per launch sequence; a probability file whose row count is not its scan's point count
+        raises (the reference would raise an IndexError or read misaligned rows). """
     dst = os.path.join(dst_folder, 'semantic')
     try:
         os.stat(dst)
@@ -128,12 +139,15 @@ def gen_semantic_data(semantic_folder, scan_folder, dst_folder, proj_H=64, proj_
     bs = 64
     for s in range(0, len(prob_paths), bs):
         scans = [np.fromfile(p, dtype=np.float32).reshape((-1, 4)) for p in scan_paths[s:s + bs][:len(prob_paths) - s]]
-        idx = project_scans(scans, proj_H=proj_H, proj_W=proj_W, max_range=np.inf, want=("idx",))["idx"].cpu().numpy()
-        for k in range(idx.shape[0]):
-            probs = np.fromfile(prob_paths[s + k], dtype=np.float32).reshape((-1, 20))
-            proj_idx = idx[k]
-            proj_prob = np.full((proj_H, proj_W, 20), -1, dtype=np.float32)
-            proj_prob[proj_idx >= 0] = probs[proj_idx[proj_idx >= 0]]
+        probs = [np.fromfile(p, dtype=np.float32).reshape((-1, 20)) for p in prob_paths[s:s + len(scans)]]
+        for k in range(len(scans)):
+            if probs[k].shape[0] != scans[k].shape[0]:
+                raise Exception('semantic file %s holds %d probability rows, its scan %s %d points'
+                                % (prob_paths[s + k], probs[k].shape[0], scan_paths[s + k], scans[k].shape[0]))
+        imgs = project_scans(scans, proj_H=proj_H, proj_W=proj_W, max_range=np.inf, want=("semantic",),
+                             probs=probs)["semantic"].cpu().numpy()
+        for k in range(imgs.shape[0]):
+            proj_prob = imgs[k]
             base_name = os.path.basename(scan_paths[s + k]).replace('.bin', '')
             dst_path = os.path.join(dst, base_name)
             np.save(dst_path, proj_prob)
