@@ -82,8 +82,8 @@ int ovn_set_head_geometry(ovn_ctx* ctx, int conv1size);
  * Width rule.  Every feature volume a context reads or writes is feat_w x 128 floats, corr vectors are feat_w floats, and the Delta
  * head has G = feat_w // conv1size column groups (at least 3) and a Dense kernel of (G - 2)^2 * 256 inputs.  At feat_w = 360 every
  * route of this header is available.  At any other width the heads run exact fp32 on the fp32 MFMA in every head precision mode
- * (ovn_set_head_precision is accepted and has no effect there: the split-operand kernels are tiled to 24 groups of 15 and to the
- * 360-point DFT), and the 360-only entry points ovn_spectrum, ovn_corr_head_spectral, ovn_heads_spectral and ovn_delta_cache
+ * (ovn_set_head_precision is accepted and has no effect there: the tuned split-operand kernels are tiled to 24 groups of 15 and to
+ * the 360-point DFT) unless ovn_set_head_width_split asks for the f16x3 Delta head there, and the 360-only entry points ovn_spectrum, ovn_corr_head_spectral, ovn_heads_spectral and ovn_delta_cache
  * return OVN_ERR_ARG.  If ovn_set_head_weights ran first, finalize also requires feat_w // conv1size to match the Dense kernel
  * registered there. */
 #define OVN_FEAT_W_MIN 45
@@ -334,6 +334,16 @@ int ovn_gt_overlap_counts(ovn_ctx* ctx, const float* ref_ranges_dev, const float
  *       rounded once in fp32, the same class of error as mode 0's l - r).  Delta cache rows are ignored, as in mode 0.
  * Any other value: OVN_ERR_ARG. */
 int ovn_set_head_precision(ovn_ctx* ctx, int mode);
+
+/* Delta head at a feature width other than 360 with conv1size 15 (default 0):
+ *   0 = exact fp32 in every head precision mode (delta_head_w.hip),
+ *   1 = head precision 1 (f16x3) runs DeltaLayer + c_conv1 + c_conv2 there in its scaled 3-term fp16 split on kernels with a
+ *       run-time width (delta_head_w_f16x3.hip: |l - r| formed in fp32, scaled per PAIR and split; a pair's result depends on its
+ *       two volumes alone); c_conv3, Dense and the correlation head stay fp32, head precisions 0 and 2 keep the fp32 kernels.
+ * Every entry point that reaches the Delta head follows it (ovn_heads, ovn_delta_head, ovn_heads_segments, indexed or not).  No
+ * effect at feat_w = 360.  Any other value: OVN_ERR_ARG. */
+int ovn_set_head_width_split(ovn_ctx* ctx, int on);
+int ovn_get_head_width_split(ovn_ctx* ctx, int* on);
 
 /* Arithmetic of the leg convolutions, same two modes as ovn_set_head_precision (default 1). */
 int ovn_set_leg_precision(ovn_ctx* ctx, int mode);

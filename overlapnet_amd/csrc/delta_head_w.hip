@@ -173,12 +173,15 @@ int launch_c12(const ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, co
 
 }  // namespace
 
-// Bytes of scratch per pair: o2 (G, G, 128) | o3 (G - 2, G - 2, 256), each region 256-byte aligned per call (see below)
+// Bytes of scratch per pair: o2 (G, G, 128) | o3 (G - 2, G - 2, 256) | the split route's per-pair scales, each region 256-byte
+// aligned per call (see below)
 size_t ovn_delta_w_pair_bytes(int G) {
-  return ((size_t)G * G * OVN_C2_OUT + (size_t)(G - 2) * (G - 2) * OVN_C3_OUT) * sizeof(float);
+  return ((size_t)G * G * OVN_C2_OUT + (size_t)(G - 2) * (G - 2) * OVN_C3_OUT) * sizeof(float) + ovn_delta_w_split_pair_bytes();
 }
 
-// The whole Delta head for n pairs at feature width ctx->feat_w, conv1size 15; scratch: n * ovn_delta_w_pair_bytes(G) + 256 bytes
+// The whole Delta head for n pairs at feature width ctx->feat_w, conv1size 15; scratch: n * ovn_delta_w_pair_bytes(G) + 512 bytes.
+// DeltaLayer + c_conv1 + c_conv2 run exact fp32 here, or in f16x3 arithmetic (delta_head_w_f16x3.hip) when the context asks for
+// it (head mode 1 with ovn_set_head_width_split); c_conv3 and Dense are the same fp32 kernels either way.
 int ovn_delta_w_forward(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx, int n,
                         void* scratch, float* overlap, float* logit, hipStream_t stream) {
   const int W = ctx->feat_w, G = W / S, R = G * S;
@@ -188,7 +191,12 @@ int ovn_delta_w_forward(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx,
   float* o2 = static_cast<float*>(scratch);
   float* o3 = reinterpret_cast<float*>(static_cast<char*>(scratch) + al((size_t)n * G * G * OVN_C2_OUT * sizeof(float)));
   int rc;
-  {
+  if (ctx->head_width_split && ctx->head_mode == 1) {   // times its prepare and contraction kernels itself
+    void* scales = static_cast<char*>(scratch) + al((size_t)n * G * G * OVN_C2_OUT * sizeof(float)) +
+                   al((size_t)n * (G - 2) * (G - 2) * OVN_C3_OUT * sizeof(float));
+    rc = ovn_delta_w_split_c12_forward(ctx, feats_l, lidx, feats_r, ridx, n, scales, o2, stream);
+    if (rc) return rc;
+  } else {
     OvnProfScope ps(ctx, OVN_K_DELTA, stream);
     const int mt = (G + 15) / 16;
     if (R <= 384)

@@ -468,7 +468,8 @@ static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lid
   const int fw = ctx_feat_w(ctx);
   const size_t feat_elems = (size_t)fw * OVN_FEAT_C;
   // general conv1size, or a feature width other than 360: fp32 paths (every head mode), chunked so that the scratch stays near 2 GB.
-  // At W != 360 with conv1size 15 the Delta head is the fused MFMA kernel of delta_head_w.hip, and the chunk honours head_chunk.
+  // At W != 360 with conv1size 15 the Delta head is the fused MFMA kernel of delta_head_w.hip, and the chunk honours head_chunk;
+  // with ovn_set_head_width_split, head mode 1 takes the f16x3 kernels of delta_head_w_f16x3.hip inside ovn_delta_w_forward.
   if (ctx->head_s != OVN_S || fw != OVN_FEAT_W) {
     OVN_REQUIRE(corr_mode != 2 || fw == OVN_FEAT_W, OVN_ERR_ARG, "spectral correlation head at feature width %d", fw);
     const bool wide = (ctx->head_s == OVN_S);
@@ -970,6 +971,19 @@ int ovn_set_head_precision(ovn_ctx* ctx, int mode) {
   OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_set_head_precision: ctx is NULL");
   OVN_REQUIRE(mode >= 0 && mode <= 2, OVN_ERR_ARG, "ovn_set_head_precision: mode %d (0 = fp32 MFMA, 1 = f16x3 MFMA, 2 = bf16x3 MFMA)", mode);
   ctx->head_mode = mode;
+  return OVN_OK;
+}
+
+int ovn_set_head_width_split(ovn_ctx* ctx, int on) {
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_set_head_width_split: ctx is NULL");
+  OVN_REQUIRE(on == 0 || on == 1, OVN_ERR_ARG, "ovn_set_head_width_split: %d (0 = exact fp32 at widths other than 360, 1 = f16x3 there)", on);
+  ctx->head_width_split = on;
+  return OVN_OK;
+}
+
+int ovn_get_head_width_split(ovn_ctx* ctx, int* on) {
+  OVN_REQUIRE(ctx != nullptr && on != nullptr, OVN_ERR_ARG, "ovn_get_head_width_split: NULL argument");
+  *on = ctx->head_width_split;
   return OVN_OK;
 }
 

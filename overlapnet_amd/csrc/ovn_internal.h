@@ -263,6 +263,7 @@ struct ovn_ctx {
   unsigned* actmax = nullptr;   // [layer][scan of the slice][OVN_ACTMAX_STRIDE] float bits of max |layer input| of that scan (f16x3 scales)
   int head_mode = 1;       // 0 = fp32 MFMA (exact fp32), 1 = scaled 3-term fp16 split on the fp16 MFMA (default),
                            // 2 = exact 3-term bf16 split on the bf16 MFMA (operands at least as wide as fp32)
+  int head_width_split = 0;  // ovn_set_head_width_split: 1 = head mode 1 runs delta_head_w_f16x3.hip at widths other than 360
   float* wd = nullptr;   // dense kernel [123904]
   float* bd = nullptr;   // dense bias [1]
   // spectral correlation head: constant twiddle layers (corr_spectral.hip)
@@ -400,6 +401,12 @@ int ovn_dense_sigmoid_any_forward(const ovn_ctx* ctx, const float* o3, int n, lo
 size_t ovn_delta_w_pair_bytes(int G);
 int ovn_delta_w_forward(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx, int n,
                         void* scratch, float* overlap, float* logit, hipStream_t stream);
+
+// delta_head_w_f16x3.hip: DeltaLayer + c_conv1 + c_conv2 of that route in f16x3 arithmetic (ovn_set_head_width_split with head
+// mode 1): o2 (n, G, G, 128) from n * ovn_delta_w_split_pair_bytes() bytes of per-pair scales (16-byte aligned scratch)
+size_t ovn_delta_w_split_pair_bytes();
+int ovn_delta_w_split_c12_forward(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx,
+                                  int n, void* scales, float* o2, hipStream_t stream);
 
 // corr_head_w.hip: the direct correlation head at a feature width W != 360 (fp32 MFMA, all normalisation modes)
 int ovn_corr_w_forward(const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx, int n, int W,

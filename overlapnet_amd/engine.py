@@ -58,6 +58,7 @@ class OvnEngine:
         self._leg_ready = False
         self._head_ready = False
         self.head_precision = "f16x3"
+        self.head_width_split = False
         self.leg_precision = "f16x3"
         self.projection_trig = "numpy_avx512"
         self.head_compaction = True
@@ -659,14 +660,25 @@ class OvnEngine:
         'f16x3' (default) = scaled 3-term fp16 split on the fp16 matrix cores (22 significand bits per operand: the error of an
         fp32 evaluation), 'f32' = fp32 matrix cores (bit-for-bit an fp32 FMA chain, 1/16 of the rate), 'bf16x3' = exact 3-term bf16
         split on the bf16 matrix cores (operands at least as wide as fp32: 24 significand bits; include/ovn_hip.h).
-        At a feature width other than 360 every mode runs the exact fp32 heads (delta_head_w.hip / corr_head_w.hip): the
-        split-operand kernels are tiled to 24 column groups of 15 and to the 360-point DFT, and fp32 is the reference's own
-        arithmetic.  The mode is still recorded (and the leg follows its own precision setting)."""
+        At a feature width other than 360 every mode runs the exact fp32 heads (delta_head_w.hip / corr_head_w.hip) by default: the
+        tuned split-operand kernels are tiled to 24 column groups of 15 and to the 360-point DFT, and fp32 is the reference's own
+        arithmetic.  With `set_head_width_split(True)` the 'f16x3' mode runs DeltaLayer + c_conv1 + c_conv2 there in its own
+        arithmetic on the runtime-width kernels of delta_head_w_f16x3.hip (c_conv3, Dense and the yaw head stay fp32); 'f32' and
+        'bf16x3' keep the fp32 kernels.  The mode is recorded either way (and the leg follows its own precision setting)."""
         table = {"f32": 0, "f16x3": 1, "bf16x3": 2}
         if mode not in table:
             raise ValueError("head precision must be one of %s" % sorted(table))
         _lib.check(self.lib.ovn_set_head_precision(self._h, table[mode]), "ovn_set_head_precision")
         self.head_precision = mode
+
+    def set_head_width_split(self, on: bool) -> None:
+        """Delta head at a feature width other than 360 (conv1size 15): False (default) = exact fp32 in every head precision, True =
+        head precision 'f16x3' runs DeltaLayer + c_conv1 + c_conv2 in the scaled 3-term fp16 split (delta_head_w_f16x3.hip),
+        several times the fp32 rate at the error of the 360 path.  No effect at 360 columns or in the other head precisions."""
+        _lib.check(self.lib.ovn_set_head_width_split(self._h, 1 if on else 0), "ovn_set_head_width_split")
+        got = C.c_int()
+        _lib.check(self.lib.ovn_get_head_width_split(self._h, C.byref(got)), "ovn_get_head_width_split")
+        self.head_width_split = bool(got.value)
 
     def set_corr_normalization(self, mode: str) -> None:
         """Normalisation of the correlation head's inputs, NormalizedCorrelation2D(normalize=mode): 'none' (default, what
@@ -775,6 +787,7 @@ class QueryAhead:
         self.side.load_weights(weights, model_cfg)
         self.side.set_leg_precision(engine.leg_precision)
         self.side.set_head_precision(engine.head_precision)       # the spectrum kernel follows the head arithmetic
+        self.side.set_head_width_split(engine.head_width_split)
         self.side.set_projection_trig(engine.projection_trig)     # (the look-ahead of Infer projects raw scans in this context)
         self.side.set_corr_normalization(engine.corr_normalization)   # the query spectrum is that of the normalised volume
         dev = engine.device
@@ -816,6 +829,8 @@ class QueryAhead:
             self.side.set_leg_precision(self.main.leg_precision)
         if self.side.head_precision != self.main.head_precision:
             self.side.set_head_precision(self.main.head_precision)
+        if self.side.head_width_split != self.main.head_width_split:
+            self.side.set_head_width_split(self.main.head_width_split)
         if self.side.projection_trig != self.main.projection_trig:
             self.side.set_projection_trig(self.main.projection_trig)
         if self.side.corr_normalization != self.main.corr_normalization:

@@ -12,6 +12,9 @@ types and error behaviour; the Keras/TensorFlow models behind it are replaced by
     running every contraction in fp32, profiles/r2_parity_1024.json).  `config['precision'] = 'f32'` (optional key, absent
     from the reference's network.yml) selects bit-for-bit fp32 FMA chains on the fp32 matrix cores at ~1/3 of the speed, and
     'bf16x3' the fp32 leg with the exact 3-term bf16 split in the Delta head (fp32-wide operands, include/ovn_hip.h);
+    `config['width_precision']` (optional key): at a leg output width other than 360 the heads run exact fp32 in every precision
+    ('exact', the default); 'split' runs the Delta head's DeltaLayer + c_conv1 + c_conv2 in the f16x3 arithmetic there too
+    (needs precision 'f16x3'; no effect at 360 columns);
   * `config['model']['correlationHead_normalize']` ('none' default | 'euclidean' | 'scaling' | 'standardization': the modes of
     NormalizedCorrelation2D, compared by value -- the reference's `is` test would turn a YAML string into 'none') and
     `config['model']['deltaLayer_negateDiffs']` (bool, default False: DeltaLayer(negateDiffs=True)) build the heads a model was
@@ -310,6 +313,15 @@ class Infer():
     if self._world > 1 and self.feat_w != FEAT_W:
       raise ValueError('Infer(world=%d): the sharded sweep runs 360-column feature volumes only, this leg produces %d'
                        % (self._world, self.feat_w))
+    # extension key: the Delta head's arithmetic at a feature width other than 360 ('exact' = fp32 in every precision, 'split' = the
+    # f16x3 split on the runtime-width kernels); checked before any GPU work
+    self.width_precision = config.get('width_precision', 'exact')
+    if self.width_precision not in ('exact', 'split'):
+      raise Exception("config['width_precision'] must be 'exact' or 'split'")
+    if self.width_precision == 'split' and config.get('precision', 'f16x3') != 'f16x3':
+      raise Exception("config['width_precision'] = 'split' runs the f16x3 arithmetic at widths other than 360: it needs "
+                      "config['precision'] = 'f16x3', not %r (the 'f32' and 'bf16x3' heads stay on the exact fp32 kernels there)"
+                      % (config.get('precision'),))
     self.engine = OvnEngine(self.inputShape[0], self.inputShape[1], self.inputShape[2], device=device)
     self.leg = self.engine    # reference: keras.Model (infer.py:101)
     self.head = self.engine   # reference: keras.Model (infer.py:111)
@@ -319,6 +331,7 @@ class Infer():
     # bf16x3: the head's bf16x3 mode with the fp32 leg (the only leg arithmetic at least as wide as fp32)
     self.engine.set_leg_precision('f32' if self.precision == 'bf16x3' else self.precision)
     self.engine.set_head_precision(self.precision)
+    self.engine.set_head_width_split(self.width_precision == 'split')   # no effect at 360 columns
     self.engine.set_projection_trig(self._projection_trig)
 
     # previous feature volumes (infer.py:114): list-like view of the HBM-resident cache
