@@ -336,7 +336,7 @@ int ovn_gt_overlap_counts(ovn_ctx* ctx, const float* ref_ranges_dev, const float
 int ovn_set_head_precision(ovn_ctx* ctx, int mode);
 
 /* Delta head at a feature width other than 360 with conv1size 15 (default 0):
- *   0 = exact fp32 in every head precision mode (delta_head_w.hip),
+ *   0 = exact fp32 in every head precision mode (delta_head.hip),
  *   1 = head precision 1 (f16x3) runs DeltaLayer + c_conv1 + c_conv2 there in its scaled 3-term fp16 split on kernels with a
  *       run-time width (delta_head_w_f16x3.hip: |l - r| formed in fp32, scaled per PAIR and split; a pair's result depends on its
  *       two volumes alone); c_conv3, Dense and the correlation head stay fp32, head precisions 0 and 2 keep the fp32 kernels.
@@ -377,8 +377,9 @@ int ovn_debug_conv(ovn_ctx* ctx, int layer, const float* in_dev, int nb, int h, 
 
 /* Test hook: copy the c_conv2 (n,G,G,128) and c_conv3 (n,G-2,G-2,256) activations that the most recent
  * ovn_heads call left in scratch (its first chunk / sub-chunk, n <= min(pairs, chunk_pairs, sub_chunk_pairs)); either output may be NULL.
- * G = feat_w // 15: 24 at feat_w = 360.  At any other feat_w (conv1size 15) only a call that ran as ONE chunk keeps them (n <= its
- * pair count); after a call of several chunks, and on the general conv1size path, the hook returns OVN_ERR_STATE.
+ * G = feat_w // 15: 24 at feat_w = 360.  The fp32 kernels (head precision 0 at feat_w = 360, every precision at any other feat_w;
+ * conv1size 15) keep them only for a call that ran as ONE chunk (n <= its pair count); after a call of several chunks, and on the
+ * general conv1size path, the hook returns OVN_ERR_STATE.
  * (generateNet.py:102-110 intermediates; the reference exposes them as Keras layer outputs.) */
 int ovn_debug_head_activations(ovn_ctx* ctx, int64_t n, float* o2_dev, float* o3_dev, void* stream);
 

@@ -234,7 +234,7 @@ def head_bounds(h: dict, weights, mode: str) -> dict:
 def corr_pair(l: np.ndarray, r: np.ndarray) -> dict:
     """Correlation vector of the pair (W,), W = l.shape[0], with its elementwise bounds in both forms:
         corr[k] = sum_j sum_c l[(k + j + W // 2) mod W, c] r[j, c]
-      direct    one fp32 contraction of W x 128 products (corr_head.hip, corr_head_w.hip): SAFETY (u rms + sqrt(n) u (|v| + rms))
+      direct    one fp32 contraction of W x 128 products (corr_head.hip): SAFETY (u rms + sqrt(n) u (|v| + rms))
                 per shift, plus the subnormal floor of n fp32 products.
       spectral  corr_spectral.hip: each spectrum X^[f, c] = sum_i x[i, c] e^(-2 pi i f i / 360) is a 360-term contraction split on
                 the fp16 matrix cores, its operands scaled by 2^k from the scan's largest |value| (unclamped: dft_f16x3_kernel);

@@ -255,9 +255,9 @@ __global__ __launch_bounds__(512) void dft_f16x3_kernel(const float* __restrict_
     for (int j = 0; j < 8; ++j) v[k][j] = *reinterpret_cast<const f32x4*>(X + (size_t)(8 * ib + j) * FC + 4 * cq);
   }
   if constexpr (NORM) {
-    static_assert(sizeof(OvnNormLds<DFT_CH>) <= DFT_CH * DFT_LD * sizeof(_Float16), "normalisation LDS must fit in the hi image");
-    OvnNormLds<DFT_CH>& nl = *reinterpret_cast<OvnNormLds<DFT_CH>*>(dsm);
-    ovn_corr_norm_affine<DFT_CH>(X, norm_mode, nl);
+    static_assert(sizeof(OvnNormLds<OVN_NORM_NB, DFT_CH>) <= DFT_CH * DFT_LD * sizeof(_Float16), "normalisation LDS must fit in the hi image");
+    OvnNormLds<OVN_NORM_NB, DFT_CH>& nl = *reinterpret_cast<OvnNormLds<OVN_NORM_NB, DFT_CH>*>(dsm);
+    ovn_corr_norm_affine(X, FW, norm_mode, nl);
     const double na = ovn_corr_norm_add(norm_mode);
     const int cq = tid & 15;   // (item & 15 for both items of the thread)
 #pragma unroll
@@ -456,10 +456,10 @@ int launch_dft_f16x3(ovn_ctx* ctx, const float* feats, int n, float* spectra, hi
 // Standalone normalisation of whole feature volumes (the fp32 transform's input): one workgroup per volume, the same affine forms
 // as every other route (ovn_corr_norm_affine)
 __global__ __launch_bounds__(512) void corr_normalize_kernel(const float* __restrict__ feats, float* __restrict__ out, int mode) {
-  __shared__ OvnNormLds<FC> nl;
+  __shared__ OvnNormLds<OVN_NORM_NB, FC> nl;
   const float* X = feats + (size_t)blockIdx.x * OVN_FEAT_ELEMS;
   float* Y = out + (size_t)blockIdx.x * OVN_FEAT_ELEMS;
-  ovn_corr_norm_affine<FC>(X, mode, nl);
+  ovn_corr_norm_affine(X, FW, mode, nl);
   const double na = ovn_corr_norm_add(mode);
   const int c4 = threadIdx.x & 31;   // channels 4 c4 .. 4 c4 + 3, rows threadIdx.x / 32 + 16 r
   double m[4], sc[4];

@@ -80,32 +80,6 @@ __global__ __launch_bounds__(256) void delta_c1_generic_kernel(const float* __re
   }
 }
 
-// logit[n] = bd + <o3[n,:], wd>, overlap = sigmoid(logit) for a Dense input of `dense_in` floats (a multiple of 4); Flatten order
-// (H, W, C) == o3's NHWC layout (generateNet.py:112-114).  One workgroup per pair, fixed reduction order.
-__global__ __launch_bounds__(256) void dense_sigmoid_any_kernel(const float* __restrict__ o3, const float* __restrict__ wd,
-                                                                const float* __restrict__ bd, long long dense_in,
-                                                                float* __restrict__ overlap, float* __restrict__ logit) {
-  __shared__ float red[4];
-  const int n = blockIdx.x;
-  const f32x4* x = reinterpret_cast<const f32x4*>(o3 + (long long)n * dense_in);
-  const f32x4* w = reinterpret_cast<const f32x4*>(wd);
-  float s = 0.f;
-  for (long long i = threadIdx.x; i < dense_in / 4; i += 256) {
-    const f32x4 a = x[i];
-    const f32x4 b = w[i];
-    s += (a[0] * b[0] + a[1] * b[1]) + (a[2] * b[2] + a[3] * b[3]);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const float z = ((red[0] + red[1]) + (red[2] + red[3])) + bd[0];
-    if (logit) logit[n] = z;
-    overlap[n] = 1.0f / (1.0f + expf(-z));
-  }
-}
-
 }  // namespace
 
 // Bytes of scratch per pair of the general path: out1 (W, G, 64) | o2 (G, G, 128) | o3 (G - 2, G - 2, 256), each 256-byte aligned
@@ -137,12 +111,5 @@ int ovn_delta_generic_forward(const ovn_ctx* ctx, const float* feats_l, const in
   OVN_REQUIRE(oh == G && ow == G, OVN_ERR_STATE, "general Delta head: c_conv2 produced %dx%d, expected %dx%d", oh, ow, G, G);
   rc = ovn_conv_forward(ctx->c3, o2, n, G, G, o3, &oh, &ow, stream);              // -> (n, G - 2, G - 2, 256)
   if (rc) return rc;
-  return ovn_dense_sigmoid_any_forward(ctx, o3, n, (long long)(G - 2) * (G - 2) * OVN_C3_OUT, overlap, logit, stream);
-}
-
-int ovn_dense_sigmoid_any_forward(const ovn_ctx* ctx, const float* o3, int n, long long dense_in, float* overlap, float* logit,
-                                  hipStream_t stream) {
-  hipLaunchKernelGGL(dense_sigmoid_any_kernel, dim3(n), dim3(256), 0, stream, o3, ctx->wd, ctx->bd, dense_in, overlap, logit);
-  OVN_HIP_CHECK(hipGetLastError());
-  return OVN_OK;
+  return ovn_dense_sigmoid_forward(ctx, o3, n, (long long)(G - 2) * (G - 2) * OVN_C3_OUT, overlap, logit, stream);
 }

@@ -1,8 +1,8 @@
 // Delta (overlap) head of OverlapNet at a runtime feature width W (45 <= W <= 512, W != 360) in the split-operand ("f16x3")
 // arithmetic of delta_head_f16x3.hip for gfx950: DeltaLayer + c_conv1 + c_conv2 on v_mfma_f32_16x16x32_f16, fp32 accumulate.
-// Opt-in (ovn_set_head_width_split); c_conv3 and Dense stay on the fp32 kernels of the width route (delta_head_w.hip).
+// Opt-in (ovn_set_head_width_split); c_conv3 and Dense stay on the fp32 kernels of ovn_delta_forward (delta_head.hip).
 //
-// Geometry: that of delta_head_w.hip.  G = W // 15 column groups (3..34), R = 15 G rows of l reach c_conv2, the last W - 15 G
+// Geometry: that of delta_head.hip.  G = W // 15 column groups (3..34), R = 15 G rows of l reach c_conv2, the last W - 15 G
 // columns of r are never read.
 //
 // Arithmetic: as delta_head_f16x3.hip's header defines it.  Every operand x is scaled by a power of two and written hi + lo
@@ -328,7 +328,7 @@ int launch_split(const ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, 
 
 }  // namespace
 
-// Bytes of per-pair scales the split route adds to the scratch of ovn_delta_w_forward
+// Bytes of per-pair scales the split route adds to the scratch of ovn_delta_forward
 size_t ovn_delta_w_split_pair_bytes() { return sizeof(f32x4); }
 
 // DeltaLayer + c_conv1 + c_conv2 for n pairs at feature width ctx->feat_w, conv1size 15, in f16x3 arithmetic: o2 (n, G, G, 128).

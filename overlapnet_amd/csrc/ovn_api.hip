@@ -368,9 +368,7 @@ int ovn_corr_head(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const
   OVN_REQUIRE(feats_l && feats_r && yaw, OVN_ERR_ARG, "ovn_corr_head: NULL buffer");
   OVN_ON_DEVICE(ctx->device);
   OvnProfScope ps(ctx, OVN_K_CORR, (hipStream_t)stream);
-  if (ctx_feat_w(ctx) != OVN_FEAT_W)
-    return ovn_corr_w_forward(feats_l, lidx, feats_r, ridx, (int)n, ctx_feat_w(ctx), yaw, corr, (hipStream_t)stream, ctx->corr_norm);
-  return ovn_corr_forward(feats_l, lidx, feats_r, ridx, (int)n, yaw, corr, (hipStream_t)stream, ctx->corr_norm);
+  return ovn_corr_forward(feats_l, lidx, feats_r, ridx, (int)n, ctx_feat_w(ctx), yaw, corr, (hipStream_t)stream, ctx->corr_norm);
 }
 
 int ovn_spectrum(ovn_ctx* ctx, const float* feats_dev, int64_t n, float* spectra_dev, void* stream) {
@@ -454,90 +452,100 @@ struct OvnFork {   // fork on construction-time request, join (on every exit pat
   ~OvnFork() { (void)join(); }
 };
 
+// The fp32 routes of a head call: the fused MFMA kernel of delta_head.hip at conv1size 15 (any width; with ovn_set_head_width_split,
+// head mode 1 takes the f16x3 kernels of delta_head_w_f16x3.hip inside ovn_delta_forward at widths other than 360), the general
+// kernels of delta_head_generic.hip at any other conv1size.  Chunked so that the scratch stays near 2 GB and within head_chunk pairs.
+static int delta_head_run_f32(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx,
+                              int64_t n, float* overlap, float* logit, int32_t* yaw, float* corr, int corr_mode, const float* spec_l,
+                              const float* spec_r, hipStream_t stream) {
+  const int fw = ctx_feat_w(ctx);
+  const size_t feat_elems = (size_t)fw * OVN_FEAT_C;
+  OVN_REQUIRE(corr_mode != 2 || fw == OVN_FEAT_W, OVN_ERR_ARG, "spectral correlation head at feature width %d", fw);
+  const bool fusedc12 = (ctx->head_s == OVN_S);
+  const size_t pb = fusedc12 ? ovn_delta_pair_bytes(ctx->head_g) : ovn_delta_generic_pair_bytes(fw, ctx->head_g);
+  int64_t chunk = (int64_t)((2ull << 30) / pb);
+  chunk = chunk < 1 ? 1 : (chunk > 1024 ? 1024 : chunk);
+  if (ctx->head_chunk < chunk) chunk = ctx->head_chunk;
+  const int64_t cmax = n < chunk ? n : chunk;
+  int rc = ovn_ws_reserve(ctx, (size_t)cmax * pb + 1024, stream);
+  if (rc) return rc;
+  ctx->dbg_o2 = ctx->dbg_o3 = nullptr;
+  ctx->dbg_partial = nullptr;
+  ctx->dbg_o2max = nullptr;
+  ctx->dbg_n = 0;
+  OvnFork fk(ctx, stream);
+  if (corr_mode == 2) {   // ONE launch for all n pairs, beside the Delta kernels when the pipeline asks for a side stream
+    hipStream_t ys = stream;
+    if (ctx->head_yaw_side) {
+      rc = fk.side(1, &ys);
+      if (rc) return rc;
+    }
+    OvnProfScope ps(ctx, OVN_K_CORR_SPECTRAL, ys);
+    rc = ovn_corr_spectral_forward(ctx, spec_l, lidx, spec_r, ridx, (int)n, yaw, corr, ys);
+    if (rc) return rc;
+  }
+  for (int64_t p0 = 0; p0 < n; p0 += chunk) {
+    const int np = (int)((n - p0 < chunk) ? (n - p0) : chunk);
+    const float* fl = lidx ? feats_l : feats_l + (size_t)p0 * feat_elems;
+    const int32_t* li = lidx ? lidx + p0 : nullptr;
+    const int32_t* ri = ridx ? ridx + p0 : nullptr;
+    if (corr_mode == 1) {
+      OvnProfScope ps(ctx, OVN_K_CORR, stream);
+      rc = ovn_corr_forward(fl, li, feats_r, ri, np, fw, yaw + p0, corr ? corr + (size_t)p0 * fw : nullptr, stream, ctx->corr_norm);
+      if (rc) return rc;
+    }
+    if (fusedc12) {   // times its Delta, c_conv3 and Dense kernels separately
+      rc = ovn_delta_forward(ctx, fl, li, feats_r, ri, np, ctx->ws, overlap + p0, logit ? logit + p0 : nullptr, stream);
+    } else {
+      OvnProfScope ps(ctx, OVN_K_DELTA, stream);
+      rc = ovn_delta_generic_forward(ctx, fl, li, feats_r, ri, np, ctx->ws, overlap + p0, logit ? logit + p0 : nullptr, stream);
+    }
+    if (rc) return rc;
+  }
+  if (fusedc12 && n > 0 && n <= chunk) {   // one chunk: its o2 / o3 regions (ovn_delta_forward) hold every pair for the test hook
+    const size_t o2w = (size_t)n * ctx->head_g * ctx->head_g * OVN_C2_OUT * sizeof(float);
+    ctx->dbg_o2 = static_cast<const float*>(ctx->ws);
+    ctx->dbg_o3 = reinterpret_cast<const float*>(static_cast<const char*>(ctx->ws) + ((o2w + 255) & ~(size_t)255));
+    ctx->dbg_n = n;
+  }
+  return fk.join();
+}
+
 // Delta (overlap) head on n pairs [+ one of the correlation heads]; shared by ovn_heads, ovn_delta_head and ovn_heads_spectral.
 //   corr_mode 0: none; 1: direct form on the feature volumes (per chunk, on the caller's stream, as ovn_heads always did);
 //             2: spectral form on (spec_l, spec_r): ONE launch for all n pairs on a side stream, beside the Delta kernels.
-// The sweep is cut into chunks of <= ctx->head_chunk pairs (the scratch is sized for one chunk) and every chunk into sub-chunks of
-// ctx->head_sub pairs that alternate between ctx->head_streams streams (sub-chunk j of every chunk uses scratch region j and
-// stream j % streams, so a region is only ever reused in stream order).
+// conv1size != 15, W != 360 or head mode 0 run the fp32 routes above.  The split-operand modes (360 columns) follow: the sweep is cut
+// into chunks of <= ctx->head_chunk pairs (the scratch is sized for one chunk) and every chunk into sub-chunks of ctx->head_sub pairs
+// that alternate between ctx->head_streams streams (sub-chunk j of every chunk uses scratch region j and stream j % streams, so a
+// region is only ever reused in stream order).
 static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r,
                           const int32_t* ridx, int64_t n, float* overlap, float* logit, int32_t* yaw, float* corr,
                           int corr_mode, const float* spec_l, const float* spec_r, const float* dcache_l, hipStream_t stream,
                           const OvnSegPass* seg = nullptr) {   // seg: a pass of ovn_heads_segments (f16x3 fused path only)
   ctx->dbg_live = nullptr;   // ovn_head_walk_stats describes THIS call (a sweep that compacts sets it again)
   const int fw = ctx_feat_w(ctx);
+  if (ctx->head_s != OVN_S || fw != OVN_FEAT_W || ctx->head_mode == 0)
+    return delta_head_run_f32(ctx, feats_l, lidx, feats_r, ridx, n, overlap, logit, yaw, corr, corr_mode, spec_l, spec_r, stream);
   const size_t feat_elems = (size_t)fw * OVN_FEAT_C;
-  // general conv1size, or a feature width other than 360: fp32 paths (every head mode), chunked so that the scratch stays near 2 GB.
-  // At W != 360 with conv1size 15 the Delta head is the fused MFMA kernel of delta_head_w.hip, and the chunk honours head_chunk;
-  // with ovn_set_head_width_split, head mode 1 takes the f16x3 kernels of delta_head_w_f16x3.hip inside ovn_delta_w_forward.
-  if (ctx->head_s != OVN_S || fw != OVN_FEAT_W) {
-    OVN_REQUIRE(corr_mode != 2 || fw == OVN_FEAT_W, OVN_ERR_ARG, "spectral correlation head at feature width %d", fw);
-    const bool wide = (ctx->head_s == OVN_S);
-    const size_t pb = wide ? ovn_delta_w_pair_bytes(ctx->head_g) : ovn_delta_generic_pair_bytes(fw, ctx->head_g);
-    int64_t chunk = (int64_t)((2ull << 30) / pb);
-    chunk = chunk < 1 ? 1 : (chunk > 1024 ? 1024 : chunk);
-    if (fw != OVN_FEAT_W && ctx->head_chunk < chunk) chunk = ctx->head_chunk;
-    const int64_t cmax = n < chunk ? n : chunk;
-    int rc = ovn_ws_reserve(ctx, (size_t)cmax * pb + 1024, stream);
-    if (rc) return rc;
-    ctx->dbg_o2 = ctx->dbg_o3 = nullptr;
-    ctx->dbg_partial = nullptr;
-    ctx->dbg_o2max = nullptr;
-    ctx->dbg_n = 0;
-    if (corr_mode == 2) {
-      OvnProfScope ps(ctx, OVN_K_CORR_SPECTRAL, stream);
-      rc = ovn_corr_spectral_forward(ctx, spec_l, lidx, spec_r, ridx, (int)n, yaw, corr, stream);
-      if (rc) return rc;
-    }
-    for (int64_t p0 = 0; p0 < n; p0 += chunk) {
-      const int np = (int)((n - p0 < chunk) ? (n - p0) : chunk);
-      const float* fl = lidx ? feats_l : feats_l + (size_t)p0 * feat_elems;
-      const int32_t* li = lidx ? lidx + p0 : nullptr;
-      const int32_t* ri = ridx ? ridx + p0 : nullptr;
-      if (corr_mode == 1) {
-        OvnProfScope ps(ctx, OVN_K_CORR, stream);
-        float* cp = corr ? corr + (size_t)p0 * fw : nullptr;
-        rc = (fw == OVN_FEAT_W) ? ovn_corr_forward(fl, li, feats_r, ri, np, yaw + p0, cp, stream, ctx->corr_norm)
-                                : ovn_corr_w_forward(fl, li, feats_r, ri, np, fw, yaw + p0, cp, stream, ctx->corr_norm);
-        if (rc) return rc;
-      }
-      if (wide) {   // times its Delta, c_conv3 and Dense kernels separately
-        rc = ovn_delta_w_forward(ctx, fl, li, feats_r, ri, np, ctx->ws, overlap + p0, logit ? logit + p0 : nullptr, stream);
-      } else {
-        OvnProfScope ps(ctx, OVN_K_DELTA, stream);
-        rc = ovn_delta_generic_forward(ctx, fl, li, feats_r, ri, np, ctx->ws, overlap + p0, logit ? logit + p0 : nullptr, stream);
-      }
-      if (rc) return rc;
-    }
-    if (wide && n > 0 && n <= chunk) {   // one chunk: its o2 / o3 regions (ovn_delta_w_forward) hold every pair for the test hook
-      const size_t o2w = (size_t)n * ctx->head_g * ctx->head_g * OVN_C2_OUT * sizeof(float);
-      ctx->dbg_o2 = static_cast<const float*>(ctx->ws);
-      ctx->dbg_o3 = reinterpret_cast<const float*>(static_cast<const char*>(ctx->ws) + ((o2w + 255) & ~(size_t)255));
-      ctx->dbg_n = n;
-    }
-    return OVN_OK;
-  }
   const size_t o2_elems = (size_t)OVN_G * OVN_G * OVN_C2_OUT;   // 24*24*128 per pair
   const size_t o3_elems = (size_t)OVN_DENSE_IN;                 // 22*22*256 per pair
-  // head modes: 0 = fp32 (one kernel for DeltaLayer + c_conv1 + c_conv2, generic c_conv3, Dense); 1 = f16x3 (prepare / contraction /
-  // c_conv2 kernels, fused c_conv3 + Dense); 2 = bf16x3 (the same three Delta kernels with the exact bf16 split, generic fp32 c_conv3, Dense)
+  // head modes: 1 = f16x3 (prepare / contraction / c_conv2 kernels, fused c_conv3 + Dense); 2 = bf16x3 (the same three Delta kernels
+  // with the exact bf16 split, generic fp32 c_conv3, Dense)
   const bool fused = (ctx->head_mode == 1);
-  const bool split = (ctx->head_mode != 0);                     // the two-kernel Delta path with its per-pair scratch
   const int64_t chunk = ctx->head_chunk;                        // pairs per pass over the scratch (f16x3: 3.2 MB per pair)
   const int64_t cmax = n < chunk ? n : chunk;
-  // sub-chunks: only the f16x3 / bf16x3 kernels are split (the fp32 mode is one long kernel per chunk and keeps the round-2 structure)
-  // (a segmented pass keeps one sub-chunk: its per-segment query state is shared by all of its pairs)
-  int64_t sub = (split && !seg && ctx->head_sub > 0 && ctx->head_sub < cmax) ? ctx->head_sub : cmax;
+  // sub-chunks (a segmented pass keeps one: its per-segment query state is shared by all of its pairs)
+  int64_t sub = (!seg && ctx->head_sub > 0 && ctx->head_sub < cmax) ? ctx->head_sub : cmax;
   const int nsub_max = (int)((cmax + sub - 1) / sub);
-  const int nstreams = (split && nsub_max > 1 && ctx->head_streams > 1) ? 2 : 1;
+  const int nstreams = (nsub_max > 1 && ctx->head_streams > 1) ? 2 : 1;
   auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const size_t o2_bytes = al((size_t)cmax * o2_elems * sizeof(float));
-  // second scratch region: o3 (n,22,22,256) in fp32 mode; in f16x3 mode c_conv3 and the Dense layer are one kernel and only
+  // second scratch region: o3 (n,22,22,256) in bf16x3 mode; in f16x3 mode c_conv3 and the Dense layer are one kernel and only
   // OVN_DENSE_PARTIALS partial sums per pair (band x half of the output channels x half of the m-tiles) leave it
   const size_t o3_bytes = fused ? al((size_t)cmax * OVN_DENSE_PARTIALS * sizeof(float)) : al((size_t)cmax * o3_elems * sizeof(float));
-  // f16x3 mode: per-pair scales, packed volumes, linear terms and the c_conv1 rows between the two Delta kernels (2.9 MB per pair),
-  // one self-contained block per sub-chunk
-  const size_t sc_sub = split ? al(ovn_delta_f16x3_scratch_bytes((int)sub, ridx != nullptr)) : 0;
+  // per-pair scales, packed volumes, linear terms and the c_conv1 rows between the two Delta kernels (2.9 MB per pair), one
+  // self-contained block per sub-chunk
+  const size_t sc_sub = al(ovn_delta_f16x3_scratch_bytes((int)sub, ridx != nullptr));
   const size_t seg_bytes = seg ? al(ovn_delta_f16x3_seg_bytes(seg->nseg)) : 0;
   int rc = ovn_ws_reserve(ctx, o2_bytes + o3_bytes + sc_sub * nsub_max + seg_bytes, stream);
   if (rc) return rc;
@@ -569,7 +577,7 @@ static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lid
     }
     OvnProfScope ps(ctx, OVN_K_CORR_SPECTRAL, ys);
     // a small 1-vs-N sweep in one sub-chunk: the query's right-volume term of the Delta head rides in the yaw launch (csrc/delta_a2.h)
-    a2_in_yaw = split && ridx == nullptr && n <= OVN_A2_IN_YAW_MAX_PAIRS && n <= chunk && ys == stream && nsub_max == 1 && ctx->head_s == OVN_S;
+    a2_in_yaw = ridx == nullptr && n <= OVN_A2_IN_YAW_MAX_PAIRS && n <= chunk && ys == stream && nsub_max == 1;
     rc = ovn_corr_spectral_forward(ctx, spec_l, lidx, spec_r, ridx, (int)n, yaw, corr, ys, a2_in_yaw ? feats_r : nullptr,
                                    a2_in_yaw ? ovn_delta_f16x3_a2raw(dscratch, (int)n) : nullptr);
     if (rc) return rc;
@@ -579,7 +587,7 @@ static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lid
     if (corr_mode == 1) {
       OvnProfScope ps(ctx, OVN_K_CORR, stream);
       rc = ovn_corr_forward(lidx ? feats_l : feats_l + (size_t)c0 * feat_elems, lidx ? lidx + c0 : nullptr, feats_r,
-                            ridx ? ridx + c0 : nullptr, (int)cn, yaw + c0, corr ? corr + (size_t)c0 * fw : nullptr, stream,
+                            ridx ? ridx + c0 : nullptr, (int)cn, fw, yaw + c0, corr ? corr + (size_t)c0 * fw : nullptr, stream,
                             ctx->corr_norm);
       if (rc) return rc;
     }
@@ -615,15 +623,10 @@ static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lid
           OvnProfScope ps(ctx, OVN_K_C3, st);
           rc = ovn_c3_dense_forward(ctx, o2s, o2max, np, part, nullptr, ctx->c3_arrived + q0, overlap + p0, logit ? logit + p0 : nullptr, st);
         }
-      } else {
+      } else {   // bf16x3: times its prepare kernels, the contraction kernel and c_conv2 separately
         float* o3s = o3 + (size_t)q0 * o3_elems;
-        if (split) {   // bf16x3: times its prepare kernels, the contraction kernel and c_conv2 separately
-          rc = ovn_delta_c12_bf16x3_forward(ctx, fl, li, feats_r, ri, np, dscratch + (size_t)j * sc_sub, o2s, st, (int)(p0 & 0x3fffffff),
-                                            a2_in_yaw);
-        } else {
-          OvnProfScope ps(ctx, OVN_K_DELTA, st);
-          rc = ovn_delta_c12_forward(ctx, fl, li, feats_r, ri, np, o2s, st);
-        }
+        rc = ovn_delta_c12_bf16x3_forward(ctx, fl, li, feats_r, ri, np, dscratch + (size_t)j * sc_sub, o2s, st, (int)(p0 & 0x3fffffff),
+                                          a2_in_yaw);
         if (rc) return rc;
         int oh = 0, ow = 0;
         {
@@ -632,7 +635,7 @@ static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lid
         }
         if (rc) return rc;
         OvnProfScope ps(ctx, OVN_K_DENSE, st);
-        rc = ovn_dense_sigmoid_forward(ctx, o3s, np, overlap + p0, logit ? logit + p0 : nullptr, st);
+        rc = ovn_dense_sigmoid_forward(ctx, o3s, np, OVN_DENSE_IN, overlap + p0, logit ? logit + p0 : nullptr, st);
       }
       if (rc) return rc;
     }
@@ -1079,7 +1082,7 @@ int ovn_debug_head_activations(ovn_ctx* ctx, int64_t n, float* o2_dev, float* o3
   OVN_REQUIRE(ctx && ctx->dbg_o2 && n >= 0 && n <= ctx->dbg_n, OVN_ERR_STATE,
               "ovn_debug_head_activations: call right after ovn_heads with n <= its (first-chunk) pair count");
   OVN_ON_DEVICE(ctx->device);
-  const size_t g = (size_t)ctx->head_g;   // 24 at W = 360; W // 15 on the width path (delta_head_w.hip)
+  const size_t g = (size_t)ctx->head_g;   // 24 at W = 360; W // 15 at any other width
   if (o2_dev)
     OVN_HIP_CHECK(hipMemcpyAsync(o2_dev, ctx->dbg_o2, (size_t)n * g * g * OVN_C2_OUT * sizeof(float),
                                  hipMemcpyDeviceToDevice, (hipStream_t)stream));

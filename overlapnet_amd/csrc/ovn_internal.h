@@ -62,8 +62,9 @@ struct OvnDeviceGuard {
 constexpr int OVN_FEAT_W = 360;   // leg_output_width, config/network.yml:77
 constexpr int OVN_FEAT_C = 128;   // s_conv10 filters, generateNet.py:214
 constexpr int OVN_FEAT_ELEMS = OVN_FEAT_W * OVN_FEAT_C;
-// any other leg output width W in [OVN_FEAT_W_MIN, OVN_FEAT_W_MAX] (include/ovn_hip.h) runs the runtime-W fp32 heads
-// (delta_head_w.hip, corr_head_w.hip, delta_head_generic.hip); every feature volume is ctx->feat_w * 128 floats
+// the fp32 heads (delta_head.hip, corr_head.hip, delta_head_generic.hip) take the leg output width W at run time, any W in
+// [OVN_FEAT_W_MIN, OVN_FEAT_W_MAX] (include/ovn_hip.h); every feature volume is ctx->feat_w * 128 floats.  The constants below that
+// derive from 360 describe the shipped configuration, which the split-operand and spectral kernels are tiled around
 constexpr int OVN_S = 15;         // conv1NetworkHead_conv1size default, generateNet.py:88-89
 constexpr int OVN_G = OVN_FEAT_W / OVN_S;            // 24
 constexpr int OVN_C1_OUT = 64;    // c_conv1 filters
@@ -114,22 +115,24 @@ __device__ __forceinline__ void ovn_fold_absmax_wg(float vmax, unsigned* word, f
 #endif
 
 // ---- normalisation of the correlation head's inputs (NormalizedCorrelation2D normalize=..., ovn_set_corr_normalization) ----------
-// Per (volume, channel), over the 360 columns:
+// Per (volume, channel), over the W columns:
 //   1 euclidean        x' = x / sqrt(max(sum x^2, 1e-12))
 //   2 scaling          x' = (x - min x) / (max x - min x + 1e-6)
 //   3 standardization  y = (x - mean x) + 1e-5, x' = y / sqrt(max(sum y^2, 1e-12))
 // all of the form x' = RN32(((x - m) + a) s) with the per-channel m, s and the mode's constant a in fp64; each element is evaluated
-// in fp64 and rounded ONCE to fp32.  The statistics are fp64 sums in ONE fixed order: per channel 15 blocks of 24 consecutive
-// columns, each summed in column order, then the 15 block sums in block order.  Every route (direct head, fused DFT, standalone
-// pass) calls ovn_corr_norm_affine, so a volume's normalised values do not depend on the batch, the pair, the launch or the rank.
+// in fp64 and rounded ONCE to fp32.  The statistics are fp64 sums in ONE fixed order: per channel ceil(W / 24) blocks of 24
+// consecutive columns (the last one partial unless 24 divides W; 15 whole blocks at W = 360), each summed in column order, then the
+// block sums in block order.  Every route (direct head at any width, fused DFT, standalone pass) calls ovn_corr_norm_affine, so a
+// volume's normalised values do not depend on the batch, the pair, the launch or the rank.
 constexpr int OVN_NORM_BLK = 24;                          // columns per partial sum
-constexpr int OVN_NORM_NB = OVN_FEAT_W / OVN_NORM_BLK;    // 15 partial sums per channel
-static_assert(OVN_NORM_NB * OVN_NORM_BLK == OVN_FEAT_W, "normalisation blocks must tile the 360 columns");
+constexpr int OVN_NORM_NB = OVN_FEAT_W / OVN_NORM_BLK;    // 15 partial sums per channel at W = 360
+static_assert(OVN_NORM_NB * OVN_NORM_BLK == OVN_FEAT_W, "15 whole blocks tile the 360 columns (the spectral kernels' LDS)");
+constexpr int OVN_NORM_NB_MAX = (OVN_FEAT_W_MAX + OVN_NORM_BLK - 1) / OVN_NORM_BLK;   // 22 at W = 512
 
-template <int NCH>
-struct OvnNormLds {       // LDS of ovn_corr_norm_affine for NCH channels (NCH = 128: 32 KB)
-  double part[OVN_NORM_NB][NCH];
-  float mn[OVN_NORM_NB][NCH], mx[OVN_NORM_NB][NCH];
+template <int NB, int NCH>
+struct OvnNormLds {       // LDS of ovn_corr_norm_affine for up to NB blocks of NCH channels (NB = 15, NCH = 128: 32 KB)
+  double part[NB][NCH];
+  float mn[NB][NCH], mx[NB][NCH];
   double m[NCH], s[NCH];  // the affine form: x' = RN32(((x - m) + a) s)
 };
 
@@ -140,23 +143,40 @@ __device__ __forceinline__ float ovn_corr_norm_apply(float x, double m, double a
   return (float)((((double)x - m) + a) * s);
 }
 
-// Affine form of channels c0 .. c0 + NCH - 1 of one (360, 128) feature volume (X = volume + c0) for mode 1..3 into L.m / L.s.
-// Every thread of the (1-D) workgroup must call it; it ends with a barrier, after which L.m / L.s are valid.
-template <int NCH>
-__device__ void ovn_corr_norm_affine(const float* __restrict__ X, int mode, OvnNormLds<NCH>& L) {
+// One block of pass 1 / pass 2 over n consecutive columns of a channel (p: its first element), in column order.  The whole blocks
+// pass the constant OVN_NORM_BLK (a constant trip count), the last, partial block its runtime length.
+__device__ __forceinline__ void ovn_norm_block_stats(const float* __restrict__ p, int n, double& sm, float& lo, float& hi) {
+#pragma unroll 8
+  for (int i = 0; i < n; ++i) {
+    const float v = p[(size_t)i * OVN_FEAT_C];
+    sm += (double)v;
+    lo = fminf(lo, v);
+    hi = fmaxf(hi, v);
+  }
+}
+__device__ __forceinline__ double ovn_norm_block_sumsq(const float* __restrict__ p, int n, double m, double a) {
+  double q = 0.0;
+#pragma unroll 8
+  for (int i = 0; i < n; ++i) {
+    const double y = ((double)p[(size_t)i * OVN_FEAT_C] - m) + a;
+    q = __builtin_fma(y, y, q);
+  }
+  return q;
+}
+
+// Affine form of channels c0 .. c0 + NCH - 1 of one (W, 128) feature volume (X = volume + c0, W <= 24 NB) for mode 1..3 into
+// L.m / L.s.  Every thread of the (1-D) workgroup must call it; it ends with a barrier, after which L.m / L.s are valid.
+template <int NB, int NCH>
+__device__ void ovn_corr_norm_affine(const float* __restrict__ X, int W, int mode, OvnNormLds<NB, NCH>& L) {
   const int tid = threadIdx.x, nt = blockDim.x;
-  for (int t = tid; t < OVN_NORM_NB * NCH; t += nt) {   // pass 1: block sums, minima, maxima
+  const int nfull = W / OVN_NORM_BLK, tail = W - nfull * OVN_NORM_BLK, nb = nfull + (tail ? 1 : 0);
+  for (int t = tid; t < nb * NCH; t += nt) {   // pass 1: block sums, minima, maxima
     const int c = t % NCH, b = t / NCH;
     const float* p = X + (size_t)(b * OVN_NORM_BLK) * OVN_FEAT_C + c;
     double sm = 0.0;
     float lo = INFINITY, hi = -INFINITY;
-#pragma unroll 8
-    for (int i = 0; i < OVN_NORM_BLK; ++i) {
-      const float v = p[(size_t)i * OVN_FEAT_C];
-      sm += (double)v;
-      lo = fminf(lo, v);
-      hi = fmaxf(hi, v);
-    }
+    if (b < nfull) ovn_norm_block_stats(p, OVN_NORM_BLK, sm, lo, hi);
+    else ovn_norm_block_stats(p, tail, sm, lo, hi);
     L.part[b][c] = sm;
     L.mn[b][c] = lo;
     L.mx[b][c] = hi;
@@ -165,7 +185,7 @@ __device__ void ovn_corr_norm_affine(const float* __restrict__ X, int mode, OvnN
   if (tid < NCH) {
     double sm = 0.0;
     float lo = INFINITY, hi = -INFINITY;
-    for (int b = 0; b < OVN_NORM_NB; ++b) {
+    for (int b = 0; b < nb; ++b) {
       sm += L.part[b][tid];
       lo = fminf(lo, L.mn[b][tid]);
       hi = fmaxf(hi, L.mx[b][tid]);
@@ -174,29 +194,22 @@ __device__ void ovn_corr_norm_affine(const float* __restrict__ X, int mode, OvnN
       L.m[tid] = (double)lo;
       L.s[tid] = 1.0 / (((double)hi - (double)lo) + 1e-6);
     } else {
-      L.m[tid] = (mode == 3) ? sm / (double)OVN_FEAT_W : 0.0;
+      L.m[tid] = (mode == 3) ? sm / (double)W : 0.0;
       L.s[tid] = 0.0;
     }
   }
   __syncthreads();
   if (mode == 2) return;
   const double a = ovn_corr_norm_add(mode);
-  for (int t = tid; t < OVN_NORM_NB * NCH; t += nt) {   // pass 2 (euclidean, standardization): block sums of y^2
+  for (int t = tid; t < nb * NCH; t += nt) {   // pass 2 (euclidean, standardization): block sums of y^2
     const int c = t % NCH, b = t / NCH;
     const float* p = X + (size_t)(b * OVN_NORM_BLK) * OVN_FEAT_C + c;
-    const double m = L.m[c];
-    double q = 0.0;
-#pragma unroll 8
-    for (int i = 0; i < OVN_NORM_BLK; ++i) {
-      const double y = ((double)p[(size_t)i * OVN_FEAT_C] - m) + a;
-      q = __builtin_fma(y, y, q);
-    }
-    L.part[b][c] = q;
+    L.part[b][c] = ovn_norm_block_sumsq(p, b < nfull ? OVN_NORM_BLK : tail, L.m[c], a);
   }
   __syncthreads();
   if (tid < NCH) {
     double q = 0.0;
-    for (int b = 0; b < OVN_NORM_NB; ++b) q += L.part[b][tid];
+    for (int b = 0; b < nb; ++b) q += L.part[b][tid];
     L.s[tid] = 1.0 / sqrt(q > 1e-12 ? q : 1e-12);
   }
   __syncthreads();
@@ -353,11 +366,14 @@ int ovn_conv_forward_f16x3(const OvnConvLayer& L, const float* in, int nb, int h
                            const unsigned* in_max, unsigned* out_max, hipStream_t stream);
 int ovn_absmax_forward(const float* x, int n_scans, long long per_scan, unsigned* out_max, hipStream_t stream);
 
-// delta_head.hip
+// delta_head.hip: the fp32 Delta head at the context's feature width with conv1size 15 (fused fp32 MFMA DeltaLayer + c_conv1 +
+// c_conv2, generic c_conv3, Dense); scratch: n * ovn_delta_pair_bytes(G) + 512 bytes
 int ovn_delta_prepare_w1(const float* c1_kernel_dev, float** w1p_out, hipStream_t stream);
-int ovn_delta_c12_forward(const ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r,
-                          const int32_t* ridx, int n, float* o2, hipStream_t stream);
-int ovn_dense_sigmoid_forward(const ovn_ctx* ctx, const float* o3, int n, float* overlap, float* logit,
+size_t ovn_delta_pair_bytes(int G);
+int ovn_delta_forward(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx, int n,
+                      void* scratch, float* overlap, float* logit, hipStream_t stream);
+// Dense(1) + sigmoid over dense_in floats per pair (fixed reduction order)
+int ovn_dense_sigmoid_forward(const ovn_ctx* ctx, const float* o3, int n, long long dense_in, float* overlap, float* logit,
                               hipStream_t stream);
 
 // delta_head_f16x3.hip.  `scratch` (ovn_delta_f16x3_scratch_bytes(n, ridx != NULL) bytes, caller-owned: 2.9 MB per pair) holds the
@@ -392,32 +408,19 @@ int ovn_delta_walk_stats(ovn_ctx* ctx, int32_t* out16, hipStream_t stream);
 
 // delta_head_generic.hip: the Delta head for any conv1size (fp32, generality path) at feature width ctx->feat_w
 size_t ovn_delta_generic_pair_bytes(int W, int G);
-// Dense(1) + sigmoid over dense_in floats per pair (fixed reduction order)
-int ovn_dense_sigmoid_any_forward(const ovn_ctx* ctx, const float* o3, int n, long long dense_in, float* overlap, float* logit,
-                                  hipStream_t stream);
+int ovn_delta_generic_forward(const ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r,
+                              const int32_t* ridx, int n, void* scratch, float* overlap, float* logit, hipStream_t stream);
 
-// delta_head_w.hip: the Delta head at a feature width W != 360 with conv1size 15 (fused fp32 MFMA DeltaLayer + c_conv1 + c_conv2,
-// generic c_conv3, Dense); scratch: n * ovn_delta_w_pair_bytes(G) + 256 bytes
-size_t ovn_delta_w_pair_bytes(int G);
-int ovn_delta_w_forward(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx, int n,
-                        void* scratch, float* overlap, float* logit, hipStream_t stream);
-
-// delta_head_w_f16x3.hip: DeltaLayer + c_conv1 + c_conv2 of that route in f16x3 arithmetic (ovn_set_head_width_split with head
+// delta_head_w_f16x3.hip: DeltaLayer + c_conv1 + c_conv2 of ovn_delta_forward in f16x3 arithmetic at widths other than 360 (ovn_set_head_width_split with head
 // mode 1): o2 (n, G, G, 128) from n * ovn_delta_w_split_pair_bytes() bytes of per-pair scales (16-byte aligned scratch)
 size_t ovn_delta_w_split_pair_bytes();
 int ovn_delta_w_split_c12_forward(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx,
                                   int n, void* scales, float* o2, hipStream_t stream);
 
-// corr_head_w.hip: the direct correlation head at a feature width W != 360 (fp32 MFMA, all normalisation modes)
-int ovn_corr_w_forward(const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx, int n, int W,
-                       int32_t* yaw, float* corr, hipStream_t stream, int norm_mode);
-int ovn_delta_generic_forward(const ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r,
-                              const int32_t* ridx, int n, void* scratch, float* overlap, float* logit, hipStream_t stream);
-
-// corr_head.hip
-// norm_mode: ovn_set_corr_normalization (0 = none: the kernel of ABI 7, unchanged; else both volumes normalised on load)
-int ovn_corr_forward(const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx,
-                     int n, int32_t* yaw, float* corr, hipStream_t stream, int norm_mode);
+// corr_head.hip: the direct correlation head at feature width W (fp32 MFMA)
+// norm_mode: ovn_set_corr_normalization (0 = none; else both volumes normalised on load)
+int ovn_corr_forward(const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx, int n, int W,
+                     int32_t* yaw, float* corr, hipStream_t stream, int norm_mode);
 
 // corr_spectral.hip
 int ovn_spectral_prepare(ovn_ctx* ctx, hipStream_t stream);

@@ -635,7 +635,8 @@ class OvnEngine:
 
     def debug_head_activations(self, n: int):
         """(o2 (n,G,G,128), o3 (n,G-2,G-2,256)), G = feat_w // 15, left in scratch by the last heads() call -- test hook.
-        At feat_w != 360 only a heads() call that ran as one chunk keeps them."""
+        The fp32 kernels (head precision 'f32', or any precision at feat_w != 360) keep them only for a heads() call that ran as
+        one chunk; the split-operand modes keep those of the call's first sub-chunk."""
         g = self._fw // 15
         o2 = torch.empty((n, g, g, 128), dtype=torch.float32, device=self.device)
         o3 = torch.empty((n, g - 2, g - 2, 256), dtype=torch.float32, device=self.device)
@@ -660,7 +661,7 @@ class OvnEngine:
         'f16x3' (default) = scaled 3-term fp16 split on the fp16 matrix cores (22 significand bits per operand: the error of an
         fp32 evaluation), 'f32' = fp32 matrix cores (bit-for-bit an fp32 FMA chain, 1/16 of the rate), 'bf16x3' = exact 3-term bf16
         split on the bf16 matrix cores (operands at least as wide as fp32: 24 significand bits; include/ovn_hip.h).
-        At a feature width other than 360 every mode runs the exact fp32 heads (delta_head_w.hip / corr_head_w.hip) by default: the
+        At a feature width other than 360 every mode runs the exact fp32 heads of the 'f32' mode (delta_head.hip / corr_head.hip) by default: the
         tuned split-operand kernels are tiled to 24 column groups of 15 and to the 360-point DFT, and fp32 is the reference's own
         arithmetic.  With `set_head_width_split(True)` the 'f16x3' mode runs DeltaLayer + c_conv1 + c_conv2 there in its own
         arithmetic on the runtime-width kernels of delta_head_w_f16x3.hip (c_conv3, Dense and the yaw head stay fp32); 'f32' and

@@ -1,4 +1,4 @@
-"""CPU: the elementwise error bounds at feature widths other than 360 (the runtime-W heads, delta_head_w.hip and corr_head_w.hip).
+"""CPU: the elementwise error bounds at feature widths other than 360 (the fp32 heads at a runtime width, delta_head.hip and corr_head.hip).
 
 The fp64 restatement (oracle/error_bounds.py, tests/_corr_norm_ref.py) is pinned to the oracle at widths that sit on the edges of the
 width kernels' tiling, and every fault below -- built as the output a faulty width kernel would produce and pushed through the rest
@@ -95,7 +95,7 @@ def _tail_from_o2(o2, w):
 
 
 def _fault_gemm2_last_row_tile(l, r, w):
-    """delta_c12_w_kernel run with MT = G // 16 row tiles instead of ceil(G / 16): the o2 rows of the last tile are never written
+    """delta_c12_kernel run with MT = G // 16 row tiles instead of ceil(G / 16): the o2 rows of the last tile are never written
     (left at zero here)."""
     h = E.head_pair(l, r, w)
     o2 = h["o2"].copy()
@@ -116,7 +116,7 @@ def _fault_conv1_reads_late(l, r, w):
 
 
 def _corr_rolled_wrap(l, r):
-    """corr_head_w_kernel wrapping with (W + 1) // 2 instead of W // 2: at odd W every bin reads its right-hand neighbour."""
+    """corr_head_kernel wrapping with (W + 1) // 2 instead of W // 2: at odd W every bin reads its right-hand neighbour."""
     c = E.corr_pair(l, r)
     fw = l.shape[0]
     assert fw % 2 == 1
@@ -137,7 +137,7 @@ def _corr_last_panel_dropped(l, r):
 
 
 def _affine_without_last_block(v, mode):
-    """(m, a, s) of corr_norm_affine_w with its last (partial) 24-column block lost from the statistics; the mean still divides by
+    """(m, a, s) of ovn_corr_norm_affine with its last (partial) 24-column block lost from the statistics; the mean still divides by
     W, as the kernel does."""
     x = np.asarray(v, np.float64)
     fw = x.shape[0]

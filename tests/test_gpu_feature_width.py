@@ -1,4 +1,4 @@
-"""GPU (MI355X): feature widths other than 360 -- the leg, both heads (delta_head_w.hip, corr_head_w.hip, delta_head_generic.hip at a
+"""GPU (MI355X): feature widths other than 360 -- the leg, both heads (delta_head.hip, corr_head.hip, delta_head_generic.hip at a
 runtime W), launch-shape independence and `Infer` end to end, against the fp64 oracle.  Tolerances of tests/test_gpu_parity.py:
 overlap |d| <= 1e-4, logit <= 1e-3 (1 + |logit|), corr / activations <= 2e-5 max|oracle|, identical yaw bin unless the oracle's
 top-two gap is below 1e-5 relative."""
@@ -176,8 +176,9 @@ def test_same_bits_across_launch_shapes(fw):
 
 
 def test_width_371_delta_head_matches_360_fp32(capsys):
-    """At W = 371, G = 24: the Delta head reads only columns < 360 of both volumes, so its overlap equals the 360 fp32 mode's on
-    feats[:, :360] (the same Dense kernel: (24 - 2)^2 * 256 inputs at both widths)."""
+    """At W = 371, G = 24: the Delta head reads only columns < 360 of both volumes, and both engines launch delta_c12_kernel<3, 2>,
+    c_conv3 and dense_sigmoid_kernel over (24 - 2)^2 * 256 inputs on the same operands: overlap and logit have the bits of the 360
+    fp32 mode's on feats[:, :360]."""
     w371 = _weights(371)
     e371 = _engine(371, w371)
     from overlapnet_amd.engine import OvnEngine
@@ -197,10 +198,9 @@ def test_width_371_delta_head_matches_360_fp32(capsys):
         a = e371.heads(v371, v371, lidx=li, ridx=ri, want_logit=True)
         b = e360.heads(v360, v360, lidx=li, ridx=ri, want_logit=True)
         d = float(torch.max(torch.abs(a["overlap"] - b["overlap"])))
-        assert d <= 2e-6
-        same = torch.equal(a["overlap"], b["overlap"]) and torch.equal(a["logit"], b["logit"])
         with capsys.disabled():
-            print("\nW=371 vs 360 fp32 Delta head: max |d overlap| = %.3g, bits equal: %s" % (d, same))
+            print("\nW=371 vs 360 fp32 Delta head: max |d overlap| = %.3g" % d)
+        assert torch.equal(a["overlap"], b["overlap"]) and torch.equal(a["logit"], b["logit"])
     finally:
         e371.close()
         e360.close()

@@ -1,12 +1,13 @@
-"""GPU (MI355X): the runtime-width heads (delta_head_w.hip, corr_head_w.hip) at the ends of every tile-shape range they choose from
-the feature width W, against the elementwise fp64 bounds of oracle/error_bounds.py (the standard the W = 360 path is held to in
-tests/test_gpu_error_bounds.py).
+"""GPU (MI355X): the fp32 heads (delta_head.hip, corr_head.hip) at the ends of every tile-shape range they choose from the feature
+width W, and at the shipped 360 columns, against the elementwise fp64 bounds of oracle/error_bounds.py (the standard the
+split-operand paths at W = 360 are held to in tests/test_gpu_error_bounds.py).
 
-How the width kernels tile, with G = W // 15 and R = 15 G (the rule of ovn_delta_w_forward / ovn_corr_w_forward):
-    delta_c12_w_kernel<T, MT>   T = 3 row tiles per wave for R <= 384, else 4;  MT = ceil(G / 16) GEMM2 row tiles
-    corr_head_w_kernel<T, NORM> T = 3 for W <= 384, else 4;  NORM with a normalisation mode
+How the kernels tile, with G = W // 15 and R = 15 G (the rule of ovn_delta_forward / ovn_corr_forward):
+    delta_c12_kernel<T, MT>   T = 3 row tiles per wave for R <= 384, else 4;  MT = ceil(G / 16) GEMM2 row tiles
+    corr_head_kernel<T, NORM> T = 3 for W <= 384, else 4;  NORM with a normalisation mode
 WIDTHS holds one end of every range: <3,1> 45 / 254, <3,2> 255 / 375 / 384 (R = 375 at both), <4,2> 390 / 494, <4,3> 495 / 512;
-the correlation's <3,*> / <4,*> edge at 384 / 385; G = 3 at 45 (c_conv3 to 1 x 1, a 256-input Dense); 14 unread tail columns at
+360 itself (<3,2>, correlation <3,*>: there the fp32 kernels are head precision "f32", the other two precisions have kernels and
+tests of their own); the correlation's <3,*> / <4,*> edge at 384 / 385; G = 3 at 45 (c_conv3 to 1 x 1, a 256-input Dense); 14 unread tail columns at
 59; a one-column last Gram panel at 385 and a 13-column one at 45; 22 normalisation blocks (the most) at 512.  Each engine is built
 from a real leg geometry (32 x N scans; 64 x N with additional_unsymmetric_layer3a for the A3 cases).  Each test prints its worst
 err / bound per stage (<= 1 passes)."""
@@ -27,19 +28,19 @@ def gpu(f):
     return pytest.mark.gpu(pytest.mark.skipif(not torch.cuda.is_available(), reason="needs an MI355X")(f))
 
 
-# W -> input (H, W) of a leg that produces it, additional_unsymmetric_layer3a off
-WIDTHS = {45: (32, 247), 59: (32, 275), 254: (32, 665), 255: (32, 667), 375: (32, 907), 384: (32, 925), 385: (32, 927),
-          390: (32, 937), 494: (32, 1145), 495: (32, 1147), 512: (32, 1181)}
-A3_GEOM = {45: (64, 269), 512: (64, 1203)}           # the same widths with additional_unsymmetric_layer3a on
+# W -> input (H, W) of a leg that produces it, additional_unsymmetric_layer3a off (but on at 360: 64 x 900 is the shipped geometry)
+WIDTHS = {45: (32, 247), 59: (32, 275), 254: (32, 665), 255: (32, 667), 360: (64, 900), 375: (32, 907), 384: (32, 925),
+          385: (32, 927), 390: (32, 937), 494: (32, 1145), 495: (32, 1147), 512: (32, 1181)}
+A3_GEOM = {45: (64, 269), 360: (64, 900), 512: (64, 1203)}   # widths with additional_unsymmetric_layer3a on
 # W -> (G, Delta T, Delta MT, correlation T), the table of the issue this file was written for
-TILING = {45: (3, 3, 1, 3), 59: (3, 3, 1, 3), 254: (16, 3, 1, 3), 255: (17, 3, 2, 3), 375: (25, 3, 2, 3), 384: (25, 3, 2, 3),
-          385: (25, 3, 2, 4), 390: (26, 4, 2, 4), 494: (32, 4, 2, 4), 495: (33, 4, 3, 4), 512: (34, 4, 3, 4)}
-NORM_WIDTHS = (45, 385, 512)
+TILING = {45: (3, 3, 1, 3), 59: (3, 3, 1, 3), 254: (16, 3, 1, 3), 255: (17, 3, 2, 3), 360: (24, 3, 2, 3), 375: (25, 3, 2, 3),
+          384: (25, 3, 2, 3), 385: (25, 3, 2, 4), 390: (26, 4, 2, 4), 494: (32, 4, 2, 4), 495: (33, 4, 3, 4), 512: (34, 4, 3, 4)}
+NORM_WIDTHS = (45, 360, 385, 512)
 PRECISIONS = ("f32", "f16x3", "bf16x3")
 
 
 def _tiling(fw):
-    """(G, T, MT, correlation T) as ovn_delta_w_forward and ovn_corr_w_forward choose them."""
+    """(G, T, MT, correlation T) as ovn_delta_forward and ovn_corr_forward choose them."""
     g = fw // 15
     return g, 3 if 15 * g <= 384 else 4, -(-g // 16), 3 if fw <= 384 else 4
 
@@ -58,10 +59,13 @@ def test_widths_reach_every_instantiation():
     for t, mt in ((3, 1), (3, 2), (4, 2), (4, 3)):           # both ends of every Delta range
         ws = [fw for fw in WIDTHS if TILING[fw][1:3] == (t, mt)]
         assert len(ws) >= 2, (t, mt)
+    # the shipped 360 columns: delta_c12_kernel<3, 2>, corr_head_kernel<3, false> and, with a mode, <3, true>
+    assert TILING[360] == (24, 3, 2, 3) and 360 in NORM_WIDTHS and 360 % 24 == 0
     assert 59 - 15 * (59 // 15) == 14 and 385 % 16 == 1 and 45 % 16 == 13 and -(-512 // 24) == 22
 
 
 def _cfg(fw, a3=False, **extra):
+    a3 = a3 or fw == 360
     h, w = A3_GEOM[fw] if a3 else WIDTHS[fw]
     return dict(S.REFERENCE_MODEL_CFG, inputShape=[h, w], leg_output_width=fw, additional_unsymmetric_layer3a=a3, **extra)
 
@@ -77,7 +81,7 @@ def _weights(fw, seed=0):
 
 def _engine(fw, w=None, a3=False, **extra):
     from overlapnet_amd.engine import OvnEngine
-    h, wi = A3_GEOM[fw] if a3 else WIDTHS[fw]
+    h, wi = A3_GEOM[fw] if a3 else WIDTHS[fw]                     # (the same entry at 360)
     e = OvnEngine(h, wi, 4)
     try:
         e.load_weights(_weights(fw) if w is None else w, _cfg(fw, a3, **extra))
@@ -153,7 +157,8 @@ def _check_pairs(tag, out, o2, o3, v, pairs, w, worst, corr_bound=None):
 @pytest.mark.parametrize("fw", sorted(WIDTHS), ids=lambda fw: "W%d" % fw)
 def test_stages_against_the_bound(engines, fw):
     """o2 and o3 (through ovn_debug_head_activations), the logit, the overlap and every correlation element of every pair against
-    the fp32 bound, on ReLU volumes with dead channels, a x300 set and the value-edge sets; f16x3 and bf16x3 give the f32 bits."""
+    the fp32 bound, on ReLU volumes with dead channels, a x300 set and the value-edge sets; off 360 f16x3 and bf16x3 give the f32
+    bits (at 360 they are kernels of their own, held to their own bounds in tests/test_gpu_error_bounds.py)."""
     e = engines(fw)
     w = _weights(fw)
     g = fw // 15
@@ -163,13 +168,13 @@ def test_stages_against_the_bound(engines, fw):
         ft = torch.from_numpy(np.ascontiguousarray(v)).cuda()
         li, ri = [p[0] for p in pairs], [p[1] for p in pairs]
         res = {}
-        for prec in PRECISIONS:
+        for prec in PRECISIONS if fw != 360 else PRECISIONS[:1]:
             e.set_head_precision(prec)
             res[prec] = e.heads(ft, ft, lidx=li, ridx=ri, want_logit=True, want_corr=True)
             a2, a3 = e.debug_head_activations(len(pairs))
             res[prec]["o2"], res[prec]["o3"] = a2, a3
         e.set_head_precision("f16x3")
-        for prec in PRECISIONS[1:]:                                 # every precision runs the exact fp32 kernels off 360
+        for prec in PRECISIONS[1:] if fw != 360 else ():            # every precision runs the exact fp32 kernels off 360
             for k in ("overlap", "logit", "yaw", "corr", "o2", "o3"):
                 assert torch.equal(res[prec][k], res["f32"][k]), (name, prec, k)
         o2, o3 = res["f32"]["o2"].cpu().numpy(), res["f32"]["o3"].cpu().numpy()
@@ -214,6 +219,8 @@ def test_routes_and_launch_shapes_same_bits(engines, fw):
     v = torch.from_numpy(_relu(fw, 12, 7 * fw)).cuda()
     q = v[5:6].contiguous()
     try:
+        if fw == 360:
+            e.set_head_precision("f32")                             # off 360 every precision runs these kernels
         a = e.heads(v, q, want_logit=True, want_corr=True)                                      # 1-vs-N
         b = e.heads(v, v, lidx=list(range(12)), ridx=[5] * 12, want_logit=True, want_corr=True)  # the same pairs by index
         parts = [e.heads(v[i:i + 3].contiguous(), q, want_logit=True, want_corr=True) for i in range(0, 12, 3)]   # small sweeps
@@ -248,6 +255,7 @@ def test_routes_and_launch_shapes_same_bits(engines, fw):
             assert torch.equal(tk[bq], one), bq
     finally:
         e.set_head_pipeline(1024)
+        e.set_head_precision("f16x3")
 
 
 # ---- known answer ------------------------------------------------------------------------------------------------------------------
@@ -275,7 +283,7 @@ def test_known_answer_yaw_every_normalize_mode(engines, fw):
 @gpu
 @pytest.mark.parametrize("fw", NORM_WIDTHS, ids=lambda fw: "W%d" % fw)
 def test_normalize_modes_and_negate_diffs(fw):
-    """W = 45 runs corr_head_w_kernel<3, true>, 385 and 512 <4, true>: every mode against corr_norm_pair's direct bound on
+    """W = 45 and 360 run corr_head_kernel<3, true>, 385 and 512 <4, true>: every mode against corr_norm_pair's direct bound on
     edge_volume (its 2^100 channel zeroed in mode 'none', where the products leave fp32); DeltaLayer negateDiffs against the bound
     of the negated c_conv1 kernel, with the Delta head's bits the same in every mode."""
     ev = np.stack([R.edge_volume(fw + i, fw) for i in range(3)])

@@ -1,7 +1,7 @@
-"""Heads throughput at feature widths other than 360: a 1-vs-N sweep (1 query vs --pool candidates) through `engine.heads` (the
-direct correlation head on the feature volumes, no spectra) at W = 360 in the fp32 head mode, and at W = 371 (32 x 900, the leg's
-defaults) and W = 422 (64 x 1024, additional_unsymmetric_layer3a), which run the runtime-W fp32 kernels (delta_head_w.hip,
-corr_head_w.hip).  Seeded synthetic weights and ReLU-like random feature volumes (a quarter of the channels dead).
+"""Heads throughput of the fp32 heads (delta_head.hip, corr_head.hip) across feature widths: a 1-vs-N sweep (1 query vs --pool
+candidates) through `engine.heads` (the direct correlation head on the feature volumes, no spectra) at W = 360 in the fp32 head
+mode (delta_c12_kernel<3,2>, corr_head_kernel<3,false>), at W = 371 (32 x 900, the leg's defaults: the same two instantiations) and
+at W = 422 (64 x 1024, additional_unsymmetric_layer3a: <4,2> and <4,false>).  Seeded synthetic weights and ReLU-like random feature volumes (a quarter of the channels dead).
 
 The widths alternate in rounds inside one process (clock and thermal drift fall on all of them alike); per width and round
 `--warmup` untimed and `--steps` timed sweeps.  Output: ONE JSON object on stdout with pairs/s (median over rounds of the timed

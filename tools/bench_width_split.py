@@ -1,4 +1,4 @@
-"""The Delta head's two arithmetics at feature widths other than 360, side by side: the exact fp32 route (delta_head_w.hip) and the
+"""The Delta head's two arithmetics at feature widths other than 360, side by side: the exact fp32 route (delta_head.hip) and the
 split f16x3 route (delta_head_w_f16x3.hip, `OvnEngine.set_head_width_split(True)`), head precision 'f16x3' in both.
 
 Per width in {371 (32 x 900), 422 (64 x 1024), 512 (32 x 1181)}: ONE engine, a 1-vs-N sweep (1 query vs --pool candidates) through
