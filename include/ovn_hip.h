@@ -148,6 +148,35 @@ int ovn_corr_head_spectral(ovn_ctx* ctx, const float* spec_l_dev, const int32_t*
 #define OVN_DELTA_CACHE_ELEMS 49216
 int ovn_delta_cache(ovn_ctx* ctx, const float* feats_dev, int64_t n, float* cache_dev, void* stream);
 
+/* Fitting the Delta head on frozen legs (the reference's `360OutputkLegsFixed` model, training.py): the gradient of
+ *   L = scale / n * sum_p loss(y_p, t_p),  y_p = the overlap of pair p, t_p = target_dev[p]
+ * with respect to the eight head tensors as registered by ovn_set_head_weights.  Indexing as ovn_heads (lidx NULL: p, ridx NULL: 0).
+ *   loss 0   the reference's my_sigmoid_loss (training.py:71-83): sigmoid(24 |y - t| - 6), d/dy = 24 l (1 - l) sign(y - t), sign(0) = 0
+ *   loss 1   squared error (y - t)^2
+ * ovn_head_param_sizes: elements of c_conv1 kernel, c_conv1 bias, c_conv2 kernel, c_conv2 bias, c_conv3 kernel, c_conv3 bias, Dense
+ * kernel, Dense bias for the context's geometry (s = conv1size, W = feat_w, G = W // s): 128 s 64, 64, s 64 128, 128, 3 3 128 256, 256,
+ * (G - 2)^2 256, 1.
+ *   grad_dev     the eight gradients in that order, concatenated, each in its Keras layout
+ *   loss_dev     1 float: L
+ *   overlap_dev  (n) or NULL: y
+ *   o2_dev, o3_dev   (n, G, G, 128), (n, G - 2, G - 2, 256) or NULL: the c_conv2 / c_conv3 activations of the forward pass
+ * The forward pass has fp32 operands and keeps every stage output in fp32, at any conv1size and width; the sums of a stage are
+ * carried in fp64 and rounded once (the gradient is sensitive to the logit's rounding error), so overlap_dev
+ * may differ from ovn_heads' in the last bits.  ovn_set_head_precision does not affect this call.  ReLU'(0) = 0, the masks come from the stored activations.  A c_conv1
+ * kernel registered negated (DeltaLayer negateDiffs) gets the gradient of that negated kernel.
+ * Deterministic: no floating-point atomics; partial sums per block of OVN_GRAD_PAIR_BLOCK consecutive pairs are added in pair-block
+ * order, so the same call gives the same bits, whatever chunks of pairs the workspace forces (ovn_set_head_pipeline's chunk_pairs
+ * bounds them; chunks are whole pair blocks).  Workspace: about three times the forward's stage outputs per pair of a chunk
+ * (6.3 MB at 360 / 15) plus one set of gradients per pair block.  Under ovn_profile_begin the kernels report as classes 2 (forward),
+ * 4 (loss, Dense gradients), 3 (c_conv3 gradients), 9 (c_conv2 gradients), 8 (c_conv1 gradients).
+ * OVN_ERR_ARG before any launch: NULL ctx / feats / target / grad / loss pointer, n < 1, another `loss`, a non-finite scale;
+ * OVN_ERR_STATE: head weights not registered. */
+#define OVN_GRAD_PAIR_BLOCK 4
+int ovn_head_param_sizes(ovn_ctx* ctx, int64_t* sizes8);
+int ovn_delta_head_grad(ovn_ctx* ctx, const float* feats_l_dev, const int32_t* lidx_dev, const float* feats_r_dev,
+                        const int32_t* ridx_dev, int64_t n, const float* target_dev, int loss, float scale, float* grad_dev,
+                        float* loss_dev, float* overlap_dev, float* o2_dev, float* o3_dev, void* stream);
+
 /* Normalisation of the correlation head's inputs, NormalizedCorrelation2D(normalize=...) (NormalizedCorrelation2D.py:23-73):
  *   0 none (default; what generateCorrelationHead builds, generateNet.py:343), 1 euclidean (the layer's own default:
  *   x / sqrt(max(sum x^2, 1e-12))), 2 scaling ((x - min) / (max - min + 1e-6)), 3 standardization (y = x - mean + 1e-5,

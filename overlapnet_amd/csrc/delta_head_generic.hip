@@ -22,6 +22,12 @@ constexpr int O1 = OVN_C1_OUT;    // 64
 constexpr int IB = 64;            // rows i per workgroup
 constexpr int RPT = 16;           // rows per thread
 
+// Acc = float: the sums run in fp32 in the fixed order (dj, c).  Acc = double (the forward of ovn_delta_head_grad): the same fp32
+// operands and order, the sum carried in fp64 and rounded once, so out1 is the correctly rounded fp32 value.
+__device__ __forceinline__ float acc_fma(float x, float w, float a) { return fmaf(x, w, a); }
+__device__ __forceinline__ double acc_fma(float x, float w, double a) { return fma((double)x, (double)w, a); }
+
+template <typename Acc>
 __global__ __launch_bounds__(256) void delta_c1_generic_kernel(const float* __restrict__ feats_l, const int32_t* __restrict__ lidx,
                                                                const float* __restrict__ feats_r, const int32_t* __restrict__ ridx,
                                                                const float* __restrict__ w1, const float* __restrict__ b1, int s, int G,
@@ -49,9 +55,9 @@ __global__ __launch_bounds__(256) void delta_c1_generic_kernel(const float* __re
   }
   for (int e = tid; e < s * FC / 4; e += 256) *reinterpret_cast<f32x4*>(rl + 4 * e) = *reinterpret_cast<const f32x4*>(R + (size_t)s * jb * FC + 4 * e);
   __syncthreads();
-  float acc[RPT];
+  Acc acc[RPT];
 #pragma unroll
-  for (int u = 0; u < RPT; ++u) acc[u] = 0.f;
+  for (int u = 0; u < RPT; ++u) acc[u] = 0;
   const float* lrow = ll + (RPT * ig) * FC;
   for (int dj = 0; dj < s; ++dj) {
     const float* wrow = w1 + (size_t)dj * FC * O1 + o;
@@ -63,11 +69,11 @@ __global__ __launch_bounds__(256) void delta_c1_generic_kernel(const float* __re
 #pragma unroll
       for (int u = 0; u < RPT; ++u) {
         const f32x4 lv = *reinterpret_cast<const f32x4*>(lrow + u * FC + c);
-        float a = acc[u];
-        a = fmaf(fabsf(lv[0] - rv[0]), w0, a);    // fixed order over (dj, c): deterministic
-        a = fmaf(fabsf(lv[1] - rv[1]), w1v, a);
-        a = fmaf(fabsf(lv[2] - rv[2]), w2, a);
-        a = fmaf(fabsf(lv[3] - rv[3]), w3, a);
+        Acc a = acc[u];
+        a = acc_fma(fabsf(lv[0] - rv[0]), w0, a);    // fixed order over (dj, c): deterministic
+        a = acc_fma(fabsf(lv[1] - rv[1]), w1v, a);
+        a = acc_fma(fabsf(lv[2] - rv[2]), w2, a);
+        a = acc_fma(fabsf(lv[3] - rv[3]), w3, a);
         acc[u] = a;
       }
     }
@@ -76,7 +82,7 @@ __global__ __launch_bounds__(256) void delta_c1_generic_kernel(const float* __re
 #pragma unroll
   for (int u = 0; u < RPT; ++u) {
     const int i = i0 + RPT * ig + u;
-    if (i < FW) out1[(((size_t)pair * FW + i) * G + jb) * O1 + o] = acc[u] + bv;   // c_conv1 is linear (generateNet.py:96-99)
+    if (i < FW) out1[(((size_t)pair * FW + i) * G + jb) * O1 + o] = (float)(acc[u] + (Acc)bv);   // c_conv1 is linear (generateNet.py:96-99)
   }
 }
 
@@ -86,6 +92,20 @@ __global__ __launch_bounds__(256) void delta_c1_generic_kernel(const float* __re
 size_t ovn_delta_generic_pair_bytes(int FW, int G) {
   auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
   return al((size_t)FW * G * O1 * 4) + al((size_t)G * G * OVN_C2_OUT * 4) + al((size_t)(G - 2) * (G - 2) * OVN_C3_OUT * 4);
+}
+
+// DeltaLayer + c_conv1 alone with the sums carried in fp64: out1 (n, W, G, 64), each element the correctly rounded fp32 value
+int ovn_delta_generic_c1_wide(const ovn_ctx* ctx, int FW, const float* feats_l, const int32_t* lidx, const float* feats_r,
+                              const int32_t* ridx, int n, float* out1, hipStream_t stream) {
+  const int s = ctx->head_s, G = ctx->head_g;
+  const size_t lds = ((size_t)IB * FC + (size_t)s * FC) * sizeof(float);
+  int rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_c1_generic_kernel<double>), lds);
+  if (rc) return rc;
+  const int nib = (FW + IB - 1) / IB;
+  hipLaunchKernelGGL(delta_c1_generic_kernel<double>, dim3((unsigned)(nib * G * n)), dim3(256), lds, stream, feats_l, lidx, feats_r, ridx,
+                     ctx->w1raw, ctx->b1, s, G, FW, out1);
+  OVN_HIP_CHECK(hipGetLastError());
+  return OVN_OK;
 }
 
 // The whole Delta head for n pairs at conv1size s = ctx->head_s (any value with W // s >= 3) and feature width W = ctx->feat_w (360
@@ -99,10 +119,10 @@ int ovn_delta_generic_forward(const ovn_ctx* ctx, const float* feats_l, const in
   float* o2 = reinterpret_cast<float*>(static_cast<char*>(scratch) + al((size_t)n * FW * G * O1 * 4));
   float* o3 = reinterpret_cast<float*>(reinterpret_cast<char*>(o2) + al((size_t)n * G * G * OVN_C2_OUT * 4));
   const size_t lds = ((size_t)IB * FC + (size_t)s * FC) * sizeof(float);
-  int rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_c1_generic_kernel), lds);
+  int rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_c1_generic_kernel<float>), lds);
   if (rc) return rc;
   const int nib = (FW + IB - 1) / IB;
-  hipLaunchKernelGGL(delta_c1_generic_kernel, dim3((unsigned)(nib * G * n)), dim3(256), lds, stream, feats_l, lidx, feats_r, ridx,
+  hipLaunchKernelGGL(delta_c1_generic_kernel<float>, dim3((unsigned)(nib * G * n)), dim3(256), lds, stream, feats_l, lidx, feats_r, ridx,
                      ctx->w1raw, ctx->b1, s, G, FW, out1);
   OVN_HIP_CHECK(hipGetLastError());
   int oh = 0, ow = 0;

@@ -119,6 +119,7 @@ int ovn_destroy(ovn_ctx* ctx) {
   if (ctx->w1p_b3) (void)hipFree(ctx->w1p_b3);
   if (ctx->w2p_b3) (void)hipFree(ctx->w2p_b3);
   if (ctx->w2raw) (void)hipFree(ctx->w2raw);
+  if (ctx->w3raw) (void)hipFree(ctx->w3raw);
   if (ctx->ws) (void)hipFree(ctx->ws);
   if (ctx->norm_buf) (void)hipFree(ctx->norm_buf);
   if (ctx->actmax) (void)hipFree(ctx->actmax);
@@ -189,6 +190,8 @@ int ovn_set_head_weights(ovn_ctx* ctx, const float* c1k, const float* c1b, const
     if (ctx->w1p_b3) (void)hipFree(ctx->w1p_b3);
     if (ctx->w2p_b3) (void)hipFree(ctx->w2p_b3);
     if (ctx->w2raw) (void)hipFree(ctx->w2raw);
+    if (ctx->w3raw) (void)hipFree(ctx->w3raw);
+    ctx->w3raw = nullptr;
     ctx->w1p_h = ctx->w2p_h = ctx->wsp_h = ctx->w1p_b3 = ctx->w2p_b3 = nullptr;
     ctx->w1raw = ctx->w1sum = ctx->w1col = ctx->w2sum = ctx->w2raw = nullptr;
     ctx->w1p = ctx->b1 = ctx->wd = ctx->bd = nullptr;
@@ -239,6 +242,15 @@ int ovn_set_head_weights(ovn_ctx* ctx, const float* c1k, const float* c1b, const
   if (!general) {
     rc = ovn_conv_prepare_f16x3(&ctx->c3, c3k, stream);
     if (rc) return rc;
+  }
+  // Keras-order copies for ovn_delta_head_grad: W3 always, W2 where the fast-path preparation above did not leave one
+  const size_t w3_bytes = (size_t)9 * OVN_C2_OUT * OVN_C3_OUT * sizeof(float);
+  OVN_HIP_CHECK(hipMalloc((void**)&ctx->w3raw, w3_bytes));
+  OVN_HIP_CHECK(hipMemcpyAsync(ctx->w3raw, c3k, w3_bytes, hipMemcpyDeviceToDevice, stream));
+  if (!ctx->w2raw) {
+    const size_t w2_bytes = (size_t)hs * OVN_C1_OUT * OVN_C2_OUT * sizeof(float);
+    OVN_HIP_CHECK(hipMalloc((void**)&ctx->w2raw, w2_bytes));
+    OVN_HIP_CHECK(hipMemcpyAsync(ctx->w2raw, c2k, w2_bytes, hipMemcpyDeviceToDevice, stream));
   }
   const size_t dense_in = (size_t)(hg - 2) * (hg - 2) * OVN_C3_OUT;   // 123904 at conv1size 15
   OVN_HIP_CHECK(hipMalloc((void**)&ctx->wd, dense_in * sizeof(float)));
@@ -675,6 +687,25 @@ int ovn_delta_head(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, cons
   OVN_REQUIRE(feats_l && feats_r && overlap, OVN_ERR_ARG, "ovn_delta_head: NULL buffer");
   OVN_ON_DEVICE(ctx->device);
   return delta_head_run(ctx, feats_l, lidx, feats_r, ridx, n, overlap, logit, nullptr, nullptr, 0, nullptr, nullptr, nullptr, (hipStream_t)stream_);
+}
+
+int ovn_head_param_sizes(ovn_ctx* ctx, int64_t* sizes8) {
+  OVN_REQUIRE(ctx && sizes8, OVN_ERR_ARG, "ovn_head_param_sizes: NULL argument");
+  ovn_head_param_sizes_of(ctx->head_s, ctx_feat_w(ctx), sizes8);
+  return OVN_OK;
+}
+
+int ovn_delta_head_grad(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx, int64_t n,
+                        const float* target, int loss, float scale, float* grad, float* loss_dev, float* overlap, float* o2, float* o3,
+                        void* stream_) {
+  OVN_REQUIRE(ctx && feats_l && feats_r && target && grad && loss_dev, OVN_ERR_ARG, "ovn_delta_head_grad: NULL argument");
+  OVN_REQUIRE(n >= 1 && n < (1ll << 31), OVN_ERR_ARG, "ovn_delta_head_grad: bad n %lld", (long long)n);
+  OVN_REQUIRE(loss == 0 || loss == 1, OVN_ERR_ARG, "ovn_delta_head_grad: loss %d (0 = sigmoid loss, 1 = squared error)", loss);
+  OVN_REQUIRE(isfinite(scale), OVN_ERR_ARG, "ovn_delta_head_grad: scale is not finite");
+  OVN_REQUIRE(ctx->head_set, OVN_ERR_STATE, "ovn_delta_head_grad: head weights not set");
+  OVN_ON_DEVICE(ctx->device);
+  return ovn_delta_head_grad_run(ctx, ctx_feat_w(ctx), feats_l, lidx, feats_r, ridx, n, target, loss, scale, grad, loss_dev, overlap, o2,
+                                 o3, (hipStream_t)stream_);
 }
 
 int ovn_delta_cache(ovn_ctx* ctx, const float* feats_dev, int64_t n, float* cache_dev, void* stream) {

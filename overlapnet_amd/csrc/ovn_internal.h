@@ -269,6 +269,7 @@ struct ovn_ctx {
   void* w1p_b3 = nullptr;  // c_conv1 / c_conv2 as three bf16 planes in the fragment orders of the f16x3 path (bf16x3 head mode)
   void* w2p_b3 = nullptr;
   float* w2raw = nullptr;  // c_conv2 kernel as registered, [960][128] (k = di * 64 + o): B operand of TT in bf16x3 mode
+  float* w3raw = nullptr;  // c_conv3 kernel as registered, [3][3][128][256]: the data gradient of ovn_delta_head_grad
   OvnHeadScales hs;
   int leg_mode = 1;        // 0 = fp32 MFMA (conv_f32.hip), 1 = scaled 3-term fp16 split on the fp16 MFMA (conv_f16x3.hip)
   int head_compact = 1;    // ovn_set_head_compaction: 1 = 1-vs-N sweeps drop the query's dead channels from the Delta contraction (exact)
@@ -410,6 +411,14 @@ int ovn_delta_walk_stats(ovn_ctx* ctx, int32_t* out16, hipStream_t stream);
 size_t ovn_delta_generic_pair_bytes(int W, int G);
 int ovn_delta_generic_forward(const ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r,
                               const int32_t* ridx, int n, void* scratch, float* overlap, float* logit, hipStream_t stream);
+int ovn_delta_generic_c1_wide(const ovn_ctx* ctx, int FW, const float* feats_l, const int32_t* lidx, const float* feats_r,
+                              const int32_t* ridx, int n, float* out1, hipStream_t stream);
+
+// delta_head_backward.hip: weight gradients of the Delta head (ovn_delta_head_grad) at feature width FW; sizes8 as ovn_head_param_sizes
+void ovn_head_param_sizes_of(int s, int FW, int64_t* sizes8);
+int ovn_delta_head_grad_run(ovn_ctx* ctx, int FW, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx,
+                            int64_t n, const float* target, int loss, float scale, float* grad, float* loss_out, float* overlap,
+                            float* o2_out, float* o3_out, hipStream_t stream);
 
 // delta_head_w_f16x3.hip: DeltaLayer + c_conv1 + c_conv2 of ovn_delta_forward in f16x3 arithmetic at widths other than 360 (ovn_set_head_width_split with head
 // mode 1): o2 (n, G, G, 128) from n * ovn_delta_w_split_pair_bytes() bytes of per-pair scales (16-byte aligned scratch)

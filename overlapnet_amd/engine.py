@@ -325,6 +325,81 @@ class OvnEngine:
                                               _ptr(corr), self._stream()), "ovn_corr_head")
         return {"yaw": yaw, "corr": corr} if want_corr else {"yaw": yaw}
 
+    # -- fitting the Delta head on frozen legs ---------------------------------------------------------
+    HEAD_PARAMS = ("c_conv1/kernel", "c_conv1/bias", "c_conv2/kernel", "c_conv2/bias", "c_conv3/kernel", "c_conv3/bias",
+                   "overlap_output/kernel", "overlap_output/bias")
+    GRAD_PAIR_BLOCK = 4            # OVN_GRAD_PAIR_BLOCK of include/ovn_hip.h
+    _LOSSES = {"sigmoid": 0, "mse": 1}
+
+    def head_param_sizes(self) -> List[int]:
+        """Elements of the eight head tensors (HEAD_PARAMS order) for this engine's conv1size and feature width."""
+        sizes = (C.c_int64 * 8)()
+        _lib.check(self.lib.ovn_head_param_sizes(self._h, sizes), "ovn_head_param_sizes")
+        return [int(v) for v in sizes]
+
+    def head_param_shapes(self) -> List[Tuple[int, ...]]:
+        """Keras shapes of the eight head tensors (HEAD_PARAMS order)."""
+        shapes = W.expected_shapes(self.in_c, {"conv1NetworkHead_conv1size": self.conv1size}, self._fw)
+        return [tuple(shapes[k]) for k in self.HEAD_PARAMS]
+
+    def set_head_weights(self, params: Sequence[torch.Tensor]) -> None:
+        """Re-register the Delta head from eight float32 device tensors (HEAD_PARAMS order, Keras layouts, c_conv1 as the library
+        holds it: negated under deltaLayer_negateDiffs).  Delta cache rows built under the old weights are stale afterwards."""
+        if len(params) != 8:
+            raise _lib.OvnError("set_head_weights takes the eight head tensors")
+        ts = []
+        for t, size in zip(params, self.head_param_sizes()):
+            if t.device != self.device or t.dtype != torch.float32 or t.numel() != size:
+                raise _lib.OvnError("head tensors must be float32 on %s with %s elements" % (self.device, self.head_param_sizes()))
+            ts.append(t.contiguous())
+        with self._dev():
+            _lib.check(self.lib.ovn_set_head_weights(self._h, *[_ptr(t) for t in ts], self._stream()), "ovn_set_head_weights")
+        self._head_ready = True
+
+    def delta_head_grad(self, feats_l: torch.Tensor, feats_r: torch.Tensor, targets, lidx=None, ridx=None, loss: str = "sigmoid",
+                        scale: float = 1.0, want_activations: bool = False):
+        """Gradient of scale / n * sum_p loss(overlap_p, targets[p]) with respect to the eight head tensors as registered
+        (`ovn_delta_head_grad`; pairs as in `heads`: lidx None -> p, ridx None -> 0).  loss: 'sigmoid' (the reference's
+        my_sigmoid_loss) or 'mse'.  Returns dict: grads (layer name -> {'kernel', 'bias'} device tensors in Keras shapes, views of
+        the one buffer 'flat'), loss (1,), overlap (n) [, o2 (n, G, G, 128), o3 (n, G - 2, G - 2, 256)]."""
+        if not self._head_ready:
+            raise _lib.OvnError("head weights not loaded")
+        if loss not in self._LOSSES:
+            raise ValueError("loss must be one of %s, got %r" % (sorted(self._LOSSES), loss))
+        if not np.isfinite(float(scale)):
+            raise ValueError("scale must be finite")
+        self._check_feats(feats_l, "feats_l")
+        self._check_feats(feats_r, "feats_r")
+        nl = feats_l.numel() // (self._fw * FEAT_C)
+        nr = feats_r.numel() // (self._fw * FEAT_C)
+        if not isinstance(targets, torch.Tensor):
+            targets = torch.from_numpy(np.ascontiguousarray(targets, np.float32))
+        t = targets.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+        li, ri, n = self._pairs(nl, nr, lidx, ridx, t.numel() if lidx is None else None)
+        if n < 1 or t.numel() != n:
+            raise _lib.OvnError("%d targets for %d pairs (at least one pair)" % (t.numel(), n))
+        sizes = self.head_param_sizes()
+        flat = torch.empty(sum(sizes), dtype=torch.float32, device=self.device)
+        lossv = torch.empty(1, dtype=torch.float32, device=self.device)
+        overlap = torch.empty(n, dtype=torch.float32, device=self.device)
+        g = self._fw // self.conv1size
+        o2 = torch.empty((n, g, g, 128), dtype=torch.float32, device=self.device) if want_activations else None
+        o3 = torch.empty((n, g - 2, g - 2, 256), dtype=torch.float32, device=self.device) if want_activations else None
+        with self._dev():
+            _lib.check(self.lib.ovn_delta_head_grad(self._h, _ptr(feats_l), _ptr(li), _ptr(feats_r), _ptr(ri), n, _ptr(t),
+                                                    self._LOSSES[loss], float(scale), _ptr(flat), _ptr(lossv), _ptr(overlap),
+                                                    _ptr(o2), _ptr(o3), self._stream()), "ovn_delta_head_grad")
+        grads: Dict[str, Dict[str, torch.Tensor]] = {}
+        off = 0
+        for name, size, shape in zip(self.HEAD_PARAMS, sizes, self.head_param_shapes()):
+            layer, kind = name.split("/")
+            grads.setdefault(layer, {})[kind] = flat[off:off + size].view(shape)
+            off += size
+        out = {"grads": grads, "flat": flat, "loss": lossv, "overlap": overlap}
+        if want_activations:
+            out["o2"], out["o3"] = o2, o3
+        return out
+
     SPEC_W = 368
     DELTA_CACHE_ELEMS = 49216      # floats per Delta cache row (include/ovn_hip.h: OVN_DELTA_CACHE_ELEMS)
 

@@ -141,6 +141,12 @@ class FeatureVolumeCache(object):
       self._dc.index_copy_(0, idx, self._engine.delta_cache(fv))
     self._n = max(self._n, int(slots.max()) + 1)
 
+  def rebuild_delta_cache(self) -> None:
+    """Recompute the Delta cache rows of every cached volume: a row is valid only for the head weights it was built under, so
+    whoever re-registers the head (train.OverlapHeadTrainer) calls this."""
+    if self._with_dc and self._n and self._fv is not None:
+      self._engine.delta_cache(self._fv[:self._n], out=self._dc[:self._n])
+
   def extend_device(self, fv: torch.Tensor, spec: Optional[torch.Tensor] = None, dc: Optional[torch.Tensor] = None) -> None:
     """Append k volumes (see put_device)."""
     self.put_device(self._n, fv, spec=spec, dc=dc)
