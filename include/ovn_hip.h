@@ -177,6 +177,39 @@ int ovn_delta_head_grad(ovn_ctx* ctx, const float* feats_l_dev, const int32_t* l
                         const int32_t* ridx_dev, int64_t n, const float* target_dev, int loss, float scale, float* grad_dev,
                         float* loss_dev, float* overlap_dev, float* o2_dev, float* o3_dev, void* stream);
 
+/* Both heads' losses differentiated down to the leg outputs (the feature volumes): what a leg trainer needs from the heads.
+ *   L_ov  = overlap_scale / n * sum_p loss(y_p, t_p)                       exactly the loss of ovn_delta_head_grad (same `loss` codes)
+ *   L_yaw = yaw_scale / (n W) * sum_p sum_{k < W} wce(z_p[k], q_p[k])      the reference's my_entropy (training.py:86-92):
+ *           z_p[k] = sum_{j < W, c < 128} l_p[(k + j + W / 2) mod W, c] r_p[j, c]   (NormalizedCorrelation2D 'none' + RangePadding2D),
+ *           q_p[k] = 1 where k == yaw_bin_dev[p] and t_p > min_overlap_for_angle, else 0 (a pair at or below the threshold has q = 0
+ *           and still contributes), wce = weighted_cross_entropy_with_logits with pos_weight = W:
+ *           (1 - q) z + (1 + (W - 1) q) (log1p(exp(-|z|)) + max(-z, 0)).
+ *   dfeat_l_dev, dfeat_r_dev   (n, W, 128): row p = d (L_ov + L_yaw) / d (the left / right volume pair p read).  Per PAIR: rows that
+ *                    address the same pool entry are not summed here (no atomics, no knowledge of the pool).  The overlap part reaches
+ *                    rows < s (W // s) only; sgn(0) = 0 in d|l - r|.
+ *   head_grad_dev    NULL, or the eight head gradients: the bits ovn_delta_head_grad returns for scale = overlap_scale
+ *   loss_dev         2 floats: L_ov, L_yaw
+ *   overlap_dev      (n) or NULL: y, the bits of ovn_delta_head_grad;  corr_dev  (n, W) or NULL: z as defined above, always the
+ *                    un-normalised logits, whatever ovn_set_corr_normalization holds (also when the yaw part is off); NULL with
+ *                    the yaw part off skips the correlation altogether
+ * yaw_bin_dev == NULL or yaw_scale == 0: no yaw part, L_yaw = 0.  overlap_scale == 0: the overlap backward is skipped, its share is
+ * exact zeros, head_grad_dev (if given) is zero-filled, L_ov = 0.  A bin outside [0, W) gives its pair q = 0; it is compared, never
+ * used as an index.  Only correlation normalisation mode 0 ('none', the mode generateCorrelationHead builds) is differentiated.
+ * The forward is ovn_delta_head_grad's (fp64 sums, rounded once); so are z, the scalar chain z -> loss, dL/dz and the yaw gradients.
+ * The Delta data gradient forms E[i, j, c] = sum_o dO1[i, j // s, o] W1[j % s, c, o] tile by tile on the fp32 matrix cores, with the
+ * sign of l - r applied in registers; E is never stored.  fp32 sums run over at most one column group, the groups join in fp64.
+ * Deterministic: no floating-point atomics; the same bits twice and in any chunking (as ovn_delta_head_grad); both loss sums
+ * join in pair-block order.  ovn_set_head_pipeline's chunk_pairs cuts the overlap part only; the yaw part runs in fixed chunks of
+ * 4096 pairs (whole pair blocks, so the bits do not depend on it).  Workspace: ovn_delta_head_grad's, then 12 W bytes per pair (of
+ * at most 4096) for the yaw part, which chunk_pairs does not limit.  Under
+ * ovn_profile_begin the Delta data gradient reports as class 8, the correlation forward / yaw loss / yaw gradients as class 1.
+ * OVN_ERR_ARG before any launch: NULL ctx / feats / target / dfeat / loss pointer, n < 1, another `loss`, a non-finite scale or
+ * threshold; OVN_ERR_STATE: head weights not registered, or the yaw part requested under a correlation normalisation other than 0. */
+int ovn_heads_feature_grad(ovn_ctx* ctx, const float* feats_l_dev, const int32_t* lidx_dev, const float* feats_r_dev,
+                           const int32_t* ridx_dev, int64_t n, const float* overlap_target_dev, const int32_t* yaw_bin_dev, int loss,
+                           float overlap_scale, float yaw_scale, float min_overlap_for_angle, float* dfeat_l_dev, float* dfeat_r_dev,
+                           float* head_grad_dev, float* loss_dev, float* overlap_dev, float* corr_dev, void* stream);
+
 /* Normalisation of the correlation head's inputs, NormalizedCorrelation2D(normalize=...) (NormalizedCorrelation2D.py:23-73):
  *   0 none (default; what generateCorrelationHead builds, generateNet.py:343), 1 euclidean (the layer's own default:
  *   x / sqrt(max(sum x^2, 1e-12))), 2 scaling ((x - min) / (max - min + 1e-6)), 3 standardization (y = x - mean + 1e-5,

@@ -40,6 +40,8 @@ SIGNATURES = {
     "ovn_delta_cache": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp]),
     "ovn_head_param_sizes": (C.c_int, [_vp, _i64p]),
     "ovn_delta_head_grad": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_int, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ovn_heads_feature_grad": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_int, C.c_float, C.c_float, C.c_float, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _vp]),
     "ovn_set_head_pipeline": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int, C.c_int]),
     "ovn_get_head_pipeline": (C.c_int, [_vp, _i64p, _i64p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ovn_best_match": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_float, C.c_int64, _vp, _vp]),

@@ -343,7 +343,7 @@ void ovn_head_param_sizes_of(int s, int FW, int64_t* sizes8) {
 
 int ovn_delta_head_grad_run(ovn_ctx* ctx, int FW, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx,
                             int64_t n, const float* target, int loss, float scale, float* grad, float* loss_out, float* overlap,
-                            float* o2_out, float* o3_out, hipStream_t stream) {
+                            float* o2_out, float* o3_out, hipStream_t stream, float* dfeat_l, float* dfeat_r, bool forward_only) {
   const int s = ctx->head_s, G = ctx->head_g, H = G - 2;
   int64_t sz[8], off[8], total = 0;
   ovn_head_param_sizes_of(s, FW, sz);
@@ -362,8 +362,9 @@ int ovn_delta_head_grad_run(ovn_ctx* ctx, int FW, const float* feats_l, const in
   const int64_t nbmax = (cmax + PB - 1) / PB;
   const size_t b_fwd = al256((size_t)cmax * fwd_pair + 1024), b_d1 = al256((size_t)cmax * o1e * 4), b_d2 = al256((size_t)cmax * o2e * 4),
                b_d3 = al256((size_t)cmax * o3e * 4), b_v = al256((size_t)cmax * 4), b_w3t = al256((size_t)sz[4] * 4),
-               b_w2t = al256((size_t)sz[2] * 4), b_part = al256((size_t)nbmax * stride * 4);
-  int rc = ovn_ws_reserve(ctx, b_fwd + b_d1 + b_d2 + b_d3 + 3 * b_v + b_w3t + b_w2t + b_part, stream);
+               b_w2t = al256((size_t)sz[2] * 4), b_part = al256((size_t)nbmax * stride * 4),
+               b_grad = (grad || forward_only) ? 0 : al256((size_t)total * 4);   // ovn_heads_feature_grad without head_grad_dev: the sums stay in scratch
+  int rc = ovn_ws_reserve(ctx, b_fwd + b_d1 + b_d2 + b_d3 + 3 * b_v + b_w3t + b_w2t + b_part + b_grad, stream);
   if (rc) return rc;
   ctx->dbg_o2 = ctx->dbg_o3 = nullptr;   // the scratch of an earlier head call is overwritten
   ctx->dbg_partial = nullptr;
@@ -383,6 +384,7 @@ int ovn_delta_head_grad_run(ovn_ctx* ctx, int FW, const float* feats_l, const in
   float* w3t = reinterpret_cast<float*>(w += b_v);
   float* w2t = reinterpret_cast<float*>(w += b_w3t);
   float* part = reinterpret_cast<float*>(w += b_w2t);
+  if (!grad && !forward_only) grad = reinterpret_cast<float*>(w += b_part);
   // W3 (tap, ci, co) -> (tap, co, ci); W2 (di, o, ch) -> (di, ch, o)
   hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((sz[4] + 255) / 256)), dim3(256), 0, stream, ctx->w3raw, w3t, 9, O2, O3);
   hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((sz[2] + 255) / 256)), dim3(256), 0, stream, ctx->w2raw, w2t, s, O1, O2);
@@ -407,6 +409,10 @@ int ovn_delta_head_grad_run(ovn_ctx* ctx, int FW, const float* feats_l, const in
     }
     if (o2_out) OVN_HIP_CHECK(hipMemcpyAsync(o2_out + (size_t)p0 * o2e, o2, (size_t)np * o2e * 4, hipMemcpyDeviceToDevice, stream));
     if (o3_out) OVN_HIP_CHECK(hipMemcpyAsync(o3_out + (size_t)p0 * o3e, o3, (size_t)np * o3e * 4, hipMemcpyDeviceToDevice, stream));
+    if (forward_only) {
+      OVN_HIP_CHECK(hipGetLastError());
+      continue;
+    }
     {   // loss, dz, Dense gradients, dO3
       OvnProfScope ps(ctx, OVN_K_DENSE, stream);
       hipLaunchKernelGGL(loss_dz_kernel, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, stream, zbuf, target + p0, np, nb, loss, coef, dz, part,
@@ -438,6 +444,11 @@ int ovn_delta_head_grad_run(ovn_ctx* ctx, int FW, const float* feats_l, const in
                          np, part + off[1], stride);
       hipLaunchKernelGGL(gw1_mfma_kernel, dim3((unsigned)s, (unsigned)nb), dim3(512), 0, stream, fl, li, feats_r, ri, dO1, s, G, FW, np,
                          part + off[0], stride);
+    }
+    if (dfeat_l) {   // ovn_heads_feature_grad: the overlap loss's gradient down to both feature volumes (heads_feature_grad.hip)
+      rc = ovn_delta_data_grad(ctx, FW, fl, li, feats_r, ri, dO1, np, dfeat_l + (size_t)p0 * feat_elems, dfeat_r + (size_t)p0 * feat_elems,
+                               stream);
+      if (rc) return rc;
     }
     hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((total + 1 + 255) / 256)), dim3(256), 0, stream, part, nb, stride,
                        (long long)total, p0 == 0 ? 1 : 0, grad, loss_out);

@@ -708,6 +708,49 @@ int ovn_delta_head_grad(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx,
                                  o3, (hipStream_t)stream_);
 }
 
+int ovn_heads_feature_grad(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx, int64_t n,
+                           const float* target, const int32_t* yaw_bin, int loss, float overlap_scale, float yaw_scale,
+                           float min_overlap_for_angle, float* dfeat_l, float* dfeat_r, float* head_grad, float* loss_dev, float* overlap,
+                           float* corr, void* stream_) {
+  OVN_REQUIRE(ctx && feats_l && feats_r && target && dfeat_l && dfeat_r && loss_dev, OVN_ERR_ARG, "ovn_heads_feature_grad: NULL argument");
+  OVN_REQUIRE(n >= 1 && n < (1ll << 31), OVN_ERR_ARG, "ovn_heads_feature_grad: bad n %lld", (long long)n);
+  OVN_REQUIRE(loss == 0 || loss == 1, OVN_ERR_ARG, "ovn_heads_feature_grad: loss %d (0 = sigmoid loss, 1 = squared error)", loss);
+  OVN_REQUIRE(isfinite(overlap_scale) && isfinite(yaw_scale) && isfinite(min_overlap_for_angle), OVN_ERR_ARG,
+              "ovn_heads_feature_grad: a scale or the threshold is not finite");
+  OVN_REQUIRE(ctx->head_set, OVN_ERR_STATE, "ovn_heads_feature_grad: head weights not set");
+  const bool yaw_on = yaw_bin != nullptr && yaw_scale != 0.f;
+  OVN_REQUIRE(!yaw_on || ctx->corr_norm == 0, OVN_ERR_STATE,
+              "ovn_heads_feature_grad: the yaw loss is differentiated for correlation normalisation 'none' only (mode %d is set)",
+              ctx->corr_norm);
+  OVN_ON_DEVICE(ctx->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  const int fw = ctx_feat_w(ctx);
+  const size_t bytes = (size_t)n * fw * OVN_FEAT_C * sizeof(float);
+  OVN_HIP_CHECK(hipMemsetAsync(dfeat_l, 0, bytes, stream));
+  OVN_HIP_CHECK(hipMemsetAsync(dfeat_r, 0, bytes, stream));
+  OVN_HIP_CHECK(hipMemsetAsync(loss_dev, 0, 2 * sizeof(float), stream));
+  int rc = OVN_OK;
+  if (overlap_scale != 0.f) {
+    rc = ovn_delta_head_grad_run(ctx, fw, feats_l, lidx, feats_r, ridx, n, target, loss, overlap_scale, head_grad, loss_dev, overlap, nullptr,
+                                 nullptr, stream, dfeat_l, dfeat_r);
+  } else {
+    if (head_grad) {
+      int64_t sz[8], total = 0;
+      ovn_head_param_sizes_of(ctx->head_s, fw, sz);
+      for (int t = 0; t < 8; ++t) total += sz[t];
+      OVN_HIP_CHECK(hipMemsetAsync(head_grad, 0, (size_t)total * sizeof(float), stream));
+    }
+    if (overlap)
+      rc = ovn_delta_head_grad_run(ctx, fw, feats_l, lidx, feats_r, ridx, n, target, loss, 0.f, nullptr, nullptr, overlap, nullptr, nullptr,
+                                   stream, nullptr, nullptr, true);
+  }
+  if (rc) return rc;
+  if (yaw_on || corr)
+    rc = ovn_yaw_grad_run(ctx, fw, feats_l, lidx, feats_r, ridx, n, target, yaw_on ? yaw_bin : nullptr, yaw_scale, min_overlap_for_angle,
+                          dfeat_l, dfeat_r, loss_dev + 1, corr, stream);
+  return rc;
+}
+
 int ovn_delta_cache(ovn_ctx* ctx, const float* feats_dev, int64_t n, float* cache_dev, void* stream) {
   OVN_REQUIRE(ctx && ctx->head_set, OVN_ERR_STATE, "ovn_delta_cache: head weights not set");
   OVN_REQUIRE(ctx_feat_w(ctx) == OVN_FEAT_W, OVN_ERR_ARG,

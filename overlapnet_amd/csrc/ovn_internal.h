@@ -418,7 +418,18 @@ int ovn_delta_generic_c1_wide(const ovn_ctx* ctx, int FW, const float* feats_l, 
 void ovn_head_param_sizes_of(int s, int FW, int64_t* sizes8);
 int ovn_delta_head_grad_run(ovn_ctx* ctx, int FW, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx,
                             int64_t n, const float* target, int loss, float scale, float* grad, float* loss_out, float* overlap,
-                            float* o2_out, float* o3_out, hipStream_t stream);
+                            float* o2_out, float* o3_out, hipStream_t stream,
+                            float* dfeat_l = nullptr, float* dfeat_r = nullptr,   // ovn_heads_feature_grad: per-pair (n, FW, 128) rows, zeroed by the caller
+                            bool forward_only = false);                           // overlap (and o2 / o3) alone; grad may then be NULL, as with dfeat_l
+
+// heads_feature_grad.hip: the data gradients behind ovn_heads_feature_grad.  ovn_delta_data_grad: the overlap part of a chunk of np
+// pairs from its dO1 (np, FW, G, 64), stored to rows < R of dfeat_l / dfeat_r (np, FW, 128).  ovn_yaw_grad_run: correlation logits
+// (to `corr` if given), yaw loss (loss_yaw, 1 float) and its gradient ADDED to dfeat_l / dfeat_r; yaw_bin NULL: the logits alone
+int ovn_delta_data_grad(ovn_ctx* ctx, int FW, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx,
+                        const float* dO1, int np, float* dfeat_l, float* dfeat_r, hipStream_t stream);
+int ovn_yaw_grad_run(ovn_ctx* ctx, int FW, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx,
+                     int64_t n, const float* target, const int32_t* yaw_bin, float yaw_scale, float thr, float* dfeat_l, float* dfeat_r,
+                     float* loss_yaw, float* corr, hipStream_t stream);
 
 // delta_head_w_f16x3.hip: DeltaLayer + c_conv1 + c_conv2 of ovn_delta_forward in f16x3 arithmetic at widths other than 360 (ovn_set_head_width_split with head
 // mode 1): o2 (n, G, G, 128) from n * ovn_delta_w_split_pair_bytes() bytes of per-pair scales (16-byte aligned scratch)

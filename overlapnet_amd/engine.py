@@ -400,6 +400,67 @@ class OvnEngine:
             out["o2"], out["o3"] = o2, o3
         return out
 
+    def heads_feature_grad(self, feats_l: torch.Tensor, feats_r: torch.Tensor, targets, yaw_bins=None, lidx=None, ridx=None,
+                           loss: str = "sigmoid", overlap_scale: float = 5.0, yaw_scale: float = 1.0,
+                           min_overlap_for_angle: float = 0.7, want_head_grads: bool = False, want_corr: bool = True):
+        """Both heads' losses differentiated down to the feature volumes (`ovn_heads_feature_grad`; pairs as in `heads`).
+        L_ov = overlap_scale / n sum_p loss(overlap_p, targets[p]) (the loss of `delta_head_grad`), L_yaw = yaw_scale / (n W) sum of
+        the reference's weighted cross entropy of the W correlation logits against the one-hot of yaw_bins[p] (all zeros where
+        targets[p] <= min_overlap_for_angle or the bin lies outside [0, W)).  yaw_bins None: no yaw part.
+        Returns dict: dfeat_l, dfeat_r (n, W, 128): row p = the gradient reaching the volume pair p read (rows that address the same
+        pool entry are NOT summed; `train.heads_loss` does that), loss_overlap, loss_yaw (0-dim views of 'loss' (2,)), overlap (n),
+        corr (n, W): the correlation logits z, always un-normalised, whatever `set_corr_normalization` holds (want_corr=False leaves
+        them out; a call without a yaw part then runs no correlation at all) [, grads, flat as `delta_head_grad` returns them for
+        scale = overlap_scale]."""
+        if not self._head_ready:
+            raise _lib.OvnError("head weights not loaded")
+        if loss not in self._LOSSES:
+            raise ValueError("loss must be one of %s, got %r" % (sorted(self._LOSSES), loss))
+        for name, v in (("overlap_scale", overlap_scale), ("yaw_scale", yaw_scale), ("min_overlap_for_angle", min_overlap_for_angle)):
+            if not np.isfinite(float(v)):
+                raise ValueError("%s must be finite" % name)
+        self._check_feats(feats_l, "feats_l")
+        self._check_feats(feats_r, "feats_r")
+        nl = feats_l.numel() // (self._fw * FEAT_C)
+        nr = feats_r.numel() // (self._fw * FEAT_C)
+        if not isinstance(targets, torch.Tensor):
+            targets = torch.from_numpy(np.ascontiguousarray(targets, np.float32))
+        t = targets.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+        li, ri, n = self._pairs(nl, nr, lidx, ridx, t.numel() if lidx is None else None)
+        if n < 1 or t.numel() != n:
+            raise _lib.OvnError("%d targets for %d pairs (at least one pair)" % (t.numel(), n))
+        yb = None
+        if yaw_bins is not None:
+            if not isinstance(yaw_bins, torch.Tensor):
+                yaw_bins = torch.from_numpy(np.ascontiguousarray(yaw_bins, np.int32))
+            yb = yaw_bins.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+            if yb.numel() != n:
+                raise _lib.OvnError("%d yaw bins for %d pairs" % (yb.numel(), n))
+        dl = torch.empty((n, self._fw, FEAT_C), dtype=torch.float32, device=self.device)
+        dr = torch.empty((n, self._fw, FEAT_C), dtype=torch.float32, device=self.device)
+        lossv = torch.empty(2, dtype=torch.float32, device=self.device)
+        overlap = torch.empty(n, dtype=torch.float32, device=self.device)
+        corr = torch.empty((n, self._fw), dtype=torch.float32, device=self.device) if want_corr else None
+        sizes = self.head_param_sizes()
+        flat = torch.empty(sum(sizes), dtype=torch.float32, device=self.device) if want_head_grads else None
+        with self._dev():
+            _lib.check(self.lib.ovn_heads_feature_grad(self._h, _ptr(feats_l), _ptr(li), _ptr(feats_r), _ptr(ri), n, _ptr(t), _ptr(yb),
+                                                       self._LOSSES[loss], float(overlap_scale), float(yaw_scale),
+                                                       float(min_overlap_for_angle), _ptr(dl), _ptr(dr), _ptr(flat), _ptr(lossv),
+                                                       _ptr(overlap), _ptr(corr), self._stream()), "ovn_heads_feature_grad")
+        out = {"dfeat_l": dl, "dfeat_r": dr, "loss": lossv, "loss_overlap": lossv[0], "loss_yaw": lossv[1], "overlap": overlap}
+        if want_corr:
+            out["corr"] = corr
+        if want_head_grads:
+            grads: Dict[str, Dict[str, torch.Tensor]] = {}
+            off = 0
+            for name, size, shape in zip(self.HEAD_PARAMS, sizes, self.head_param_shapes()):
+                layer, kind = name.split("/")
+                grads.setdefault(layer, {})[kind] = flat[off:off + size].view(shape)
+                off += size
+            out["grads"], out["flat"] = grads, flat
+        return out
+
     SPEC_W = 368
     DELTA_CACHE_ELEMS = 49216      # floats per Delta cache row (include/ovn_hip.h: OVN_DELTA_CACHE_ELEMS)
 

@@ -2,8 +2,13 @@
 down to the one part of the network that is both geometry-dependent and trainable once the legs are frozen.
 
 The gradients come from the HIP library (`OvnEngine.delta_head_grad`, csrc/delta_head_backward.hip); the optimizer is the
-reference's Adagrad (training.py:253) as elementwise torch on the device -- plumbing, not a kernel.  Leg gradients and the yaw
-loss (it has no parameter downstream of frozen legs) are out of scope.
+reference's Adagrad (training.py:253) as elementwise torch on the device -- plumbing, not a kernel.
+
+Training the legs: the yaw head has no weights, so the reference's orientation loss (`my_entropy`, training.py:86-92) acts only
+through the leg outputs, and `OverlapHeadTrainer` (frozen legs) has no use for it.  `heads_loss` is where it exists: both heads'
+losses as ONE differentiable scalar of the feature-volume pools (`OvnEngine.heads_feature_grad`, csrc/heads_feature_grad.hip: the
+overlap loss and the yaw loss differentiated down to the leg outputs on the GPU).  A leg written in torch plugs into it and gets
+d L / d (its output) from `backward()`; the leg's own backward pass and a leg trainer are not part of this package.
 """
 from __future__ import annotations
 
@@ -37,6 +42,68 @@ def epoch_batches(n: int, batch_size: int, epoch: int, seed: int = 0) -> List[np
     perm = np.random.default_rng([int(seed), int(epoch)]).permutation(int(n))
     bs = max(1, int(batch_size))
     return [perm[a:a + bs] for a in range(0, int(n), bs)]
+
+
+def sum_rows_by_entry(rows: torch.Tensor, idx, entries: int) -> torch.Tensor:
+    """rows (n, ...) -> (entries, ...): out[e] = the sum of rows[p] over the pairs p with idx[p] == e, in a fixed order, so the
+    same bits every time: the pairs are sorted by entry (stable: pair order inside an entry) and every entry's run is summed by one
+    pairwise tree -- round d adds, inside each run, position r + d onto position r for the r that are multiples of 2 d.  Within a
+    round no destination occurs twice, so no float `index_add_` and no atomics; ceil(log2(longest run)) rounds, each one indexed
+    add over the rows, whatever the batch size (the 1-vs-N form, in which every pair addresses entry 0, costs log2 N rounds).  An
+    index list that lives on the device is copied to the host once."""
+    idx = np.asarray(idx.cpu() if isinstance(idx, torch.Tensor) else idx, np.int64).reshape(-1)
+    if len(idx) != rows.shape[0]:
+        raise ValueError("%d indices for %d rows" % (len(idx), rows.shape[0]))
+    out = torch.zeros((int(entries),) + tuple(rows.shape[1:]), dtype=rows.dtype, device=rows.device)
+    if len(idx) == 0:
+        return out
+    order = np.argsort(idx, kind="stable")
+    si = idx[order]
+    start = np.concatenate([[0], np.flatnonzero(si[1:] != si[:-1]) + 1])
+    length = np.diff(np.concatenate([start, [len(si)]]))
+    rank = np.arange(len(si)) - np.repeat(start, length)
+    left = np.repeat(length, length) - rank                      # rows from this position to the end of its run
+    buf = rows[torch.from_numpy(order).to(rows.device)]
+    d = 1
+    while d < int(length.max()):
+        dst = torch.from_numpy(np.flatnonzero((rank % (2 * d) == 0) & (left > d))).to(rows.device)
+        buf[dst] = buf[dst] + buf[dst + d]
+        d *= 2
+    out[torch.from_numpy(si[start]).to(rows.device)] = buf[torch.from_numpy(start).to(rows.device)]
+    return out
+
+
+class _HeadsLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feats_l, feats_r, engine, targets, yaw_bins, lidx, ridx, kw):
+        fl, fr = feats_l.detach().contiguous(), feats_r.detach().contiguous()
+        r = engine.heads_feature_grad(fl, fr, targets, yaw_bins, lidx=lidx, ridx=ridx, want_corr=False, **kw)    # the one engine call
+        n = r["overlap"].numel()
+        nl, nr = fl.numel() // (engine._fw * 128), fr.numel() // (engine._fw * 128)
+        # a pool that asks for no gradient (a frozen leg, torch.no_grad()) gets no sum and keeps nothing
+        ctx.gl = ctx.gr = None
+        if ctx.needs_input_grad[0]:
+            ctx.gl = sum_rows_by_entry(r["dfeat_l"], np.arange(n) if lidx is None else lidx, nl).view(feats_l.shape)
+        if ctx.needs_input_grad[1]:
+            ctx.gr = sum_rows_by_entry(r["dfeat_r"], np.zeros(n, np.int64) if ridx is None else ridx, nr).view(feats_r.shape)
+        return r["loss_overlap"] + r["loss_yaw"]
+
+    @staticmethod
+    def backward(ctx, g):
+        return (None if ctx.gl is None else g * ctx.gl, None if ctx.gr is None else g * ctx.gr, None, None, None, None, None, None)
+
+
+def heads_loss(engine, feats_l: torch.Tensor, feats_r: torch.Tensor, targets, yaw_bins, lidx=None, ridx=None, loss: str = "sigmoid",
+               overlap_scale: float = 5.0, yaw_scale: float = 1.0, min_overlap_for_angle: float = 0.7) -> torch.Tensor:
+    """The reference's training loss of a batch of pairs, lossWeights included (training.py:240-252), as a 0-dim tensor that is
+    differentiable with respect to the feature-volume pools feats_l (k, W, 128) and feats_r (the same tensor may be both):
+    overlap_scale / n sum_p loss(overlap_p, targets[p]) + yaw_scale / (n W) sum of the weighted cross entropy of the correlation
+    logits against yaw_bins (`OvnEngine.heads_feature_grad`; pairs as in `heads`: lidx None -> p, ridx None -> 0, the 1-vs-N form in
+    which every pair addresses right entry 0).  The engine runs once, in forward; backward hands each pool the per-pair rows summed
+    over the pairs that address each entry, in a fixed order (`sum_rows_by_entry`: deterministic).  The head weights are constants here;
+    their gradients come from `OvnEngine.heads_feature_grad(..., want_head_grads=True)` or `delta_head_grad`."""
+    kw = dict(loss=loss, overlap_scale=overlap_scale, yaw_scale=yaw_scale, min_overlap_for_angle=min_overlap_for_angle)
+    return _HeadsLoss.apply(feats_l, feats_r, engine, targets, yaw_bins, lidx, ridx, kw)
 
 
 class OverlapHeadTrainer(object):
