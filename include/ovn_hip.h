@@ -210,6 +210,46 @@ int ovn_heads_feature_grad(ovn_ctx* ctx, const float* feats_l_dev, const int32_t
                            float overlap_scale, float yaw_scale, float min_overlap_for_angle, float* dfeat_l_dev, float* dfeat_r_dev,
                            float* head_grad_dev, float* loss_dev, float* overlap_dev, float* corr_dev, void* stream);
 
+/* Training the legs (the reference's default: training.py trains the whole Siamese network): the leg's forward with every layer
+ * output kept, and its backward.  Together with ovn_heads_feature_grad this is the gradient of both losses with respect to all
+ * 2 x layers leg tensors.
+ *   ovn_leg_layer_count        *layers = number of registered leg layers
+ *   ovn_leg_param_sizes        sizes[2 li], sizes[2 li + 1] = elements of layer li's kernel (kh, kw, cin, cout: Keras layout) and bias
+ *   ovn_leg_activation_sizes   sizes[li] = elements per scan of layer li's output (oh, ow, cout) for the context's input geometry
+ * ovn_leg_forward_train: images_dev (n, in_h, in_w, in_c) -> acts_dev, layer-major: block li is (n, oh_li, ow_li, cout_li), all n
+ *   scans of a layer together; the last block is the feature volumes (n, feat_w, 128).  Exact fp32 (the fp32 MFMA convolution of leg
+ *   precision 0, layer by layer), whatever ovn_set_leg_precision holds: the last block has the bits ovn_leg gives in precision 0.
+ * ovn_leg_backward: dfeat_dev (n, feat_w, 128) = dL/d(feature volume of scan i), already summed over the pairs that read it;
+ *   grad_dev = the 2 x layers gradients in the order of ovn_leg_param_sizes, concatenated, each summed over the n scans.
+ *   ReLU'(0) = 0, the masks come from acts_dev.  The input images get no gradient (nothing trains upstream), so the data gradient
+ *   stops at the input of the second layer.  slice_scans: 0 = the library's choice (32); otherwise the scans are processed in slices
+ *   of at most that many, rounded down to whole scan blocks (at least one).
+ *   Sums: an fp32 MFMA accumulator runs over at most 256 terms; everything above that joins in fp64 and is rounded once.
+ *   Deterministic: no floating-point atomics; partial sums are cut inside blocks of OVN_LEG_GRAD_SCAN_BLOCK consecutive scans and
+ *   added in (scan block, piece) order, so the same call gives the same bits twice, and the same bits for every slice_scans.
+ *   Workspace: two buffers of the largest activation per scan of a slice, the fp64 sums (8 bytes per weight) and the partials of
+ *   one layer (a slice of 32 scans of 64 x 900 x 4: about 200 MB).  The kernels report as class 0 under ovn_profile_begin.
+ * ovn_set_leg_layer_weights: replaces the weights of leg layer `layer` in a FINALIZED context (ovn_add_leg_layer keeps refusing
+ *   calls after ovn_finalize) and rebuilds every copy derived from them; afterwards ovn_leg in every precision mode gives the bits
+ *   of a fresh context loaded with the new weights.  Synchronises `stream`.  Cached feature volumes, spectra and Delta cache rows
+ *   computed by the old weights are stale.
+ * ovn_debug_conv_grad (test hook, companion of ovn_debug_conv): the three gradients of leg layer `layer` alone on an arbitrary
+ *   input in_dev (nb, h, w, cin) with its stored output out_dev (nb, oh, ow, cout) and dout_dev = dL/d(out): din_dev (nb, h, w, cin),
+ *   dkernel_dev, dbias_dev; any of the three may be NULL.  din_dev is available for every layer: a layer whose cin is not a multiple
+ *   of 16 (the first one) runs a plain fp64 kernel instead of the MFMA one.
+ * OVN_ERR_ARG before any launch: NULL ctx / buffer, n (nb) < 1, slice_scans < 0, a bad layer index, an input smaller than the kernel;
+ * OVN_ERR_STATE: context not finalized (ovn_leg_activation_sizes, ovn_leg_forward_train, ovn_leg_backward, ovn_set_leg_layer_weights). */
+#define OVN_LEG_GRAD_SCAN_BLOCK 4
+int ovn_leg_layer_count(ovn_ctx* ctx, int* layers);
+int ovn_leg_param_sizes(ovn_ctx* ctx, int64_t* sizes);
+int ovn_leg_activation_sizes(ovn_ctx* ctx, int64_t* sizes);
+int ovn_leg_forward_train(ovn_ctx* ctx, const float* images_dev, int64_t n, float* acts_dev, void* stream);
+int ovn_leg_backward(ovn_ctx* ctx, const float* images_dev, const float* acts_dev, int64_t n, const float* dfeat_dev, float* grad_dev,
+                     int64_t slice_scans, void* stream);
+int ovn_set_leg_layer_weights(ovn_ctx* ctx, int layer, const float* kernel_dev, const float* bias_dev, void* stream);
+int ovn_debug_conv_grad(ovn_ctx* ctx, int layer, const float* in_dev, const float* out_dev, const float* dout_dev, int nb, int h, int w,
+                        float* din_dev, float* dkernel_dev, float* dbias_dev, void* stream);
+
 /* Normalisation of the correlation head's inputs, NormalizedCorrelation2D(normalize=...) (NormalizedCorrelation2D.py:23-73):
  *   0 none (default; what generateCorrelationHead builds, generateNet.py:343), 1 euclidean (the layer's own default:
  *   x / sqrt(max(sum x^2, 1e-12))), 2 scaling ((x - min) / (max - min + 1e-6)), 3 standardization (y = x - mean + 1e-5,

@@ -42,7 +42,14 @@ SIGNATURES = {
     "ovn_delta_head_grad": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_int, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ovn_heads_feature_grad": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_int, C.c_float, C.c_float, C.c_float, _vp, _vp,
                                          _vp, _vp, _vp, _vp, _vp]),
-    "ovn_set_head_pipeline": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int, C.c_int]),
+    "ovn_leg_layer_count": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "ovn_leg_param_sizes": (C.c_int, [_vp, _i64p]),
+    "ovn_leg_activation_sizes": (C.c_int, [_vp, _i64p]),
+    "ovn_leg_forward_train": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp]),
+    "ovn_leg_backward": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_int64, _vp]),
+    "ovn_set_leg_layer_weights": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    "ovn_debug_conv_grad": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "ovn_set_head_pipeline":(C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int, C.c_int]),
     "ovn_get_head_pipeline": (C.c_int, [_vp, _i64p, _i64p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ovn_best_match": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_float, C.c_int64, _vp, _vp]),
     "ovn_top_k": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int, C.c_float, C.c_int64, _vp, _vp]),

@@ -229,6 +229,8 @@ void ovn_conv_release(OvnConvLayer* L) {
   L->wp_h = nullptr;
   if (L->wp_h16) (void)hipFree(L->wp_h16);
   L->wp_h16 = nullptr;
+  if (L->wraw) (void)hipFree(L->wraw);
+  L->wraw = nullptr;
   L->wp = nullptr;
   L->bias = nullptr;
 }

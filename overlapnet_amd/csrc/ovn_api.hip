@@ -139,6 +139,25 @@ int ovn_destroy(ovn_ctx* ctx) {
   return OVN_OK;
 }
 
+// Every device copy a leg layer keeps of its weights: the fp32 fragments + bias, the f16x3 fragments, and the kernel as registered
+// (the data gradient of ovn_leg_backward reads it).  On failure nothing is left allocated.
+static int leg_layer_prepare(OvnConvLayer* L, const float* kernel_dev, const float* bias_dev, hipStream_t stream) {
+  int rc = ovn_conv_prepare(L, kernel_dev, bias_dev, stream);
+  if (rc == OVN_OK) rc = ovn_conv_prepare_f16x3(L, kernel_dev, stream);
+  if (rc == OVN_OK) {
+    const size_t bytes = (size_t)L->kh * L->kw * L->cin * L->cout * sizeof(float);
+    hipError_t e = hipMalloc((void**)&L->wraw, bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(L->wraw, kernel_dev, bytes, hipMemcpyDeviceToDevice, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) {
+      ovn_set_error("layer %s: keeping the raw kernel failed: %s", L->name.c_str(), hipGetErrorString(e));
+      rc = OVN_ERR_HIP;
+    }
+  }
+  if (rc) ovn_conv_release(L);
+  return rc;
+}
+
 int ovn_add_leg_layer(ovn_ctx* ctx, const char* name, const float* kernel_dev, const float* bias_dev, int kh, int kw,
                       int cin, int cout, int stride_h, int stride_w, void* stream) {
   OVN_REQUIRE(ctx && name && kernel_dev && bias_dev, OVN_ERR_ARG, "ovn_add_leg_layer: NULL argument");
@@ -157,14 +176,25 @@ int ovn_add_leg_layer(ovn_ctx* ctx, const char* name, const float* kernel_dev, c
   L.sh = stride_h;
   L.sw = stride_w;
   L.relu = 1;  // every leg layer is Conv2D(..., activation='relu'), generateNet.py:161-214
-  int rc = ovn_conv_prepare(&L, kernel_dev, bias_dev, (hipStream_t)stream);
+  int rc = leg_layer_prepare(&L, kernel_dev, bias_dev, (hipStream_t)stream);
   if (rc) return rc;
-  rc = ovn_conv_prepare_f16x3(&L, kernel_dev, (hipStream_t)stream);
-  if (rc) {
-    ovn_conv_release(&L);
-    return rc;
-  }
   ctx->leg.push_back(L);
+  return OVN_OK;
+}
+
+int ovn_set_leg_layer_weights(ovn_ctx* ctx, int layer, const float* kernel_dev, const float* bias_dev, void* stream) {
+  OVN_REQUIRE(ctx && kernel_dev && bias_dev, OVN_ERR_ARG, "ovn_set_leg_layer_weights: NULL argument");
+  OVN_REQUIRE(ctx->finalized, OVN_ERR_STATE, "ovn_set_leg_layer_weights: context not finalized");
+  OVN_REQUIRE(layer >= 0 && layer < (int)ctx->leg.size(), OVN_ERR_ARG, "ovn_set_leg_layer_weights: no such leg layer %d", layer);
+  OVN_ON_DEVICE(ctx->device);
+  OvnConvLayer N = ctx->leg[layer];       // geometry; the new copies are built beside the old ones, which stay valid on failure
+  N.wp = N.bias = N.wraw = nullptr;
+  N.wp_h = N.wp_h16 = nullptr;
+  N.sw_h = 1.f;
+  int rc = leg_layer_prepare(&N, kernel_dev, bias_dev, (hipStream_t)stream);   // synchronises `stream`
+  if (rc) return rc;
+  ovn_conv_release(&ctx->leg[layer]);     // hipFree waits for whatever still reads the old copies
+  ctx->leg[layer] = N;
   return OVN_OK;
 }
 
@@ -370,6 +400,168 @@ int ovn_leg(ovn_ctx* ctx, const float* images_dev, int64_t n, float* features_de
     }
   }
   return OVN_OK;
+}
+
+// ---- training the legs (leg_backward.hip) ---------------------------------------------------------------------------------------
+// per layer: input height / width and elements per scan of its output
+struct LegGeom {
+  std::vector<int> h, w;
+  std::vector<int64_t> act;
+  int64_t act_total = 0, act_max = 0, params = 0;
+};
+
+static LegGeom leg_geom(const ovn_ctx* ctx) {
+  LegGeom g;
+  int h = ctx->in_h, w = ctx->in_w;
+  for (const auto& l : ctx->leg) {
+    g.h.push_back(h);
+    g.w.push_back(w);
+    h = (h - l.kh) / l.sh + 1;
+    w = (w - l.kw) / l.sw + 1;
+    g.act.push_back((int64_t)h * w * l.cout);
+    g.act_total += g.act.back();
+    g.act_max = std::max(g.act_max, g.act.back());
+    g.params += (int64_t)l.kh * l.kw * l.cin * l.cout + l.cout;
+  }
+  return g;
+}
+
+static void scratch_overwritten(ovn_ctx* ctx) {   // the debug hooks of an earlier head call pointed into the scratch
+  ctx->dbg_o2 = ctx->dbg_o3 = nullptr;
+  ctx->dbg_partial = nullptr;
+  ctx->dbg_o2max = nullptr;
+  ctx->dbg_n = 0;
+  ctx->dbg_live = nullptr;
+}
+
+int ovn_leg_layer_count(ovn_ctx* ctx, int* layers) {
+  OVN_REQUIRE(ctx && layers, OVN_ERR_ARG, "ovn_leg_layer_count: NULL argument");
+  *layers = (int)ctx->leg.size();
+  return OVN_OK;
+}
+
+int ovn_leg_param_sizes(ovn_ctx* ctx, int64_t* sizes) {
+  OVN_REQUIRE(ctx && sizes, OVN_ERR_ARG, "ovn_leg_param_sizes: NULL argument");
+  for (size_t li = 0; li < ctx->leg.size(); ++li) {
+    const auto& l = ctx->leg[li];
+    sizes[2 * li] = (int64_t)l.kh * l.kw * l.cin * l.cout;
+    sizes[2 * li + 1] = l.cout;
+  }
+  return OVN_OK;
+}
+
+int ovn_leg_activation_sizes(ovn_ctx* ctx, int64_t* sizes) {
+  OVN_REQUIRE(ctx && sizes, OVN_ERR_ARG, "ovn_leg_activation_sizes: NULL argument");
+  OVN_REQUIRE(ctx->finalized, OVN_ERR_STATE, "ovn_leg_activation_sizes: context not finalized");
+  const LegGeom g = leg_geom(ctx);
+  for (size_t li = 0; li < g.act.size(); ++li) sizes[li] = g.act[li];
+  return OVN_OK;
+}
+
+int ovn_leg_forward_train(ovn_ctx* ctx, const float* images_dev, int64_t n, float* acts_dev, void* stream_) {
+  OVN_REQUIRE(ctx && images_dev && acts_dev, OVN_ERR_ARG, "ovn_leg_forward_train: NULL argument");
+  OVN_REQUIRE(n >= 1 && n < (1ll << 31), OVN_ERR_ARG, "ovn_leg_forward_train: bad n %lld", (long long)n);
+  OVN_REQUIRE(ctx->finalized, OVN_ERR_STATE, "ovn_leg_forward_train: context not finalized");
+  OVN_ON_DEVICE(ctx->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  const LegGeom g = leg_geom(ctx);
+  const float* cur = images_dev;
+  float* dst = acts_dev;
+  for (size_t li = 0; li < ctx->leg.size(); ++li) {
+    OvnProfScope ps(ctx, OVN_K_LEG, stream);
+    int oh = 0, ow = 0;
+    int rc = ovn_conv_forward(ctx->leg[li], cur, (int)n, g.h[li], g.w[li], dst, &oh, &ow, stream);
+    if (rc) return rc;
+    cur = dst;
+    dst += (size_t)n * g.act[li];
+  }
+  return OVN_OK;
+}
+
+int ovn_leg_backward(ovn_ctx* ctx, const float* images_dev, const float* acts_dev, int64_t n, const float* dfeat_dev, float* grad_dev,
+                     int64_t slice_scans, void* stream_) {
+  OVN_REQUIRE(ctx && images_dev && acts_dev && dfeat_dev && grad_dev, OVN_ERR_ARG, "ovn_leg_backward: NULL argument");
+  OVN_REQUIRE(n >= 1 && n < (1ll << 31), OVN_ERR_ARG, "ovn_leg_backward: bad n %lld", (long long)n);
+  OVN_REQUIRE(slice_scans >= 0, OVN_ERR_ARG, "ovn_leg_backward: slice_scans %lld < 0", (long long)slice_scans);
+  OVN_REQUIRE(ctx->finalized, OVN_ERR_STATE, "ovn_leg_backward: context not finalized");
+  OVN_ON_DEVICE(ctx->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  const LegGeom g = leg_geom(ctx);
+  const int L = (int)ctx->leg.size();
+  constexpr int64_t SB = OVN_LEG_GRAD_SCAN_BLOCK;
+  int64_t slice = slice_scans == 0 ? 8 * SB : std::max<int64_t>(SB, slice_scans / SB * SB);
+  slice = std::min(slice, std::min<int64_t>((n + SB - 1) / SB * SB, 65535 / SB * SB));
+  const int nmax = (int)std::min(slice, n);
+  size_t part_bytes = 0;
+  for (int li = 0; li < L; ++li) part_bytes = std::max(part_bytes, ovn_leg_grad_part_bytes(ctx->leg[li], g.h[li], g.w[li], nmax));
+  const size_t buf_bytes = ((size_t)nmax * g.act_max * sizeof(float) + 255) & ~(size_t)255;
+  const size_t acc_bytes = ((size_t)g.params * sizeof(double) + 255) & ~(size_t)255;
+  int rc = ovn_ws_reserve(ctx, 2 * buf_bytes + acc_bytes + part_bytes, stream);
+  if (rc) return rc;
+  scratch_overwritten(ctx);
+  char* ws = static_cast<char*>(ctx->ws);
+  float* buf[2] = {reinterpret_cast<float*>(ws), reinterpret_cast<float*>(ws + buf_bytes)};
+  double* acc = reinterpret_cast<double*>(ws + 2 * buf_bytes);
+  double* part = reinterpret_cast<double*>(ws + 2 * buf_bytes + acc_bytes);
+  OVN_HIP_CHECK(hipMemsetAsync(acc, 0, (size_t)g.params * sizeof(double), stream));
+  std::vector<int64_t> act_off(L, 0), par_off(L, 0);
+  for (int li = 1; li < L; ++li) {
+    act_off[li] = act_off[li - 1] + g.act[li - 1];
+    par_off[li] = par_off[li - 1] + (int64_t)ctx->leg[li - 1].K * ctx->leg[li - 1].cout + ctx->leg[li - 1].cout;
+  }
+  const size_t in_elems = (size_t)ctx->in_h * ctx->in_w * ctx->in_c;
+  for (int64_t s0 = 0; s0 < n; s0 += slice) {
+    const int nb = (int)std::min(slice, n - s0);
+    OvnProfScope ps(ctx, OVN_K_LEG, stream);
+    int cur = 0;
+    rc = ovn_leg_mask_forward(dfeat_dev + (size_t)s0 * g.act[L - 1], acts_dev + (size_t)n * act_off[L - 1] + (size_t)s0 * g.act[L - 1],
+                              buf[cur], (long long)nb * g.act[L - 1], stream);
+    if (rc) return rc;
+    for (int li = L - 1; li >= 0; --li) {
+      const auto& l = ctx->leg[li];
+      const float* x = li ? acts_dev + (size_t)n * act_off[li - 1] + (size_t)s0 * g.act[li - 1] : images_dev + (size_t)s0 * in_elems;
+      double* ak = acc + par_off[li];
+      // nothing trains upstream of the leg: the data gradient stops at the input of layer 1
+      rc = ovn_leg_layer_backward(l, x, buf[cur], nb, g.h[li], g.w[li], li ? buf[cur ^ 1] : nullptr, li ? x : nullptr, ak,
+                                  ak + (int64_t)l.K * l.cout, part, stream);
+      if (rc) return rc;
+      cur ^= 1;
+    }
+  }
+  return ovn_leg_grad_round(acc, grad_dev, g.params, stream);
+}
+
+int ovn_debug_conv_grad(ovn_ctx* ctx, int layer, const float* in_dev, const float* out_dev, const float* dout_dev, int nb, int h, int w,
+                        float* din_dev, float* dkernel_dev, float* dbias_dev, void* stream_) {
+  OVN_REQUIRE(ctx && in_dev && out_dev && dout_dev, OVN_ERR_ARG, "ovn_debug_conv_grad: NULL argument");
+  OVN_REQUIRE(layer >= 0 && layer < (int)ctx->leg.size(), OVN_ERR_ARG, "ovn_debug_conv_grad: no such leg layer %d", layer);
+  OVN_REQUIRE(nb >= 1 && nb <= 65535, OVN_ERR_ARG, "ovn_debug_conv_grad: bad nb %d", nb);
+  const OvnConvLayer& l = ctx->leg[layer];
+  OVN_REQUIRE(h >= l.kh && w >= l.kw, OVN_ERR_ARG, "ovn_debug_conv_grad: input %dx%d smaller than the kernel of %s", h, w, l.name.c_str());
+  OVN_ON_DEVICE(ctx->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  const int oh = (h - l.kh) / l.sh + 1, ow = (w - l.kw) / l.sw + 1;
+  const long long out_elems = (long long)nb * oh * ow * l.cout;
+  const int64_t kelems = (int64_t)l.K * l.cout;
+  const size_t buf_bytes = ((size_t)out_elems * sizeof(float) + 255) & ~(size_t)255;
+  const size_t acc_bytes = ((size_t)(kelems + l.cout) * sizeof(double) + 255) & ~(size_t)255;
+  int rc = ovn_ws_reserve(ctx, buf_bytes + acc_bytes + ovn_leg_grad_part_bytes(l, h, w, nb), stream);
+  if (rc) return rc;
+  scratch_overwritten(ctx);
+  char* ws = static_cast<char*>(ctx->ws);
+  float* dym = reinterpret_cast<float*>(ws);
+  double* acc = reinterpret_cast<double*>(ws + buf_bytes);
+  double* part = reinterpret_cast<double*>(ws + buf_bytes + acc_bytes);
+  OVN_HIP_CHECK(hipMemsetAsync(acc, 0, (size_t)(kelems + l.cout) * sizeof(double), stream));
+  OvnProfScope ps(ctx, OVN_K_LEG, stream);
+  rc = ovn_leg_mask_forward(dout_dev, out_dev, dym, out_elems, stream);
+  if (rc) return rc;
+  rc = ovn_leg_layer_backward(l, in_dev, dym, nb, h, w, din_dev, nullptr, dkernel_dev ? acc : nullptr, dbias_dev ? acc + kelems : nullptr,
+                              part, stream);
+  if (rc) return rc;
+  if (dkernel_dev) rc = ovn_leg_grad_round(acc, dkernel_dev, kelems, stream);
+  if (rc == OVN_OK && dbias_dev) rc = ovn_leg_grad_round(acc + kelems, dbias_dev, l.cout, stream);
+  return rc;
 }
 
 int ovn_corr_head(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx,

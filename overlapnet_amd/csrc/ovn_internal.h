@@ -243,6 +243,7 @@ struct OvnConvLayer {
   float sw_h = 1.f;       // power-of-two weight scale of wp_h
   void* wp_h16 = nullptr; // layers with cin 4 / 16 and kw <= 16: the same fragments in the K order (ky, kx padded to 16, c) of the
                           // pixel-major strip kernel (conv_strip.hip), [kh * 512 / cin... steps][cout/16][2][64][8]
+  float* wraw = nullptr;  // leg layers: the kernel as registered, (kh, kw, cin, cout): B operand of the data gradient (leg_backward.hip)
 };
 
 struct ovn_ctx {
@@ -430,6 +431,16 @@ int ovn_delta_data_grad(ovn_ctx* ctx, int FW, const float* feats_l, const int32_
 int ovn_yaw_grad_run(ovn_ctx* ctx, int FW, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx,
                      int64_t n, const float* target, const int32_t* yaw_bin, float yaw_scale, float thr, float* dfeat_l, float* dfeat_r,
                      float* loss_yaw, float* corr, hipStream_t stream);
+
+// leg_backward.hip: one leg layer's gradients (ovn_leg_backward, ovn_debug_conv_grad).  dym (nb, oh, ow, cout): dL/d(output) already
+// multiplied by [output > 0].  acc_kernel / acc_bias: fp64 running sums in the Keras layouts, onto which the layer's partials are
+// added in (scan block, piece) order; part: ovn_leg_grad_part_bytes(L, h, w, nb) bytes of scratch; dx (nb, h, w, cin) is stored times
+// [mask > 0] when mask is given; dx, acc_kernel and acc_bias may each be NULL
+size_t ovn_leg_grad_part_bytes(const OvnConvLayer& L, int h, int w, int nb);
+int ovn_leg_mask_forward(const float* dy, const float* y, float* out, long long n, hipStream_t stream);
+int ovn_leg_grad_round(const double* acc, float* out, long long n, hipStream_t stream);
+int ovn_leg_layer_backward(const OvnConvLayer& L, const float* x, const float* dym, int nb, int h, int w, float* dx, const float* mask,
+                           double* acc_kernel, double* acc_bias, double* part, hipStream_t stream);
 
 // delta_head_w_f16x3.hip: DeltaLayer + c_conv1 + c_conv2 of ovn_delta_forward in f16x3 arithmetic at widths other than 360 (ovn_set_head_width_split with head
 // mode 1): o2 (n, G, G, 128) from n * ovn_delta_w_split_pair_bytes() bytes of per-pair scales (16-byte aligned scratch)

@@ -64,6 +64,7 @@ class OvnEngine:
         self.head_compaction = True
         self.negate_diffs = False            # deltaLayer_negateDiffs of the registered weights (load_weights)
         self.conv1size = 15
+        self._leg_cfg: dict = {}             # the model keys the registered leg was built from (load_weights)
         self.check_device_indices = False    # opt-in range check of pair-index tensors that already live on the device (_idx)
 
     # -- lifetime -----------------------------------------------------------------------------------
@@ -114,6 +115,7 @@ class OvnEngine:
             _lib.check(self.lib.ovn_finalize(self._h, C.byref(fw)), "ovn_finalize")
             self.feat_w = fw.value
             self._leg_ready = True
+            self._leg_cfg = {k: cfg[k] for k in ("strides_layer1", "additional_unsymmetric_layer3a") if k in cfg}
             if self.conv1size != 15:   # any other value: the library's general fp32 Delta path (no Delta cache)
                 _lib.check(self.lib.ovn_set_head_geometry(self._h, self.conv1size), "ovn_set_head_geometry")
             names = ["c_conv1", "c_conv2", "c_conv3", "overlap_output"]
@@ -461,8 +463,172 @@ class OvnEngine:
             out["grads"], out["flat"] = grads, flat
         return out
 
+    # -- training the legs ---------------------------------------------------------------------------------
+    LEG_GRAD_SCAN_BLOCK = 4        # OVN_LEG_GRAD_SCAN_BLOCK of include/ovn_hip.h
+
+    def _require_leg(self) -> None:
+        if not self._leg_ready:
+            raise _lib.OvnError("leg weights not loaded")
+
+    def _leg_specs(self) -> List[Tuple[str, Tuple[int, ...]]]:
+        """(layer name, Keras kernel shape) of the registered leg layers, in network order."""
+        return [(l.name, (l.kh, l.kw, l.cin, l.cout)) for l in W.leg_layers(self.in_c, self._leg_cfg)]
+
+    def leg_param_names(self) -> List[str]:
+        """Keras names of the 2 x layers leg tensors in the library's order: s_conv1/kernel, s_conv1/bias, s_conv2/kernel, ..."""
+        return [n + "/" + kind for n, _ in self._leg_specs() for kind in ("kernel", "bias")]
+
+    def leg_param_shapes(self) -> List[Tuple[int, ...]]:
+        """Keras shapes of the leg tensors (leg_param_names order), checked against `ovn_leg_param_sizes`."""
+        self._require_leg()
+        shapes = [s for _, k in self._leg_specs() for s in (k, (k[3],))]
+        nl = C.c_int(0)
+        _lib.check(self.lib.ovn_leg_layer_count(self._h, C.byref(nl)), "ovn_leg_layer_count")
+        sizes = (C.c_int64 * (2 * nl.value))()
+        _lib.check(self.lib.ovn_leg_param_sizes(self._h, sizes), "ovn_leg_param_sizes")
+        if [int(v) for v in sizes] != [int(np.prod(s)) for s in shapes]:
+            raise _lib.OvnError("the library holds leg tensors of %s elements, the layer table says %s"
+                                % ([int(v) for v in sizes], shapes))
+        return shapes
+
+    def leg_activation_shapes(self) -> List[Tuple[int, int, int]]:
+        """(oh, ow, cout) of every leg layer's output for this engine's input geometry, checked against `ovn_leg_activation_sizes`."""
+        self._require_leg()
+        h, w, shapes = self.in_h, self.in_w, []
+        for l in W.leg_layers(self.in_c, self._leg_cfg):
+            h, w = (h - l.kh) // l.sh + 1, (w - l.kw) // l.sw + 1
+            shapes.append((h, w, l.cout))
+        sizes = (C.c_int64 * len(shapes))()
+        _lib.check(self.lib.ovn_leg_activation_sizes(self._h, sizes), "ovn_leg_activation_sizes")
+        if [int(v) for v in sizes] != [a * b * c for a, b, c in shapes]:
+            raise _lib.OvnError("the library's leg activations %s do not match the layer table %s" % ([int(v) for v in sizes], shapes))
+        return shapes
+
+    def _check_images(self, images: torch.Tensor) -> int:
+        if images.device != self.device or images.dtype != torch.float32 or not images.is_contiguous():
+            raise _lib.OvnError("leg input must be a contiguous float32 tensor on %s" % self.device)
+        if images.dim() != 4 or tuple(images.shape[1:]) != (self.in_h, self.in_w, self.in_c) or images.shape[0] < 1:
+            raise _lib.OvnError("leg input shape %s, expected (n >= 1,%d,%d,%d)" % (tuple(images.shape), self.in_h, self.in_w, self.in_c))
+        return int(images.shape[0])
+
+    def leg_forward_train(self, images: torch.Tensor) -> List[torch.Tensor]:
+        """images (n, H, W, C) -> the list of every leg layer's post-ReLU output (n, oh, ow, cout), in exact fp32 whatever
+        `set_leg_precision` says (`ovn_leg_forward_train`).  The tensors are views of ONE layer-major buffer, which `leg_backward`
+        takes back; the last one, viewed (n, feat_w, 128), is the feature volumes."""
+        self._require_leg()
+        n = self._check_images(images)
+        shapes = self.leg_activation_shapes()
+        flat = torch.empty(n * sum(a * b * c for a, b, c in shapes), dtype=torch.float32, device=self.device)
+        with self._dev():
+            _lib.check(self.lib.ovn_leg_forward_train(self._h, _ptr(images), n, _ptr(flat), self._stream()), "ovn_leg_forward_train")
+        acts, off = [], 0
+        for a, b, c in shapes:
+            acts.append(flat[off:off + n * a * b * c].view(n, a, b, c))
+            off += n * a * b * c
+        return acts
+
+    def leg_backward(self, images: torch.Tensor, acts: Sequence[torch.Tensor], dfeat: torch.Tensor, slice_scans: int = 0):
+        """Gradients of the 2 x layers leg tensors, summed over the n scans, from dfeat (n, feat_w, 128) = dL/d(feature volume of
+        scan i) (`ovn_leg_backward`).  acts: what `leg_forward_train` returned for `images`.  Returns dict: Keras name
+        ('s_conv1/kernel', ...) -> device tensor in its Keras shape (views of the one buffer 'flat')."""
+        self._require_leg()
+        n = self._check_images(images)
+        shapes = self.leg_activation_shapes()
+        if len(acts) != len(shapes):
+            raise _lib.OvnError("leg_backward takes the %d activations of leg_forward_train" % len(shapes))
+        base = acts[0].data_ptr()
+        off = 0
+        for t, (a, b, c) in zip(acts, shapes):
+            if (t.device != self.device or t.dtype != torch.float32 or tuple(t.shape) != (n, a, b, c) or not t.is_contiguous()
+                    or t.data_ptr() != base + 4 * off):
+                raise _lib.OvnError("leg_backward: acts must be the list leg_forward_train returned for these %d scans" % n)
+            off += n * a * b * c
+        if (dfeat.device != self.device or dfeat.dtype != torch.float32 or not dfeat.is_contiguous()
+                or dfeat.numel() != n * self.feat_w * FEAT_C):
+            raise _lib.OvnError("dfeat must be a contiguous float32 tensor of %d feature volumes on %s" % (n, self.device))
+        if int(slice_scans) < 0:
+            raise ValueError("slice_scans must be >= 0")
+        pshapes = self.leg_param_shapes()
+        flat = torch.empty(sum(int(np.prod(s)) for s in pshapes), dtype=torch.float32, device=self.device)
+        with self._dev():
+            _lib.check(self.lib.ovn_leg_backward(self._h, _ptr(images), C.c_void_p(base), n, _ptr(dfeat), _ptr(flat), int(slice_scans),
+                                                 self._stream()), "ovn_leg_backward")
+        out: Dict[str, torch.Tensor] = {}
+        off = 0
+        for name, shape in zip(self.leg_param_names(), pshapes):
+            size = int(np.prod(shape))
+            out[name] = flat[off:off + size].view(shape)
+            off += size
+        out["flat"] = flat
+        return out
+
+    def set_leg_weights(self, params) -> None:
+        """Replace leg weights in place (`ovn_set_leg_layer_weights`).  params: dict Keras name -> float32 device tensor (both tensors
+        of every layer it names), or the full list in `leg_param_names` order.  Feature volumes, spectra and Delta cache rows
+        computed by the old legs are stale afterwards."""
+        self._require_leg()
+        names, shapes = self.leg_param_names(), self.leg_param_shapes()
+        if not isinstance(params, dict):
+            if len(params) != len(names):
+                raise _lib.OvnError("set_leg_weights takes the %d leg tensors" % len(names))
+            params = dict(zip(names, params))
+        with self._dev():
+            for li, (layer, _) in enumerate(self._leg_specs()):
+                k, b = params.get(layer + "/kernel"), params.get(layer + "/bias")
+                if k is None and b is None:
+                    continue
+                if k is None or b is None:
+                    raise _lib.OvnError("set_leg_weights: layer %s needs its kernel and its bias" % layer)
+                for t, shape in ((k, shapes[2 * li]), (b, shapes[2 * li + 1])):
+                    if t.device != self.device or t.dtype != torch.float32 or t.numel() != int(np.prod(shape)):
+                        raise _lib.OvnError("set_leg_weights: %s tensors must be float32 on %s with shapes %s, %s"
+                                            % (layer, self.device, shapes[2 * li], shapes[2 * li + 1]))
+                k, b = k.contiguous(), b.contiguous()
+                _lib.check(self.lib.ovn_set_leg_layer_weights(self._h, li, _ptr(k), _ptr(b), self._stream()),
+                           "ovn_set_leg_layer_weights(%s)" % layer)
+
+    def debug_conv(self, layer: int, x: torch.Tensor) -> torch.Tensor:
+        """Leg layer `layer` alone on x (nb, h, w, cin) in the current leg precision (`ovn_debug_conv`)."""
+        self._require_leg()
+        l = W.leg_layers(self.in_c, self._leg_cfg)[layer]
+        nb, h, w, _ = x.shape
+        out = torch.empty((nb, (h - l.kh) // l.sh + 1, (w - l.kw) // l.sw + 1, l.cout), dtype=torch.float32, device=self.device)
+        with self._dev():
+            _lib.check(self.lib.ovn_debug_conv(self._h, int(layer), _ptr(x.contiguous()), nb, h, w, _ptr(out), self._stream()), "ovn_debug_conv")
+        return out
+
+    def debug_conv_grad(self, layer: int, x: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, want=("din", "dkernel", "dbias")):
+        """The gradients of leg layer `layer` alone (`ovn_debug_conv_grad`): x (nb, h, w, cin) its input, out (nb, oh, ow, cout) its
+        post-ReLU output (the mask), dout = dL/d(out).  Returns dict of the requested 'din' (nb, h, w, cin), 'dkernel' (Keras
+        shape), 'dbias' (cout).  din of a layer whose cin is not a multiple of 16 comes from a plain fp64 kernel."""
+        self._require_leg()
+        specs = W.leg_layers(self.in_c, self._leg_cfg)
+        if not 0 <= int(layer) < len(specs):
+            raise IndexError("no leg layer %r" % (layer,))
+        l = specs[int(layer)]
+        for t in (x, out, dout):
+            if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous():
+                raise _lib.OvnError("debug_conv_grad takes contiguous float32 tensors on %s" % self.device)
+        if x.dim() != 4 or x.shape[3] != l.cin or x.shape[0] < 1 or x.shape[1] < l.kh or x.shape[2] < l.kw:
+            raise _lib.OvnError("debug_conv_grad: input shape %s for layer %s" % (tuple(x.shape), l.name))
+        nb, h, w, _ = (int(v) for v in x.shape)
+        oshape = (nb, (h - l.kh) // l.sh + 1, (w - l.kw) // l.sw + 1, l.cout)
+        if tuple(out.shape) != oshape or tuple(dout.shape) != oshape:
+            raise _lib.OvnError("debug_conv_grad: out / dout must be %s" % (oshape,))
+        r = {}
+        if "din" in want:
+            r["din"] = torch.empty_like(x)
+        if "dkernel" in want:
+            r["dkernel"] = torch.empty((l.kh, l.kw, l.cin, l.cout), dtype=torch.float32, device=self.device)
+        if "dbias" in want:
+            r["dbias"] = torch.empty(l.cout, dtype=torch.float32, device=self.device)
+        with self._dev():
+            _lib.check(self.lib.ovn_debug_conv_grad(self._h, int(layer), _ptr(x), _ptr(out), _ptr(dout), nb, h, w, _ptr(r.get("din")),
+                                                    _ptr(r.get("dkernel")), _ptr(r.get("dbias")), self._stream()), "ovn_debug_conv_grad")
+        return r
+
     SPEC_W = 368
-    DELTA_CACHE_ELEMS = 49216      # floats per Delta cache row (include/ovn_hip.h: OVN_DELTA_CACHE_ELEMS)
+    DELTA_CACHE_ELEMS = 49216     # floats per Delta cache row (include/ovn_hip.h: OVN_DELTA_CACHE_ELEMS)
 
     @property
     def has_delta_cache(self) -> bool:

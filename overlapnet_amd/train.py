@@ -8,7 +8,13 @@ Training the legs: the yaw head has no weights, so the reference's orientation l
 through the leg outputs, and `OverlapHeadTrainer` (frozen legs) has no use for it.  `heads_loss` is where it exists: both heads'
 losses as ONE differentiable scalar of the feature-volume pools (`OvnEngine.heads_feature_grad`, csrc/heads_feature_grad.hip: the
 overlap loss and the yaw loss differentiated down to the leg outputs on the GPU).  A leg written in torch plugs into it and gets
-d L / d (its output) from `backward()`; the leg's own backward pass and a leg trainer are not part of this package.
+d L / d (its output) from `backward()`.
+
+Training the whole network: `OverlapNetTrainer` is the reference's default training step (training.py: both losses, all tensors of
+the Siamese network, Adagrad).  The leg's forward with stored activations and its backward run in the library
+(`OvnEngine.leg_forward_train` / `leg_backward`, csrc/leg_backward.hip); the chain is leg forward -> `heads_feature_grad` ->
+`sum_rows_by_entry` for both sides (the leg is shared: a scan that is left in one pair and right in another gets both sums) ->
+leg backward -> Adagrad on the 8 head and 2 x layers leg tensors.
 """
 from __future__ import annotations
 
@@ -214,6 +220,153 @@ class OverlapHeadTrainer(object):
         """The full weight dict by Keras layer name: the legs untouched, the head as fitted (negateDiffs undone: the file's kernel)."""
         out = dict(self.infer._weights)
         for name, p, shape in zip(self.engine.HEAD_PARAMS, self.params, self.engine.head_param_shapes()):
+            a = p.detach().cpu().numpy().reshape(shape).copy()
+            out[name] = -a if (name == "c_conv1/kernel" and self.engine.negate_diffs) else a
+        return out
+
+    def save(self, path: str) -> None:
+        """Write `weights()` as npz; the file loads through config['pretrained_weightsfilename']."""
+        W.save_npz(path, self.weights())
+
+
+class OverlapNetTrainer(object):
+    """The reference's full training step (training.py) on `infer`'s engine: Adagrad on the eight head tensors and the 2 x layers
+    leg tensors under  overlap_scale / n sum_p loss(overlap_p, t_p)  +  yaw_scale / (n W) sum of the weighted cross entropy of the
+    correlation logits against the yaw bins (`OvnEngine.heads_feature_grad`).  A batch is given by scan NAMES (the cue files
+    `Infer._inputs_device` reads): pair p = (left_names[p] -> head-left, right_names[p] -> head-right).
+
+    train_legs=False keeps the legs frozen (the reference's `360OutputkLegsFixed`): the yaw loss then has nothing to act on and only
+    the head tensors move.  Every step re-registers the weights it changed.  When `step` / `fit` return, the look-ahead context
+    (which holds weights of its own) is closed, `infer._weights` is current, and `infer.feature_volumes` is empty: every cached
+    volume, spectrum and Delta row was computed by the old legs (train_legs=False: the volumes stay, their Delta rows are rebuilt)."""
+
+    def __init__(self, infer, learning_rate: float, lr_alpha: float = 0.99, loss: str = "sigmoid", overlap_scale: float = 5.0,
+                 yaw_scale: float = 1.0, min_overlap_for_angle: float = 0.7, train_legs: bool = True):
+        if getattr(infer, "_world", 1) > 1:
+            raise OvnError("OverlapNetTrainer: not available on a sharded Infer (world %d)" % infer._world)
+        self.infer = infer
+        self.engine = infer.engine
+        self.learning_rate, self.lr_alpha = float(learning_rate), float(lr_alpha)
+        self.loss, self.overlap_scale, self.yaw_scale = loss, float(overlap_scale), float(yaw_scale)
+        self.min_overlap_for_angle, self.train_legs = float(min_overlap_for_angle), bool(train_legs)
+        if loss not in self.engine._LOSSES:
+            raise ValueError("loss must be one of %s, got %r" % (sorted(self.engine._LOSSES), loss))
+        self.epoch = 0
+        self.last: Optional[dict] = None      # result of the most recent heads_feature_grad call (values BEFORE the update)
+        dev = self.engine.device
+        self.head_names = list(self.engine.HEAD_PARAMS)
+        self.leg_names = self.engine.leg_param_names()
+        self.names = self.head_names + self.leg_names         # the 8 + 2 x layers tensors, in the order of `params`
+        self.params: List[torch.Tensor] = []
+        for name in self.names:
+            k = np.ascontiguousarray(infer._weights[name], np.float32)
+            if name == "c_conv1/kernel" and self.engine.negate_diffs:
+                k = -k                          # as registered (engine.load_weights)
+            self.params.append(torch.from_numpy(k).to(dev))
+        self.accum = [torch.zeros_like(p) for p in self.params]
+
+    # -- the chain ----------------------------------------------------------------------------------
+    @staticmethod
+    def _pool(left_names, right_names):
+        """The unique scans of a batch (sorted) and each pair's two positions among them."""
+        ln, rn = [str(v) for v in left_names], [str(v) for v in right_names]
+        if len(ln) != len(rn) or not ln:
+            raise ValueError("%d left and %d right names (at least one pair)" % (len(ln), len(rn)))
+        names = sorted(set(ln) | set(rn))
+        pos = {v: i for i, v in enumerate(names)}
+        return names, np.array([pos[v] for v in ln], np.int64), np.array([pos[v] for v in rn], np.int64)
+
+    def _chain(self, left_names, right_names, overlaps, yaw_bins):
+        names, lidx, ridx = self._pool(left_names, right_names)
+        x = self.infer._inputs_device(names)
+        acts = self.engine.leg_forward_train(x)
+        feats = acts[-1].view(len(names), self.engine.feat_w, 128)
+        r = self.engine.heads_feature_grad(feats, feats, overlaps, yaw_bins, lidx=lidx, ridx=ridx, loss=self.loss,
+                                           overlap_scale=self.overlap_scale, yaw_scale=self.yaw_scale,
+                                           min_overlap_for_angle=self.min_overlap_for_angle, want_head_grads=True, want_corr=False)
+        grads = [r["grads"][n.split("/")[0]][n.split("/")[1]] for n in self.head_names]
+        if self.train_legs:
+            dfeat = sum_rows_by_entry(r["dfeat_l"], lidx, len(names)) + sum_rows_by_entry(r["dfeat_r"], ridx, len(names))
+            leg = self.engine.leg_backward(x, acts, dfeat)
+            grads += [leg[n] for n in self.leg_names]
+        return r, grads
+
+    def gradients(self, left_names, right_names, overlaps, yaw_bins) -> Dict[str, torch.Tensor]:
+        """The gradients of one batch with respect to the tensors of the weight FILE, by Keras name (the c_conv1 kernel's sign under
+        deltaLayer_negateDiffs is undone, as in OverlapHeadTrainer.gradients; train_legs=False: the head tensors only), plus
+        'loss_overlap', 'loss_yaw' and 'overlap'.  No update."""
+        r, grads = self._chain(left_names, right_names, overlaps, yaw_bins)
+        out = {n: (-g if (n == "c_conv1/kernel" and self.engine.negate_diffs) else g) for n, g in zip(self.names, grads)}
+        out["loss_overlap"], out["loss_yaw"], out["overlap"] = r["loss_overlap"], r["loss_yaw"], r["overlap"]
+        return out
+
+    def _update(self, left_names, right_names, overlaps, yaw_bins) -> torch.Tensor:
+        r, grads = self._chain(left_names, right_names, overlaps, yaw_bins)
+        k = len(grads)
+        adagrad_step(self.params[:k], self.accum[:k], [g.reshape(p.shape) for g, p in zip(grads, self.params)],
+                     float(lr_schedule(self.epoch, self.learning_rate, self.lr_alpha)))
+        self.engine.set_head_weights(self.params[:8])
+        if self.train_legs:
+            self.engine.set_leg_weights(dict(zip(self.leg_names, self.params[8:])))
+        self.last = r
+        return (r["loss_overlap"] + r["loss_yaw"]).reshape(1)
+
+    def _weights_changed(self) -> None:
+        inf = self.infer
+        inf._drop_ahead()
+        if inf._qa is not None:                 # the look-ahead context registered the old weights
+            inf._qa.close()
+            inf._qa = None
+        inf._weights = self.weights()
+        if self.train_legs:
+            inf.feature_volumes = []
+        else:
+            inf.feature_volumes.rebuild_delta_cache()
+
+    def step(self, left_names, right_names, overlaps, yaw_bins) -> float:
+        """One Adagrad step on the batch at the current epoch's learning rate.  Returns the loss (both parts) before the update."""
+        try:
+            loss = self._update(left_names, right_names, overlaps, yaw_bins)
+        finally:
+            self._weights_changed()
+        return float(loss)
+
+    def fit(self, left_names, right_names, overlaps, yaw_bins, epochs: int, batch_size: Optional[int] = None, seed: int = 0) -> List[float]:
+        """`epochs` passes over the pairs in shuffled mini-batches (`epoch_batches`; batch_size defaults to infer.batch_size).
+        Returns the loss of every step."""
+        ln, rn = [str(v) for v in left_names], [str(v) for v in right_names]
+        ov = np.asarray(overlaps, np.float32).reshape(-1)
+        yb = np.asarray(yaw_bins, np.int32).reshape(-1)
+        if not (len(ln) == len(rn) == len(ov) == len(yb)) or len(ln) == 0:
+            raise ValueError("fit: %d left, %d right names, %d overlaps and %d yaw bins" % (len(ln), len(rn), len(ov), len(yb)))
+        bs = int(self.infer.batch_size if batch_size is None else batch_size)
+        losses = []
+        try:
+            for _ in range(int(epochs)):
+                for b in epoch_batches(len(ln), bs, self.epoch, seed):
+                    losses.append(self._update([ln[i] for i in b], [rn[i] for i in b], ov[b], yb[b]))
+                self.epoch += 1
+        finally:
+            self._weights_changed()
+        return [float(v) for v in torch.cat(losses).cpu()] if losses else []
+
+    def fit_from_npz(self, npz_files: Sequence[str], epochs: int, batch_size: Optional[int] = None, seed: int = 0,
+                     no_pairs: Optional[int] = None) -> List[float]:
+        """`fit` on the pairs of the reference's ground-truth npz files (evaluate.load_pairs) with the roles of evaluate.run_test:
+        imgf1 -> head-left, imgf2 -> head-right, column 3 the yaw bin."""
+        from .evaluate import load_pairs
+        f1, f2, _d1, _d2, ov, yaw = load_pairs(npz_files, shuffle=False)
+        n = len(f1) if no_pairs is None else min(int(no_pairs), len(f1))
+        if n == 0:
+            raise Exception("no training pairs")
+        return self.fit(f1[:n], f2[:n], ov[:n], np.asarray(yaw[:n]).astype(np.int32), epochs, batch_size, seed)
+
+    # -- results ------------------------------------------------------------------------------------
+    def weights(self) -> Dict[str, np.ndarray]:
+        """The full weight dict by Keras layer name as trained (negateDiffs undone: the file's c_conv1 kernel)."""
+        out = dict(self.infer._weights)
+        shapes = list(self.engine.head_param_shapes()) + list(self.engine.leg_param_shapes())
+        for name, p, shape in zip(self.names, self.params, shapes):
             a = p.detach().cpu().numpy().reshape(shape).copy()
             out[name] = -a if (name == "c_conv1/kernel" and self.engine.negate_diffs) else a
         return out
