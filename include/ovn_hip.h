@@ -424,6 +424,19 @@ int ovn_gt_range_images(ovn_ctx* ctx, const float* points_dev, const int64_t* of
 int ovn_gt_overlap_counts(ovn_ctx* ctx, const float* ref_ranges_dev, const float* cur_range_dev, int n_scans, int proj_h,
                           int proj_w, int32_t* counts_dev, void* stream);
 
+/* All pairs of a sequence in one call: counts_dev[f * n_refs + r] = the integer ovn_gt_overlap_counts gives for frame
+ * frame_idx[f] against scan ref_idx[r], without the pair's range image (two bit planes in LDS, one workgroup per pair;
+ * csrc/overlap_gt.hip).  points/offsets as in ovn_gt_range_images for all n_scans scans; poses_dev (n_scans,4,4) f64;
+ * inv_poses_dev (n_scans,4,4) f64, the caller's inverses (the host's np.linalg.inv, so that the bits are those ovn_gt_range_images
+ * is given); cur_ranges_dev (n_scans,H,W) f32 indexed by SCAN: the own range images (ovn_gt_range_images with both poses NULL),
+ * read only for the scans frame_idx names.  frame_idx_dev / ref_idx_dev: int32 device lists, NULL = 0..n-1; entries may repeat and
+ * need not be sorted; an entry outside [0, n_scans) reads nothing and reports -1 for its pairs.  OVN_ERR_ARG when H*W > 262144
+ * (the planes exceed 64 KB of LDS) or n_frames * n_refs > 2^31 - 1.  overlap = counts / #{cur_range > 0} is the caller's division. */
+int ovn_gt_pair_counts(ovn_ctx* ctx, const float* points_dev, const int64_t* offsets_dev, int n_scans, const double* poses_dev,
+                       const double* inv_poses_dev, const float* cur_ranges_dev, const int32_t* frame_idx_dev, int n_frames,
+                       const int32_t* ref_idx_dev, int n_refs, int proj_h, int proj_w, double fov_up_deg, double fov_down_deg,
+                       double max_range, int32_t* counts_dev, void* stream);
+
 /* Arithmetic of the Delta head's contractions (c_conv1, c_conv2, c_conv3) and of ovn_spectrum's DFT; storage and accumulation
  * are fp32 in every mode:
  *   0 = fp32 matrix cores (v_mfma_f32_16x16x4_f32; bit-for-bit an fp32 FMA chain),

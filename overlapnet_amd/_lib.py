@@ -66,6 +66,8 @@ SIGNATURES = {
     "ovn_gt_range_images": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double,
                                       C.c_double, _vp, _vp]),
     "ovn_gt_overlap_counts": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "ovn_gt_pair_counts": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_double,
+                                     C.c_double, C.c_double, _vp, _vp]),
     "ovn_set_head_precision": (C.c_int, [_vp, C.c_int]),
     "ovn_set_head_width_split": (C.c_int, [_vp, C.c_int]),
     "ovn_get_head_width_split": (C.c_int, [_vp, C.POINTER(C.c_int)]),

@@ -1236,6 +1236,33 @@ int ovn_gt_overlap_counts(ovn_ctx* ctx, const float* ref_ranges_dev, const float
   return ovn_gt_count_forward(ref_ranges_dev, cur_range_dev, n_scans, proj_h * proj_w, counts_dev, (hipStream_t)stream);
 }
 
+int ovn_gt_pair_counts(ovn_ctx* ctx, const float* points_dev, const int64_t* offsets_dev, int n_scans, const double* poses_dev,
+                       const double* inv_poses_dev, const float* cur_ranges_dev, const int32_t* frame_idx_dev, int n_frames,
+                       const int32_t* ref_idx_dev, int n_refs, int proj_h, int proj_w, double fov_up_deg, double fov_down_deg,
+                       double max_range, int32_t* counts_dev, void* stream) {
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_gt_pair_counts: ctx is NULL");
+  OVN_REQUIRE(n_scans >= 0 && n_frames >= 0 && n_refs >= 0 && proj_h > 0 && proj_w > 0, OVN_ERR_ARG,
+              "ovn_gt_pair_counts: bad sizes");
+  OVN_REQUIRE((long long)proj_h * proj_w <= 262144, OVN_ERR_ARG,
+              "ovn_gt_pair_counts: %d x %d pixels need %lld bytes of LDS for the two bit planes, 65536 at the most (H*W <= 262144)",
+              proj_h, proj_w, 8ll * (((long long)proj_h * proj_w + 31) / 32));
+  OVN_REQUIRE((long long)n_frames * n_refs <= 2147483647ll, OVN_ERR_ARG,
+              "ovn_gt_pair_counts: %d frames x %d references exceed the grid (2^31 - 1 pairs per call)", n_frames, n_refs);
+  if (n_frames == 0 || n_refs == 0) return OVN_OK;
+  OVN_REQUIRE(counts_dev != nullptr, OVN_ERR_ARG, "ovn_gt_pair_counts: counts is NULL");
+  OVN_REQUIRE(n_scans > 0 && offsets_dev && poses_dev && inv_poses_dev && cur_ranges_dev, OVN_ERR_ARG,
+              "ovn_gt_pair_counts: NULL buffer");
+  OVN_REQUIRE((frame_idx_dev || n_frames <= n_scans) && (ref_idx_dev || n_refs <= n_scans), OVN_ERR_ARG,
+              "ovn_gt_pair_counts: without an index list at most n_scans (%d) frames / references", n_scans);
+  // workgroup order: neighbouring pairs share the reference scan (frame fastest, the default: DESIGN.md 22) or the frame's image
+  int frame_fastest = 1;
+  if (const char* e = getenv("OVN_GT_PAIR_ORDER")) frame_fastest = e[0] == 'r' ? 0 : 1;
+  OVN_ON_DEVICE(ctx->device);
+  return ovn_gt_pair_forward(points_dev, offsets_dev, n_scans, poses_dev, inv_poses_dev, cur_ranges_dev, frame_idx_dev, n_frames,
+                             ref_idx_dev, n_refs, proj_h, proj_w, fov_up_deg, fov_down_deg, max_range, frame_fastest, counts_dev,
+                             (hipStream_t)stream);
+}
+
 int ovn_set_head_precision(ovn_ctx* ctx, int mode) {
   OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_set_head_precision: ctx is NULL");
   OVN_REQUIRE(mode >= 0 && mode <= 2, OVN_ERR_ARG, "ovn_set_head_precision: mode %d (0 = fp32 MFMA, 1 = f16x3 MFMA, 2 = bf16x3 MFMA)", mode);

@@ -481,6 +481,11 @@ int ovn_gt_range_forward(const float* points, const int64_t* offsets, int n_scan
                          const double* inv_cur_pose, int H, int W, double fov_up_deg, double fov_down_deg, double max_range,
                          float* range_out, hipStream_t stream);
 int ovn_gt_count_forward(const float* ref_ranges, const float* cur_range, int n, int npix, int32_t* counts, hipStream_t stream);
+// counts[f * n_refs + r] of frame frame_idx[f] against scan ref_idx[r] from two LDS bit planes, one workgroup per pair
+int ovn_gt_pair_forward(const float* points, const int64_t* offsets, int n_scans, const double* poses, const double* inv_poses,
+                        const float* cur_ranges, const int32_t* frame_idx, int n_frames, const int32_t* ref_idx, int n_refs, int H,
+                        int W, double fov_up_deg, double fov_down_deg, double max_range, int frame_fastest, int32_t* counts,
+                        hipStream_t stream);
 int ovn_best_match_forward(const float* overlap, const int32_t* yaw, const int32_t* ids, int n, float threshold,
                            int index_offset, int32_t* out, hipStream_t stream);
 // top_k.hip

@@ -717,6 +717,35 @@ class OvnEngine:
                                                       self._stream()), "ovn_gt_overlap_counts")
         return counts
 
+    def gt_pair_counts(self, points: torch.Tensor, offsets: torch.Tensor, poses: torch.Tensor, inv_poses: torch.Tensor,
+                       cur_ranges: torch.Tensor, frame_idx: Optional[torch.Tensor] = None,
+                       ref_idx: Optional[torch.Tensor] = None, fov_up: float = 3.0, fov_down: float = -25.0,
+                       max_range: float = 50.0) -> torch.Tensor:
+        """(F, R) int32 device tensor: for frame frame_idx[f] and scan ref_idx[r] the integer `gt_overlap_counts` gives for that
+        pair, from one kernel without the pair's range image.  points (total,4) f32 and offsets (n+1) i64 of all n scans, poses
+        and inv_poses (n,4,4) f64, cur_ranges (n,H,W) f32 = `gt_range_images` without poses (rows of scans that are no frame are
+        never read), frame_idx / ref_idx int32 device lists or None = all scans in order."""
+        n = int(offsets.numel()) - 1
+        for t, what, dt in ((points, "points", torch.float32), (offsets, "offsets", torch.int64), (poses, "poses", torch.float64),
+                            (inv_poses, "inv_poses", torch.float64), (cur_ranges, "cur_ranges", torch.float32),
+                            (frame_idx, "frame_idx", torch.int32), (ref_idx, "ref_idx", torch.int32)):
+            if t is not None and (t.device != self.device or t.dtype != dt or not t.is_contiguous()):
+                raise _lib.OvnError("%s must be a contiguous %s tensor on %s" % (what, dt, self.device))
+        if poses.numel() != 16 * n or inv_poses.numel() != 16 * n:
+            raise _lib.OvnError("poses and inv_poses must hold %d 4x4 matrices each" % n)
+        if cur_ranges.dim() != 3 or cur_ranges.shape[0] != n:
+            raise _lib.OvnError("cur_ranges must be (%d, H, W), one own range image per scan" % n)
+        h, w = int(cur_ranges.shape[1]), int(cur_ranges.shape[2])
+        nf = n if frame_idx is None else int(frame_idx.numel())
+        nr = n if ref_idx is None else int(ref_idx.numel())
+        counts = torch.empty((nf, nr), dtype=torch.int32, device=self.device)
+        with self._dev():
+            _lib.check(self.lib.ovn_gt_pair_counts(self._h, _ptr(points), _ptr(offsets), n, _ptr(poses), _ptr(inv_poses),
+                                                   _ptr(cur_ranges), _ptr(frame_idx), nf, _ptr(ref_idx), nr, h, w, float(fov_up),
+                                                   float(fov_down), float(max_range), _ptr(counts), self._stream()),
+                       "ovn_gt_pair_counts")
+        return counts
+
     # -- loop-closure decision -----------------------------------------------------------------------
     def best_match(self, overlap: torch.Tensor, yaw: Optional[torch.Tensor] = None, threshold: float = 0.3,
                    ids: Optional[torch.Tensor] = None, index_offset: int = 0, host: bool = False) -> torch.Tensor:
