@@ -250,6 +250,23 @@ int ovn_set_leg_layer_weights(ovn_ctx* ctx, int layer, const float* kernel_dev, 
 int ovn_debug_conv_grad(ovn_ctx* ctx, int layer, const float* in_dev, const float* out_dev, const float* dout_dev, int nb, int h, int w,
                         float* din_dev, float* dkernel_dev, float* dbias_dev, void* stream);
 
+/* Data-parallel training: the gradients of `world` ranks reduced and Keras 2.1.5's Adagrad applied, one kernel (grad_reduce.hip).
+ *   grads_dev         (world, stride) float32: row r holds the flat gradient of rank r in its first `count` elements
+ *   rank_weight_host  world doubles on the HOST: n_r / n, the share of the global batch rank r held
+ *   params_dev, accum_dev   (count) each, updated in place; both NULL: the call only reduces
+ *   grad_out_dev      (count) or NULL: the reduced gradient
+ * For every i < count, each operation one correctly rounded IEEE operation (nothing fused, fp32 denormals kept):
+ *   s = 0.0 (fp64); for r = 0 .. world - 1 in this order, rows with weight 0.0 skipped and NOT READ:  s = s + w[r] * (double)G[r][i]
+ *   g = (float)s;  grad_out[i] = g;  a = accum[i] + g * g;  accum[i] = a;  params[i] = params[i] - (lr * g) / (sqrtf(a) + eps)
+ * No atomics, a fixed order: the same bits on every call and every rank.  Buffers that are all 16-byte aligned are walked with
+ * 16-byte accesses; any other alignment is served element by element.  Reports as class 0 under ovn_profile_begin.
+ * OVN_ERR_ARG before any launch: NULL ctx / grads / weights, world outside 1..OVN_GRAD_REDUCE_MAX_WORLD, count < 1, stride < count
+ * or not a multiple of 4, exactly one of params / accum NULL, all three outputs NULL, a non-finite lr or eps, eps < 0, a weight that
+ * is negative or not finite, all weights zero. */
+#define OVN_GRAD_REDUCE_MAX_WORLD 64
+int ovn_grad_reduce_adagrad(ovn_ctx* ctx, const float* grads_dev, int world, int64_t stride, const double* rank_weight_host,
+                            int64_t count, float* params_dev, float* accum_dev, float lr, float eps, float* grad_out_dev, void* stream);
+
 /* Normalisation of the correlation head's inputs, NormalizedCorrelation2D(normalize=...) (NormalizedCorrelation2D.py:23-73):
  *   0 none (default; what generateCorrelationHead builds, generateNet.py:343), 1 euclidean (the layer's own default:
  *   x / sqrt(max(sum x^2, 1e-12))), 2 scaling ((x - min) / (max - min + 1e-6)), 3 standardization (y = x - mean + 1e-5,

@@ -48,6 +48,8 @@ SIGNATURES = {
     "ovn_leg_forward_train": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp]),
     "ovn_leg_backward": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_int64, _vp]),
     "ovn_set_leg_layer_weights": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    "ovn_grad_reduce_adagrad": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, C.POINTER(C.c_double), C.c_int64, _vp, _vp, C.c_float, C.c_float, _vp,
+                                          _vp]),
     "ovn_debug_conv_grad": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "ovn_set_head_pipeline":(C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int, C.c_int]),
     "ovn_get_head_pipeline": (C.c_int, [_vp, _i64p, _i64p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

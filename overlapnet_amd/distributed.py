@@ -155,6 +155,68 @@ def allgather_by_owner(overlap: torch.Tensor, yaw: torch.Tensor, owner: np.ndarr
     return ov, yw, statuses
 
 
+# ---- data-parallel training: one all-gather of the ranks' gradients per step (train.DataParallelTrainer) ------------------------
+GRAD_TRAILER = 4      # floats behind the padded gradient: loss_overlap, loss_yaw, pair count (int32 bits), status (int32 bits)
+
+
+def grad_row_floats(count: int) -> int:
+    """Floats per rank in the payload of `exchange_gradients`: the gradient padded to a multiple of 4, then GRAD_TRAILER words.  A
+    multiple of 4, so every row of the gathered (world, row) tensor starts 16-byte aligned (the stride `ovn_grad_reduce_adagrad` asks for)."""
+    return (int(count) + 3) // 4 * 4 + GRAD_TRAILER
+
+
+def unpack_grad_trailer(rows: torch.Tensor):
+    """The trailer columns of gathered rows -> (losses (world, 2) float64, pair counts (world,) int64, statuses (world,) int64) on the
+    host.  The two integers travel bit-cast in the float payload (exact, as `pack_scores` moves the yaw bins)."""
+    t = rows[:, -GRAD_TRAILER:].contiguous().cpu()
+    ints = t[:, 2:4].contiguous().view(torch.int32).numpy().astype(np.int64)
+    return t[:, 0:2].numpy().astype(np.float64), ints[:, 0], ints[:, 1]
+
+
+def exchange_gradients(flat: torch.Tensor, n_local: int, losses, status: int = 0, group=None):
+    """ONE all-gather per training step.  flat: this rank's flat float32 gradient (its mean over the rank's OWN n_local pairs, as the
+    engine returns it); losses: its (loss_overlap, loss_yaw), means over the same pairs; status: 0, or non-zero when the local
+    chain failed.  Every rank enters, also one with no pair (n_local 0) or a failure: it sends weight 0 and whatever `flat` holds
+    (nobody reads that row), so no rank blocks in a collective another never reaches and all ranks learn about a failure from the
+    same payload (the rule of `allgather_by_owner`).
+    -> (rows, rank_weights, loss, statuses): rows (world, grad_row_floats(count)) float32 in rank order on flat's device (under gloo
+    the host tensors are moved back there), row r = rank r's gradient | padding | trailer; rank_weights (world,) float64 = n_r / n
+    over the ranks with status 0 (all zero when no pair is left); loss = sum_r rank_weights[r] (loss_overlap_r + loss_yaw_r) in
+    float64, zero-weight ranks skipped; statuses (world,) int64.  Without a process group (group None, torch.distributed not initialised) the
+    call is world 1 and moves nothing."""
+    alone = group is None and not dist.is_initialized()      # a single process without a process group: its row is the result
+    world = 1 if alone else dist.get_world_size(group)
+    flat = flat.reshape(-1)
+    if flat.dtype != torch.float32:
+        raise ValueError("exchange_gradients takes a float32 gradient")
+    count = flat.numel()
+    row = grad_row_floats(count)
+    n_local = int(n_local) if int(status) == 0 else 0
+    if not 0 <= n_local < 2 ** 31:
+        raise ValueError("bad pair count %d" % n_local)
+    lv = [float(v) for v in losses] if n_local else [0.0, 0.0]
+    tail = torch.tensor(lv, dtype=torch.float32)
+    tail = torch.cat([tail, torch.tensor([n_local, int(status)], dtype=torch.int32).view(torch.float32)])
+    payload = torch.zeros(row, dtype=torch.float32, device=flat.device)
+    payload[:count] = flat
+    payload[row - GRAD_TRAILER:] = tail.to(flat.device)
+    if alone:
+        rows = payload.view(1, row)
+    else:
+        payload = _comm_device(payload, group)
+        rows = torch.empty((world, row), dtype=torch.float32, device=payload.device)
+        dist.all_gather(list(rows.unbind(0)), payload, group=group)
+    lss, counts, statuses = unpack_grad_trailer(rows)
+    counts = np.where(statuses == 0, counts, 0)
+    n = int(counts.sum())
+    weights = counts.astype(np.float64) / n if n > 0 else np.zeros(world, np.float64)
+    loss = 0.0
+    for r in range(world):
+        if weights[r] != 0.0:
+            loss = loss + weights[r] * (lss[r, 0] + lss[r, 1])
+    return rows.to(flat.device), weights, float(loss), statuses
+
+
 def best_match(overlap: torch.Tensor, yaw: torch.Tensor, threshold: float = 0.3):
     """Loop-closure decision of demo3 (demo3_lcd.py:118-120): argmax overlap if it exceeds the threshold."""
     if overlap.numel() == 0:

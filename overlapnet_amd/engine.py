@@ -587,6 +587,43 @@ class OvnEngine:
                 _lib.check(self.lib.ovn_set_leg_layer_weights(self._h, li, _ptr(k), _ptr(b), self._stream()),
                            "ovn_set_leg_layer_weights(%s)" % layer)
 
+    # -- data-parallel training ------------------------------------------------------------------------------
+    GRAD_REDUCE_MAX_WORLD = 64     # OVN_GRAD_REDUCE_MAX_WORLD of include/ovn_hip.h
+
+    def grad_reduce_adagrad(self, grads: torch.Tensor, rank_weights, params: Optional[torch.Tensor] = None,
+                            accum: Optional[torch.Tensor] = None, lr: float = 0.0, eps: float = 1e-7, want_grad: bool = False,
+                            count: Optional[int] = None):
+        """The ranks' gradients reduced and Adagrad applied in one kernel (`ovn_grad_reduce_adagrad`).  grads (world, stride) float32,
+        stride a multiple of 4: row r is rank r's flat gradient; rank_weights: world host numbers n_r / n (a row with weight 0 is not
+        read).  params / accum: flat float32 tensors of count <= stride elements, updated IN PLACE with
+        g = float32(sum_r w_r G[r] in fp64, rank order); a += g g; p -= lr g / (sqrt(a) + eps); both None: reduce only (the first
+        `count` elements of the rows, default all).  Returns the reduced gradient (count) when want_grad or when only reducing, else None."""
+        if grads.device != self.device or grads.dtype != torch.float32 or grads.dim() != 2 or not grads.is_contiguous():
+            raise _lib.OvnError("grads must be a contiguous (world, stride) float32 tensor on %s" % self.device)
+        world, stride = int(grads.shape[0]), int(grads.shape[1])
+        w = np.ascontiguousarray(np.asarray(rank_weights, np.float64).reshape(-1))
+        if len(w) != world or not 1 <= world <= self.GRAD_REDUCE_MAX_WORLD:
+            raise _lib.OvnError("%d rank weights for %d gradient rows (1 .. %d ranks)" % (len(w), world, self.GRAD_REDUCE_MAX_WORLD))
+        if (params is None) != (accum is None):
+            raise _lib.OvnError("params and accum are given together or not at all")
+        if params is None:
+            count = stride if count is None else int(count)
+            if not 1 <= count <= stride:
+                raise _lib.OvnError("count %d for gradient rows of %d" % (count, stride))
+        else:
+            for t in (params, accum):
+                if t.device != self.device or t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous():
+                    raise _lib.OvnError("params and accum must be flat contiguous float32 tensors on %s" % self.device)
+            count = int(params.numel())
+            if accum.numel() != count or not 1 <= count <= stride:
+                raise _lib.OvnError("params %d and accum %d elements for gradient rows of %d" % (count, accum.numel(), stride))
+        out = torch.empty(count, dtype=torch.float32, device=self.device) if (want_grad or params is None) else None
+        with self._dev():
+            _lib.check(self.lib.ovn_grad_reduce_adagrad(self._h, _ptr(grads), world, stride, w.ctypes.data_as(C.POINTER(C.c_double)), count,
+                                                        _ptr(params), _ptr(accum), float(lr), float(eps), _ptr(out), self._stream()),
+                       "ovn_grad_reduce_adagrad")
+        return out
+
     def debug_conv(self, layer: int, x: torch.Tensor) -> torch.Tensor:
         """Leg layer `layer` alone on x (nb, h, w, cin) in the current leg precision (`ovn_debug_conv`)."""
         self._require_leg()

@@ -15,6 +15,11 @@ the Siamese network, Adagrad).  The leg's forward with stored activations and it
 (`OvnEngine.leg_forward_train` / `leg_backward`, csrc/leg_backward.hip); the chain is leg forward -> `heads_feature_grad` ->
 `sum_rows_by_entry` for both sides (the leg is shared: a scan that is left in one pair and right in another gets both sums) ->
 leg backward -> Adagrad on the 8 head and 2 x layers leg tensors.
+
+Training on every GPU of a node: `DataParallelTrainer` runs that chain on each rank's share of the global batch; the ranks' flat
+gradients meet in one all-gather (`distributed.exchange_gradients`), and the share-weighted sum in a fixed order plus Adagrad on one
+flat parameter buffer is a kernel (`OvnEngine.grad_reduce_adagrad`, csrc/grad_reduce.hip): behind a collective the update is on the
+critical path of every rank.
 """
 from __future__ import annotations
 
@@ -374,3 +379,102 @@ class OverlapNetTrainer(object):
     def save(self, path: str) -> None:
         """Write `weights()` as npz; the file loads through config['pretrained_weightsfilename']."""
         W.save_npz(path, self.weights())
+
+
+class DataParallelTrainer(OverlapNetTrainer):
+    """`OverlapNetTrainer` on every GPU of a node: one process per GPU (torch.distributed; `group` None = the default group), each
+    with an ordinary, UNSHARDED `Infer` holding the same weights.  `step`, `fit` and `fit_from_npz` take the GLOBAL batch,
+    identically on every rank (`epoch_batches` depends on (seed, epoch) alone, batch_size is the global one); rank r runs the chain
+    of the base class on pairs `distributed.shard_bounds(len(batch), world, r)` of it, in order, over the unique scans of ITS pairs
+    (a scan two ranks need is run by both).  The ranks' flat gradients [head | leg] meet in ONE all-gather
+    (`distributed.exchange_gradients`), and one kernel (`OvnEngine.grad_reduce_adagrad`, csrc/grad_reduce.hip) forms
+    g = float32(sum_r (n_r / n) g_r), in fp64 and rank order, and applies Adagrad to ONE flat parameter buffer and ONE flat
+    accumulator, of which `params` / `accum` (names order; c_conv1/kernel as registered) are views.
+
+    A rank that gets no pair (the last, partial batch of an epoch can have fewer pairs than ranks) runs no engine call and sends
+    weight 0.  If the chain of any rank raises, that rank still enters the collective with a status; EVERY rank then raises
+    `OvnError` naming the failed ranks, and no parameter or accumulator has moved anywhere.
+
+    The same (seed, world) gives the same bits on every run and on every rank, whatever the backend: the reduction has a fixed
+    order and no atomics, and does not depend on the order in which the collective delivers the rows.  Another `world` regroups a sum
+    of float32-rounded per-rank means: it agrees to rounding, not bit for bit.  At world 1 the gradients are `OverlapNetTrainer`'s
+    bits (one row, weight 1.0).  The post-conditions of the base class hold on every rank; `weights()` / `save()` work on any rank."""
+
+    def __init__(self, infer, learning_rate: float, lr_alpha: float = 0.99, loss: str = "sigmoid", overlap_scale: float = 5.0,
+                 yaw_scale: float = 1.0, min_overlap_for_angle: float = 0.7, train_legs: bool = True, group=None):
+        import os
+        import torch.distributed as dist
+        if getattr(infer, "_world", 1) > 1:
+            raise OvnError("DataParallelTrainer: not available on a sharded Infer (world %d): every rank takes an unsharded one" % infer._world)
+        self.group = group
+        if dist.is_available() and dist.is_initialized():
+            self.world, self.rank = dist.get_world_size(group), dist.get_rank(group)
+        else:
+            if group is not None or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+                raise OvnError("DataParallelTrainer: torch.distributed is not initialised (init_process_group first)")
+            self.world, self.rank = 1, 0
+        super().__init__(infer, learning_rate, lr_alpha, loss, overlap_scale, yaw_scale, min_overlap_for_angle, train_legs)
+        if self.world > self.engine.GRAD_REDUCE_MAX_WORLD:
+            raise OvnError("DataParallelTrainer: at most %d ranks, got %d" % (self.engine.GRAD_REDUCE_MAX_WORLD, self.world))
+        # the tensors of the base class become views of one flat buffer each, in `names` order
+        sizes = [int(p.numel()) for p in self.params]
+        self.flat_params = torch.cat([p.reshape(-1) for p in self.params])
+        self.flat_accum = torch.zeros_like(self.flat_params)
+        offs = np.concatenate([[0], np.cumsum(sizes)])
+        self.params = [self.flat_params[a:a + s].view(p.shape) for a, s, p in zip(offs, sizes, self.params)]
+        self.accum = [self.flat_accum[a:a + s].view(p.shape) for a, s, p in zip(offs, sizes, self.params)]
+        self.count = int(offs[-1] if self.train_legs else offs[8])       # elements exchanged and updated
+        self._idle = torch.zeros(self.count, dtype=torch.float32, device=self.engine.device)     # what a rank without a gradient sends
+
+    # -- one exchange -------------------------------------------------------------------------------
+    def _exchange(self, left_names, right_names, overlaps, yaw_bins):
+        """This rank's share of the global batch through the chain, then the all-gather.  -> (rows, rank weights, loss, r)."""
+        from .distributed import exchange_gradients, shard_bounds
+        ln, rn = [str(v) for v in left_names], [str(v) for v in right_names]
+        ov = np.asarray(overlaps.cpu() if isinstance(overlaps, torch.Tensor) else overlaps, np.float32).reshape(-1)
+        yb = np.asarray(yaw_bins.cpu() if isinstance(yaw_bins, torch.Tensor) else yaw_bins, np.int32).reshape(-1)
+        if not (len(ln) == len(rn) == len(ov) == len(yb)) or not ln:
+            raise ValueError("%d left, %d right names, %d overlaps and %d yaw bins (at least one pair)" % (len(ln), len(rn), len(ov), len(yb)))
+        lo, hi = shard_bounds(len(ln), self.world, self.rank)
+        flat, lv, status, err, r = self._idle, (0.0, 0.0), 0, None, None
+        if hi > lo:
+            try:
+                r, grads = self._chain(ln[lo:hi], rn[lo:hi], ov[lo:hi], yb[lo:hi])
+                flat = torch.cat([g.reshape(-1) for g in grads])
+                lv = [float(v) for v in r["loss"].cpu()]
+            except Exception as e:           # still enter the collective: the others must not wait for this rank
+                flat, status, err = self._idle, 1, e
+        rows, w, loss, statuses = exchange_gradients(flat, hi - lo, lv, status, self.group)
+        bad = [int(k) for k in np.flatnonzero(statuses != 0)]
+        if bad:
+            raise OvnError("DataParallelTrainer: the chain of rank(s) %s failed, no weight moved%s"
+                           % (bad, "" if err is None else " (this rank: %s)" % err)) from err
+        return rows, w, loss, r
+
+    def gradients(self, left_names, right_names, overlaps, yaw_bins) -> Dict[str, torch.Tensor]:
+        """The reduced gradients of the GLOBAL batch with respect to the tensors of the weight FILE, by Keras name (the same bits on
+        every rank), plus the global 'loss_overlap' and 'loss_yaw' (float64, 0-dim, host).  No update."""
+        from .distributed import unpack_grad_trailer
+        rows, w, _loss, _r = self._exchange(left_names, right_names, overlaps, yaw_bins)
+        flat = self.engine.grad_reduce_adagrad(rows, w, count=self.count)
+        out, off = {}, 0
+        for name, p in zip(self.names, self.params):
+            if off >= self.count:
+                break
+            g = flat[off:off + p.numel()].view(p.shape)
+            out[name] = -g if (name == "c_conv1/kernel" and self.engine.negate_diffs) else g
+            off += p.numel()
+        lss = unpack_grad_trailer(rows)[0]
+        for k, key in enumerate(("loss_overlap", "loss_yaw")):
+            out[key] = torch.tensor(sum(w[r] * lss[r, k] for r in range(self.world) if w[r] != 0.0), dtype=torch.float64)
+        return out
+
+    def _update(self, left_names, right_names, overlaps, yaw_bins) -> torch.Tensor:
+        rows, w, loss, r = self._exchange(left_names, right_names, overlaps, yaw_bins)
+        self.engine.grad_reduce_adagrad(rows, w, self.flat_params[:self.count], self.flat_accum[:self.count],
+                                        float(lr_schedule(self.epoch, self.learning_rate, self.lr_alpha)))
+        self.engine.set_head_weights(self.params[:8])
+        if self.train_legs:
+            self.engine.set_leg_weights(dict(zip(self.leg_names, self.params[8:])))
+        self.last = r
+        return torch.tensor([loss], dtype=torch.float64)
