@@ -55,6 +55,20 @@ int ovn_destroy(ovn_ctx* ctx);
  * s_conv10).  kernel_dev: Keras layout (kh, kw, cin, cout); bias_dev: (cout).  The library keeps its
  * own re-tiled copy (MFMA fragment order), so the caller may release its buffers after the call
  * returns (the call synchronises `stream`).  All leg layers are valid-padded + bias + ReLU.
+ * Geometry: any kh, kw, cin, stride_h, stride_w >= 1 and any cout that is a multiple of 16; cin must be
+ * the cout of the layer registered before (the context's in_c for the first).  Anything else returns
+ * OVN_ERR_ARG and leaves the context as it was: a valid layer may follow.
+ * One rule depends on the input size, which is only known per call: in leg precision f16x3 (the default,
+ * ovn_set_leg_precision) a layer that none of the shape-specialised leg kernels takes -- every layer but
+ * the reference's s_conv1 with strides (2, 2) at in_c = 4 and s_conv2 ... s_conv10 -- runs a general
+ * kernel whose tiles need at least 128 output positions (oh * ow) per image.  For the context's own
+ * input size the rule is applied where everything is known: ovn_finalize in leg precision f16x3, and
+ * ovn_set_leg_precision(ctx, 1) on a finalized context, return OVN_ERR_ARG "layer <name>: fewer than 128
+ * output positions per image" (set precision f32 before ovn_finalize to run such a leg in fp32), so
+ * ovn_leg never meets it.  ovn_debug_conv takes its input size per call and returns the same error
+ * before launching the layer, writing nothing to the output.  Leg precision f32, the training forward
+ * and the backward pass have no such limit.  Every leg the reference's `strides_layer1` can produce for
+ * a feature volume of 1 x W, W >= 45, gives its first layer more positions than that.
  * Replaces `leg.load_weights(file, by_name=True)` (infer.py:119). */
 int ovn_add_leg_layer(ovn_ctx* ctx, const char* name, const float* kernel_dev, const float* bias_dev,
                       int kh, int kw, int cin, int cout, int stride_h, int stride_w, void* stream);

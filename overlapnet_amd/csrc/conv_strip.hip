@@ -739,11 +739,30 @@ bool ovn_conv_strip_own_scale(const OvnConvLayer& L, long long call_nb, int h, i
   return true;
 }
 
+// True when ovn_conv_strip_try takes this layer at every 16-byte aligned input of h x w: the choice depends on the layer's
+// geometry alone, never on the size of the call (ovn_finalize uses it to tell which layers fall to the generic kernel).
+bool ovn_conv_strip_matches(const OvnConvLayer& L, int h, int w) {
+  if (!(L.relu && L.wp_h != nullptr) || h < L.kh || w < L.kw) return false;
+  if (L.wp_h16 != nullptr)
+    return (L.kh == 5 && L.kw == 15 && L.cin == 4 && L.cout == 16 && L.sh == 2 && L.sw == 2) ||
+           (L.kh == 3 && L.kw == 15 && L.cin == 16 && L.cout == 32 && L.sh == 2 && L.sw == 1);
+  if (L.sw != 1 || (L.kh > 1 && L.sh != 2) || (L.kh == 1 && L.sh != 1)) return false;
+  switch (((L.kh * 100 + L.kw) * 1000 + L.cin) * 1000 + L.cout) {
+    case ((3 * 100 + 15) * 1000 + 32) * 1000 + 64:
+    case ((3 * 100 + 12) * 1000 + 64) * 1000 + 64:
+    case ((2 * 100 + 9) * 1000 + 64) * 1000 + 128:
+    case ((1 * 100 + 9) * 1000 + 128) * 1000 + 128:
+    case ((1 * 100 + 7) * 1000 + 128) * 1000 + 128:
+    case ((1 * 100 + 5) * 1000 + 128) * 1000 + 128:
+    case ((1 * 100 + 3) * 1000 + 128) * 1000 + 128: return true;
+    default: return false;
+  }
+}
+
 // Returns 1 when the layer / call was taken (result in out), 0 when the caller should use the generic kernel, < 0 on error.
 int ovn_conv_strip_try(const OvnConvLayer& L, const float* in, int nb, long long call_nb, int h, int w, float* out,
                        const unsigned* in_max, unsigned* out_max, hipStream_t stream) {
-  if (!(L.relu && L.wp_h != nullptr) || (reinterpret_cast<uintptr_t>(in) & 15) != 0) return 0;
-  if (h < L.kh || w < L.kw) return 0;
+  if (!ovn_conv_strip_matches(L, h, w) || (reinterpret_cast<uintptr_t>(in) & 15) != 0) return 0;
   bool took = false;
   int rc = OVN_OK;
   if (L.wp_h16 != nullptr) {   // few input channels: pixel-major strips, taps padded to 16

@@ -292,6 +292,30 @@ int ovn_set_head_weights(ovn_ctx* ctx, const float* c1k, const float* c1b, const
   return OVN_OK;
 }
 
+// Leg precision f16x3 at the context's input size: the first layer that falls to the generic kernel (neither the fused front or
+// tail nor a strip kernel takes it) with fewer output positions per image than that kernel's tiles need
+// (ovn_conv_forward_f16x3), or -1.  Known once the layers and the input size are: refused before the first ovn_leg.
+static int leg_f16x3_unserved(const ovn_ctx* ctx) {
+  int h = ctx->in_h, w = ctx->in_w;
+  for (size_t li = 0; li < ctx->leg.size(); ++li) {
+    const auto& l = ctx->leg[li];
+    if (h < l.kh || w < l.kw) return -1;          // ovn_finalize refuses that itself
+    const int oh = (h - l.kh) / l.sh + 1, ow = (w - l.kw) / l.sw + 1;
+    if (li == 0 && ovn_leg_front_matches(ctx, li, h, w)) {
+      const auto& l2 = ctx->leg[1];
+      h = (oh - l2.kh) / l2.sh + 1;
+      w = (ow - l2.kw) / l2.sw + 1;
+      ++li;
+      continue;
+    }
+    if (ovn_leg_tail_matches(ctx, li, h, w)) return -1;
+    if (!ovn_conv_strip_matches(l, h, w) && (long long)oh * ow < 128) return (int)li;
+    h = oh;
+    w = ow;
+  }
+  return -1;
+}
+
 int ovn_finalize(ovn_ctx* ctx, int* feat_w) {
   OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_finalize: ctx is NULL");
   OVN_REQUIRE(!ctx->leg.empty(), OVN_ERR_STATE, "ovn_finalize: no leg layers registered");
@@ -308,6 +332,12 @@ int ovn_finalize(ovn_ctx* ctx, int* feat_w) {
   OVN_REQUIRE(!ctx->head_set || w / ctx->head_s == ctx->head_g, OVN_ERR_STATE,
               "ovn_finalize: leg width %d gives %d column groups, the head weights were registered for %d", w, w / ctx->head_s,
               ctx->head_g);
+  if (ctx->leg_mode != 0) {
+    const int bad = leg_f16x3_unserved(ctx);
+    OVN_REQUIRE(bad < 0, OVN_ERR_ARG,
+                "ovn_finalize: layer %s: fewer than 128 output positions per image in leg precision f16x3 (ovn_set_leg_precision(ctx, 0) "
+                "before ovn_finalize runs this leg in fp32)", ctx->leg[bad < 0 ? 0 : bad].name.c_str());
+  }
   ctx->feat_w = w;
   ctx->finalized = true;
   if (feat_w) *feat_w = w;
@@ -1314,6 +1344,11 @@ int ovn_set_projection_trig(ovn_ctx* ctx, int mode) {
 int ovn_set_leg_precision(ovn_ctx* ctx, int mode) {
   OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_set_leg_precision: ctx is NULL");
   OVN_REQUIRE(mode == 0 || mode == 1, OVN_ERR_ARG, "ovn_set_leg_precision: mode %d (0 = fp32 MFMA, 1 = f16x3 MFMA)", mode);
+  if (mode != 0 && ctx->finalized) {   // the rule ovn_finalize applies to a leg registered in f16x3
+    const int bad = leg_f16x3_unserved(ctx);
+    OVN_REQUIRE(bad < 0, OVN_ERR_ARG, "ovn_set_leg_precision: layer %s: fewer than 128 output positions per image in leg precision f16x3",
+                ctx->leg[bad < 0 ? 0 : bad].name.c_str());
+  }
   ctx->leg_mode = mode;
   return OVN_OK;
 }

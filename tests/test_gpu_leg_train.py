@@ -34,6 +34,7 @@ from oracle import error_bounds as E
 from overlapnet_amd import _lib
 from overlapnet_amd import weights as WT
 from tests import _head_grad_ref as R
+from tests import _leg_geometry_ref as G
 from tests import _leg_grad_ref as L
 
 pytestmark = pytest.mark.gpu
@@ -85,20 +86,15 @@ def eng3a():
 
 # ---- 1. each layer alone ---------------------------------------------------------------------------------------------------------
 
-def _layer_inputs(l):
-    """name -> (nb, h, w) for one layer (see the module docstring)."""
-    xr, xc = (1 if l.sh == 2 else 0), (1 if l.sw == 2 else 0)
-    return {"few": (1, l.kh, l.kw + 4 * l.sw), "odd": (SB + 1, l.kh + l.sh + xr, l.kw + 36 * l.sw + xc),
-            "long": (1, l.kh + l.sh, l.kw + 149 * l.sw)}
+_layer_inputs = G.layer_inputs      # name -> (nb, h, w) for one layer (see the module docstring); any stride: stride - 1 uncovered rows / columns
 
 
 def _check_layer(eng, weights, li, l, which, tag):
+    """Layer `l` (index li of `eng`: an OvnEngine, or a `_leg_geometry_ref.LayerEngine` holding the one layer) on input `which`."""
     nb, h, w = _layer_inputs(l)[which]
     oh, ow = (h - l.kh) // l.sh + 1, (w - l.kw) // l.sw + 1
     assert (oh, ow) == {"few": (1, 5), "odd": (2, 37), "long": (2, 150)}[which]
-    rng = np.random.default_rng([li, nb, h, w, l.cin])
-    x = rng.normal(0.0, 1.0, (nb, h, w, l.cin)).astype(np.float32)
-    dout = rng.normal(0.0, 1.0, (nb, oh, ow, l.cout)).astype(np.float32)
+    x, dout = G.backward_data(li, l, which)
     xt, dt = torch.from_numpy(x).to(eng.device), torch.from_numpy(dout).to(eng.device)
     eng.set_leg_precision("f32")
     out = eng.debug_conv(li, xt)
@@ -118,9 +114,13 @@ def _check_layer(eng, weights, li, l, which, tag):
     din = g["din"].cpu().numpy()
     ch, cw = (oh - 1) * l.sh + l.kh, (ow - 1) * l.sw + l.kw          # rows / columns some window covers
     if which == "odd":
-        assert ch == h - (1 if l.sh == 2 else 0) and cw == w - (1 if l.sw == 2 else 0)
+        assert ch == h - (l.sh - 1) and cw == w - (l.sw - 1)
     assert np.all(din[:, ch:] == 0) and np.all(din[:, :, cw:] == 0), tag
     assert np.any(din[:, ch - 1] != 0) and np.any(din[:, :, cw - 1] != 0), tag
+    if l.sh <= l.kh:                                                  # no gaps between the windows: every covered row gets a gradient
+        assert np.all(np.any(din[:, :ch] != 0, axis=(0, 2, 3))), tag
+    if l.sw <= l.kw:
+        assert np.all(np.any(din[:, :, :cw] != 0, axis=(0, 1, 3))), tag
 
 
 LAYERS3A = WT.leg_layers(4, CFG3A)
@@ -153,14 +153,11 @@ def test_first_layer_at_other_channel_counts(in_c, parity_file):
 LEG_CASES = [(45, n) for n in (1, 3, SB + 1)] + [(77, n) for n in (1, 3, SB + 1)] + [(360, 2)]
 
 
-@pytest.mark.parametrize("W,n", LEG_CASES, ids=["W%d-n%d" % c for c in LEG_CASES])
-def test_whole_leg(W, n, parity_file):
-    cfg = R.model_cfg(W, 15)
-    h, wi = R.GEOMS[(W, 15)]
+def _whole_leg(cfg, h, wi, W, n, tag, seed=None):
+    """The training forward and the whole leg's backward pass for model section `cfg` on n scans of h x wi (feature width W)."""
     layers = WT.leg_layers(4, cfg)
-    assert len(layers) == (11 if W == 360 else 10)
     rng = np.random.default_rng([W, n, 5])
-    weights = L.leg_weights(4, cfg, seed=W, feat_w=W)
+    weights = L.leg_weights(4, cfg, seed=W if seed is None else seed, feat_w=W)
     images = L.make_images(rng, n, h, wi, 4)
     eng = _engine(h, wi, 4, weights, cfg)
     try:
@@ -198,9 +195,17 @@ def test_whole_leg(W, n, parity_file):
         g32, _ = L.leg_grads(weights, images, dfeat, cfg, torch.float32, masks)
         for name in L.leg_names(4, cfg):
             assert tuple(g[name].shape) == g64[name].shape
-            _within_4T("leg W%d n%d" % (W, n), name, g[name].cpu().numpy(), g32[name], g64[name])
+            _within_4T(tag, name, g[name].cpu().numpy(), g32[name], g64[name])
     finally:
         eng.close()
+
+
+@pytest.mark.parametrize("W,n", LEG_CASES, ids=["W%d-n%d" % c for c in LEG_CASES])
+def test_whole_leg(W, n, parity_file):
+    cfg = R.model_cfg(W, 15)
+    h, wi = R.GEOMS[(W, 15)]
+    assert len(WT.leg_layers(4, cfg)) == (11 if W == 360 else 10)
+    _whole_leg(cfg, h, wi, W, n, "leg W%d n%d" % (W, n))
 
 
 # ---- 4. set_leg_weights -------------------------------------------------------------------------------------------------------------

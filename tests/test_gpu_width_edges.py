@@ -329,15 +329,12 @@ def test_normalize_modes_and_negate_diffs(fw):
 LEGS = [(45, False), (45, True), (512, False), (512, True)]
 
 
-@gpu
-@pytest.mark.parametrize("fw,a3", LEGS, ids=lambda x: str(x))
-def test_leg_against_the_bound(fw, a3):
-    """The leg at 32 x 247, 64 x 269, 32 x 1181 and 64 x 1203 in both leg precisions: its output against the bound of
-    leg_with_bounds, and every layer in isolation (ovn_debug_conv) on the fp32 rounding of its exact input."""
+def leg_against_the_bound(cfg, h, wi, fw, tag, layers=True):
+    """The leg of model section `cfg` at input h x wi (feature width fw) on two scans, in both leg precisions: its output against the
+    bound of leg_with_bounds, and with `layers` every layer in isolation (ovn_debug_conv on a context holding that layer alone) on
+    the fp32 rounding of its exact input.  Prints the worst err / bound per precision and layer."""
     from overlapnet_amd import _lib
     from overlapnet_amd.engine import OvnEngine, _ptr
-    cfg = _cfg(fw, a3)
-    h, wi = A3_GEOM[fw] if a3 else WIDTHS[fw]
     rng = np.random.default_rng(h * 10000 + wi)
     imgs = rng.normal(0.5, 1.0, size=(2, h, wi, 4)).astype(np.float32)
     wts = S.make_test_weights(4, seed=0, model_cfg=cfg, feat_w=fw)
@@ -352,7 +349,7 @@ def test_leg_against_the_bound(fw, a3):
             name, x, B = bounds[mode][-1]
             assert out.shape == (2, fw, 128)
             rt = E.ratio(out, x.reshape(out.shape), B.reshape(out.shape))
-            print("\n[leg %dx%d a3=%s %s] worst err / bound of %s: %.3g" % (h, wi, a3, mode, name, rt))
+            print("\n[leg %dx%d %s %s] worst err / bound of %s: %.3g" % (h, wi, tag, mode, name, rt))
             assert rt <= 1.0, (h, wi, mode, rt)
     finally:
         e.close()
@@ -360,29 +357,39 @@ def test_leg_against_the_bound(fw, a3):
     hh, ww = h, wi
     for l, (name, ref_out, _) in zip(WT.leg_layers(4, cfg), bounds["f32"]):
         assert l.name == name
-        el = OvnEngine(hh, ww, l.cin)
-        try:
-            kt = torch.from_numpy(wts[name + "/kernel"]).cuda()
-            bt = torch.from_numpy(wts[name + "/bias"]).cuda()
-            st = el._stream()
-            _lib.check(el.lib.ovn_add_leg_layer(el._h, name.encode(), _ptr(kt), _ptr(bt), l.kh, l.kw, l.cin, l.cout, l.sh, l.sw, st),
-                       "ovn_add_leg_layer")
-            oh, ow = (hh - l.kh) // l.sh + 1, (ww - l.kw) // l.sw + 1
-            xt = torch.from_numpy(np.ascontiguousarray(x)).cuda()
-            out = torch.empty((x.shape[0], oh, ow, l.cout), dtype=torch.float32, device="cuda")
-            ref, B = E.leg_layer_bound(x, wts[name + "/kernel"], wts[name + "/bias"], (l.sh, l.sw))
-            for mode in ("f16x3", "f32"):
-                el.set_leg_precision(mode)
-                out.fill_(float("nan"))
-                _lib.check(el.lib.ovn_debug_conv(el._h, 0, _ptr(xt), x.shape[0], hh, ww, _ptr(out), st), "ovn_debug_conv")
-                torch.cuda.synchronize()
-                rt = E.ratio(out.cpu().numpy(), ref, B[mode])
-                print("[leg layer %s %dx%d %s] worst err / bound: %.3g" % (name, hh, ww, mode, rt))
-                assert rt <= 1.0, (name, hh, ww, mode, rt)
-        finally:
-            el.close()
+        oh, ow = (hh - l.kh) // l.sh + 1, (ww - l.kw) // l.sw + 1
+        if layers is True or name in layers:
+            el = OvnEngine(hh, ww, l.cin)
+            try:
+                kt = torch.from_numpy(wts[name + "/kernel"]).cuda()
+                bt = torch.from_numpy(wts[name + "/bias"]).cuda()
+                st = el._stream()
+                _lib.check(el.lib.ovn_add_leg_layer(el._h, name.encode(), _ptr(kt), _ptr(bt), l.kh, l.kw, l.cin, l.cout, l.sh, l.sw, st),
+                           "ovn_add_leg_layer")
+                xt = torch.from_numpy(np.ascontiguousarray(x)).cuda()
+                out = torch.empty((x.shape[0], oh, ow, l.cout), dtype=torch.float32, device="cuda")
+                ref, B = E.leg_layer_bound(x, wts[name + "/kernel"], wts[name + "/bias"], (l.sh, l.sw))
+                for mode in ("f16x3", "f32"):
+                    el.set_leg_precision(mode)
+                    out.fill_(float("nan"))
+                    _lib.check(el.lib.ovn_debug_conv(el._h, 0, _ptr(xt), x.shape[0], hh, ww, _ptr(out), st), "ovn_debug_conv")
+                    torch.cuda.synchronize()
+                    rt = E.ratio(out.cpu().numpy(), ref, B[mode])
+                    print("[leg layer %s %dx%d %s] worst err / bound: %.3g" % (name, hh, ww, mode, rt))
+                    assert rt <= 1.0, (name, hh, ww, mode, rt)
+            finally:
+                el.close()
         x = ref_out.astype(np.float32)
         hh, ww = oh, ow
+
+
+@gpu
+@pytest.mark.parametrize("fw,a3", LEGS, ids=lambda x: str(x))
+def test_leg_against_the_bound(fw, a3):
+    """The leg at 32 x 247, 64 x 269, 32 x 1181 and 64 x 1203 in both leg precisions: its output against the bound of
+    leg_with_bounds, and every layer in isolation (ovn_debug_conv) on the fp32 rounding of its exact input."""
+    h, wi = A3_GEOM[fw] if a3 else WIDTHS[fw]
+    leg_against_the_bound(_cfg(fw, a3), h, wi, fw, "a3=%s" % a3)
 
 
 # ---- Infer end to end --------------------------------------------------------------------------------------------------------------
@@ -403,17 +410,13 @@ def _write_cues(root, fx, n, h, wi):
     return np.stack(imgs)
 
 
-@gpu
-@pytest.mark.parametrize("fw", [45, 512], ids=lambda fw: "W%d" % fw)
-def test_infer_end_to_end(tmp_path, fixture_npz, fw):
-    """Infer on 32-beam scans of width 247 / 1181: overlap and yaw of every pair against the oracle, infer_top_k against
-    decide_top_k on infer_multiple's outputs."""
+def infer_end_to_end(tmp_path, fixture_npz, mcfg, h, wi, fw):
+    """Infer with model section `mcfg` on five h x wi scans cut from the fixture images: overlap and yaw of every pair against the
+    oracle, infer_top_k against decide_top_k on infer_multiple's outputs."""
     from overlapnet_amd import lcd
     from overlapnet_amd.infer import Infer
-    h, wi = WIDTHS[fw]
     n = 5
     imgs = _write_cues(str(tmp_path / "data"), fixture_npz, n, h, wi)
-    mcfg = _cfg(fw)
     cfg = {"model": mcfg, "infer_seqs": "07", "data_root_folder": str(tmp_path / "data"), "use_depth": True, "use_normals": True,
            "use_class_probabilities": False, "use_class_probabilities_pca": False, "use_intensity": False, "batch_size": 16,
            "pretrained_weightsfilename": "", "precision": "f32"}
@@ -444,3 +447,11 @@ def test_infer_end_to_end(tmp_path, fixture_npz, fw):
         inf.close()
         tk.close()
 
+
+
+@gpu
+@pytest.mark.parametrize("fw", [45, 512], ids=lambda fw: "W%d" % fw)
+def test_infer_end_to_end(tmp_path, fixture_npz, fw):
+    """Infer on 32-beam scans of width 247 / 1181."""
+    h, wi = WIDTHS[fw]
+    infer_end_to_end(tmp_path, fixture_npz, _cfg(fw), h, wi, fw)
