@@ -235,28 +235,30 @@ int ovn_delta_prepare_w1(const float* c1_kernel_dev, float** w1p_out, hipStream_
   return OVN_OK;
 }
 
-// Bytes of scratch per pair: o2 (G, G, 128) | o3 (G - 2, G - 2, 256) | the split route's per-pair scales, each region 256-byte
-// aligned per call (see below)
+OvnDeltaF32Scratch::OvnDeltaF32Scratch(OvnCarver& c, int64_t n, int G, bool split) {
+  o2 = c.take<float>((size_t)n * G * G * OVN_C2_OUT);
+  o3 = c.take<float>((size_t)n * (G - 2) * (G - 2) * OVN_C3_OUT);
+  scales = c.take<char>(split ? (size_t)n * ovn_delta_w_split_pair_bytes() : 0);
+}
+
+// Bytes of scratch per pair, unaligned: o2 (G, G, 128) | o3 (G - 2, G - 2, 256) | the split route's per-pair scales
 size_t ovn_delta_pair_bytes(int G) {
   return ((size_t)G * G * OVN_C2_OUT + (size_t)(G - 2) * (G - 2) * OVN_C3_OUT) * sizeof(float) + ovn_delta_w_split_pair_bytes();
 }
 
-// The whole Delta head for n pairs at the context's feature width (360 before ovn_finalize), conv1size 15; scratch: n * ovn_delta_pair_bytes(G) + 512 bytes.
+// The whole Delta head for n pairs at the context's feature width (360 before ovn_finalize), conv1size 15, in a scratch laid out for
+// at least n pairs (with its scales when the split route is on).
 // DeltaLayer + c_conv1 + c_conv2 run exact fp32 here, or in f16x3 arithmetic (delta_head_w_f16x3.hip) when the context asks for
 // it (head mode 1 with ovn_set_head_width_split); c_conv3 and Dense are the same fp32 kernels either way.
 int ovn_delta_forward(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx, int n,
-                      void* scratch, float* overlap, float* logit, hipStream_t stream) {
+                      const OvnDeltaF32Scratch& scratch, float* overlap, float* logit, hipStream_t stream) {
   const int W = ctx->finalized ? ctx->feat_w : OVN_FEAT_W, G = W / S, R = G * S;
   OVN_REQUIRE(ctx->head_s == S && G == ctx->head_g && W >= OVN_FEAT_W_MIN && W <= OVN_FEAT_W_MAX, OVN_ERR_STATE,
               "Delta head at width %d: geometry (conv1size %d, %d groups) does not match", W, ctx->head_s, ctx->head_g);
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  float* o2 = static_cast<float*>(scratch);
-  float* o3 = reinterpret_cast<float*>(static_cast<char*>(scratch) + al((size_t)n * G * G * OVN_C2_OUT * sizeof(float)));
+  float *o2 = scratch.o2, *o3 = scratch.o3;
   int rc;
   if (ctx->head_width_split && ctx->head_mode == 1) {   // times its prepare and contraction kernels itself
-    void* scales = static_cast<char*>(scratch) + al((size_t)n * G * G * OVN_C2_OUT * sizeof(float)) +
-                   al((size_t)n * (G - 2) * (G - 2) * OVN_C3_OUT * sizeof(float));
-    rc = ovn_delta_w_split_c12_forward(ctx, feats_l, lidx, feats_r, ridx, n, scales, o2, stream);
+    rc = ovn_delta_w_split_c12_forward(ctx, feats_l, lidx, feats_r, ridx, n, scratch.scales, o2, stream);
     if (rc) return rc;
   } else {
     OvnProfScope ps(ctx, OVN_K_DELTA, stream);

@@ -42,7 +42,29 @@ constexpr int O2 = OVN_C2_OUT;    // 128
 constexpr int O3 = OVN_C3_OUT;    // 256
 constexpr int PB = OVN_GRAD_PAIR_BLOCK;
 
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+// Scratch of ovn_delta_head_grad_run for chunks of up to cmax pairs: the stage outputs o1 | o2 | o3, their gradients, per-pair dz /
+// overlap / logits, the transposed kernels, the pair blocks' partials and (a call without a grad output) the running sums
+struct GradScratch {
+  float *o1 = nullptr, *o2 = nullptr, *o3 = nullptr, *dO1 = nullptr, *dO2 = nullptr, *dO3 = nullptr, *dz = nullptr, *ybuf = nullptr,
+        *zbuf = nullptr, *w3t = nullptr, *w2t = nullptr, *part = nullptr, *grad = nullptr;
+  GradScratch() = default;
+  GradScratch(OvnCarver& c, size_t cmax, size_t o1e, size_t o2e, size_t o3e, size_t w3_elems, size_t w2_elems, size_t part_elems,
+              size_t grad_elems) {
+    o1 = c.take<float>(cmax * o1e);
+    o2 = c.take<float>(cmax * o2e);
+    o3 = c.take<float>(cmax * o3e);
+    dO1 = c.take<float>(cmax * o1e);
+    dO2 = c.take<float>(cmax * o2e);
+    dO3 = c.take<float>(cmax * o3e);
+    dz = c.take<float>(cmax);
+    ybuf = c.take<float>(cmax);
+    zbuf = c.take<float>(cmax);     // logits
+    w3t = c.take<float>(w3_elems);
+    w2t = c.take<float>(w2_elems);
+    part = c.take<float>(part_elems);
+    grad = c.take<float>(grad_elems);
+  }
+};
 
 // out[t][b][a] = in[t][a][b]
 __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict__ in, float* __restrict__ out, int T, int A, int B) {
@@ -360,31 +382,14 @@ int ovn_delta_head_grad_run(ovn_ctx* ctx, int FW, const float* feats_l, const in
   chunk = chunk < PB ? PB : chunk / PB * PB;           // whole pair blocks: the partials do not depend on the chunking
   const int64_t cmax = n < chunk ? n : chunk;
   const int64_t nbmax = (cmax + PB - 1) / PB;
-  const size_t b_fwd = al256((size_t)cmax * fwd_pair + 1024), b_d1 = al256((size_t)cmax * o1e * 4), b_d2 = al256((size_t)cmax * o2e * 4),
-               b_d3 = al256((size_t)cmax * o3e * 4), b_v = al256((size_t)cmax * 4), b_w3t = al256((size_t)sz[4] * 4),
-               b_w2t = al256((size_t)sz[2] * 4), b_part = al256((size_t)nbmax * stride * 4),
-               b_grad = (grad || forward_only) ? 0 : al256((size_t)total * 4);   // ovn_heads_feature_grad without head_grad_dev: the sums stay in scratch
-  int rc = ovn_ws_reserve(ctx, b_fwd + b_d1 + b_d2 + b_d3 + 3 * b_v + b_w3t + b_w2t + b_part + b_grad, stream);
+  GradScratch sc;   // (ovn_heads_feature_grad without head_grad_dev: the sums stay in scratch)
+  int rc = ovn_ws_layout(ctx, stream, &sc, (size_t)cmax, o1e, o2e, o3e, (size_t)sz[4], (size_t)sz[2], (size_t)nbmax * stride,
+                         (grad || forward_only) ? (size_t)0 : (size_t)total);
   if (rc) return rc;
-  ctx->dbg_o2 = ctx->dbg_o3 = nullptr;   // the scratch of an earlier head call is overwritten
-  ctx->dbg_partial = nullptr;
-  ctx->dbg_o2max = nullptr;
-  ctx->dbg_n = 0;
-  ctx->dbg_live = nullptr;
-  char* w = static_cast<char*>(ctx->ws);
-  float* o1 = reinterpret_cast<float*>(w);                 // the stage outputs of a chunk: o1 | o2 | o3, each for cmax pairs
-  float* o2 = o1 + (size_t)cmax * o1e;
-  float* o3 = o2 + (size_t)cmax * o2e;
-  float* dO1 = reinterpret_cast<float*>(w += b_fwd);
-  float* dO2 = reinterpret_cast<float*>(w += b_d1);
-  float* dO3 = reinterpret_cast<float*>(w += b_d2);
-  float* dz = reinterpret_cast<float*>(w += b_d3);
-  float* ybuf = reinterpret_cast<float*>(w += b_v);
-  float* zbuf = reinterpret_cast<float*>(w += b_v);     // logits
-  float* w3t = reinterpret_cast<float*>(w += b_v);
-  float* w2t = reinterpret_cast<float*>(w += b_w3t);
-  float* part = reinterpret_cast<float*>(w += b_w2t);
-  if (!grad && !forward_only) grad = reinterpret_cast<float*>(w += b_part);
+  scratch_overwritten(ctx);
+  float *o1 = sc.o1, *o2 = sc.o2, *o3 = sc.o3, *dO1 = sc.dO1, *dO2 = sc.dO2, *dO3 = sc.dO3, *dz = sc.dz, *ybuf = sc.ybuf, *zbuf = sc.zbuf,
+        *w3t = sc.w3t, *w2t = sc.w2t, *part = sc.part;
+  if (!grad && !forward_only) grad = sc.grad;
   // W3 (tap, ci, co) -> (tap, co, ci); W2 (di, o, ch) -> (di, ch, o)
   hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((sz[4] + 255) / 256)), dim3(256), 0, stream, ctx->w3raw, w3t, 9, O2, O3);
   hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((sz[2] + 255) / 256)), dim3(256), 0, stream, ctx->w2raw, w2t, s, O1, O2);

@@ -1731,20 +1731,31 @@ __global__ __launch_bounds__(256, 2) void delta_c2_kernel(const float* __restric
 
 }  // namespace
 
-size_t ovn_delta_f16x3_scratch_bytes(int n, bool per_pair_right) {
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  return al((size_t)n * 8 * sizeof(float)) + al((size_t)n * sizeof(unsigned)) + 2 * al((size_t)n * OVN_FEAT_ELEMS * sizeof(unsigned)) +
-         al((size_t)n * LIN_ELEMS * sizeof(float)) + al((size_t)(per_pair_right ? n : 1) * A2_KSPLIT * A2_ELEMS * sizeof(float)) +
-         al((size_t)n * O1RAW_ELEMS * sizeof(float)) + al((size_t)n * sizeof(DeltaDesc)) + al(QBLOCK_WORDS * sizeof(unsigned)) +
-         al(LIVE_WORDS * sizeof(unsigned)) + al((size_t)S * FC * O1 * 2 * sizeof(_Float16));
+// THE layout of a sub-chunk's block (f16x3 and bf16x3 paths; a segmented pass leaves a2raw, qblock, live and w1c unused: its
+// segments' state lives in an OvnDeltaSegScratch)
+OvnDeltaSubScratch::OvnDeltaSubScratch(OvnCarver& c, int n, bool per_pair_right) {
+  scales = c.take<f32x4>((size_t)n * 2);
+  o2max = c.take<unsigned>(n);
+  pl = c.take<unsigned>((size_t)n * OVN_FEAT_ELEMS);
+  pr = c.take<unsigned>((size_t)n * OVN_FEAT_ELEMS);
+  lin = c.take<float>((size_t)n * LIN_ELEMS);
+  a2raw = c.take<float>((size_t)(per_pair_right ? n : 1) * A2_KSPLIT * A2_ELEMS);
+  o1raw = c.take<float>((size_t)n * O1RAW_ELEMS);
+  desc = c.take<DeltaDesc>(n);
+  qblock = c.take<unsigned>(QBLOCK_WORDS);   // bf16x3: the query's shared words
+  static_assert(QBLOCK_WORDS >= (size_t)OVN_FEAT_ELEMS, "query block too small for the shared words");
+  live = c.take<unsigned>(LIVE_WORDS);
+  w1c = c.take<_Float16>(W1C_HALFS);
 }
+size_t ovn_delta_f16x3_scratch_bytes(int n, bool per_pair_right) { return ovn_scratch_bytes<OvnDeltaSubScratch>(n, per_pair_right); }
 
-// per-segment query state of a segmented pass: A2raw, query block, live list, gathered W1 fragments per segment
-size_t ovn_delta_f16x3_seg_bytes(int nseg) {
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  return al((size_t)nseg * A2_KSPLIT * A2_ELEMS * sizeof(float)) + al((size_t)nseg * QBLOCK_WORDS * sizeof(unsigned)) +
-         al((size_t)nseg * LIVE_WORDS * sizeof(unsigned)) + al((size_t)nseg * W1C_HALFS * sizeof(_Float16));
+OvnDeltaSegScratch::OvnDeltaSegScratch(OvnCarver& c, int nseg) {
+  a2raw = c.take<float>((size_t)nseg * A2_KSPLIT * A2_ELEMS);
+  qblock = c.take<unsigned>((size_t)nseg * QBLOCK_WORDS);
+  live = c.take<unsigned>((size_t)nseg * LIVE_WORDS);
+  w1c = c.take<_Float16>((size_t)nseg * W1C_HALFS);
 }
+size_t ovn_delta_f16x3_seg_bytes(int nseg) { return ovn_scratch_bytes<OvnDeltaSegScratch>(nseg); }
 
 static int pick_nsplit(int n) {
   // divisors of the 12 passes (11 of two row tiles + the short one): time ~ rounds of workgroups over the 256 CUs x 1/d of a pair's
@@ -1811,50 +1822,24 @@ static void launch_c2(int n, const float* o1raw, const void* w2, const DeltaDesc
 }
 
 // a2 + prepare (profile class delta_prep), c_conv1 contraction (delta_c12), c_conv2 GEMM (delta_c2)
-// where ovn_delta_c12_f16x3_forward keeps A2raw inside its scratch (the yaw launch of a small sweep fills it: a2_done)
-float* ovn_delta_f16x3_a2raw(void* scratch, int n) {
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  char* p = static_cast<char*>(scratch);
-  p += al((size_t)n * 8 * sizeof(float)) + al((size_t)n * sizeof(unsigned)) + 2 * al((size_t)n * OVN_FEAT_ELEMS * sizeof(unsigned)) +
-       al((size_t)n * LIN_ELEMS * sizeof(float));
-  return reinterpret_cast<float*>(p);
-}
-
 // Segmented pass (ovn_heads_segments, compaction on): the pairs of several segments, pair p = (feats_l[lidx[p]], feats_r[ridx[p]]) in
 // segment seg.pseg[p].  Each segment's query state -- A2, the query block, the live list and the W1 fragments gathered for it -- is
 // computed ONCE, for all segments of the pass in one launch each; the prepare and contraction kernels find a pair's through pseg.
 // Every pair then runs exactly what its segment's 1-vs-N sweep runs for it (same scales, same compacted K walk rotated by the
 // candidate's slot, same cache-row rule): the same bits.
 static int delta_c12_f16x3_segments(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx,
-                                    int n, void* scratch, unsigned** o2max_out, float* o2, hipStream_t stream, const float* dcache_l,
+                                    int n, const OvnDeltaSubScratch& sc, float* o2, hipStream_t stream, const float* dcache_l,
                                     const OvnSegPass& seg) {
   int rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_prepare_split_kernel<false, true>), PREP_SPLIT_LDS);
   if (rc) return rc;
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  char* p = static_cast<char*>(scratch);
-  f32x4* scales = reinterpret_cast<f32x4*>(p);
-  p += al((size_t)n * 8 * sizeof(float));
-  unsigned* o2max = reinterpret_cast<unsigned*>(p);
-  p += al((size_t)n * sizeof(unsigned));
-  unsigned* pl = reinterpret_cast<unsigned*>(p);
-  p += al((size_t)n * OVN_FEAT_ELEMS * sizeof(unsigned));
-  unsigned* pr = reinterpret_cast<unsigned*>(p);
-  p += al((size_t)n * OVN_FEAT_ELEMS * sizeof(unsigned));
-  float* lin = reinterpret_cast<float*>(p);
-  p += al((size_t)n * LIN_ELEMS * sizeof(float));
-  float* o1raw = reinterpret_cast<float*>(p);
-  p += al((size_t)n * O1RAW_ELEMS * sizeof(float));
-  DeltaDesc* desc = reinterpret_cast<DeltaDesc*>(p);
-  char* q = static_cast<char*>(seg.scratch);   // ovn_delta_f16x3_seg_bytes(seg.nseg)
-  float* a2raw = reinterpret_cast<float*>(q);
-  q += al((size_t)seg.nseg * A2_KSPLIT * A2_ELEMS * sizeof(float));
-  unsigned* qblock = reinterpret_cast<unsigned*>(q);
-  q += al((size_t)seg.nseg * QBLOCK_WORDS * sizeof(unsigned));
-  unsigned* live = reinterpret_cast<unsigned*>(q);
-  q += al((size_t)seg.nseg * LIVE_WORDS * sizeof(unsigned));
-  _Float16* w1c = reinterpret_cast<_Float16*>(q);
+  f32x4* scales = sc.scales;
+  unsigned *o2max = sc.o2max, *pl = sc.pl, *pr = sc.pr;
+  float *lin = sc.lin, *o1raw = sc.o1raw;
+  DeltaDesc* desc = static_cast<DeltaDesc*>(sc.desc);
+  float* a2raw = seg.state.a2raw;
+  unsigned *qblock = seg.state.qblock, *live = seg.state.live;
+  _Float16* w1c = seg.state.w1c;
   ctx->dbg_live = nullptr;   // (ovn_head_walk_stats describes 1-vs-N sweeps)
-  *o2max_out = o2max;
   const int nsplit = pick_nsplit(n);
   {
     OvnProfScope ps(ctx, OVN_K_DELTA_PREP, stream);
@@ -1881,40 +1866,21 @@ static int delta_c12_f16x3_segments(ovn_ctx* ctx, const float* feats_l, const in
 }
 
 int ovn_delta_c12_f16x3_forward(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r,
-                                const int32_t* ridx, int n, void* scratch, unsigned** o2max_out, float* o2, hipStream_t stream,
-                                int pair0, const float* dcache_l, bool a2_done, const OvnSegPass* seg) {
+                                const int32_t* ridx, int n, const OvnDeltaSubScratch& sc, float* o2, hipStream_t stream, int pair0,
+                                const float* dcache_l, bool a2_done, const OvnSegPass* seg) {
   int rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_prepare_split_kernel<false>), PREP_SPLIT_LDS);
   if (rc) return rc;
-  if (seg) return delta_c12_f16x3_segments(ctx, feats_l, lidx, feats_r, ridx, n, scratch, o2max_out, o2, stream, dcache_l, *seg);
+  if (seg) return delta_c12_f16x3_segments(ctx, feats_l, lidx, feats_r, ridx, n, sc, o2, stream, dcache_l, *seg);
   if (ridx) dcache_l = nullptr;   // the cache serves the 1-vs-N form (one query against many cached candidates)
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  char* p = static_cast<char*>(scratch);
-  f32x4* scales = reinterpret_cast<f32x4*>(p);
-  p += al((size_t)n * 8 * sizeof(float));
-  unsigned* o2max = reinterpret_cast<unsigned*>(p);
-  p += al((size_t)n * sizeof(unsigned));
-  unsigned* pl = reinterpret_cast<unsigned*>(p);
-  p += al((size_t)n * OVN_FEAT_ELEMS * sizeof(unsigned));
-  unsigned* pr = reinterpret_cast<unsigned*>(p);
-  p += al((size_t)n * OVN_FEAT_ELEMS * sizeof(unsigned));
-  float* lin = reinterpret_cast<float*>(p);
-  p += al((size_t)n * LIN_ELEMS * sizeof(float));
-  float* a2raw = reinterpret_cast<float*>(p);
-  p += al((size_t)(ridx ? n : 1) * A2_KSPLIT * A2_ELEMS * sizeof(float));
-  float* o1raw = reinterpret_cast<float*>(p);
-  p += al((size_t)n * O1RAW_ELEMS * sizeof(float));
-  DeltaDesc* desc = reinterpret_cast<DeltaDesc*>(p);
-  p += al((size_t)n * sizeof(DeltaDesc));
-  unsigned* qblock = reinterpret_cast<unsigned*>(p);
-  p += al(QBLOCK_WORDS * sizeof(unsigned));
-  unsigned* live_buf = reinterpret_cast<unsigned*>(p);
-  p += al(LIVE_WORDS * sizeof(unsigned));
-  _Float16* w1c = reinterpret_cast<_Float16*>(p);
+  f32x4* scales = sc.scales;
+  unsigned *o2max = sc.o2max, *pl = sc.pl, *pr = sc.pr, *qblock = sc.qblock, *live_buf = sc.live;
+  float *lin = sc.lin, *a2raw = sc.a2raw, *o1raw = sc.o1raw;
+  DeltaDesc* desc = static_cast<DeltaDesc*>(sc.desc);
+  _Float16* w1c = sc.w1c;
   // 1-vs-N sweeps (one query for all pairs): the query's live-channel list and the W1 fragments gathered for it; indexed pairs walk
   // the plain K (every pair has its own right volume)
   const unsigned* live = (ridx || !ctx->head_compact) ? nullptr : live_buf;
   ctx->dbg_live = live;   // ovn_head_walk_stats: the K walk of the most recent sweep (its last chunk)
-  *o2max_out = o2max;
   const int nsplit = pick_nsplit(n);   // 45 / 23: 8-row / one-row-tile passes, one per workgroup, chosen for <= 5 / <= 10 pairs
   {
     OvnProfScope ps(ctx, OVN_K_DELTA_PREP, stream);
@@ -1946,32 +1912,17 @@ int ovn_delta_c12_f16x3_forward(ovn_ctx* ctx, const float* feats_l, const int32_
   return OVN_OK;
 }
 
-// bf16x3 mode (ovn_set_head_precision 2): same scratch layout as the f16x3 path (its query block holds the query's shared words), same
+// bf16x3 mode (ovn_set_head_precision 2): the scratch layout of the f16x3 path (its query block holds the query's shared words), same
 // launch structure and profile classes; dense walk of all 128 channels, no Delta cache rows.
 int ovn_delta_c12_bf16x3_forward(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx,
-                                 int n, void* scratch, float* o2, hipStream_t stream, int pair0, bool a2_done) {
+                                 int n, const OvnDeltaSubScratch& sc, float* o2, hipStream_t stream, int pair0, bool a2_done) {
   int rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_prepare_bf16x3_kernel), PREP_B3_LDS);
   if (rc) return rc;
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  char* p = static_cast<char*>(scratch);
-  f32x4* scales = reinterpret_cast<f32x4*>(p);
-  p += al((size_t)n * 8 * sizeof(float));
-  unsigned* o2max = reinterpret_cast<unsigned*>(p);
-  p += al((size_t)n * sizeof(unsigned));
-  unsigned* pl = reinterpret_cast<unsigned*>(p);
-  p += al((size_t)n * OVN_FEAT_ELEMS * sizeof(unsigned));
-  unsigned* pr = reinterpret_cast<unsigned*>(p);
-  p += al((size_t)n * OVN_FEAT_ELEMS * sizeof(unsigned));
-  float* lin = reinterpret_cast<float*>(p);
-  p += al((size_t)n * LIN_ELEMS * sizeof(float));
-  float* a2raw = reinterpret_cast<float*>(p);
-  p += al((size_t)(ridx ? n : 1) * A2_KSPLIT * A2_ELEMS * sizeof(float));
-  float* o1raw = reinterpret_cast<float*>(p);
-  p += al((size_t)n * O1RAW_ELEMS * sizeof(float));
-  DeltaDesc* desc = reinterpret_cast<DeltaDesc*>(p);
-  p += al((size_t)n * sizeof(DeltaDesc));
-  unsigned* qwords = ridx ? nullptr : reinterpret_cast<unsigned*>(p);   // QBLOCK_WORDS >= one volume of words
-  static_assert(QBLOCK_WORDS >= (size_t)OVN_FEAT_ELEMS, "query block too small for the shared words");
+  f32x4* scales = sc.scales;
+  unsigned *o2max = sc.o2max, *pl = sc.pl, *pr = sc.pr;
+  float *lin = sc.lin, *a2raw = sc.a2raw, *o1raw = sc.o1raw;
+  DeltaDesc* desc = static_cast<DeltaDesc*>(sc.desc);
+  unsigned* qwords = ridx ? nullptr : sc.qblock;   // the query block holds the query's shared words
   ctx->dbg_live = nullptr;   // every pair walks all 128 channels
   const int nsplit = pick_nsplit(n);
   {

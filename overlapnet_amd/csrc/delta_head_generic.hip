@@ -88,11 +88,14 @@ __global__ __launch_bounds__(256) void delta_c1_generic_kernel(const float* __re
 
 }  // namespace
 
-// Bytes of scratch per pair of the general path: out1 (W, G, 64) | o2 (G, G, 128) | o3 (G - 2, G - 2, 256), each 256-byte aligned
-size_t ovn_delta_generic_pair_bytes(int FW, int G) {
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  return al((size_t)FW * G * O1 * 4) + al((size_t)G * G * OVN_C2_OUT * 4) + al((size_t)(G - 2) * (G - 2) * OVN_C3_OUT * 4);
+OvnDeltaGenericScratch::OvnDeltaGenericScratch(OvnCarver& c, int64_t n, int FW, int G) {
+  out1 = c.take<float>((size_t)n * FW * G * O1);
+  o2 = c.take<float>((size_t)n * G * G * OVN_C2_OUT);
+  o3 = c.take<float>((size_t)n * (G - 2) * (G - 2) * OVN_C3_OUT);
 }
+
+// Bytes of scratch of ONE pair of the general path; n pairs never need more than n times that
+size_t ovn_delta_generic_pair_bytes(int FW, int G) { return ovn_scratch_bytes<OvnDeltaGenericScratch>((int64_t)1, FW, G); }
 
 // DeltaLayer + c_conv1 alone with the sums carried in fp64: out1 (n, W, G, 64), each element the correctly rounded fp32 value
 int ovn_delta_generic_c1_wide(const ovn_ctx* ctx, int FW, const float* feats_l, const int32_t* lidx, const float* feats_r,
@@ -109,15 +112,13 @@ int ovn_delta_generic_c1_wide(const ovn_ctx* ctx, int FW, const float* feats_l, 
 }
 
 // The whole Delta head for n pairs at conv1size s = ctx->head_s (any value with W // s >= 3) and feature width W = ctx->feat_w (360
-// before ovn_finalize); scratch: n * pair_bytes
+// before ovn_finalize), in a scratch laid out for at least n pairs
 int ovn_delta_generic_forward(const ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r,
-                              const int32_t* ridx, int n, void* scratch, float* overlap, float* logit, hipStream_t stream) {
+                              const int32_t* ridx, int n, const OvnDeltaGenericScratch& scratch, float* overlap, float* logit,
+                              hipStream_t stream) {
   const int s = ctx->head_s, G = ctx->head_g;
   const int FW = ctx->finalized ? ctx->feat_w : OVN_FEAT_W;
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  float* out1 = static_cast<float*>(scratch);
-  float* o2 = reinterpret_cast<float*>(static_cast<char*>(scratch) + al((size_t)n * FW * G * O1 * 4));
-  float* o3 = reinterpret_cast<float*>(reinterpret_cast<char*>(o2) + al((size_t)n * G * G * OVN_C2_OUT * 4));
+  float *out1 = scratch.out1, *o2 = scratch.o2, *o3 = scratch.o3;
   const size_t lds = ((size_t)IB * FC + (size_t)s * FC) * sizeof(float);
   int rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_c1_generic_kernel<float>), lds);
   if (rc) return rc;

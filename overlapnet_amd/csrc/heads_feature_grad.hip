@@ -260,6 +260,19 @@ __global__ __launch_bounds__(256) void yaw_grad_kernel(const float* __restrict__
   }
 }
 
+// Scratch of ovn_yaw_grad_run for chunks of up to cmax pairs: dL/d(logits) in fp64 | per-pair losses | the logits, unless the caller
+// takes them
+struct YawGradScratch {
+  double* g = nullptr;
+  float *pl = nullptr, *zbuf = nullptr;
+  YawGradScratch() = default;
+  YawGradScratch(OvnCarver& c, size_t cmax, int FW, bool own_logits) {
+    g = c.take<double>(cmax * FW);
+    pl = c.take<float>(cmax);
+    zbuf = c.take<float>(own_logits ? cmax * FW : 0);
+  }
+};
+
 }  // namespace
 
 int ovn_delta_data_grad(ovn_ctx* ctx, int FW, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx,
@@ -279,19 +292,12 @@ int ovn_yaw_grad_run(ovn_ctx* ctx, int FW, const float* feats_l, const int32_t* 
                      float* loss_yaw, float* corr, hipStream_t stream) {
   const int64_t chunk = 4096;                       // whole pair blocks; the grids' y extent
   const int64_t cmax = n < chunk ? n : chunk;
-  const size_t b_g = ((size_t)cmax * FW * sizeof(double) + 255) & ~(size_t)255, b_pl = ((size_t)cmax * 4 + 255) & ~(size_t)255;
-  const size_t b_z = corr ? 0 : ((size_t)cmax * FW * 4 + 255) & ~(size_t)255;
-  int rc = ovn_ws_reserve(ctx, b_g + b_pl + b_z, stream);
+  YawGradScratch sc;
+  int rc = ovn_ws_layout(ctx, stream, &sc, (size_t)cmax, FW, corr == nullptr);
   if (rc) return rc;
-  ctx->dbg_o2 = ctx->dbg_o3 = nullptr;   // the scratch of an earlier head call is overwritten
-  ctx->dbg_partial = nullptr;
-  ctx->dbg_o2max = nullptr;
-  ctx->dbg_n = 0;
-  ctx->dbg_live = nullptr;
-  char* w = static_cast<char*>(ctx->ws);
-  double* g = reinterpret_cast<double*>(w);
-  float* pl = reinterpret_cast<float*>(w + b_g);
-  float* zbuf = reinterpret_cast<float*>(w + b_g + b_pl);
+  scratch_overwritten(ctx);
+  double* g = sc.g;
+  float *pl = sc.pl, *zbuf = sc.zbuf;
   const double coef = (double)yaw_scale / ((double)n * (double)FW);
   const size_t feat_elems = (size_t)FW * FC;
   for (int64_t p0 = 0; p0 < n; p0 += chunk) {

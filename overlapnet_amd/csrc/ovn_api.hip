@@ -32,6 +32,14 @@ void ovn_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
+void scratch_overwritten(ovn_ctx* ctx) {
+  ctx->dbg_o2 = ctx->dbg_o3 = nullptr;
+  ctx->dbg_partial = nullptr;
+  ctx->dbg_o2max = nullptr;
+  ctx->dbg_n = 0;
+  ctx->dbg_live = nullptr;
+}
+
 // One scratch block per context, grown on demand and never shrunk.  Growing it synchronises `stream` and frees the old block
 // (hipFree waits for the device), so a context must be driven from ONE stream at a time (include/ovn_hip.h says so).
 int ovn_ws_reserve(ovn_ctx* ctx, size_t bytes, hipStream_t stream) {
@@ -41,11 +49,7 @@ int ovn_ws_reserve(ovn_ctx* ctx, size_t bytes, hipStream_t stream) {
     OVN_HIP_CHECK(hipFree(ctx->ws));
     ctx->ws = nullptr;
     ctx->ws_bytes = 0;
-    ctx->dbg_o2 = ctx->dbg_o3 = nullptr;          // they pointed into the old block
-    ctx->dbg_partial = nullptr;
-    ctx->dbg_o2max = nullptr;
-    ctx->dbg_n = 0;
-    ctx->dbg_live = nullptr;
+    scratch_overwritten(ctx);
   }
   const size_t want = bytes + bytes / 8;  // a little headroom so near-equal requests do not thrash
   OVN_HIP_CHECK(hipMalloc(&ctx->ws, want));
@@ -56,6 +60,19 @@ int ovn_ws_reserve(ovn_ctx* ctx, size_t bytes, hipStream_t stream) {
 // Width of the context's feature volumes: the leg's output once finalized, the reference's 360 before (a context that registers head
 // weights without a leg keeps the behaviour it always had)
 static int ctx_feat_w(const ovn_ctx* ctx) { return ctx->finalized ? ctx->feat_w : OVN_FEAT_W; }
+
+// Scratch of the leg calls: `nbuf` (1 or 2) activation buffers of buf_elems floats | fp64 running sums | the partials of
+// ovn_leg_layer_backward (ovn_leg_grad_part_bytes)
+struct LegScratch {
+  float* buf[2] = {nullptr, nullptr};
+  double *acc = nullptr, *part = nullptr;
+  LegScratch() = default;
+  LegScratch(OvnCarver& c, size_t buf_elems, int nbuf, size_t acc_elems, size_t part_bytes) {
+    for (int i = 0; i < nbuf; ++i) buf[i] = c.take<float>(buf_elems);
+    acc = c.take<double>(acc_elems);
+    part = reinterpret_cast<double*>(c.take<char>(part_bytes));
+  }
+};
 
 extern "C" {
 
@@ -368,10 +385,10 @@ int ovn_leg(ovn_ctx* ctx, const float* images_dev, int64_t n, float* features_de
   // scans: 5.18 / 5.00 / 4.93 ms per 1025 scans (fewer launch ramps and drains between the five kernels of a slice)
   const int64_t nslices = (n + OVN_LEG_SLICE - 1) / OVN_LEG_SLICE;
   const int64_t slice = (n + nslices - 1) / nslices;
-  const size_t buf_bytes = ((size_t)slice * max_act * sizeof(float) + 255) & ~(size_t)255;
-  int rc = ovn_ws_reserve(ctx, 2 * buf_bytes, stream);
+  LegScratch sc;
+  int rc = ovn_ws_layout(ctx, stream, &sc, (size_t)slice * max_act, 2, (size_t)0, (size_t)0);
   if (rc) return rc;
-  float* buf[2] = {reinterpret_cast<float*>(ctx->ws), reinterpret_cast<float*>(static_cast<char*>(ctx->ws) + buf_bytes)};
+  float* const* buf = sc.buf;
   const size_t in_elems = (size_t)ctx->in_h * ctx->in_w * ctx->in_c;
   const size_t feat_elems = (size_t)ctx->feat_w * OVN_FEAT_C;
   OVN_REQUIRE(ctx->leg.size() + 1 <= OVN_ACTMAX_SLOTS, OVN_ERR_STATE, "ovn_leg: too many leg layers");
@@ -456,14 +473,6 @@ static LegGeom leg_geom(const ovn_ctx* ctx) {
   return g;
 }
 
-static void scratch_overwritten(ovn_ctx* ctx) {   // the debug hooks of an earlier head call pointed into the scratch
-  ctx->dbg_o2 = ctx->dbg_o3 = nullptr;
-  ctx->dbg_partial = nullptr;
-  ctx->dbg_o2max = nullptr;
-  ctx->dbg_n = 0;
-  ctx->dbg_live = nullptr;
-}
-
 int ovn_leg_layer_count(ovn_ctx* ctx, int* layers) {
   OVN_REQUIRE(ctx && layers, OVN_ERR_ARG, "ovn_leg_layer_count: NULL argument");
   *layers = (int)ctx->leg.size();
@@ -524,15 +533,12 @@ int ovn_leg_backward(ovn_ctx* ctx, const float* images_dev, const float* acts_de
   const int nmax = (int)std::min(slice, n);
   size_t part_bytes = 0;
   for (int li = 0; li < L; ++li) part_bytes = std::max(part_bytes, ovn_leg_grad_part_bytes(ctx->leg[li], g.h[li], g.w[li], nmax));
-  const size_t buf_bytes = ((size_t)nmax * g.act_max * sizeof(float) + 255) & ~(size_t)255;
-  const size_t acc_bytes = ((size_t)g.params * sizeof(double) + 255) & ~(size_t)255;
-  int rc = ovn_ws_reserve(ctx, 2 * buf_bytes + acc_bytes + part_bytes, stream);
+  LegScratch sc;
+  int rc = ovn_ws_layout(ctx, stream, &sc, (size_t)nmax * g.act_max, 2, (size_t)g.params, part_bytes);
   if (rc) return rc;
   scratch_overwritten(ctx);
-  char* ws = static_cast<char*>(ctx->ws);
-  float* buf[2] = {reinterpret_cast<float*>(ws), reinterpret_cast<float*>(ws + buf_bytes)};
-  double* acc = reinterpret_cast<double*>(ws + 2 * buf_bytes);
-  double* part = reinterpret_cast<double*>(ws + 2 * buf_bytes + acc_bytes);
+  float* const* buf = sc.buf;
+  double *acc = sc.acc, *part = sc.part;
   OVN_HIP_CHECK(hipMemsetAsync(acc, 0, (size_t)g.params * sizeof(double), stream));
   std::vector<int64_t> act_off(L, 0), par_off(L, 0);
   for (int li = 1; li < L; ++li) {
@@ -573,15 +579,12 @@ int ovn_debug_conv_grad(ovn_ctx* ctx, int layer, const float* in_dev, const floa
   const int oh = (h - l.kh) / l.sh + 1, ow = (w - l.kw) / l.sw + 1;
   const long long out_elems = (long long)nb * oh * ow * l.cout;
   const int64_t kelems = (int64_t)l.K * l.cout;
-  const size_t buf_bytes = ((size_t)out_elems * sizeof(float) + 255) & ~(size_t)255;
-  const size_t acc_bytes = ((size_t)(kelems + l.cout) * sizeof(double) + 255) & ~(size_t)255;
-  int rc = ovn_ws_reserve(ctx, buf_bytes + acc_bytes + ovn_leg_grad_part_bytes(l, h, w, nb), stream);
+  LegScratch sc;
+  int rc = ovn_ws_layout(ctx, stream, &sc, (size_t)out_elems, 1, (size_t)(kelems + l.cout), ovn_leg_grad_part_bytes(l, h, w, nb));
   if (rc) return rc;
   scratch_overwritten(ctx);
-  char* ws = static_cast<char*>(ctx->ws);
-  float* dym = reinterpret_cast<float*>(ws);
-  double* acc = reinterpret_cast<double*>(ws + buf_bytes);
-  double* part = reinterpret_cast<double*>(ws + buf_bytes + acc_bytes);
+  float* dym = sc.buf[0];
+  double *acc = sc.acc, *part = sc.part;
   OVN_HIP_CHECK(hipMemsetAsync(acc, 0, (size_t)(kelems + l.cout) * sizeof(double), stream));
   OvnProfScope ps(ctx, OVN_K_LEG, stream);
   rc = ovn_leg_mask_forward(dout_dev, out_dev, dym, out_elems, stream);
@@ -701,12 +704,12 @@ static int delta_head_run_f32(ovn_ctx* ctx, const float* feats_l, const int32_t*
   chunk = chunk < 1 ? 1 : (chunk > 1024 ? 1024 : chunk);
   if (ctx->head_chunk < chunk) chunk = ctx->head_chunk;
   const int64_t cmax = n < chunk ? n : chunk;
-  int rc = ovn_ws_reserve(ctx, (size_t)cmax * pb + 1024, stream);
+  OvnDeltaF32Scratch sc;        // one chunk of either route
+  OvnDeltaGenericScratch gsc;
+  int rc = fusedc12 ? ovn_ws_layout(ctx, stream, &sc, cmax, ctx->head_g, ctx->head_width_split && ctx->head_mode == 1)
+                    : ovn_ws_layout(ctx, stream, &gsc, cmax, fw, ctx->head_g);
   if (rc) return rc;
-  ctx->dbg_o2 = ctx->dbg_o3 = nullptr;
-  ctx->dbg_partial = nullptr;
-  ctx->dbg_o2max = nullptr;
-  ctx->dbg_n = 0;
+  scratch_overwritten(ctx);
   OvnFork fk(ctx, stream);
   if (corr_mode == 2) {   // ONE launch for all n pairs, beside the Delta kernels when the pipeline asks for a side stream
     hipStream_t ys = stream;
@@ -729,21 +732,42 @@ static int delta_head_run_f32(ovn_ctx* ctx, const float* feats_l, const int32_t*
       if (rc) return rc;
     }
     if (fusedc12) {   // times its Delta, c_conv3 and Dense kernels separately
-      rc = ovn_delta_forward(ctx, fl, li, feats_r, ri, np, ctx->ws, overlap + p0, logit ? logit + p0 : nullptr, stream);
+      rc = ovn_delta_forward(ctx, fl, li, feats_r, ri, np, sc, overlap + p0, logit ? logit + p0 : nullptr, stream);
     } else {
       OvnProfScope ps(ctx, OVN_K_DELTA, stream);
-      rc = ovn_delta_generic_forward(ctx, fl, li, feats_r, ri, np, ctx->ws, overlap + p0, logit ? logit + p0 : nullptr, stream);
+      rc = ovn_delta_generic_forward(ctx, fl, li, feats_r, ri, np, gsc, overlap + p0, logit ? logit + p0 : nullptr, stream);
     }
     if (rc) return rc;
   }
-  if (fusedc12 && n > 0 && n <= chunk) {   // one chunk: its o2 / o3 regions (ovn_delta_forward) hold every pair for the test hook
-    const size_t o2w = (size_t)n * ctx->head_g * ctx->head_g * OVN_C2_OUT * sizeof(float);
-    ctx->dbg_o2 = static_cast<const float*>(ctx->ws);
-    ctx->dbg_o3 = reinterpret_cast<const float*>(static_cast<const char*>(ctx->ws) + ((o2w + 255) & ~(size_t)255));
+  if (fusedc12 && n > 0 && n <= chunk) {   // one chunk: its o2 / o3 regions hold every pair for the test hook
+    ctx->dbg_o2 = sc.o2;
+    ctx->dbg_o3 = sc.o3;
     ctx->dbg_n = n;
   }
   return fk.join();
 }
+
+// Scratch of a split-operand head call (f16x3 / bf16x3 at 360 columns): o2 of a chunk | o3 of the chunk (bf16x3) or its Dense partials
+// (f16x3) | nsub blocks of sub_bytes, sub-chunk j's OvnDeltaSubScratch in block j | the segment state of a segmented pass
+struct HeadScratch {
+  float *o2 = nullptr, *o3 = nullptr;
+  char* sub = nullptr;
+  size_t sub_bytes = 0;
+  OvnDeltaSegScratch seg;
+  HeadScratch() = default;
+  HeadScratch(OvnCarver& c, int64_t cmax, bool fused, int64_t sub_pairs, int nsub, bool per_pair_right, int nseg) {
+    o2 = c.take<float>((size_t)cmax * OVN_G * OVN_G * OVN_C2_OUT);
+    o3 = c.take<float>((size_t)cmax * (fused ? OVN_DENSE_PARTIALS : OVN_DENSE_IN));
+    sub_bytes = ovn_delta_f16x3_scratch_bytes((int)sub_pairs, per_pair_right);
+    sub = c.take<char>(sub_bytes * nsub);
+    if (nseg) seg = OvnDeltaSegScratch(c, nseg);
+  }
+  // the block of sub-chunk j, laid out for its np <= sub_pairs pairs
+  OvnDeltaSubScratch sub_chunk(int j, int np, bool per_pair_right) const {
+    OvnCarver c(sub + (size_t)j * sub_bytes);
+    return OvnDeltaSubScratch(c, np, per_pair_right);
+  }
+};
 
 // Delta (overlap) head on n pairs [+ one of the correlation heads]; shared by ovn_heads, ovn_delta_head and ovn_heads_spectral.
 //   corr_mode 0: none; 1: direct form on the feature volumes (per chunk, on the caller's stream, as ovn_heads always did);
@@ -772,16 +796,12 @@ static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lid
   int64_t sub = (!seg && ctx->head_sub > 0 && ctx->head_sub < cmax) ? ctx->head_sub : cmax;
   const int nsub_max = (int)((cmax + sub - 1) / sub);
   const int nstreams = (nsub_max > 1 && ctx->head_streams > 1) ? 2 : 1;
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t o2_bytes = al((size_t)cmax * o2_elems * sizeof(float));
   // second scratch region: o3 (n,22,22,256) in bf16x3 mode; in f16x3 mode c_conv3 and the Dense layer are one kernel and only
-  // OVN_DENSE_PARTIALS partial sums per pair (band x half of the output channels x half of the m-tiles) leave it
-  const size_t o3_bytes = fused ? al((size_t)cmax * OVN_DENSE_PARTIALS * sizeof(float)) : al((size_t)cmax * o3_elems * sizeof(float));
-  // per-pair scales, packed volumes, linear terms and the c_conv1 rows between the two Delta kernels (2.9 MB per pair), one
-  // self-contained block per sub-chunk
-  const size_t sc_sub = al(ovn_delta_f16x3_scratch_bytes((int)sub, ridx != nullptr));
-  const size_t seg_bytes = seg ? al(ovn_delta_f16x3_seg_bytes(seg->nseg)) : 0;
-  int rc = ovn_ws_reserve(ctx, o2_bytes + o3_bytes + sc_sub * nsub_max + seg_bytes, stream);
+  // OVN_DENSE_PARTIALS partial sums per pair (band x half of the output channels x half of the m-tiles) leave it.  Then per-pair
+  // scales, packed volumes, linear terms and the c_conv1 rows between the two Delta kernels (2.9 MB per pair), one self-contained
+  // block per sub-chunk
+  HeadScratch hs;
+  int rc = ovn_ws_layout(ctx, stream, &hs, cmax, fused, sub, nsub_max, ridx != nullptr, seg ? seg->nseg : 0);
   if (rc) return rc;
   if (fused && ctx->c3_arrived_n < chunk) {   // arrival counters of the fused c_conv3 + Dense kernel, one per pair of a chunk (sized
     OVN_HIP_CHECK(hipStreamSynchronize(stream));   // by the chunk, not by this call: a growing sweep must not re-allocate): zeroed
@@ -792,9 +812,7 @@ static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lid
     OVN_HIP_CHECK(hipMemsetAsync(ctx->c3_arrived, 0, (size_t)chunk * sizeof(unsigned), stream));
     ctx->c3_arrived_n = chunk;
   }
-  float* o2 = reinterpret_cast<float*>(ctx->ws);
-  float* o3 = reinterpret_cast<float*>(static_cast<char*>(ctx->ws) + o2_bytes);
-  char* dscratch = static_cast<char*>(ctx->ws) + o2_bytes + o3_bytes;
+  float *o2 = hs.o2, *o3 = hs.o3;
   ctx->dbg_o2max = nullptr;
   ctx->dbg_o2 = o2;
   ctx->dbg_o3 = fused ? nullptr : o3;
@@ -813,7 +831,7 @@ static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lid
     // a small 1-vs-N sweep in one sub-chunk: the query's right-volume term of the Delta head rides in the yaw launch (csrc/delta_a2.h)
     a2_in_yaw = ridx == nullptr && n <= OVN_A2_IN_YAW_MAX_PAIRS && n <= chunk && ys == stream && nsub_max == 1;
     rc = ovn_corr_spectral_forward(ctx, spec_l, lidx, spec_r, ridx, (int)n, yaw, corr, ys, a2_in_yaw ? feats_r : nullptr,
-                                   a2_in_yaw ? ovn_delta_f16x3_a2raw(dscratch, (int)n) : nullptr);
+                                   a2_in_yaw ? hs.sub_chunk(0, (int)n, false).a2raw : nullptr);
     if (rc) return rc;
   }
   for (int64_t c0 = 0; c0 < n; c0 += chunk) {
@@ -838,16 +856,17 @@ static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lid
       const int32_t* li = lidx ? lidx + p0 : nullptr;
       const int32_t* ri = ridx ? ridx + p0 : nullptr;
       float* o2s = o2 + (size_t)q0 * o2_elems;
+      const OvnDeltaSubScratch ds = hs.sub_chunk(j, np, ridx != nullptr);
       if (fused) {   // times its prepare kernels, the contraction kernel and c_conv2 separately
-        unsigned* o2max = nullptr;
+        unsigned* o2max = ds.o2max;
         float* part = o3 + (size_t)q0 * OVN_DENSE_PARTIALS;
         OvnSegPass sp{};
         if (seg) {
           sp = *seg;
           sp.pseg += p0;
-          sp.scratch = dscratch + sc_sub * nsub_max;
+          sp.state = hs.seg;
         }
-        rc = ovn_delta_c12_f16x3_forward(ctx, fl, li, feats_r, ri, np, dscratch + (size_t)j * sc_sub, &o2max, o2s, st, (int)(p0 & 0x3fffffff),
+        rc = ovn_delta_c12_f16x3_forward(ctx, fl, li, feats_r, ri, np, ds, o2s, st, (int)(p0 & 0x3fffffff),
                                           // a cache row belongs to a CANDIDATE: without an index list it moves with the feature pointer
                                           dcache_l ? (lidx ? dcache_l : dcache_l + (size_t)p0 * OVN_DELTA_CACHE_ELEMS) : nullptr, a2_in_yaw,
                                           seg ? &sp : nullptr);
@@ -859,7 +878,7 @@ static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lid
         }
       } else {   // bf16x3: times its prepare kernels, the contraction kernel and c_conv2 separately
         float* o3s = o3 + (size_t)q0 * o3_elems;
-        rc = ovn_delta_c12_bf16x3_forward(ctx, fl, li, feats_r, ri, np, dscratch + (size_t)j * sc_sub, o2s, st, (int)(p0 & 0x3fffffff),
+        rc = ovn_delta_c12_bf16x3_forward(ctx, fl, li, feats_r, ri, np, ds, o2s, st, (int)(p0 & 0x3fffffff),
                                           a2_in_yaw);
         if (rc) return rc;
         int oh = 0, ow = 0;
@@ -1043,8 +1062,19 @@ int ovn_top_k(ovn_ctx* ctx, const float* overlap, const int32_t* yaw, const int3
 
 // ---- segmented batches ---------------------------------------------------------------------------------------------------------
 // The host segment table (offsets, and the query of every segment when it is given) is validated, staged in a context-owned pinned
-// buffer and copied to seg_dev on `stream`; `extra` more bytes of device space follow it (the indexed route's right index).  The
-// pinned buffer is rewritten only after the previous call's copy has left it (seg_ev).
+// buffer and copied to seg_dev on `stream`; device space for the per-pair right index and segment index follows it.  The pinned buffer
+// is rewritten only after the previous call's copy has left it (seg_ev).
+struct SegTable {   // ONE layout for the pinned mirror and for seg_dev: offsets (B + 1) | query_idx (B) | ridx (n) | pseg (n), each optional but the first
+  int64_t* offs = nullptr;
+  int32_t *qidx = nullptr, *ridx = nullptr, *pseg = nullptr;
+  SegTable() = default;
+  SegTable(OvnCarver& c, int64_t B, bool with_qidx, int64_t n_ridx, int64_t n_pseg) {
+    offs = c.take<int64_t>((size_t)B + 1);
+    qidx = with_qidx ? c.take<int32_t>((size_t)B) : nullptr;
+    ridx = n_ridx ? c.take<int32_t>((size_t)n_ridx) : nullptr;
+    pseg = n_pseg ? c.take<int32_t>((size_t)n_pseg) : nullptr;
+  }
+};
 static const char* seg_offsets_error(const int64_t* offs, int64_t B, int64_t* n_out) {
   if (B < 0 || B >= (1ll << 31)) return "B outside [0, 2^31)";
   if (!offs) return "seg_offsets is NULL";
@@ -1056,11 +1086,10 @@ static const char* seg_offsets_error(const int64_t* offs, int64_t B, int64_t* n_
   return nullptr;
 }
 
-static int seg_stage(ovn_ctx* ctx, const int64_t* offs, const int32_t* qidx, int64_t B, size_t extra, hipStream_t stream,
-                     int64_t** offs_dev, int32_t** qidx_dev, void** extra_dev) {
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t ob = al((size_t)(B + 1) * sizeof(int64_t)), qb = qidx ? al((size_t)B * sizeof(int32_t)) : 0;
-  const size_t need = ob + qb + al(extra);
+static int seg_stage(ovn_ctx* ctx, const int64_t* offs, const int32_t* qidx, int64_t B, int64_t n_ridx, int64_t n_pseg,
+                     hipStream_t stream, SegTable* dev) {
+  const size_t staged = ovn_scratch_bytes<SegTable>(B, qidx != nullptr, (int64_t)0, (int64_t)0);   // what the host fills in
+  const size_t need = ovn_scratch_bytes<SegTable>(B, qidx != nullptr, n_ridx, n_pseg);
   if (!ctx->seg_ev) {
     OVN_HIP_CHECK(hipEventCreateWithFlags(&ctx->seg_ev, hipEventDisableTiming));
     OVN_HIP_CHECK(hipEventCreateWithFlags(&ctx->seg_done, hipEventDisableTiming));
@@ -1081,16 +1110,14 @@ static int seg_stage(ovn_ctx* ctx, const int64_t* offs, const int32_t* qidx, int
     OVN_HIP_CHECK(hipHostMalloc(&ctx->seg_host, want, hipHostMallocDefault));
     ctx->seg_cap = want;
   }
-  char* h = static_cast<char*>(ctx->seg_host);
-  memcpy(h, offs, (size_t)(B + 1) * sizeof(int64_t));
-  if (qidx) memcpy(h + ob, qidx, (size_t)B * sizeof(int32_t));
-  OVN_HIP_CHECK(hipMemcpyAsync(ctx->seg_dev, h, ob + qb, hipMemcpyHostToDevice, stream));
+  OvnCarver hc(ctx->seg_host), dc(ctx->seg_dev);
+  const SegTable h(hc, B, qidx != nullptr, n_ridx, n_pseg);
+  *dev = SegTable(dc, B, qidx != nullptr, n_ridx, n_pseg);
+  memcpy(h.offs, offs, (size_t)(B + 1) * sizeof(int64_t));
+  if (qidx) memcpy(h.qidx, qidx, (size_t)B * sizeof(int32_t));
+  OVN_HIP_CHECK(hipMemcpyAsync(ctx->seg_dev, ctx->seg_host, staged, hipMemcpyHostToDevice, stream));
   OVN_HIP_CHECK(hipEventRecord(ctx->seg_ev, stream));
   ctx->seg_ev_pending = true;
-  char* d = static_cast<char*>(ctx->seg_dev);
-  *offs_dev = reinterpret_cast<int64_t*>(d);
-  if (qidx_dev) *qidx_dev = qidx ? reinterpret_cast<int32_t*>(d + ob) : nullptr;
-  if (extra_dev) *extra_dev = d + ob + qb;
   return OVN_OK;
 }
 
@@ -1132,15 +1159,11 @@ int ovn_heads_segments(ovn_ctx* ctx, const float* feats_pool, const float* spec_
   // the Delta cache rows, as in its 1-vs-N sweep).  Every other mode and geometry -- and f16x3 with compaction off, whose 1-vs-N walk
   // is the 128-channel walk of an indexed pair -- is the same per pair in the indexed form: one indexed pass over all pairs.
   const bool segmented = ctx->head_mode == 1 && fw == OVN_FEAT_W && ctx->head_s == OVN_S && ctx->head_compact;
-  int64_t* offs_dev = nullptr;
-  int32_t* qidx_dev = nullptr;
-  void* rbuf = nullptr;
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t rbytes = al((size_t)n * sizeof(int32_t));
-  int rc = seg_stage(ctx, seg_offsets, query_idx, B, rbytes * (segmented ? 2 : 1), stream, &offs_dev, &qidx_dev, &rbuf);
+  SegTable tab;
+  int rc = seg_stage(ctx, seg_offsets, query_idx, B, n, segmented ? n : 0, stream, &tab);
   if (rc) return rc;
-  int32_t* ridx = static_cast<int32_t*>(rbuf);
-  int32_t* pseg = segmented ? reinterpret_cast<int32_t*>(static_cast<char*>(rbuf) + rbytes) : nullptr;
+  int64_t* offs_dev = tab.offs;
+  int32_t *qidx_dev = tab.qidx, *ridx = tab.ridx, *pseg = tab.pseg;
   {
     OvnProfScope ps(ctx, OVN_K_DELTA_PREP, stream);
     rc = ovn_segment_ridx_forward(offs_dev, qidx_dev, (int)B, (int)n, ridx, pseg, stream);
@@ -1159,7 +1182,7 @@ int ovn_heads_segments(ovn_ctx* ctx, const float* feats_pool, const float* spec_
     int64_t p1 = std::min(n, p0 + ctx->head_chunk);
     if (seg_of(p1 - 1) - b0 + 1 > OVN_SEG_PASS_MAX) p1 = o[b0 + OVN_SEG_PASS_MAX];
     const int64_t np = p1 - p0;
-    OvnSegPass sp{pseg + p0, qidx_dev, offs_dev, (int)b0, (int)(seg_of(p1 - 1) - b0 + 1), nullptr};
+    OvnSegPass sp{pseg + p0, qidx_dev, offs_dev, (int)b0, (int)(seg_of(p1 - 1) - b0 + 1), {}};
     rc = delta_head_run(ctx, feats_pool, cand_idx + p0, feats_q, ridx + p0, np, overlap + p0, logit ? logit + p0 : nullptr, yaw + p0,
                         corr ? corr + (size_t)p0 * fw : nullptr, corr_mode, spec_pool, spec_q, dc, stream, &sp);
     if (rc) return rc;
@@ -1181,10 +1204,10 @@ int ovn_top_k_segments(ovn_ctx* ctx, const float* overlap, const int32_t* yaw, c
   OVN_REQUIRE(!misaligned(overlap, 4) && !misaligned(yaw, 4) && !misaligned(ids, 4), OVN_ERR_ARG,
               "ovn_top_k_segments: misaligned buffer");
   OVN_ON_DEVICE(ctx->device);
-  int64_t* offs_dev = nullptr;
-  int rc = seg_stage(ctx, seg_offsets, nullptr, B, 0, (hipStream_t)stream, &offs_dev, nullptr, nullptr);
+  SegTable tab;
+  int rc = seg_stage(ctx, seg_offsets, nullptr, B, 0, 0, (hipStream_t)stream, &tab);
   if (rc) return rc;
-  rc = ovn_top_k_segments_forward(overlap, yaw, ids, offs_dev, (int)B, k, threshold, out, (hipStream_t)stream);
+  rc = ovn_top_k_segments_forward(overlap, yaw, ids, tab.offs, (int)B, k, threshold, out, (hipStream_t)stream);
   return rc ? rc : seg_release(ctx, (hipStream_t)stream);
 }
 

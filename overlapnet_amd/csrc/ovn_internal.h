@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/ovn_hip.h"
+#include "ovn_scratch.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -320,7 +321,7 @@ struct ovn_ctx {
   const unsigned* dbg_live = nullptr;   // live-channel list of the most recent Delta sweep (NULL: it walked all 128 channels; reset
                                         // by every head call and with the scratch it points into)
   // segmented batches (ovn_heads_segments / ovn_top_k_segments): the host segment table staged in pinned memory and copied to
-  // seg_dev = [seg_offsets int64 (B + 1) | query_idx int32 (B) | per-pair right index int32 (n)]; seg_ev orders the reuse of seg_host
+  // seg_dev, both laid out by SegTable (ovn_api.hip: offsets | query_idx | per-pair right index | segment index); seg_ev orders the reuse of seg_host
   void* seg_host = nullptr;
   void* seg_dev = nullptr;
   size_t seg_cap = 0;
@@ -350,6 +351,19 @@ struct OvnProfScope {
 };
 
 int ovn_ws_reserve(ovn_ctx* ctx, size_t bytes, hipStream_t stream);
+// The scratch is about to be overwritten (or has moved): the debug hooks of an earlier head call pointed into it.  The ONE place that
+// clears them; ovn_ws_reserve calls it when the block moves, every call that reuses the block for something else calls it itself.
+void scratch_overwritten(ovn_ctx* ctx);
+// The scratch of a call, laid out by L (ovn_scratch.h) for the shape `a...`: measure, reserve exactly that, THEN place -- the reserve
+// may move the block, so nothing is carved before it.
+template <class L, class... A>
+int ovn_ws_layout(ovn_ctx* ctx, hipStream_t stream, L* out, const A&... a) {
+  int rc = ovn_ws_reserve(ctx, ovn_scratch_bytes<L>(a...), stream);
+  if (rc) return rc;
+  OvnCarver c(ctx->ws);
+  *out = L(c, a...);
+  return OVN_OK;
+}
 
 // ---- kernels' host launchers (each returns an OVN_* code) ------------------------------------------
 // conv_f32.hip
@@ -369,49 +383,77 @@ int ovn_conv_forward_f16x3(const OvnConvLayer& L, const float* in, int nb, int h
 int ovn_absmax_forward(const float* x, int n_scans, long long per_scan, unsigned* out_max, hipStream_t stream);
 
 // delta_head.hip: the fp32 Delta head at the context's feature width with conv1size 15 (fused fp32 MFMA DeltaLayer + c_conv1 +
-// c_conv2, generic c_conv3, Dense); scratch: n * ovn_delta_pair_bytes(G) + 512 bytes
+// c_conv2, generic c_conv3, Dense); scratch: an OvnDeltaF32Scratch for at least n pairs
 int ovn_delta_prepare_w1(const float* c1_kernel_dev, float** w1p_out, hipStream_t stream);
-size_t ovn_delta_pair_bytes(int G);
+struct OvnDeltaF32Scratch {   // o2 (n, G, G, 128) | o3 (n, G - 2, G - 2, 256) | the split route's per-pair scales (`split` only)
+  float *o2 = nullptr, *o3 = nullptr;
+  void* scales = nullptr;
+  OvnDeltaF32Scratch() = default;
+  OvnDeltaF32Scratch(OvnCarver& c, int64_t n, int G, bool split);
+};
+size_t ovn_delta_pair_bytes(int G);   // what a pair costs, unaligned: the chunk size of a head call derives from it
 int ovn_delta_forward(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx, int n,
-                      void* scratch, float* overlap, float* logit, hipStream_t stream);
+                      const OvnDeltaF32Scratch& scratch, float* overlap, float* logit, hipStream_t stream);
 // Dense(1) + sigmoid over dense_in floats per pair (fixed reduction order)
 int ovn_dense_sigmoid_forward(const ovn_ctx* ctx, const float* o3, int n, long long dense_in, float* overlap, float* logit,
                               hipStream_t stream);
 
-// delta_head_f16x3.hip.  `scratch` (ovn_delta_f16x3_scratch_bytes(n, ridx != NULL) bytes, caller-owned: 2.9 MB per pair) holds the
-// per-pair scales, both packed volumes, the linear terms and the c_conv1 min-term rows between the two kernels; *o2max_out points
-// at the per-pair maxima of the c_conv2 output inside it (input of ovn_c3_dense_forward).
+// delta_head_f16x3.hip.  An OvnDeltaSubScratch (caller-owned: 2.9 MB per pair) holds the per-pair scales, both packed volumes, the
+// linear terms and the c_conv1 min-term rows between the two kernels of a call on n pairs (one sub-chunk); its o2max, the per-pair
+// maxima of the c_conv2 output, is the input of ovn_c3_dense_forward.  The f16x3 and bf16x3 paths share it.
 int ovn_delta_prepare_f16x3(ovn_ctx* ctx, const float* c1_kernel_dev, const float* c1_bias_dev, const float* c2_kernel_dev,
                             hipStream_t stream);
-size_t ovn_delta_f16x3_scratch_bytes(int n, bool per_pair_right);
+struct OvnDeltaSubScratch {
+  f32x4* scales = nullptr;
+  unsigned *o2max = nullptr, *pl = nullptr, *pr = nullptr;
+  float *lin = nullptr, *a2raw = nullptr, *o1raw = nullptr;   // a2raw: one right volume, or n with per_pair_right (unused by a segmented pass)
+  void* desc = nullptr;                                       // n DeltaDesc
+  unsigned *qblock = nullptr, *live = nullptr;
+  _Float16* w1c = nullptr;
+  OvnDeltaSubScratch() = default;
+  OvnDeltaSubScratch(OvnCarver& c, int n, bool per_pair_right);
+};
+struct OvnDeltaSegScratch {   // per-segment query state of a segmented pass: A2raw, query block, live list, gathered W1 fragments
+  float* a2raw = nullptr;
+  unsigned *qblock = nullptr, *live = nullptr;
+  _Float16* w1c = nullptr;
+  OvnDeltaSegScratch() = default;
+  OvnDeltaSegScratch(OvnCarver& c, int nseg);
+};
+size_t ovn_delta_f16x3_scratch_bytes(int n, bool per_pair_right);   // = the size of an OvnDeltaSubScratch: a sub-chunk's block
 // A pass of ovn_heads_segments over the pairs of segments seg0 .. seg0 + nseg - 1 (f16x3, compaction on): pseg = the pass's first
-// pair's entry of the per-pair segment index, qidx / offs = the whole batch's query indices and offsets (device), scratch =
-// ovn_delta_f16x3_seg_bytes(nseg) bytes for the per-segment query state.  ridx must hold each pair's query index.
+// pair's entry of the per-pair segment index, qidx / offs = the whole batch's query indices and offsets (device), state = the
+// per-segment query state, laid out for nseg segments.  ridx must hold each pair's query index.
 struct OvnSegPass {
   const int32_t* pseg;
   const int32_t* qidx;
   const int64_t* offs;
   int seg0, nseg;
-  void* scratch;
+  OvnDeltaSegScratch state;
 };
-size_t ovn_delta_f16x3_seg_bytes(int nseg);
+size_t ovn_delta_f16x3_seg_bytes(int nseg);   // = the size of an OvnDeltaSegScratch
 int ovn_delta_c12_f16x3_forward(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r,
-                                const int32_t* ridx, int n, void* scratch, unsigned** o2max_out, float* o2, hipStream_t stream,
+                                const int32_t* ridx, int n, const OvnDeltaSubScratch& scratch, float* o2, hipStream_t stream,
                                 int pair0 = 0,    // pair0: index of the call's first pair in the sweep (rotation of the K walks)
                                 const float* dcache_l = nullptr,   // Delta cache rows of the left pool (ovn_delta_cache), 1-vs-N only
-                                bool a2_done = false,    // A2raw of the (single) right volume is already in the scratch (ovn_delta_f16x3_a2raw)
-                                const struct OvnSegPass* seg = nullptr);   // a segmented pass (ovn_heads_segments), see below
-float* ovn_delta_f16x3_a2raw(void* scratch, int n);
-// bf16x3 head mode: the same two-kernel path with the exact bf16 split (delta_head_f16x3.hip); same scratch size and A2raw location
+                                bool a2_done = false,    // A2raw of the (single) right volume is already in scratch.a2raw
+                                const struct OvnSegPass* seg = nullptr);   // a segmented pass (ovn_heads_segments), see above
+// bf16x3 head mode: the same two-kernel path with the exact bf16 split (delta_head_f16x3.hip) on the same scratch layout
 int ovn_delta_c12_bf16x3_forward(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx,
-                                 int n, void* scratch, float* o2, hipStream_t stream, int pair0, bool a2_done);
+                                 int n, const OvnDeltaSubScratch& scratch, float* o2, hipStream_t stream, int pair0, bool a2_done);
 int ovn_delta_cache_forward(ovn_ctx* ctx, const float* feats, int n, float* cache, hipStream_t stream);
 int ovn_delta_walk_stats(ovn_ctx* ctx, int32_t* out16, hipStream_t stream);
 
 // delta_head_generic.hip: the Delta head for any conv1size (fp32, generality path) at feature width ctx->feat_w
-size_t ovn_delta_generic_pair_bytes(int W, int G);
+struct OvnDeltaGenericScratch {   // out1 (n, W, G, 64) | o2 (n, G, G, 128) | o3 (n, G - 2, G - 2, 256)
+  float *out1 = nullptr, *o2 = nullptr, *o3 = nullptr;
+  OvnDeltaGenericScratch() = default;
+  OvnDeltaGenericScratch(OvnCarver& c, int64_t n, int W, int G);
+};
+size_t ovn_delta_generic_pair_bytes(int W, int G);   // the layout of ONE pair: the chunk sizes of the fp32 and training calls derive from it
 int ovn_delta_generic_forward(const ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r,
-                              const int32_t* ridx, int n, void* scratch, float* overlap, float* logit, hipStream_t stream);
+                              const int32_t* ridx, int n, const OvnDeltaGenericScratch& scratch, float* overlap, float* logit,
+                              hipStream_t stream);
 int ovn_delta_generic_c1_wide(const ovn_ctx* ctx, int FW, const float* feats_l, const int32_t* lidx, const float* feats_r,
                               const int32_t* ridx, int n, float* out1, hipStream_t stream);
 
@@ -443,7 +485,7 @@ int ovn_leg_layer_backward(const OvnConvLayer& L, const float* x, const float* d
                            double* acc_kernel, double* acc_bias, double* part, hipStream_t stream);
 
 // delta_head_w_f16x3.hip: DeltaLayer + c_conv1 + c_conv2 of ovn_delta_forward in f16x3 arithmetic at widths other than 360 (ovn_set_head_width_split with head
-// mode 1): o2 (n, G, G, 128) from n * ovn_delta_w_split_pair_bytes() bytes of per-pair scales (16-byte aligned scratch)
+// mode 1): o2 (n, G, G, 128) from n * ovn_delta_w_split_pair_bytes() bytes of per-pair scales (OvnDeltaF32Scratch::scales)
 size_t ovn_delta_w_split_pair_bytes();
 int ovn_delta_w_split_c12_forward(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx,
                                   int n, void* scales, float* o2, hipStream_t stream);

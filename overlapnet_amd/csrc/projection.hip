@@ -340,6 +340,20 @@ ProjGeom make_geom(int H, int W, double fov_up_deg, double fov_down_deg, double 
   return gm;
 }
 
+// Scratch of a projection call: the key image | ovn_project's kept-point numbering | ovn_project_semantic's keep masks | the scatter
+// blocks' kept counts; a region the call does not need has no elements and a NULL pointer
+struct ProjScratch {
+  unsigned long long *keys = nullptr, *masks = nullptr;
+  int *local_idx = nullptr, *block_cnt = nullptr;
+  ProjScratch() = default;
+  ProjScratch(OvnCarver& c, size_t npix, size_t lidx_elems, size_t mask_words, size_t block_cnts) {
+    keys = c.take<unsigned long long>(npix);
+    local_idx = lidx_elems ? c.take<int>(lidx_elems) : nullptr;
+    masks = mask_words ? c.take<unsigned long long>(mask_words) : nullptr;
+    block_cnt = block_cnts ? c.take<int>(block_cnts) : nullptr;
+  }
+};
+
 }  // namespace
 
 int ovn_projection_angles_forward(const float* points, int64_t n, int H, int W, double fov_up_deg, double fov_down_deg,
@@ -367,23 +381,13 @@ int ovn_project_forward(ovn_ctx* ctx, const float* points, const int64_t* offset
   const long long npix = HW * n_scans;
   const int blocks_per_scan = (int)((max_points + PB - 1) / PB) > 0 ? (int)((max_points + PB - 1) / PB) : 1;
 
-  // scratch carve-up (all 16-byte aligned): the key image, and for the index image the kept-point numbering
-  size_t off = 0;
-  auto carve = [&](size_t bytes) {
-    size_t o = off;
-    off += (bytes + 255) & ~(size_t)255;
-    return o;
-  };
-  const size_t o_keys = carve((size_t)npix * 8);
-  const size_t o_lidx = idx ? carve((size_t)n_scans * (size_t)max_points * 4 + 16) : 0;
-  const size_t o_bcnt = idx ? carve((size_t)n_scans * blocks_per_scan * 4) : 0;
-  int rc = ovn_ws_reserve(ctx, off, stream);
+  // scratch: the key image, and for the index image the kept-point numbering ([scan][point]) and the blocks' kept counts
+  ProjScratch sc;
+  int rc = ovn_ws_layout(ctx, stream, &sc, (size_t)npix, idx ? (size_t)n_scans * (size_t)max_points + 4 : (size_t)0, (size_t)0,
+                         idx ? (size_t)n_scans * blocks_per_scan : (size_t)0);
   if (rc) return rc;
-  char* ws = static_cast<char*>(ctx->ws);
-  unsigned long long* keys = reinterpret_cast<unsigned long long*>(ws + o_keys);
-  int* block_cnt = idx ? reinterpret_cast<int*>(ws + o_bcnt) : nullptr;
-  // local_idx is indexed [scan][point]: n_scans * max_points ints
-  int* local_idx = idx ? reinterpret_cast<int*>(ws + o_lidx) : nullptr;
+  unsigned long long* keys = sc.keys;
+  int *block_cnt = sc.block_cnt, *local_idx = sc.local_idx;
 
   hipLaunchKernelGGL(proj_clear_kernel, dim3(1024), dim3(256), 0, stream, keys, npix);
   if (max_points > 0) {
@@ -654,21 +658,12 @@ int ovn_project_semantic_forward(ovn_ctx* ctx, const float* points, const int64_
   const long long npix = HW * n_scans;
   const int blocks_per_scan = (int)((max_points + PB - 1) / PB) > 0 ? (int)((max_points + PB - 1) / PB) : 1;
   const bool ranks = idx || sem_idx || want_p;
-  size_t off = 0;
-  auto carve = [&](size_t bytes) {
-    size_t o = off;
-    off += (bytes + 255) & ~(size_t)255;
-    return o;
-  };
-  const size_t o_keys = carve((size_t)npix * 8);
-  const size_t o_mask = ranks ? carve((size_t)2 * n_scans * blocks_per_scan * MASK_WORDS * 8) : 0;
-  const size_t o_bcnt = ranks ? carve((size_t)2 * n_scans * blocks_per_scan * 4) : 0;
-  int rc = ovn_ws_reserve(ctx, off, stream);
+  ProjScratch sc;
+  int rc = ovn_ws_layout(ctx, stream, &sc, (size_t)npix, (size_t)0, ranks ? (size_t)2 * n_scans * blocks_per_scan * MASK_WORDS : (size_t)0,
+                         ranks ? (size_t)2 * n_scans * blocks_per_scan : (size_t)0);
   if (rc) return rc;
-  char* ws = static_cast<char*>(ctx->ws);
-  unsigned long long* keys = reinterpret_cast<unsigned long long*>(ws + o_keys);
-  unsigned long long* masks = ranks ? reinterpret_cast<unsigned long long*>(ws + o_mask) : nullptr;
-  int* block_cnt = ranks ? reinterpret_cast<int*>(ws + o_bcnt) : nullptr;
+  unsigned long long *keys = sc.keys, *masks = sc.masks;
+  int* block_cnt = sc.block_cnt;
   const long long* offs = reinterpret_cast<const long long*>(offsets);
 
   hipLaunchKernelGGL(proj_clear_kernel, dim3(1024), dim3(256), 0, stream, keys, npix);
