@@ -392,6 +392,30 @@ int ovn_top_k(ovn_ctx* ctx, const float* overlap_dev, const int32_t* yaw_dev, co
 int ovn_top_k_segments(ovn_ctx* ctx, const float* overlap_dev, const int32_t* yaw_dev, const int32_t* ids_dev,
                        const int64_t* seg_offsets, int64_t B, int k, float threshold, int32_t* out_dev, void* stream);
 
+/* Verification of loop-closure candidates: projective point-to-plane ICP on the images ovn_project writes, a batch of pairs in one
+ * launch (csrc/icp_register.hip; the algorithm is stated step by step in DESIGN.md, "Loop-closure verification").
+ *   vertex_dev (n_scans,H,W,4), normal_dev (n_scans,H,W,3), range_dev (n_scans,H,W) f32: ovn_project's outputs (-1 = empty pixel /
+ *       no normal); fov_up_deg / fov_down_deg / max_range: the values they were projected with
+ *   src_idx_dev, tgt_idx_dev  (n_pairs) int32: pair p registers scan src_idx[p] onto scan tgt_idx[p]
+ *   init_pose_dev  (n_pairs,4,4) f64 row-major: T0, source-frame points into the target frame (the yaw head's Rz)
+ *   iterations 0..1000 solve passes (no early exit) + one pass without a solve that describes the returned pose;
+ *   max_dist [m], cos_min, huber [m]: correspondence gates and the Huber threshold, all > 0; min_inliers >= 0
+ *   pose_dev   (n_pairs,4,4) f64: the registered pose
+ *   stats_dev  (n_pairs,8) f64: status (0 ok; 1 stopped: a pass found fewer than min_inliers correspondences or the 6x6 Cholesky
+ *              met a non-positive / non-finite pivot -- the pose is the last one the pair had, T0 bit for bit when no step was
+ *              taken; 2 an index outside [0, n_scans): pose = T0, nothing read), passes solved, inliers, valid source pixels,
+ *              rms = sqrt(sum w r^2 / inliers) (0 without inliers), |v| and |omega| of the last step, 0 (reserved)
+ *   system_dev (n_pairs,28) f64 or NULL: the first pass's A (upper triangle by rows, 21), b (6) and inlier count -- validation output
+ * The pose and every sum are fp64, the per-point arithmetic fp32.  No atomics: a pair's outputs have the same bits alone or in
+ * any batch, at any position, on every call.  With a finite T0 nothing non-finite is ever written (a T0
+ * holding a NaN or Inf matches no point and comes back as it is, status 1).  n_pairs == 0 is a no-op.  OVN_ERR_ARG for
+ * iterations outside 0..1000, a gate that is not > 0, min_inliers < 0, H*W > 2^31 - 1, a NULL buffer. */
+int ovn_icp_register(ovn_ctx* ctx, const float* vertex_dev, const float* normal_dev, const float* range_dev, int n_scans,
+                     int proj_h, int proj_w, double fov_up_deg, double fov_down_deg, double max_range,
+                     const int32_t* src_idx_dev, const int32_t* tgt_idx_dev, int64_t n_pairs, const double* init_pose_dev,
+                     int iterations, double max_dist, double cos_min, double huber, int min_inliers, double* pose_dev,
+                     double* stats_dev, double* system_dev, void* stream);
+
 /* Spherical projection + normals for a batch of scans (src/utils/utils.py:59-134 range_projection and
  * :137-186 gen_normal_map; the drivers gen_depth_data.py:24-46 etc. loop over files and call these).
  *   points_dev   concatenated (x,y,z,intensity) float32 points of all scans

@@ -1060,6 +1060,29 @@ int ovn_top_k(ovn_ctx* ctx, const float* overlap, const int32_t* yaw, const int3
   return ovn_top_k_forward(overlap, yaw, ids, (int)n, k, threshold, (int)index_offset, out, (hipStream_t)stream);
 }
 
+int ovn_icp_register(ovn_ctx* ctx, const float* vertex, const float* normal, const float* range, int n_scans, int proj_h, int proj_w,
+                     double fov_up_deg, double fov_down_deg, double max_range, const int32_t* src_idx, const int32_t* tgt_idx,
+                     int64_t n_pairs, const double* init_pose, int iterations, double max_dist, double cos_min, double huber,
+                     int min_inliers, double* pose, double* stats, double* system, void* stream) {
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_icp_register: ctx is NULL");
+  OVN_REQUIRE(n_scans >= 0 && proj_h > 0 && proj_w > 0 && n_pairs >= 0 && n_pairs < (1ll << 31), OVN_ERR_ARG,
+              "ovn_icp_register: bad sizes");
+  OVN_REQUIRE((int64_t)proj_h * proj_w <= 2147483647ll, OVN_ERR_ARG, "ovn_icp_register: H*W exceeds 2^31 - 1");
+  OVN_REQUIRE(iterations >= 0 && iterations <= 1000, OVN_ERR_ARG, "ovn_icp_register: iterations must be in 0..1000");
+  OVN_REQUIRE(max_dist > 0.0 && cos_min > 0.0 && huber > 0.0 && max_range > 0.0, OVN_ERR_ARG,
+              "ovn_icp_register: max_dist, cos_min, huber and max_range must be > 0");
+  OVN_REQUIRE(max_dist < 1e18 && cos_min <= 1.0 && huber < 1e18, OVN_ERR_ARG, "ovn_icp_register: gate out of range");
+  OVN_REQUIRE(min_inliers >= 0, OVN_ERR_ARG, "ovn_icp_register: min_inliers < 0");
+  OVN_REQUIRE(fabs(fov_up_deg) + fabs(fov_down_deg) > 0.0, OVN_ERR_ARG, "ovn_icp_register: empty vertical field of view");
+  if (n_pairs == 0) return OVN_OK;
+  OVN_REQUIRE(src_idx && tgt_idx && init_pose && pose && stats, OVN_ERR_ARG, "ovn_icp_register: NULL buffer");
+  OVN_REQUIRE(n_scans == 0 || (vertex && normal && range), OVN_ERR_ARG, "ovn_icp_register: NULL image buffer");
+  OVN_ON_DEVICE(ctx->device);
+  return ovn_icp_register_forward(vertex, normal, range, n_scans, proj_h, proj_w, fov_up_deg, fov_down_deg, max_range, src_idx,
+                                  tgt_idx, (int)n_pairs, init_pose, iterations, max_dist, cos_min, huber, min_inliers, pose, stats,
+                                  system, (hipStream_t)stream);
+}
+
 // ---- segmented batches ---------------------------------------------------------------------------------------------------------
 // The host segment table (offsets, and the query of every segment when it is given) is validated, staged in a context-owned pinned
 // buffer and copied to seg_dev on `stream`; device space for the per-pair right index and segment index follows it.  The pinned buffer

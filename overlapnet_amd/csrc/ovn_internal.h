@@ -540,6 +540,11 @@ int ovn_top_k_segments_forward(const float* overlap, const int32_t* yaw, const i
 // ridx[p] = qidx[b] and pseg[p] = b (pseg may be NULL) for offs[b] <= p < offs[b + 1]: the per-pair query and segment of a batch
 int ovn_segment_ridx_forward(const int64_t* offs_dev, const int32_t* qidx_dev, int B, int n, int32_t* ridx, int32_t* pseg,
                              hipStream_t stream);
+// icp_register.hip: one workgroup per pair, all passes in one launch
+int ovn_icp_register_forward(const float* vertex, const float* normal, const float* range, int n_scans, int H, int W,
+                             double fov_up_deg, double fov_down_deg, double max_range, const int32_t* src_idx, const int32_t* tgt_idx,
+                             int n_pairs, const double* init_pose, int iterations, double max_dist, double cos_min, double huber,
+                             int min_inliers, double* pose, double* stats, double* system, hipStream_t stream);
 // a2_feats_r / a2raw non-NULL (small 1-vs-N sweeps): the launch also computes A2raw of that right volume (delta_a2.h) in extra workgroups
 int ovn_corr_spectral_forward(ovn_ctx* ctx, const float* spec_l, const int32_t* lidx, const float* spec_r,
                               const int32_t* ridx, int n, int32_t* yaw, float* corr, hipStream_t stream,

@@ -984,6 +984,39 @@ class OvnEngine:
                        "ovn_normals")
         return out
 
+    def icp_register(self, vertex: torch.Tensor, normal: torch.Tensor, rng: torch.Tensor, src_idx: torch.Tensor,
+                     tgt_idx: torch.Tensor, init_pose: torch.Tensor, iterations: int = 20, max_dist: float = 2.0,
+                     cos_min: float = 0.8, huber: float = 0.2, min_inliers: int = 64, fov_up: float = 3.0, fov_down: float = -25.0,
+                     max_range: float = 50.0, want_system: bool = False):
+        """Projective point-to-plane ICP on `project`'s images, every pair in one launch (`ovn_icp_register`).  vertex (n,H,W,4),
+        normal (n,H,W,3), rng (n,H,W) f32; src_idx / tgt_idx (P) int32; init_pose (P,4,4) f64, source-frame points into the target
+        frame.  Returns (pose (P,4,4) f64, stats (P,8) f64: status, passes solved, inliers, valid source pixels, rms, |v| and
+        |omega| of the last step, 0) as device tensors, plus the first pass's normal equations (P,28) with want_system=True."""
+        for t, what, dt in ((vertex, "vertex", torch.float32), (normal, "normal", torch.float32), (rng, "range", torch.float32),
+                            (src_idx, "src_idx", torch.int32), (tgt_idx, "tgt_idx", torch.int32),
+                            (init_pose, "init_pose", torch.float64)):
+            if t.device != self.device or t.dtype != dt or not t.is_contiguous():
+                raise _lib.OvnError("icp_register(): %s must be a contiguous %s tensor on %s" % (what, dt, self.device))
+        if rng.dim() != 3:
+            raise _lib.OvnError("icp_register(): range must be (n, H, W), got %s" % (tuple(rng.shape),))
+        n, h, w = (int(v) for v in rng.shape)
+        if tuple(vertex.shape) != (n, h, w, 4) or tuple(normal.shape) != (n, h, w, 3):
+            raise _lib.OvnError("icp_register(): vertex %s / normal %s do not match range %s"
+                                % (tuple(vertex.shape), tuple(normal.shape), tuple(rng.shape)))
+        p = int(src_idx.numel())
+        if int(tgt_idx.numel()) != p or tuple(init_pose.shape) != (p, 4, 4):
+            raise _lib.OvnError("icp_register(): %d source indices, %d target indices, init_pose %s"
+                                % (p, int(tgt_idx.numel()), tuple(init_pose.shape)))
+        pose = torch.empty((p, 4, 4), dtype=torch.float64, device=self.device)
+        stats = torch.empty((p, 8), dtype=torch.float64, device=self.device)
+        system = torch.empty((p, 28), dtype=torch.float64, device=self.device) if want_system else None
+        with self._dev():
+            _lib.check(self.lib.ovn_icp_register(self._h, _ptr(vertex), _ptr(normal), _ptr(rng), n, h, w, float(fov_up),
+                                                 float(fov_down), float(max_range), _ptr(src_idx), _ptr(tgt_idx), p, _ptr(init_pose),
+                                                 int(iterations), float(max_dist), float(cos_min), float(huber), int(min_inliers),
+                                                 _ptr(pose), _ptr(stats), _ptr(system), self._stream()), "ovn_icp_register")
+        return (pose, stats, system) if want_system else (pose, stats)
+
     def projection_angles(self, points: torch.Tensor, proj_h: int = 64, proj_w: int = 900, fov_up: float = 3.0,
                           fov_down: float = -25.0, max_range: float = 50.0):
         """(yaw, pitch, pixel) of every point of an (n, 4) float32 device tensor as the projection kernel evaluates them

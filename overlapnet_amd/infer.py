@@ -946,6 +946,39 @@ class Infer():
     self._start_ahead(current_frame_id)     # next frame's files, copy and leg in the shadow of the kernels just enqueued
     return [(i, ov, yw) for i, ov, yw, above in decode_top_k(rec) if overlap_thres is None or above]
 
+  def verify_top_k(self, current_frame_id, reference_frame_id, k=5, overlap_thres=0.3, min_fitness=None, max_rms=None,
+                   **icp_params):
+    """ Addition to the reference API: `infer_top_k` plus the geometric check a back end makes before it accepts a loop closure --
+        every candidate's raw scan is registered onto the current frame's by a range-image ICP on the GPU (`ovn_icp_register`, all
+        candidates in one launch), started from the yaw the network gave (registration.pose_from_network_yaw: Rz(-yaw degrees) at
+        width 360, because `Infer` puts the reference on the first leg).  Returns, best overlap first, (reference frame id,
+        overlap, yaw, pose, fitness, rms, accepted): pose (4,4) takes the reference scan's points into the current scan's frame, fitness = inliers / valid pixels of the reference scan, rms of the point-to-plane residuals [m].
+        `accepted` is None unless `min_fitness` and / or `max_rms` is given (then: the registration finished and meets them); no
+        default threshold is chosen here.  Needs config['scan_folder']: the .npy cue files hold no vertex image.
+        The scans are read and projected on every call, with the projection parameters `Infer` uses everywhere (fov 3 / -25
+        degrees, max_range 50 m: the defaults of `register_scans`).  **icp_params: iterations, max_dist, cos_min, huber, min_inliers. """
+    from . import registration as G
+    if self._world > 1:
+      raise Exception('Infer.verify_top_k: not available on a sharded Infer; use a single-rank Infer (world %d)' % self._world)
+    if self._scan_folder is None:
+      raise ValueError("Infer.verify_top_k needs config['scan_folder']: the registration runs on the raw scans' vertex images, "
+                       "which the .npy cue files do not hold")
+    cands = self.infer_top_k(current_frame_id, reference_frame_id, k=k, overlap_thres=overlap_thres)
+    if not cands:
+      return []
+    clouds = []
+    for fid in [current_frame_id] + [c[0] for c in cands]:
+      f = self._scan_path(str(fid).zfill(6))
+      try:
+        clouds.append(np.fromfile(f, dtype=np.float32).reshape((-1, 4)))
+      except (IOError, OSError):
+        raise Exception('Could not read scan file %s' % f)
+    pairs = [(i + 1, 0) for i in range(len(cands))]                    # source: the candidate, target: the current frame
+    init = [G.pose_from_network_yaw(c[2], self.feat_w) for c in cands]
+    h, w = int(self.inputShape[0]), int(self.inputShape[1])
+    regs = G.register_scans(self.engine, clouds, pairs, init, proj_H=h, proj_W=w, **icp_params)
+    return [(fid, ov, yw, r.pose, r.fitness, r.rms, G.accept(r, min_fitness, max_rms)) for (fid, ov, yw), r in zip(cands, regs)]
+
   def infer_multiple(self, current_frame_id, reference_frame_id):
     """ Loop closing: current frame vs old frames (infer.py:162-203).  The current frame's feature
         volume is computed and appended (index == frame id); older ones must already be cached. """
