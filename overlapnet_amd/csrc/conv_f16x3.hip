@@ -14,8 +14,6 @@
 
 #include "ovn_internal.h"
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
@@ -36,19 +34,6 @@ struct ConvArgsB {
   long long M;
   int relu;
 };
-
-// (s d0, s d1) -> hi, lo as packed fp16 pairs.  hi = fp16_rtz (v_cvt_pkrtz_f16_f32: one instruction per pair), lo = fp16_rne of the
-// exact remainder, through v_fma_mixlo/hi_f16 (`one` = 1.0f in a register keeps the compiler from folding the fma into a subtraction
-// that needs two more conversions, see delta_head_f16x3.hip).
-__device__ __forceinline__ void split_pair_f16(float d0, float d1, float s, float one, unsigned& hi_pk, unsigned& lo_pk) {
-  const float x0 = d0 * s, x1 = d1 * s;
-  const f16x2 h = __builtin_bit_cast(f16x2, __builtin_amdgcn_cvt_pkrtz(x0, x1));
-  f16x2 l;
-  l[0] = (_Float16)__builtin_fmaf(x0, one, -(float)h[0]);
-  l[1] = (_Float16)__builtin_fmaf(x1, one, -(float)h[1]);
-  hi_pk = __builtin_bit_cast(unsigned, h);
-  lo_pk = __builtin_bit_cast(unsigned, l);
-}
 
 // Scaled fp16 hi/lo fragments (f16x3 arithmetic), same fragment order: sw * W = hi + lo, both rounded to nearest.
 __global__ void conv_prep_f16_kernel(const float* __restrict__ w, _Float16* __restrict__ wp, int K, int nkc, int Cout, float sw) {
@@ -229,14 +214,12 @@ __device__ __forceinline__ void conv_mfma_f16x3_body(const ConvArgsB& a, float o
 #pragma unroll
     for (int r = 0; r < A_SLOTS; ++r) {
       const int slot = tid + r * NTHREADS;
-      unsigned h0, h1, h2, h3, l0, l1, l2, l3;
-      split_pair_f16(areg[r][0][0], areg[r][0][1], s_row[r], one, h0, l0);
-      split_pair_f16(areg[r][0][2], areg[r][0][3], s_row[r], one, h1, l1);
-      split_pair_f16(areg[r][1][0], areg[r][1][1], s_row[r], one, h2, l2);
-      split_pair_f16(areg[r][1][2], areg[r][1][3], s_row[r], one, h3, l3);
+      f16x4 h0, h1, l0, l1;
+      ovn_split_f16(areg[r][0], s_row[r], one, h0, l0);
+      ovn_split_f16(areg[r][1], s_row[r], one, h1, l1);
       const int off = (slot >> 2) * A_STRIDE + 8 * (slot & 3);
-      *reinterpret_cast<u32x4*>(&Ah[buf * ATILE + off]) = (u32x4){h0, h1, h2, h3};
-      *reinterpret_cast<u32x4*>(&Al[buf * ATILE + off]) = (u32x4){l0, l1, l2, l3};
+      *reinterpret_cast<f16x8*>(&Ah[buf * ATILE + off]) = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
+      *reinterpret_cast<f16x8*>(&Al[buf * ATILE + off]) = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
     }
 #pragma unroll
     for (int r = 0; r < B_PER_THREAD; ++r) {
@@ -465,7 +448,7 @@ int ovn_conv_forward_f16x3(const OvnConvLayer& L, const float* in, int nb, int h
   if (a.M == 0) return OVN_OK;
   {  // the leg's layer shapes: input strip resident in LDS (conv_strip.hip), for EVERY call size -- same per-accumulator summation
      // order as the generic kernel below and per-scan scales in both, so which of the two runs never shows in the result
-    const int took = ovn_conv_strip_try(L, in, nb, nb, h, w, out, in_max, out_max, stream);
+    const int took = ovn_conv_strip_try(L, in, nb, h, w, out, in_max, out_max, stream);
     if (took < 0) return -took;
     if (took > 0) return OVN_OK;
   }

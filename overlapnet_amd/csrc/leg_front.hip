@@ -13,10 +13,6 @@
 // intermediate tile is a power of two taken from the tile itself (like leg_tail.hip), so a scan's result depends on that scan alone.
 #include "ovn_internal.h"
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
 // FRONT_ABL (timing-only builds of tools/experiments/front_ablate.sh, never the product): 1 strip of constants instead of the global
 // loads, 2 no stage A MFMAs, 4 no stage B MFMAs, 8 no output stores, 16 no strip staging at all, 32 no intermediate-tile exchange
 #ifndef FRONT_ABL
@@ -171,28 +167,13 @@ __global__ __launch_bounds__(NTHR, 2) void leg_front_kernel(FrontArgs a) {
     float m = 0.f;
 #pragma unroll
     for (int u = 0; u < ITERS; ++u) m = fmaxf(m, fmaxf(fmaxf(fabsf(v[u][0]), fabsf(v[u][1])), fmaxf(fabsf(v[u][2]), fabsf(v[u][3]))));
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_down(m, off, 64));
-    if (lane == 0) wg_red[wave] = m;
-    __syncthreads();
-    m = wg_red[0];
-#pragma unroll
-    for (int w = 1; w < NWF; ++w) m = fmaxf(m, wg_red[w]);
-    s_in = ovn_pow2_scale_for(m);
+    s_in = ovn_pow2_scale_for(ovn_wg_max_all<NWF>(m, wg_red));
 #pragma unroll
     for (int u = 0; u < ITERS; ++u) {
       const int i = tid + u * NTHR;
       if (i < TOTAL) {
         f16x4 h, l;
-#pragma unroll
-        for (int e = 0; e < 4; e += 2) {
-          const float x0f = v[u][e] * s_in, x1f = v[u][e + 1] * s_in;
-          const f16x2 hp = __builtin_bit_cast(f16x2, __builtin_amdgcn_cvt_pkrtz(x0f, x1f));
-          h[e] = hp[0];
-          h[e + 1] = hp[1];
-          l[e] = (_Float16)__builtin_fmaf(x0f, one, -(float)hp[0]);
-          l[e + 1] = (_Float16)__builtin_fmaf(x1f, one, -(float)hp[1]);
-        }
+        ovn_split_f16(v[u], s_in, one, h, l);
         *reinterpret_cast<f16x4*>(sh + 4 * i) = h;           // [row][pix][4] is the linear order of i
         *reinterpret_cast<f16x4*>(sl + 4 * i) = l;
       }
@@ -250,13 +231,8 @@ __global__ __launch_bounds__(NTHR, 2) void leg_front_kernel(FrontArgs a) {
   }
   FRONT_LOAD_B2(0, 0)
   FRONT_LOAD_B2(1, 1)
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_down(amax, off, 64));
-  if (lane == 0) wg_red[8 + wave] = amax;
-  __syncthreads();   // every wave has finished reading the input strip
-  amax = wg_red[8];
-#pragma unroll
-  for (int w = 1; w < NWF; ++w) amax = fmaxf(amax, wg_red[8 + w]);
+  amax = ovn_wg_max_all<NWF>(amax, wg_red + 8);   // words of their own (the first maximum's may still be being read); its barrier:
+                                                  // every wave has finished reading the input strip
   const float s_mid = ovn_pow2_scale_for(amax);
   // intermediate tile -> LDS as [row][pixel][16 channels] hi / lo: lane = channel lrow of pixels 4 g .. 4 g + 3 of each m-tile
 #pragma unroll
@@ -267,15 +243,13 @@ __global__ __launch_bounds__(NTHR, 2) void leg_front_kernel(FrontArgs a) {
       for (int ry = 0; ry < R1; ++ry) {
 #pragma unroll
         for (int r = 0; r < 4; r += 2) {
-          const float x0f = va[c][ry][r] * s_mid, x1f = va[c][ry][r + 1] * s_mid;
-          const f16x2 hp = __builtin_bit_cast(f16x2, __builtin_amdgcn_cvt_pkrtz(x0f, x1f));
-          const _Float16 l0 = (_Float16)__builtin_fmaf(x0f, one, -(float)hp[0]);
-          const _Float16 l1 = (_Float16)__builtin_fmaf(x1f, one, -(float)hp[1]);
+          f16x2 hp, lp;
+          ovn_split_f16(va[c][ry][r], va[c][ry][r + 1], s_mid, one, hp, lp);
           const int o = (ry * PIXM + 16 * col + 4 * g + r) * C1 + lrow;
           mh[o] = hp[0];
           mh[o + C1] = hp[1];
-          ml[o] = l0;
-          ml[o + C1] = l1;
+          ml[o] = lp[0];
+          ml[o + C1] = lp[1];
         }
       }
     }

@@ -17,9 +17,6 @@
 
 #include "ovn_internal.h"
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
 namespace {
 
 constexpr int NLAY = 6;
@@ -41,14 +38,6 @@ struct TailArgs {
   float one;          // 1.0f (keeps v_fma_mix selectable, see conv_f16x3.hip)
   int win;            // input width (396)
 };
-
-__device__ __forceinline__ void split2(float x0, float x1, float one, _Float16& h0, _Float16& h1, _Float16& l0, _Float16& l1) {
-  const f16x2 hp = __builtin_bit_cast(f16x2, __builtin_amdgcn_cvt_pkrtz(x0, x1));
-  h0 = hp[0];
-  h1 = hp[1];
-  l0 = (_Float16)__builtin_fmaf(x0, one, -(float)hp[0]);
-  l1 = (_Float16)__builtin_fmaf(x1, one, -(float)hp[1]);
-}
 
 // K steps 0 .. RING - 2 of a layer's weights -> the ring slots of the same numbers (n-tiles 2 wn, 2 wn + 1 of this wave)
 template <int RING>
@@ -168,6 +157,8 @@ __device__ __forceinline__ float tail_layer(const _Float16* ih, const _Float16* 
       }
     return 1.0f;
   }
+  // ovn_wg_max_all written out, here and in the kernel below: through the helper this kernel, which sits at its 128-register
+  // budget, spills 28 / 32 B per lane instead of 20
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) vmax = fmaxf(vmax, __shfl_down(vmax, off, 64));
   if (lane == 0) red[wave] = vmax;
@@ -187,12 +178,12 @@ __device__ __forceinline__ float tail_layer(const _Float16* ih, const _Float16* 
       for (int r = 0; r < 4; r += 2) {
         const int p = 16 * (wm + 2 * i) + 4 * g + r;
         if (p < PIXP - 1) {   // rows past WOUT are never read by a valid output of the next layer; keep the stores inside the plane
-          _Float16 h0, h1, l0, l1;
-          split2(acc[i][j][r] * s_out, acc[i][j][r + 1] * s_out, one, h0, h1, l0, l1);
-          dh[p * 8] = h0;
-          dh[(p + 1) * 8] = h1;
-          dl[p * 8] = l0;
-          dl[(p + 1) * 8] = l1;
+          f16x2 h, l;
+          ovn_split_f16(acc[i][j][r], acc[i][j][r + 1], s_out, one, h, l);
+          dh[p * 8] = h[0];
+          dh[(p + 1) * 8] = h[1];
+          dl[p * 8] = l[0];
+          dl[(p + 1) * 8] = l[1];
         }
       }
     }
@@ -252,13 +243,11 @@ __global__ __launch_bounds__(512, 4) void leg_tail_kernel(TailArgs a) {
     if (i < TOTAL) {
       const int pix = i / Q;
       const int c = 4 * (i - pix * Q);
-      _Float16 h[4], l[4];
-      split2(v[k][0] * s0, v[k][1] * s0, a.one, h[0], h[1], l[0], l[1]);
-      split2(v[k][2] * s0, v[k][3] * s0, a.one, h[2], h[3], l[2], l[3]);
+      f16x4 h, l;
+      ovn_split_f16(v[k], s0, a.one, h, l);
       const int o = (c >> 3) * PLANE + pix * 8 + (c & 7);
-      typedef _Float16 f16x4v __attribute__((ext_vector_type(4)));
-      *reinterpret_cast<f16x4v*>(b0h + o) = (f16x4v){h[0], h[1], h[2], h[3]};
-      *reinterpret_cast<f16x4v*>(b0l + o) = (f16x4v){l[0], l[1], l[2], l[3]};
+      *reinterpret_cast<f16x4*>(b0h + o) = h;
+      *reinterpret_cast<f16x4*>(b0l + o) = l;
     }
   }
   __syncthreads();

@@ -404,7 +404,7 @@ int ovn_leg(ovn_ctx* ctx, const float* images_dev, int64_t n, float* features_de
       // and every call size runs the same kernels, so a scan's feature volume does not depend on the batch it is computed in
       // (the first layer's kernel at C = 4 and the fused tail take the maximum of their own strip / tile instead)
       OVN_HIP_CHECK(hipMemsetAsync(ctx->actmax, 0, (ctx->leg.size() + 1) * (size_t)slice * OVN_ACTMAX_STRIDE * sizeof(unsigned), stream));
-      const bool own = (reinterpret_cast<uintptr_t>(cur) & 15) == 0 && ovn_conv_strip_own_scale(ctx->leg[0], n, h, w);
+      const bool own = (reinterpret_cast<uintptr_t>(cur) & 15) == 0 && ovn_conv_strip_own_scale(ctx->leg[0], h, w);
       if (!own) {
         OvnProfScope ps(ctx, OVN_K_LEG, stream);
         rc = ovn_absmax_forward(cur, nb, (long long)in_elems, ctx->actmax, stream);

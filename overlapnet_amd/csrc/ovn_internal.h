@@ -113,6 +113,48 @@ __device__ __forceinline__ void ovn_fold_absmax_wg(float vmax, unsigned* word, f
     if (m > 0.f && bits > __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(word, bits);
   }
 }
+
+// The largest of a workgroup's per-thread values, returned to EVERY thread (a strip or tile that takes its scale from its own
+// maximum): wave shuffle reduction, one word of `red` per wave, ONE barrier, every thread reads all NWAVES words.  `red` is NWAVES
+// floats of LDS that nothing else uses from the call until a later barrier: whoever writes them next -- a second maximum through
+// the same words, or the data `red` was borrowed from -- puts that barrier first.  Every thread of the workgroup must call it.
+template <int NWAVES>
+__device__ __forceinline__ float ovn_wg_max_all(float m, float* red) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_down(m, off, 64));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+  __syncthreads();
+  m = red[0];
+#pragma unroll
+  for (int w = 1; w < NWAVES; ++w) m = fmaxf(m, red[w]);
+  return m;
+}
+
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+
+// The leg's scaled hi/lo split: (s d0, s d1) -> hi = fp16_rtz (v_cvt_pkrtz_f16_f32: one instruction per pair), lo = fp16_rne of the
+// exact remainder, through v_fma_mixlo/hi_f16 (`one` = 1.0f in a register keeps the compiler from folding the fma into a subtraction
+// that needs two more conversions, see delta_head_f16x3.hip).  The Delta head, c3_dense.hip and corr_spectral.hip split under
+// arithmetic policies of their own and do not use it.
+__device__ __forceinline__ void ovn_split_f16(float d0, float d1, float s, float one, f16x2& hi, f16x2& lo) {
+  const float x0 = d0 * s, x1 = d1 * s;
+  hi = __builtin_bit_cast(f16x2, __builtin_amdgcn_cvt_pkrtz(x0, x1));
+  lo[0] = (_Float16)__builtin_fmaf(x0, one, -(float)hi[0]);
+  lo[1] = (_Float16)__builtin_fmaf(x1, one, -(float)hi[1]);
+}
+__device__ __forceinline__ void ovn_split_f16(f32x4 d, float s, float one, f16x4& hi, f16x4& lo) {
+#pragma unroll
+  for (int e = 0; e < 4; e += 2) {
+    f16x2 h, l;
+    ovn_split_f16(d[e], d[e + 1], s, one, h, l);
+    hi[e] = h[0];
+    hi[e + 1] = h[1];
+    lo[e] = l[0];
+    lo[e + 1] = l[1];
+  }
+}
 #endif
 
 // ---- normalisation of the correlation head's inputs (NormalizedCorrelation2D normalize=..., ovn_set_corr_normalization) ----------
@@ -498,12 +540,12 @@ int ovn_corr_forward(const float* feats_l, const int32_t* lidx, const float* fea
 // corr_spectral.hip
 int ovn_spectral_prepare(ovn_ctx* ctx, hipStream_t stream);
 int ovn_spectrum_forward(ovn_ctx* ctx, const float* feats, int n, float* spectra, hipStream_t stream);
-// conv_strip.hip: LDS-resident strip kernels for the 3 x KW / stride (2,1) leg layers with 64 outputs (f16x3 mode)
-// call_nb: scans of the whole call this slice belongs to (kernel choice is per call, not per slice)
-bool ovn_conv_strip_own_scale(const OvnConvLayer& L, long long call_nb, int h, int w);
+// conv_strip.hip: LDS-resident strip kernels for the leg layer shapes of its table (f16x3 mode); the three look a layer up in that
+// one table, so `matches` and a 16-byte aligned input imply that `try` launches
+bool ovn_conv_strip_own_scale(const OvnConvLayer& L, int h, int w);
 bool ovn_conv_strip_matches(const OvnConvLayer& L, int h, int w);
-int ovn_conv_strip_try(const OvnConvLayer& L, const float* in, int nb, long long call_nb, int h, int w, float* out,
-                       const unsigned* in_max, unsigned* out_max, hipStream_t stream);
+int ovn_conv_strip_try(const OvnConvLayer& L, const float* in, int nb, int h, int w, float* out, const unsigned* in_max,
+                       unsigned* out_max, hipStream_t stream);
 
 // leg_front.hip: s_conv1 + s_conv2 of the C = 4 network fused (f16x3): the 850 KB activation between them stays in LDS
 bool ovn_leg_front_matches(const ovn_ctx* ctx, size_t first, int h, int w);

@@ -18,7 +18,9 @@ from tests import _leg_grad_ref as L
 from tools import synthetic as S
 
 SCAN_BLOCK = L.SCAN_BLOCK
-SMALL_NB = 4                 # conv_strip.hip: calls of at most this many scans take conv_strip_kernel, larger ones conv_strip2_kernel
+SMALL_NB = 4                 # conv_strip.hip: calls of at most this many scans take the narrow configuration of conv_strip_kernel (one
+                             # n-tile per wave, NTW = 1), larger ones the batched one (NTW = 2)
+STRIP_NARROW, STRIP_BATCHED = "conv_strip_kernel<NTW=1>", "conv_strip_kernel<NTW=2>"
 MIN_POSITIONS = 128          # conv_f16x3.hip: the generic f16x3 kernel needs this many output positions per image
 FEAT_W_TAIL = 360            # leg_tail.hip: the fused tail runs 360-column volumes only
 
@@ -62,6 +64,17 @@ FINALIZE_LAYER = _spec(1, 2, 128, 128, 1, 1)       # a whole "leg" of one layer 
 STRIP_LAYERS = [l for l in WT.leg_layers(4) if l.name in ("s_conv5", "s_conv8", "s_conv9", "s_conv10")]      # kw 9, 7, 5, 3
 STRIP_WIDTHS = {80: (80, 0), 81: (96, 15), 96: (96, 0), 97: (80, 63), 160: (80, 0)}       # output width -> (tile, padded pixels)
 S_CONV3 = WT.leg_layers(4)[2]
+CFG_3A = dict(S.REFERENCE_MODEL_CFG, additional_unsymmetric_layer3a=True)
+_BY_NAME = {l.name: l for l in WT.leg_layers(4, CFG_3A)}
+# the plane-layout strip layers with a narrow and a batched configuration, on inputs (h, w) of at least 128 output positions (the
+# generic kernel takes them too): layer, h, w, then what each input is there for
+STRIP_BITS = [(S_CONV3, 5, 150),               # 2 x 136: one full row pair; tiles 96 + 40 batched, 52 + 52 + 32 narrow
+              (S_CONV3, 7, 150),               # 3 x 136: the second row block has one row past the image (load and store guards)
+              (_BY_NAME["s_conv3a"], 7, 60),   # 3 x 49: batched tiles 48 + 1 (one m-tile, one valid pixel), narrow 32 + 17
+              (_BY_NAME["s_conv4"], 4, 100)]   # 2 x 92: batched tiles 80 + 12, narrow 32 + 32 + 28 (fragments read at their own step)
+# s_conv1 (C = 4) and s_conv2 registered alone, (h, w): the pixel-major strip kernel, which the fused front kernel keeps the shipped
+# leg away from.  5 x 23 output pixels in row blocks of 3 and 3 x 46 in row blocks of 2: the last block has rows past the image
+FRONT_ALONE = [(_BY_NAME["s_conv1"], 13, 60), (_BY_NAME["s_conv2"], 7, 60)]
 
 
 def layer_weights(l, seed=0):
@@ -84,6 +97,21 @@ def forward_input(l):
     scan are no multiple of 16: a tile spans two scans)."""
     _, _, h, w = forward_shape(l)
     rng = np.random.default_rng([7, l.kh, l.kw, l.cin, l.cout, l.sh, l.sw])
+    x = rng.normal(0.0, 1.0, (3, h, w, l.cin)).astype(np.float32)
+    x[1] = np.float32(300.0) * x[0]
+    return x
+
+
+def strip_bits_input(l, h, w, nb):
+    """nb = 2: two scans, scan 1 scaled by 300 (per-scan scales); nb = 6: the same two followed by four more."""
+    x = strip_input(l, w - l.kw + 1, nb=2, h=h)
+    x[1] *= np.float32(300.0)
+    return x if nb == 2 else np.concatenate([x, strip_input(l, w - l.kw + 1, nb=nb - 2, h=h)])
+
+
+def front_alone_input(l, h, w):
+    """Three scans; scan 1 is scan 0 times 300."""
+    rng = np.random.default_rng([13, l.kh, l.kw, l.cin, h, w])
     x = rng.normal(0.0, 1.0, (3, h, w, l.cin)).astype(np.float32)
     x[1] = np.float32(300.0) * x[0]
     return x
@@ -115,7 +143,8 @@ def has_pad16_fragments(l):
 
 
 def strip_kernel(l, nb, aligned=True):
-    """Name of the strip kernel ovn_conv_strip_try runs for this layer, or None when it declines."""
+    """Name of the strip kernel (for the plane-layout kernel: and which of its two kinds of configuration) ovn_conv_strip_try runs
+    for this layer, or None when it declines: the rows of STRIP_ROWS in conv_strip.hip."""
     if not aligned:
         return None
     g = (l.kh, l.kw, l.cin, l.cout, l.sh, l.sw)
@@ -124,9 +153,9 @@ def strip_kernel(l, nb, aligned=True):
     if l.sw != 1 or (l.kh > 1 and l.sh != 2) or (l.kh == 1 and l.sh != 1):
         return None
     if g[:4] in ((3, 15, 32, 64), (3, 12, 64, 64), (2, 9, 64, 128)):
-        return "conv_strip_kernel" if nb <= SMALL_NB else "conv_strip2_kernel"
+        return STRIP_NARROW if nb <= SMALL_NB else STRIP_BATCHED
     if g[:4] in ((1, 9, 128, 128), (1, 7, 128, 128), (1, 5, 128, 128), (1, 3, 128, 128)):
-        return "conv_strip_kernel"
+        return STRIP_NARROW
     return None
 
 

@@ -9,18 +9,20 @@ Every test prints its worst err / bound or err / T.
   1. `strides_layer1` [1, 1], [1, 2], [2, 1], with and without `additional_unsymmetric_layer3a`, at the smallest input that gives
      1 x 45, and INTEGRATION.md's 16 x 900 with [1, 2] -> 1 x 371.  There s_conv1 leaves the fused front kernels: ovn_absmax_forward,
      the generic f16x3 kernel with per-row scales, then the s_conv2 strip fed by the generic kernel's maxima.
-       whole leg and every layer alone against the bounds; a scan alone, in a batch of 6 (conv_strip2_kernel instead of
-       conv_strip_kernel for s_conv3 / 3a / 4) and next to a scan scaled by 300: the same bits; the training forward's last block
+       whole leg and every layer alone against the bounds; a scan alone, in a batch of 6 (the batched configuration of
+       conv_strip_kernel instead of the narrow one for s_conv3 / 3a / 4) and next to a scan scaled by 300: the same bits; the training forward's last block
        bitwise `engine.leg` under 'f32'; s_conv1 alone through ovn_debug_conv_grad ('few', 'odd', 'long'; with a row stride of 1
        every input row gets a gradient); the whole leg's backward pass at n = 1 and n = scan block + 1; `Infer` on 16 x 247.
   2. Single layers (kh, kw, cin, cout, sh, sw) registered alone through ovn_add_leg_layer: forward on three scans of 8 x 17 output
      pixels (M tiles span two scans, scan 1 = 300 x scan 0) in both precisions, backward on 'few' / 'odd' / 'long'.  Fewer than
      128 output positions: 'f32' runs, 'f16x3' returns OVN_ERR_ARG and leaves the output untouched; for a context's own input
-     size ovn_finalize refuses in f16x3, so ovn_leg never meets the rule.  Registration refusals.
+     size ovn_finalize refuses in f16x3, so ovn_leg never meets the rule.  Registration refusals.  The shipped s_conv1 / s_conv2
+     alone (conv_strip_small_kernel, which the fused front kernel keeps the shipped leg away from) with a row block past the image.
   3. s_conv5 / 8 / 9 / 10 alone at output widths 80, 81, 96, 97, 160 (80- and 96-pixel tiles, exact and padded) against the bound;
-     at 160, and for s_conv3 at nb = 2 and nb = 6, the strip kernels' output is BITWISE the generic kernel's (the same layer on a
-     view of the input 4 bytes into an allocation, which ovn_conv_strip_try declines): conv_strip_kernel, conv_strip2_kernel and
-     conv_mfma_f16x3_kernel give the same bits, which is what batch independence rests on."""
+     at 160, and for s_conv3 / s_conv3a / s_conv4 at nb = 2 and nb = 6 (full and partial row blocks and tiles), the strip kernel's
+     output is BITWISE the generic kernel's (the same layer on a view of the input 4 bytes into an allocation, which
+     ovn_conv_strip_try declines): conv_strip_kernel in its narrow (one n-tile per wave) and batched (two n-tiles per wave, two
+     rows per workgroup) configurations and conv_mfma_f16x3_kernel give the same bits, which is what batch independence rests on."""
 import numpy as np
 import pytest
 import torch
@@ -155,6 +157,29 @@ def test_single_layer_forward(l, layer_engines):
         le.set_leg_precision("f32")
 
 
+@pytest.mark.parametrize("l,h,wi", G.FRONT_ALONE, ids=[c[0].name for c in G.FRONT_ALONE])
+def test_front_layers_alone_forward(l, h, wi):
+    """The shipped s_conv1 (C = 4) and s_conv2 registered alone: conv_strip_small_kernel (s_conv1: scaled by its strip's own maximum),
+    with a last row block that reaches past the image, against the f16x3 bound; a scan alone has the bits it has in the batch.
+    (Not compared with the generic kernel: the K chunks are laid out differently, taps padded to 16, and s_conv1 scales by its
+    strip's maximum, so equal bits are not claimed.)"""
+    w = S.make_test_weights(4, seed=0)
+    le = G.LayerEngine(l, w)
+    try:
+        le.set_leg_precision("f16x3")
+        x = G.front_alone_input(l, h, wi)
+        ref, B = E.leg_layer_bound(x, w[l.name + "/kernel"], w[l.name + "/bias"], (l.sh, l.sw), modes=("f16x3",))
+        xt = _dev(x)
+        out = le.debug_conv(0, xt)
+        rt = E.ratio(out.cpu().numpy(), ref, B["f16x3"])
+        print("\n[%s alone %dx%d f16x3] worst err / bound: %.3g" % (l.name, h, wi, rt))
+        assert out.shape == (3,) + G.out_shape(l, h, wi) + (l.cout,) and rt <= 1.0, (l.name, rt)
+        for i in range(3):
+            assert torch.equal(le.debug_conv(0, xt[i:i + 1].contiguous()), out[i:i + 1]), "%s: scan %d alone" % (l.name, i)
+    finally:
+        le.close()
+
+
 @pytest.mark.parametrize("which", ("few", "odd", "long"))
 @pytest.mark.parametrize("l", G.SYNTH, ids=G.SYNTH_IDS)
 def test_single_layer_backward(l, which, layer_engines):
@@ -266,7 +291,7 @@ def _off4(x):
 
 
 def _strip_layer(l):
-    w = S.make_test_weights(4, seed=0)
+    w = S.make_test_weights(4, seed=0, model_cfg=G.CFG_3A if l.name == "s_conv3a" else None)
     return G.LayerEngine(l, w), w
 
 
@@ -293,24 +318,29 @@ def test_strip_tile_choice(l):
 
 @pytest.mark.parametrize("nb", (2, 6))
 def test_strip_kernels_give_the_generic_kernels_bits(nb):
-    """s_conv3 on 5 x 150: conv_strip_kernel (nb = 2) and conv_strip2_kernel (nb = 6) against conv_mfma_f16x3_kernel."""
-    l = G.S_CONV3
-    le, w = _strip_layer(l)
-    try:
-        le.set_leg_precision("f16x3")
-        x = G.strip_input(l, 150 - l.kw + 1, nb=nb, h=5)
-        assert x.shape == (nb, 5, 150, 32)
-        x[1] *= np.float32(300.0)                                      # per-scan scales
-        ref, B = E.leg_layer_bound(x, w[l.name + "/kernel"], w[l.name + "/bias"], (2, 1), modes=("f16x3",))
-        xt = _dev(x)
-        out = le.debug_conv(0, xt)
-        rt = E.ratio(out.cpu().numpy(), ref, B["f16x3"])
-        print("\n[s_conv3 5x150 nb %d] worst err / bound: %.3g" % (nb, rt))
-        assert out.shape == (nb, 2, 136, 64) and rt <= 1.0
-        generic = le.debug_conv(0, _off4(xt))
-        rg = E.ratio(generic.cpu().numpy(), ref, B["f16x3"])
-        print("[s_conv3 5x150 nb %d, generic kernel] worst err / bound: %.3g" % (nb, rg))
-        assert rg <= 1.0
-        assert torch.equal(generic, out), "nb = %d: the strip kernel and the generic kernel differ" % nb
-    finally:
-        le.close()
+    """Every input of G.STRIP_BITS (s_conv3 on 5 x 150 and 7 x 150, s_conv3a on 7 x 60, s_conv4 on 4 x 100): the narrow (nb = 2) and
+    the batched (nb = 6) configuration of conv_strip_kernel against the fp64 bound and, bitwise, against conv_mfma_f16x3_kernel;
+    scans 0 and 1 of the nb = 6 call have the bits of the nb = 2 call (narrow = batched)."""
+    for l, h, wi in G.STRIP_BITS:
+        le, w = _strip_layer(l)
+        tag = "%s %dx%d nb %d" % (l.name, h, wi, nb)
+        try:
+            le.set_leg_precision("f16x3")
+            x = G.strip_bits_input(l, h, wi, nb)
+            assert x.shape == (nb, h, wi, l.cin)
+            ref, B = E.leg_layer_bound(x, w[l.name + "/kernel"], w[l.name + "/bias"], (l.sh, l.sw), modes=("f16x3",))
+            xt = _dev(x)
+            out = le.debug_conv(0, xt)
+            rt = E.ratio(out.cpu().numpy(), ref, B["f16x3"])
+            print("\n[%s] worst err / bound: %.3g" % (tag, rt))
+            assert out.shape == (nb,) + G.out_shape(l, h, wi) + (l.cout,) and rt <= 1.0, (tag, rt)
+            generic = le.debug_conv(0, _off4(xt))
+            rg = E.ratio(generic.cpu().numpy(), ref, B["f16x3"])
+            print("[%s, generic kernel] worst err / bound: %.3g" % (tag, rg))
+            assert rg <= 1.0, (tag, rg)
+            assert torch.equal(generic, out), "%s: the strip kernel and the generic kernel differ" % tag
+            if nb > G.SMALL_NB:
+                narrow = le.debug_conv(0, xt[:2].contiguous())
+                assert torch.equal(out[:2], narrow), "%s: the batched and the narrow configuration differ" % tag
+        finally:
+            le.close()

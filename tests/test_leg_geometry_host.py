@@ -81,28 +81,38 @@ def test_dispatch_mirror_reaches_every_branch():
             path, absmax = G.leg_path_f16x3(layers, nb, h, w)
             k = dict(path)
             assert absmax and k["s_conv1"] == "conv_mfma_f16x3_kernel" and k["s_conv2"] == "conv_strip_small_kernel", (strides, a3)
-            mid = "conv_strip_kernel" if nb <= G.SMALL_NB else "conv_strip2_kernel"
+            mid = "conv_strip_kernel<NTW=1>" if nb <= G.SMALL_NB else "conv_strip_kernel<NTW=2>"
             assert k["s_conv3"] == k["s_conv4"] == mid and (not a3 or k["s_conv3a"] == mid)
-            assert all(k["s_conv%d" % i] == "conv_strip_kernel" for i in range(5, 11))
+            assert all(k["s_conv%d" % i] == "conv_strip_kernel<NTW=1>" for i in range(5, 11))
         assert G.forward_f16x3(layers[0], 2, h, w)["gather"] == "vec4"
         assert G.backward(layers[0], 1, h, w)["dgrad"] == ("plain",)
     shipped, absmax = G.leg_path_f16x3(WT.leg_layers(4, S.REFERENCE_MODEL_CFG), 2, 64, 900)
     assert not absmax and "conv_mfma_f16x3_kernel" not in dict(shipped).values()
-    assert [k for _, k in shipped] == ["leg_front"] * 2 + ["conv_strip_kernel"] * 3 + ["leg_tail"] * 6
+    assert [k for _, k in shipped] == ["leg_front"] * 2 + ["conv_strip_kernel<NTW=1>"] * 3 + ["leg_tail"] * 6
     # 4. the strip layers on both sides of the tile choice, and what the bit-identity cases compare
     assert [l.kw for l in G.STRIP_LAYERS] == [9, 7, 5, 3]
     for l in G.STRIP_LAYERS:
         for ow, want in G.STRIP_WIDTHS.items():
             assert G.strip_tile(ow) == want, (l.name, ow)
-            assert G.forward_f16x3(l, 2, 1, ow + l.kw - 1)["kernel"] == "conv_strip_kernel"
+            assert G.forward_f16x3(l, 2, 1, ow + l.kw - 1)["kernel"] == "conv_strip_kernel<NTW=1>"
         generic = G.forward_f16x3(l, 2, 1, 160 + l.kw - 1, aligned=False)
         assert generic["kernel"] == "conv_mfma_f16x3_kernel" and generic["gather"] == "scalar"
     assert {(tw, pad > 0) for tw, pad in G.STRIP_WIDTHS.values()} == {(80, False), (80, True), (96, False), (96, True)}
     assert G.strip_tile(160) == (80, 0) and G.pad_rows(160, 96) == 32 and G.strip_tile(81)[0] != G.strip_tile(80)[0]
     assert tuple(G.S_CONV3[1:7]) == (3, 15, 32, 64, 2, 1)
-    assert G.forward_f16x3(G.S_CONV3, 2, 5, 150)["kernel"] == "conv_strip_kernel"
-    assert G.forward_f16x3(G.S_CONV3, 6, 5, 150)["kernel"] == "conv_strip2_kernel"
+    assert G.forward_f16x3(G.S_CONV3, 2, 5, 150)["kernel"] == "conv_strip_kernel<NTW=1>"
+    assert G.forward_f16x3(G.S_CONV3, 6, 5, 150)["kernel"] == "conv_strip_kernel<NTW=2>"
     assert G.forward_f16x3(G.S_CONV3, 6, 5, 150, aligned=False)["kernel"] == "conv_mfma_f16x3_kernel"
+    assert [(l.name, G.out_shape(l, h, w)) for l, h, w in G.STRIP_BITS] == [("s_conv3", (2, 136)), ("s_conv3", (3, 136)),
+                                                                           ("s_conv3a", (3, 49)), ("s_conv4", (2, 92))]
+    for l, h, w in G.STRIP_BITS:
+        assert G.forward_f16x3(l, 2, h, w)["kernel"] == "conv_strip_kernel<NTW=1>"
+        assert G.forward_f16x3(l, 6, h, w)["kernel"] == "conv_strip_kernel<NTW=2>"
+        assert G.forward_f16x3(l, 6, h, w, aligned=False)["kernel"] == "conv_mfma_f16x3_kernel"
+        x2, x6 = G.strip_bits_input(l, h, w, 2), G.strip_bits_input(l, h, w, 6)
+        assert x6.shape == (6, h, w, l.cin) and np.array_equal(x6[:2], x2)
+    assert [(l.name, G.out_shape(l, h, w)) for l, h, w in G.FRONT_ALONE] == [("s_conv1", (5, 23)), ("s_conv2", (3, 46))]
+    assert all(G.strip_kernel(l, nb) == "conv_strip_small_kernel" for l, _, _ in G.FRONT_ALONE for nb in (1, 3))
     # 5. fewer than 128 output positions per image
     l = G.SMALL_LAYER
     assert G.out_shape(l, 11, 13) == (5, 5) and G.forward_f16x3(l, 1, 11, 13)["kernel"] == "refused"
