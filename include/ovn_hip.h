@@ -416,6 +416,68 @@ int ovn_icp_register(ovn_ctx* ctx, const float* vertex_dev, const float* normal_
                      int iterations, double max_dist, double cos_min, double huber, int min_inliers, double* pose_dev,
                      double* stats_dev, double* system_dev, void* stream);
 
+/* Overlap-based Monte Carlo localization: the particle filter around a 1-vs-U sweep over the frames of a map (csrc/mcl.hip; every
+ * formula is stated in DESIGN.md, "Localization").  Shared by the three calls:
+ *   particles_dev  (P,4) f32 rows x, y, theta, w; 16-byte aligned; 1 <= P <= OVN_MCL_MAX_PARTICLES; theta in (-pi, pi]
+ *   a map of M >= 1 frames, frame f with heading frame_yaw_dev[f] (f32, radians), and a grid of nx * ny cells (1 .. 2^31 - 1):
+ *   cell_frame_dev (ny*nx) i32, row iy * nx + ix = the frame of that cell or -1 (an entry >= M counts as -1)
+ *   seed, step     key and counter words of Philox4x32-10: key (seed lo, seed hi), counter (i, step lo, step hi, purpose)
+ * Every buffer is the caller's and lives on the context's device unless stated otherwise; nothing uses the context's scratch and no
+ * call uses an atomic: the same arguments give the same bits on every call.  Per-particle arithmetic is fp32 with every operation
+ * rounded on its own (no FMA contraction), sums are fp64 in an order that depends on P alone, the resampler is integer arithmetic.
+ * OVN_ERR_ARG before any launch, buffers untouched: P or n_out outside 1..OVN_MCL_MAX_PARTICLES; nx * ny outside 1..2^31 - 1 (or
+ * nx, ny < 1); M < 1; resolution, sigma_yaw_deg or overlap_min not > 0 (NaN included); eps_yaw outside [0, 1]; n_scores outside
+ * [0, M]; a NULL buffer (overlap_dev / yaw_dev may be NULL when n_scores == 0, spread_dev always); particles_dev,
+ * out_particles_dev, estimate_dev or a record that is not 16-byte aligned; out_particles_dev overlapping particles_dev.
+ *
+ * ovn_mcl_predict: motion, lookup, the distinct frames.  Host doubles dx, dy, dtheta (odometry in the robot frame) and sigma_x,
+ * sigma_y, sigma_theta are rounded to f32.  Particle i draws counter (i, step, 0): u = ((word >> 8) + 0.5) 2^-24 in f32,
+ * z_x = sqrt(-2 ln u0) cos(2 pi u1), z_y the same with sin, z_theta from u2, u3 with cos; dx' = dx + sigma_x z_x (dy', dtheta'
+ * alike); x += cos(theta) dx' - sin(theta) dy', y += sin(theta) dx' + cos(theta) dy', theta = wrap(theta + dtheta'); w untouched.
+ * Lookup: ix = floorf((x - (float)origin_x) * (float)(1 / resolution)), iy alike;
+ *   particle_frame_dev (P) i32: cell_frame[iy * nx + ix], or -1 outside the grid, for a non-finite x or y, or in an empty cell
+ *   frame_list_dev     (M) i32: the first U entries are the ascending ids of the frames at least one particle landed on
+ *   frame_slot_dev     (M) i32: a frame's position in that list, -1 if no particle landed on it
+ *   record_dev         4 x i32, 16-byte aligned: { U, particles off the map, 0, 1 }, ONE 16-byte store; may be pinned host memory
+ *                      (device-visible at the same address): all the host needs to read before it launches the sweep
+ * Three launches (clear M flags, P particles, one workgroup that compacts the flags in tiles of 1024 and counts). */
+#define OVN_MCL_MAX_PARTICLES 65536
+int ovn_mcl_predict(ovn_ctx* ctx, float* particles_dev, int n_particles, double dx, double dy, double dtheta, double sigma_x,
+                    double sigma_y, double sigma_theta, uint64_t seed, uint64_t step, const int32_t* cell_frame_dev, double origin_x,
+                    double origin_y, double resolution, int nx, int ny, int n_frames, int32_t* particle_frame_dev,
+                    int32_t* frame_slot_dev, int32_t* frame_list_dev, int32_t* record_dev, void* stream);
+
+/* ovn_mcl_update: observation model and estimate; two launches (weights: one particle per thread; maximum, rescale and sums: one
+ * workgroup).
+ *   particle_frame_dev, frame_slot_dev: as ovn_mcl_predict left them; frame_yaw_dev (M) f32
+ *   overlap_dev (n_scores) f32, yaw_dev (n_scores) i32: the sweep over frame_list[0 .. U) with the map frame on head-left and the
+ *   query on head-right (ovn_heads' outputs; yaw in degrees as Infer returns it); n_scores = U (a slot >= n_scores is off the map)
+ * A particle on frame f with slot s: d = (theta - frame_yaw[f]) (180 / pi) - yaw[s], d -= 360 rintf(d / 360);
+ * g = eps + (1 - eps) expf(-0.5 (d / sigma_yaw_deg)^2); o = overlap[s] > overlap_min ? overlap[s] : overlap_min (a NaN score gives
+ * overlap_min); w = (w o) g.  A particle off the map: w = (w overlap_min) eps.  Then every weight is multiplied by 2^-e, e the frexp
+ * exponent of the largest finite product, so that the maximum lands in [0.5, 1): exact.
+ *   estimate_dev (8) f64, 16-byte aligned: status, sum w, N_eff = (sum w)^2 / sum w^2, sum w x / sum w, sum w y / sum w,
+ *                atan2(sum w sin theta, sum w cos theta), position of the first maximum weight (NaN never wins), particles on the map
+ *   spread_dev   (1) f64 or NULL: sqrt(sum w ((x - mean x)^2 + (y - mean y)^2) / sum w)
+ * status 1: no product is finite and positive -- the weights stay the products, the estimate is { 1, 0, 0, 0, 0, 0, -1, on the map },
+ * the spread 0.  Otherwise 0. */
+int ovn_mcl_update(ovn_ctx* ctx, float* particles_dev, int n_particles, const int32_t* particle_frame_dev,
+                   const int32_t* frame_slot_dev, const float* frame_yaw_dev, int n_frames, const float* overlap_dev,
+                   const int32_t* yaw_dev, int n_scores, double sigma_yaw_deg, double eps_yaw, double overlap_min,
+                   double* estimate_dev, double* spread_dev, void* stream);
+
+/* ovn_mcl_resample: systematic resampling, exact in integers; one launch, one workgroup per 1024 particles, no word between them.
+ * q_i = floor(w_i 2^30) (0 for a negative or non-finite weight, 2^30 - 1 for a weight >= 1: ovn_mcl_update leaves every weight
+ * below 1), C the inclusive prefix sum of q in 64 bits,
+ * S = C[P - 1], r = (word0 | word1 << 32) mod S of counter (0, step, 1).  Output j of n_out copies ancestor a_j = the smallest a
+ * with C[a] n_out > j S + r (both sides < 2^62) with weight 1.0f.
+ *   out_particles_dev (n_out,4) f32, 16-byte aligned, not overlapping particles_dev; ancestor_dev (n_out) i32
+ *   record_dev        4 x i32, 16-byte aligned, ONE 16-byte store: { status, outputs written, 0, 1 }; may be pinned host memory
+ * status 1: S == 0 -- the record is { 1, 0, 0, 1 } and nothing else is written.  Ancestors are non-decreasing, a particle with
+ * q_i == 0 is never chosen, and particle i is copied floor or ceil of n_out q_i / S times. */
+int ovn_mcl_resample(ovn_ctx* ctx, const float* particles_dev, int n_particles, uint64_t seed, uint64_t step,
+                     float* out_particles_dev, int n_out, int32_t* ancestor_dev, int32_t* record_dev, void* stream);
+
 /* Spherical projection + normals for a batch of scans (src/utils/utils.py:59-134 range_projection and
  * :137-186 gen_normal_map; the drivers gen_depth_data.py:24-46 etc. loop over files and call these).
  *   points_dev   concatenated (x,y,z,intensity) float32 points of all scans

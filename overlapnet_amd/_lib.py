@@ -57,6 +57,12 @@ SIGNATURES = {
     "ovn_top_k": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int, C.c_float, C.c_int64, _vp, _vp]),
     "ovn_icp_register": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, _vp, _vp,
                                    C.c_int64, _vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp]),
+    "ovn_mcl_predict": (C.c_int, [_vp, _vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint64,
+                                  C.c_uint64, _vp, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp,
+                                  _vp]),
+    "ovn_mcl_update": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_double, _vp,
+                                 _vp, _vp]),
+    "ovn_mcl_resample": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64, C.c_uint64, _vp, C.c_int, _vp, _vp, _vp]),
     "ovn_heads_segments": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32p, _i64p, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp,
                                      _vp]),
     "ovn_top_k_segments": (C.c_int, [_vp, _vp, _vp, _vp, _i64p, C.c_int64, C.c_int, C.c_float, _vp, _vp]),

@@ -1083,6 +1083,69 @@ int ovn_icp_register(ovn_ctx* ctx, const float* vertex, const float* normal, con
                                   system, (hipStream_t)stream);
 }
 
+// ---- Monte Carlo localization (mcl.hip) ------------------------------------------------------------------------------------------
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+int ovn_mcl_predict(ovn_ctx* ctx, float* particles, int n_particles, double dx, double dy, double dtheta, double sigma_x, double sigma_y,
+                    double sigma_theta, uint64_t seed, uint64_t step, const int32_t* cell_frame, double origin_x, double origin_y,
+                    double resolution, int nx, int ny, int n_frames, int32_t* particle_frame, int32_t* frame_slot, int32_t* frame_list,
+                    int32_t* record, void* stream) {
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_mcl_predict: ctx is NULL");
+  OVN_REQUIRE(n_particles >= 1 && n_particles <= OVN_MCL_MAX_PARTICLES, OVN_ERR_ARG,
+              "ovn_mcl_predict: n_particles %d outside 1..%d", n_particles, OVN_MCL_MAX_PARTICLES);
+  OVN_REQUIRE(nx >= 1 && ny >= 1 && (int64_t)nx * ny <= 2147483647ll, OVN_ERR_ARG, "ovn_mcl_predict: grid %d x %d outside 1..2^31 - 1 cells",
+              nx, ny);
+  OVN_REQUIRE(n_frames >= 1, OVN_ERR_ARG, "ovn_mcl_predict: n_frames %d < 1", n_frames);
+  OVN_REQUIRE(resolution > 0.0 && resolution < INFINITY, OVN_ERR_ARG, "ovn_mcl_predict: resolution must be > 0");
+  OVN_REQUIRE(particles && cell_frame && particle_frame && frame_slot && frame_list && record, OVN_ERR_ARG,
+              "ovn_mcl_predict: NULL buffer");
+  OVN_REQUIRE(aligned16(particles), OVN_ERR_ARG, "ovn_mcl_predict: particles_dev is not 16-byte aligned");
+  OVN_REQUIRE(aligned16(record), OVN_ERR_ARG, "ovn_mcl_predict: record_dev is not 16-byte aligned");
+  OVN_ON_DEVICE(ctx->device);
+  const double motion6[6] = {dx, dy, dtheta, sigma_x, sigma_y, sigma_theta};
+  return ovn_mcl_predict_forward(particles, n_particles, motion6, seed, step, cell_frame, origin_x, origin_y, resolution, nx, ny,
+                                 n_frames, particle_frame, frame_slot, frame_list, record, (hipStream_t)stream);
+}
+
+int ovn_mcl_update(ovn_ctx* ctx, float* particles, int n_particles, const int32_t* particle_frame, const int32_t* frame_slot,
+                   const float* frame_yaw, int n_frames, const float* overlap, const int32_t* yaw, int n_scores, double sigma_yaw_deg,
+                   double eps_yaw, double overlap_min, double* estimate, double* spread, void* stream) {
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_mcl_update: ctx is NULL");
+  OVN_REQUIRE(n_particles >= 1 && n_particles <= OVN_MCL_MAX_PARTICLES, OVN_ERR_ARG,
+              "ovn_mcl_update: n_particles %d outside 1..%d", n_particles, OVN_MCL_MAX_PARTICLES);
+  OVN_REQUIRE(n_frames >= 1, OVN_ERR_ARG, "ovn_mcl_update: n_frames %d < 1", n_frames);
+  OVN_REQUIRE(n_scores >= 0 && n_scores <= n_frames, OVN_ERR_ARG, "ovn_mcl_update: n_scores %d outside [0, n_frames]", n_scores);
+  OVN_REQUIRE(sigma_yaw_deg > 0.0 && sigma_yaw_deg < INFINITY, OVN_ERR_ARG, "ovn_mcl_update: sigma_yaw_deg must be > 0");
+  OVN_REQUIRE(overlap_min > 0.0 && overlap_min < INFINITY, OVN_ERR_ARG, "ovn_mcl_update: overlap_min must be > 0");
+  OVN_REQUIRE(eps_yaw >= 0.0 && eps_yaw <= 1.0, OVN_ERR_ARG, "ovn_mcl_update: eps_yaw outside [0, 1]");
+  OVN_REQUIRE(particles && particle_frame && frame_slot && frame_yaw && estimate, OVN_ERR_ARG, "ovn_mcl_update: NULL buffer");
+  OVN_REQUIRE(n_scores == 0 || (overlap && yaw), OVN_ERR_ARG, "ovn_mcl_update: NULL score buffer with n_scores %d", n_scores);
+  OVN_REQUIRE(aligned16(particles), OVN_ERR_ARG, "ovn_mcl_update: particles_dev is not 16-byte aligned");
+  OVN_REQUIRE(aligned16(estimate), OVN_ERR_ARG, "ovn_mcl_update: estimate_dev is not 16-byte aligned");
+  OVN_ON_DEVICE(ctx->device);
+  return ovn_mcl_update_forward(particles, n_particles, particle_frame, frame_slot, frame_yaw, n_frames, overlap, yaw, n_scores,
+                                sigma_yaw_deg, eps_yaw, overlap_min, estimate, spread, (hipStream_t)stream);
+}
+
+int ovn_mcl_resample(ovn_ctx* ctx, const float* particles, int n_particles, uint64_t seed, uint64_t step, float* out_particles,
+                     int n_out, int32_t* ancestor, int32_t* record, void* stream) {
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_mcl_resample: ctx is NULL");
+  OVN_REQUIRE(n_particles >= 1 && n_particles <= OVN_MCL_MAX_PARTICLES, OVN_ERR_ARG,
+              "ovn_mcl_resample: n_particles %d outside 1..%d", n_particles, OVN_MCL_MAX_PARTICLES);
+  OVN_REQUIRE(n_out >= 1 && n_out <= OVN_MCL_MAX_PARTICLES, OVN_ERR_ARG, "ovn_mcl_resample: n_out %d outside 1..%d", n_out,
+              OVN_MCL_MAX_PARTICLES);
+  OVN_REQUIRE(particles && out_particles && ancestor && record, OVN_ERR_ARG, "ovn_mcl_resample: NULL buffer");
+  OVN_REQUIRE(aligned16(particles) && aligned16(out_particles), OVN_ERR_ARG, "ovn_mcl_resample: particle buffers must be 16-byte aligned");
+  OVN_REQUIRE(aligned16(record), OVN_ERR_ARG, "ovn_mcl_resample: record_dev is not 16-byte aligned");
+  {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(particles), b = reinterpret_cast<uintptr_t>(out_particles);
+    OVN_REQUIRE(a + 16ull * n_particles <= b || b + 16ull * n_out <= a, OVN_ERR_ARG,
+                "ovn_mcl_resample: out_particles_dev overlaps particles_dev");
+  }
+  OVN_ON_DEVICE(ctx->device);
+  return ovn_mcl_resample_forward(particles, n_particles, seed, step, out_particles, n_out, ancestor, record, (hipStream_t)stream);
+}
+
 // ---- segmented batches ---------------------------------------------------------------------------------------------------------
 // The host segment table (offsets, and the query of every segment when it is given) is validated, staged in a context-owned pinned
 // buffer and copied to seg_dev on `stream`; device space for the per-pair right index and segment index follows it.  The pinned buffer

@@ -587,6 +587,15 @@ int ovn_icp_register_forward(const float* vertex, const float* normal, const flo
                              double fov_up_deg, double fov_down_deg, double max_range, const int32_t* src_idx, const int32_t* tgt_idx,
                              int n_pairs, const double* init_pose, int iterations, double max_dist, double cos_min, double huber,
                              int min_inliers, double* pose, double* stats, double* system, hipStream_t stream);
+// mcl.hip: the particle filter of the overlap-based localization (ovn_mcl_*); motion6 = dx, dy, dtheta, sigma_x, sigma_y, sigma_theta
+int ovn_mcl_predict_forward(float* particles, int P, const double* motion6, uint64_t seed, uint64_t step, const int32_t* cell_frame,
+                            double origin_x, double origin_y, double resolution, int nx, int ny, int M, int32_t* particle_frame,
+                            int32_t* frame_slot, int32_t* frame_list, int32_t* record, hipStream_t stream);
+int ovn_mcl_update_forward(float* particles, int P, const int32_t* particle_frame, const int32_t* frame_slot, const float* frame_yaw,
+                           int M, const float* overlap, const int32_t* yaw, int U, double sigma_yaw, double eps_yaw, double overlap_min,
+                           double* estimate, double* spread, hipStream_t stream);
+int ovn_mcl_resample_forward(const float* particles, int P, uint64_t seed, uint64_t step, float* out, int n_out, int32_t* ancestor,
+                             int32_t* record, hipStream_t stream);
 // a2_feats_r / a2raw non-NULL (small 1-vs-N sweeps): the launch also computes A2raw of that right volume (delta_a2.h) in extra workgroups
 int ovn_corr_spectral_forward(ovn_ctx* ctx, const float* spec_l, const int32_t* lidx, const float* spec_r,
                               const int32_t* ridx, int n, int32_t* yaw, float* corr, hipStream_t stream,

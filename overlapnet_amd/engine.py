@@ -1017,6 +1017,108 @@ class OvnEngine:
                                                  _ptr(pose), _ptr(stats), _ptr(system), self._stream()), "ovn_icp_register")
         return (pose, stats, system) if want_system else (pose, stats)
 
+    # -- Monte Carlo localization (csrc/mcl.hip) -------------------------------------------------------
+    def _check_mcl(self, t: torch.Tensor, what: str, dtype, numel: Optional[int] = None, pinned_ok: bool = False) -> None:
+        """A buffer of the mcl_* calls: contiguous, of `dtype`, on this device (a record may instead be pinned host memory, which the
+        device sees at the same address), holding `numel` elements when given."""
+        on_dev = t.device == self.device or (pinned_ok and t.device.type == "cpu" and t.is_pinned())
+        if not on_dev or t.dtype != dtype or not t.is_contiguous():
+            raise _lib.OvnError("%s must be a contiguous %s tensor on %s%s" % (what, dtype, self.device,
+                                                                             " (or pinned host memory)" if pinned_ok else ""))
+        if numel is not None and t.numel() != numel:
+            raise _lib.OvnError("%s holds %d elements, expected %d" % (what, t.numel(), numel))
+
+    def _mcl_particles(self, particles: torch.Tensor, what: str = "particles") -> int:
+        self._check_mcl(particles, what, torch.float32)
+        if particles.dim() != 2 or particles.shape[1] != 4:
+            raise _lib.OvnError("%s must be (P, 4) rows x, y, theta, w; got %s" % (what, tuple(particles.shape)))
+        return int(particles.shape[0])
+
+    def mcl_predict(self, particles: torch.Tensor, odom, sigma, seed: int, step: int, cell_frame: torch.Tensor, origin, resolution: float,
+                    nx: int, ny: int, n_frames: int, particle_frame: Optional[torch.Tensor] = None,
+                    frame_slot: Optional[torch.Tensor] = None, frame_list: Optional[torch.Tensor] = None,
+                    record: Optional[torch.Tensor] = None):
+        """Motion update of the (P,4) particles IN PLACE with Philox noise, their map frames, and the ascending list of the distinct
+        frames (`ovn_mcl_predict`).  odom = (dx, dy, dtheta) in the robot frame, sigma = (sigma_x, sigma_y, sigma_theta), origin =
+        (origin_x, origin_y); cell_frame (ny*nx) int32.  Returns (particle_frame (P), frame_slot (M), frame_list (M), record (4)) int32;
+        record = {U, particles off the map, 0, 1} may be a pinned host tensor (the caller synchronises before reading it)."""
+        p = self._mcl_particles(particles)
+        nx, ny, m = int(nx), int(ny), int(n_frames)
+        self._check_mcl(cell_frame, "cell_frame", torch.int32, max(nx, 0) * max(ny, 0))
+        if particle_frame is None:
+            particle_frame = torch.empty(p, dtype=torch.int32, device=self.device)
+        if frame_slot is None:
+            frame_slot = torch.empty(max(m, 0), dtype=torch.int32, device=self.device)
+        if frame_list is None:
+            frame_list = torch.empty(max(m, 0), dtype=torch.int32, device=self.device)
+        if record is None:
+            record = torch.empty(4, dtype=torch.int32, device=self.device)
+        self._check_mcl(particle_frame, "particle_frame", torch.int32, p)
+        self._check_mcl(frame_slot, "frame_slot", torch.int32, max(m, 0))
+        self._check_mcl(frame_list, "frame_list", torch.int32, max(m, 0))
+        self._check_mcl(record, "record", torch.int32, 4, pinned_ok=True)
+        dx, dy, dth = (float(v) for v in odom)
+        sx, sy, sth = (float(v) for v in sigma)
+        with self._dev():
+            _lib.check(self.lib.ovn_mcl_predict(self._h, _ptr(particles), p, dx, dy, dth, sx, sy, sth, int(seed) & (2 ** 64 - 1),
+                                                int(step) & (2 ** 64 - 1), _ptr(cell_frame), float(origin[0]), float(origin[1]),
+                                                float(resolution), nx, ny, m, _ptr(particle_frame), _ptr(frame_slot), _ptr(frame_list),
+                                                _ptr(record), self._stream()), "ovn_mcl_predict")
+        return particle_frame, frame_slot, frame_list, record
+
+    def mcl_update(self, particles: torch.Tensor, particle_frame: torch.Tensor, frame_slot: torch.Tensor, frame_yaw: torch.Tensor,
+                   overlap: Optional[torch.Tensor], yaw: Optional[torch.Tensor], sigma_yaw: float, eps_yaw: float, overlap_min: float,
+                   estimate: Optional[torch.Tensor] = None, want_spread: bool = False):
+        """Observation-model weights IN PLACE from the sweep's scores over frame_list[:U] (overlap (U) f32, yaw (U) int32; both None
+        when U == 0), the exact power-of-two rescale and the estimate (`ovn_mcl_update`): a (8,) float64 device tensor {status,
+        sum w, N_eff, mean x, mean y, circular mean heading, position of the first maximum weight, particles on the map}; with
+        want_spread=True also the weighted rms distance from the mean position, a (1,) float64 device tensor."""
+        p = self._mcl_particles(particles)
+        m = int(frame_slot.numel())
+        self._check_mcl(particle_frame, "particle_frame", torch.int32, p)
+        self._check_mcl(frame_slot, "frame_slot", torch.int32)
+        self._check_mcl(frame_yaw, "frame_yaw", torch.float32, m)
+        if (overlap is None) != (yaw is None):
+            raise _lib.OvnError("mcl_update(): overlap and yaw must be given together")
+        u = 0
+        if overlap is not None:
+            u = int(overlap.numel())
+            self._check_mcl(overlap, "overlap", torch.float32)
+            self._check_mcl(yaw, "yaw", torch.int32, u)
+        if estimate is None:
+            estimate = torch.empty(8, dtype=torch.float64, device=self.device)
+        self._check_mcl(estimate, "estimate", torch.float64, 8)
+        spread = torch.empty(1, dtype=torch.float64, device=self.device) if want_spread else None
+        with self._dev():
+            _lib.check(self.lib.ovn_mcl_update(self._h, _ptr(particles), p, _ptr(particle_frame), _ptr(frame_slot), _ptr(frame_yaw), m,
+                                               _ptr(overlap) if u else None, _ptr(yaw) if u else None, u, float(sigma_yaw),
+                                               float(eps_yaw), float(overlap_min), _ptr(estimate), _ptr(spread), self._stream()),
+                       "ovn_mcl_update")
+        return (estimate, spread) if want_spread else estimate
+
+    def mcl_resample(self, particles: torch.Tensor, seed: int, step: int, n_out: Optional[int] = None,
+                     out: Optional[torch.Tensor] = None, ancestors: Optional[torch.Tensor] = None,
+                     record: Optional[torch.Tensor] = None):
+        """Systematic resampling, exact in integers (`ovn_mcl_resample`): n_out (default P) copies with weight 1 into `out`, which must
+        not overlap `particles`.  Returns (out (n_out,4) f32, ancestors (n_out) int32, record (4) int32 = {status, written, 0, 1});
+        status 1: no positive weight, nothing but the record is written.  `record` may be a pinned host tensor."""
+        p = self._mcl_particles(particles)
+        n_out = p if n_out is None else int(n_out)
+        if out is None:
+            out = torch.empty((max(n_out, 0), 4), dtype=torch.float32, device=self.device)
+        if self._mcl_particles(out, "out") != n_out:
+            raise _lib.OvnError("mcl_resample(): out holds %d particles, n_out is %d" % (out.shape[0], n_out))
+        if ancestors is None:
+            ancestors = torch.empty(max(n_out, 0), dtype=torch.int32, device=self.device)
+        if record is None:
+            record = torch.empty(4, dtype=torch.int32, device=self.device)
+        self._check_mcl(ancestors, "ancestors", torch.int32, max(n_out, 0))
+        self._check_mcl(record, "record", torch.int32, 4, pinned_ok=True)
+        with self._dev():
+            _lib.check(self.lib.ovn_mcl_resample(self._h, _ptr(particles), p, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1),
+                                                 _ptr(out), n_out, _ptr(ancestors), _ptr(record), self._stream()), "ovn_mcl_resample")
+        return out, ancestors, record
+
     def projection_angles(self, points: torch.Tensor, proj_h: int = 64, proj_w: int = 900, fov_up: float = 3.0,
                           fov_down: float = -25.0, max_range: float = 50.0):
         """(yaw, pitch, pixel) of every point of an (n, 4) float32 device tensor as the projection kernel evaluates them
