@@ -319,16 +319,16 @@ int ovn_c3_dense_forward(const ovn_ctx* ctx, const float* o2, const unsigned* o2
     rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(c3_dense_kernel<ArithF16, 4, 2>), LDS_BYTES);
     if (rc) return rc;
     hipLaunchKernelGGL((c3_dense_kernel<ArithF16, 4, 2>), dim3(4 * NBAND * n), dim3(64 * 4), LDS_BYTES, stream, o2,
-                       reinterpret_cast<const _Float16*>(ctx->c3.wp_h), ctx->c3.bias, ctx->wd, o2max, ctx->c3.sw_h, partial, o3, arrived,
-                       ctx->bd, overlap, logit);
+                       reinterpret_cast<const _Float16*>(ctx->head.c3.wp_h), ctx->head.c3.bias, ctx->head.wd, o2max, ctx->head.c3.sw_h, partial, o3, arrived,
+                       ctx->head.bd, overlap, logit);
   } else {         // sweeps: the finish as its own small launch (see dense_finish_kernel)
     rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(c3_dense_kernel<ArithF16, NW, 1>), LDS_BYTES);
     if (rc) return rc;
     hipLaunchKernelGGL((c3_dense_kernel<ArithF16, NW, 1>), dim3(NBAND * n), dim3(64 * NW), LDS_BYTES, stream, o2,
-                       reinterpret_cast<const _Float16*>(ctx->c3.wp_h), ctx->c3.bias, ctx->wd, o2max, ctx->c3.sw_h, partial, o3,
-                       (unsigned*)nullptr, ctx->bd, (float*)nullptr, (float*)nullptr);
+                       reinterpret_cast<const _Float16*>(ctx->head.c3.wp_h), ctx->head.c3.bias, ctx->head.wd, o2max, ctx->head.c3.sw_h, partial, o3,
+                       (unsigned*)nullptr, ctx->head.bd, (float*)nullptr, (float*)nullptr);
     if (overlap != nullptr)
-      hipLaunchKernelGGL(dense_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, partial, ctx->bd, n, overlap, logit);
+      hipLaunchKernelGGL(dense_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, partial, ctx->head.bd, n, overlap, logit);
   }
   OVN_HIP_CHECK(hipGetLastError());
   return OVN_OK;

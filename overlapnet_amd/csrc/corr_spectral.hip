@@ -512,7 +512,7 @@ int ovn_corr_spectral_forward(ovn_ctx* ctx, const float* spec_l, const int32_t* 
                               float* a2raw) {
   if (a2_feats_r != nullptr && a2raw != nullptr)
     hipLaunchKernelGGL(spectral_corr_kernel<true>, dim3(n + A2_WGS), dim3(PROD_THREADS), 0, stream, spec_l, lidx, spec_r, ridx,
-                       ctx->tw64, yaw, corr, n, a2_feats_r, ctx->w1raw, a2raw);
+                       ctx->tw64, yaw, corr, n, a2_feats_r, ctx->head.w1raw, a2raw);
   else
     hipLaunchKernelGGL(spectral_corr_kernel<false>, dim3(n), dim3(PROD_THREADS), 0, stream, spec_l, lidx, spec_r, ridx, ctx->tw64, yaw,
                        corr, n, (const float*)nullptr, (const float*)nullptr, (float*)nullptr);

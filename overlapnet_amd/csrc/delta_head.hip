@@ -193,8 +193,8 @@ int launch_c12(const ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, co
   const size_t lds_max = ((size_t)G_MAX * O1S_STRIDE + (size_t)S * FC) * sizeof(float);
   int rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_c12_kernel<T, MT>), lds_max);
   if (rc) return rc;
-  hipLaunchKernelGGL((delta_c12_kernel<T, MT>), dim3(n), dim3(512), lds, stream, feats_l, lidx, feats_r, ridx, ctx->w1p, ctx->b1,
-                     ctx->c2.wp, ctx->c2.bias, W, o2);
+  hipLaunchKernelGGL((delta_c12_kernel<T, MT>), dim3(n), dim3(512), lds, stream, feats_l, lidx, feats_r, ridx, ctx->head.w1p, ctx->head.b1,
+                     ctx->head.c2.wp, ctx->head.c2.bias, W, o2);
   OVN_HIP_CHECK(hipGetLastError());
   return OVN_OK;
 }
@@ -227,10 +227,10 @@ __global__ __launch_bounds__(256) void dense_sigmoid_kernel(const float* __restr
 
 }  // namespace
 
-int ovn_delta_prepare_w1(const float* c1_kernel_dev, float** w1p_out, hipStream_t stream) {
+int ovn_delta_prepare_w1(OvnHeadWeights* hw, const float* c1_kernel_dev, hipStream_t stream) {
   const size_t elems = (size_t)S * FC * O1;
-  OVN_HIP_CHECK(hipMalloc((void**)w1p_out, elems * sizeof(float)));
-  hipLaunchKernelGGL(delta_prep_w1_kernel, dim3(120), dim3(256), 0, stream, c1_kernel_dev, *w1p_out);
+  OVN_HIP_CHECK(hipMalloc((void**)&hw->w1p, elems * sizeof(float)));
+  hipLaunchKernelGGL(delta_prep_w1_kernel, dim3(120), dim3(256), 0, stream, c1_kernel_dev, hw->w1p);
   OVN_HIP_CHECK(hipGetLastError());
   return OVN_OK;
 }
@@ -274,7 +274,7 @@ int ovn_delta_forward(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, c
   int oh = 0, ow = 0;
   {
     OvnProfScope ps(ctx, OVN_K_C3, stream);
-    rc = ovn_conv_forward(ctx->c3, o2, n, G, G, o3, &oh, &ow, stream);    // (n, G, G, 128) -> (n, G - 2, G - 2, 256)
+    rc = ovn_conv_forward(ctx->head.c3, o2, n, G, G, o3, &oh, &ow, stream);    // (n, G, G, 128) -> (n, G - 2, G - 2, 256)
   }
   if (rc) return rc;
   OVN_REQUIRE(oh == G - 2 && ow == G - 2, OVN_ERR_STATE, "Delta head at width %d: c_conv3 produced %dx%d", W, oh, ow);
@@ -284,7 +284,7 @@ int ovn_delta_forward(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, c
 
 int ovn_dense_sigmoid_forward(const ovn_ctx* ctx, const float* o3, int n, long long dense_in, float* overlap, float* logit,
                               hipStream_t stream) {
-  hipLaunchKernelGGL(dense_sigmoid_kernel, dim3(n), dim3(256), 0, stream, o3, ctx->wd, ctx->bd, dense_in, overlap, logit);
+  hipLaunchKernelGGL(dense_sigmoid_kernel, dim3(n), dim3(256), 0, stream, o3, ctx->head.wd, ctx->head.bd, dense_in, overlap, logit);
   OVN_HIP_CHECK(hipGetLastError());
   return OVN_OK;
 }

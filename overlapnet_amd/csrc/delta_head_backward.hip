@@ -391,8 +391,8 @@ int ovn_delta_head_grad_run(ovn_ctx* ctx, int FW, const float* feats_l, const in
         *w3t = sc.w3t, *w2t = sc.w2t, *part = sc.part;
   if (!grad && !forward_only) grad = sc.grad;
   // W3 (tap, ci, co) -> (tap, co, ci); W2 (di, o, ch) -> (di, ch, o)
-  hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((sz[4] + 255) / 256)), dim3(256), 0, stream, ctx->w3raw, w3t, 9, O2, O3);
-  hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((sz[2] + 255) / 256)), dim3(256), 0, stream, ctx->w2raw, w2t, s, O1, O2);
+  hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((sz[4] + 255) / 256)), dim3(256), 0, stream, ctx->head.w3raw, w3t, 9, O2, O3);
+  hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((sz[2] + 255) / 256)), dim3(256), 0, stream, ctx->head.w2raw, w2t, s, O1, O2);
   OVN_HIP_CHECK(hipGetLastError());
   const double coef = (double)scale / (double)n;
   const size_t feat_elems = (size_t)FW * FC;
@@ -408,9 +408,9 @@ int ovn_delta_head_grad_run(ovn_ctx* ctx, int FW, const float* feats_l, const in
       rc = ovn_delta_generic_c1_wide(ctx, FW, fl, li, feats_r, ri, np, o1, stream);
       if (rc) return rc;
       const long long npos2 = (long long)np * G * G, npos3 = (long long)np * H * H;
-      hipLaunchKernelGGL(fwd_c2_kernel, dim3((unsigned)((npos2 + 1) / 2)), dim3(256), 0, stream, o1, ctx->w2raw, ctx->c2.bias, s, G, FW, npos2, o2);
-      hipLaunchKernelGGL(fwd_c3_kernel, dim3((unsigned)npos3), dim3(256), 0, stream, o2, ctx->w3raw, ctx->c3.bias, G, H, npos3, o3);
-      hipLaunchKernelGGL(fwd_dense_kernel, dim3((unsigned)np), dim3(256), 0, stream, o3, ctx->wd, ctx->bd, (long long)sz[6], y, zbuf);
+      hipLaunchKernelGGL(fwd_c2_kernel, dim3((unsigned)((npos2 + 1) / 2)), dim3(256), 0, stream, o1, ctx->head.w2raw, ctx->head.c2.bias, s, G, FW, npos2, o2);
+      hipLaunchKernelGGL(fwd_c3_kernel, dim3((unsigned)npos3), dim3(256), 0, stream, o2, ctx->head.w3raw, ctx->head.c3.bias, G, H, npos3, o3);
+      hipLaunchKernelGGL(fwd_dense_kernel, dim3((unsigned)np), dim3(256), 0, stream, o3, ctx->head.wd, ctx->head.bd, (long long)sz[6], y, zbuf);
     }
     if (o2_out) OVN_HIP_CHECK(hipMemcpyAsync(o2_out + (size_t)p0 * o2e, o2, (size_t)np * o2e * 4, hipMemcpyDeviceToDevice, stream));
     if (o3_out) OVN_HIP_CHECK(hipMemcpyAsync(o3_out + (size_t)p0 * o3e, o3, (size_t)np * o3e * 4, hipMemcpyDeviceToDevice, stream));
@@ -422,7 +422,7 @@ int ovn_delta_head_grad_run(ovn_ctx* ctx, int FW, const float* feats_l, const in
       OvnProfScope ps(ctx, OVN_K_DENSE, stream);
       hipLaunchKernelGGL(loss_dz_kernel, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, stream, zbuf, target + p0, np, nb, loss, coef, dz, part,
                          stride, (long long)off[7], (long long)total);
-      hipLaunchKernelGGL(dense_grad_kernel, dim3((unsigned)((sz[6] + 255) / 256), (unsigned)nb), dim3(256), 0, stream, o3, ctx->wd, dz, np,
+      hipLaunchKernelGGL(dense_grad_kernel, dim3((unsigned)((sz[6] + 255) / 256), (unsigned)nb), dim3(256), 0, stream, o3, ctx->head.wd, dz, np,
                          (long long)sz[6], dO3, part + off[6], stride);
     }
     {   // c_conv3: bias, kernel, dO2

@@ -40,6 +40,7 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include <initializer_list>
 #include <type_traits>
 
 #include "ovn_internal.h"
@@ -455,6 +456,25 @@ __device__ __forceinline__ int load_chan_table(const unsigned* __restrict__ live
   return use ? (int)live[0] : 4;
 }
 
+// The `live` record of a query, as delta_live_kernel / delta_query_kernel leave it and the prepare and contraction kernels
+// (load_chan_table) and ovn_delta_walk_stats read it
+struct LiveRecord {
+  unsigned ns, nlive, pad[2];       // largest slice count of the twelve column-group pairs, live channels
+  unsigned char table[CHAN_BYTES];  // the channel table
+};
+static_assert(sizeof(LiveRecord) == LIVE_WORDS * sizeof(unsigned), "LiveRecord is LIVE_WORDS words");
+// the largest walk of a table: what is packed and gathered for the query
+__device__ __forceinline__ int largest_walk(const unsigned char* table) {
+  int ns = 1;
+#pragma unroll
+  for (int p = 0; p < NPAIR; ++p) ns = table[FC + p] > ns ? table[FC + p] : ns;
+  return ns;
+}
+__device__ __forceinline__ void store_live(unsigned* __restrict__ live, int ns, int nlive, const unsigned char* chan_s, int tid) {
+  if (tid == 0) *reinterpret_cast<u32x4*>(live) = (u32x4){(unsigned)ns, (unsigned)nlive, 0u, 0u};
+  if (tid < CHAN_BYTES / 4) live[4 + tid] = reinterpret_cast<const unsigned*>(chan_s)[tid];
+}
+
 // Channel list of a query from its flags alive2[p][ch] (channel ch is non-zero somewhere in the 30 query columns of column groups 2 p,
 // 2 p + 1; `shifted`: the volume has a negative value -> everything counts as alive).  The channels are ordered by the NUMBER OF
 // PAIRS p they are alive in (descending; ties and the dead ones in walk order -- a query alive everywhere gets the identity), and pair p
@@ -559,14 +579,7 @@ __global__ __launch_bounds__(512) void delta_live_kernel(const float* __restrict
   if (ng) neg_s = 1;
   __syncthreads();
   const int nlive = build_chan_list(alive2, neg_s != 0, chan_s, scr, tid);
-  if (tid == 0) {
-    int nsm = 1;
-    for (int p = 0; p < NPAIR; ++p) nsm = chan_s[FC + p] > nsm ? chan_s[FC + p] : nsm;
-    live[0] = (unsigned)nsm;
-    live[1] = (unsigned)nlive;
-    live[2] = live[3] = 0u;
-  }
-  if (tid < FC / 4 + 4) live[4 + tid] = reinterpret_cast<const unsigned*>(chan_s)[tid];
+  store_live(live, largest_walk(chan_s), nlive, chan_s, tid);
 }
 
 // 8 consecutive elements (one lane's 16 bytes) of the compacted W1 fragments: out[sc][dj][nt][hi,lo][lane][0..7] <- w1p[...] of the
@@ -604,6 +617,54 @@ __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
                                    (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
+// ---- stages the preparation kernels share.  None of them moves a load: each is called where its loads stood -------------------------
+// A2[i] of one right volume (i = 64 jb + o, true units): the K slices of delta_a2_kernel, loaded together, summed in slice order
+__device__ __forceinline__ void a2_load(const float* __restrict__ a2raw, int i, float (&v)[A2_KSPLIT]) {
+#pragma unroll
+  for (int k = 0; k < A2_KSPLIT; ++k) v[k] = a2raw[(size_t)k * A2_ELEMS + i];
+}
+__device__ __forceinline__ float a2_fold(const float (&v)[A2_KSPLIT]) {
+  float s = v[0];
+#pragma unroll
+  for (int k = 1; k < A2_KSPLIT; ++k) s += v[k];
+  return s;
+}
+// AA[jb][p] = sum_o A2[jb][o] W2s[o][p] from A2l in LDS (the caller's barrier stands before the call): thread = (p, 6 consecutive
+// jb), its column of W2s in registers (64 loads in flight).  512 threads.
+__device__ __forceinline__ void aa_product(const float* A2l, const float* __restrict__ w2sum, float* __restrict__ aa, int tid) {
+  const int p = tid & (O2 - 1), jb0 = 6 * (tid >> 7);
+  float wcol[O1];
+#pragma unroll
+  for (int o = 0; o < O1; ++o) wcol[o] = w2sum[o * O2 + p];
+  float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int o = 0; o < O1; ++o)
+#pragma unroll
+    for (int j = 0; j < 6; ++j) s[j] = fmaf(A2l[(jb0 + j) * O1 + o], wcol[o], s[j]);
+#pragma unroll
+  for (int j = 0; j < 6; ++j) aa[(jb0 + j) * O2 + p] = s[j];
+}
+// Store phase of the R words in walk order: the 8 values of (row jrow, slice sc, lane group gq), loaded by the caller, packed to
+// Pr[jb][sc][dj][gq][0..7]
+__device__ __forceinline__ void store_rwords8(unsigned* __restrict__ Pr, int jrow, int sc, int gq, const f32x4& v0, const f32x4& v1, float sa,
+                                              float csa) {
+  const int jb = jrow / S, dj = jrow - jb * S;
+  unsigned* dst = Pr + ((jb * 4 + sc) * S + dj) * 32 + gq * 8;
+  *reinterpret_cast<u32x4*>(dst) = pack4(v0, sa, csa);
+  *reinterpret_cast<u32x4*>(dst + 4) = pack4(v1, sa, csa);
+}
+
+// What the prepare kernel reads of the registered weights (OvnHeadWeights), by value
+struct PrepWeights {
+  const _Float16* wsp;     // Ws fragments
+  const float* w1col;
+  const float* b1;
+  const _Float16* w2p;     // W2 fragments
+  const float* w2sum;
+  const float* b2;
+  float sw1, sw2, sws, w1_colsum, b1_absmax;
+};
+
 // Per pair: value range -> shift and scales; both volumes packed ONCE into the word streams the c_conv1 kernel DMAs into LDS
 //   pl[pair][c(128)][i(360)]              L words, CHANNEL-major: the contraction kernel fetches 32 rows of the channels its walk names
 //   pr[pair][jb(24)][s(4)][dj(15)][g(4)][8] R words in the order of the K walk: a chunk of 3 taps of a column group is 384 contiguous bytes
@@ -624,10 +685,8 @@ __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
 template <bool BUILD, bool SEG = false>
 __global__ __launch_bounds__(512) void delta_prepare_split_kernel(
     const float* __restrict__ feats_l, const int32_t* __restrict__ lidx, const float* __restrict__ feats_r,
-    const int32_t* __restrict__ ridx, const _Float16* __restrict__ wsp, const float* __restrict__ w1col,
-    const float* __restrict__ b1, const float* __restrict__ a2raw, const _Float16* __restrict__ w2p,
-    const float* __restrict__ w2sum, const float* __restrict__ b2, float sw1, float sw2, float sws, float w1_colsum, float b1_absmax,
-    float one, f32x4* __restrict__ scales, unsigned* __restrict__ o2max, unsigned* __restrict__ pl, unsigned* __restrict__ pr,
+    const int32_t* __restrict__ ridx, const PrepWeights W, const float* __restrict__ a2raw, float one, f32x4* __restrict__ scales,
+    unsigned* __restrict__ o2max, unsigned* __restrict__ pl, unsigned* __restrict__ pr,
     float* __restrict__ lin, DeltaDesc* __restrict__ desc, const float* __restrict__ dcache, const unsigned* __restrict__ qblock,
     float* __restrict__ cache_out, const unsigned* __restrict__ live, const int32_t* __restrict__ pseg = nullptr, int seg0 = 0) {
   extern __shared__ __attribute__((aligned(16))) unsigned char psm[];
@@ -642,6 +701,12 @@ __global__ __launch_bounds__(512) void delta_prepare_split_kernel(
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int lrow = lane & 15, g = lane >> 4;
+  const _Float16* __restrict__ wsp = W.wsp;
+  const _Float16* __restrict__ w2p = W.w2p;
+  const float* __restrict__ w1col = W.w1col;
+  const float* __restrict__ b1 = W.b1;
+  const float* __restrict__ b2 = W.b2;
+  const float sw1 = W.sw1, sw2 = W.sw2, sws = W.sws, w1_colsum = W.w1_colsum, b1_absmax = W.b1_absmax;
   const long long cand = lidx ? lidx[pair] : pair;
   if constexpr (SEG) {   // workgroup-uniform
     const int sg = pseg[pair] - seg0;
@@ -706,9 +771,7 @@ __global__ __launch_bounds__(512) void delta_prepare_split_kernel(
   if (!BUILD) {
     const float* src = a2raw + (size_t)((!SEG && ridx) ? pair : 0) * A2_KSPLIT * A2_ELEMS;
 #pragma unroll
-    for (int u = 0; u < 3; ++u)
-#pragma unroll
-      for (int k = 0; k < A2_KSPLIT; ++k) a2v[u][k] = src[(size_t)k * A2_ELEMS + tid + 512 * u];
+    for (int u = 0; u < 3; ++u) a2_load(src, tid + 512 * u, a2v[u]);
   }
   // R: range scan now (12 x 32 B per thread, two batches of loads), packed in a second pass once the scale is known
   constexpr int R_ITEMS = OVN_FEAT_ELEMS / 8;   // 5760 = 11.25 x 512
@@ -746,25 +809,11 @@ __global__ __launch_bounds__(512) void delta_prepare_split_kernel(
           mn = fminf(mn, fminf(fminf(a[0], a[1]), fminf(a[2], a[3])));
         }
     }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    mx = fmaxf(mx, __shfl_down(mx, off, 64));
-    mn = fminf(mn, __shfl_down(mn, off, 64));
-  }
-  if (lane == 0) {
-    red[wave] = mx;
-    red[NWAVE + wave] = mn;
-  }
+  ovn_wg_minmax_put<NWAVE>(mx, mn, red);
 #pragma unroll
   for (int q = 0; q < 4; ++q) reinterpret_cast<f32x4*>(wsl)[tid + 512 * q] = wsv[q];
   __syncthreads();
-  mx = red[0];
-  mn = red[NWAVE];
-#pragma unroll
-  for (int w = 1; w < NWAVE; ++w) {
-    mx = fmaxf(mx, red[w]);
-    mn = fminf(mn, red[NWAVE + w]);
-  }
+  ovn_wg_minmax_get<NWAVE>(red, mx, mn);
   const float c = (mn < 0.0f) ? -mn : 0.0f;       // shift that makes both volumes non-negative
   const float span = mx + c;                       // largest shifted value
   const float sa = ovn_pow2_scale_for(span);
@@ -793,11 +842,8 @@ __global__ __launch_bounds__(512) void delta_prepare_split_kernel(
   // A2[jb][o] of this pair (true units): sum of the K slices of delta_a2_kernel (fixed order) + c (column sums of W1)
 #pragma unroll
   for (int u = 0; u < 3; ++u) {
-    float v = a2v[u][0];
-#pragma unroll
-    for (int k = 1; k < A2_KSPLIT; ++k) v += a2v[u][k];
     const int i = tid + 512 * u;
-    A2l[i] = v + c * w1col[i & (O1 - 1)];
+    A2l[i] = a2_fold(a2v[u]) + c * w1col[i & (O1 - 1)];
   }
   // R words in the order of the pair's K walk (second read of R: L2 hits): the query's compacted channel list when the pair has no
   // shift (1-vs-N sweeps; `live` is NULL for indexed pairs), the plain slice order otherwise
@@ -814,7 +860,6 @@ __global__ __launch_bounds__(512) void delta_prepare_split_kernel(
       if (i8 < R_ITEMS) {
         const int jrow = i8 >> 4, sc = (i8 >> 2) & 3, gq = i8 & 3;
         if (sc < ns && sc != tp.sl) {
-          const int jb = jrow / S, dj = jrow - jb * S;
           const float* rrow = Rf + (size_t)jrow * FC;
           const unsigned char* ch = chan_p + 32 * sc + 8 * gq;
           f32x4 v0, v1;
@@ -825,9 +870,7 @@ __global__ __launch_bounds__(512) void delta_prepare_split_kernel(
             v0 = (f32x4){rrow[ch[0]], rrow[ch[1]], rrow[ch[2]], rrow[ch[3]]};
             v1 = (f32x4){rrow[ch[4]], rrow[ch[5]], rrow[ch[6]], rrow[ch[7]]};
           }
-          unsigned* dst = Pr + ((jb * 4 + sc) * S + dj) * 32 + gq * 8;
-          *reinterpret_cast<u32x4*>(dst) = pack4(v0, sa, csa);
-          *reinterpret_cast<u32x4*>(dst + 4) = pack4(v1, sa, csa);
+          store_rwords8(Pr, jrow, sc, gq, v0, v1, sa, csa);
         }
       }
     }
@@ -942,20 +985,7 @@ __global__ __launch_bounds__(512) void delta_prepare_split_kernel(
       }
     }
   }
-  // AA[jb][p] = sum_o A2[jb][o] W2s[o][p]: thread = (p, 6 consecutive jb); its column of W2s in registers (64 loads in flight)
-  if (!BUILD) {
-    const int p = tid & (O2 - 1), jb0 = 6 * (tid >> 7);
-    float wcol[O1];
-#pragma unroll
-    for (int o = 0; o < O1; ++o) wcol[o] = w2sum[o * O2 + p];
-    float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int o = 0; o < O1; ++o)
-#pragma unroll
-      for (int j = 0; j < 6; ++j) s[j] = fmaf(A2l[(jb0 + j) * O1 + o], wcol[o], s[j]);
-#pragma unroll
-    for (int j = 0; j < 6; ++j) lp[G * O2 + (jb0 + j) * O2 + p] = s[j];
-  }
+  if (!BUILD) aa_product(A2l, W.w2sum, lp + G * O2, tid);
 }
 
 // The query's side of a cached 1-vs-N sweep, once per call: workgroup v packs the query's words at scale sa_q / 2^v (the version a
@@ -984,7 +1014,7 @@ __global__ __launch_bounds__(512) void delta_query_kernel(const float* __restric
   __shared__ int scr[2 * FC + 32];
   __shared__ __attribute__((aligned(16))) unsigned char chan_q[CHAN_BYTES];
   const int ver = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const f32x4* R4 = reinterpret_cast<const f32x4*>(feats_r);
   constexpr int R_ITEMS = OVN_FEAT_ELEMS / 8;
   f32x4 rv[12][2];
@@ -1008,15 +1038,7 @@ __global__ __launch_bounds__(512) void delta_query_kernel(const float* __restric
       mn = fminf(mn, fminf(fminf(rv[k][h][0], rv[k][h][1]), fminf(rv[k][h][2], rv[k][h][3])));
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    mx = fmaxf(mx, __shfl_down(mx, off, 64));
-    mn = fminf(mn, __shfl_down(mn, off, 64));
-  }
-  if (lane == 0) {
-    red[wave] = mx;
-    red[NWAVE + wave] = mn;
-  }
+  ovn_wg_minmax_put<NWAVE>(mx, mn, red);
   __syncthreads();   // (also: alive2[][] cleared)
   // item i8 = (row i8 / 16, channels 8 (i8 % 16) ..): flag the channels that are non-zero in the row's column-group pair
   if (live_out != nullptr) {
@@ -1033,13 +1055,7 @@ __global__ __launch_bounds__(512) void delta_query_kernel(const float* __restric
       }
     }
   }
-  mx = red[0];
-  mn = red[NWAVE];
-#pragma unroll
-  for (int w = 1; w < NWAVE; ++w) {
-    mx = fmaxf(mx, red[w]);
-    mn = fminf(mn, red[NWAVE + w]);
-  }
+  ovn_wg_minmax_get<NWAVE>(red, mx, mn);
   __syncthreads();
   const float sa = ldexpf(ovn_pow2_scale_for(mx), -(ver < QV ? ver : 0));
   unsigned* Pr = qblock + (size_t)(ver < QV ? ver : 0) * OVN_FEAT_ELEMS;
@@ -1048,17 +1064,8 @@ __global__ __launch_bounds__(512) void delta_query_kernel(const float* __restric
   int ns = 4;
   if (live_out != nullptr) {
     const int nlive = build_chan_list(alive2, mn < 0.0f, chan_q, scr, tid);
-    ns = 1;
-#pragma unroll
-    for (int p = 0; p < NPAIR; ++p) ns = chan_q[FC + p] > ns ? chan_q[FC + p] : ns;   // the largest walk: what is packed and gathered
-    if (ver == 0) {
-      if (tid == 0) {
-        live_out[0] = (unsigned)ns;
-        live_out[1] = (unsigned)nlive;
-        live_out[2] = live_out[3] = 0u;
-      }
-      if (tid < FC / 4 + 4) live_out[4 + tid] = reinterpret_cast<const unsigned*>(chan_q)[tid];
-    }
+    ns = largest_walk(chan_q);
+    if (ver == 0) store_live(live_out, ns, nlive, chan_q, tid);
     // this workgroup's share of the W1 fragments gathered for the list (workgroups QV .. QV + QGW - 1 do nothing else)
     const int total8 = ns * S * 4 * 2 * 64;
     for (int idx8 = ver * 512 + tid; idx8 < total8; idx8 += gridDim.x * 512) w1c_gather8(w1p, chan_q, idx8, w1c);
@@ -1088,12 +1095,7 @@ __global__ __launch_bounds__(512) void delta_query_kernel(const float* __restric
       const int i8 = tid + 512 * k;
       if (i8 < R_ITEMS) {
         const int jrow = i8 >> 4, sc = (i8 >> 2) & 3, gq = i8 & 3;
-        if (sc < ns && sc != tp.sl) {
-          const int jb = jrow / S, dj = jrow - jb * S;
-          unsigned* dst = Pr + ((jb * 4 + sc) * S + dj) * 32 + gq * 8;
-          *reinterpret_cast<u32x4*>(dst) = pack4(gv[k][0], sa, 0.0f);
-          *reinterpret_cast<u32x4*>(dst + 4) = pack4(gv[k][1], sa, 0.0f);
-        }
+        if (sc < ns && sc != tp.sl) store_rwords8(Pr, jrow, sc, gq, gv[k][0], gv[k][1], sa, 0.0f);
       }
     }
     // the packed last slice (TailPack): step u of column group jb holds the taps u T .. u T + T - 1 of its n channels
@@ -1106,26 +1108,14 @@ __global__ __launch_bounds__(512) void delta_query_kernel(const float* __restric
   if (tid == 0) *reinterpret_cast<f32x4*>(aa + G * O2) = (f32x4){mx, mn, 0.f, 0.f};
 #pragma unroll
   for (int u = 0; u < 3; ++u) {
-    const int i = tid + 512 * u;
+    const int i = tid + 512 * u;   // (written out: through a2_load / a2_fold this kernel grows from 5217 to 5233 instructions)
     float v = a2raw[i];
 #pragma unroll
     for (int k = 1; k < A2_KSPLIT; ++k) v += a2raw[(size_t)k * A2_ELEMS + i];
     A2l[i] = v;   // (+ c * w1col with c = 0)
   }
   __syncthreads();
-  {
-    const int p = tid & (O2 - 1), jb0 = 6 * (tid >> 7);
-    float wcol[O1];
-#pragma unroll
-    for (int o = 0; o < O1; ++o) wcol[o] = w2sum[o * O2 + p];
-    float sacc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int o = 0; o < O1; ++o)
-#pragma unroll
-      for (int j = 0; j < 6; ++j) sacc[j] = fmaf(A2l[(jb0 + j) * O1 + o], wcol[o], sacc[j]);
-#pragma unroll
-    for (int j = 0; j < 6; ++j) aa[(jb0 + j) * O2 + p] = sacc[j];
-  }
+  aa_product(A2l, w2sum, aa, tid);
 }
 
 // ---- bf16x3 mode: the preparation of a pair --------------------------------------------------------------------------------------
@@ -1179,13 +1169,7 @@ __global__ __launch_bounds__(512) void delta_prepare_bf16x3_kernel(
     const f32x4 a = reinterpret_cast<const f32x4*>(Lf)[i], b = reinterpret_cast<const f32x4*>(Rf)[i];
     mn = fminf(mn, fminf(fminf(fminf(a[0], a[1]), fminf(a[2], a[3])), fminf(fminf(b[0], b[1]), fminf(b[2], b[3]))));
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) mn = fminf(mn, __shfl_down(mn, off, 64));
-  if (lane == 0) red[wave] = mn;
-  __syncthreads();
-  mn = red[0];
-#pragma unroll
-  for (int w = 1; w < NWAVE; ++w) mn = fminf(mn, red[w]);
+  mn = -ovn_wg_max_all<NWAVE>(-mn, red);   // (min = -max of the negated values, exactly)
   const float c = mn < 0.0f ? -mn : 0.0f;
   const bool own_r = ridx != nullptr || c != 0.0f || qwords == nullptr;
   unsigned* Pl = pl + (size_t)pair * OVN_FEAT_ELEMS;
@@ -1212,11 +1196,9 @@ __global__ __launch_bounds__(512) void delta_prepare_bf16x3_kernel(
 #pragma unroll
   for (int u = 0; u < 3; ++u) {
     const int i = tid + 512 * u;
-    const float* src = a2raw + (size_t)(ridx ? pair : 0) * A2_KSPLIT * A2_ELEMS;
-    float v = src[i];
-#pragma unroll
-    for (int k = 1; k < A2_KSPLIT; ++k) v += src[(size_t)k * A2_ELEMS + i];
-    A2l[i] = v + c * w1col[i & (O1 - 1)];
+    float v[A2_KSPLIT];
+    a2_load(a2raw + (size_t)(ridx ? pair : 0) * A2_KSPLIT * A2_ELEMS, i, v);
+    A2l[i] = a2_fold(v) + c * w1col[i & (O1 - 1)];
   }
   // T = b1 + l' Ws: 23 row tiles x 4 n-tiles of 16 x 16, wave = task; k = 16 j + 4 g + e, chain e (as ovn_delta_a2_task)
   for (int task = wave; task < 23 * 4; task += NWAVE) {
@@ -1283,20 +1265,7 @@ __global__ __launch_bounds__(512) void delta_prepare_bf16x3_kernel(
       }
     }
   }
-  // AA[jb][p] = sum_o A2[jb][o] W2s[o][p]
-  {
-    const int p = tid & (O2 - 1), jb0 = 6 * (tid >> 7);
-    float wcol[O1];
-#pragma unroll
-    for (int o = 0; o < O1; ++o) wcol[o] = w2sum[o * O2 + p];
-    float sacc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int o = 0; o < O1; ++o)
-#pragma unroll
-      for (int j = 0; j < 6; ++j) sacc[j] = fmaf(A2l[(jb0 + j) * O1 + o], wcol[o], sacc[j]);
-#pragma unroll
-    for (int j = 0; j < 6; ++j) lp[G * O2 + (jb0 + j) * O2 + p] = sacc[j];
-  }
+  aa_product(A2l, w2sum, lp + G * O2, tid);
 }
 
 // W2s[o][p] = sum_di W2[di][o][p] (fp64 accumulation, rounded once)
@@ -1774,54 +1743,54 @@ static int pick_nsplit(int n) {
   return 1;
 }
 
-// the contraction kernel for n pairs split nsplit ways (pick_nsplit): 45 / 23 = 8-row / one-row-tile passes, one per workgroup; the
-// passes of a pair are independent, so any split (and RT 0 / 1 / 2) gives the same bits
-template <class AR, bool SEG>
-static int launch_c1_t(int n, int nsplit, const DeltaDesc* desc, const void* w1, const f32x4* scales, float* o1raw, int pair0,
-                       const int32_t* lidx, const unsigned* live, const void* w1c, hipStream_t stream, const int32_t* pseg, int seg0) {
-  const size_t lds = t_lds_bytes(3, AR::PLANES);
-  int rc = OVN_OK;
-  if (nsplit == 45) {   // up to five pairs: 8-row passes, one per workgroup
-    rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_c1_kernel<AR, 0, 3, SEG>), lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((delta_c1_kernel<AR, 0, 3, SEG>), dim3(n * nsplit), dim3(512), lds, stream, desc, w1, scales, o1raw, 1, nsplit, pair0,
-                       lidx, live, w1c, pseg, seg0);
-    return OVN_OK;
-  }
-  if constexpr (AR::MAX_RT >= 2) {
-    if (nsplit != 23) {
-      rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_c1_kernel<AR, 2, 3, SEG>), lds);
+static PrepWeights prep_weights(const OvnHeadWeights& hw) {
+  return {reinterpret_cast<const _Float16*>(hw.wsp_h), hw.w1col, hw.b1, reinterpret_cast<const _Float16*>(hw.w2p_h), hw.w2sum, hw.c2.bias,
+          hw.hs.sw1, hw.hs.sw2, hw.hs.sws, hw.hs.w1_colsum, hw.hs.b1_absmax};
+}
+
+// The contraction (profile class delta_c12) and c_conv2 (delta_c2) of a sub-chunk of n pairs prepared in `sc`, in either arithmetic.
+// live / w1c: the compacted K walk of a 1-vs-N sweep and the W1 fragments gathered for it; pseg / seg0: a segmented pass (SEG), where
+// both are per segment.  The contraction is split nsplit ways (pick_nsplit): 45 / 23 = 8-row / one-row-tile passes, one per workgroup;
+// the passes of a pair are independent, so any split (and RT 0 / 1 / 2) gives the same bits.
+template <class AR, bool SEG = false>
+static int run_pass(ovn_ctx* ctx, int n, const OvnDeltaSubScratch& sc, float* o2, hipStream_t stream, int pair0, const int32_t* lidx,
+                    const unsigned* live = nullptr, const void* w1c = nullptr, const int32_t* pseg = nullptr, int seg0 = 0) {
+  constexpr bool F16 = std::is_same<AR, ArithF16x3>::value;
+  const OvnHeadWeights& hw = ctx->head;
+  const DeltaDesc* desc = static_cast<const DeltaDesc*>(sc.desc);
+  {
+    OvnProfScope ps(ctx, OVN_K_DELTA, stream);
+    const int nsplit = pick_nsplit(n);
+    const void* w1 = F16 ? hw.w1p_h : hw.w1p_b3;
+    auto c1 = [&](auto rt) {   // RT row tiles per pass (0: 8-row passes)
+      constexpr int RT = decltype(rt)::value;
+      const size_t lds = t_lds_bytes(3, AR::PLANES);
+      const int rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_c1_kernel<AR, RT, 3, SEG>), lds);
       if (rc) return rc;
-      hipLaunchKernelGGL((delta_c1_kernel<AR, 2, 3, SEG>), dim3(n * nsplit), dim3(512), lds, stream, desc, w1, scales, o1raw, 1, nsplit,
+      hipLaunchKernelGGL((delta_c1_kernel<AR, RT, 3, SEG>), dim3(n * nsplit), dim3(512), lds, stream, desc, w1, sc.scales, sc.o1raw, 1, nsplit,
                          pair0, lidx, live, w1c, pseg, seg0);
-      return OVN_OK;
-    }
+      return (int)OVN_OK;
+    };
+    int rc;
+    if (nsplit == 45) rc = c1(std::integral_constant<int, 0>());   // up to five pairs
+    else if (AR::MAX_RT >= 2 && nsplit != 23) rc = c1(std::integral_constant<int, AR::MAX_RT>());
+    else rc = c1(std::integral_constant<int, 1>());   // a handful of pairs (nsplit 23) -- or every sweep when MAX_RT = 1
+    if (rc) return rc;
   }
-  // one row tile per pass (22 + 1 passes): a handful of pairs, one pass per workgroup (nsplit 23) -- or every sweep when MAX_RT = 1
-  rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_c1_kernel<AR, 1, 3, SEG>), lds);
-  if (rc) return rc;
-  hipLaunchKernelGGL((delta_c1_kernel<AR, 1, 3, SEG>), dim3(n * nsplit), dim3(512), lds, stream, desc, w1, scales, o1raw, 1, nsplit, pair0,
-                     lidx, live, w1c, pseg, seg0);
+  {
+    OvnProfScope ps(ctx, OVN_K_DELTA_C2, stream);
+    const void* w2 = F16 ? hw.w2p_h : hw.w2p_b3;
+    if (n <= 28)   // 9 workgroups of 64 rows per pair, operands several k-steps ahead (a handful of pairs: latency, not throughput)
+      hipLaunchKernelGGL((delta_c2_kernel<AR, 1, 6, 3>), dim3(n * G * G / 64), dim3(256), 0, stream, sc.o1raw, w2, desc, sc.scales, o2, sc.o2max, 1.0f);
+    else
+      hipLaunchKernelGGL((delta_c2_kernel<AR, 3, 3, 1>), dim3(n * G * G / C2_TILE_ROWS), dim3(256), 0, stream, sc.o1raw, w2, desc, sc.scales, o2,
+                         sc.o2max, 1.0f);
+  }
+  OVN_HIP_CHECK(hipGetLastError());
   return OVN_OK;
 }
 
-template <class AR>
-static int launch_c1(int n, int nsplit, const DeltaDesc* desc, const void* w1, const f32x4* scales, float* o1raw, int pair0,
-                     const int32_t* lidx, const unsigned* live, const void* w1c, hipStream_t stream) {
-  return launch_c1_t<AR, false>(n, nsplit, desc, w1, scales, o1raw, pair0, lidx, live, w1c, stream, nullptr, 0);
-}
-
-template <class AR>
-static void launch_c2(int n, const float* o1raw, const void* w2, const DeltaDesc* desc, const f32x4* scales, float* o2, unsigned* o2max,
-                      hipStream_t stream) {
-  const int total_rows = n * G * G;
-  if (n <= 28)   // 9 workgroups of 64 rows per pair, operands several k-steps ahead (a handful of pairs: latency, not throughput)
-    hipLaunchKernelGGL((delta_c2_kernel<AR, 1, 6, 3>), dim3(total_rows / 64), dim3(256), 0, stream, o1raw, w2, desc, scales, o2, o2max, 1.0f);
-  else
-    hipLaunchKernelGGL((delta_c2_kernel<AR, 3, 3, 1>), dim3(total_rows / C2_TILE_ROWS), dim3(256), 0, stream, o1raw, w2, desc, scales, o2, o2max, 1.0f);
-}
-
-// a2 + prepare (profile class delta_prep), c_conv1 contraction (delta_c12), c_conv2 GEMM (delta_c2)
+// The three entry points below keep their own preparation (a2 + prepare kernels, profile class delta_prep) and hand run_pass the rest.
 // Segmented pass (ovn_heads_segments, compaction on): the pairs of several segments, pair p = (feats_l[lidx[p]], feats_r[ridx[p]]) in
 // segment seg.pseg[p].  Each segment's query state -- A2, the query block, the live list and the W1 fragments gathered for it -- is
 // computed ONCE, for all segments of the pass in one launch each; the prepare and contraction kernels find a pair's through pseg.
@@ -1832,37 +1801,19 @@ static int delta_c12_f16x3_segments(ovn_ctx* ctx, const float* feats_l, const in
                                     const OvnSegPass& seg) {
   int rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_prepare_split_kernel<false, true>), PREP_SPLIT_LDS);
   if (rc) return rc;
-  f32x4* scales = sc.scales;
-  unsigned *o2max = sc.o2max, *pl = sc.pl, *pr = sc.pr;
-  float *lin = sc.lin, *o1raw = sc.o1raw;
-  DeltaDesc* desc = static_cast<DeltaDesc*>(sc.desc);
-  float* a2raw = seg.state.a2raw;
-  unsigned *qblock = seg.state.qblock, *live = seg.state.live;
-  _Float16* w1c = seg.state.w1c;
+  const OvnHeadWeights& hw = ctx->head;
+  const OvnDeltaSegScratch& st = seg.state;
   ctx->dbg_live = nullptr;   // (ovn_head_walk_stats describes 1-vs-N sweeps)
-  const int nsplit = pick_nsplit(n);
   {
     OvnProfScope ps(ctx, OVN_K_DELTA_PREP, stream);
-    hipLaunchKernelGGL(delta_a2_kernel, dim3(seg.nseg, A2_KSPLIT), dim3(512), 0, stream, feats_r, seg.qidx + seg.seg0, ctx->w1raw, a2raw);
-    hipLaunchKernelGGL(delta_query_kernel<true>, dim3(QV + QGW, seg.nseg), dim3(512), 0, stream, feats_r, a2raw, ctx->w2sum, qblock, live,
-                       reinterpret_cast<const _Float16*>(ctx->w1p_h), w1c, seg.qidx, seg.offs, seg.seg0);
+    hipLaunchKernelGGL(delta_a2_kernel, dim3(seg.nseg, A2_KSPLIT), dim3(512), 0, stream, feats_r, seg.qidx + seg.seg0, hw.w1raw, st.a2raw);
+    hipLaunchKernelGGL(delta_query_kernel<true>, dim3(QV + QGW, seg.nseg), dim3(512), 0, stream, feats_r, st.a2raw, hw.w2sum, st.qblock,
+                       st.live, reinterpret_cast<const _Float16*>(hw.w1p_h), st.w1c, seg.qidx, seg.offs, seg.seg0);
     hipLaunchKernelGGL((delta_prepare_split_kernel<false, true>), dim3(n), dim3(512), PREP_SPLIT_LDS, stream, feats_l, lidx, feats_r, ridx,
-                       reinterpret_cast<const _Float16*>(ctx->wsp_h), ctx->w1col, ctx->b1, a2raw,
-                       reinterpret_cast<const _Float16*>(ctx->w2p_h), ctx->w2sum, ctx->c2.bias, ctx->hs.sw1, ctx->hs.sw2, ctx->hs.sws,
-                       ctx->hs.w1_colsum, ctx->hs.b1_absmax, 1.0f, scales, o2max, pl, pr, lin, desc, dcache_l, qblock, (float*)nullptr, live,
-                       seg.pseg, seg.seg0);
+                       prep_weights(hw), st.a2raw, 1.0f, sc.scales, sc.o2max, sc.pl, sc.pr, sc.lin, static_cast<DeltaDesc*>(sc.desc), dcache_l,
+                       st.qblock, (float*)nullptr, st.live, seg.pseg, seg.seg0);
   }
-  {
-    OvnProfScope ps(ctx, OVN_K_DELTA, stream);
-    rc = launch_c1_t<ArithF16x3, true>(n, nsplit, desc, ctx->w1p_h, scales, o1raw, 0, lidx, live, w1c, stream, seg.pseg, seg.seg0);
-    if (rc) return rc;
-  }
-  {
-    OvnProfScope ps(ctx, OVN_K_DELTA_C2, stream);
-    launch_c2<ArithF16x3>(n, o1raw, ctx->w2p_h, desc, scales, o2, o2max, stream);
-  }
-  OVN_HIP_CHECK(hipGetLastError());
-  return OVN_OK;
+  return run_pass<ArithF16x3, true>(ctx, n, sc, o2, stream, 0, lidx, st.live, st.w1c, seg.pseg, seg.seg0);
 }
 
 int ovn_delta_c12_f16x3_forward(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r,
@@ -1872,44 +1823,28 @@ int ovn_delta_c12_f16x3_forward(ovn_ctx* ctx, const float* feats_l, const int32_
   if (rc) return rc;
   if (seg) return delta_c12_f16x3_segments(ctx, feats_l, lidx, feats_r, ridx, n, sc, o2, stream, dcache_l, *seg);
   if (ridx) dcache_l = nullptr;   // the cache serves the 1-vs-N form (one query against many cached candidates)
-  f32x4* scales = sc.scales;
-  unsigned *o2max = sc.o2max, *pl = sc.pl, *pr = sc.pr, *qblock = sc.qblock, *live_buf = sc.live;
-  float *lin = sc.lin, *a2raw = sc.a2raw, *o1raw = sc.o1raw;
-  DeltaDesc* desc = static_cast<DeltaDesc*>(sc.desc);
-  _Float16* w1c = sc.w1c;
+  const OvnHeadWeights& hw = ctx->head;
+  const _Float16* w1p = reinterpret_cast<const _Float16*>(hw.w1p_h);
   // 1-vs-N sweeps (one query for all pairs): the query's live-channel list and the W1 fragments gathered for it; indexed pairs walk
   // the plain K (every pair has its own right volume)
-  const unsigned* live = (ridx || !ctx->head_compact) ? nullptr : live_buf;
+  unsigned* live = (ridx || !ctx->head_compact) ? nullptr : sc.live;
   ctx->dbg_live = live;   // ovn_head_walk_stats: the K walk of the most recent sweep (its last chunk)
-  const int nsplit = pick_nsplit(n);   // 45 / 23: 8-row / one-row-tile passes, one per workgroup, chosen for <= 5 / <= 10 pairs
   {
     OvnProfScope ps(ctx, OVN_K_DELTA_PREP, stream);
     if (!a2_done)
-      hipLaunchKernelGGL(delta_a2_kernel, dim3(ridx ? n : 1, A2_KSPLIT), dim3(512), 0, stream, feats_r, ridx, ctx->w1raw, a2raw);
+      hipLaunchKernelGGL(delta_a2_kernel, dim3(ridx ? n : 1, A2_KSPLIT), dim3(512), 0, stream, feats_r, ridx, hw.w1raw, sc.a2raw);
     if (dcache_l) {   // the query kernel also builds the live-channel list and gathers the W1 fragments for it
-      hipLaunchKernelGGL(delta_query_kernel<false>, dim3(live ? QV + QGW : QV), dim3(512), 0, stream, feats_r, a2raw, ctx->w2sum, qblock,
-                         live ? live_buf : nullptr, reinterpret_cast<const _Float16*>(ctx->w1p_h), w1c, (const int32_t*)nullptr,
-                         (const int64_t*)nullptr, 0);
+      hipLaunchKernelGGL(delta_query_kernel<false>, dim3(live ? QV + QGW : QV), dim3(512), 0, stream, feats_r, sc.a2raw, hw.w2sum, sc.qblock,
+                         live, w1p, sc.w1c, (const int32_t*)nullptr, (const int64_t*)nullptr, 0);
     } else if (live) {
-      hipLaunchKernelGGL(delta_live_kernel, dim3(1), dim3(512), 0, stream, feats_r, live_buf);
-      hipLaunchKernelGGL(delta_w1c_kernel, dim3(240), dim3(256), 0, stream, reinterpret_cast<const _Float16*>(ctx->w1p_h), live, w1c);
+      hipLaunchKernelGGL(delta_live_kernel, dim3(1), dim3(512), 0, stream, feats_r, live);
+      hipLaunchKernelGGL(delta_w1c_kernel, dim3(240), dim3(256), 0, stream, w1p, live, sc.w1c);
     }
     hipLaunchKernelGGL(delta_prepare_split_kernel<false>, dim3(n), dim3(512), PREP_SPLIT_LDS, stream, feats_l, lidx, feats_r, ridx,
-                       reinterpret_cast<const _Float16*>(ctx->wsp_h), ctx->w1col, ctx->b1, a2raw,
-                       reinterpret_cast<const _Float16*>(ctx->w2p_h), ctx->w2sum, ctx->c2.bias, ctx->hs.sw1, ctx->hs.sw2, ctx->hs.sws,
-                       ctx->hs.w1_colsum, ctx->hs.b1_absmax, 1.0f, scales, o2max, pl, pr, lin, desc, dcache_l, qblock, (float*)nullptr, live);
+                       prep_weights(hw), sc.a2raw, 1.0f, sc.scales, sc.o2max, sc.pl, sc.pr, sc.lin, static_cast<DeltaDesc*>(sc.desc), dcache_l,
+                       sc.qblock, (float*)nullptr, live);
   }
-  {
-    OvnProfScope ps(ctx, OVN_K_DELTA, stream);
-    rc = launch_c1<ArithF16x3>(n, nsplit, desc, ctx->w1p_h, scales, o1raw, pair0, lidx, live, w1c, stream);
-    if (rc) return rc;
-  }
-  {
-    OvnProfScope ps(ctx, OVN_K_DELTA_C2, stream);
-    launch_c2<ArithF16x3>(n, o1raw, ctx->w2p_h, desc, scales, o2, o2max, stream);
-  }
-  OVN_HIP_CHECK(hipGetLastError());
-  return OVN_OK;
+  return run_pass<ArithF16x3>(ctx, n, sc, o2, stream, pair0, lidx, live, sc.w1c);
 }
 
 // bf16x3 mode (ovn_set_head_precision 2): the scratch layout of the f16x3 path (its query block holds the query's shared words), same
@@ -1918,32 +1853,19 @@ int ovn_delta_c12_bf16x3_forward(ovn_ctx* ctx, const float* feats_l, const int32
                                  int n, const OvnDeltaSubScratch& sc, float* o2, hipStream_t stream, int pair0, bool a2_done) {
   int rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_prepare_bf16x3_kernel), PREP_B3_LDS);
   if (rc) return rc;
-  f32x4* scales = sc.scales;
-  unsigned *o2max = sc.o2max, *pl = sc.pl, *pr = sc.pr;
-  float *lin = sc.lin, *a2raw = sc.a2raw, *o1raw = sc.o1raw;
-  DeltaDesc* desc = static_cast<DeltaDesc*>(sc.desc);
+  const OvnHeadWeights& hw = ctx->head;
   unsigned* qwords = ridx ? nullptr : sc.qblock;   // the query block holds the query's shared words
   ctx->dbg_live = nullptr;   // every pair walks all 128 channels
-  const int nsplit = pick_nsplit(n);
   {
     OvnProfScope ps(ctx, OVN_K_DELTA_PREP, stream);
     if (!a2_done)
-      hipLaunchKernelGGL(delta_a2_kernel, dim3(ridx ? n : 1, A2_KSPLIT), dim3(512), 0, stream, feats_r, ridx, ctx->w1raw, a2raw);
+      hipLaunchKernelGGL(delta_a2_kernel, dim3(ridx ? n : 1, A2_KSPLIT), dim3(512), 0, stream, feats_r, ridx, hw.w1raw, sc.a2raw);
     if (qwords) hipLaunchKernelGGL(delta_qwords_bf16x3_kernel, dim3(12), dim3(512), 0, stream, feats_r, qwords);
-    hipLaunchKernelGGL(delta_prepare_bf16x3_kernel, dim3(n), dim3(512), PREP_B3_LDS, stream, feats_l, lidx, feats_r, ridx, ctx->w1sum,
-                       ctx->w1col, ctx->b1, a2raw, ctx->w2raw, ctx->w2sum, ctx->c2.bias, scales, o2max, pl, pr, qwords, lin, desc);
+    hipLaunchKernelGGL(delta_prepare_bf16x3_kernel, dim3(n), dim3(512), PREP_B3_LDS, stream, feats_l, lidx, feats_r, ridx, hw.w1sum, hw.w1col,
+                       hw.b1, sc.a2raw, hw.w2raw, hw.w2sum, hw.c2.bias, sc.scales, sc.o2max, sc.pl, sc.pr, qwords, sc.lin,
+                       static_cast<DeltaDesc*>(sc.desc));
   }
-  {
-    OvnProfScope ps(ctx, OVN_K_DELTA, stream);
-    rc = launch_c1<ArithBF16x3>(n, nsplit, desc, ctx->w1p_b3, scales, o1raw, pair0, lidx, nullptr, nullptr, stream);
-    if (rc) return rc;
-  }
-  {
-    OvnProfScope ps(ctx, OVN_K_DELTA_C2, stream);
-    launch_c2<ArithBF16x3>(n, o1raw, ctx->w2p_b3, desc, scales, o2, o2max, stream);
-  }
-  OVN_HIP_CHECK(hipGetLastError());
-  return OVN_OK;
+  return run_pass<ArithBF16x3>(ctx, n, sc, o2, stream, pair0, lidx);
 }
 
 // ovn_head_walk_stats: {largest slice count, live channels, slices of passes 0 .. 11, compacted?, 0} of the most recent sweep
@@ -1955,15 +1877,14 @@ int ovn_delta_walk_stats(ovn_ctx* ctx, int32_t* out16, hipStream_t stream) {
     for (int p = 0; p < NPAIR; ++p) out16[2 + p] = 4;
     return OVN_OK;
   }
-  unsigned h[LIVE_WORDS];
-  OVN_HIP_CHECK(hipMemcpyAsync(h, ctx->dbg_live, sizeof(h), hipMemcpyDeviceToHost, stream));
+  LiveRecord h;
+  OVN_HIP_CHECK(hipMemcpyAsync(&h, ctx->dbg_live, sizeof(h), hipMemcpyDeviceToHost, stream));
   OVN_HIP_CHECK(hipStreamSynchronize(stream));
-  out16[0] = (int32_t)h[0];
-  out16[1] = (int32_t)h[1];
-  const unsigned char* nsp = reinterpret_cast<const unsigned char*>(h + 4) + FC;
-  for (int p = 0; p < NPAIR; ++p) out16[2 + p] = nsp[p];
+  out16[0] = (int32_t)h.ns;
+  out16[1] = (int32_t)h.nlive;
+  for (int p = 0; p < NPAIR; ++p) out16[2 + p] = h.table[FC + p];
   out16[14] = 1;
-  out16[15] = nsp[TB_STEPS - FC] < S ? (int32_t)nsp[TB_STEPS - FC] : 0;   // steps of the packed last slice (0: none)
+  out16[15] = h.table[TB_STEPS] < S ? (int32_t)h.table[TB_STEPS] : 0;   // steps of the packed last slice (0: none)
   return OVN_OK;
 }
 
@@ -1971,70 +1892,71 @@ int ovn_delta_walk_stats(ovn_ctx* ctx, int32_t* out16, hipStream_t stream) {
 int ovn_delta_cache_forward(ovn_ctx* ctx, const float* feats, int n, float* cache, hipStream_t stream) {
   int rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_prepare_split_kernel<true>), PREP_SPLIT_LDS);
   if (rc) return rc;
-  hipLaunchKernelGGL(delta_prepare_split_kernel<true>, dim3(n), dim3(512), PREP_SPLIT_LDS, stream, feats, (const int32_t*)nullptr,
-                     (const float*)nullptr, (const int32_t*)nullptr, reinterpret_cast<const _Float16*>(ctx->wsp_h), ctx->w1col, ctx->b1,
-                     (const float*)nullptr, reinterpret_cast<const _Float16*>(ctx->w2p_h), ctx->w2sum, ctx->c2.bias, ctx->hs.sw1,
-                     ctx->hs.sw2, ctx->hs.sws, ctx->hs.w1_colsum, ctx->hs.b1_absmax, 1.0f, (f32x4*)nullptr, (unsigned*)nullptr,
-                     (unsigned*)nullptr, (unsigned*)nullptr, (float*)nullptr, (DeltaDesc*)nullptr, (const float*)nullptr,
-                     (const unsigned*)nullptr, cache, (const unsigned*)nullptr);
+  const float* nof = nullptr;      // no right volume, no A2, no per-pair outputs: a row is all a BUILD workgroup writes
+  const int32_t* noi = nullptr;
+  unsigned* nou = nullptr;
+  hipLaunchKernelGGL(delta_prepare_split_kernel<true>, dim3(n), dim3(512), PREP_SPLIT_LDS, stream, feats, noi, nof, noi, prep_weights(ctx->head),
+                     nof, 1.0f, (f32x4*)nullptr, nou, nou, nou, (float*)nullptr, (DeltaDesc*)nullptr, nof, (const unsigned*)nou, cache,
+                     (const unsigned*)nou);
   OVN_HIP_CHECK(hipGetLastError());
   return OVN_OK;
 }
 
-// Weight statistics (host copies: this call synchronises `stream`, like every weight registration), the tap-summed c_conv1
-// kernel of the linear terms, and the scaled fp16 hi/lo fragments of c_conv1 / c_conv2.
-int ovn_delta_prepare_f16x3(ovn_ctx* ctx, const float* c1_kernel_dev, const float* c1_bias_dev, const float* c2_kernel_dev,
-                            hipStream_t stream) {
-  OvnHeadScales* hs = &ctx->hs;
-  float* stats = nullptr;
-  OVN_HIP_CHECK(hipMalloc((void**)&stats, 6 * sizeof(float)));
-  hipLaunchKernelGGL(delta_wstats_kernel, dim3(1), dim3(256), 0, stream, c1_kernel_dev, K1, O1, stats);
-  hipLaunchKernelGGL(delta_wstats_kernel, dim3(1), dim3(256), 0, stream, c2_kernel_dev, K2, O2, stats + 2);
-  hipLaunchKernelGGL(delta_wstats_kernel, dim3(1), dim3(256), 0, stream, c1_bias_dev, 1, O1, stats + 4);
-  float h[6];
-  hipError_t e = hipMemcpyAsync(h, stats, sizeof(h), hipMemcpyDeviceToHost, stream);
+// {max |w|, max column sum of |w|} (delta_wstats_kernel) of each of the row-major [K][N] matrices `mats`, read back into out[2 m],
+// out[2 m + 1]; synchronises `stream`
+struct WMat {
+  const float* w;
+  int K, N;
+};
+static int weight_stats(std::initializer_list<WMat> mats, float* out, hipStream_t stream) {
+  float* st = nullptr;
+  const size_t bytes = 2 * mats.size() * sizeof(float);
+  OVN_HIP_CHECK(hipMalloc((void**)&st, bytes));
+  int m = 0;
+  for (const WMat& a : mats) hipLaunchKernelGGL(delta_wstats_kernel, dim3(1), dim3(256), 0, stream, a.w, a.K, a.N, st + 2 * m++);
+  hipError_t e = hipMemcpyAsync(out, st, bytes, hipMemcpyDeviceToHost, stream);
   if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  (void)hipFree(stats);
+  (void)hipFree(st);
   OVN_HIP_CHECK(e);
+  return OVN_OK;
+}
+
+// Into the set hw (whose b1 / c2 the caller fills): weight statistics (host copies: this call synchronises `stream`, like every
+// weight registration), the tap-summed c_conv1 kernel of the linear terms, the scaled fp16 hi/lo fragments of c_conv1 / c_conv2 and
+// their bf16x3 planes.  On failure hw keeps what was allocated so far: its owner releases it.
+int ovn_delta_prepare_f16x3(OvnHeadWeights* hw, const float* c1_kernel_dev, const float* c1_bias_dev, const float* c2_kernel_dev,
+                            hipStream_t stream) {
+  OvnHeadScales* hs = &hw->hs;
+  float h[6];
+  int rc = weight_stats({{c1_kernel_dev, K1, O1}, {c2_kernel_dev, K2, O2}, {c1_bias_dev, 1, O1}}, h, stream);
+  if (rc) return rc;
   hs->sw1 = ovn_pow2_scale_for(h[0]);
   hs->w1_colsum = h[1];
   hs->sw2 = ovn_pow2_scale_for(h[2]);
   hs->b1_absmax = h[4];
-  const size_t w1_elems = (size_t)S * FC * O1 * 2;   // hi + lo
-  const size_t w2_elems = (size_t)K2 * O2 * 2;
-  OVN_HIP_CHECK(hipMalloc(&ctx->w1p_h, w1_elems * sizeof(_Float16)));
-  OVN_HIP_CHECK(hipMalloc(&ctx->w2p_h, w2_elems * sizeof(_Float16)));
-  OVN_HIP_CHECK(hipMalloc((void**)&ctx->w1raw, (size_t)K1 * O1 * sizeof(float)));
-  OVN_HIP_CHECK(hipMalloc((void**)&ctx->w1sum, (size_t)FC * O1 * sizeof(float)));
-  OVN_HIP_CHECK(hipMalloc((void**)&ctx->w1col, (size_t)O1 * sizeof(float)));
-  OVN_HIP_CHECK(hipMalloc(&ctx->wsp_h, (size_t)FC * O1 * 2 * sizeof(_Float16)));
-  OVN_HIP_CHECK(hipMalloc((void**)&ctx->w2sum, (size_t)O1 * O2 * sizeof(float)));
-  hipLaunchKernelGGL(delta_w2sum_kernel, dim3((O1 * O2 + 255) / 256), dim3(256), 0, stream, c2_kernel_dev, ctx->w2sum);
-  OVN_HIP_CHECK(hipMemcpyAsync(ctx->w1raw, c1_kernel_dev, (size_t)K1 * O1 * sizeof(float), hipMemcpyDeviceToDevice, stream));
-  hipLaunchKernelGGL(delta_w1sum_kernel, dim3((FC * O1 + 255) / 256), dim3(256), 0, stream, c1_kernel_dev, ctx->w1sum, ctx->w1col);
-  {   // scale of the tap-summed kernel (up to 15x the largest single weight)
-    float* st = nullptr;
-    OVN_HIP_CHECK(hipMalloc((void**)&st, 2 * sizeof(float)));
-    hipLaunchKernelGGL(delta_wstats_kernel, dim3(1), dim3(256), 0, stream, ctx->w1sum, FC, O1, st);
-    float hws[2];
-    hipError_t e2 = hipMemcpyAsync(hws, st, sizeof(hws), hipMemcpyDeviceToHost, stream);
-    if (e2 == hipSuccess) e2 = hipStreamSynchronize(stream);
-    (void)hipFree(st);
-    OVN_HIP_CHECK(e2);
-    hs->sws = ovn_pow2_scale_for(hws[0]);
-  }
-  hipLaunchKernelGGL(delta_prep_ws_f16_kernel, dim3(32), dim3(256), 0, stream, ctx->w1sum, reinterpret_cast<_Float16*>(ctx->wsp_h), hs->sws);
-  hipLaunchKernelGGL(delta_prep_w1_f16_kernel, dim3(240), dim3(256), 0, stream, c1_kernel_dev,
-                     reinterpret_cast<_Float16*>(ctx->w1p_h), hs->sw1);
-  hipLaunchKernelGGL(delta_prep_w2_f16_kernel, dim3(240), dim3(256), 0, stream, c2_kernel_dev,
-                     reinterpret_cast<_Float16*>(ctx->w2p_h), hs->sw2);
+  OVN_HIP_CHECK(hipMalloc(&hw->w1p_h, (size_t)K1 * O1 * 2 * sizeof(_Float16)));   // hi + lo
+  OVN_HIP_CHECK(hipMalloc(&hw->w2p_h, (size_t)K2 * O2 * 2 * sizeof(_Float16)));
+  OVN_HIP_CHECK(hipMalloc((void**)&hw->w1raw, (size_t)K1 * O1 * sizeof(float)));
+  OVN_HIP_CHECK(hipMalloc((void**)&hw->w1sum, (size_t)FC * O1 * sizeof(float)));
+  OVN_HIP_CHECK(hipMalloc((void**)&hw->w1col, (size_t)O1 * sizeof(float)));
+  OVN_HIP_CHECK(hipMalloc(&hw->wsp_h, (size_t)FC * O1 * 2 * sizeof(_Float16)));
+  OVN_HIP_CHECK(hipMalloc((void**)&hw->w2sum, (size_t)O1 * O2 * sizeof(float)));
+  hipLaunchKernelGGL(delta_w2sum_kernel, dim3((O1 * O2 + 255) / 256), dim3(256), 0, stream, c2_kernel_dev, hw->w2sum);
+  OVN_HIP_CHECK(hipMemcpyAsync(hw->w1raw, c1_kernel_dev, (size_t)K1 * O1 * sizeof(float), hipMemcpyDeviceToDevice, stream));
+  hipLaunchKernelGGL(delta_w1sum_kernel, dim3((FC * O1 + 255) / 256), dim3(256), 0, stream, c1_kernel_dev, hw->w1sum, hw->w1col);
+  rc = weight_stats({{hw->w1sum, FC, O1}}, h, stream);   // scale of the tap-summed kernel (up to 15x the largest single weight)
+  if (rc) return rc;
+  hs->sws = ovn_pow2_scale_for(h[0]);
+  hipLaunchKernelGGL(delta_prep_ws_f16_kernel, dim3(32), dim3(256), 0, stream, hw->w1sum, reinterpret_cast<_Float16*>(hw->wsp_h), hs->sws);
+  hipLaunchKernelGGL(delta_prep_w1_f16_kernel, dim3(240), dim3(256), 0, stream, c1_kernel_dev, reinterpret_cast<_Float16*>(hw->w1p_h), hs->sw1);
+  hipLaunchKernelGGL(delta_prep_w2_f16_kernel, dim3(240), dim3(256), 0, stream, c2_kernel_dev, reinterpret_cast<_Float16*>(hw->w2p_h), hs->sw2);
   // bf16x3 mode: three bf16 planes of c_conv1 / c_conv2, c_conv2 as registered (B operand of TT)
-  OVN_HIP_CHECK(hipMalloc(&ctx->w1p_b3, (size_t)S * FC * O1 * 3 * sizeof(__bf16)));
-  OVN_HIP_CHECK(hipMalloc(&ctx->w2p_b3, (size_t)K2 * O2 * 3 * sizeof(__bf16)));
-  OVN_HIP_CHECK(hipMalloc((void**)&ctx->w2raw, (size_t)K2 * O2 * sizeof(float)));
-  hipLaunchKernelGGL(delta_prep_w1_bf16x3_kernel, dim3(240), dim3(256), 0, stream, c1_kernel_dev, reinterpret_cast<__bf16*>(ctx->w1p_b3));
-  hipLaunchKernelGGL(delta_prep_w2_bf16x3_kernel, dim3(240), dim3(256), 0, stream, c2_kernel_dev, reinterpret_cast<__bf16*>(ctx->w2p_b3));
-  OVN_HIP_CHECK(hipMemcpyAsync(ctx->w2raw, c2_kernel_dev, (size_t)K2 * O2 * sizeof(float), hipMemcpyDeviceToDevice, stream));
+  OVN_HIP_CHECK(hipMalloc(&hw->w1p_b3, (size_t)K1 * O1 * 3 * sizeof(__bf16)));
+  OVN_HIP_CHECK(hipMalloc(&hw->w2p_b3, (size_t)K2 * O2 * 3 * sizeof(__bf16)));
+  OVN_HIP_CHECK(hipMalloc((void**)&hw->w2raw, (size_t)K2 * O2 * sizeof(float)));
+  hipLaunchKernelGGL(delta_prep_w1_bf16x3_kernel, dim3(240), dim3(256), 0, stream, c1_kernel_dev, reinterpret_cast<__bf16*>(hw->w1p_b3));
+  hipLaunchKernelGGL(delta_prep_w2_bf16x3_kernel, dim3(240), dim3(256), 0, stream, c2_kernel_dev, reinterpret_cast<__bf16*>(hw->w2p_b3));
+  OVN_HIP_CHECK(hipMemcpyAsync(hw->w2raw, c2_kernel_dev, (size_t)K2 * O2 * sizeof(float), hipMemcpyDeviceToDevice, stream));
   OVN_HIP_CHECK(hipGetLastError());
   return OVN_OK;
 }

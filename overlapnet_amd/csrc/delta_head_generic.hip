@@ -106,7 +106,7 @@ int ovn_delta_generic_c1_wide(const ovn_ctx* ctx, int FW, const float* feats_l, 
   if (rc) return rc;
   const int nib = (FW + IB - 1) / IB;
   hipLaunchKernelGGL(delta_c1_generic_kernel<double>, dim3((unsigned)(nib * G * n)), dim3(256), lds, stream, feats_l, lidx, feats_r, ridx,
-                     ctx->w1raw, ctx->b1, s, G, FW, out1);
+                     ctx->head.w1raw, ctx->head.b1, s, G, FW, out1);
   OVN_HIP_CHECK(hipGetLastError());
   return OVN_OK;
 }
@@ -124,13 +124,13 @@ int ovn_delta_generic_forward(const ovn_ctx* ctx, const float* feats_l, const in
   if (rc) return rc;
   const int nib = (FW + IB - 1) / IB;
   hipLaunchKernelGGL(delta_c1_generic_kernel<float>, dim3((unsigned)(nib * G * n)), dim3(256), lds, stream, feats_l, lidx, feats_r, ridx,
-                     ctx->w1raw, ctx->b1, s, G, FW, out1);
+                     ctx->head.w1raw, ctx->head.b1, s, G, FW, out1);
   OVN_HIP_CHECK(hipGetLastError());
   int oh = 0, ow = 0;
-  rc = ovn_conv_forward(ctx->c2, out1, n, FW, G, o2, &oh, &ow, stream);          // (n, W, G, 64) -> (n, G, G, 128), s x 1 / stride (s, 1)
+  rc = ovn_conv_forward(ctx->head.c2, out1, n, FW, G, o2, &oh, &ow, stream);          // (n, W, G, 64) -> (n, G, G, 128), s x 1 / stride (s, 1)
   if (rc) return rc;
   OVN_REQUIRE(oh == G && ow == G, OVN_ERR_STATE, "general Delta head: c_conv2 produced %dx%d, expected %dx%d", oh, ow, G, G);
-  rc = ovn_conv_forward(ctx->c3, o2, n, G, G, o3, &oh, &ow, stream);              // -> (n, G - 2, G - 2, 256)
+  rc = ovn_conv_forward(ctx->head.c3, o2, n, G, G, o3, &oh, &ow, stream);              // -> (n, G - 2, G - 2, 256)
   if (rc) return rc;
   return ovn_dense_sigmoid_forward(ctx, o3, n, (long long)(G - 2) * (G - 2) * OVN_C3_OUT, overlap, logit, stream);
 }

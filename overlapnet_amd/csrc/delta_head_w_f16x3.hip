@@ -8,7 +8,7 @@
 // Arithmetic: as delta_head_f16x3.hip's header defines it.  Every operand x is scaled by a power of two and written hi + lo
 // (hi = fp16_rtz(x), lo = fp16_rne(x - hi)); a w = a_hi w_hi + a_lo w_hi + a_hi w_lo, three MFMAs in that order per product, the
 // scales divided out of the fp32 accumulators.  Weight fragments and their static scales are the ones the 360 path registers
-// (ctx->w1p_h, ctx->w2p_h, ctx->hs): no operand of its own.
+// (ctx->head.w1p_h, ctx->head.w2p_h, ctx->head.hs): no operand of its own.
 //
 // The DeltaLayer in ABS FORM: |l - r| is formed in fp32 registers, then split.  The min form of the 360 path buys its cheap inner
 // loop (one v_min_u32 per element) with packed copies of both volumes and two linear terms pushed through c_conv2: three more
@@ -25,13 +25,13 @@
 //   o1  = acc1 / (sa sw1) + b1;   o2 = relu(acc2 / (s1 sw2) + b2)
 //
 // One workgroup (8 waves) per pair, for each column group jb:
-//   GEMM1  (R x 1920) x (1920 x 64): 60 MFMA steps u = 15 s + dj (channel slice s, tap dj: the K order of ctx->w1p_h).  Row tiles
+//   GEMM1  (R x 1920) x (1920 x 64): 60 MFMA steps u = 15 s + dj (channel slice s, tap dj: the K order of ctx->head.w1p_h).  Row tiles
 //          go to the waves interleaved, tile = 24 pass + wave + 8 t (t < 3), in ceil(ntiles / 24) passes (1 for R <= 384, else 2);
 //          a lane holds its rows of l (scaled, channels 32 g .. 32 g + 31) in registers for the pass, the 15 rows of r sit in LDS
 //          (scaled).  The pass is compiled per tile count of a wave (0..3): straight-line steps, no branch around an MFMA.
 //          The W1 fragments of a step (8 KB) are shared by all waves through a double-buffered LDS window, one barrier per step.
 //   o1     (+ b1, scaled by s1, split) goes to LDS as the hi and lo fp16 A images of GEMM2, [plane][G][968]: row ib, position
-//          k' = 64 di + 4 (o & 15) + (o >> 4), the K order of ctx->w2p_h.  Rows >= R are computed on zeros and dropped here.
+//          k' = 64 di + 4 (o & 15) + (o >> 4), the K order of ctx->head.w2p_h.  Rows >= R are computed on zeros and dropped here.
 //   GEMM2  (G x 960) x (960 x 128): wave w owns output channels 16 w .. 16 w + 15 for all ceil(G / 16) row tiles; padding rows
 //          (>= G) are clamped reads and never stored.
 // LDS: 2 G 1936 + 7680 + 16384 bytes: 155,712 at G = 34.  Every output element is summed in one fixed order that depends on W alone.
@@ -320,7 +320,7 @@ int launch_split(const ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, 
   int rc = ovn_allow_dynamic_lds(reinterpret_cast<const void*>(delta_c12_w_split_kernel<MT>), lds_bytes(G_MAX));
   if (rc) return rc;
   hipLaunchKernelGGL((delta_c12_w_split_kernel<MT>), dim3(n), dim3(512), lds_bytes(W / S), stream, feats_l, lidx, feats_r, ridx,
-                     reinterpret_cast<const u32x4*>(ctx->w1p_h), ctx->b1, reinterpret_cast<const u32x4*>(ctx->w2p_h), ctx->c2.bias,
+                     reinterpret_cast<const u32x4*>(ctx->head.w1p_h), ctx->head.b1, reinterpret_cast<const u32x4*>(ctx->head.w2p_h), ctx->head.c2.bias,
                      scales, W, 1.0f, o2);
   OVN_HIP_CHECK(hipGetLastError());
   return OVN_OK;
@@ -336,14 +336,14 @@ size_t ovn_delta_w_split_pair_bytes() { return sizeof(f32x4); }
 int ovn_delta_w_split_c12_forward(ovn_ctx* ctx, const float* feats_l, const int32_t* lidx, const float* feats_r, const int32_t* ridx,
                                   int n, void* scales, float* o2, hipStream_t stream) {
   const int W = ctx->feat_w, G = W / S;
-  OVN_REQUIRE(ctx->head_s == S && G == ctx->head_g && W >= OVN_FEAT_W_MIN && W <= OVN_FEAT_W_MAX && ctx->w1p_h && ctx->w2p_h,
+  OVN_REQUIRE(ctx->head_s == S && G == ctx->head_g && W >= OVN_FEAT_W_MIN && W <= OVN_FEAT_W_MAX && ctx->head.w1p_h && ctx->head.w2p_h,
               OVN_ERR_STATE, "split Delta head at width %d: geometry (conv1size %d, %d groups) or operands do not match", W,
               ctx->head_s, ctx->head_g);
   f32x4* sc = static_cast<f32x4*>(scales);
   {
     OvnProfScope ps(ctx, OVN_K_DELTA_PREP, stream);
-    hipLaunchKernelGGL(delta_w_split_prepare_kernel, dim3(n), dim3(256), 0, stream, feats_l, lidx, feats_r, ridx, W, ctx->hs.sw1,
-                       ctx->hs.sw2, ctx->hs.w1_colsum, ctx->hs.b1_absmax, sc);
+    hipLaunchKernelGGL(delta_w_split_prepare_kernel, dim3(n), dim3(256), 0, stream, feats_l, lidx, feats_r, ridx, W, ctx->head.hs.sw1,
+                       ctx->head.hs.sw2, ctx->head.hs.w1_colsum, ctx->head.hs.b1_absmax, sc);
     OVN_HIP_CHECK(hipGetLastError());
   }
   OvnProfScope ps(ctx, OVN_K_DELTA, stream);

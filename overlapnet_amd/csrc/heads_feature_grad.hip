@@ -280,9 +280,9 @@ int ovn_delta_data_grad(ovn_ctx* ctx, int FW, const float* feats_l, const int32_
   const int s = ctx->head_s, G = ctx->head_g, R = s * G;
   OvnProfScope ps(ctx, OVN_K_DELTA_PREP, stream);
   hipLaunchKernelGGL(delta_dl_kernel, dim3((unsigned)((R + 15) / 16), (unsigned)np), dim3(512), 0, stream, feats_l, lidx, feats_r, ridx,
-                     dO1, ctx->w1raw, s, G, FW, dfeat_l);
+                     dO1, ctx->head.w1raw, s, G, FW, dfeat_l);
   hipLaunchKernelGGL(delta_dr_kernel, dim3((unsigned)R, (unsigned)np), dim3(512), 0, stream, feats_l, lidx, feats_r, ridx, dO1,
-                     ctx->w1raw, s, G, FW, dfeat_r);
+                     ctx->head.w1raw, s, G, FW, dfeat_r);
   OVN_HIP_CHECK(hipGetLastError());
   return OVN_OK;
 }

@@ -118,25 +118,9 @@ int ovn_destroy(ovn_ctx* ctx) {
   OVN_ON_DEVICE(ctx->device);
   (void)hipDeviceSynchronize();
   for (auto& l : ctx->leg) ovn_conv_release(&l);
-  ovn_conv_release(&ctx->c2);
-  ovn_conv_release(&ctx->c3);
+  ctx->head.release();
   ovn_conv_release(&ctx->dft);
   if (ctx->tw64) (void)hipFree(ctx->tw64);
-  if (ctx->w1p) (void)hipFree(ctx->w1p);
-  if (ctx->b1) (void)hipFree(ctx->b1);
-  if (ctx->wd) (void)hipFree(ctx->wd);
-  if (ctx->bd) (void)hipFree(ctx->bd);
-  if (ctx->w1p_h) (void)hipFree(ctx->w1p_h);
-  if (ctx->w2p_h) (void)hipFree(ctx->w2p_h);
-  if (ctx->w1raw) (void)hipFree(ctx->w1raw);
-  if (ctx->w1sum) (void)hipFree(ctx->w1sum);
-  if (ctx->w1col) (void)hipFree(ctx->w1col);
-  if (ctx->wsp_h) (void)hipFree(ctx->wsp_h);
-  if (ctx->w2sum) (void)hipFree(ctx->w2sum);
-  if (ctx->w1p_b3) (void)hipFree(ctx->w1p_b3);
-  if (ctx->w2p_b3) (void)hipFree(ctx->w2p_b3);
-  if (ctx->w2raw) (void)hipFree(ctx->w2raw);
-  if (ctx->w3raw) (void)hipFree(ctx->w3raw);
   if (ctx->ws) (void)hipFree(ctx->ws);
   if (ctx->norm_buf) (void)hipFree(ctx->norm_buf);
   if (ctx->actmax) (void)hipFree(ctx->actmax);
@@ -215,96 +199,73 @@ int ovn_set_leg_layer_weights(ovn_ctx* ctx, int layer, const float* kernel_dev, 
   return OVN_OK;
 }
 
+void OvnHeadWeights::release() {
+  ovn_conv_release(&c2);
+  ovn_conv_release(&c3);
+  for (void* p : {(void*)w1p, (void*)b1, w1p_h, w2p_h, (void*)w1raw, (void*)w1sum, (void*)w1col, wsp_h, (void*)w2sum, w1p_b3, w2p_b3,
+                  (void*)w2raw, (void*)w3raw, (void*)wd, (void*)bd})
+    if (p) (void)hipFree(p);
+  *this = OvnHeadWeights();
+}
+
+// a device copy of n floats registered with the head
+static int head_keep(float** dst, const float* src, size_t n, hipStream_t stream) {
+  OVN_HIP_CHECK(hipMalloc((void**)dst, n * sizeof(float)));
+  OVN_HIP_CHECK(hipMemcpyAsync(*dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, stream));
+  return OVN_OK;
+}
+
+static OvnConvLayer head_conv(const char* name, int kh, int kw, int cin, int cout, int sh) {
+  OvnConvLayer L;
+  L.name = name;
+  L.kh = kh;
+  L.kw = kw;
+  L.cin = cin;
+  L.cout = cout;
+  L.sh = sh;
+  L.sw = 1;
+  L.relu = 1;
+  return L;
+}
+
+// Every copy of a head weight set for conv1size hs and hg column groups into the (empty) set N; synchronises `stream`.  On failure N
+// holds whatever was allocated so far: the caller releases it.
+static int head_weights_prepare(OvnHeadWeights* N, int hs, int hg, const float* c1k, const float* c1b, const float* c2k, const float* c2b,
+                                const float* c3k, const float* c3b, const float* dk, const float* db, hipStream_t stream) {
+  const bool general = (hs != OVN_S);   // any other conv1size: general fp32 path (delta_head_generic.hip), no fast-path operands
+  int rc = general ? head_keep(&N->w1raw, c1k, (size_t)hs * OVN_FEAT_C * OVN_C1_OUT, stream) : ovn_delta_prepare_w1(N, c1k, stream);
+  if (rc == OVN_OK) rc = head_keep(&N->b1, c1b, OVN_C1_OUT, stream);
+  // c_conv2 (15,1,64,128): as a GEMM operand it is the [960][128] matrix, k = di*64 + o
+  N->c2 = head_conv("c_conv2", hs, 1, OVN_C1_OUT, OVN_C2_OUT, hs);
+  if (rc == OVN_OK) rc = ovn_conv_prepare(&N->c2, c2k, c2b, stream);
+  if (rc == OVN_OK && !general) rc = ovn_delta_prepare_f16x3(N, c1k, c1b, c2k, stream);
+  N->c3 = head_conv("c_conv3", 3, 3, OVN_C2_OUT, OVN_C3_OUT, 1);
+  if (rc == OVN_OK) rc = ovn_conv_prepare(&N->c3, c3k, c3b, stream);
+  if (rc == OVN_OK && !general) rc = ovn_conv_prepare_f16x3(&N->c3, c3k, stream);
+  // Keras-order copies for ovn_delta_head_grad: W3 always, W2 where the fast-path preparation above did not leave one
+  if (rc == OVN_OK) rc = head_keep(&N->w3raw, c3k, (size_t)9 * OVN_C2_OUT * OVN_C3_OUT, stream);
+  if (rc == OVN_OK && !N->w2raw) rc = head_keep(&N->w2raw, c2k, (size_t)hs * OVN_C1_OUT * OVN_C2_OUT, stream);
+  if (rc == OVN_OK) rc = head_keep(&N->wd, dk, (size_t)(hg - 2) * (hg - 2) * OVN_C3_OUT, stream);   // 123904 at conv1size 15
+  if (rc == OVN_OK) rc = head_keep(&N->bd, db, 1, stream);
+  if (rc == OVN_OK) OVN_HIP_CHECK(hipStreamSynchronize(stream));
+  return rc;
+}
+
 int ovn_set_head_weights(ovn_ctx* ctx, const float* c1k, const float* c1b, const float* c2k, const float* c2b,
                          const float* c3k, const float* c3b, const float* dk, const float* db, void* stream_) {
   OVN_REQUIRE(ctx && c1k && c1b && c2k && c2b && c3k && c3b && dk && db, OVN_ERR_ARG, "ovn_set_head_weights: NULL argument");
   OVN_ON_DEVICE(ctx->device);
-  hipStream_t stream = (hipStream_t)stream_;
-  {  // drop whatever an earlier (possibly half-failed) call left behind
-    ovn_conv_release(&ctx->c2);
-    ovn_conv_release(&ctx->c3);
-    if (ctx->w1p) (void)hipFree(ctx->w1p);
-    if (ctx->b1) (void)hipFree(ctx->b1);
-    if (ctx->wd) (void)hipFree(ctx->wd);
-    if (ctx->bd) (void)hipFree(ctx->bd);
-    if (ctx->w1p_h) (void)hipFree(ctx->w1p_h);
-    if (ctx->w2p_h) (void)hipFree(ctx->w2p_h);
-    if (ctx->w1raw) (void)hipFree(ctx->w1raw);
-    if (ctx->w1sum) (void)hipFree(ctx->w1sum);
-    if (ctx->w1col) (void)hipFree(ctx->w1col);
-    if (ctx->wsp_h) (void)hipFree(ctx->wsp_h);
-      if (ctx->w2sum) (void)hipFree(ctx->w2sum);
-    if (ctx->w1p_b3) (void)hipFree(ctx->w1p_b3);
-    if (ctx->w2p_b3) (void)hipFree(ctx->w2p_b3);
-    if (ctx->w2raw) (void)hipFree(ctx->w2raw);
-    if (ctx->w3raw) (void)hipFree(ctx->w3raw);
-    ctx->w3raw = nullptr;
-    ctx->w1p_h = ctx->w2p_h = ctx->wsp_h = ctx->w1p_b3 = ctx->w2p_b3 = nullptr;
-    ctx->w1raw = ctx->w1sum = ctx->w1col = ctx->w2sum = ctx->w2raw = nullptr;
-    ctx->w1p = ctx->b1 = ctx->wd = ctx->bd = nullptr;
-    ctx->head_set = false;
+  const int hg = ctx_feat_w(ctx) / ctx->head_s;   // G of the Dense kernel registered below
+  OVN_REQUIRE(hg >= 3, OVN_ERR_ARG, "ovn_set_head_weights: conv1size %d leaves %d column groups, c_conv3 needs 3", ctx->head_s, hg);
+  OvnHeadWeights N;   // the new set is built beside the one in use, which keeps serving (head_set unchanged) on failure
+  const int rc = head_weights_prepare(&N, ctx->head_s, hg, c1k, c1b, c2k, c2b, c3k, c3b, dk, db, (hipStream_t)stream_);
+  if (rc) {
+    N.release();
+    return rc;
   }
-  ctx->head_g = ctx_feat_w(ctx) / ctx->head_s;   // G of the Dense kernel registered below
-  const int hs = ctx->head_s, hg = ctx->head_g;
-  OVN_REQUIRE(hg >= 3, OVN_ERR_ARG, "ovn_set_head_weights: conv1size %d leaves %d column groups, c_conv3 needs 3", hs, hg);
-  const bool general = (hs != OVN_S);   // any other conv1size: general fp32 path (delta_head_generic.hip), no fast-path operands
-  int rc = OVN_OK;
-  if (!general) {
-    rc = ovn_delta_prepare_w1(c1k, &ctx->w1p, stream);
-    if (rc) return rc;
-  } else {
-    const size_t w1_bytes = (size_t)hs * OVN_FEAT_C * OVN_C1_OUT * sizeof(float);
-    OVN_HIP_CHECK(hipMalloc((void**)&ctx->w1raw, w1_bytes));
-    OVN_HIP_CHECK(hipMemcpyAsync(ctx->w1raw, c1k, w1_bytes, hipMemcpyDeviceToDevice, stream));
-  }
-  OVN_HIP_CHECK(hipMalloc((void**)&ctx->b1, OVN_C1_OUT * sizeof(float)));
-  OVN_HIP_CHECK(hipMemcpyAsync(ctx->b1, c1b, OVN_C1_OUT * sizeof(float), hipMemcpyDeviceToDevice, stream));
-  // c_conv2 (15,1,64,128): as a GEMM operand it is the [960][128] matrix, k = di*64 + o
-  ctx->c2 = OvnConvLayer();
-  ctx->c2.name = "c_conv2";
-  ctx->c2.kh = hs;
-  ctx->c2.kw = 1;
-  ctx->c2.cin = OVN_C1_OUT;
-  ctx->c2.cout = OVN_C2_OUT;
-  ctx->c2.sh = hs;
-  ctx->c2.sw = 1;
-  ctx->c2.relu = 1;
-  rc = ovn_conv_prepare(&ctx->c2, c2k, c2b, stream);
-  if (rc) return rc;
-  if (!general) {
-    rc = ovn_delta_prepare_f16x3(ctx, c1k, c1b, c2k, stream);
-    if (rc) return rc;
-  }
-  ctx->c3 = OvnConvLayer();
-  ctx->c3.name = "c_conv3";
-  ctx->c3.kh = 3;
-  ctx->c3.kw = 3;
-  ctx->c3.cin = OVN_C2_OUT;
-  ctx->c3.cout = OVN_C3_OUT;
-  ctx->c3.sh = 1;
-  ctx->c3.sw = 1;
-  ctx->c3.relu = 1;
-  rc = ovn_conv_prepare(&ctx->c3, c3k, c3b, stream);
-  if (rc) return rc;
-  if (!general) {
-    rc = ovn_conv_prepare_f16x3(&ctx->c3, c3k, stream);
-    if (rc) return rc;
-  }
-  // Keras-order copies for ovn_delta_head_grad: W3 always, W2 where the fast-path preparation above did not leave one
-  const size_t w3_bytes = (size_t)9 * OVN_C2_OUT * OVN_C3_OUT * sizeof(float);
-  OVN_HIP_CHECK(hipMalloc((void**)&ctx->w3raw, w3_bytes));
-  OVN_HIP_CHECK(hipMemcpyAsync(ctx->w3raw, c3k, w3_bytes, hipMemcpyDeviceToDevice, stream));
-  if (!ctx->w2raw) {
-    const size_t w2_bytes = (size_t)hs * OVN_C1_OUT * OVN_C2_OUT * sizeof(float);
-    OVN_HIP_CHECK(hipMalloc((void**)&ctx->w2raw, w2_bytes));
-    OVN_HIP_CHECK(hipMemcpyAsync(ctx->w2raw, c2k, w2_bytes, hipMemcpyDeviceToDevice, stream));
-  }
-  const size_t dense_in = (size_t)(hg - 2) * (hg - 2) * OVN_C3_OUT;   // 123904 at conv1size 15
-  OVN_HIP_CHECK(hipMalloc((void**)&ctx->wd, dense_in * sizeof(float)));
-  OVN_HIP_CHECK(hipMalloc((void**)&ctx->bd, sizeof(float)));
-  OVN_HIP_CHECK(hipMemcpyAsync(ctx->wd, dk, dense_in * sizeof(float), hipMemcpyDeviceToDevice, stream));
-  OVN_HIP_CHECK(hipMemcpyAsync(ctx->bd, db, sizeof(float), hipMemcpyDeviceToDevice, stream));
-  OVN_HIP_CHECK(hipStreamSynchronize(stream));
+  ctx->head.release();   // hipFree waits for whatever still reads the old copies
+  ctx->head = N;
+  ctx->head_g = hg;
   ctx->head_set = true;
   return OVN_OK;
 }
@@ -884,7 +845,7 @@ static int delta_head_run(ovn_ctx* ctx, const float* feats_l, const int32_t* lid
         int oh = 0, ow = 0;
         {
           OvnProfScope ps(ctx, OVN_K_C3, st);
-          rc = ovn_conv_forward(ctx->c3, o2s, np, OVN_G, OVN_G, o3s, &oh, &ow, st);
+          rc = ovn_conv_forward(ctx->head.c3, o2s, np, OVN_G, OVN_G, o3s, &oh, &ow, st);
         }
         if (rc) return rc;
         OvnProfScope ps(ctx, OVN_K_DENSE, st);

@@ -130,6 +130,32 @@ __device__ __forceinline__ float ovn_wg_max_all(float m, float* red) {
   return m;
 }
 
+// The largest AND the smallest, in the two halves of ovn_wg_max_all for a caller that has LDS work of its own to put in front of the
+// barrier: _put = the wave reductions and the waves' words (red[w] maxima, red[NWAVES + w] minima), then the CALLER's barrier, then
+// _get on every thread.  `red`: 2 NWAVES floats, under the rule above.
+template <int NWAVES>
+__device__ __forceinline__ void ovn_wg_minmax_put(float mx, float mn, float* red) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    mx = fmaxf(mx, __shfl_down(mx, off, 64));
+    mn = fminf(mn, __shfl_down(mn, off, 64));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6] = mx;
+    red[NWAVES + (threadIdx.x >> 6)] = mn;
+  }
+}
+template <int NWAVES>
+__device__ __forceinline__ void ovn_wg_minmax_get(const float* red, float& mx, float& mn) {
+  mx = red[0];
+  mn = red[NWAVES];
+#pragma unroll
+  for (int w = 1; w < NWAVES; ++w) {
+    mx = fmaxf(mx, red[w]);
+    mn = fminf(mn, red[NWAVES + w]);
+  }
+}
+
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
@@ -289,16 +315,10 @@ struct OvnConvLayer {
   float* wraw = nullptr;  // leg layers: the kernel as registered, (kh, kw, cin, cout): B operand of the data gradient (leg_backward.hip)
 };
 
-struct ovn_ctx {
-  int device = 0;
-  int in_h = 0, in_w = 0, in_c = 0;
-  std::vector<OvnConvLayer> leg;
-  bool finalized = false;
-  int feat_w = 0;
-  // head
-  bool head_set = false;
-  int head_s = OVN_S;      // conv1NetworkHead_conv1size (ovn_set_head_geometry); the fast Delta paths serve 15, anything else the
-  int head_g = OVN_G;      // general fp32 path of delta_head_generic.hip; head_g = 360 // head_s
+// Every device copy the heads keep of the registered head weights, and their static scales: ONE owner.  ovn_set_head_weights builds a
+// whole new set beside the one in use and swaps it in only when all of it exists (as ovn_set_leg_layer_weights does for a leg layer);
+// release() is the one place that frees a set.
+struct OvnHeadWeights {
   float* w1p = nullptr;  // c_conv1 in the K-permuted fragment order of the fused kernel
   float* b1 = nullptr;
   OvnConvLayer c2;       // c_conv2 as a [960][128] GEMM operand in fragment order
@@ -314,7 +334,23 @@ struct ovn_ctx {
   void* w2p_b3 = nullptr;
   float* w2raw = nullptr;  // c_conv2 kernel as registered, [960][128] (k = di * 64 + o): B operand of TT in bf16x3 mode
   float* w3raw = nullptr;  // c_conv3 kernel as registered, [3][3][128][256]: the data gradient of ovn_delta_head_grad
+  float* wd = nullptr;     // dense kernel [123904]
+  float* bd = nullptr;     // dense bias [1]
   OvnHeadScales hs;
+  void release();          // frees every buffer and leaves an empty set (ovn_api.hip)
+};
+
+struct ovn_ctx {
+  int device = 0;
+  int in_h = 0, in_w = 0, in_c = 0;
+  std::vector<OvnConvLayer> leg;
+  bool finalized = false;
+  int feat_w = 0;
+  // head
+  bool head_set = false;
+  int head_s = OVN_S;      // conv1NetworkHead_conv1size (ovn_set_head_geometry); the fast Delta paths serve 15, anything else the
+  int head_g = OVN_G;      // general fp32 path of delta_head_generic.hip; head_g = 360 // head_s
+  OvnHeadWeights head;     // every device copy of the registered head weights (valid while head_set)
   int leg_mode = 1;        // 0 = fp32 MFMA (conv_f32.hip), 1 = scaled 3-term fp16 split on the fp16 MFMA (conv_f16x3.hip)
   int head_compact = 1;    // ovn_set_head_compaction: 1 = 1-vs-N sweeps drop the query's dead channels from the Delta contraction (exact)
   int proj_trig = 0;       // ovn_set_projection_trig: 0 = NumPy-on-AVX512 (SVML) float32 angles, 1 = correctly rounded float32 angles
@@ -322,8 +358,6 @@ struct ovn_ctx {
   int head_mode = 1;       // 0 = fp32 MFMA (exact fp32), 1 = scaled 3-term fp16 split on the fp16 MFMA (default),
                            // 2 = exact 3-term bf16 split on the bf16 MFMA (operands at least as wide as fp32)
   int head_width_split = 0;  // ovn_set_head_width_split: 1 = head mode 1 runs delta_head_w_f16x3.hip at widths other than 360
-  float* wd = nullptr;   // dense kernel [123904]
-  float* bd = nullptr;   // dense bias [1]
   // spectral correlation head: constant twiddle layers (corr_spectral.hip)
   OvnConvLayer dft;        // forward transform as a conv layer (fp32 mode) + its fp16 hi/lo fragments (dft_f16x3_kernel)
   double* tw64 = nullptr;  // [2][360] cos / sin (2 pi m / 360) in fp64: start values of the inverse transform (spectral_corr_kernel)
@@ -426,7 +460,7 @@ int ovn_absmax_forward(const float* x, int n_scans, long long per_scan, unsigned
 
 // delta_head.hip: the fp32 Delta head at the context's feature width with conv1size 15 (fused fp32 MFMA DeltaLayer + c_conv1 +
 // c_conv2, generic c_conv3, Dense); scratch: an OvnDeltaF32Scratch for at least n pairs
-int ovn_delta_prepare_w1(const float* c1_kernel_dev, float** w1p_out, hipStream_t stream);
+int ovn_delta_prepare_w1(OvnHeadWeights* hw, const float* c1_kernel_dev, hipStream_t stream);   // fills hw->w1p
 struct OvnDeltaF32Scratch {   // o2 (n, G, G, 128) | o3 (n, G - 2, G - 2, 256) | the split route's per-pair scales (`split` only)
   float *o2 = nullptr, *o3 = nullptr;
   void* scales = nullptr;
@@ -443,7 +477,7 @@ int ovn_dense_sigmoid_forward(const ovn_ctx* ctx, const float* o3, int n, long l
 // delta_head_f16x3.hip.  An OvnDeltaSubScratch (caller-owned: 2.9 MB per pair) holds the per-pair scales, both packed volumes, the
 // linear terms and the c_conv1 min-term rows between the two kernels of a call on n pairs (one sub-chunk); its o2max, the per-pair
 // maxima of the c_conv2 output, is the input of ovn_c3_dense_forward.  The f16x3 and bf16x3 paths share it.
-int ovn_delta_prepare_f16x3(ovn_ctx* ctx, const float* c1_kernel_dev, const float* c1_bias_dev, const float* c2_kernel_dev,
+int ovn_delta_prepare_f16x3(OvnHeadWeights* hw, const float* c1_kernel_dev, const float* c1_bias_dev, const float* c2_kernel_dev,
                             hipStream_t stream);
 struct OvnDeltaSubScratch {
   f32x4* scales = nullptr;

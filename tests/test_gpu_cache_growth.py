@@ -6,7 +6,7 @@ engine (64 x 900 depth-only leg, feature width 360: the width that has spectra a
   b. a 1-vs-N sweep over the grown cache: the bits of the sweep over a cache built in one piece with the volumes at the same slots,
      and of the scratch route; a sample of pairs against oracle/error_bounds, err / bound <= 1 (f16x3), as test_gpu_error_bounds.py;
   c. the shipped constant once: 1024 volumes, one more, 1024 -> 2050;
-  d. `rebuild_delta_cache` on a grown cache after the head has been re-registered;
+  d. `rebuild_delta_cache` on a grown cache after the head has been re-registered; the head registered A, B, A in every head precision;
   e. `Infer` over a run that grows its cache, with and without the look-ahead, against an `Infer` whose cache never grows;
   f. the slot sequence of one rank of a sharded `Infer`, without a process group.
 Bits are compared as int32 words: a Delta row holds packed words that need not be numbers."""
@@ -237,6 +237,48 @@ def test_rebuild_delta_cache_on_a_grown_cache_after_a_new_head():
         qspec = e.spectrum(q)
         lidx = np.asarray(slots, np.int32)
         assert _same_result(_sweep(e, cache, q, qspec, lidx), _sweep(e, cache, q, qspec, lidx, dcache=None))
+        torch.cuda.synchronize()
+    finally:
+        e.close()
+
+
+def test_head_registered_again_and_again_in_every_precision():
+    """Head weights A, then B, then A again, in each head precision: a 1-vs-6 sweep over Delta cache rows rebuilt after every
+    registration and a 4-pair indexed call.  Under B the rows, logits and overlaps differ from those under A (the yaw head has no
+    weights: its bins stay); after the second A everything is what it was after the first, bit for bit -- a device copy of the
+    weight set that a registration leaves behind shows up as stale bits in one of the routes."""
+    from overlapnet_amd.engine import OvnEngine
+    e = OvnEngine(64, 900, 1, device=0)
+    try:
+        e.load_weights(W1, CFG)
+        sets = {name: [torch.from_numpy(np.ascontiguousarray(w[k], np.float32)).to(e.device) for k in e.HEAD_PARAMS]
+                for name, w in (("A", W1), ("B", S.make_test_weights(1, seed=5)))}
+        vols = _volumes(7, 79, e.device)
+        cand, q = vols[:6], vols[6:7]
+        spec = e.spectrum(vols)
+
+        def run(precision):
+            e.set_head_precision("f16x3")     # the engine builds rows in the modes that read them: the weight set decides them, not the mode
+            rows = e.delta_cache(cand)
+            e.set_head_precision(precision)
+            sweep = e.heads(cand, q, spec_l=spec[:6], spec_r=spec[6:7], dcache_l=rows, want_logit=True)
+            pairs = e.heads(vols, vols, lidx=[0, 1, 2, 3], ridx=[4, 5, 6, 2], spec_l=spec, spec_r=spec, want_logit=True)
+            assert sweep["overlap"].shape[0] == 6 and pairs["overlap"].shape[0] == 4
+            out = {"rows": rows[:, :ROW_USED]}
+            for name, r in (("sweep", sweep), ("pairs", pairs)):
+                out.update({"%s %s" % (name, k): r[k] for k in ("overlap", "logit", "yaw")})
+            return out
+
+        for precision in ("f16x3", "bf16x3", "f32"):
+            got = []
+            for name in "ABA":
+                e.set_head_weights(sets[name])
+                got.append(run(precision))
+            first, other, again = got
+            for k in first:
+                assert _same_bits(again[k], first[k]), "%s: %s after the second registration of A is not what it was after the first" % (precision, k)
+                if not k.endswith("yaw"):
+                    assert not _same_bits(other[k], first[k]), "%s: %s is the same under both weight sets" % (precision, k)
         torch.cuda.synchronize()
     finally:
         e.close()
