@@ -520,6 +520,47 @@ int ovn_project_semantic(ovn_ctx* ctx, const float* points_dev, const int64_t* o
 int ovn_normals(ovn_ctx* ctx, const float* range_dev, const float* vertex_dev, int n_scans, int proj_h, int proj_w,
                 float* normal_dev, void* stream);
 
+/* ovn_render_scans: virtual scans of a triangle mesh, one ray per pixel of the range image, nearest hit (csrc/render_mesh.hip;
+ * DESIGN.md section 28).  Builds the map frames of the localization from a mesh instead of recorded keyframes.
+ *   vertices_dev  (V,3) f32; triangles_dev (T,3) i32, 1 <= T <= OVN_RENDER_MAX_TRIANGLES; two-sided (no back-face culling); a
+ *                 triangle with a vertex index outside [0, V) is skipped and its vertices are never read
+ *   poses_dev     (n,4,4) f64 row-major, sensor to world; the rotation R and the origin o are rounded to f32.  A pose with a
+ *                 non-finite entry in R or o (after that rounding) gives an all-empty scan
+ *   cos_az_dev, sin_az_dev (W) f32; cos_pitch_dev, sin_pitch_dev (H) f32: the CALLER's tables, cos / sin evaluated in f64 and
+ *                 rounded to f32, of  azimuth[px] = -(((px + 0.5) / W) * 2 - 1) * pi  and
+ *                 pitch[py] = (1 - (py + 0.5) / H) * fov - |fov_down|,  fov = |fov_up| + |fov_down| in radians: the ray through the
+ *                 centre of the pixel ovn_project would put a point into.  No transcendental function runs on the device
+ * Every operation below is one f32 operation rounded on its own, every dot product is summed (a0 b0 + a1 b1) + a2 b2:
+ *   d_s = (cp ca, cp sa, sp);  d_w = (R[:,0] d_s.x + R[:,1] d_s.y) + R[:,2] d_s.z
+ *   e1 = v1 - v0, e2 = v2 - v0, p = d_w x e2, det = e1 . p; rejected when det == 0 or det is NaN
+ *   inv = 1 / det, s = o - v0, u = (s . p) inv, q = s x e1, v = (d_w . q) inv, t = (e2 . q) inv
+ *   a hit: u >= 0, v >= 0, u + v <= 1, t > 0, t < (float)max_range.  The pixel's winner is the hit with the smallest t, among
+ *   equal t the smaller triangle index.
+ * Outputs, each may be NULL (empty pixels: -1 in every channel):
+ *   range_dev (n,H,W) f32 = t; tri_id_dev (n,H,W) i32 = the winner; vertex_dev (n,H,W,4) f32, 16-byte aligned =
+ *   (t d_s.x, t d_s.y, t d_s.z, 1), the sensor-frame point as ovn_project stores it; normal_dev (n,H,W,3) = the kernel of ovn_normals
+ *   on these range and vertex images; stacked_dev (n,H,W, use_depth + 3 use_normals) = depth | normals, the leg input.
+ * The hierarchy (overlapnet_amd/mesh.py builds it): bvh_leaves = NL, a power of two with 4 NL >= T; bvh_order_dev (T) i32, leaf j
+ * holds triangles order[4j .. 4j + 3] (entries outside [0, T) are skipped); bvh_nodes_dev (2 NL, 8) f32, 16-byte aligned, row i =
+ * lo.x lo.y lo.z 0 hi.x hi.y hi.z 0 of node i of the implicit complete binary tree (root 1, children 2i and 2i + 1, leaves NL ..
+ * 2 NL - 1, row 0 unused, lo.x > hi.x marks an empty node).  Every box must contain its triangles with the padding DESIGN.md
+ * states; the traversal then returns what the exhaustive route returns.  Both NULL: every ray walks all T triangles in index order
+ * (the validation entry).  One writer per pixel, no atomics: the same arguments give the same bits, and a pose renders alone as in
+ * any batch.
+ * OVN_ERR_ARG, before any launch: V < 1 or > 2^31 - 1, T < 1 or > OVN_RENDER_MAX_TRIANGLES, H or W < 1 or H W > 2^31 - 1, n < 0,
+ * max_range not > 0 (NaN included), a NULL mesh buffer, only one of the two hierarchy arrays, bvh_leaves not a power of two in
+ * 1 .. 2^25 or 4 bvh_leaves < T, a misaligned bvh_nodes_dev or vertex_dev, use_intensity or use_semantic non-zero (a rendered scan
+ * has neither channel), stacked_dev with neither use_depth nor use_normals, and for n > 0 a NULL poses_dev or table.  n == 0 is a
+ * no-op. */
+#define OVN_RENDER_MAX_TRIANGLES (1ll << 27)
+#define OVN_RENDER_LEAF_TRIANGLES 4
+int ovn_render_scans(ovn_ctx* ctx, const float* vertices_dev, int64_t n_vertices, const int32_t* triangles_dev, int64_t n_triangles,
+                     const float* bvh_nodes_dev, const int32_t* bvh_order_dev, int64_t bvh_leaves, const double* poses_dev,
+                     int64_t n_scans, int proj_h, int proj_w, const float* cos_az_dev, const float* sin_az_dev,
+                     const float* cos_pitch_dev, const float* sin_pitch_dev, double max_range, float* range_dev, int32_t* tri_id_dev,
+                     float* vertex_dev, float* normal_dev, float* stacked_dev, int use_depth, int use_normals, int use_intensity,
+                     int use_semantic, void* stream);
+
 /* The per-point part of range_projection alone (src/utils/utils.py:75-104), exactly as ovn_project's scatter kernel evaluates it:
  * for each of n float32 points (x,y,z,*) yaw = -np.arctan2(y, x), pitch = np.arcsin(z / depth) with NumPy's float32 results
  * (csrc/svml_f32.h) and the pixel py * proj_w + px the point falls into (-1 for a point the range filter drops).  Outputs may

@@ -72,6 +72,8 @@ SIGNATURES = {
                                        _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int,
                                        _vp]),
     "ovn_normals": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "ovn_render_scans": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int, C.c_int, _vp, _vp,
+                                  _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "ovn_projection_angles": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp]),
     "ovn_gt_range_images": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double,
                                       C.c_double, _vp, _vp]),

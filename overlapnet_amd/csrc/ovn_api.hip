@@ -1314,6 +1314,49 @@ int ovn_normals(ovn_ctx* ctx, const float* range_dev, const float* vertex_dev, i
   return ovn_normals_forward(range_dev, vertex_dev, n_scans, proj_h, proj_w, normal_dev, (hipStream_t)stream);
 }
 
+int ovn_render_scans(ovn_ctx* ctx, const float* vertices_dev, int64_t n_vertices, const int32_t* triangles_dev, int64_t n_triangles,
+                     const float* bvh_nodes_dev, const int32_t* bvh_order_dev, int64_t bvh_leaves, const double* poses_dev,
+                     int64_t n_scans, int proj_h, int proj_w, const float* cos_az_dev, const float* sin_az_dev,
+                     const float* cos_pitch_dev, const float* sin_pitch_dev, double max_range, float* range_dev, int32_t* tri_id_dev,
+                     float* vertex_dev, float* normal_dev, float* stacked_dev, int use_depth, int use_normals, int use_intensity,
+                     int use_semantic, void* stream) {
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_render_scans: ctx is NULL");
+  OVN_REQUIRE(n_vertices >= 1 && n_vertices <= 2147483647ll, OVN_ERR_ARG, "ovn_render_scans: %lld vertices outside 1 .. 2^31 - 1",
+              (long long)n_vertices);
+  OVN_REQUIRE(n_triangles >= 1 && n_triangles <= OVN_RENDER_MAX_TRIANGLES, OVN_ERR_ARG,
+              "ovn_render_scans: %lld triangles outside 1 .. 2^27", (long long)n_triangles);
+  OVN_REQUIRE(n_scans >= 0 && n_scans <= 2147483647ll, OVN_ERR_ARG, "ovn_render_scans: bad n_scans %lld", (long long)n_scans);
+  OVN_REQUIRE(proj_h >= 1 && proj_w >= 1 && (int64_t)proj_h * proj_w <= 2147483647ll, OVN_ERR_ARG,
+              "ovn_render_scans: image %d x %d outside 1 .. 2^31 - 1 pixels", proj_h, proj_w);
+  OVN_REQUIRE(max_range > 0.0, OVN_ERR_ARG, "ovn_render_scans: max_range must be > 0");
+  OVN_REQUIRE(!use_intensity && !use_semantic, OVN_ERR_ARG,
+              "ovn_render_scans: a rendered scan has no intensity and no class probabilities (use_intensity %d, use_semantic %d)",
+              use_intensity, use_semantic);
+  OVN_REQUIRE(vertices_dev && triangles_dev, OVN_ERR_ARG, "ovn_render_scans: NULL mesh buffer");
+  OVN_REQUIRE((bvh_nodes_dev != nullptr) == (bvh_order_dev != nullptr), OVN_ERR_ARG,
+              "ovn_render_scans: the hierarchy is both arrays or neither");
+  if (bvh_nodes_dev) {
+    OVN_REQUIRE(bvh_leaves >= 1 && bvh_leaves <= OVN_RENDER_MAX_TRIANGLES / OVN_RENDER_LEAF_TRIANGLES &&
+                    (bvh_leaves & (bvh_leaves - 1)) == 0 && bvh_leaves * OVN_RENDER_LEAF_TRIANGLES >= n_triangles,
+                OVN_ERR_ARG, "ovn_render_scans: %lld leaves: not a power of two in 1 .. 2^25 that holds %lld triangles",
+                (long long)bvh_leaves, (long long)n_triangles);
+    OVN_REQUIRE(aligned16(bvh_nodes_dev), OVN_ERR_ARG, "ovn_render_scans: bvh_nodes_dev is not 16-byte aligned");
+  }
+  OVN_REQUIRE(!vertex_dev || aligned16(vertex_dev), OVN_ERR_ARG, "ovn_render_scans: vertex_dev is not 16-byte aligned");
+  use_depth = use_depth ? 1 : 0;
+  use_normals = use_normals ? 1 : 0;
+  OVN_REQUIRE(!stacked_dev || use_depth + use_normals > 0, OVN_ERR_ARG,
+              "ovn_render_scans: stacked output requested with no channel enabled");
+  if (n_scans == 0) return OVN_OK;
+  OVN_REQUIRE(poses_dev != nullptr, OVN_ERR_ARG, "ovn_render_scans: poses is NULL");
+  OVN_REQUIRE(cos_az_dev && sin_az_dev && cos_pitch_dev && sin_pitch_dev, OVN_ERR_ARG, "ovn_render_scans: NULL direction table");
+  OVN_ON_DEVICE(ctx->device);
+  return ovn_render_scans_forward(ctx, vertices_dev, (int)n_vertices, triangles_dev, (int)n_triangles, bvh_nodes_dev, bvh_order_dev,
+                                  (int)bvh_leaves, poses_dev, n_scans, proj_h, proj_w, cos_az_dev, sin_az_dev, cos_pitch_dev,
+                                  sin_pitch_dev, max_range, range_dev, tri_id_dev, vertex_dev, normal_dev, stacked_dev, use_depth,
+                                  use_normals, (hipStream_t)stream);
+}
+
 int ovn_gt_range_images(ovn_ctx* ctx, const float* points_dev, const int64_t* offsets_dev, int n_scans,
                         int64_t max_points_per_scan, const double* ref_poses_dev, const double* inv_cur_pose_dev, int proj_h,
                         int proj_w, double fov_up_deg, double fov_down_deg, double max_range, float* range_dev, void* stream) {

@@ -651,6 +651,15 @@ int ovn_projection_angles_forward(const float* points, int64_t n, int H, int W, 
                                   double max_range, float* yaw, float* pitch, int32_t* pixel, hipStream_t stream, int trig = 0);
 int ovn_normals_forward(const float* range, const float* vertex, int n_scans, int H, int W, float* normal,
                         hipStream_t stream);
+int ovn_normals_stack_forward(const float* range, const float* vertex, int n_scans, int H, int W, float* normal, float* stacked,
+                              int use_depth, int use_normals, hipStream_t stream);
+
+// render_mesh.hip: nodes / order NULL = every ray walks all T triangles; the arguments are those of ovn_render_scans, validated there
+int ovn_render_scans_forward(ovn_ctx* ctx, const float* vertices, int V, const int32_t* triangles, int T, const float* nodes,
+                             const int32_t* order, int NL, const double* poses, int64_t n, int H, int W, const float* cos_az,
+                             const float* sin_az, const float* cos_pitch, const float* sin_pitch, double max_range, float* range,
+                             int32_t* tri_id, float* vertex, float* normal, float* stacked, int use_depth, int use_normals,
+                             hipStream_t stream);
 
 // selftest.hip
 int ovn_mfma_selftest(hipStream_t stream);

@@ -699,3 +699,16 @@ int ovn_normals_forward(const float* range, const float* vertex, int n_scans, in
   OVN_HIP_CHECK(hipGetLastError());
   return OVN_OK;
 }
+
+// the same kernel with the leg input assembled beside the normals (depth | normals, no intensity): ovn_render_scans' second pass over
+// the images its ray kernel wrote.  vertex may be NULL when no normals are asked for (neither `normal` nor use_normals)
+int ovn_normals_stack_forward(const float* range, const float* vertex, int n_scans, int H, int W, float* normal, float* stacked,
+                              int use_depth, int use_normals, hipStream_t stream) {
+  const long long npix = (long long)H * W * n_scans;
+  if (npix == 0) return OVN_OK;
+  const int gblocks = (int)((npix + 255) / 256 < 4096 ? (npix + 255) / 256 : 4096);
+  hipLaunchKernelGGL(proj_normal_kernel, dim3(gblocks), dim3(256), 0, stream, range, vertex, (const float*)nullptr, H, W, n_scans,
+                     normal, stacked, use_depth, use_normals, 0, use_depth + 3 * use_normals);
+  OVN_HIP_CHECK(hipGetLastError());
+  return OVN_OK;
+}

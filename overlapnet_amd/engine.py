@@ -66,6 +66,7 @@ class OvnEngine:
         self.conv1size = 15
         self._leg_cfg: dict = {}             # the model keys the registered leg was built from (load_weights)
         self.check_device_indices = False    # opt-in range check of pair-index tensors that already live on the device (_idx)
+        self._render_tables: dict = {}       # render_scans: the device ray tables of the last sensor geometry
 
     # -- lifetime -----------------------------------------------------------------------------------
     def close(self) -> None:
@@ -982,6 +983,67 @@ class OvnEngine:
         with self._dev():
             _lib.check(self.lib.ovn_normals(self._h, _ptr(rng), _ptr(vtx), n, h, w, _ptr(out), self._stream()),
                        "ovn_normals")
+        return out
+
+    def render_scans(self, mesh, poses, proj_h: int = 64, proj_w: int = 900, fov_up: float = 3.0, fov_down: float = -25.0,
+                     max_range: float = 50.0, want: Sequence[str] = ("range", "normal"),
+                     stacked_flags: Optional[Tuple[bool, ...]] = None, stacked_out: Optional[torch.Tensor] = None,
+                     exhaustive: bool = False):
+        """Virtual scans of a `mesh.TriangleMesh` from `poses` ((n,4,4) float64 sensor-to-world, host array or device tensor), one ray
+        per pixel (ovn_render_scans).  `want` selects outputs among range, tri_id, vertex, normal; stacked_flags = (use_depth,
+        use_normals) additionally assembles the (n,H,W,C) leg input (into `stacked_out` when given); a third (intensity) or fourth
+        (class probabilities) flag that is set is refused by the library: a rendered scan has neither.  exhaustive=True walks every
+        triangle with every ray (the validation route) instead of the mesh's hierarchy.  Returns a dict of device tensors."""
+        bad = [k for k in want if k not in ("range", "tri_id", "vertex", "normal")]
+        if bad:
+            raise _lib.OvnError("render_scans: no output %s (a rendered scan has range, tri_id, vertex, normal)" % bad)
+        if isinstance(poses, torch.Tensor):
+            p = poses.to(self.device, torch.float64).contiguous()
+        else:
+            p = torch.from_numpy(np.ascontiguousarray(np.asarray(poses, np.float64))).to(self.device)
+        if p.dim() != 3 or tuple(p.shape[1:]) != (4, 4):
+            raise _lib.OvnError("render_scans: poses must be (n,4,4), got %s" % (tuple(p.shape),))
+        n, dev = p.shape[0], self.device
+        proj_h, proj_w = int(proj_h), int(proj_w)
+        key = (proj_h, proj_w, float(fov_up), float(fov_down))
+        tabs = self._render_tables.get(key)
+        if tabs is None and proj_h >= 1 and proj_w >= 1:
+            from .mesh import direction_tables
+            tabs = tuple(torch.from_numpy(t).to(dev) for t in direction_tables(proj_h, proj_w, fov_up, fov_down))
+            self._render_tables = {key: tabs}      # the last geometry only
+        tabs = tabs or (None,) * 4
+        md = mesh.device(self, with_bvh=not exhaustive)
+        nodes, order, leaves = (None, None, 0) if exhaustive else (md["nodes"], md["order"], md["leaves"])
+        mk = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)
+        rng = mk(n, proj_h, proj_w) if "range" in want else None
+        tid = mk(n, proj_h, proj_w, dt=torch.int32) if "tri_id" in want else None
+        vtx = mk(n, proj_h, proj_w, 4) if "vertex" in want else None
+        nrm = mk(n, proj_h, proj_w, 3) if "normal" in want else None
+        stk = None
+        flags = [0, 0, 0, 0]
+        if stacked_flags is not None:
+            if not 1 <= len(stacked_flags) <= 4:
+                raise _lib.OvnError("render_scans: stacked_flags is (use_depth, use_normals[, use_intensity[, use_semantic]])")
+            flags[:len(stacked_flags)] = [int(bool(v)) for v in stacked_flags]
+            c = flags[0] + 3 * flags[1]
+            if stacked_out is not None:
+                if (stacked_out.device != dev or stacked_out.dtype != torch.float32 or not stacked_out.is_contiguous()
+                        or tuple(stacked_out.shape) != (n, proj_h, proj_w, c)):
+                    raise _lib.OvnError("stacked_out must be a contiguous float32 (%d,%d,%d,%d) tensor on %s" % (n, proj_h, proj_w, c, dev))
+                stk = stacked_out
+            else:
+                stk = mk(n, proj_h, proj_w, max(c, 1))
+        with self._dev():
+            _lib.check(self.lib.ovn_render_scans(self._h, _ptr(md["vertices"]), mesh.n_vertices, _ptr(md["triangles"]),
+                                                 mesh.n_triangles, _ptr(nodes), _ptr(order), int(leaves), _ptr(p), n, proj_h, proj_w,
+                                                 _ptr(tabs[0]), _ptr(tabs[1]), _ptr(tabs[2]), _ptr(tabs[3]), float(max_range),
+                                                 _ptr(rng), _ptr(tid), _ptr(vtx), _ptr(nrm), _ptr(stk), flags[0], flags[1], flags[2],
+                                                 flags[3], self._stream()),
+                       "ovn_render_scans")
+        out = {}
+        for k, v in (("range", rng), ("tri_id", tid), ("vertex", vtx), ("normal", nrm), ("stacked", stk)):
+            if v is not None:
+                out[k] = v
         return out
 
     def icp_register(self, vertex: torch.Tensor, normal: torch.Tensor, rng: torch.Tensor, src_idx: torch.Tensor,

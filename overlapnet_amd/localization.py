@@ -12,6 +12,9 @@ hypothesis (x, y, theta) with a weight.  One step of the filter:
      keyframe minus the network's yaw; weights rescaled by a power of two; the weighted mean pose and N_eff come back as 8 doubles;
   5. `ovn_mcl_resample` (systematic, exact in integers) when N_eff < resample_fraction * P.
 
+The keyframes are recorded scans at known poses (`OverlapMap(...)`) or virtual scans rendered from a triangle mesh of the environment
+at the poses of a grid (`OverlapMap.from_mesh`, `grid_poses`; csrc/render_mesh.hip): the filter does not care.
+
 The kernels are csrc/mcl.hip; the formulas are stated in DESIGN.md, "Localization".  Everything but the two records and the estimate
 stays on the device, and a step with the same seed and inputs gives the same bits.
 
@@ -52,6 +55,41 @@ def grid_for(xy: np.ndarray, resolution: float, reach: float):
     hi = np.floor((xy.max(axis=0) + reach) / res)
     nx, ny = int(hi[0] - lo[0]) + 1, int(hi[1] - lo[1]) + 1
     return float(lo[0] * res), float(lo[1] * res), nx, ny
+
+
+def grid_poses(x_range, y_range, resolution: float, z: float, yaw: float = 0.0) -> np.ndarray:
+    """(M,4,4) float64 sensor poses for `OverlapMap.from_mesh`: one per cell of the grid of `resolution` metres laid over
+    [x_range[0], x_range[1]) x [y_range[0], y_range[1]), at the cell's centre, height `z`, heading `yaw` [rad]; rows run over y, then
+    x (pose iy * nx + ix).  A range shorter than one cell still gives one cell."""
+    res = float(resolution)
+    if not res > 0:
+        raise ValueError("resolution must be > 0")
+    x0, x1 = float(x_range[0]), float(x_range[1])
+    y0, y1 = float(y_range[0]), float(y_range[1])
+    if not (x1 >= x0 and y1 >= y0):
+        raise ValueError("ranges must be (low, high), got %s and %s" % (tuple(x_range), tuple(y_range)))
+    nx = max(1, int(math.ceil((x1 - x0) / res - 1e-9)))
+    ny = max(1, int(math.ceil((y1 - y0) / res - 1e-9)))
+    cx = x0 + (np.arange(nx) + 0.5) * res
+    cy = y0 + (np.arange(ny) + 0.5) * res
+    poses = np.zeros((ny, nx, 4, 4), np.float64)
+    c, s = math.cos(float(yaw)), math.sin(float(yaw))
+    poses[:, :] = np.array([[c, -s, 0.0, 0.0], [s, c, 0.0, 0.0], [0.0, 0.0, 1.0, float(z)], [0.0, 0.0, 0.0, 1.0]])
+    poses[:, :, 0, 3] = cx[None, :]
+    poses[:, :, 1, 3] = cy[:, None]
+    return poses.reshape(ny * nx, 4, 4)
+
+
+def keep_scans(valid_pixels, n_pixels: int, min_valid_fraction: float) -> np.ndarray:
+    """The drop rule of `OverlapMap.from_mesh`: a rendered scan with fewer than min_valid_fraction * n_pixels valid pixels is dropped
+    (the pose sits inside a wall or off the mesh).  Returns the boolean keep mask of the per-scan counts."""
+    return np.asarray(valid_pixels, np.float64) >= float(min_valid_fraction) * float(n_pixels)
+
+
+def render_chunk(h: int, w: int, c: int, budget_bytes: int = 1 << 28) -> int:
+    """Poses `from_mesh` renders per pass: the range image and the stacked leg input of a chunk take at most `budget_bytes` (256 MB)
+    beside the leg's workspace, and a chunk is at most the 1024 scans the leg processes per pass."""
+    return int(max(1, min(1024, budget_bytes // (4 * h * w * (c + 1)))))
 
 
 def build_cell_frame(xy, origin_x: float, origin_y: float, resolution: float, nx: int, ny: int, reach: Optional[float] = None) -> np.ndarray:
@@ -170,13 +208,101 @@ class OverlapMap(object):
         return np.stack([self.origin_x + (cells % self.nx + 0.5) * self.resolution,
                          self.origin_y + (cells // self.nx + 0.5) * self.resolution], axis=-1)
 
+    kept = None             # from_mesh: indices into the poses it was given of the map frames it kept (None for a keyframe map)
+    mesh_built = False
+
+    @classmethod
+    def from_mesh(cls, infer, mesh, poses, resolution: float, reach: Optional[float] = None, min_valid_fraction: float = 0.1,
+                  chunk: Optional[int] = None, fov_up: float = 3.0, fov_down: float = -25.0, max_range: float = 50.0,
+                  min_range: float = 0.0) -> "OverlapMap":
+        """A map whose frames are virtual scans of `mesh` (mesh.TriangleMesh) rendered at `poses`, (M,4,4) sensor poses in the mesh's
+        frame (`grid_poses` makes one per grid cell): the map of Chen et al., which has a frame wherever the robot can be.  The scans
+        are rendered `chunk` poses at a time (default: `render_chunk`), each chunk goes through the leg into the Infer's cache.  A
+        pose whose scan has fewer than min_valid_fraction * H * W valid pixels (inside a wall, off the mesh) is dropped before the
+        cell table is built; `map.kept` lists the indices of the others.  The sensor (fov_up, fov_down, max_range) defaults to the
+        one `MonteCarloLocalizer.step` projects a raw query cloud with.  min_range: a pixel counts as valid for the drop rule when
+        its range exceeds it -- the blind zone of a real sensor.  The mesh is two-sided, so a pose inside a closed solid sees that
+        solid from inside in every pixel and the default 0 keeps it; with min_range above the solid's half width it is dropped.  The
+        rendered images themselves are not changed by it."""
+        if getattr(infer, "_world", 1) > 1:
+            raise OvnError("OverlapMap.from_mesh: a sharded Infer (world %d) is not supported: build the map on a single-rank Infer"
+                           % infer._world)
+        if infer.use_intensity or infer.use_class_probabilities:
+            raise OvnError("OverlapMap.from_mesh: a rendered scan has no intensity and no class probabilities, but this Infer's model "
+                           "takes %s; use a model with depth and / or normals only"
+                           % " and ".join(n for n, f in (("intensity", infer.use_intensity),
+                                                         ("class probabilities", infer.use_class_probabilities)) if f))
+        if len(infer.feature_volumes) != 0:
+            raise OvnError("OverlapMap.from_mesh: the Infer already caches %d frames; the map needs slots 0 .. M-1 "
+                           "(infer.feature_volumes = [])" % len(infer.feature_volumes))
+        p = np.ascontiguousarray(np.asarray(poses, np.float64))
+        if p.ndim != 3 or p.shape[1:] != (4, 4) or p.shape[0] < 1:
+            raise ValueError("OverlapMap.from_mesh: poses must be (M,4,4) with M >= 1, got %s" % (p.shape,))
+        eng = infer.engine
+        h, w, c = (int(v) for v in infer.inputShape)
+        step = render_chunk(h, w, c) if chunk is None else max(1, int(chunk))
+        flags = (bool(infer.use_depth), bool(infer.use_normals))
+        cache = infer.feature_volumes
+        keep = np.zeros(p.shape[0], bool)
+        for a in range(0, p.shape[0], step):
+            r = eng.render_scans(mesh, p[a:a + step], h, w, fov_up, fov_down, max_range, want=("range",), stacked_flags=flags)
+            k = keep_scans((r["range"] > float(min_range)).sum(dim=(1, 2)).cpu().numpy(), h * w, min_valid_fraction)
+            keep[a:a + step] = k
+            if k.all():
+                cache.extend_device(eng.leg(r["stacked"]))
+            elif k.any():
+                cache.extend_device(eng.leg(r["stacked"][torch.from_numpy(np.nonzero(k)[0]).to(eng.device)].contiguous()))
+        kept = np.nonzero(keep)[0]
+        if len(kept) == 0:
+            raise OvnError("OverlapMap.from_mesh: none of the %d poses sees %g of its pixels: are they in the mesh's frame?"
+                           % (p.shape[0], min_valid_fraction))
+        self = cls.__new__(cls)
+        self.infer, self.engine = infer, eng
+        self.mesh_built, self.kept, self.sensor_poses = True, kept, p[kept]
+        self.min_valid_fraction, self.sensor = float(min_valid_fraction), (float(fov_up), float(fov_down), float(max_range))
+        self.min_range = float(min_range)
+        self.poses = poses_xyyaw(self.sensor_poses)
+        self.frame_names = ["mesh:%d" % i for i in kept]
+        self.resolution = float(resolution)
+        self.reach = self.resolution if reach is None else float(reach)
+        self.origin_x, self.origin_y, self.nx, self.ny = grid_for(self.poses[:, :2], self.resolution, self.reach)
+        self.cell_frame_host = build_cell_frame(self.poses[:, :2], self.origin_x, self.origin_y, self.resolution, self.nx, self.ny,
+                                                self.reach)
+        self.cell_frame = torch.from_numpy(self.cell_frame_host).to(eng.device)
+        self.frame_yaw = torch.from_numpy(self.poses[:, 2].astype(np.float32)).to(eng.device)
+        return self
+
     def save(self, path: str) -> None:
-        """What rebuilds the map: names, poses, resolution, reach (the feature volumes are recomputed through the leg by `load`)."""
+        """What rebuilds the map: names, poses, resolution, reach (the feature volumes are recomputed through the leg by `load`).  A
+        mesh-built map adds its marker, the kept sensor poses, their indices, the drop threshold and the sensor; the mesh is the
+        caller's to keep."""
+        if self.mesh_built:
+            np.savez(path, frame_names=np.asarray(self.frame_names), poses=self.poses, resolution=self.resolution, reach=self.reach,
+                     mesh_built=np.int32(1), sensor_poses=self.sensor_poses, kept=self.kept.astype(np.int64),
+                     min_valid_fraction=self.min_valid_fraction, sensor=np.asarray(self.sensor, np.float64),
+                     min_range=self.min_range)
+            return
         np.savez(path, frame_names=np.asarray(self.frame_names), poses=self.poses, resolution=self.resolution, reach=self.reach)
 
     @classmethod
-    def load(cls, infer, path: str) -> "OverlapMap":
+    def load(cls, infer, path: str, mesh=None) -> "OverlapMap":
+        """`mesh`: the TriangleMesh of a mesh-built map (its scans are rendered again); a keyframe map takes none."""
         with np.load(path) as z:
+            if "mesh_built" in z.files:
+                if mesh is None:
+                    raise OvnError("OverlapMap.load: %s holds a mesh-built map: pass the mesh (load(infer, path, mesh))" % path)
+                up, down, rmax = (float(v) for v in z["sensor"])
+                m = cls.from_mesh(infer, mesh, z["sensor_poses"], float(z["resolution"]), float(z["reach"]),
+                                  float(z["min_valid_fraction"]), fov_up=up, fov_down=down, max_range=rmax,
+                                  min_range=float(z["min_range"]))
+                if len(m.kept) != len(z["kept"]):
+                    raise OvnError("OverlapMap.load: %d of the %d saved map frames see too little of this mesh: not the mesh the map "
+                                   "was built from" % (len(z["kept"]) - len(m.kept), len(z["kept"])))
+                m.kept = z["kept"].astype(np.int64)
+                m.frame_names = [str(n) for n in z["frame_names"]]
+                return m
+            if mesh is not None:
+                raise OvnError("OverlapMap.load: %s holds a keyframe map, which takes no mesh" % path)
             return cls(infer, [str(n) for n in z["frame_names"]], z["poses"], float(z["resolution"]), float(z["reach"]))
 
 

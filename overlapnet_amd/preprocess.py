@@ -61,6 +61,17 @@ def project_scans(scans: Sequence[np.ndarray], engine: Optional[OvnEngine] = Non
                        want=want, stacked_flags=stacked_flags, probs=pr, n_classes=n_classes, n_points=int(offsets[-1]))
 
 
+def render_scans(mesh, poses, engine: Optional[OvnEngine] = None, proj_H=64, proj_W=900, fov_up=3.0, fov_down=-25.0, max_range=50,
+                 want=("range", "normal"), stacked_flags: Optional[Tuple[bool, ...]] = (True, True), exhaustive=False):
+    """Virtual scans of a `mesh.TriangleMesh` at `poses` ((n,4,4) float64, sensor to world): one ray through the centre of every pixel
+    `range_projection` fills, nearest triangle hit (ovn_render_scans, csrc/render_mesh.hip).  Returns device tensors like
+    `project_scans`: the outputs `want` names among range, tri_id, vertex, normal, plus "stacked", the (n,H,W,C) leg input under
+    stacked_flags = (use_depth, use_normals) (None: no stacked output).  exhaustive=True tests every triangle with every ray."""
+    eng = engine or _get_engine()
+    return eng.render_scans(mesh, poses, proj_H, proj_W, fov_up, fov_down, max_range, want=want, stacked_flags=stacked_flags,
+                            exhaustive=exhaustive)
+
+
 def range_projection(current_vertex, fov_up=3.0, fov_down=-25.0, proj_H=64, proj_W=900, max_range=50):
     """ Spherical projection of one point cloud (utils.py:59-134).
         Returns proj_range (H,W), proj_vertex (H,W,4), proj_intensity (H,W), proj_idx (H,W) int32. """

@@ -4,6 +4,13 @@ Build and save a map (keyframe rows `frame x y heading[rad]`, frames named as `I
 
     python tools/localize.py --config network.json --scans map_scans/ --build keyframes.txt --map map.npz --resolution 1.0
 
+Build the map from a triangle mesh instead (PLY or OBJ): virtual scans rendered on the GPU, one per cell of the grid of --resolution laid
+over the mesh's x / y bounding box (`--build grid`) or at the rows `name x y heading` of a file, the sensor --grid-height above z = 0:
+
+    python tools/localize.py --config network.json --mesh site.ply --build grid --map map.npz --resolution 1.0 --grid-height 1.7
+
+Localizing in such a map takes the mesh again (`--mesh site.ply`): its scans are re-rendered, not stored.
+
 Localize (odometry rows `frame dx dy dtheta`: the motion in the robot frame since the previous row, the scan `<scans>/<frame>.bin`):
 
     python tools/localize.py --config network.json --map map.npz --map-scans map_scans/ --scans drive_scans/ --odom odom.txt \\
@@ -53,6 +60,9 @@ def main(argv=None):
     ap.add_argument("--scans", help="folder of the .bin scans named by --build / --odom")
     ap.add_argument("--map-scans", help="folder of the map's .bin scans when it differs from --scans")
     ap.add_argument("--build", help="keyframe file: build the map, save it and exit")
+    ap.add_argument("--mesh", help="triangle mesh (.ply / .obj): --build renders the map's scans from it; needed again to localize in such a map")
+    ap.add_argument("--grid-height", type=float, default=1.7, help="sensor height of the rendered map poses (with --mesh)")
+    ap.add_argument("--min-valid", type=float, default=0.1, help="drop a rendered pose that sees less than this fraction of its pixels")
     ap.add_argument("--resolution", type=float, default=1.0)
     ap.add_argument("--reach", type=float, default=None)
     ap.add_argument("--odom", help="odometry file of the drive")
@@ -77,7 +87,25 @@ def main(argv=None):
     if map_scans:
         cfg["scan_folder"] = map_scans
     infer = Infer(cfg)
+    mesh = None
+    if a.mesh:
+        from overlapnet_amd.mesh import TriangleMesh
+        mesh = TriangleMesh.from_obj(a.mesh) if a.mesh.lower().endswith(".obj") else TriangleMesh.from_ply(a.mesh)
     try:
+        if a.build and mesh is not None:
+            from overlapnet_amd.localization import grid_poses
+            if a.build == "grid":
+                lo, hi = mesh.vertices.min(axis=0), mesh.vertices.max(axis=0)
+                poses = grid_poses((lo[0], hi[0]), (lo[1], hi[1]), a.resolution, a.grid_height)
+            else:
+                _, rows = read_rows(a.build)
+                poses = np.stack([grid_poses((x, x), (y, y), a.resolution, a.grid_height, yaw)[0] for x, y, yaw in rows])
+                poses[:, 0, 3], poses[:, 1, 3] = rows[:, 0], rows[:, 1]
+            mp = OverlapMap.from_mesh(infer, mesh, poses, a.resolution, a.reach, min_valid_fraction=a.min_valid)
+            mp.save(a.map)
+            print("map of %d rendered frames (%d of %d poses kept), %d x %d cells of %.3g m, %d occupied -> %s"
+                  % (mp.n_frames, len(mp.kept), len(poses), mp.nx, mp.ny, mp.resolution, len(mp.occupied_cells), a.map), file=sys.stderr)
+            return 0
         if a.build:
             names, poses = read_rows(a.build)
             mp = OverlapMap(infer, names, poses, a.resolution, a.reach)
@@ -85,7 +113,7 @@ def main(argv=None):
             print("map of %d keyframes, %d x %d cells of %.3g m, %d occupied -> %s"
                   % (mp.n_frames, mp.nx, mp.ny, mp.resolution, len(mp.occupied_cells), a.map), file=sys.stderr)
             return 0
-        mp = OverlapMap.load(infer, a.map)
+        mp = OverlapMap.load(infer, a.map, mesh) if mesh is not None else OverlapMap.load(infer, a.map)
         if a.scans:
             infer._scan_folder = a.scans          # the drive's scans from here on (the map is cached)
         obs = {k: v for k, v in (("sigma_yaw", a.sigma_yaw), ("eps_yaw", a.eps_yaw), ("overlap_min", a.overlap_min)) if v is not None}
