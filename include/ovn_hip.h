@@ -561,6 +561,55 @@ int ovn_render_scans(ovn_ctx* ctx, const float* vertices_dev, int64_t n_vertices
                      float* vertex_dev, float* normal_dev, float* stacked_dev, int use_depth, int use_normals, int use_intensity,
                      int use_semantic, void* stream);
 
+/* ovn_tsdf_integrate: range images and poses fused into a truncated signed distance volume (csrc/tsdf.hip).
+ * With ovn_tsdf_triangles it builds the mesh ovn_render_scans takes from a drive's own scans.
+ *   tsdf_dev, weight_dev (nz,ny,nx) f32, x fastest; 2 <= nx, ny, nz and nx ny nz <= 2^31 - 1.  A fresh volume is tsdf = 1, weight = 0
+ *   origin        3 doubles on the HOST; origin, voxel, trunc, max_weight and max_range are rounded to f32
+ *   range_dev     (n,H,W) f32, -1 = empty: the range images of ovn_project or ovn_render_scans for the same H, W, field of view
+ *   poses_dev     (n,4,4) f64 row-major, sensor to world, assumed rigid; R and o are rounded to f32.  A pose with a non-finite
+ *                 entry in R or o (after that rounding) skips its scan
+ * For every sample (i, j, k), p = origin + (float)(i, j, k) * voxel (one multiply, one add per coordinate), the scans are applied
+ * in ascending order, every operation one f32 operation rounded on its own:
+ *   1  d = p - o;  q_k = (R[0,k] d0 + R[1,k] d1) + R[2,k] d2
+ *   2  depth, yaw, pitch and the unfloored px, py of q exactly as ovn_project computes them for a point (csrc/proj_pixel.h; the
+ *      trig mode of ovn_set_projection_trig applies)
+ *   3  skipped unless depth > 0 and 0 <= py < H: a sample outside the vertical field of view is NOT compared with the top or
+ *      bottom row (ovn_project clamps there)
+ *   4  px floored and clamped to 0 .. W - 1 as in ovn_project; r = range[s, floor(py), px]; skipped unless 0 < r < max_range (no
+ *      image of ovn_project or ovn_render_scans holds a larger value)
+ *   5  sdf = r - depth; skipped when sdf < -trunc (behind the surface, unseen)
+ *   6  dv = fminf(1, sdf / trunc)
+ *   7  w1 = weight + 1;  tsdf = (weight * tsdf + dv) / w1;  weight = fminf(w1, max_weight)
+ * The launch tests scan s only on the box of samples within max_range + trunc + voxel of o (plus one index); every sample outside it
+ * fails test 5, so the result does not depend on that -- for a RIGID pose: the argument is depth = |R^T d| = |d| >= |d_a|, and a
+ * scaled or sheared matrix makes the box change results.  The margin of one voxel and one index also assumes coordinates small
+ * enough that the f32 rounding of p (2^-24 |p| per operation) stays below a voxel: |p| < 10^6 voxels, say.  One writer per sample, no atomics: the same arguments give the same bits,
+ * and scans [0, a) then [a, n) in two calls give the bits of one call.
+ * OVN_ERR_ARG, before any launch (the volume is untouched): a NULL volume buffer or origin, a dimension < 2 or more than 2^31 - 1
+ * samples, a non-finite origin, voxel, trunc, max_weight or max_range not > 0 (NaN included), H or W < 1 or H W > 2^31 - 1,
+ * n < 0, and for n > 0 a NULL range_dev or poses_dev.  n == 0 is a no-op. */
+int ovn_tsdf_integrate(ovn_ctx* ctx, float* tsdf_dev, float* weight_dev, int nx, int ny, int nz, const double* origin, double voxel,
+                       double trunc, double max_weight, const float* range_dev, const double* poses_dev, int64_t n_scans, int proj_h,
+                       int proj_w, double fov_up_deg, double fov_down_deg, double max_range, void* stream);
+
+/* ovn_tsdf_triangles: the zero level set of such a volume as a triangle soup, by marching tetrahedra (csrc/tsdf.hip; DESIGN.md
+ * section 29).  Cell (i, j, k), 0 <= i < nx - 1 .., has the corners c = dx + 2 dy + 4 dz.  It is live when all eight corners have
+ * weight >= (float)min_weight and their tsdf values are neither all < 0 nor all >= 0 (inside = tsdf < 0).  Its six tetrahedra, in
+ * this order: (0,1,3,7) (0,3,2,7) (0,2,6,7) (0,6,4,7) (0,4,5,7) (0,5,1,7).  One or three inside corners of a tetrahedron give one
+ * triangle, two give two; the vertex order per case is the table of DESIGN.md section 29, the normal (v1 - v0) x (v2 - v0) points
+ * towards positive tsdf.  The vertex on the edge between corners a and b, a the one with the smaller sample index, is
+ * p_a + (p_b - p_a) * (D_a / (D_a - D_b)) per coordinate, each operation one f32 operation: two cells compute a shared vertex from
+ * the same operands, so the soup is crack-free in bits.  Zero-area triangles (a corner with tsdf == 0) are kept.
+ *   triangles_dev   (capacity,3,3) f32 or NULL
+ *   n_triangles_dev one int64 on the device: the total count T, written by every call
+ * With triangles_dev NULL the call only counts; otherwise it writes the first min(T, capacity) triangles and nothing beyond.
+ * Triangles appear in ascending cell index (x fastest), then tetrahedron order, then triangle order: the same arguments give the same
+ * bits.  Usual use: one counting call, then one writing call.
+ * OVN_ERR_ARG, before any launch: a NULL tsdf_dev, weight_dev, origin or n_triangles_dev, a dimension < 2 or more than 2^31 - 1
+ * samples, a non-finite origin, voxel not > 0, min_weight NaN, capacity < 0. */
+int ovn_tsdf_triangles(ovn_ctx* ctx, const float* tsdf_dev, const float* weight_dev, int nx, int ny, int nz, const double* origin,
+                       double voxel, double min_weight, float* triangles_dev, int64_t capacity, int64_t* n_triangles_dev, void* stream);
+
 /* The per-point part of range_projection alone (src/utils/utils.py:75-104), exactly as ovn_project's scatter kernel evaluates it:
  * for each of n float32 points (x,y,z,*) yaw = -np.arctan2(y, x), pitch = np.arcsin(z / depth) with NumPy's float32 results
  * (csrc/svml_f32.h) and the pixel py * proj_w + px the point falls into (-1 for a point the range filter drops).  Outputs may

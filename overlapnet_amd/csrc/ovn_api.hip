@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include "ovn_internal.h"
 
 int ovn_allow_dynamic_lds(const void* kernel, size_t bytes) {
@@ -1355,6 +1356,51 @@ int ovn_render_scans(ovn_ctx* ctx, const float* vertices_dev, int64_t n_vertices
                                   (int)bvh_leaves, poses_dev, n_scans, proj_h, proj_w, cos_az_dev, sin_az_dev, cos_pitch_dev,
                                   sin_pitch_dev, max_range, range_dev, tri_id_dev, vertex_dev, normal_dev, stacked_dev, use_depth,
                                   use_normals, (hipStream_t)stream);
+}
+
+namespace {
+bool tsdf_volume_ok(int nx, int ny, int nz, const double* origin, double voxel) {
+  if (nx < 2 || ny < 2 || nz < 2 || (int64_t)nx * ny > 2147483647ll || (int64_t)nx * ny * nz > 2147483647ll) return false;
+  if (!origin || !(voxel > 0.0) || !((float)voxel > 0.0f) || !std::isfinite((float)voxel)) return false;
+  for (int a = 0; a < 3; ++a)
+    if (!std::isfinite((float)origin[a])) return false;
+  return true;
+}
+}  // namespace
+
+int ovn_tsdf_integrate(ovn_ctx* ctx, float* tsdf_dev, float* weight_dev, int nx, int ny, int nz, const double* origin, double voxel,
+                       double trunc, double max_weight, const float* range_dev, const double* poses_dev, int64_t n_scans, int proj_h,
+                       int proj_w, double fov_up_deg, double fov_down_deg, double max_range, void* stream) {
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_tsdf_integrate: ctx is NULL");
+  OVN_REQUIRE(tsdf_dev && weight_dev, OVN_ERR_ARG, "ovn_tsdf_integrate: NULL volume buffer");
+  OVN_REQUIRE(tsdf_volume_ok(nx, ny, nz, origin, voxel), OVN_ERR_ARG,
+              "ovn_tsdf_integrate: volume %d x %d x %d (each >= 2, at most 2^31 - 1 samples) needs a finite origin and a voxel > 0", nx,
+              ny, nz);
+  OVN_REQUIRE((float)trunc > 0.0f && std::isfinite((float)trunc), OVN_ERR_ARG, "ovn_tsdf_integrate: trunc must be > 0");
+  OVN_REQUIRE((float)max_weight > 0.0f, OVN_ERR_ARG, "ovn_tsdf_integrate: max_weight must be > 0");
+  OVN_REQUIRE((float)max_range > 0.0f && std::isfinite((float)max_range), OVN_ERR_ARG, "ovn_tsdf_integrate: max_range must be > 0");
+  OVN_REQUIRE(proj_h >= 1 && proj_w >= 1 && (int64_t)proj_h * proj_w <= 2147483647ll, OVN_ERR_ARG,
+              "ovn_tsdf_integrate: image %d x %d outside 1 .. 2^31 - 1 pixels", proj_h, proj_w);
+  OVN_REQUIRE(n_scans >= 0 && n_scans <= 2147483646ll, OVN_ERR_ARG, "ovn_tsdf_integrate: bad n_scans %lld", (long long)n_scans);
+  if (n_scans == 0) return OVN_OK;
+  OVN_REQUIRE(range_dev && poses_dev, OVN_ERR_ARG, "ovn_tsdf_integrate: NULL range images or poses");
+  OVN_ON_DEVICE(ctx->device);
+  return ovn_tsdf_integrate_forward(ctx, tsdf_dev, weight_dev, nx, ny, nz, origin, voxel, trunc, max_weight, range_dev, poses_dev,
+                                    (int)n_scans, proj_h, proj_w, fov_up_deg, fov_down_deg, max_range, (hipStream_t)stream);
+}
+
+int ovn_tsdf_triangles(ovn_ctx* ctx, const float* tsdf_dev, const float* weight_dev, int nx, int ny, int nz, const double* origin,
+                       double voxel, double min_weight, float* triangles_dev, int64_t capacity, int64_t* n_triangles_dev, void* stream) {
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_tsdf_triangles: ctx is NULL");
+  OVN_REQUIRE(tsdf_dev && weight_dev && n_triangles_dev, OVN_ERR_ARG, "ovn_tsdf_triangles: NULL buffer");
+  OVN_REQUIRE(tsdf_volume_ok(nx, ny, nz, origin, voxel), OVN_ERR_ARG,
+              "ovn_tsdf_triangles: volume %d x %d x %d (each >= 2, at most 2^31 - 1 samples) needs a finite origin and a voxel > 0", nx,
+              ny, nz);
+  OVN_REQUIRE(min_weight == min_weight, OVN_ERR_ARG, "ovn_tsdf_triangles: min_weight is NaN");
+  OVN_REQUIRE(capacity >= 0, OVN_ERR_ARG, "ovn_tsdf_triangles: capacity %lld < 0", (long long)capacity);
+  OVN_ON_DEVICE(ctx->device);
+  return ovn_tsdf_triangles_forward(ctx, tsdf_dev, weight_dev, nx, ny, nz, origin, voxel, min_weight, triangles_dev, capacity,
+                                    n_triangles_dev, (hipStream_t)stream);
 }
 
 int ovn_gt_range_images(ovn_ctx* ctx, const float* points_dev, const int64_t* offsets_dev, int n_scans,

@@ -654,6 +654,14 @@ int ovn_normals_forward(const float* range, const float* vertex, int n_scans, in
 int ovn_normals_stack_forward(const float* range, const float* vertex, int n_scans, int H, int W, float* normal, float* stacked,
                               int use_depth, int use_normals, hipStream_t stream);
 
+// tsdf.hip: the arguments are those of ovn_tsdf_integrate / ovn_tsdf_triangles, validated there (n_scans >= 1)
+int ovn_tsdf_integrate_forward(ovn_ctx* ctx, float* tsdf, float* weight, int nx, int ny, int nz, const double* origin, double voxel,
+                               double trunc, double max_weight, const float* range, const double* poses, int n_scans, int H, int W,
+                               double fov_up_deg, double fov_down_deg, double max_range, hipStream_t stream);
+int ovn_tsdf_triangles_forward(ovn_ctx* ctx, const float* tsdf, const float* weight, int nx, int ny, int nz, const double* origin,
+                               double voxel, double min_weight, float* triangles, int64_t capacity, int64_t* n_triangles,
+                               hipStream_t stream);
+
 // render_mesh.hip: nodes / order NULL = every ray walks all T triangles; the arguments are those of ovn_render_scans, validated there
 int ovn_render_scans_forward(ovn_ctx* ctx, const float* vertices, int V, const int32_t* triangles, int T, const float* nodes,
                              const int32_t* order, int NL, const double* poses, int64_t n, int H, int W, const float* cos_az,

@@ -19,7 +19,7 @@
 //   reproduces np.linalg.norm on a float32 3-vector (float32 products summed in a double -- OpenBLAS
 //   sdot's scalar tail -- then rounded to float32 and square-rooted).
 #include "ovn_internal.h"
-#include "svml_f32.h"
+#include "proj_pixel.h"   // ProjGeom, point_to_pixel, make_geom: shared with tsdf.hip
 
 #include <cstring>
 
@@ -27,39 +27,6 @@ namespace {
 
 constexpr unsigned long long EMPTY_KEY = 0xFFFFFFFFFFFFFFFFull;
 constexpr int PB = 256;  // points per block in the scatter kernel
-
-struct ProjGeom {
-  int H, W;
-  float fov_down_abs;  // float32(|fov_down| in radians)
-  float fov;           // float32(|fov_down| + |fov_up|)
-  float max_range;
-  int trig;            // 0: NumPy's float32 arctan2 / arcsin on AVX512_SKX x86-64 (SVML, svml_f32.h); 1: the correctly rounded float32
-                       // results (float64 function rounded once) -- what a host whose NumPy calls a correctly rounded libm produces
-};
-
-// utils.py:75-104 for one point: depth, the range filter, both angles and the pixel.  false = dropped by the filter.
-__device__ __forceinline__ bool point_to_pixel(float x, float y, float z, const ProjGeom& gm, float& depth, float& yaw, float& pitch,
-                                               int& pix) {
-  depth = sqrtf((x * x + y * y) + z * z);                      // utils.py:75
-  yaw = pitch = 0.f;
-  pix = 0;
-  if (!((depth > 0.0f) && (depth < gm.max_range))) return false;   // utils.py:76-77
-  if (gm.trig == 0) {
-    yaw = -ovn_svml::atan2f_np(y, x);                          // utils.py:86  (np.arctan2 on float32: svml_f32.h)
-    pitch = ovn_svml::asinf_np(z / depth);                     // utils.py:87  (np.arcsin on float32)
-  } else {                                                     // ovn_set_projection_trig(ctx, 1)
-    yaw = -(float)atan2((double)y, (double)x);
-    pitch = (float)asin((double)(z / depth));
-  }
-  float px = 0.5f * (yaw / 3.14159274101257324f + 1.0f);       // utils.py:90
-  float py = 1.0f - (pitch + gm.fov_down_abs) / gm.fov;        // utils.py:91
-  px = px * (float)gm.W;                                       // utils.py:94
-  py = py * (float)gm.H;                                       // utils.py:95
-  px = fmaxf(0.0f, fminf((float)(gm.W - 1), floorf(px)));      // utils.py:98-100
-  py = fmaxf(0.0f, fminf((float)(gm.H - 1), floorf(py)));      // utils.py:102-104
-  pix = (int)py * gm.W + (int)px;
-  return true;
-}
 
 __global__ void proj_angles_kernel(const float* __restrict__ points, long long n, ProjGeom gm, float* __restrict__ yaw_out,
                                    float* __restrict__ pitch_out, int* __restrict__ pixel_out) {
@@ -324,20 +291,6 @@ __global__ void proj_normal_kernel(const float* __restrict__ range, const float*
       if (use_intensity) o[c++] = intensity[q];
     }
   }
-}
-
-// same double arithmetic as utils.py:70-72, then the float32 casts NumPy applies to the scalars
-ProjGeom make_geom(int H, int W, double fov_up_deg, double fov_down_deg, double max_range, int trig) {
-  const double up = fov_up_deg / 180.0 * 3.14159265358979323846;
-  const double down = fov_down_deg / 180.0 * 3.14159265358979323846;
-  ProjGeom gm;
-  gm.H = H;
-  gm.W = W;
-  gm.fov_down_abs = (float)fabs(down);
-  gm.fov = (float)(fabs(down) + fabs(up));
-  gm.max_range = (float)max_range;
-  gm.trig = trig;
-  return gm;
 }
 
 // Scratch of a projection call: the key image | ovn_project's kept-point numbering | ovn_project_semantic's keep masks | the scatter

@@ -1046,6 +1046,75 @@ class OvnEngine:
                 out[k] = v
         return out
 
+    def _tsdf_volume_args(self, what: str, tsdf: torch.Tensor, weight: torch.Tensor, origin):
+        for t, name in ((tsdf, "tsdf"), (weight, "weight")):
+            if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 3:
+                raise _lib.OvnError("%s: %s must be a contiguous float32 (nz,ny,nx) tensor on %s" % (what, name, self.device))
+        if tuple(weight.shape) != tuple(tsdf.shape):
+            raise _lib.OvnError("%s: weight %s does not match tsdf %s" % (what, tuple(weight.shape), tuple(tsdf.shape)))
+        org = np.asarray(origin, np.float64).reshape(-1)
+        if org.shape[0] != 3:
+            raise _lib.OvnError("%s: origin must hold 3 numbers, got %d" % (what, org.shape[0]))
+        nz, ny, nx = (int(v) for v in tsdf.shape)
+        return nx, ny, nz, (C.c_double * 3)(*org)
+
+    def tsdf_integrate(self, tsdf: torch.Tensor, weight: torch.Tensor, origin, voxel: float, trunc: float, max_weight: float,
+                       range_images: torch.Tensor, poses, fov_up: float = 3.0, fov_down: float = -25.0, max_range: float = 50.0) -> None:
+        """Fuses `range_images` ((n,H,W) float32 device tensor, -1 = empty) taken at `poses` ((n,4,4) float64 sensor-to-world, host
+        array or device tensor) into the volume tsdf / weight ((nz,ny,nx) float32 device tensors, updated in place) whose sample
+        (i,j,k) sits at origin + (i,j,k) * voxel (ovn_tsdf_integrate)."""
+        nx, ny, nz, org = self._tsdf_volume_args("tsdf_integrate", tsdf, weight, origin)
+        r = range_images
+        if r.device != self.device or r.dtype != torch.float32 or not r.is_contiguous() or r.dim() != 3:
+            raise _lib.OvnError("tsdf_integrate: range_images must be a contiguous float32 (n,H,W) tensor on %s" % self.device)
+        if isinstance(poses, torch.Tensor):
+            p = poses.to(self.device, torch.float64).contiguous()
+        else:
+            p = torch.from_numpy(np.ascontiguousarray(np.asarray(poses, np.float64))).to(self.device)
+        n, h, w = (int(v) for v in r.shape)
+        if tuple(p.shape) != (n, 4, 4):
+            raise _lib.OvnError("tsdf_integrate: poses must be (%d,4,4) for %d range images, got %s" % (n, n, tuple(p.shape)))
+        with self._dev():
+            _lib.check(self.lib.ovn_tsdf_integrate(self._h, _ptr(tsdf), _ptr(weight), nx, ny, nz, org, float(voxel), float(trunc),
+                                                   float(max_weight), _ptr(r), _ptr(p), n, h, w, float(fov_up), float(fov_down),
+                                                   float(max_range), self._stream()),
+                       "ovn_tsdf_integrate")
+
+    def tsdf_triangles(self, tsdf: torch.Tensor, weight: torch.Tensor, origin, voxel: float, min_weight: float = 1.0,
+                       capacity: Optional[int] = None, out: Optional[torch.Tensor] = None):
+        """The zero level set of a fused volume as a triangle soup (ovn_tsdf_triangles, marching tetrahedra).  capacity=None counts
+        first and then writes every triangle; otherwise at most `capacity` triangles are written (0: count only), into `out`
+        ((capacity,3,3) float32) when given.  Returns (triangles (min(T, capacity),3,3) device tensor or None, T)."""
+        nx, ny, nz, org = self._tsdf_volume_args("tsdf_triangles", tsdf, weight, origin)
+        if out is not None:
+            if (out.device != self.device or out.dtype != torch.float32 or not out.is_contiguous() or out.dim() != 3
+                    or tuple(out.shape[1:]) != (3, 3)):
+                raise _lib.OvnError("tsdf_triangles: out must be a contiguous float32 (capacity,3,3) tensor on %s" % self.device)
+            if capacity is None:
+                capacity = int(out.shape[0])
+            if int(capacity) > int(out.shape[0]):
+                raise _lib.OvnError("tsdf_triangles: capacity %d exceeds the %d triangles of out" % (capacity, out.shape[0]))
+        count = torch.zeros(1, dtype=torch.int64, device=self.device)
+
+        def call(buf, cap):
+            with self._dev():
+                _lib.check(self.lib.ovn_tsdf_triangles(self._h, _ptr(tsdf), _ptr(weight), nx, ny, nz, org, float(voxel),
+                                                       float(min_weight), _ptr(buf), int(cap), _ptr(count), self._stream()),
+                           "ovn_tsdf_triangles")
+            return int(count.item())
+
+        if capacity is None:
+            total = call(None, 0)
+            capacity = total
+        elif int(capacity) < 0:
+            raise _lib.OvnError("tsdf_triangles: capacity %d < 0" % capacity)
+        capacity = int(capacity)
+        if capacity == 0:
+            return None, call(None, 0)
+        buf = out if out is not None else torch.empty((capacity, 3, 3), dtype=torch.float32, device=self.device)
+        total = call(buf, capacity)
+        return buf[:min(total, capacity)], total
+
     def icp_register(self, vertex: torch.Tensor, normal: torch.Tensor, rng: torch.Tensor, src_idx: torch.Tensor,
                      tgt_idx: torch.Tensor, init_pose: torch.Tensor, iterations: int = 20, max_dist: float = 2.0,
                      cos_min: float = 0.8, huber: float = 0.2, min_inliers: int = 64, fov_up: float = 3.0, fov_down: float = -25.0,

@@ -1,4 +1,4 @@
-"""Triangle meshes for `ovn_render_scans`: validation, PLY / OBJ readers, the ray tables of a sensor and the bounding-volume hierarchy.
+"""Triangle meshes for `ovn_render_scans`: validation, PLY / OBJ readers, a PLY writer, the ray tables of a sensor and the bounding-volume hierarchy.
 
 The hierarchy is built on the host, once per mesh, in vectorised NumPy (no Python loop over triangles; one step per tree LEVEL):
 triangles sorted by the 30-bit Morton code of their centroid, leaves of 4 consecutive triangles, an implicit complete binary tree over
@@ -247,6 +247,20 @@ class TriangleMesh(object):
             xyz = np.stack([vt[c].astype(np.float64) for c in "xyz"], axis=1)
             faces = ft["i"].astype(np.int64)
         return cls(xyz.astype(np.float32), faces)
+
+    def to_ply(self, path: str) -> None:
+        """binary_little_endian PLY: float x, y, z per vertex and a `uchar int vertex_indices` list per face.  `from_ply` reads it
+        back to the same arrays."""
+        head = ("ply\nformat binary_little_endian 1.0\ncomment overlapnet_amd TriangleMesh\nelement vertex %d\nproperty float x\n"
+                "property float y\nproperty float z\nelement face %d\nproperty list uchar int vertex_indices\nend_header\n"
+                % (self.n_vertices, self.n_triangles))
+        faces = np.empty(self.n_triangles, np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
+        faces["n"] = 3
+        faces["i"] = self.triangles
+        with open(path, "wb") as fh:
+            fh.write(head.encode("ascii"))
+            fh.write(self.vertices.astype("<f4").tobytes())
+            fh.write(faces.tobytes())
 
     @classmethod
     def from_obj(cls, path: str) -> "TriangleMesh":

@@ -1,0 +1,153 @@
+"""A map's mesh from a drive: range images and poses fused into a truncated signed distance volume on the GPU, and the volume's zero
+level set as a `mesh.TriangleMesh` (ovn_tsdf_integrate / ovn_tsdf_triangles, csrc/tsdf.hip).
+
+    vol = TsdfVolume(engine, lo, hi, voxel=0.2)
+    vol.integrate_scans(points, offsets, poses)        # or vol.integrate(range_images, poses)
+    mesh = vol.mesh()                                  # -> OverlapMap.from_mesh, mesh.to_ply, tools/localize.py --mesh
+
+The volume is dense: (nz, ny, nx) float32 tsdf and weight, at most 2^31 - 1 samples.  Argument errors raise before a GPU is touched.
+"""
+from __future__ import annotations
+
+from typing import Tuple
+
+import numpy as np
+
+from ._lib import OvnError
+from .mesh import MAX_TRIANGLES, TriangleMesh
+
+MAX_SAMPLES = 2 ** 31 - 1
+DEFAULT_TRUNC_VOXELS = 4.0
+
+
+def volume_shape(lo, hi, voxel: float) -> Tuple[int, int, int]:
+    """(nx, ny, nz): samples at lo + (i, j, k) * voxel up to the first one at or past hi on every axis (at least 2 per axis).  Raises
+    ValueError for bounds that are not 3 finite numbers with lo < hi, a voxel that is not > 0, or a volume over MAX_SAMPLES samples --
+    the message then names the voxel size that would fit."""
+    lo = np.asarray(lo, np.float64).reshape(-1)
+    hi = np.asarray(hi, np.float64).reshape(-1)
+    if lo.shape[0] != 3 or hi.shape[0] != 3:
+        raise ValueError("lo and hi must hold 3 numbers each, got %d and %d" % (lo.shape[0], hi.shape[0]))
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (lo < hi).all()):
+        raise ValueError("the bounds must be finite with lo < hi on every axis, got lo %s hi %s" % (lo.tolist(), hi.tolist()))
+    voxel = float(voxel)
+    if not (voxel > 0.0 and np.isfinite(voxel) and np.float32(voxel) > 0):
+        raise ValueError("voxel must be a finite number > 0, got %r" % (voxel,))
+    ext = hi - lo
+    n = np.maximum(np.ceil(ext / voxel - 1e-9) + 1.0, 2.0)
+    if float(np.prod(n)) > MAX_SAMPLES:
+        fit = float((np.prod(ext) / MAX_SAMPLES) ** (1.0 / 3.0))
+        shown = float("%.3g" % fit)                # the number the message prints must itself fit
+        while np.prod(np.maximum(np.ceil(ext / shown - 1e-9) + 1.0, 2.0)) > MAX_SAMPLES:
+            fit *= 1.01
+            shown = float("%.3g" % fit)
+        fit = shown
+        raise ValueError("a volume of %s m at voxel %g m has %.3g samples, over the limit of 2^31 - 1: a voxel of %.3g m fits"
+                         % (ext.tolist(), voxel, float(np.prod(n)), fit))
+    return int(n[0]), int(n[1]), int(n[2])
+
+
+class TsdfVolume(object):
+    """A dense TSDF over the box lo .. hi.  `trunc` (metres) defaults to 4 voxels; a sample's weight saturates at `max_weight`."""
+
+    def __init__(self, engine, lo, hi, voxel: float, trunc: float = None, max_weight: float = 64.0):
+        self.nx, self.ny, self.nz = volume_shape(lo, hi, voxel)
+        self.voxel = float(voxel)
+        self.trunc = DEFAULT_TRUNC_VOXELS * self.voxel if trunc is None else float(trunc)
+        self.max_weight = float(max_weight)
+        if not (self.trunc > 0.0 and np.isfinite(self.trunc)):
+            raise ValueError("trunc must be a finite number > 0, got %r" % (trunc,))
+        if not self.max_weight > 0.0:
+            raise ValueError("max_weight must be > 0, got %r" % (max_weight,))
+        self.origin = np.asarray(lo, np.float64).reshape(3).copy()
+        self.engine = engine
+        import torch
+        shape = (self.nz, self.ny, self.nx)
+        self.tsdf = torch.ones(shape, dtype=torch.float32, device=engine.device)
+        self.weight = torch.zeros(shape, dtype=torch.float32, device=engine.device)
+        self.n_scans = 0
+
+    @property
+    def n_samples(self) -> int:
+        return self.nx * self.ny * self.nz
+
+    def reset(self) -> None:
+        """Back to the fresh volume: tsdf = 1, weight = 0."""
+        self.tsdf.fill_(1.0)
+        self.weight.zero_()
+        self.n_scans = 0
+
+    @staticmethod
+    def _check_sensor(max_range: float) -> None:
+        if not (float(max_range) > 0.0 and np.isfinite(float(max_range))):
+            raise ValueError("max_range must be a finite number > 0, got %r" % (max_range,))
+
+    def integrate(self, range_images, poses, fov_up: float = 3.0, fov_down: float = -25.0, max_range: float = 50.0) -> None:
+        """Fuses range images ((n,H,W) float32, -1 = empty; device tensor or host array) taken at `poses` ((n,4,4) sensor to world),
+        in order.  The images must come from `project` / `render_scans` with the same field of view."""
+        import torch
+        self._check_sensor(max_range)
+        shape = tuple(range_images.shape)
+        if len(shape) != 3 or shape[1] < 1 or shape[2] < 1:
+            raise ValueError("range_images must be (n,H,W) with H, W >= 1, got %s" % (shape,))
+        pshape = tuple(np.shape(poses)) if not isinstance(poses, torch.Tensor) else tuple(poses.shape)
+        if pshape != (shape[0], 4, 4):
+            raise ValueError("poses must be (%d,4,4) for %d range images, got %s" % (shape[0], shape[0], pshape))
+        if shape[0] == 0:
+            return
+        if isinstance(range_images, torch.Tensor):
+            r = range_images.to(self.engine.device, torch.float32).contiguous()
+        else:
+            r = torch.from_numpy(np.ascontiguousarray(range_images, np.float32)).to(self.engine.device)
+        self.engine.tsdf_integrate(self.tsdf, self.weight, self.origin, self.voxel, self.trunc, self.max_weight, r, poses, fov_up,
+                                   fov_down, max_range)
+        self.n_scans += shape[0]
+
+    def integrate_scans(self, points, offsets, poses, proj_h: int = 64, proj_w: int = 900, fov_up: float = 3.0,
+                        fov_down: float = -25.0, max_range: float = 50.0, chunk: int = 64) -> None:
+        """Projects raw scans -- `points` (total,4) float32 of concatenated scans, `offsets` (n+1) int64 -- with `engine.project` and
+        fuses them, `chunk` scans at a time."""
+        import torch
+        self._check_sensor(max_range)
+        offs = np.asarray(offsets.cpu() if isinstance(offsets, torch.Tensor) else offsets, np.int64).reshape(-1)
+        n = offs.shape[0] - 1
+        pshape = tuple(np.shape(poses)) if not isinstance(poses, torch.Tensor) else tuple(poses.shape)
+        if n < 0 or pshape != (max(n, 0), 4, 4):
+            raise ValueError("poses must be (n,4,4) for the n = %d scans of offsets, got %s" % (n, pshape))
+        if int(chunk) < 1 or int(proj_h) < 1 or int(proj_w) < 1:
+            raise ValueError("chunk, proj_h and proj_w must be >= 1, got %r, %r, %r" % (chunk, proj_h, proj_w))
+        if n == 0:
+            return
+        if np.any(np.diff(offs) < 0) or offs[0] < 0 or offs[-1] > int(points.shape[0]):
+            raise ValueError("offsets must ascend within the %d points" % int(points.shape[0]))
+        dev = self.engine.device
+        pts = points if isinstance(points, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(points, np.float32))
+        pts = pts.to(dev, torch.float32).contiguous()
+        d_offs = torch.from_numpy(offs).to(dev)
+        poses = poses if isinstance(poses, torch.Tensor) else np.asarray(poses, np.float64)
+        for a in range(0, n, int(chunk)):
+            b = min(n, a + int(chunk))
+            max_points = int(np.diff(offs[a:b + 1]).max())
+            r = self.engine.project(pts, d_offs[a:b + 1], max_points, int(proj_h), int(proj_w), fov_up, fov_down, max_range,
+                                    want=("range",))["range"]
+            self.engine.tsdf_integrate(self.tsdf, self.weight, self.origin, self.voxel, self.trunc, self.max_weight, r, poses[a:b],
+                                       fov_up, fov_down, max_range)
+        self.n_scans += n
+
+    def triangles(self, min_weight: float = 1.0):
+        """(T,3,3) float32 device tensor of the triangle soup, in contract order: one counting call, then one writing call."""
+        tri, total = self.engine.tsdf_triangles(self.tsdf, self.weight, self.origin, self.voxel, min_weight)
+        if total == 0:
+            raise OvnError("TsdfVolume.mesh: no surface: no cell has all eight corners seen %g times and a sign change "
+                           "(%d scans fused)" % (min_weight, self.n_scans))
+        return tri
+
+    def mesh(self, min_weight: float = 1.0) -> TriangleMesh:
+        """The zero level set as a TriangleMesh: a soup, vertices (3T,3) and triangles arange(3T).reshape(T,3)."""
+        if np.isnan(float(min_weight)):
+            raise ValueError("min_weight is NaN")
+        tri = self.triangles(min_weight)
+        t = int(tri.shape[0])
+        if t > MAX_TRIANGLES:
+            raise OvnError("TsdfVolume.mesh: %d triangles exceed the 2^27 a TriangleMesh holds: use a larger voxel" % t)
+        return TriangleMesh(tri.reshape(3 * t, 3).cpu().numpy(), np.arange(3 * t, dtype=np.int32).reshape(t, 3))
