@@ -329,7 +329,11 @@ int ovn_heads_spectral(ovn_ctx* ctx, const float* feats_l_dev, const float* spec
  * n == 0 is a no-op.  Workspace (ovn_workspace_bytes): that of a head call over one chunk, plus 2 MB of query state per segment of a
  * pass (at most OVN_SEG_PASS_MAX x 2 MB), plus a context-owned table of 8 (B + 1) + 4 B + 8 n bytes on the device and 8 (B + 1) + 4 B
  * in pinned host memory.  The host arrays may be reused as soon as the call returns.  Successive segmented calls may use different
- * streams: each waits for the previous one's kernels before it rewrites the table. */
+ * streams: each waits for the previous one's kernels before it rewrites the table.  The table is staged through ONE pinned buffer:
+ * a segmented call (this one or ovn_top_k_segments) made while the previous one's table copy is still pending on its stream waits on
+ * the host for that copy.  A segmented call that follows a drained stream only enqueues.  (The wait guards the reuse of the staging
+ * buffer, it returns nothing to the host: a second staging buffer would remove it.  Kept, because the table is a few KB whose copy
+ * is over long before a caller has post-processed one batch and assembled the next.) */
 int ovn_heads_segments(ovn_ctx* ctx, const float* feats_pool_dev, const float* spec_pool_dev, const float* dcache_pool_dev,
                        const int32_t* cand_idx_dev, const float* feats_q_dev, const float* spec_q_dev, const int32_t* query_idx,
                        const int64_t* seg_offsets, int64_t B, int64_t n, float* overlap_dev, int32_t* yaw_dev, float* logit_dev,
@@ -388,7 +392,8 @@ int ovn_top_k(ovn_ctx* ctx, const float* overlap_dev, const int32_t* yaw_dev, co
  * same way, index_offset 0): a NULL ids_dev means the position inside the segment; k = 1 is ovn_best_match's record; an empty
  * segment gives k records { -1, 0, 0, 0 }.  A segment costs the time ovn_top_k takes on it.  OVN_ERR_ARG for k outside
  * 1..OVN_TOP_K_MAX, bad offsets, a NULL or misaligned buffer.  B == 0 is a no-op.  Workspace: the context's segment table
- * (8 (B + 1) bytes, see ovn_heads_segments). */
+ * (8 (B + 1) bytes, see ovn_heads_segments; it shares that call's one pinned staging buffer and its host wait for a table copy that
+ * is still pending). */
 int ovn_top_k_segments(ovn_ctx* ctx, const float* overlap_dev, const int32_t* yaw_dev, const int32_t* ids_dev,
                        const int64_t* seg_offsets, int64_t B, int k, float threshold, int32_t* out_dev, void* stream);
 

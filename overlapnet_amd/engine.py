@@ -275,6 +275,8 @@ class OvnEngine:
         form (`heads(feats_pool, feats_q[q:q + 1], lidx=cand_idx[segment], spec_l=spec_pool, spec_r=spec_q[q:q + 1],
         dcache_l=dcache_pool)`).  seg_offsets / query_idx are host data (lists, arrays or tensors), checked here; cand_idx is
         range-checked on the host unless it is already a device tensor (see `_idx`).  spec_pool / spec_q: both or neither.
+        The library stages the table through one pinned buffer: a segmented call (this one or `top_k_segments`) made while the
+        previous one's table copy is still pending on its stream waits on the host for that copy; otherwise the call only enqueues.
         Returns dict of flat device tensors in pair order: overlap (n) f32, yaw (n) i32 [, logit (n), corr (n, feat_w)]."""
         if not self._head_ready:
             raise _lib.OvnError("head weights not loaded")
@@ -847,7 +849,8 @@ class OvnEngine:
                        threshold: float = 0.3, ids: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """`top_k` of every segment of a `heads_segments` batch in one launch (`ovn_top_k_segments`): a (B, k, 4) int32 device
         tensor; segment b's k records are bit for bit `top_k(overlap[o0:o1], yaw[o0:o1], k, threshold, ids=ids[o0:o1])` (ids None:
-        the position inside the segment); an empty segment gives k records {-1, 0, 0, 0}.  seg_offsets: host data, checked here."""
+        the position inside the segment); an empty segment gives k records {-1, 0, 0, 0}.  seg_offsets: host data, checked here.
+        Shares `heads_segments`' pinned staging buffer, and with it the host wait for a table copy that is still pending."""
         offs, _ = segment_table(seg_offsets, None, None)
         k = check_top_k(k)
         n, B = int(offs[-1]), len(offs) - 1
