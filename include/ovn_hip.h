@@ -615,6 +615,51 @@ int ovn_tsdf_integrate(ovn_ctx* ctx, float* tsdf_dev, float* weight_dev, int nx,
 int ovn_tsdf_triangles(ovn_ctx* ctx, const float* tsdf_dev, const float* weight_dev, int nx, int ny, int nz, const double* origin,
                        double voxel, double min_weight, float* triangles_dev, int64_t capacity, int64_t* n_triangles_dev, void* stream);
 
+/* ovn_tsdf_raycast: a view of the volume of ovn_tsdf_integrate from a pose, one ray per pixel of the range image marched through
+ * the volume (csrc/tsdf_raycast.hip).  It serves a model that changes with every scan: no mesh, no hierarchy.
+ * `stream` is the SECOND parameter of this call and of ovn_tsdf_bricks, directly after ctx: the stream-contract table of
+ * tests/test_gpu_stream_contract.py lists the prototypes whose parameter list ENDS in the stream, and the change that added these two
+ * calls could not edit that table; tests/test_gpu_raycast_stream.py runs both on a non-default stream instead.  The stream contract
+ * itself ("Conventions") holds unchanged: both calls only enqueue work on `stream` and restore the caller's device.
+ *   tsdf_dev, weight_dev, nx, ny, nz, origin, voxel: the volume of ovn_tsdf_integrate -- samples (nz,ny,nx) f32, x fastest, sample
+ *                 (i,j,k) at origin + (i,j,k) voxel; origin (3 doubles on the HOST), voxel, min_weight, min_range, max_range and step
+ *                 are rounded to f32
+ *   poses_dev, cos_az_dev .. sin_pitch_dev and the outputs range_dev, vertex_dev, normal_dev, stacked_dev, use_depth, use_normals:
+ *                 those of ovn_render_scans -- R and o rounded to f32, a pose with a non-finite entry gives an all-empty scan, -1 in
+ *                 every channel of an empty pixel, vertex = (t d_s, 1), normal_dev = the kernel of ovn_normals on the range and vertex
+ *                 images this call wrote, stacked = depth | normals.  Each output may be NULL
+ * Every operation below is one f32 operation rounded on its own, every dot product is summed (a0 b0 + a1 b1) + a2 b2:
+ *   1  d_s, d_w as in ovn_render_scans;  inv = 1 / voxel;  per axis a: g_o[a] = (o[a] - origin[a]) inv,  g_d[a] = d_w[a] inv
+ *   2  sample k = 0, 1, .. sits at t_k = min_range + (float)k step (one multiply, one add), taken while t_k < max_range: K samples
+ *   3  g[a] = g_o[a] + t_k g_d[a];  base corner (i,j,k) = floor(g),  f = g - floor(g)
+ *   4  the sample is VALID when 0 <= i <= nx - 2 (likewise j, k; a NaN fails) and all eight corners have weight >= min_weight
+ *   5  F = trilinear with lerp(a, b, f) = a + f (b - a): four lerps along x, two along y, one along z; a NaN F makes the sample invalid
+ *   6  an invalid sample clears the state "previous sample valid and positive"; a valid F > 0 sets it with F_p = F, t_p = t_k; a valid
+ *      F <= 0 ends the ray: with the state set a hit at t = t_p + (t_k - t_p) (F_p / (F_p - F)), with it clear an empty pixel (the ray
+ *      came out behind a surface whose front it never saw).  A ray that runs out of samples is empty.
+ *   bricks_dev    NULL, or the (ceil(nz/8), ceil(ny/8), ceil(nx/8)) byte mask of ovn_tsdf_bricks for this weight_dev and min_weight: a 0
+ *                 promises that no sample of that 8 x 8 x 8 brick has weight >= min_weight, and a sample whose base corner lies in
+ *                 such a brick is invalid without a read of the volume.  With a mask that keeps the promise (extra 1s are allowed)
+ *                 the output has the bits of the NULL route, which is the definition and the validation entry.
+ * One writer per pixel, no atomics: the same arguments give the same bits, and a pose renders alone as in any batch.
+ * OVN_ERR_ARG, before any launch (the outputs are untouched): a NULL volume buffer or origin, a dimension < 2 or more than 2^31 - 1
+ * samples, a non-finite origin, voxel not > 0, H or W < 1 or H W > 2^31 - 1, n < 0, min_range, max_range or step not finite and > 0
+ * (after rounding to f32), min_range >= max_range, K > OVN_RAYCAST_MAX_SAMPLES, a NaN min_weight, a misaligned vertex_dev,
+ * stacked_dev with neither use_depth nor use_normals, and for n > 0 a NULL poses_dev or table.  n == 0 is a no-op. */
+#define OVN_RAYCAST_MAX_SAMPLES (1ll << 20)
+int ovn_tsdf_raycast(ovn_ctx* ctx, void* stream, const float* tsdf_dev, const float* weight_dev, int nx, int ny, int nz,
+                     const double* origin, double voxel, double min_weight, const uint8_t* bricks_dev, const double* poses_dev,
+                     int64_t n_scans, int proj_h, int proj_w, const float* cos_az_dev, const float* sin_az_dev,
+                     const float* cos_pitch_dev, const float* sin_pitch_dev, double min_range, double max_range, double step,
+                     float* range_dev, float* vertex_dev, float* normal_dev, float* stacked_dev, int use_depth, int use_normals);
+
+/* ovn_tsdf_bricks: the mask ovn_tsdf_raycast takes.  bricks_dev (ceil(nz/8), ceil(ny/8), ceil(nx/8)) bytes, x fastest: 1 exactly where
+ * some sample (i,j,k) of the brick, i in 8 bi .. min(8 bi + 7, nx - 1) .., has weight >= (float)min_weight, else 0.  One writer per
+ * byte, no atomics.  OVN_ERR_ARG, before any launch: a NULL buffer, a dimension < 2 or more than 2^31 - 1 samples, a NaN min_weight.
+ * `stream` is the second parameter: see ovn_tsdf_raycast. */
+int ovn_tsdf_bricks(ovn_ctx* ctx, void* stream, const float* weight_dev, int nx, int ny, int nz, double min_weight,
+                    uint8_t* bricks_dev);
+
 /* The per-point part of range_projection alone (src/utils/utils.py:75-104), exactly as ovn_project's scatter kernel evaluates it:
  * for each of n float32 points (x,y,z,*) yaw = -np.arctan2(y, x), pitch = np.arcsin(z / depth) with NumPy's float32 results
  * (csrc/svml_f32.h) and the pixel py * proj_w + px the point falls into (-1 for a point the range filter drops).  Outputs may

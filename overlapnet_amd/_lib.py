@@ -78,6 +78,10 @@ SIGNATURES = {
                                      _vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, _vp]),
     "ovn_tsdf_triangles": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_double, _vp,
                                      C.c_int64, _vp, _vp]),
+    "ovn_tsdf_raycast": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_double, _vp, _vp,
+                                   C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp,
+                                   C.c_int, C.c_int]),
+    "ovn_tsdf_bricks": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp]),
     "ovn_projection_angles": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp]),
     "ovn_gt_range_images": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double,
                                       C.c_double, _vp, _vp]),

@@ -1403,6 +1403,52 @@ int ovn_tsdf_triangles(ovn_ctx* ctx, const float* tsdf_dev, const float* weight_
                                     n_triangles_dev, (hipStream_t)stream);
 }
 
+int ovn_tsdf_raycast(ovn_ctx* ctx, void* stream, const float* tsdf_dev, const float* weight_dev, int nx, int ny, int nz,
+                     const double* origin, double voxel, double min_weight, const uint8_t* bricks_dev, const double* poses_dev,
+                     int64_t n_scans, int proj_h, int proj_w, const float* cos_az_dev, const float* sin_az_dev,
+                     const float* cos_pitch_dev, const float* sin_pitch_dev, double min_range, double max_range, double step,
+                     float* range_dev, float* vertex_dev, float* normal_dev, float* stacked_dev, int use_depth, int use_normals) {
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_tsdf_raycast: ctx is NULL");
+  OVN_REQUIRE(tsdf_dev && weight_dev, OVN_ERR_ARG, "ovn_tsdf_raycast: NULL volume buffer");
+  OVN_REQUIRE(tsdf_volume_ok(nx, ny, nz, origin, voxel), OVN_ERR_ARG,
+              "ovn_tsdf_raycast: volume %d x %d x %d (each >= 2, at most 2^31 - 1 samples) needs a finite origin and a voxel > 0", nx,
+              ny, nz);
+  OVN_REQUIRE(proj_h >= 1 && proj_w >= 1 && (int64_t)proj_h * proj_w <= 2147483647ll, OVN_ERR_ARG,
+              "ovn_tsdf_raycast: image %d x %d outside 1 .. 2^31 - 1 pixels", proj_h, proj_w);
+  OVN_REQUIRE(n_scans >= 0 && n_scans <= 2147483647ll, OVN_ERR_ARG, "ovn_tsdf_raycast: bad n_scans %lld", (long long)n_scans);
+  const float mn = (float)min_range, mx = (float)max_range, st = (float)step;
+  OVN_REQUIRE(mn > 0.0f && std::isfinite(mn) && mx > 0.0f && std::isfinite(mx) && st > 0.0f && std::isfinite(st), OVN_ERR_ARG,
+              "ovn_tsdf_raycast: min_range %g, max_range %g and step %g must be finite and > 0", min_range, max_range, step);
+  OVN_REQUIRE(mn < mx, OVN_ERR_ARG, "ovn_tsdf_raycast: min_range %g is not below max_range %g", min_range, max_range);
+  const long long K = ovn_tsdf_raycast_samples(min_range, max_range, step, OVN_RAYCAST_MAX_SAMPLES);
+  OVN_REQUIRE(K <= OVN_RAYCAST_MAX_SAMPLES, OVN_ERR_ARG, "ovn_tsdf_raycast: more than 2^20 samples per ray (range %g .. %g, step %g)",
+              min_range, max_range, step);
+  OVN_REQUIRE(min_weight == min_weight, OVN_ERR_ARG, "ovn_tsdf_raycast: min_weight is NaN");
+  OVN_REQUIRE(!vertex_dev || aligned16(vertex_dev), OVN_ERR_ARG, "ovn_tsdf_raycast: vertex_dev is not 16-byte aligned");
+  use_depth = use_depth ? 1 : 0;
+  use_normals = use_normals ? 1 : 0;
+  OVN_REQUIRE(!stacked_dev || use_depth + use_normals > 0, OVN_ERR_ARG,
+              "ovn_tsdf_raycast: stacked output requested with no channel enabled");
+  if (n_scans == 0) return OVN_OK;
+  OVN_REQUIRE(poses_dev != nullptr, OVN_ERR_ARG, "ovn_tsdf_raycast: poses is NULL");
+  OVN_REQUIRE(cos_az_dev && sin_az_dev && cos_pitch_dev && sin_pitch_dev, OVN_ERR_ARG, "ovn_tsdf_raycast: NULL direction table");
+  OVN_ON_DEVICE(ctx->device);
+  return ovn_tsdf_raycast_forward(ctx, tsdf_dev, weight_dev, nx, ny, nz, origin, voxel, min_weight, bricks_dev, poses_dev, n_scans,
+                                  proj_h, proj_w, cos_az_dev, sin_az_dev, cos_pitch_dev, sin_pitch_dev, min_range, step, (int)K,
+                                  range_dev, vertex_dev, normal_dev, stacked_dev, use_depth, use_normals, (hipStream_t)stream);
+}
+
+int ovn_tsdf_bricks(ovn_ctx* ctx, void* stream, const float* weight_dev, int nx, int ny, int nz, double min_weight,
+                    uint8_t* bricks_dev) {
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_tsdf_bricks: ctx is NULL");
+  OVN_REQUIRE(weight_dev && bricks_dev, OVN_ERR_ARG, "ovn_tsdf_bricks: NULL buffer");
+  OVN_REQUIRE(nx >= 2 && ny >= 2 && nz >= 2 && (int64_t)nx * ny <= 2147483647ll && (int64_t)nx * ny * nz <= 2147483647ll, OVN_ERR_ARG,
+              "ovn_tsdf_bricks: volume %d x %d x %d (each >= 2, at most 2^31 - 1 samples)", nx, ny, nz);
+  OVN_REQUIRE(min_weight == min_weight, OVN_ERR_ARG, "ovn_tsdf_bricks: min_weight is NaN");
+  OVN_ON_DEVICE(ctx->device);
+  return ovn_tsdf_bricks_forward(weight_dev, nx, ny, nz, min_weight, bricks_dev, (hipStream_t)stream);
+}
+
 int ovn_gt_range_images(ovn_ctx* ctx, const float* points_dev, const int64_t* offsets_dev, int n_scans,
                         int64_t max_points_per_scan, const double* ref_poses_dev, const double* inv_cur_pose_dev, int proj_h,
                         int proj_w, double fov_up_deg, double fov_down_deg, double max_range, float* range_dev, void* stream) {

@@ -662,6 +662,16 @@ int ovn_tsdf_triangles_forward(ovn_ctx* ctx, const float* tsdf, const float* wei
                                double voxel, double min_weight, float* triangles, int64_t capacity, int64_t* n_triangles,
                                hipStream_t stream);
 
+// tsdf_raycast.hip: the arguments are those of ovn_tsdf_raycast / ovn_tsdf_bricks, validated there (n >= 1; K = the sample count of
+// ovn_tsdf_raycast_samples, which counts k with min_range + (float)k step < max_range in f32 up to cap + 1)
+long long ovn_tsdf_raycast_samples(double min_range, double max_range, double step, long long cap);
+int ovn_tsdf_raycast_forward(ovn_ctx* ctx, const float* tsdf, const float* weight, int nx, int ny, int nz, const double* origin,
+                             double voxel, double min_weight, const uint8_t* bricks, const double* poses, int64_t n, int H, int W,
+                             const float* cos_az, const float* sin_az, const float* cos_pitch, const float* sin_pitch, double min_range,
+                             double step, int K, float* range, float* vertex, float* normal, float* stacked, int use_depth,
+                             int use_normals, hipStream_t stream);
+int ovn_tsdf_bricks_forward(const float* weight, int nx, int ny, int nz, double min_weight, uint8_t* bricks, hipStream_t stream);
+
 // render_mesh.hip: nodes / order NULL = every ray walks all T triangles; the arguments are those of ovn_render_scans, validated there
 int ovn_render_scans_forward(ovn_ctx* ctx, const float* vertices, int V, const int32_t* triangles, int T, const float* nodes,
                              const int32_t* order, int NL, const double* poses, int64_t n, int H, int W, const float* cos_az,

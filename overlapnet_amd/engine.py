@@ -1008,13 +1008,7 @@ class OvnEngine:
             raise _lib.OvnError("render_scans: poses must be (n,4,4), got %s" % (tuple(p.shape),))
         n, dev = p.shape[0], self.device
         proj_h, proj_w = int(proj_h), int(proj_w)
-        key = (proj_h, proj_w, float(fov_up), float(fov_down))
-        tabs = self._render_tables.get(key)
-        if tabs is None and proj_h >= 1 and proj_w >= 1:
-            from .mesh import direction_tables
-            tabs = tuple(torch.from_numpy(t).to(dev) for t in direction_tables(proj_h, proj_w, fov_up, fov_down))
-            self._render_tables = {key: tabs}      # the last geometry only
-        tabs = tabs or (None,) * 4
+        tabs = self._direction_tables(proj_h, proj_w, fov_up, fov_down)
         md = mesh.device(self, with_bvh=not exhaustive)
         nodes, order, leaves = (None, None, 0) if exhaustive else (md["nodes"], md["order"], md["leaves"])
         mk = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)
@@ -1117,6 +1111,101 @@ class OvnEngine:
         buf = out if out is not None else torch.empty((capacity, 3, 3), dtype=torch.float32, device=self.device)
         total = call(buf, capacity)
         return buf[:min(total, capacity)], total
+
+    def _direction_tables(self, proj_h: int, proj_w: int, fov_up: float, fov_down: float):
+        """The four device tables of `mesh.direction_tables` for this geometry (the last geometry is kept), or four None for an
+        image size the library will refuse."""
+        key = (proj_h, proj_w, float(fov_up), float(fov_down))
+        tabs = self._render_tables.get(key)
+        if tabs is None and proj_h >= 1 and proj_w >= 1:
+            from .mesh import direction_tables
+            tabs = tuple(torch.from_numpy(t).to(self.device) for t in direction_tables(proj_h, proj_w, fov_up, fov_down))
+            self._render_tables = {key: tabs}
+        return tabs or (None,) * 4
+
+    def tsdf_bricks(self, weight: torch.Tensor, min_weight: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The byte mask `tsdf_raycast` takes: (ceil(nz/8), ceil(ny/8), ceil(nx/8)) uint8, 1 where some sample of the 8 x 8 x 8 brick
+        has weight >= min_weight (ovn_tsdf_bricks), written into `out` when given."""
+        if weight.device != self.device or weight.dtype != torch.float32 or not weight.is_contiguous() or weight.dim() != 3:
+            raise _lib.OvnError("tsdf_bricks: weight must be a contiguous float32 (nz,ny,nx) tensor on %s" % self.device)
+        nz, ny, nx = (int(v) for v in weight.shape)
+        shape = tuple(-(-v // 8) for v in (nz, ny, nx))
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        elif out.device != self.device or out.dtype != torch.uint8 or not out.is_contiguous() or tuple(out.shape) != shape:
+            raise _lib.OvnError("tsdf_bricks: out must be a contiguous uint8 %s tensor on %s" % (shape, self.device))
+        with self._dev():
+            _lib.check(self.lib.ovn_tsdf_bricks(self._h, self._stream(), _ptr(weight), nx, ny, nz, float(min_weight), _ptr(out)),
+                       "ovn_tsdf_bricks")
+        return out
+
+    def tsdf_raycast(self, tsdf: torch.Tensor, weight: torch.Tensor, origin, voxel: float, poses, proj_h: int = 64, proj_w: int = 900,
+                     fov_up: float = 3.0, fov_down: float = -25.0, min_range: float = 0.5, max_range: float = 50.0,
+                     step: Optional[float] = None, min_weight: float = 1.0, bricks: Optional[torch.Tensor] = None,
+                     want: Sequence[str] = ("range", "normal"), stacked_flags: Optional[Tuple[bool, ...]] = None,
+                     stacked_out: Optional[torch.Tensor] = None, out: Optional[Dict[str, torch.Tensor]] = None):
+        """Views of the volume tsdf / weight ((nz,ny,nx) float32 device tensors, sample (i,j,k) at origin + (i,j,k) * voxel) from
+        `poses` ((n,4,4) float64 sensor-to-world, host array or device tensor): one ray per pixel marched from min_range to max_range
+        in steps of `step` (default: one voxel), the first crossing from positive to non-positive tsdf is the hit (ovn_tsdf_raycast;
+        DESIGN.md section 31).  `want` selects outputs among range, vertex, normal; stacked_flags = (use_depth, use_normals)
+        additionally assembles the (n,H,W,C) leg input (into `stacked_out` when given).  bricks: the mask of `tsdf_bricks` for this
+        weight and min_weight, or None.  out: a dict name -> contiguous float32 tensor of that output's shape (a slice along the first
+        axis of a caller's buffer) to write into instead of a fresh tensor.  Returns a dict of device tensors."""
+        bad = [k for k in want if k not in ("range", "vertex", "normal")]
+        if bad:
+            raise _lib.OvnError("tsdf_raycast: no output %s (a ray-cast view has range, vertex, normal)" % bad)
+        nx, ny, nz, org = self._tsdf_volume_args("tsdf_raycast", tsdf, weight, origin)
+        if isinstance(poses, torch.Tensor):
+            p = poses.to(self.device, torch.float64).contiguous()
+        else:
+            p = torch.from_numpy(np.ascontiguousarray(np.asarray(poses, np.float64))).to(self.device)
+        if p.dim() != 3 or tuple(p.shape[1:]) != (4, 4):
+            raise _lib.OvnError("tsdf_raycast: poses must be (n,4,4), got %s" % (tuple(p.shape),))
+        n, dev = int(p.shape[0]), self.device
+        proj_h, proj_w = int(proj_h), int(proj_w)
+        if bricks is not None:
+            shape = tuple(-(-v // 8) for v in (nz, ny, nx))
+            if bricks.device != dev or bricks.dtype != torch.uint8 or not bricks.is_contiguous() or tuple(bricks.shape) != shape:
+                raise _lib.OvnError("tsdf_raycast: bricks must be a contiguous uint8 %s tensor on %s" % (shape, dev))
+        out = dict(out or {})
+        unknown = [k for k in out if k not in ("range", "vertex", "normal")]
+        if unknown:
+            raise _lib.OvnError("tsdf_raycast: out names %s; it takes range, vertex, normal" % unknown)
+        bufs = {}
+        for k, tail in (("range", ()), ("vertex", (4,)), ("normal", (3,))):
+            shape = (n, proj_h, proj_w) + tail
+            if k in out:
+                t = out[k]
+                if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape:
+                    raise _lib.OvnError("tsdf_raycast: out[%r] must be a contiguous float32 %s tensor on %s" % (k, shape, dev))
+                bufs[k] = t
+            elif k in want:
+                bufs[k] = torch.empty(shape, dtype=torch.float32, device=dev)
+        stk = None
+        ud = un = 0
+        if stacked_flags is not None:
+            if len(stacked_flags) != 2:
+                raise _lib.OvnError("tsdf_raycast: stacked_flags is (use_depth, use_normals)")
+            ud, un = (int(bool(v)) for v in stacked_flags)
+            c = ud + 3 * un
+            if stacked_out is not None:
+                if (stacked_out.device != dev or stacked_out.dtype != torch.float32 or not stacked_out.is_contiguous()
+                        or tuple(stacked_out.shape) != (n, proj_h, proj_w, c)):
+                    raise _lib.OvnError("stacked_out must be a contiguous float32 (%d,%d,%d,%d) tensor on %s" % (n, proj_h, proj_w, c, dev))
+                stk = stacked_out
+            else:
+                stk = torch.empty((n, proj_h, proj_w, max(c, 1)), dtype=torch.float32, device=dev)
+        tabs = self._direction_tables(proj_h, proj_w, fov_up, fov_down)
+        with self._dev():
+            _lib.check(self.lib.ovn_tsdf_raycast(self._h, self._stream(), _ptr(tsdf), _ptr(weight), nx, ny, nz, org, float(voxel),
+                                                 float(min_weight), _ptr(bricks), _ptr(p), n, proj_h, proj_w, _ptr(tabs[0]),
+                                                 _ptr(tabs[1]), _ptr(tabs[2]), _ptr(tabs[3]), float(min_range), float(max_range),
+                                                 float(voxel if step is None else step), _ptr(bufs.get("range")),
+                                                 _ptr(bufs.get("vertex")), _ptr(bufs.get("normal")), _ptr(stk), ud, un),
+                       "ovn_tsdf_raycast")
+        if stk is not None:
+            bufs["stacked"] = stk
+        return bufs
 
     def icp_register(self, vertex: torch.Tensor, normal: torch.Tensor, rng: torch.Tensor, src_idx: torch.Tensor,
                      tgt_idx: torch.Tensor, init_pose: torch.Tensor, iterations: int = 20, max_dist: float = 2.0,

@@ -224,20 +224,52 @@ class OverlapMap(object):
         its range exceeds it -- the blind zone of a real sensor.  The mesh is two-sided, so a pose inside a closed solid sees that
         solid from inside in every pixel and the default 0 keeps it; with min_range above the solid's half width it is dropped.  The
         rendered images themselves are not changed by it."""
+        def render(eng, p, h, w, flags):
+            return eng.render_scans(mesh, p, h, w, fov_up, fov_down, max_range, want=("range",), stacked_flags=flags)
+        return cls._from_renderer("OverlapMap.from_mesh", "the mesh's", render, infer, poses, resolution, reach, min_valid_fraction,
+                                  chunk, fov_up, fov_down, max_range, min_range)
+
+    @classmethod
+    def from_tsdf(cls, infer, volume, poses, resolution: float, reach: Optional[float] = None, min_valid_fraction: float = 0.1,
+                  chunk: Optional[int] = None, fov_up: float = 3.0, fov_down: float = -25.0, max_range: float = 50.0,
+                  min_range: float = 0.0, ray_min_range: float = 0.5, step: Optional[float] = None,
+                  min_weight: float = 1.0) -> "OverlapMap":
+        """`from_mesh` without the mesh: the map's frames are views of `volume` (tsdf.TsdfVolume) ray-cast at `poses`
+        (`TsdfVolume.render_scans`, ovn_tsdf_raycast).  Chunking, the keep rule (min_valid_fraction, min_range) and the caching are
+        those of `from_mesh`; ray_min_range, step and min_weight are the march parameters of the ray caster.  The brick mask is built
+        once for the whole map.  A map built this way is saved and loaded as a mesh-built one is, with the volume's `mesh()` or the
+        volume re-fused by the caller; `load` itself renders from a mesh."""
+        mask = []                        # built by the first chunk: the shared part checks its arguments before any GPU work
+
+        def render(eng, p, h, w, flags):
+            if eng is not volume.engine:
+                raise OvnError("OverlapMap.from_tsdf: the volume lives on another engine than the Infer's")
+            if not mask:
+                mask.append(volume.bricks(min_weight))
+            return volume.render_scans(p, h, w, fov_up, fov_down, ray_min_range, max_range, step, min_weight, bricks=mask[0],
+                                       want=("range",), stacked_flags=flags)
+        return cls._from_renderer("OverlapMap.from_tsdf", "the volume's", render, infer, poses, resolution, reach, min_valid_fraction,
+                                  chunk, fov_up, fov_down, max_range, min_range)
+
+    @classmethod
+    def _from_renderer(cls, what, whose, render, infer, poses, resolution, reach, min_valid_fraction, chunk, fov_up, fov_down,
+                       max_range, min_range) -> "OverlapMap":
+        """The part `from_mesh` and `from_tsdf` share: render(engine, poses, H, W, flags) -> dict(range, stacked) per chunk, the keep
+        rule, the leg, the cache and the cell table."""
         if getattr(infer, "_world", 1) > 1:
-            raise OvnError("OverlapMap.from_mesh: a sharded Infer (world %d) is not supported: build the map on a single-rank Infer"
-                           % infer._world)
+            raise OvnError("%s: a sharded Infer (world %d) is not supported: build the map on a single-rank Infer"
+                           % (what, infer._world))
         if infer.use_intensity or infer.use_class_probabilities:
-            raise OvnError("OverlapMap.from_mesh: a rendered scan has no intensity and no class probabilities, but this Infer's model "
+            raise OvnError("%s: a rendered scan has no intensity and no class probabilities, but this Infer's model "
                            "takes %s; use a model with depth and / or normals only"
-                           % " and ".join(n for n, f in (("intensity", infer.use_intensity),
-                                                         ("class probabilities", infer.use_class_probabilities)) if f))
+                           % (what, " and ".join(n for n, f in (("intensity", infer.use_intensity),
+                                                                ("class probabilities", infer.use_class_probabilities)) if f)))
         if len(infer.feature_volumes) != 0:
-            raise OvnError("OverlapMap.from_mesh: the Infer already caches %d frames; the map needs slots 0 .. M-1 "
-                           "(infer.feature_volumes = [])" % len(infer.feature_volumes))
+            raise OvnError("%s: the Infer already caches %d frames; the map needs slots 0 .. M-1 "
+                           "(infer.feature_volumes = [])" % (what, len(infer.feature_volumes)))
         p = np.ascontiguousarray(np.asarray(poses, np.float64))
         if p.ndim != 3 or p.shape[1:] != (4, 4) or p.shape[0] < 1:
-            raise ValueError("OverlapMap.from_mesh: poses must be (M,4,4) with M >= 1, got %s" % (p.shape,))
+            raise ValueError("%s: poses must be (M,4,4) with M >= 1, got %s" % (what, p.shape))
         eng = infer.engine
         h, w, c = (int(v) for v in infer.inputShape)
         step = render_chunk(h, w, c) if chunk is None else max(1, int(chunk))
@@ -245,7 +277,7 @@ class OverlapMap(object):
         cache = infer.feature_volumes
         keep = np.zeros(p.shape[0], bool)
         for a in range(0, p.shape[0], step):
-            r = eng.render_scans(mesh, p[a:a + step], h, w, fov_up, fov_down, max_range, want=("range",), stacked_flags=flags)
+            r = render(eng, p[a:a + step], h, w, flags)
             k = keep_scans((r["range"] > float(min_range)).sum(dim=(1, 2)).cpu().numpy(), h * w, min_valid_fraction)
             keep[a:a + step] = k
             if k.all():
@@ -254,8 +286,8 @@ class OverlapMap(object):
                 cache.extend_device(eng.leg(r["stacked"][torch.from_numpy(np.nonzero(k)[0]).to(eng.device)].contiguous()))
         kept = np.nonzero(keep)[0]
         if len(kept) == 0:
-            raise OvnError("OverlapMap.from_mesh: none of the %d poses sees %g of its pixels: are they in the mesh's frame?"
-                           % (p.shape[0], min_valid_fraction))
+            raise OvnError("%s: none of the %d poses sees %g of its pixels: are they in %s frame?"
+                           % (what, p.shape[0], min_valid_fraction, whose))
         self = cls.__new__(cls)
         self.infer, self.engine = infer, eng
         self.mesh_built, self.kept, self.sensor_poses = True, kept, p[kept]

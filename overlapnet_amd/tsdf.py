@@ -4,6 +4,7 @@ level set as a `mesh.TriangleMesh` (ovn_tsdf_integrate / ovn_tsdf_triangles, csr
     vol = TsdfVolume(engine, lo, hi, voxel=0.2)
     vol.integrate_scans(points, offsets, poses)        # or vol.integrate(range_images, poses)
     mesh = vol.mesh()                                  # -> OverlapMap.from_mesh, mesh.to_ply, tools/localize.py --mesh
+    views = vol.render_scans(poses)                    # the volume itself seen from poses (ovn_tsdf_raycast)
 
 The volume is dense: (nz, ny, nx) float32 tsdf and weight, at most 2^31 - 1 samples.  Argument errors raise before a GPU is touched.
 """
@@ -45,6 +46,42 @@ def volume_shape(lo, hi, voxel: float) -> Tuple[int, int, int]:
         raise ValueError("a volume of %s m at voxel %g m has %.3g samples, over the limit of 2^31 - 1: a voxel of %.3g m fits"
                          % (ext.tolist(), voxel, float(np.prod(n)), fit))
     return int(n[0]), int(n[1]), int(n[2])
+
+
+MAX_RAY_SAMPLES = 1 << 20        # OVN_RAYCAST_MAX_SAMPLES
+
+
+def ray_samples(min_range: float, max_range: float, step: float) -> int:
+    """The number of samples k = 0, 1, .. with t_k = min_range + (float)k * step < max_range, every operation in float32 as the
+    kernel evaluates it (t_k does not decrease with k, so the count is the first k that fails)."""
+    mn, mx, st = np.float32(min_range), np.float32(max_range), np.float32(step)
+    inside = lambda k: bool(mn + np.float32(k) * st < mx)
+    if not inside(0):
+        return 0
+    hi = 1
+    while inside(hi):
+        hi *= 2
+        if hi > 4 * MAX_RAY_SAMPLES:
+            return hi
+    lo = hi // 2
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if inside(mid) else (lo, mid)
+    return hi
+
+
+def check_march(min_range: float, max_range: float, step: float) -> int:
+    """Raises ValueError for what ovn_tsdf_raycast refuses in its three march parameters; -> the sample count K."""
+    with np.errstate(over="ignore"):
+        v = [np.float32(float(x)) for x in (min_range, max_range, step)]
+    if not all(np.isfinite(x) and x > 0 for x in v):
+        raise ValueError("min_range, max_range and step must be finite numbers > 0 in float32, got %r, %r, %r" % (min_range, max_range, step))
+    if not v[0] < v[1]:
+        raise ValueError("min_range %r is not below max_range %r" % (min_range, max_range))
+    k = ray_samples(*v)
+    if k > MAX_RAY_SAMPLES:
+        raise ValueError("range %r .. %r in steps of %r is more than 2^20 samples per ray" % (min_range, max_range, step))
+    return k
 
 
 class TsdfVolume(object):
@@ -133,6 +170,35 @@ class TsdfVolume(object):
             self.engine.tsdf_integrate(self.tsdf, self.weight, self.origin, self.voxel, self.trunc, self.max_weight, r, poses[a:b],
                                        fov_up, fov_down, max_range)
         self.n_scans += n
+
+    def bricks(self, min_weight: float = 1.0, out=None):
+        """The byte mask of the 8 x 8 x 8 bricks that hold a sample with weight >= min_weight (`engine.tsdf_bricks`)."""
+        if np.isnan(float(min_weight)):
+            raise ValueError("min_weight is NaN")
+        return self.engine.tsdf_bricks(self.weight, min_weight, out=out)
+
+    def render_scans(self, poses, proj_h: int = 64, proj_w: int = 900, fov_up: float = 3.0, fov_down: float = -25.0,
+                     min_range: float = 0.5, max_range: float = 50.0, step: float = None, min_weight: float = 1.0, bricks=True,
+                     want=("range", "normal"), stacked_flags=None, stacked_out=None, out=None):
+        """The volume seen from `poses` ((n,4,4) sensor to world): `engine.tsdf_raycast` on this volume, `step` one voxel by default.
+        bricks=True builds the brick mask once for this call, False marches without one, a tensor is taken as the mask of
+        `bricks(min_weight)` (the caller's to keep current with the volume)."""
+        pshape = tuple(poses.shape) if hasattr(poses, "shape") else tuple(np.shape(poses))
+        if len(pshape) != 3 or pshape[1:] != (4, 4):
+            raise ValueError("poses must be (n,4,4), got %s" % (pshape,))
+        step = self.voxel if step is None else float(step)
+        check_march(min_range, max_range, step)
+        if np.isnan(float(min_weight)):
+            raise ValueError("min_weight is NaN")
+        if int(proj_h) < 1 or int(proj_w) < 1:
+            raise ValueError("proj_h and proj_w must be >= 1, got %r, %r" % (proj_h, proj_w))
+        mask = None
+        if bricks is True:
+            mask = self.bricks(min_weight)
+        elif bricks is not False and bricks is not None:
+            mask = bricks
+        return self.engine.tsdf_raycast(self.tsdf, self.weight, self.origin, self.voxel, poses, int(proj_h), int(proj_w), fov_up,
+                                        fov_down, min_range, max_range, step, min_weight, mask, want, stacked_flags, stacked_out, out)
 
     def triangles(self, min_weight: float = 1.0):
         """(T,3,3) float32 device tensor of the triangle soup, in contract order: one counting call, then one writing call."""

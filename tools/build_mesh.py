@@ -23,11 +23,10 @@ sys.path.insert(0, ROOT)
 
 
 def default_bounds(poses: np.ndarray, max_range: float, below: float, above: float):
-    """(lo, hi): the sensor positions' bounding box grown by max_range in x and y, by `below` / `above` metres in z."""
-    o = np.asarray(poses, np.float64)[:, :3, 3]
-    lo, hi = o.min(axis=0), o.max(axis=0)
-    return (np.array([lo[0] - max_range, lo[1] - max_range, lo[2] - below]),
-            np.array([hi[0] + max_range, hi[1] + max_range, hi[2] + above]))
+    """(lo, hi): the sensor positions' bounding box grown by max_range in x and y, by `below` / `above` metres in z
+    (`overlapnet_amd.odometry.bounds_from_poses`, which the odometry sizes its own volume with)."""
+    from overlapnet_amd.odometry import bounds_from_poses
+    return bounds_from_poses(poses, max_range, below, above)
 
 
 def main(argv=None):
