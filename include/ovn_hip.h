@@ -660,6 +660,78 @@ int ovn_tsdf_raycast(ovn_ctx* ctx, void* stream, const float* tsdf_dev, const fl
 int ovn_tsdf_bricks(ovn_ctx* ctx, void* stream, const float* weight_dev, int nx, int ny, int nz, double min_weight,
                     uint8_t* bricks_dev);
 
+/* SE(3) pose-graph optimization, the back end behind the loop closures of ovn_top_k + ovn_icp_register (csrc/pose_graph.hip;
+ * DESIGN.md section 32; restated in NumPy by tests/_pose_graph_ref.py).  Everything is fp64.  `stream` is the SECOND parameter of
+ * these calls, as for ovn_tsdf_raycast; tests/test_gpu_pose_graph_stream.py runs them on a non-default stream.  Every call only
+ * enqueues work and restores the caller's device; every buffer is the caller's, nothing comes from the context's scratch.
+ *   nodes     poses_dev (N,4,4) row-major, sensor to world; fixed_dev (N) bytes, non-zero = the node does not move
+ *   edge e    edge_ij_dev (E,2) int32 (i, j), i != j; meas_dev (E,4,4) Z_e measures T_i^-1 T_j (the pose of ovn_icp_register for
+ *             (current, reference) is the edge (current, reference, pose) as it stands; an odometry step is (k, k+1, T_k^-1 T_{k+1}));
+ *             info_dev (E,6,6) Omega_e, symmetric positive definite, in the twist order (v, omega) of ovn_icp_register
+ *   residual  r_e = Log(Z_e^-1 T_i^-1 T_j), translation part first.  With x = theta^2: the six coefficients sin t / t, (1 - cos t) / t^2,
+ *             (t - sin t) / t^3, (t^2 + 2 cos t - 2) / (2 t^4), (2 t - 3 sin t + t cos t) / (2 t^5), 1 / t^2 - (1 + cos t) / (2 t sin t)
+ *             are their five-term series in x for x < 1e-2 and the closed forms from there on (Exp, Log and the Jacobians alike)
+ *   update    T_i <- T_i Exp(delta_i) with the exact Exp; nothing is re-orthonormalized
+ *   Jacobians B_e = dr/d delta_j = J_r^-1(r_e) (closed form, Barfoot 7.85-7.86),  A_e = dr/d delta_i = -B_e Ad(T_j^-1 T_i)
+ *   cost      s_e = sqrt(r' Omega r), cost = sum rho(s_e), rho = s^2 / 2 for s <= huber, else huber (s - huber / 2); huber = +inf is
+ *             least squares; weight w_e = 1 or huber / s_e
+ *   H = sum w J' Omega J, g = sum w J' Omega r; rows and columns of fixed nodes are removed (their delta is 0)
+ * An edge with a non-finite pose, measurement or information entry, or with an index outside [0, N) or i == j, gets weight 0 and zero
+ * blocks and is counted in the record.  No atomics anywhere: a node's sums run over its incidence list node_ptr_dev (N + 1) /
+ * node_edge_dev (2 E) (CSR, a node's edges in ascending edge index) in list order, dot products and maxima are fixed trees, the scans
+ * are three launches (block scans, one workgroup over the block totals, add): the same arguments give the same bits.
+ *
+ * record_dev: OVN_POSE_GRAPH_RECORD doubles.  [0] cost  [1] edges with weight 0 for a non-finite input  [2] 6 x 6 blocks whose
+ * Cholesky met a non-positive pivot  [3] |g|_inf  (ovn_pose_graph_linearize; [2] and [3] are 0 from a cost-only call)
+ * [4] PCG iterations done  [5] |r|_M / |r_0|_M  [6] converged  [7] breakdown  [8] r'z  [9] r_0'z_0  [10] alpha  [11] beta
+ * (ovn_pose_graph_solve)  [12] |delta|_inf of the free nodes (ovn_pose_graph_retract).
+ *
+ * ovn_pose_graph_workspace_bytes: the size of ws_dev for N nodes and E edges (0 for N or E outside the limits).
+ *
+ * ovn_pose_graph_linearize: res_dev (E,6) r, chi_dev (E) s, weight_dev (E) w, and -- when jac_dev is given -- jac_dev (E,2,6,6) A | B,
+ * blocks_dev (E,3,6,6) A'wOmega A | A'wOmega B | B'wOmega B, grad_dev (N,6) g, diag_dev (N,6,6) the diagonal blocks of H, dinv_dev
+ * (N,6,6) their inverses by Cholesky (0 for a fixed node and for a block that broke down), and chain_dev (NULL, or (N-1,2,6,6)): the
+ * chain preconditioner's G_m | Ad(T_{m+1}^-1) of edge m = (m, m+1), which the CALLER promises are edges 0 .. N-2 with node 0 the only
+ * fixed node.  With jac_dev, blocks_dev, grad_dev, diag_dev, dinv_dev and chain_dev all NULL it is the cost-only evaluation of a
+ * trial step.  E == 0: cost 0, no buffer but the record is touched.
+ *
+ * ovn_pose_graph_solve: enqueues `iterations` iterations of preconditioned conjugate gradients on (H + lambda blockdiag(H)) delta
+ * = -g from delta = 0 (first_iteration == 0 starts the solve; a later chunk passes the number of iterations enqueued so far and
+ * continues from ws_dev).  preconditioner: OVN_POSE_GRAPH_JACOBI = dinv_dev / (1 + lambda); OVN_POSE_GRAPH_CHAIN = the inverse of the
+ * Hessian of the N-1 odometry edges alone, undamped, by two transforms per node around a prefix and a suffix sum (chain_dev).  The
+ * record's `converged` is set when |r|_M / |r_0|_M <= rtol (or g == 0), `breakdown` when the linearization's record counts a failed
+ * Cholesky or p'(H + lambda D)p is not positive and finite; from then on every remaining launch returns at its first instruction, so
+ * delta_dev holds the last good iterate (untouched by a solve that breaks down at its start) and never a non-finite value.  The call
+ * never waits on the host.  E == 0: converged after 0 iterations, delta_dev untouched.
+ *
+ * ovn_pose_graph_precondition: out_dev (N,6) = M^-1 in_dev (N,6) alone (a validation entry; with the chain, row 0 of out_dev is 0).
+ *
+ * ovn_pose_graph_retract: out_dev (N,4,4) = T_i Exp(delta_i) (a fixed node is copied), record [12].  out_dev must not be poses_dev.
+ *
+ * OVN_ERR_ARG, before any launch: a NULL ctx, record or (for E > 0) buffer, N < 1, E < 0, N > OVN_POSE_GRAPH_MAX_NODES, E >
+ * OVN_POSE_GRAPH_MAX_EDGES, huber <= 0 or NaN, lambda or rtol negative or non-finite, an unknown preconditioner, the chain without
+ * chain_dev or with E < N - 1, first_iteration < 0, iterations outside 0 .. OVN_POSE_GRAPH_MAX_CHUNK, Jacobian outputs given in part. */
+#define OVN_POSE_GRAPH_MAX_NODES (1 << 20)
+#define OVN_POSE_GRAPH_MAX_EDGES (1 << 22)
+#define OVN_POSE_GRAPH_MAX_CHUNK 4096
+#define OVN_POSE_GRAPH_RECORD 16
+#define OVN_POSE_GRAPH_JACOBI 0
+#define OVN_POSE_GRAPH_CHAIN 1
+int64_t ovn_pose_graph_workspace_bytes(int64_t n_nodes, int64_t n_edges);
+int ovn_pose_graph_linearize(ovn_ctx* ctx, void* stream, const double* poses_dev, const uint8_t* fixed_dev, int n_nodes,
+                             const int32_t* edge_ij_dev, const double* meas_dev, const double* info_dev, int n_edges,
+                             const int32_t* node_ptr_dev, const int32_t* node_edge_dev, double huber, double* res_dev, double* chi_dev,
+                             double* weight_dev, double* jac_dev, double* blocks_dev, double* grad_dev, double* diag_dev,
+                             double* dinv_dev, double* chain_dev, double* ws_dev, double* record_dev);
+int ovn_pose_graph_solve(ovn_ctx* ctx, void* stream, const uint8_t* fixed_dev, int n_nodes, const int32_t* edge_ij_dev, int n_edges,
+                         const int32_t* node_ptr_dev, const int32_t* node_edge_dev, const double* blocks_dev, const double* grad_dev,
+                         const double* diag_dev, const double* dinv_dev, const double* chain_dev, int preconditioner, double lambda,
+                         double rtol, int first_iteration, int iterations, double* delta_dev, double* ws_dev, double* record_dev);
+int ovn_pose_graph_precondition(ovn_ctx* ctx, void* stream, int n_nodes, int preconditioner, double lambda, const double* dinv_dev,
+                                const double* chain_dev, const double* in_dev, double* out_dev, double* ws_dev);
+int ovn_pose_graph_retract(ovn_ctx* ctx, void* stream, const double* poses_dev, const uint8_t* fixed_dev, const double* delta_dev,
+                           int n_nodes, double* out_dev, double* ws_dev, double* record_dev);
+
 /* The per-point part of range_projection alone (src/utils/utils.py:75-104), exactly as ovn_project's scatter kernel evaluates it:
  * for each of n float32 points (x,y,z,*) yaw = -np.arctan2(y, x), pitch = np.arcsin(z / depth) with NumPy's float32 results
  * (csrc/svml_f32.h) and the pixel py * proj_w + px the point falls into (-1 for a point the range filter drops).  Outputs may

@@ -82,6 +82,12 @@ SIGNATURES = {
                                    C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp,
                                    C.c_int, C.c_int]),
     "ovn_tsdf_bricks": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp]),
+    "ovn_pose_graph_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "ovn_pose_graph_linearize": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_double] + [_vp] * 11),
+    "ovn_pose_graph_solve": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int] + [_vp] * 7 + [C.c_int, C.c_double, C.c_double, C.c_int,
+                                       C.c_int, _vp, _vp, _vp]),
+    "ovn_pose_graph_precondition": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "ovn_pose_graph_retract": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "ovn_projection_angles": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp]),
     "ovn_gt_range_images": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double,
                                       C.c_double, _vp, _vp]),

@@ -1,0 +1,1119 @@
+// SE(3) pose-graph optimization in fp64 (ovn_pose_graph_*; include/ovn_hip.h): linearization of the edges,
+// block-sparse preconditioned conjugate gradients with a block-Jacobi or an odometry-chain preconditioner, and the retraction.
+// No atomics: a node sums over its incidence list in list order, every dot product and maximum is a fixed tree (256 lanes, halving),
+// the scans are Hillis-Steele inside a workgroup and three launches across workgroups.  No workgroup waits on another inside a launch.
+// Built without FMA contraction: tests/_pose_graph_ref.py states the same operations one by one.
+#include "ovn_internal.h"
+
+namespace {
+
+constexpr int PG_B = 256;              // threads per workgroup, elements per scan block
+constexpr double PG_SERIES_X = 1e-2;   // theta^2 below which the coefficient series are used
+
+// record slots (OVN_POSE_GRAPH_RECORD doubles)
+enum { R_COST = 0, R_BAD = 1, R_CHOL = 2, R_GMAX = 3, R_ITER = 4, R_REL = 5, R_CONV = 6, R_BREAK = 7, R_RZ = 8, R_RZ0 = 9, R_ALPHA = 10,
+       R_BETA = 11, R_DMAX = 12 };
+
+struct PgWs {   // the caller's workspace, in doubles
+  double *eg, *part_e, *part_n, *part_c, *r, *z, *q, *p[2], *sa, *sb, *bsum;
+  size_t total;
+  PgWs(double* base, int64_t N, int64_t E) {
+    const int64_t nbn = (N + PG_B - 1) / PG_B, nbe = (E + PG_B - 1) / PG_B;
+    size_t o = 0;
+    auto take = [&](size_t n) { double* q_ = base ? base + o : nullptr; o += (n + 1) & ~(size_t)1; return q_; };
+    part_n = take(2 * nbn);   // the node-sized parts first: their places do not depend on E
+    part_c = take(nbn);
+    r = take(6 * N);
+    z = take(6 * N);
+    q = take(6 * N);
+    p[0] = take(6 * N);
+    p[1] = take(6 * N);
+    sa = take(6 * N);
+    sb = take(6 * N);
+    bsum = take(12 * nbn);
+    part_e = take(2 * nbe);
+    eg = take(12 * E);
+    total = o;
+  }
+};
+
+// ---- small fixed-size algebra, every sum in index order ---------------------------------------------------------------------------------
+__device__ __forceinline__ void m3_mul(const double* a, const double* b, double* c) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) c[i * 3 + j] = (a[i * 3] * b[j] + a[i * 3 + 1] * b[3 + j]) + a[i * 3 + 2] * b[6 + j];
+}
+__device__ __forceinline__ void m3_tmul(const double* a, const double* b, double* c) {   // a' b
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) c[i * 3 + j] = (a[i] * b[j] + a[3 + i] * b[3 + j]) + a[6 + i] * b[6 + j];
+}
+__device__ __forceinline__ void m3_vec(const double* a, const double* v, double* o) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) o[i] = (a[i * 3] * v[0] + a[i * 3 + 1] * v[1]) + a[i * 3 + 2] * v[2];
+}
+__device__ __forceinline__ void m3_tvec(const double* a, const double* v, double* o) {   // a' v
+#pragma unroll
+  for (int i = 0; i < 3; ++i) o[i] = (a[i] * v[0] + a[3 + i] * v[1]) + a[6 + i] * v[2];
+}
+__device__ __forceinline__ void m3_hat(const double* w, double* h) {
+  h[0] = 0.0; h[1] = -w[2]; h[2] = w[1];
+  h[3] = w[2]; h[4] = 0.0; h[5] = -w[0];
+  h[6] = -w[1]; h[7] = w[0]; h[8] = 0.0;
+}
+__device__ __forceinline__ void m6_mul(const double* a, const double* b, double* c) {
+#pragma unroll
+  for (int i = 0; i < 6; ++i)
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      double s = a[i * 6] * b[j];
+#pragma unroll
+      for (int k = 1; k < 6; ++k) s = s + a[i * 6 + k] * b[k * 6 + j];
+      c[i * 6 + j] = s;
+    }
+}
+__device__ __forceinline__ void m6_tmul(const double* a, const double* b, double* c) {   // a' b
+#pragma unroll
+  for (int i = 0; i < 6; ++i)
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      double s = a[i] * b[j];
+#pragma unroll
+      for (int k = 1; k < 6; ++k) s = s + a[k * 6 + i] * b[k * 6 + j];
+      c[i * 6 + j] = s;
+    }
+}
+__device__ __forceinline__ void m6_mult(const double* a, const double* b, double* c) {   // a b'
+#pragma unroll
+  for (int i = 0; i < 6; ++i)
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      double s = a[i * 6] * b[j * 6];
+#pragma unroll
+      for (int k = 1; k < 6; ++k) s = s + a[i * 6 + k] * b[j * 6 + k];
+      c[i * 6 + j] = s;
+    }
+}
+__device__ __forceinline__ void m6_vec(const double* a, const double* v, double* o) {
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    double s = a[i * 6] * v[0];
+#pragma unroll
+    for (int k = 1; k < 6; ++k) s = s + a[i * 6 + k] * v[k];
+    o[i] = s;
+  }
+}
+__device__ __forceinline__ void m6_tvec(const double* a, const double* v, double* o) {   // a' v
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    double s = a[i] * v[0];
+#pragma unroll
+    for (int k = 1; k < 6; ++k) s = s + a[k * 6 + i] * v[k];
+    o[i] = s;
+  }
+}
+__device__ __forceinline__ double v6_dot(const double* a, const double* b) {
+  double s = a[0] * b[0];
+#pragma unroll
+  for (int k = 1; k < 6; ++k) s = s + a[k] * b[k];
+  return s;
+}
+__device__ __forceinline__ void ld6(const double* p, double* v) {
+#pragma unroll
+  for (int k = 0; k < 6; ++k) v[k] = p[k];
+}
+__device__ __forceinline__ void st6(double* p, const double* v) {
+#pragma unroll
+  for (int k = 0; k < 6; ++k) p[k] = v[k];
+}
+__device__ __forceinline__ void ld36(const double* p, double* v) {
+#pragma unroll
+  for (int k = 0; k < 36; ++k) v[k] = p[k];
+}
+__device__ __forceinline__ void st36(double* p, const double* v) {
+#pragma unroll
+  for (int k = 0; k < 36; ++k) p[k] = v[k];
+}
+
+// a = sin t / t, b = (1 - cos t) / t^2, c1 = (t - sin t) / t^3, c2 = (t^2 + 2 cos t - 2) / (2 t^4),
+// c3 = (2 t - 3 sin t + t cos t) / (2 t^5), e = 1 / t^2 - (1 + cos t) / (2 t sin t); x = t^2
+struct PgCoef {
+  double a, b, c1, c2, c3, e;
+};
+__device__ __forceinline__ PgCoef pg_coeffs(double x) {
+  PgCoef c;
+  if (x < PG_SERIES_X) {
+    c.a = 1.0 + x * (-1.0 / 6 + x * (1.0 / 120 + x * (-1.0 / 5040 + x * (1.0 / 362880))));
+    c.b = 0.5 + x * (-1.0 / 24 + x * (1.0 / 720 + x * (-1.0 / 40320 + x * (1.0 / 3628800))));
+    c.c1 = 1.0 / 6 + x * (-1.0 / 120 + x * (1.0 / 5040 + x * (-1.0 / 362880 + x * (1.0 / 39916800))));
+    c.c2 = 1.0 / 24 + x * (-1.0 / 720 + x * (1.0 / 40320 + x * (-1.0 / 3628800 + x * (1.0 / 479001600))));
+    c.c3 = 1.0 / 120 + x * (-2.0 / 5040 + x * (3.0 / 362880 + x * (-4.0 / 39916800 + x * (5.0 / 6227020800.0))));
+    c.e = 1.0 / 12 + x * (1.0 / 720 + x * (1.0 / 30240 + x * (1.0 / 1209600 + x * (1.0 / 47900160))));
+    return c;
+  }
+  const double t = sqrt(x), s = sin(t), cs = cos(t);
+  c.a = s / t;
+  c.b = (1.0 - cs) / x;
+  c.c1 = (t - s) / (x * t);
+  c.c2 = ((x + 2.0 * cs) - 2.0) / ((2.0 * x) * x);
+  c.c3 = ((2.0 * t - 3.0 * s) + t * cs) / (((2.0 * x) * x) * t);
+  c.e = 1.0 / x - (1.0 + cs) / ((2.0 * t) * s);
+  return c;
+}
+
+// a pose as rotation (row-major 3 x 3) and translation, from the top three rows of a (4,4) matrix
+__device__ __forceinline__ void pg_load_pose(const double* T, double* R, double* t) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    R[i * 3] = T[i * 4]; R[i * 3 + 1] = T[i * 4 + 1]; R[i * 3 + 2] = T[i * 4 + 2];
+    t[i] = T[i * 4 + 3];
+  }
+}
+__device__ __forceinline__ bool pg_finite12(const double* R, const double* t) {
+  double s = 0.0;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) s += R[k] * 0.0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) s += t[k] * 0.0;
+  return s == 0.0;   // NaN and Inf give NaN
+}
+// A^-1 B: R = Ra' Rb, t = Ra' (tb - ta)
+__device__ __forceinline__ void pg_rel(const double* Ra, const double* ta, const double* Rb, const double* tb, double* R, double* t) {
+  m3_tmul(Ra, Rb, R);
+  const double d[3] = {tb[0] - ta[0], tb[1] - ta[1], tb[2] - ta[2]};
+  m3_tvec(Ra, d, t);
+}
+// Log of (R, t): (v, omega)
+__device__ __forceinline__ void pg_log(const double* R, const double* t, double* xi) {
+  const double ax[3] = {0.5 * (R[7] - R[5]), 0.5 * (R[2] - R[6]), 0.5 * (R[3] - R[1])};
+  const double sn = sqrt((ax[0] * ax[0] + ax[1] * ax[1]) + ax[2] * ax[2]);
+  const double cs = 0.5 * (((R[0] + R[4]) + R[8]) - 1.0);
+  const double th = atan2(sn, cs);
+  const double x = th * th;
+  const double k = x < PG_SERIES_X ? 1.0 / pg_coeffs(x).a : th / sn;
+  const double w[3] = {k * ax[0], k * ax[1], k * ax[2]};
+  const double x2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];
+  const double e = pg_coeffs(x2).e;
+  double W[9], WW[9], V[9];
+  m3_hat(w, W);
+  m3_mul(W, W, WW);
+#pragma unroll
+  for (int q = 0; q < 9; ++q) V[q] = (((q % 4 == 0) ? 1.0 : 0.0) - 0.5 * W[q]) + e * WW[q];
+  m3_vec(V, t, xi);
+  xi[3] = w[0]; xi[4] = w[1]; xi[5] = w[2];
+}
+// Exp of (v, omega): rotation and translation
+__device__ __forceinline__ void pg_exp(const double* xi, double* R, double* t) {
+  const double* w = xi + 3;
+  const double x = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];
+  const PgCoef c = pg_coeffs(x);
+  double W[9], WW[9], V[9];
+  m3_hat(w, W);
+  m3_mul(W, W, WW);
+#pragma unroll
+  for (int q = 0; q < 9; ++q) {
+    const double id = (q % 4 == 0) ? 1.0 : 0.0;
+    R[q] = (id + c.a * W[q]) + c.b * WW[q];
+    V[q] = (id + c.b * W[q]) + c.c1 * WW[q];
+  }
+  m3_vec(V, xi, t);
+}
+// Ad(R, t) = [[R, t^ R], [0, R]]
+__device__ __forceinline__ void pg_adjoint(const double* R, const double* t, double* Ad) {
+  double H[9], HR[9];
+  m3_hat(t, H);
+  m3_mul(H, R, HR);
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      Ad[i * 6 + j] = R[i * 3 + j];
+      Ad[i * 6 + 3 + j] = HR[i * 3 + j];
+      Ad[(i + 3) * 6 + j] = 0.0;
+      Ad[(i + 3) * 6 + 3 + j] = R[i * 3 + j];
+    }
+}
+// inverse left Jacobian of SE(3) at xi = (rho, phi), closed form (Barfoot, State Estimation for Robotics, 7.85-7.86)
+__device__ __forceinline__ void pg_jl_inv(const double* xi, double* J) {
+  const double* rho = xi;
+  const double* phi = xi + 3;
+  const double x = (phi[0] * phi[0] + phi[1] * phi[1]) + phi[2] * phi[2];
+  const PgCoef c = pg_coeffs(x);
+  double P[9], F[9], FP[9], PF[9], FF[9], FPF[9], FFP[9], PFF[9], FPFF[9], FFPF[9], Q[9], Ji[9], T1[9], T2[9];
+  m3_hat(rho, P);
+  m3_hat(phi, F);
+  m3_mul(F, P, FP);
+  m3_mul(P, F, PF);
+  m3_mul(F, F, FF);
+  m3_mul(FP, F, FPF);
+  m3_mul(F, FP, FFP);
+  m3_mul(PF, F, PFF);
+  m3_mul(FPF, F, FPFF);
+  m3_mul(F, FPF, FFPF);
+#pragma unroll
+  for (int q = 0; q < 9; ++q) {
+    Q[q] = ((0.5 * P[q] + c.c1 * ((FP[q] + PF[q]) + FPF[q])) + c.c2 * ((FFP[q] + PFF[q]) - 3.0 * FPF[q])) + c.c3 * (FPFF[q] + FFPF[q]);
+    Ji[q] = (((q % 4 == 0) ? 1.0 : 0.0) - 0.5 * F[q]) + c.e * FF[q];
+  }
+  m3_mul(Ji, Q, T1);
+  m3_mul(T1, Ji, T2);
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      J[i * 6 + j] = Ji[i * 3 + j];
+      J[i * 6 + 3 + j] = -T2[i * 3 + j];
+      J[(i + 3) * 6 + j] = 0.0;
+      J[(i + 3) * 6 + 3 + j] = Ji[i * 3 + j];
+    }
+}
+// inverse of a 6 x 6 SPD block by Cholesky; false (and `inv` untouched) on a non-positive or non-finite pivot
+__device__ __forceinline__ bool pg_chol_inv(const double* D, double* inv) {
+  double L[36], Li[36];
+#pragma unroll
+  for (int q = 0; q < 36; ++q) L[q] = Li[q] = 0.0;
+  bool ok = true;
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    double d = D[c * 6 + c];
+#pragma unroll
+    for (int t = 0; t < c; ++t) d = d - L[c * 6 + t] * L[c * 6 + t];
+    if (!(d > 0.0) || !(d * 0.0 == 0.0)) ok = false;
+    const double l = sqrt(ok ? d : 1.0);
+    L[c * 6 + c] = l;
+#pragma unroll
+    for (int r = c + 1; r < 6; ++r) {
+      double v = D[r * 6 + c];
+#pragma unroll
+      for (int t = 0; t < c; ++t) v = v - L[r * 6 + t] * L[c * 6 + t];
+      L[r * 6 + c] = v / l;
+    }
+  }
+  if (!ok) return false;
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    Li[c * 6 + c] = 1.0 / L[c * 6 + c];
+#pragma unroll
+    for (int r = c + 1; r < 6; ++r) {
+      double v = 0.0;
+#pragma unroll
+      for (int t = c; t < r; ++t) v = v - L[r * 6 + t] * Li[t * 6 + c];
+      Li[r * 6 + c] = v / L[r * 6 + r];
+    }
+  }
+  double out[36];
+  m6_tmul(Li, Li, out);
+  bool fin = true;
+#pragma unroll
+  for (int q = 0; q < 36; ++q) fin = fin && (out[q] * 0.0 == 0.0);
+  if (!fin) return false;
+#pragma unroll
+  for (int q = 0; q < 36; ++q) inv[q] = out[q];
+  return true;
+}
+
+// sum / maximum of one value per thread over the workgroup by a halving tree; the result is valid on thread 0
+__device__ __forceinline__ double pg_wg_sum(double v, double* sh) {
+  __syncthreads();
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  for (int h = PG_B / 2; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) sh[threadIdx.x] = sh[threadIdx.x] + sh[threadIdx.x + h];
+    __syncthreads();
+  }
+  return sh[0];
+}
+__device__ __forceinline__ double pg_wg_max(double v, double* sh) {
+  __syncthreads();
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  for (int h = PG_B / 2; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) sh[threadIdx.x] = fmax(sh[threadIdx.x], sh[threadIdx.x + h]);
+    __syncthreads();
+  }
+  return sh[0];
+}
+// the same over n per-workgroup partials (stride `stride` doubles) inside ONE workgroup: lane t takes partials t, t + 256, ... in order
+__device__ __forceinline__ double pg_partial_sum(const double* part, int n, int stride, double* sh) {
+  double v = 0.0;
+  for (int k = threadIdx.x; k < n; k += PG_B) v = v + part[(size_t)k * stride];
+  return pg_wg_sum(v, sh);
+}
+__device__ __forceinline__ double pg_partial_max(const double* part, int n, int stride, double* sh) {
+  double v = 0.0;
+  for (int k = threadIdx.x; k < n; k += PG_B) v = fmax(v, part[(size_t)k * stride]);
+  return pg_wg_max(v, sh);
+}
+__device__ __forceinline__ bool pg_stopped(const double* rec) { return rec != nullptr && (rec[R_CONV] != 0.0 || rec[R_BREAK] != 0.0); }
+
+// ---- linearization ------------------------------------------------------------------------------------------------------------------------
+// one edge per thread: r, s, w, rho; with JAC also A, B, the three Hessian blocks and the two gradient terms
+template <bool JAC>
+__global__ __launch_bounds__(PG_B) void pg_edge_kernel(const double* __restrict__ poses, int N, const int32_t* __restrict__ ij,
+                                                       const double* __restrict__ meas, const double* __restrict__ info, int E,
+                                                       double huber, double* __restrict__ res, double* __restrict__ chi,
+                                                       double* __restrict__ weight, double* __restrict__ jac,
+                                                       double* __restrict__ blocks, double* __restrict__ eg, double* __restrict__ part) {
+  __shared__ double sh[PG_B];
+  const int e = blockIdx.x * PG_B + threadIdx.x;
+  double rho = 0.0, bad = 0.0;
+  if (e < E) {
+    const int i = ij[2 * e], j = ij[2 * e + 1];
+    double r[6] = {0, 0, 0, 0, 0, 0}, s = 0.0, w = 0.0;
+    double Om[36], A[36], B[36];
+    bool ok = i >= 0 && i < N && j >= 0 && j < N && i != j;
+    if (ok) {
+      double Ri[9], ti[3], Rj[9], tj[3], Rz[9], tz[3], Rij[9], tij[3], Rd[9], td[3];
+      pg_load_pose(poses + (size_t)i * 16, Ri, ti);
+      pg_load_pose(poses + (size_t)j * 16, Rj, tj);
+      pg_load_pose(meas + (size_t)e * 16, Rz, tz);
+      ld36(info + (size_t)e * 36, Om);
+      double f = 0.0;
+#pragma unroll
+      for (int q = 0; q < 36; ++q) f += Om[q] * 0.0;
+      ok = pg_finite12(Ri, ti) && pg_finite12(Rj, tj) && pg_finite12(Rz, tz) && f == 0.0;
+      if (ok) {
+        pg_rel(Ri, ti, Rj, tj, Rij, tij);
+        pg_rel(Rz, tz, Rij, tij, Rd, td);
+        pg_log(Rd, td, r);
+        ok = v6_dot(r, r) * 0.0 == 0.0;
+      }
+      if (ok) {
+        double Or[6];
+        m6_vec(Om, r, Or);
+        const double s2 = v6_dot(r, Or);
+        s = sqrt(s2 > 0.0 ? s2 : 0.0);
+        if (s <= huber) {
+          rho = (0.5 * s) * s;
+          w = 1.0;
+        } else {
+          rho = huber * (s - 0.5 * huber);
+          w = huber / s;
+        }
+        if (JAC) {
+          const double nr[6] = {-r[0], -r[1], -r[2], -r[3], -r[4], -r[5]};
+          pg_jl_inv(nr, B);                      // J_r^-1(r) = J_l^-1(-r)
+          double Rji[9], tji[3], Ad[36];
+#pragma unroll
+          for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int b = 0; b < 3; ++b) Rji[a * 3 + b] = Rij[b * 3 + a];
+          m3_tvec(Rij, tij, tji);
+#pragma unroll
+          for (int a = 0; a < 3; ++a) tji[a] = -tji[a];
+          pg_adjoint(Rji, tji, Ad);
+          m6_mul(B, Ad, A);
+#pragma unroll
+          for (int q = 0; q < 36; ++q) A[q] = -A[q];
+          double g[6], t6[6];
+          m6_tvec(A, Or, t6);
+#pragma unroll
+          for (int q = 0; q < 6; ++q) g[q] = w * t6[q];
+          st6(eg + (size_t)e * 12, g);
+          m6_tvec(B, Or, t6);
+#pragma unroll
+          for (int q = 0; q < 6; ++q) g[q] = w * t6[q];
+          st6(eg + (size_t)e * 12 + 6, g);
+        }
+      }
+    }
+    if (!ok) {
+      bad = 1.0;
+      rho = 0.0;
+      s = 0.0;
+      w = 0.0;
+#pragma unroll
+      for (int q = 0; q < 6; ++q) r[q] = 0.0;
+    }
+    st6(res + (size_t)e * 6, r);
+    chi[e] = s;
+    weight[e] = w;
+    if (JAC) {
+      double* jb = jac + (size_t)e * 72;
+      double* hb = blocks + (size_t)e * 108;
+      if (ok) {
+        double W6[36], H[36];
+        st36(jb, A);
+        st36(jb + 36, B);
+        m6_mul(Om, B, W6);
+#pragma unroll
+        for (int q = 0; q < 36; ++q) W6[q] = w * W6[q];
+        m6_tmul(B, W6, H);
+        st36(hb + 72, H);
+        m6_tmul(A, W6, H);
+        st36(hb + 36, H);
+        m6_mul(Om, A, W6);
+#pragma unroll
+        for (int q = 0; q < 36; ++q) W6[q] = w * W6[q];
+        m6_tmul(A, W6, H);
+        st36(hb, H);
+      } else {
+        for (int q = 0; q < 72; ++q) jb[q] = 0.0;
+        for (int q = 0; q < 108; ++q) hb[q] = 0.0;
+        for (int q = 0; q < 12; ++q) eg[(size_t)e * 12 + q] = 0.0;
+      }
+    }
+  }
+  const double c = pg_wg_sum(rho, sh);
+  const double nb = pg_wg_sum(bad, sh);
+  if (threadIdx.x == 0) {
+    part[2 * blockIdx.x] = c;
+    part[2 * blockIdx.x + 1] = nb;
+  }
+}
+
+// one node per thread: gradient, diagonal block and its inverse over the incidence list, in list order
+__global__ __launch_bounds__(PG_B) void pg_node_kernel(const uint8_t* __restrict__ fixed, int N, const int32_t* __restrict__ ij, int E,
+                                                       const int32_t* __restrict__ ptr, const int32_t* __restrict__ lst,
+                                                       const double* __restrict__ blocks, const double* __restrict__ eg,
+                                                       double* __restrict__ grad, double* __restrict__ diag, double* __restrict__ dinv,
+                                                       double* __restrict__ part) {
+  __shared__ double sh[PG_B];
+  const int v = blockIdx.x * PG_B + threadIdx.x;
+  double fail = 0.0, gmax = 0.0;
+  if (v < N) {
+    double g[6], D[36], Di[36];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) g[q] = 0.0;
+#pragma unroll
+    for (int q = 0; q < 36; ++q) D[q] = Di[q] = 0.0;
+    if (!fixed[v]) {
+      int b = ptr[v], en = ptr[v + 1];
+      b = b < 0 ? 0 : b;
+      en = en > 2 * E ? 2 * E : en;
+      bool first = true;
+      for (int k = b; k < en; ++k) {
+        const int e = lst[k];
+        if (e < 0 || e >= E) continue;
+        const int side = ij[2 * e] == v ? 0 : 1;
+        const double* gp = eg + (size_t)e * 12 + 6 * side;
+        const double* hp = blocks + (size_t)e * 108 + 72 * side;
+        if (first) {
+#pragma unroll
+          for (int q = 0; q < 6; ++q) g[q] = gp[q];
+#pragma unroll
+          for (int q = 0; q < 36; ++q) D[q] = hp[q];
+          first = false;
+        } else {
+#pragma unroll
+          for (int q = 0; q < 6; ++q) g[q] = g[q] + gp[q];
+#pragma unroll
+          for (int q = 0; q < 36; ++q) D[q] = D[q] + hp[q];
+        }
+      }
+      if (!pg_chol_inv(D, Di)) fail = 1.0;
+#pragma unroll
+      for (int q = 0; q < 6; ++q) gmax = fmax(gmax, fabs(g[q]));
+    }
+    st6(grad + (size_t)v * 6, g);
+    st36(diag + (size_t)v * 36, D);
+    st36(dinv + (size_t)v * 36, Di);
+  }
+  const double f = pg_wg_sum(fail, sh);
+  const double m = pg_wg_max(gmax, sh);
+  if (threadIdx.x == 0) {
+    part[2 * blockIdx.x] = f;
+    part[2 * blockIdx.x + 1] = m;
+  }
+}
+
+// one chain edge m = (m, m + 1) per thread: G_m = P (w Omega)^-1 P' with P = Ad(T_{m+1}) B_m^-1, and N_m = Ad(T_{m+1}^-1)
+__global__ __launch_bounds__(PG_B) void pg_chain_kernel(const double* __restrict__ poses, int N, const double* __restrict__ info,
+                                                        const double* __restrict__ weight, const double* __restrict__ jac,
+                                                        double* __restrict__ chain, double* __restrict__ part) {
+  __shared__ double sh[PG_B];
+  const int m = blockIdx.x * PG_B + threadIdx.x;
+  double fail = 0.0;
+  if (m < N - 1) {
+    double G[36], Nm[36];
+#pragma unroll
+    for (int q = 0; q < 36; ++q) G[q] = Nm[q] = 0.0;
+    double R[9], t[3];
+    pg_load_pose(poses + (size_t)(m + 1) * 16, R, t);
+    const double* B = jac + (size_t)m * 72 + 36;
+    double J[9], K[9], Ji[9];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = 0; b < 3; ++b) {
+        J[a * 3 + b] = B[a * 6 + b];
+        K[a * 3 + b] = B[a * 6 + 3 + b];
+      }
+    const double c00 = J[4] * J[8] - J[5] * J[7], c01 = J[5] * J[6] - J[3] * J[8], c02 = J[3] * J[7] - J[4] * J[6];
+    const double det = (J[0] * c00 + J[1] * c01) + J[2] * c02;
+    const double id = 1.0 / det;
+    Ji[0] = c00 * id; Ji[1] = (J[2] * J[7] - J[1] * J[8]) * id; Ji[2] = (J[1] * J[5] - J[2] * J[4]) * id;
+    Ji[3] = c01 * id; Ji[4] = (J[0] * J[8] - J[2] * J[6]) * id; Ji[5] = (J[2] * J[3] - J[0] * J[5]) * id;
+    Ji[6] = c02 * id; Ji[7] = (J[1] * J[6] - J[0] * J[7]) * id; Ji[8] = (J[0] * J[4] - J[1] * J[3]) * id;
+    double T1[9], T2[9], Binv[36], Ad[36], P[36], Wm[36], Wi[36], PW[36];
+    m3_mul(Ji, K, T1);
+    m3_mul(T1, Ji, T2);
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = 0; b < 3; ++b) {
+        Binv[a * 6 + b] = Ji[a * 3 + b];
+        Binv[a * 6 + 3 + b] = -T2[a * 3 + b];
+        Binv[(a + 3) * 6 + b] = 0.0;
+        Binv[(a + 3) * 6 + 3 + b] = Ji[a * 3 + b];
+      }
+    pg_adjoint(R, t, Ad);
+    m6_mul(Ad, Binv, P);
+    const double w = weight[m];
+#pragma unroll
+    for (int q = 0; q < 36; ++q) Wm[q] = w * info[(size_t)m * 36 + q];
+    bool ok = pg_chol_inv(Wm, Wi);
+    if (ok) {
+      m6_mul(P, Wi, PW);
+      m6_mult(PW, P, G);
+      double Rt[9], tt[3];
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) Rt[a * 3 + b] = R[b * 3 + a];
+      m3_tvec(R, t, tt);
+#pragma unroll
+      for (int a = 0; a < 3; ++a) tt[a] = -tt[a];
+      pg_adjoint(Rt, tt, Nm);
+      double f = 0.0;
+#pragma unroll
+      for (int q = 0; q < 36; ++q) f += (G[q] + Nm[q]) * 0.0;
+      ok = f == 0.0;
+    }
+    if (!ok) {
+      fail = 1.0;
+#pragma unroll
+      for (int q = 0; q < 36; ++q) G[q] = Nm[q] = 0.0;
+    }
+    st36(chain + (size_t)m * 72, G);
+    st36(chain + (size_t)m * 72 + 36, Nm);
+  }
+  const double f = pg_wg_sum(fail, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = f;
+}
+
+// ONE workgroup: the linearization's slots of the record
+__global__ __launch_bounds__(PG_B) void pg_lin_record_kernel(const double* part_e, int nbe, const double* part_n, int nbn,
+                                                             const double* part_c, int nbc, double* rec) {
+  __shared__ double sh[PG_B];
+  const double cost = pg_partial_sum(part_e, nbe, 2, sh);
+  const double bad = pg_partial_sum(part_e + 1, nbe, 2, sh);
+  double fail = 0.0, gmax = 0.0, cfail = 0.0;
+  if (part_n) {
+    fail = pg_partial_sum(part_n, nbn, 2, sh);
+    gmax = pg_partial_max(part_n + 1, nbn, 2, sh);
+  }
+  if (part_c) cfail = pg_partial_sum(part_c, nbc, 1, sh);
+  if (threadIdx.x == 0) {
+    rec[R_COST] = cost;
+    rec[R_BAD] = bad;
+    rec[R_CHOL] = fail + cfail;
+    rec[R_GMAX] = gmax;
+  }
+}
+
+__global__ void pg_set_record_kernel(double* rec, int first, int n, double value) {
+  const int k = threadIdx.x;
+  if (k < n) rec[first + k] = value;
+}
+
+// ---- the solver ---------------------------------------------------------------------------------------------------------------------------
+__global__ void pg_solve_reset_kernel(double* rec) {
+  if (threadIdx.x != 0) return;
+  rec[R_ITER] = 0.0;
+  rec[R_REL] = 1.0;
+  rec[R_CONV] = 0.0;
+  rec[R_BREAK] = rec[R_CHOL] != 0.0 ? 1.0 : 0.0;
+  rec[R_RZ] = rec[R_RZ0] = rec[R_ALPHA] = rec[R_BETA] = 0.0;
+}
+
+// z = Dinv r / (1 + lambda) of one node, and its term of r . z
+__device__ __forceinline__ double pg_jacobi_node(const double* dinv, double scale, const double* r, double* z) {
+  double Di[36], t6[6];
+  ld36(dinv, Di);
+  m6_vec(Di, r, t6);
+#pragma unroll
+  for (int q = 0; q < 6; ++q) z[q] = scale * t6[q];
+  return v6_dot(r, z);
+}
+
+// x = 0, r = -g, both search directions 0; with `dinv` also z = M^-1 r (block-Jacobi) and the partials of r . z
+__global__ __launch_bounds__(PG_B) void pg_solve_init_kernel(const uint8_t* __restrict__ fixed, int N, const double* __restrict__ grad,
+                                                             const double* __restrict__ dinv, double scale, double* __restrict__ x,
+                                                             double* __restrict__ r, double* __restrict__ z, double* __restrict__ p0,
+                                                             double* __restrict__ p1, double* __restrict__ part, const double* rec) {
+  if (pg_stopped(rec)) return;
+  __shared__ double sh[PG_B];
+  const int v = blockIdx.x * PG_B + threadIdx.x;
+  double d = 0.0;
+  if (v < N) {
+    double rv[6], zv[6];
+    const bool fx = fixed[v] != 0;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+      rv[q] = fx ? 0.0 : -grad[(size_t)v * 6 + q];
+      zv[q] = 0.0;
+    }
+    if (dinv) d = pg_jacobi_node(dinv + (size_t)v * 36, scale, rv, zv);
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+      x[(size_t)v * 6 + q] = 0.0;
+      p0[(size_t)v * 6 + q] = 0.0;
+      p1[(size_t)v * 6 + q] = 0.0;
+    }
+    st6(r + (size_t)v * 6, rv);
+    st6(z + (size_t)v * 6, zv);
+  }
+  if (dinv) {
+    const double s = pg_wg_sum(d, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+  }
+}
+
+// ONE workgroup: rz0 = rz = r . z of the start
+__global__ __launch_bounds__(PG_B) void pg_solve_rz0_kernel(const double* part, int nb, double* rec) {
+  if (pg_stopped(rec)) return;
+  __shared__ double sh[PG_B];
+  const double rz = pg_partial_sum(part, nb, 1, sh);
+  if (threadIdx.x == 0) {
+    rec[R_RZ] = rec[R_RZ0] = rz;
+    rec[R_BETA] = 0.0;
+    if (rz == 0.0) {
+      rec[R_REL] = 0.0;
+      rec[R_CONV] = 1.0;
+    } else if (!(rz > 0.0) || !(rz * 0.0 == 0.0)) {
+      rec[R_BREAK] = 1.0;
+    }
+  }
+}
+
+// p = z + beta p_old for the node and its neighbours, q = (H + lambda blockdiag H) p over the incidence list, partials of p . q
+__global__ __launch_bounds__(PG_B) void pg_matvec_kernel(const uint8_t* __restrict__ fixed, int N, const int32_t* __restrict__ ij, int E,
+                                                         const int32_t* __restrict__ ptr, const int32_t* __restrict__ lst,
+                                                         const double* __restrict__ blocks, const double* __restrict__ diag, double lambda,
+                                                         const double* __restrict__ z, const double* __restrict__ pold,
+                                                         double* __restrict__ pnew, double* __restrict__ q, double* __restrict__ part,
+                                                         const double* rec) {
+  if (pg_stopped(rec)) return;
+  __shared__ double sh[PG_B];
+  const double beta = rec[R_BETA];
+  const int v = blockIdx.x * PG_B + threadIdx.x;
+  double d = 0.0;
+  if (v < N) {
+    double pv[6], acc[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) pv[k] = acc[k] = 0.0;
+    if (!fixed[v]) {
+#pragma unroll
+      for (int k = 0; k < 6; ++k) pv[k] = z[(size_t)v * 6 + k] + beta * pold[(size_t)v * 6 + k];
+      double M[36], t6[6], u6[6];
+      ld36(diag + (size_t)v * 36, M);
+      m6_vec(M, pv, t6);
+#pragma unroll
+      for (int k = 0; k < 6; ++k) acc[k] = lambda * t6[k];
+      int b = ptr[v], en = ptr[v + 1];
+      b = b < 0 ? 0 : b;
+      en = en > 2 * E ? 2 * E : en;
+      for (int c = b; c < en; ++c) {
+        const int e = lst[c];
+        if (e < 0 || e >= E) continue;
+        const int i = ij[2 * e], j = ij[2 * e + 1];
+        if (i < 0 || i >= N || j < 0 || j >= N || i == j) continue;
+        double xi[6], xj[6];
+        const bool fi = fixed[i] != 0, fj = fixed[j] != 0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+          xi[k] = fi ? 0.0 : z[(size_t)i * 6 + k] + beta * pold[(size_t)i * 6 + k];
+          xj[k] = fj ? 0.0 : z[(size_t)j * 6 + k] + beta * pold[(size_t)j * 6 + k];
+        }
+        const double* hb = blocks + (size_t)e * 108;
+        if (i == v) {
+          ld36(hb, M);
+          m6_vec(M, xi, t6);
+          ld36(hb + 36, M);
+          m6_vec(M, xj, u6);
+        } else {
+          ld36(hb + 36, M);
+          m6_tvec(M, xi, t6);
+          ld36(hb + 72, M);
+          m6_vec(M, xj, u6);
+        }
+#pragma unroll
+        for (int k = 0; k < 6; ++k) acc[k] = acc[k] + (t6[k] + u6[k]);
+      }
+      d = v6_dot(pv, acc);
+    }
+    st6(pnew + (size_t)v * 6, pv);
+    st6(q + (size_t)v * 6, acc);
+  }
+  const double s = pg_wg_sum(d, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// ONE workgroup: alpha = rz / p . q, or breakdown
+__global__ __launch_bounds__(PG_B) void pg_alpha_kernel(const double* part, int nb, double* rec) {
+  if (pg_stopped(rec)) return;
+  __shared__ double sh[PG_B];
+  const double pq = pg_partial_sum(part, nb, 1, sh);
+  if (threadIdx.x == 0) {
+    const double a = rec[R_RZ] / pq;
+    if (!(pq > 0.0) || !(a * 0.0 == 0.0)) rec[R_BREAK] = 1.0;
+    else rec[R_ALPHA] = a;
+  }
+}
+
+// x += alpha p, r -= alpha q; with `dinv` also z = M^-1 r (block-Jacobi) and the partials of r . z
+__global__ __launch_bounds__(PG_B) void pg_update_kernel(int N, const double* __restrict__ p, const double* __restrict__ q,
+                                                         const double* __restrict__ dinv, double scale, double* __restrict__ x,
+                                                         double* __restrict__ r, double* __restrict__ z, double* __restrict__ part,
+                                                         const double* rec) {
+  if (pg_stopped(rec)) return;
+  __shared__ double sh[PG_B];
+  const double alpha = rec[R_ALPHA];
+  const int v = blockIdx.x * PG_B + threadIdx.x;
+  double d = 0.0;
+  if (v < N) {
+    double rv[6], zv[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      x[(size_t)v * 6 + k] = x[(size_t)v * 6 + k] + alpha * p[(size_t)v * 6 + k];
+      rv[k] = r[(size_t)v * 6 + k] - alpha * q[(size_t)v * 6 + k];
+    }
+    st6(r + (size_t)v * 6, rv);
+    if (dinv) {
+      d = pg_jacobi_node(dinv + (size_t)v * 36, scale, rv, zv);
+      st6(z + (size_t)v * 6, zv);
+    }
+  }
+  if (dinv) {
+    const double s = pg_wg_sum(d, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+  }
+}
+
+// ONE workgroup: beta = rz' / rz, the iteration count and the convergence test sqrt(rz' / rz0) <= rtol
+__global__ __launch_bounds__(PG_B) void pg_beta_kernel(const double* part, int nb, double rtol, double* rec) {
+  if (pg_stopped(rec)) return;
+  __shared__ double sh[PG_B];
+  const double rz = pg_partial_sum(part, nb, 1, sh);
+  if (threadIdx.x == 0) {
+    if (!(rz >= 0.0) || !(rz * 0.0 == 0.0)) {
+      rec[R_BREAK] = 1.0;
+      return;
+    }
+    const double rel = sqrt(rz / rec[R_RZ0]);
+    rec[R_BETA] = rz / rec[R_RZ];
+    rec[R_RZ] = rz;
+    rec[R_ITER] = rec[R_ITER] + 1.0;
+    rec[R_REL] = rel;
+    if (rel <= rtol) rec[R_CONV] = 1.0;
+  }
+}
+
+// ---- the chain preconditioner: z = N S G S' N' r, S = inclusive prefix sums over the chain edges ------------------------------------------
+// launch 1 of a scan over n 6-vectors (REV: from the last element down): the block-local inclusive scan and the block totals.
+// PRE: element m is N_m' in[m + 1] (`in` has a row per NODE); else it is in[m] (a row per chain edge)
+template <bool REV, bool PRE>
+__global__ __launch_bounds__(PG_B) void pg_scan_local_kernel(int n, const double* __restrict__ in, const double* __restrict__ chain,
+                                                             double* __restrict__ local, double* __restrict__ bsum, const double* rec) {
+  if (pg_stopped(rec)) return;
+  __shared__ double sh[2][PG_B][6];
+  const int l = blockIdx.x * PG_B + threadIdx.x;
+  const int m = REV ? n - 1 - l : l;
+  double v[6] = {0, 0, 0, 0, 0, 0};
+  if (l < n) {
+    if (PRE) {
+      double Nm[36], y[6];
+      ld36(chain + (size_t)m * 72 + 36, Nm);
+      ld6(in + (size_t)(m + 1) * 6, y);
+      m6_tvec(Nm, y, v);
+    } else {
+      ld6(in + (size_t)m * 6, v);
+    }
+  }
+  int cur = 0;
+  st6(sh[0][threadIdx.x], v);
+  __syncthreads();
+  for (int d = 1; d < PG_B; d <<= 1) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      const double a = sh[cur][threadIdx.x][k];
+      sh[cur ^ 1][threadIdx.x][k] = (int)threadIdx.x >= d ? a + sh[cur][threadIdx.x - d][k] : a;
+    }
+    cur ^= 1;
+    __syncthreads();
+  }
+  if (l < n) st6(local + (size_t)m * 6, sh[cur][threadIdx.x]);
+  const int last = min(n - blockIdx.x * PG_B, PG_B) - 1;
+  if ((int)threadIdx.x == last) st6(bsum + (size_t)blockIdx.x * 6, sh[cur][threadIdx.x]);
+}
+
+// launch 2, ONE workgroup: off[b] = the totals of the blocks before b, added in block order
+__global__ void pg_scan_sums_kernel(int nb, const double* __restrict__ bsum, double* __restrict__ off, const double* rec) {
+  if (pg_stopped(rec)) return;
+  const int k = threadIdx.x;
+  if (k >= 6) return;
+  double tot = 0.0;
+  for (int b = 0; b < nb; ++b) {
+    off[(size_t)b * 6 + k] = tot;
+    tot = b ? tot + bsum[(size_t)b * 6 + k] : bsum[k];
+  }
+}
+
+// launch 3: the block offset added, then the element's transform.  POSTN: out[m + 1] = N_m (.), a row per node, with the partials
+// of r . z when `r` is given; else out[m] = G_m (.), a row per chain edge
+template <bool REV, bool POSTN>
+__global__ __launch_bounds__(PG_B) void pg_scan_apply_kernel(int n, const double* __restrict__ local, const double* __restrict__ off,
+                                                             const double* __restrict__ chain, double* __restrict__ out,
+                                                             const double* __restrict__ r, double* __restrict__ part, const double* rec) {
+  if (pg_stopped(rec)) return;
+  __shared__ double sh[PG_B];
+  const int l = blockIdx.x * PG_B + threadIdx.x;
+  const int m = REV ? n - 1 - l : l;
+  double d = 0.0;
+  if (l < n) {
+    double v[6], M[36], o[6];
+    ld6(local + (size_t)m * 6, v);
+    if (blockIdx.x > 0) {
+#pragma unroll
+      for (int k = 0; k < 6; ++k) v[k] = v[k] + off[(size_t)blockIdx.x * 6 + k];
+    }
+    ld36(chain + (size_t)m * 72 + (POSTN ? 36 : 0), M);
+    m6_vec(M, v, o);
+    st6(out + (size_t)(POSTN ? m + 1 : m) * 6, o);
+    if (POSTN && r) {
+      double rv[6];
+      ld6(r + (size_t)(m + 1) * 6, rv);
+      d = v6_dot(rv, o);
+    }
+  }
+  if (POSTN && part) {
+    const double s = pg_wg_sum(d, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+  }
+}
+
+// z = Dinv r / (1 + lambda) alone (ovn_pose_graph_precondition)
+__global__ __launch_bounds__(PG_B) void pg_jacobi_apply_kernel(int N, const double* __restrict__ dinv, double scale,
+                                                               const double* __restrict__ in, double* __restrict__ out) {
+  const int v = blockIdx.x * PG_B + threadIdx.x;
+  if (v >= N) return;
+  double rv[6], zv[6];
+  ld6(in + (size_t)v * 6, rv);
+  (void)pg_jacobi_node(dinv + (size_t)v * 36, scale, rv, zv);
+  st6(out + (size_t)v * 6, zv);
+}
+
+// six launches: out = M_chain^-1 in over the nodes 1 .. N - 1 (row 0 of `out` is not written: it is 0 from the start of a solve)
+int pg_chain_apply(int N, const double* chain, const double* in, double* out, const PgWs& w, const double* r_for_dot, double* part,
+                   const double* rec, hipStream_t stream) {
+  const int n = N - 1;
+  if (n < 1) return OVN_OK;
+  const int nb = (n + PG_B - 1) / PG_B;
+  pg_scan_local_kernel<true, true><<<nb, PG_B, 0, stream>>>(n, in, chain, w.sa, w.bsum, rec);
+  pg_scan_sums_kernel<<<1, 64, 0, stream>>>(nb, w.bsum, w.bsum + (size_t)6 * nb, rec);
+  pg_scan_apply_kernel<true, false><<<nb, PG_B, 0, stream>>>(n, w.sa, w.bsum + (size_t)6 * nb, chain, w.sb, nullptr, nullptr, rec);
+  pg_scan_local_kernel<false, false><<<nb, PG_B, 0, stream>>>(n, w.sb, chain, w.sa, w.bsum, rec);
+  pg_scan_sums_kernel<<<1, 64, 0, stream>>>(nb, w.bsum, w.bsum + (size_t)6 * nb, rec);
+  pg_scan_apply_kernel<false, true><<<nb, PG_B, 0, stream>>>(n, w.sa, w.bsum + (size_t)6 * nb, chain, out, r_for_dot, part, rec);
+  OVN_HIP_CHECK(hipGetLastError());
+  return OVN_OK;
+}
+
+// ---- retraction ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(PG_B) void pg_retract_kernel(const double* __restrict__ poses, const uint8_t* __restrict__ fixed,
+                                                          const double* __restrict__ delta, int N, double* __restrict__ out,
+                                                          double* __restrict__ part) {
+  __shared__ double sh[PG_B];
+  const int v = blockIdx.x * PG_B + threadIdx.x;
+  double dm = 0.0;
+  if (v < N) {
+    double T[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) T[q] = poses[(size_t)v * 16 + q];
+    if (!fixed[v]) {
+      double R[9], t[3], xi[6], Re[9], te[3], Ro[9], to[3];
+      pg_load_pose(T, R, t);
+      ld6(delta + (size_t)v * 6, xi);
+#pragma unroll
+      for (int q = 0; q < 6; ++q) dm = fmax(dm, fabs(xi[q]));
+      pg_exp(xi, Re, te);
+      m3_mul(R, Re, Ro);
+      m3_vec(R, te, to);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        T[i * 4] = Ro[i * 3]; T[i * 4 + 1] = Ro[i * 3 + 1]; T[i * 4 + 2] = Ro[i * 3 + 2];
+        T[i * 4 + 3] = to[i] + t[i];
+      }
+      T[12] = 0.0; T[13] = 0.0; T[14] = 0.0; T[15] = 1.0;
+    }
+#pragma unroll
+    for (int q = 0; q < 16; ++q) out[(size_t)v * 16 + q] = T[q];
+  }
+  const double m = pg_wg_max(dm, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = m;
+}
+
+__global__ __launch_bounds__(PG_B) void pg_dmax_kernel(const double* part, int nb, double* rec) {
+  __shared__ double sh[PG_B];
+  const double m = pg_partial_max(part, nb, 1, sh);
+  if (threadIdx.x == 0) rec[R_DMAX] = m;
+}
+
+bool pg_finite(double v) { return v * 0.0 == 0.0; }
+
+}  // namespace
+
+// ---- C ABI --------------------------------------------------------------------------------------------------------------------------------
+extern "C" {
+
+int64_t ovn_pose_graph_workspace_bytes(int64_t n_nodes, int64_t n_edges) {
+  if (n_nodes < 1 || n_edges < 0 || n_nodes > OVN_POSE_GRAPH_MAX_NODES || n_edges > OVN_POSE_GRAPH_MAX_EDGES) return 0;
+  return (int64_t)(PgWs(nullptr, n_nodes, n_edges).total * sizeof(double));
+}
+
+int ovn_pose_graph_linearize(ovn_ctx* ctx, void* stream, const double* poses_dev, const uint8_t* fixed_dev, int n_nodes,
+                             const int32_t* edge_ij_dev, const double* meas_dev, const double* info_dev, int n_edges,
+                             const int32_t* node_ptr_dev, const int32_t* node_edge_dev, double huber, double* res_dev, double* chi_dev,
+                             double* weight_dev, double* jac_dev, double* blocks_dev, double* grad_dev, double* diag_dev,
+                             double* dinv_dev, double* chain_dev, double* ws_dev, double* record_dev) {
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_pose_graph_linearize: ctx is NULL");
+  OVN_REQUIRE(n_nodes >= 1 && n_nodes <= OVN_POSE_GRAPH_MAX_NODES && n_edges >= 0 && n_edges <= OVN_POSE_GRAPH_MAX_EDGES, OVN_ERR_ARG,
+              "ovn_pose_graph_linearize: %d nodes (1..%d), %d edges (0..%d)", n_nodes, OVN_POSE_GRAPH_MAX_NODES, n_edges,
+              OVN_POSE_GRAPH_MAX_EDGES);
+  OVN_REQUIRE(huber > 0.0 && huber == huber, OVN_ERR_ARG, "ovn_pose_graph_linearize: huber must be > 0 (+inf: least squares)");
+  OVN_REQUIRE(record_dev != nullptr, OVN_ERR_ARG, "ovn_pose_graph_linearize: record_dev is NULL");
+  OVN_ON_DEVICE(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (n_edges == 0) {   // nothing to measure: cost 0, no buffer but the record touched
+    pg_set_record_kernel<<<1, 64, 0, s>>>(record_dev, R_COST, 4, 0.0);
+    OVN_HIP_CHECK(hipGetLastError());
+    return OVN_OK;
+  }
+  const bool jac = jac_dev != nullptr;
+  OVN_REQUIRE(jac ? (blocks_dev && grad_dev && diag_dev && dinv_dev) : (!blocks_dev && !grad_dev && !diag_dev && !dinv_dev && !chain_dev),
+              OVN_ERR_ARG, "ovn_pose_graph_linearize: jac, blocks, grad, diag and dinv are given together, or none of them (cost only)");
+  OVN_REQUIRE(poses_dev && fixed_dev && edge_ij_dev && meas_dev && info_dev && res_dev && chi_dev && weight_dev && ws_dev, OVN_ERR_ARG,
+              "ovn_pose_graph_linearize: NULL buffer");
+  OVN_REQUIRE(!jac || (node_ptr_dev && node_edge_dev), OVN_ERR_ARG, "ovn_pose_graph_linearize: NULL incidence list");
+  OVN_REQUIRE(!chain_dev || n_edges >= n_nodes - 1, OVN_ERR_ARG, "ovn_pose_graph_linearize: a chain needs the %d odometry edges first",
+              n_nodes - 1);
+  PgWs w(ws_dev, n_nodes, n_edges);
+  const int nbe = (n_edges + PG_B - 1) / PG_B, nbn = (n_nodes + PG_B - 1) / PG_B;
+  const int nbc = (chain_dev && n_nodes > 1) ? (n_nodes - 1 + PG_B - 1) / PG_B : 0;
+  if (jac) {
+    pg_edge_kernel<true><<<nbe, PG_B, 0, s>>>(poses_dev, n_nodes, edge_ij_dev, meas_dev, info_dev, n_edges, huber, res_dev, chi_dev,
+                                              weight_dev, jac_dev, blocks_dev, w.eg, w.part_e);
+    pg_node_kernel<<<nbn, PG_B, 0, s>>>(fixed_dev, n_nodes, edge_ij_dev, n_edges, node_ptr_dev, node_edge_dev, blocks_dev, w.eg, grad_dev,
+                                        diag_dev, dinv_dev, w.part_n);
+    if (nbc) pg_chain_kernel<<<nbc, PG_B, 0, s>>>(poses_dev, n_nodes, info_dev, weight_dev, jac_dev, chain_dev, w.part_c);
+    pg_lin_record_kernel<<<1, PG_B, 0, s>>>(w.part_e, nbe, w.part_n, nbn, nbc ? w.part_c : nullptr, nbc, record_dev);
+  } else {
+    pg_edge_kernel<false><<<nbe, PG_B, 0, s>>>(poses_dev, n_nodes, edge_ij_dev, meas_dev, info_dev, n_edges, huber, res_dev, chi_dev,
+                                               weight_dev, nullptr, nullptr, nullptr, w.part_e);
+    pg_lin_record_kernel<<<1, PG_B, 0, s>>>(w.part_e, nbe, nullptr, 0, nullptr, 0, record_dev);
+  }
+  OVN_HIP_CHECK(hipGetLastError());
+  return OVN_OK;
+}
+
+int ovn_pose_graph_solve(ovn_ctx* ctx, void* stream, const uint8_t* fixed_dev, int n_nodes, const int32_t* edge_ij_dev, int n_edges,
+                         const int32_t* node_ptr_dev, const int32_t* node_edge_dev, const double* blocks_dev, const double* grad_dev,
+                         const double* diag_dev, const double* dinv_dev, const double* chain_dev, int preconditioner, double lambda,
+                         double rtol, int first_iteration, int iterations, double* delta_dev, double* ws_dev, double* record_dev) {
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_pose_graph_solve: ctx is NULL");
+  OVN_REQUIRE(n_nodes >= 1 && n_nodes <= OVN_POSE_GRAPH_MAX_NODES && n_edges >= 0 && n_edges <= OVN_POSE_GRAPH_MAX_EDGES, OVN_ERR_ARG,
+              "ovn_pose_graph_solve: %d nodes (1..%d), %d edges (0..%d)", n_nodes, OVN_POSE_GRAPH_MAX_NODES, n_edges,
+              OVN_POSE_GRAPH_MAX_EDGES);
+  OVN_REQUIRE(preconditioner == OVN_POSE_GRAPH_JACOBI || preconditioner == OVN_POSE_GRAPH_CHAIN, OVN_ERR_ARG,
+              "ovn_pose_graph_solve: preconditioner %d (0 = block-Jacobi, 1 = odometry chain)", preconditioner);
+  OVN_REQUIRE(pg_finite(lambda) && lambda >= 0.0, OVN_ERR_ARG, "ovn_pose_graph_solve: lambda must be finite and >= 0");
+  OVN_REQUIRE(pg_finite(rtol) && rtol >= 0.0, OVN_ERR_ARG, "ovn_pose_graph_solve: rtol must be finite and >= 0");
+  OVN_REQUIRE(first_iteration >= 0 && iterations >= 0 && iterations <= OVN_POSE_GRAPH_MAX_CHUNK, OVN_ERR_ARG,
+              "ovn_pose_graph_solve: first_iteration %d (>= 0), iterations %d (0..%d)", first_iteration, iterations,
+              OVN_POSE_GRAPH_MAX_CHUNK);
+  OVN_REQUIRE(record_dev != nullptr, OVN_ERR_ARG, "ovn_pose_graph_solve: record_dev is NULL");
+  OVN_ON_DEVICE(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (n_edges == 0) {   // nothing to solve: converged after 0 iterations, delta untouched
+    pg_set_record_kernel<<<1, 64, 0, s>>>(record_dev, R_ITER, 8, 0.0);
+    pg_set_record_kernel<<<1, 64, 0, s>>>(record_dev, R_CONV, 1, 1.0);
+    OVN_HIP_CHECK(hipGetLastError());
+    return OVN_OK;
+  }
+  OVN_REQUIRE(fixed_dev && edge_ij_dev && node_ptr_dev && node_edge_dev && blocks_dev && grad_dev && diag_dev && dinv_dev && delta_dev &&
+                  ws_dev, OVN_ERR_ARG, "ovn_pose_graph_solve: NULL buffer");
+  const bool chain = preconditioner == OVN_POSE_GRAPH_CHAIN;
+  OVN_REQUIRE(!chain || chain_dev, OVN_ERR_ARG, "ovn_pose_graph_solve: the chain preconditioner needs chain_dev");
+  PgWs w(ws_dev, n_nodes, n_edges);
+  const int nbn = (n_nodes + PG_B - 1) / PG_B, nbc = (n_nodes - 1 + PG_B - 1) / PG_B;
+  const double scale = 1.0 / (1.0 + lambda);
+  const double* dj = chain ? nullptr : dinv_dev;
+  double* part = w.part_n;
+  if (first_iteration == 0) {
+    pg_solve_reset_kernel<<<1, 64, 0, s>>>(record_dev);
+    pg_solve_init_kernel<<<nbn, PG_B, 0, s>>>(fixed_dev, n_nodes, grad_dev, dj, scale, delta_dev, w.r, w.z, w.p[0], w.p[1], part, record_dev);
+    if (chain) {
+      int rc = pg_chain_apply(n_nodes, chain_dev, w.r, w.z, w, w.r, part, record_dev, s);
+      if (rc) return rc;
+    }
+    pg_solve_rz0_kernel<<<1, PG_B, 0, s>>>(part, chain ? nbc : nbn, record_dev);
+  }
+  for (int k = 0; k < iterations; ++k) {
+    const int cur = (first_iteration + k) & 1;
+    pg_matvec_kernel<<<nbn, PG_B, 0, s>>>(fixed_dev, n_nodes, edge_ij_dev, n_edges, node_ptr_dev, node_edge_dev, blocks_dev, diag_dev, lambda,
+                                          w.z, w.p[cur], w.p[cur ^ 1], w.q, part, record_dev);
+    pg_alpha_kernel<<<1, PG_B, 0, s>>>(part, nbn, record_dev);
+    pg_update_kernel<<<nbn, PG_B, 0, s>>>(n_nodes, w.p[cur ^ 1], w.q, dj, scale, delta_dev, w.r, w.z, part, record_dev);
+    if (chain) {
+      int rc = pg_chain_apply(n_nodes, chain_dev, w.r, w.z, w, w.r, part, record_dev, s);
+      if (rc) return rc;
+    }
+    pg_beta_kernel<<<1, PG_B, 0, s>>>(part, chain ? nbc : nbn, rtol, record_dev);
+  }
+  OVN_HIP_CHECK(hipGetLastError());
+  return OVN_OK;
+}
+
+int ovn_pose_graph_precondition(ovn_ctx* ctx, void* stream, int n_nodes, int preconditioner, double lambda, const double* dinv_dev,
+                                const double* chain_dev, const double* in_dev, double* out_dev, double* ws_dev) {
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_pose_graph_precondition: ctx is NULL");
+  OVN_REQUIRE(n_nodes >= 1 && n_nodes <= OVN_POSE_GRAPH_MAX_NODES, OVN_ERR_ARG, "ovn_pose_graph_precondition: %d nodes (1..%d)", n_nodes,
+              OVN_POSE_GRAPH_MAX_NODES);
+  OVN_REQUIRE(preconditioner == OVN_POSE_GRAPH_JACOBI || preconditioner == OVN_POSE_GRAPH_CHAIN, OVN_ERR_ARG,
+              "ovn_pose_graph_precondition: preconditioner %d (0 = block-Jacobi, 1 = odometry chain)", preconditioner);
+  OVN_REQUIRE(pg_finite(lambda) && lambda >= 0.0, OVN_ERR_ARG, "ovn_pose_graph_precondition: lambda must be finite and >= 0");
+  const bool chain = preconditioner == OVN_POSE_GRAPH_CHAIN;
+  OVN_REQUIRE(in_dev && out_dev && ws_dev && (chain ? chain_dev != nullptr : dinv_dev != nullptr), OVN_ERR_ARG,
+              "ovn_pose_graph_precondition: NULL buffer");
+  OVN_ON_DEVICE(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  if (!chain) {
+    pg_jacobi_apply_kernel<<<(n_nodes + PG_B - 1) / PG_B, PG_B, 0, s>>>(n_nodes, dinv_dev, 1.0 / (1.0 + lambda), in_dev, out_dev);
+    OVN_HIP_CHECK(hipGetLastError());
+    return OVN_OK;
+  }
+  OVN_HIP_CHECK(hipMemsetAsync(out_dev, 0, 6 * sizeof(double), s));   // the fixed node 0
+  PgWs w(ws_dev, n_nodes, 0);
+  return pg_chain_apply(n_nodes, chain_dev, in_dev, out_dev, w, nullptr, nullptr, nullptr, s);
+}
+
+int ovn_pose_graph_retract(ovn_ctx* ctx, void* stream, const double* poses_dev, const uint8_t* fixed_dev, const double* delta_dev,
+                           int n_nodes, double* out_dev, double* ws_dev, double* record_dev) {
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_pose_graph_retract: ctx is NULL");
+  OVN_REQUIRE(n_nodes >= 1 && n_nodes <= OVN_POSE_GRAPH_MAX_NODES, OVN_ERR_ARG, "ovn_pose_graph_retract: %d nodes (1..%d)", n_nodes,
+              OVN_POSE_GRAPH_MAX_NODES);
+  OVN_REQUIRE(poses_dev && fixed_dev && delta_dev && out_dev && ws_dev && record_dev, OVN_ERR_ARG, "ovn_pose_graph_retract: NULL buffer");
+  OVN_ON_DEVICE(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  PgWs w(ws_dev, n_nodes, 0);
+  const int nbn = (n_nodes + PG_B - 1) / PG_B;
+  pg_retract_kernel<<<nbn, PG_B, 0, s>>>(poses_dev, fixed_dev, delta_dev, n_nodes, out_dev, w.part_n);
+  pg_dmax_kernel<<<1, PG_B, 0, s>>>(w.part_n, nbn, record_dev);
+  OVN_HIP_CHECK(hipGetLastError());
+  return OVN_OK;
+}
+
+}  // extern "C"

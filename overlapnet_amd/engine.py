@@ -1479,6 +1479,105 @@ class OvnEngine:
             _lib.check(self.lib.ovn_profile_end(self._h, ms, cnt), "ovn_profile_end")
         return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(self.PROFILE_KINDS)}
 
+    # -- pose-graph optimization (ovn_pose_graph_*) -------------------------------------------
+    POSE_GRAPH_RECORD = ("cost", "bad_edges", "cholesky_failures", "grad_max", "iterations", "relative_residual", "converged",
+                         "breakdown", "rz", "rz0", "alpha", "beta", "delta_max")
+    POSE_GRAPH_PRECONDITIONERS = {"jacobi": 0, "chain": 1}
+
+    def _pg_tensor(self, what: str, t: Optional[torch.Tensor], dtype, shape, optional: bool = False):
+        if t is None and optional:
+            return None
+        if (t is None or t.device != self.device or t.dtype != dtype or not t.is_contiguous()
+                or (shape is not None and tuple(t.shape) != tuple(shape))):
+            raise _lib.OvnError("%s must be a contiguous %s %s tensor on %s" % (what, dtype, tuple(shape) if shape else "", self.device))
+        return t
+
+    def pose_graph_buffers(self, n_nodes: int, n_edges: int, chain: bool = False) -> Dict[str, torch.Tensor]:
+        """Every device buffer the pose-graph calls write, sized for n_nodes and n_edges: res, chi, weight, jac, blocks, grad, diag,
+        dinv, chain (when asked), delta, ws (ovn_pose_graph_workspace_bytes) and record."""
+        n, e = int(n_nodes), int(n_edges)
+        nbytes = int(self.lib.ovn_pose_graph_workspace_bytes(n, e))
+        if nbytes <= 0:
+            raise _lib.OvnError("pose graph of %d nodes and %d edges is outside the library's limits" % (n, e))
+        z = lambda *s: torch.zeros(s, dtype=torch.float64, device=self.device)
+        b = dict(res=z(e, 6), chi=z(e), weight=z(e), jac=z(e, 2, 6, 6), blocks=z(e, 3, 6, 6), grad=z(n, 6), diag=z(n, 6, 6),
+                 dinv=z(n, 6, 6), delta=z(n, 6), ws=z(nbytes // 8), record=z(16))
+        if chain:
+            b["chain"] = z(max(n - 1, 0), 2, 6, 6)
+        return b
+
+    def pose_graph_linearize(self, poses, fixed, edge_ij, meas, info, node_ptr, node_edge, huber: float, buf: Dict[str, torch.Tensor],
+                             jacobians: bool = True, record: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Residuals, weights and cost of the edges at `poses` into buf's res, chi, weight, and with jacobians=True the Jacobians,
+        Hessian blocks, gradient, diagonal blocks, their inverses and (when buf has "chain") the chain preconditioner's terms
+        (ovn_pose_graph_linearize).  Returns the record tensor (buf["record"] unless another is given)."""
+        f64, n, e = torch.float64, int(poses.shape[0]), int(edge_ij.shape[0])
+        self._pg_tensor("pose_graph_linearize: poses", poses, f64, (n, 4, 4))
+        self._pg_tensor("pose_graph_linearize: fixed", fixed, torch.uint8, (n,))
+        self._pg_tensor("pose_graph_linearize: edge_ij", edge_ij, torch.int32, (e, 2))
+        self._pg_tensor("pose_graph_linearize: meas", meas, f64, (e, 4, 4))
+        self._pg_tensor("pose_graph_linearize: info", info, f64, (e, 6, 6))
+        self._pg_tensor("pose_graph_linearize: node_ptr", node_ptr, torch.int32, (n + 1,))
+        self._pg_tensor("pose_graph_linearize: node_edge", node_edge, torch.int32, (2 * e,))
+        rec = self._pg_tensor("pose_graph_linearize: record", buf["record"] if record is None else record, f64, (16,))
+        for k, s in (("res", (e, 6)), ("chi", (e,)), ("weight", (e,)), ("jac", (e, 2, 6, 6)), ("blocks", (e, 3, 6, 6)), ("grad", (n, 6)),
+                     ("diag", (n, 6, 6)), ("dinv", (n, 6, 6))):
+            self._pg_tensor("pose_graph_linearize: buf[%r]" % k, buf[k], f64, s)
+        ch = self._pg_tensor("pose_graph_linearize: buf['chain']", buf.get("chain"), f64, (max(n - 1, 0), 2, 6, 6), optional=True)
+        j = (lambda k: _ptr(buf[k])) if jacobians else (lambda k: None)
+        with self._dev():
+            _lib.check(self.lib.ovn_pose_graph_linearize(
+                self._h, self._stream(), _ptr(poses), _ptr(fixed), n, _ptr(edge_ij), _ptr(meas), _ptr(info), e, _ptr(node_ptr),
+                _ptr(node_edge), float(huber), _ptr(buf["res"]), _ptr(buf["chi"]), _ptr(buf["weight"]), j("jac"), j("blocks"), j("grad"),
+                j("diag"), j("dinv"), _ptr(ch) if jacobians else None, _ptr(buf["ws"]), _ptr(rec)), "ovn_pose_graph_linearize")
+        return rec
+
+    def pose_graph_solve(self, fixed, edge_ij, node_ptr, node_edge, buf: Dict[str, torch.Tensor], preconditioner="jacobi",
+                         lam: float = 0.0, rtol: float = 1e-8, first_iteration: int = 0, iterations: int = 32) -> torch.Tensor:
+        """Enqueues `iterations` PCG iterations on the linearization in `buf` (ovn_pose_graph_solve); delta in buf["delta"], state in
+        buf["ws"], status in the returned record tensor.  Never waits for the GPU."""
+        n, e = int(fixed.shape[0]), int(edge_ij.shape[0])
+        kind = self.POSE_GRAPH_PRECONDITIONERS.get(preconditioner, preconditioner)
+        if not isinstance(kind, int):
+            raise _lib.OvnError("pose_graph_solve: no preconditioner %r (jacobi, chain)" % (preconditioner,))
+        with self._dev():
+            _lib.check(self.lib.ovn_pose_graph_solve(
+                self._h, self._stream(), _ptr(fixed), n, _ptr(edge_ij), e, _ptr(node_ptr), _ptr(node_edge), _ptr(buf["blocks"]),
+                _ptr(buf["grad"]), _ptr(buf["diag"]), _ptr(buf["dinv"]), _ptr(buf.get("chain")), kind, float(lam), float(rtol),
+                int(first_iteration), int(iterations), _ptr(buf["delta"]), _ptr(buf["ws"]), _ptr(buf["record"])), "ovn_pose_graph_solve")
+        return buf["record"]
+
+    def pose_graph_precondition(self, vec: torch.Tensor, buf: Dict[str, torch.Tensor], preconditioner="jacobi", lam: float = 0.0,
+                                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """out (N,6) = M^-1 vec (N,6) for the preconditioner of the linearization in `buf` (ovn_pose_graph_precondition)."""
+        n = int(vec.shape[0])
+        self._pg_tensor("pose_graph_precondition: vec", vec, torch.float64, (n, 6))
+        out = torch.zeros_like(vec) if out is None else self._pg_tensor("pose_graph_precondition: out", out, torch.float64, (n, 6))
+        kind = self.POSE_GRAPH_PRECONDITIONERS.get(preconditioner, preconditioner)
+        if not isinstance(kind, int):
+            raise _lib.OvnError("pose_graph_precondition: no preconditioner %r (jacobi, chain)" % (preconditioner,))
+        with self._dev():
+            _lib.check(self.lib.ovn_pose_graph_precondition(self._h, self._stream(), n, kind, float(lam), _ptr(buf.get("dinv")),
+                                                            _ptr(buf.get("chain")), _ptr(vec), _ptr(out), _ptr(buf["ws"])),
+                       "ovn_pose_graph_precondition")
+        return out
+
+    def pose_graph_retract(self, poses: torch.Tensor, fixed: torch.Tensor, buf: Dict[str, torch.Tensor],
+                           out: Optional[torch.Tensor] = None, record: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """out (N,4,4) = T_i Exp(delta_i) with delta = buf["delta"] (ovn_pose_graph_retract); |delta|_inf goes to slot 12 of the record."""
+        n = int(poses.shape[0])
+        self._pg_tensor("pose_graph_retract: poses", poses, torch.float64, (n, 4, 4))
+        self._pg_tensor("pose_graph_retract: fixed", fixed, torch.uint8, (n,))
+        self._pg_tensor("pose_graph_retract: buf['delta']", buf["delta"], torch.float64, (n, 6))
+        out = torch.empty_like(poses) if out is None else self._pg_tensor("pose_graph_retract: out", out, torch.float64, (n, 4, 4))
+        if out.data_ptr() == poses.data_ptr():
+            raise _lib.OvnError("pose_graph_retract: out must not be poses")
+        rec = buf["record"] if record is None else record
+        with self._dev():
+            _lib.check(self.lib.ovn_pose_graph_retract(self._h, self._stream(), _ptr(poses), _ptr(fixed), _ptr(buf["delta"]), n,
+                                                       _ptr(out), _ptr(buf["ws"]), _ptr(rec)), "ovn_pose_graph_retract")
+        return out
+
     def selftest(self) -> None:
         with self._dev():
             _lib.check(self.lib.ovn_selftest(self._h), "ovn_selftest")
