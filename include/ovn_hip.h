@@ -684,7 +684,8 @@ int ovn_tsdf_bricks(ovn_ctx* ctx, void* stream, const float* weight_dev, int nx,
  * record_dev: OVN_POSE_GRAPH_RECORD doubles.  [0] cost  [1] edges with weight 0 for a non-finite input  [2] 6 x 6 blocks whose
  * Cholesky met a non-positive pivot  [3] |g|_inf  (ovn_pose_graph_linearize; [2] and [3] are 0 from a cost-only call)
  * [4] PCG iterations done  [5] |r|_M / |r_0|_M  [6] converged  [7] breakdown  [8] r'z  [9] r_0'z_0  [10] alpha  [11] beta
- * (ovn_pose_graph_solve)  [12] |delta|_inf of the free nodes (ovn_pose_graph_retract).
+ * (ovn_pose_graph_solve)  [12] |delta|_inf of the free nodes (ovn_pose_graph_retract)  [13] failed pivots and [14] loop edges left
+ * out (ovn_pose_graph_loops_prepare, below).
  *
  * ovn_pose_graph_workspace_bytes: the size of ws_dev for N nodes and E edges (0 for N or E outside the limits).
  *
@@ -731,6 +732,56 @@ int ovn_pose_graph_precondition(ovn_ctx* ctx, void* stream, int n_nodes, int pre
                                 const double* chain_dev, const double* in_dev, double* out_dev, double* ws_dev);
 int ovn_pose_graph_retract(ovn_ctx* ctx, void* stream, const double* poses_dev, const uint8_t* fixed_dev, const double* delta_dev,
                            int n_nodes, double* out_dev, double* ws_dev, double* record_dev);
+
+/* The chain-plus-loops inverse: the third preconditioner, for a drive with many loop closures (csrc/pose_graph.hip; DESIGN.md section
+ * 33; restated by tests/_pose_graph_loops_ref.py).  PRECONDITION, which the CALLER promises as for chain_dev: edges 0 .. N-2 are the
+ * chain (k, k+1) in order, node 0 is the only fixed node, and the L = E - (N-1) edges after the chain are the loop edges (i, j) -- in
+ * either order, touching node 0 or not, repeated or not.  In chain coordinates the linear part of loop edge a is sigma_a C_a times a
+ * sum over the chain edges [lo_a, hi_a) (C_a = B_a Ad(T_j^-1), lo = min(i, j), hi = max(i, j), sigma = +1 for j > i, else -1), so
+ * Woodbury's identity gives the exact inverse of the UNDAMPED Hessian from the chain inverse and the 6 L x 6 L matrix
+ *   S_ab = delta_ab (w_a Omega_a)^-1 + sigma_a sigma_b C_a (Gamma[min(hi_a, hi_b)] - Gamma[max(lo_a, lo_b)]) C_b'   (spans that overlap)
+ * with Gamma[k] = sum_{m<k} G_m.  With lambda > 0 it is a preconditioner only.
+ *
+ * ovn_pose_graph_loops_bytes: the size of loops_dev for N nodes and L loop edges; 0 for N outside 2 .. OVN_POSE_GRAPH_MAX_NODES or L
+ * outside 1 .. OVN_POSE_GRAPH_MAX_LOOPS.  ovn_pose_graph_loops_layout: out[0] the factorization's block size b, out[1] the padded
+ * order sp of S (6 L rounded up to b, an identity diagonal in the padding), out[2..7] the offsets in doubles of Gamma (N,6,6), C (L,6,6),
+ * (w Omega)^-1 (L,6,6), the spans (L,4: lo, hi, sigma, live), S (sp,sp) and its lower Cholesky factor (sp,sp) inside loops_dev.
+ *
+ * ovn_pose_graph_loops_prepare: runs after an ovn_pose_graph_linearize with chain_dev on the same buffers; writes all of the above
+ * and record [13] = pivots that were not positive and finite (in a loop edge's w Omega or in the blocked right-looking Cholesky
+ * factorization of S; one launch per stage -- panel, triangular solve, symmetric update -- per block column) and [14] = loop edges
+ * left out because their weight is 0 (a non-finite input): zero C, identity block in S.  `stages` is OVN_POSE_GRAPH_LOOPS_ALL; a
+ * benchmark times the three stages by asking for them one at a time, in order (SCAN: Gamma; ASSEMBLE: C, the spans, S and a copy of
+ * its lower triangle; FACTOR: that copy factored in place, and the record).
+ *
+ * ovn_pose_graph_solve_loops: the contract of ovn_pose_graph_solve with this preconditioner (OVN_POSE_GRAPH_LOOPS): z = H^-1 r by the
+ * chain's suffix and prefix scans, d = S^-1 v by two triangular sweeps, a difference scan over the incidence list, and one more
+ * prefix scan; loops_dev also holds the apply's scratch.  `breakdown` is also set, before delta_dev is touched, when record [13] is
+ * not 0.  ovn_pose_graph_precondition_loops: out_dev (N,6) = H^-1 in_dev alone, row 0 zero (a validation entry).
+ *
+ * OVN_ERR_ARG, before any launch: a NULL ctx or buffer, N < 2, L < 1, L > OVN_POSE_GRAPH_MAX_LOOPS, E != N - 1 + L, and what
+ * ovn_pose_graph_solve refuses. */
+#define OVN_POSE_GRAPH_LOOPS 2
+#ifndef OVN_POSE_GRAPH_MAX_LOOPS   /* a benchmark build may raise it (to 512 at most) to measure beyond the cap */
+#define OVN_POSE_GRAPH_MAX_LOOPS 256
+#endif
+#define OVN_POSE_GRAPH_LOOPS_SCAN 1
+#define OVN_POSE_GRAPH_LOOPS_ASSEMBLE 2
+#define OVN_POSE_GRAPH_LOOPS_FACTOR 4
+#define OVN_POSE_GRAPH_LOOPS_ALL 7
+int64_t ovn_pose_graph_loops_bytes(int64_t n_nodes, int64_t n_loops);
+int ovn_pose_graph_loops_layout(int64_t n_nodes, int64_t n_loops, int64_t* out);
+int ovn_pose_graph_loops_prepare(ovn_ctx* ctx, void* stream, const double* poses_dev, int n_nodes, const int32_t* edge_ij_dev,
+                                 const double* info_dev, const double* weight_dev, const double* jac_dev, int n_edges, int n_loops,
+                                 const double* chain_dev, int stages, double* loops_dev, double* record_dev);
+int ovn_pose_graph_solve_loops(ovn_ctx* ctx, void* stream, const uint8_t* fixed_dev, int n_nodes, const int32_t* edge_ij_dev, int n_edges,
+                               const int32_t* node_ptr_dev, const int32_t* node_edge_dev, const double* blocks_dev, const double* grad_dev,
+                               const double* diag_dev, const double* dinv_dev, const double* chain_dev, double* loops_dev, int n_loops,
+                               double lambda, double rtol, int first_iteration, int iterations, double* delta_dev, double* ws_dev,
+                               double* record_dev);
+int ovn_pose_graph_precondition_loops(ovn_ctx* ctx, void* stream, int n_nodes, int n_edges, int n_loops, const int32_t* node_ptr_dev,
+                                      const int32_t* node_edge_dev, const double* chain_dev, double* loops_dev, const double* in_dev,
+                                      double* out_dev, double* ws_dev);
 
 /* The per-point part of range_projection alone (src/utils/utils.py:75-104), exactly as ovn_project's scatter kernel evaluates it:
  * for each of n float32 points (x,y,z,*) yaw = -np.arctan2(y, x), pitch = np.arcsin(z / depth) with NumPy's float32 results

@@ -1,5 +1,7 @@
 // SE(3) pose-graph optimization in fp64 (ovn_pose_graph_*; include/ovn_hip.h): linearization of the edges,
-// block-sparse preconditioned conjugate gradients with a block-Jacobi or an odometry-chain preconditioner, and the retraction.
+// block-sparse preconditioned conjugate gradients with a block-Jacobi or an odometry-chain preconditioner, and the retraction; and the
+// chain-plus-loops inverse (ovn_pose_graph_loops_*; tests/_pose_graph_loops_ref.py): the exact inverse of the
+// undamped Hessian of a chain plus L loop edges, with a dense Cholesky factorization of order 6 L.
 // No atomics: a node sums over its incidence list in list order, every dot product and maximum is a fixed tree (256 lanes, halving),
 // the scans are Hillis-Steele inside a workgroup and three launches across workgroups.  No workgroup waits on another inside a launch.
 // Built without FMA contraction: tests/_pose_graph_ref.py states the same operations one by one.
@@ -964,6 +966,528 @@ __global__ __launch_bounds__(PG_B) void pg_dmax_kernel(const double* part, int n
 
 bool pg_finite(double v) { return v * 0.0 == 0.0; }
 
+// ---- the chain-plus-loops inverse (ovn_pose_graph_loops_*) -----------------------------------------------------------
+// H = H_chain + sum_a J_a' w_a Omega_a J_a over the L loop edges; in chain coordinates J_a is sigma_a C_a times a sum over the chain
+// edges [lo_a, hi_a), so Woodbury needs the 6 L x 6 L matrix S = W^-1 + J H_chain^-1 J', whose blocks are differences of the prefix
+// sums Gamma of G.  S is factored by a blocked right-looking Cholesky (block PGL_NB) and applied by two triangular sweeps.
+constexpr int PGL_NB = 48;                                  // block size of the factorization: eight 6 x 6 blocks
+constexpr int PGL_TS = 1024;                                // threads of the one-workgroup triangular sweeps
+constexpr int PGL_MAX_SP = (6 * OVN_POSE_GRAPH_MAX_LOOPS + PGL_NB - 1) / PGL_NB * PGL_NB;
+enum { R_LPIV = 13, R_LOUT = 14 };
+
+struct PgLoops {   // the caller's loops_dev, in doubles
+  double *gamma, *gsum, *C, *winv, *span, *s, *d, *part, *pf, *S, *F;
+  int64_t sp, nbk, nbc, nbl;
+  size_t total;
+  PgLoops(double* base, int64_t N, int64_t L) {
+    nbc = (N - 1 + PG_B - 1) / PG_B;
+    nbl = (L + PG_B - 1) / PG_B;
+    sp = (6 * L + PGL_NB - 1) / PGL_NB * PGL_NB;
+    nbk = sp / PGL_NB;
+    size_t o = 0;
+    auto take = [&](size_t n) { double* q_ = base ? base + o : nullptr; o += (n + 1) & ~(size_t)1; return q_; };
+    gamma = take(36 * N);       // Gamma[k] = sum_{m < k} G_m
+    C = take(36 * L);           // C_a = B_a Ad(T_j^-1), 0 for an edge that is left out
+    winv = take(36 * L);        // (w_a Omega_a)^-1, the identity for an edge that is left out
+    span = take(4 * L);         // lo, hi, sigma, live
+    S = take((size_t)sp * sp);
+    F = take((size_t)sp * sp);  // the lower Cholesky factor of S, zero above the diagonal
+    gsum = take(72 * nbc);      // the scan's block totals and offsets
+    s = take(6 * N);
+    d = take(sp);
+    part = take(2 * nbl);
+    pf = take(nbk);
+    total = o;
+  }
+};
+
+// the Hillis-Steele scan of pg_scan_local_kernel over one value of six per thread; the result is sh[returned][threadIdx.x]
+__device__ __forceinline__ int pgl_block_scan6(double (*sh)[PG_B][6], const double* v) {
+  int cur = 0;
+  st6(sh[0][threadIdx.x], v);
+  __syncthreads();
+  for (int d = 1; d < PG_B; d <<= 1) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      const double a = sh[cur][threadIdx.x][k];
+      sh[cur ^ 1][threadIdx.x][k] = (int)threadIdx.x >= d ? a + sh[cur][threadIdx.x - d][k] : a;
+    }
+    cur ^= 1;
+    __syncthreads();
+  }
+  return cur;
+}
+
+// Gamma, launch 1, grid (blocks, 6): row blockIdx.y of the 6 x 6 blocks G_m, scanned inside the block; Gamma[m + 1] gets the inclusive sum
+__global__ __launch_bounds__(PG_B) void pgl_gamma_local_kernel(int n, const double* __restrict__ chain, double* __restrict__ gamma,
+                                                               double* __restrict__ bsum) {
+  __shared__ double sh[2][PG_B][6];
+  const int m = blockIdx.x * PG_B + threadIdx.x, row = blockIdx.y;
+  double v[6] = {0, 0, 0, 0, 0, 0};
+  if (m < n) ld6(chain + (size_t)m * 72 + row * 6, v);
+  const int cur = pgl_block_scan6(sh, v);
+  if (m < n) st6(gamma + (size_t)(m + 1) * 36 + row * 6, sh[cur][threadIdx.x]);
+  const int last = min(n - (int)blockIdx.x * PG_B, PG_B) - 1;
+  if ((int)threadIdx.x == last) st6(bsum + ((size_t)row * gridDim.x + blockIdx.x) * 6, sh[cur][threadIdx.x]);
+}
+// launch 2, ONE workgroup of 36 lanes: the totals of the blocks before b, added in block order
+__global__ void pgl_gamma_sums_kernel(int nb, const double* __restrict__ bsum, double* __restrict__ off) {
+  const int k = threadIdx.x;
+  if (k >= 36) return;
+  const int row = k / 6, q = k % 6;
+  double tot = 0.0;
+  for (int b = 0; b < nb; ++b) {
+    const size_t at = ((size_t)row * nb + b) * 6 + q;
+    off[at] = tot;
+    tot = b ? tot + bsum[at] : bsum[at];
+  }
+}
+// launch 3: the block offset added; Gamma[0] = 0
+__global__ __launch_bounds__(PG_B) void pgl_gamma_add_kernel(int n, const double* __restrict__ off, double* __restrict__ gamma) {
+  const int m = blockIdx.x * PG_B + threadIdx.x, row = blockIdx.y;
+  if (m == 0) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) gamma[row * 6 + k] = 0.0;
+  }
+  if (m >= n || blockIdx.x == 0) return;
+  double* g = gamma + (size_t)(m + 1) * 36 + row * 6;
+  const double* o = off + ((size_t)row * gridDim.x + blockIdx.x) * 6;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) g[k] = g[k] + o[k];
+}
+
+// one loop edge a = edge N - 1 + a per thread: C_a = B_a Ad(T_j^-1), (w_a Omega_a)^-1, lo, hi, sigma.  An edge of weight 0 is left out
+// (zero C, identity block) and counted; an edge whose w Omega has no Cholesky factor is left out too and counted as a failed pivot
+__global__ __launch_bounds__(PG_B) void pgl_edge_kernel(const double* __restrict__ poses, int N, const int32_t* __restrict__ ij,
+                                                        const double* __restrict__ info, const double* __restrict__ weight,
+                                                        const double* __restrict__ jac, int L, double* __restrict__ C,
+                                                        double* __restrict__ winv, double* __restrict__ span, double* __restrict__ part) {
+  __shared__ double sh[PG_B];
+  const int a = blockIdx.x * PG_B + threadIdx.x;
+  double fail = 0.0, out = 0.0;
+  if (a < L) {
+    const size_t e = (size_t)(N - 1) + a;
+    const int i = ij[2 * e], j = ij[2 * e + 1];
+    const double w = weight[e];
+    bool live = w > 0.0 && i >= 0 && i < N && j >= 0 && j < N && i != j;
+    double Ca[36], Wi[36];
+#pragma unroll
+    for (int q = 0; q < 36; ++q) {
+      Ca[q] = 0.0;
+      Wi[q] = (q % 7 == 0) ? 1.0 : 0.0;
+    }
+    if (!live) out = 1.0;
+    if (live) {
+      double Wm[36];
+#pragma unroll
+      for (int q = 0; q < 36; ++q) Wm[q] = w * info[e * 36 + q];
+      if (!pg_chol_inv(Wm, Wi)) {
+        fail = 1.0;
+        live = false;
+      }
+    }
+    if (live) {
+      double R[9], t[3], Rt[9], tt[3], Ad[36], Bm[36];
+      pg_load_pose(poses + (size_t)j * 16, R, t);
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
+#pragma unroll
+        for (int q = 0; q < 3; ++q) Rt[p * 3 + q] = R[q * 3 + p];
+      m3_tvec(R, t, tt);
+#pragma unroll
+      for (int p = 0; p < 3; ++p) tt[p] = -tt[p];
+      pg_adjoint(Rt, tt, Ad);
+      ld36(jac + e * 72 + 36, Bm);
+      m6_mul(Bm, Ad, Ca);
+    }
+    st36(C + (size_t)a * 36, Ca);
+    st36(winv + (size_t)a * 36, Wi);
+    span[4 * a] = live ? (double)min(i, j) : 0.0;
+    span[4 * a + 1] = live ? (double)max(i, j) : 0.0;
+    span[4 * a + 2] = live ? (j > i ? 1.0 : -1.0) : 0.0;
+    span[4 * a + 3] = live ? 1.0 : 0.0;
+  }
+  const double f = pg_wg_sum(fail, sh);
+  const double o = pg_wg_sum(out, sh);
+  if (threadIdx.x == 0) {
+    part[2 * blockIdx.x] = f;
+    part[2 * blockIdx.x + 1] = o;
+  }
+}
+
+// one 6 x 6 block (a, b), a <= b, per thread, written to (a, b) and transposed to (b, a):
+// S_ab = delta_ab (w_a Omega_a)^-1 + sigma_a sigma_b (C_a (Gamma[min hi] - Gamma[max lo])) C_b' where the spans overlap.
+// F gets the lower triangle of the same values and zeros above the diagonal.
+__global__ __launch_bounds__(PG_B) void pgl_assemble_kernel(int L, int sp, const double* __restrict__ gamma, const double* __restrict__ C,
+                                                            const double* __restrict__ winv, const double* __restrict__ span,
+                                                            double* __restrict__ S, double* __restrict__ F) {
+  const int a = blockIdx.y, b = blockIdx.x * PG_B + threadIdx.x;
+  if (b >= L || b < a) return;
+  double out[36];
+#pragma unroll
+  for (int q = 0; q < 36; ++q) out[q] = 0.0;
+  if (span[4 * a + 3] != 0.0 && span[4 * b + 3] != 0.0) {
+    const int lo = (int)fmax(span[4 * a], span[4 * b]), hi = (int)fmin(span[4 * a + 1], span[4 * b + 1]);
+    if (lo < hi) {
+      double M[36], T[36];
+      const double* gh = gamma + (size_t)hi * 36;
+      const double* gl = gamma + (size_t)lo * 36;
+#pragma unroll
+      for (int q = 0; q < 36; ++q) M[q] = gh[q] - gl[q];
+      m6_mul(C + (size_t)a * 36, M, T);
+      m6_mult(T, C + (size_t)b * 36, out);
+      const double sg = span[4 * a + 2] * span[4 * b + 2];
+#pragma unroll
+      for (int q = 0; q < 36; ++q) out[q] = sg * out[q];
+    }
+  }
+  if (a == b) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = i + 1; j < 6; ++j) out[i * 6 + j] = out[j * 6 + i];
+#pragma unroll
+    for (int q = 0; q < 36; ++q) out[q] = winv[(size_t)a * 36 + q] + out[q];
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i)
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      const size_t up = (size_t)(6 * a + i) * sp + 6 * b + j, low = (size_t)(6 * b + j) * sp + 6 * a + i;
+      const double v = out[i * 6 + j];
+      S[up] = v;
+      S[low] = v;
+      if (a != b) {
+        F[up] = 0.0;
+        F[low] = v;
+      } else {
+        F[up] = i >= j ? v : 0.0;
+      }
+    }
+}
+// the padding rows and columns 6 L .. sp - 1: an identity diagonal
+__global__ __launch_bounds__(PG_B) void pgl_pad_kernel(int n6, int sp, double* __restrict__ S, double* __restrict__ F) {
+  const int64_t t = (int64_t)blockIdx.x * PG_B + threadIdx.x;
+  if (t >= (int64_t)(sp - n6) * sp) return;
+  const int row = n6 + (int)(t / sp), c = (int)(t % sp);
+  const double v = c == row ? 1.0 : 0.0;
+  S[(size_t)row * sp + c] = v;
+  S[(size_t)c * sp + row] = v;
+  F[(size_t)row * sp + c] = v;
+  F[(size_t)c * sp + row] = v;
+}
+
+// the factorization, stage 1 of block column k, ONE wave: the Cholesky factor of the diagonal block, column by column as pg_chol_inv
+// takes it (d = A_cc - sum_{t<c} L_ct^2 and v = A_rc - sum_{t<c} L_rt L_ct in the order of t, L_rc = v / sqrt d).  A pivot that is not
+// positive and finite is counted in pf[k] and replaced by 1
+__global__ __launch_bounds__(64) void pgl_panel_kernel(int sp, int k, double* __restrict__ F, double* __restrict__ pf) {
+  __shared__ double A[PGL_NB][PGL_NB + 1];
+  const int lane = threadIdx.x;
+  const size_t base = (size_t)k * PGL_NB;
+  for (int t = lane; t < PGL_NB * PGL_NB; t += 64) {
+    const int r = t / PGL_NB, c = t % PGL_NB;
+    A[r][c] = F[(base + r) * sp + base + c];
+  }
+  __syncthreads();
+  double fails = 0.0;
+  for (int c = 0; c < PGL_NB; ++c) {
+    double d = A[c][c];
+    for (int t = 0; t < c; ++t) d = d - A[c][t] * A[c][t];
+    const bool ok = d > 0.0 && d * 0.0 == 0.0;
+    if (!ok) fails += 1.0;
+    const double l = sqrt(ok ? d : 1.0);
+    double v = 0.0;
+    if (lane > c && lane < PGL_NB) {
+      v = A[lane][c];
+      for (int t = 0; t < c; ++t) v = v - A[lane][t] * A[c][t];
+      v = v / l;
+    }
+    __syncthreads();
+    if (lane > c && lane < PGL_NB) A[lane][c] = v;
+    if (lane == c) A[c][c] = l;
+    __syncthreads();
+  }
+  for (int t = lane; t < PGL_NB * PGL_NB; t += 64) {
+    const int r = t / PGL_NB, c = t % PGL_NB;
+    if (r >= c) F[(base + r) * sp + base + c] = A[r][c];
+  }
+  if (lane == 0) pf[k] = fails;
+}
+// stage 2, one row below the diagonal block per thread: L_rk = A_rk L_kk^-T by forward substitution in column order
+__global__ __launch_bounds__(PG_B) void pgl_trsm_kernel(int sp, int k, double* __restrict__ F) {
+  __shared__ double Lk[PGL_NB][PGL_NB + 1];
+  const size_t base = (size_t)k * PGL_NB;
+  for (int t = threadIdx.x; t < PGL_NB * PGL_NB; t += PG_B) {
+    const int r = t / PGL_NB, c = t % PGL_NB;
+    Lk[r][c] = F[(base + r) * sp + base + c];
+  }
+  __syncthreads();
+  const size_t r = base + PGL_NB + (size_t)blockIdx.x * PG_B + threadIdx.x;
+  if (r >= (size_t)sp) return;
+  double* p = F + r * sp + base;
+  double x[PGL_NB];
+#pragma unroll
+  for (int c = 0; c < PGL_NB; ++c) {
+    double v = p[c];
+#pragma unroll
+    for (int t = 0; t < c; ++t) v = v - x[t] * Lk[c][t];
+    x[c] = v / Lk[c][c];
+  }
+#pragma unroll
+  for (int c = 0; c < PGL_NB; ++c) p[c] = x[c];
+}
+// stage 3, one 48 x 48 tile (ti >= tj) of the trailing matrix per workgroup, 3 x 3 entries per thread:
+// A_rc <- A_rc - (sum_t L_rt L_ct), the sum in the order of t, then one subtraction
+__global__ __launch_bounds__(PG_B) void pgl_syrk_kernel(int sp, int k, double* __restrict__ F) {
+  const int ti = blockIdx.y, tj = blockIdx.x;
+  if (tj > ti) return;
+  __shared__ double A[PGL_NB][PGL_NB + 1], B[PGL_NB][PGL_NB + 1];
+  const size_t p0 = (size_t)k * PGL_NB, r0 = p0 + (size_t)(1 + ti) * PGL_NB, c0 = p0 + (size_t)(1 + tj) * PGL_NB;
+  for (int t = threadIdx.x; t < PGL_NB * PGL_NB; t += PG_B) {
+    const int r = t / PGL_NB, c = t % PGL_NB;
+    A[r][c] = F[(r0 + r) * sp + p0 + c];
+    B[r][c] = F[(c0 + r) * sp + p0 + c];
+  }
+  __syncthreads();
+  const int tr = threadIdx.x / 16 * 3, tc = threadIdx.x % 16 * 3;
+  double acc[3][3];
+#pragma unroll
+  for (int u = 0; u < 3; ++u)
+#pragma unroll
+    for (int v = 0; v < 3; ++v) acc[u][v] = A[tr + u][0] * B[tc + v][0];
+#pragma unroll 4
+  for (int t = 1; t < PGL_NB; ++t) {
+    double av[3], bv[3];
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+      av[u] = A[tr + u][t];
+      bv[u] = B[tc + u][t];
+    }
+#pragma unroll
+    for (int u = 0; u < 3; ++u)
+#pragma unroll
+      for (int v = 0; v < 3; ++v) acc[u][v] = acc[u][v] + av[u] * bv[v];
+  }
+#pragma unroll
+  for (int u = 0; u < 3; ++u)
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+      if (ti == tj && tc + v > tr + u) continue;
+      double* q = F + (r0 + tr + u) * sp + c0 + tc + v;
+      *q = *q - acc[u][v];
+    }
+}
+// ONE thread: record [13] and [14], every sum in index order
+__global__ void pgl_record_kernel(const double* part, int nbl, const double* pf, int nbk, double* rec) {
+  if (threadIdx.x != 0) return;
+  double fail = 0.0, out = 0.0;
+  for (int b = 0; b < nbl; ++b) {
+    fail = fail + part[2 * b];
+    out = out + part[2 * b + 1];
+  }
+  for (int k = 0; k < nbk; ++k) fail = fail + pf[k];
+  rec[R_LPIV] = fail;
+  rec[R_LOUT] = out;
+}
+
+__global__ void pgl_solve_reset_kernel(double* rec) {
+  if (threadIdx.x != 0) return;
+  rec[R_ITER] = 0.0;
+  rec[R_REL] = 1.0;
+  rec[R_CONV] = 0.0;
+  rec[R_BREAK] = (rec[R_CHOL] != 0.0 || rec[R_LPIV] != 0.0) ? 1.0 : 0.0;
+  rec[R_RZ] = rec[R_RZ0] = rec[R_ALPHA] = rec[R_BETA] = 0.0;
+}
+
+// launch 3 of the suffix scan: s[m] = the scan with its block offset, kept for later, and out[m] = G_m s[m]
+__global__ __launch_bounds__(PG_B) void pgl_suffix_apply_kernel(int n, const double* __restrict__ local, const double* __restrict__ off,
+                                                                const double* __restrict__ chain, double* __restrict__ s_out,
+                                                                double* __restrict__ out, const double* rec) {
+  if (pg_stopped(rec)) return;
+  const int l = blockIdx.x * PG_B + threadIdx.x;
+  if (l >= n) return;
+  const int m = n - 1 - l;
+  double v[6], M[36], o[6];
+  ld6(local + (size_t)m * 6, v);
+  if (blockIdx.x > 0) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) v[k] = v[k] + off[(size_t)blockIdx.x * 6 + k];
+  }
+  st6(s_out + (size_t)m * 6, v);
+  ld36(chain + (size_t)m * 72, M);
+  m6_vec(M, v, o);
+  st6(out + (size_t)m * 6, o);
+}
+
+// c[m] of the forward scan whose launch 3 has not run: the block-local value and the block's offset
+__device__ __forceinline__ void pgl_prefix_at(const double* local, const double* off, int m, double* c) {
+  ld6(local + (size_t)m * 6, c);
+  const int b = m / PG_B;
+  if (b > 0) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) c[k] = c[k] + off[(size_t)b * 6 + k];
+  }
+}
+
+// ONE workgroup: v_a = sigma_a C_a (c[hi_a - 1] - c[lo_a - 1]), then d = S^-1 v by L y = v and L' d = y.  Block column by block
+// column: the diagonal block is solved in one wave (one subtraction per column, in column order: forward ascending, backward
+// descending), then every remaining entry takes ONE subtraction of a 48-term sum in index order.  One launch: per block column a
+// launch of its own measured slower up to 6 L = 1536 (profiles/pose_graph_loops.json)
+__global__ __launch_bounds__(PGL_TS) void pgl_solve_kernel(int L, int sp, const double* __restrict__ local, const double* __restrict__ off,
+                                                           const double* __restrict__ C, const double* __restrict__ span,
+                                                           const double* __restrict__ F, double* __restrict__ d, const double* rec) {
+  if (pg_stopped(rec)) return;
+  __shared__ double x[PGL_MAX_SP];
+  __shared__ double D[PGL_NB][PGL_NB + 1];
+  const int tid = threadIdx.x;
+  for (int idx = tid; idx < sp; idx += PGL_TS) {
+    double v = 0.0;
+    const int a = idx / 6, q = idx % 6;
+    if (a < L && span[4 * a + 3] != 0.0) {
+      const int lo = (int)span[4 * a], hi = (int)span[4 * a + 1];
+      double ch[6], cl[6] = {0, 0, 0, 0, 0, 0};
+      pgl_prefix_at(local, off, hi - 1, ch);
+      if (lo > 0) pgl_prefix_at(local, off, lo - 1, cl);
+      const double* cr = C + (size_t)a * 36 + q * 6;
+      double s = cr[0] * (ch[0] - cl[0]);
+#pragma unroll
+      for (int k = 1; k < 6; ++k) s = s + cr[k] * (ch[k] - cl[k]);
+      v = span[4 * a + 2] * s;
+    }
+    x[idx] = v;
+  }
+  __syncthreads();
+  const int nbk = sp / PGL_NB;
+  for (int k = 0; k < nbk; ++k) {
+    const size_t base = (size_t)k * PGL_NB;
+    for (int t = tid; t < PGL_NB * PGL_NB; t += PGL_TS) {
+      const int r = t / PGL_NB, c = t % PGL_NB;
+      D[r][c] = F[(base + r) * sp + base + c];
+    }
+    __syncthreads();
+    if (tid < 64) {
+      double xv = tid < PGL_NB ? x[base + tid] : 0.0;
+      for (int c = 0; c < PGL_NB; ++c) {
+        const double y = __shfl(xv, c) / D[c][c];
+        if (tid == c) xv = y;
+        else if (tid > c && tid < PGL_NB) xv = xv - D[tid][c] * y;
+      }
+      if (tid < PGL_NB) x[base + tid] = xv;
+    }
+    __syncthreads();
+    for (size_t r = base + PGL_NB + tid; r < (size_t)sp; r += PGL_TS) {
+      const double* p = F + r * sp + base;
+      double s = p[0] * x[base];
+#pragma unroll 8
+      for (int c = 1; c < PGL_NB; ++c) s = s + p[c] * x[base + c];
+      x[r] = x[r] - s;
+    }
+    __syncthreads();
+  }
+  for (int k = nbk - 1; k >= 0; --k) {
+    const size_t base = (size_t)k * PGL_NB;
+    for (int t = tid; t < PGL_NB * PGL_NB; t += PGL_TS) {
+      const int r = t / PGL_NB, c = t % PGL_NB;
+      D[r][c] = F[(base + r) * sp + base + c];
+    }
+    __syncthreads();
+    if (tid < 64) {
+      double xv = tid < PGL_NB ? x[base + tid] : 0.0;
+      for (int c = PGL_NB - 1; c >= 0; --c) {
+        const double y = __shfl(xv, c) / D[c][c];
+        if (tid == c) xv = y;
+        else if (tid < c) xv = xv - D[c][tid] * y;
+      }
+      if (tid < PGL_NB) x[base + tid] = xv;
+    }
+    __syncthreads();
+    for (size_t r = tid; r < base; r += PGL_TS) {
+      const double* p = F + base * sp + r;
+      double s = p[0] * x[base];
+#pragma unroll 8
+      for (int c = 1; c < PGL_NB; ++c) s = s + p[(size_t)c * sp] * x[base + c];
+      x[r] = x[r] - s;
+    }
+    __syncthreads();
+  }
+  for (int idx = tid; idx < sp; idx += PGL_TS) d[idx] = x[idx];
+}
+
+// launch 1 of the difference scan: chain edge m takes + sigma_a C_a' d_a for the loop edges whose lo is node m and - for those whose
+// hi is node m, over node m's incidence list in list order, then the block-local scan
+__global__ __launch_bounds__(PG_B) void pgl_diff_local_kernel(int n, int N, int E, int L, const int32_t* __restrict__ ptr,
+                                                              const int32_t* __restrict__ lst, const double* __restrict__ C,
+                                                              const double* __restrict__ span, const double* __restrict__ d,
+                                                              double* __restrict__ local, double* __restrict__ bsum, const double* rec) {
+  if (pg_stopped(rec)) return;
+  __shared__ double sh[2][PG_B][6];
+  const int m = blockIdx.x * PG_B + threadIdx.x;
+  double v[6] = {0, 0, 0, 0, 0, 0};
+  if (m < n) {
+    int b = ptr[m], en = ptr[m + 1];
+    b = b < 0 ? 0 : b;
+    en = en > 2 * E ? 2 * E : en;
+    for (int k = b; k < en; ++k) {
+      const int a = lst[k] - (N - 1);
+      if (a < 0 || a >= L || span[4 * a + 3] == 0.0) continue;
+      double Ca[36], da[6], t6[6];
+      ld36(C + (size_t)a * 36, Ca);
+      ld6(d + (size_t)a * 6, da);
+      m6_tvec(Ca, da, t6);
+      const double sg = span[4 * a + 2];
+      if ((int)span[4 * a] == m) {
+#pragma unroll
+        for (int q = 0; q < 6; ++q) v[q] = v[q] + sg * t6[q];
+      } else if ((int)span[4 * a + 1] == m) {
+#pragma unroll
+        for (int q = 0; q < 6; ++q) v[q] = v[q] - sg * t6[q];
+      }
+    }
+  }
+  const int cur = pgl_block_scan6(sh, v);
+  if (m < n) st6(local + (size_t)m * 6, sh[cur][threadIdx.x]);
+  const int last = min(n - (int)blockIdx.x * PG_B, PG_B) - 1;
+  if ((int)threadIdx.x == last) st6(bsum + (size_t)blockIdx.x * 6, sh[cur][threadIdx.x]);
+}
+// launch 3 of the difference scan: e[m] = the scan with its block offset, out[m] = G_m (s[m] - e[m])
+__global__ __launch_bounds__(PG_B) void pgl_diff_apply_kernel(int n, const double* __restrict__ local, const double* __restrict__ off,
+                                                              const double* __restrict__ s, const double* __restrict__ chain,
+                                                              double* __restrict__ out, const double* rec) {
+  if (pg_stopped(rec)) return;
+  const int m = blockIdx.x * PG_B + threadIdx.x;
+  if (m >= n) return;
+  double e[6], sv[6], M[36], o[6];
+  pgl_prefix_at(local, off, m, e);
+  ld6(s + (size_t)m * 6, sv);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) sv[k] = sv[k] - e[k];
+  ld36(chain + (size_t)m * 72, M);
+  m6_vec(M, sv, o);
+  st6(out + (size_t)m * 6, o);
+}
+
+// twelve launches: out = H^-1 in (undamped) over the nodes 1 .. N - 1; row 0 of `out` is not written
+int pg_loops_apply(int N, int E, int L, const int32_t* ptr, const int32_t* lst, const double* chain, const PgLoops& lp, const double* in,
+                   double* out, const PgWs& w, const double* r_for_dot, double* part, const double* rec, hipStream_t stream) {
+  const int n = N - 1;
+  const int nb = (n + PG_B - 1) / PG_B;
+  double* off = w.bsum + (size_t)6 * nb;
+  pg_scan_local_kernel<true, true><<<nb, PG_B, 0, stream>>>(n, in, chain, w.sa, w.bsum, rec);
+  pg_scan_sums_kernel<<<1, 64, 0, stream>>>(nb, w.bsum, off, rec);
+  pgl_suffix_apply_kernel<<<nb, PG_B, 0, stream>>>(n, w.sa, off, chain, lp.s, w.sb, rec);
+  pg_scan_local_kernel<false, false><<<nb, PG_B, 0, stream>>>(n, w.sb, chain, w.sa, w.bsum, rec);
+  pg_scan_sums_kernel<<<1, 64, 0, stream>>>(nb, w.bsum, off, rec);
+  pgl_solve_kernel<<<1, PGL_TS, 0, stream>>>(L, (int)lp.sp, w.sa, off, lp.C, lp.span, lp.F, lp.d, rec);
+  pgl_diff_local_kernel<<<nb, PG_B, 0, stream>>>(n, N, E, L, ptr, lst, lp.C, lp.span, lp.d, w.sa, w.bsum, rec);
+  pg_scan_sums_kernel<<<1, 64, 0, stream>>>(nb, w.bsum, off, rec);
+  pgl_diff_apply_kernel<<<nb, PG_B, 0, stream>>>(n, w.sa, off, lp.s, chain, w.sb, rec);
+  pg_scan_local_kernel<false, false><<<nb, PG_B, 0, stream>>>(n, w.sb, chain, w.sa, w.bsum, rec);
+  pg_scan_sums_kernel<<<1, 64, 0, stream>>>(nb, w.bsum, off, rec);
+  pg_scan_apply_kernel<false, true><<<nb, PG_B, 0, stream>>>(n, w.sa, off, chain, out, r_for_dot, part, rec);
+  OVN_HIP_CHECK(hipGetLastError());
+  return OVN_OK;
+}
+
 }  // namespace
 
 // ---- C ABI --------------------------------------------------------------------------------------------------------------------------------
@@ -1114,6 +1638,131 @@ int ovn_pose_graph_retract(ovn_ctx* ctx, void* stream, const double* poses_dev, 
   pg_dmax_kernel<<<1, PG_B, 0, s>>>(w.part_n, nbn, record_dev);
   OVN_HIP_CHECK(hipGetLastError());
   return OVN_OK;
+}
+
+// ---- the chain-plus-loops inverse -------------------------------------------------------------------------------------------------------
+#define PGL_REQUIRE_SHAPE(what)                                                                                                          \
+  OVN_REQUIRE(n_nodes >= 2 && n_nodes <= OVN_POSE_GRAPH_MAX_NODES && n_loops >= 1 && n_loops <= OVN_POSE_GRAPH_MAX_LOOPS &&              \
+                  (int64_t)n_edges == (int64_t)n_nodes - 1 + n_loops, OVN_ERR_ARG,                                                       \
+              what ": %d nodes (2..%d), %d loop edges (1..%d), %d edges (must be nodes - 1 + loop edges)", n_nodes,                      \
+              OVN_POSE_GRAPH_MAX_NODES, n_loops, OVN_POSE_GRAPH_MAX_LOOPS, n_edges)
+
+int64_t ovn_pose_graph_loops_bytes(int64_t n_nodes, int64_t n_loops) {
+  if (n_nodes < 2 || n_nodes > OVN_POSE_GRAPH_MAX_NODES || n_loops < 1 || n_loops > OVN_POSE_GRAPH_MAX_LOOPS) return 0;
+  return (int64_t)(PgLoops(nullptr, n_nodes, n_loops).total * sizeof(double));
+}
+
+int ovn_pose_graph_loops_layout(int64_t n_nodes, int64_t n_loops, int64_t* out) {
+  OVN_REQUIRE(out != nullptr, OVN_ERR_ARG, "ovn_pose_graph_loops_layout: out is NULL");
+  OVN_REQUIRE(ovn_pose_graph_loops_bytes(n_nodes, n_loops) > 0, OVN_ERR_ARG, "ovn_pose_graph_loops_layout: %lld nodes, %lld loop edges",
+              (long long)n_nodes, (long long)n_loops);
+  double* const base = reinterpret_cast<double*>(sizeof(double));   // never dereferenced: offsets only
+  PgLoops lp(base, n_nodes, n_loops);
+  out[0] = PGL_NB;
+  out[1] = lp.sp;
+  out[2] = lp.gamma - base;
+  out[3] = lp.C - base;
+  out[4] = lp.winv - base;
+  out[5] = lp.span - base;
+  out[6] = lp.S - base;
+  out[7] = lp.F - base;
+  return OVN_OK;
+}
+
+int ovn_pose_graph_loops_prepare(ovn_ctx* ctx, void* stream, const double* poses_dev, int n_nodes, const int32_t* edge_ij_dev,
+                                 const double* info_dev, const double* weight_dev, const double* jac_dev, int n_edges, int n_loops,
+                                 const double* chain_dev, int stages, double* loops_dev, double* record_dev) {
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_pose_graph_loops_prepare: ctx is NULL");
+  PGL_REQUIRE_SHAPE("ovn_pose_graph_loops_prepare");
+  OVN_REQUIRE(stages >= 1 && stages <= OVN_POSE_GRAPH_LOOPS_ALL, OVN_ERR_ARG, "ovn_pose_graph_loops_prepare: stages %d (a sum of 1 = scan, "
+              "2 = assembly, 4 = factorization)", stages);
+  OVN_REQUIRE(poses_dev && edge_ij_dev && info_dev && weight_dev && jac_dev && chain_dev && loops_dev && record_dev, OVN_ERR_ARG,
+              "ovn_pose_graph_loops_prepare: NULL buffer");
+  OVN_ON_DEVICE(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  PgLoops lp(loops_dev, n_nodes, n_loops);
+  const int n = n_nodes - 1, nbc = (int)lp.nbc, nbl = (int)lp.nbl, sp = (int)lp.sp, nbk = (int)lp.nbk, n6 = 6 * n_loops;
+  double* goff = lp.gsum + (size_t)36 * nbc;
+  if (stages & OVN_POSE_GRAPH_LOOPS_SCAN) {
+    pgl_gamma_local_kernel<<<dim3(nbc, 6), PG_B, 0, s>>>(n, chain_dev, lp.gamma, lp.gsum);
+    pgl_gamma_sums_kernel<<<1, 64, 0, s>>>(nbc, lp.gsum, goff);
+    pgl_gamma_add_kernel<<<dim3(nbc, 6), PG_B, 0, s>>>(n, goff, lp.gamma);
+  }
+  if (stages & OVN_POSE_GRAPH_LOOPS_ASSEMBLE) {
+    pgl_edge_kernel<<<nbl, PG_B, 0, s>>>(poses_dev, n_nodes, edge_ij_dev, info_dev, weight_dev, jac_dev, n_loops, lp.C, lp.winv, lp.span,
+                                         lp.part);
+    pgl_assemble_kernel<<<dim3(nbl, n_loops), PG_B, 0, s>>>(n_loops, sp, lp.gamma, lp.C, lp.winv, lp.span, lp.S, lp.F);
+    if (sp > n6) pgl_pad_kernel<<<(int)(((int64_t)(sp - n6) * sp + PG_B - 1) / PG_B), PG_B, 0, s>>>(n6, sp, lp.S, lp.F);
+  }
+  for (int k = 0; k < ((stages & OVN_POSE_GRAPH_LOOPS_FACTOR) ? nbk : 0); ++k) {
+    pgl_panel_kernel<<<1, 64, 0, s>>>(sp, k, lp.F, lp.pf);
+    const int rest = nbk - 1 - k;
+    if (rest > 0) {
+      pgl_trsm_kernel<<<(rest * PGL_NB + PG_B - 1) / PG_B, PG_B, 0, s>>>(sp, k, lp.F);
+      pgl_syrk_kernel<<<dim3(rest, rest), PG_B, 0, s>>>(sp, k, lp.F);
+    }
+  }
+  if (stages & OVN_POSE_GRAPH_LOOPS_FACTOR) pgl_record_kernel<<<1, 64, 0, s>>>(lp.part, nbl, lp.pf, nbk, record_dev);
+  OVN_HIP_CHECK(hipGetLastError());
+  return OVN_OK;
+}
+
+int ovn_pose_graph_solve_loops(ovn_ctx* ctx, void* stream, const uint8_t* fixed_dev, int n_nodes, const int32_t* edge_ij_dev, int n_edges,
+                               const int32_t* node_ptr_dev, const int32_t* node_edge_dev, const double* blocks_dev, const double* grad_dev,
+                               const double* diag_dev, const double* dinv_dev, const double* chain_dev, double* loops_dev, int n_loops,
+                               double lambda, double rtol, int first_iteration, int iterations, double* delta_dev, double* ws_dev,
+                               double* record_dev) {
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_pose_graph_solve_loops: ctx is NULL");
+  PGL_REQUIRE_SHAPE("ovn_pose_graph_solve_loops");
+  OVN_REQUIRE(pg_finite(lambda) && lambda >= 0.0, OVN_ERR_ARG, "ovn_pose_graph_solve_loops: lambda must be finite and >= 0");
+  OVN_REQUIRE(pg_finite(rtol) && rtol >= 0.0, OVN_ERR_ARG, "ovn_pose_graph_solve_loops: rtol must be finite and >= 0");
+  OVN_REQUIRE(first_iteration >= 0 && iterations >= 0 && iterations <= OVN_POSE_GRAPH_MAX_CHUNK, OVN_ERR_ARG,
+              "ovn_pose_graph_solve_loops: first_iteration %d (>= 0), iterations %d (0..%d)", first_iteration, iterations,
+              OVN_POSE_GRAPH_MAX_CHUNK);
+  OVN_REQUIRE(fixed_dev && edge_ij_dev && node_ptr_dev && node_edge_dev && blocks_dev && grad_dev && diag_dev && dinv_dev && chain_dev &&
+                  loops_dev && delta_dev && ws_dev && record_dev, OVN_ERR_ARG, "ovn_pose_graph_solve_loops: NULL buffer");
+  OVN_ON_DEVICE(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  PgWs w(ws_dev, n_nodes, n_edges);
+  PgLoops lp(loops_dev, n_nodes, n_loops);
+  const int nbn = (n_nodes + PG_B - 1) / PG_B, nbc = (n_nodes - 1 + PG_B - 1) / PG_B;
+  double* part = w.part_n;
+  if (first_iteration == 0) {
+    pgl_solve_reset_kernel<<<1, 64, 0, s>>>(record_dev);
+    pg_solve_init_kernel<<<nbn, PG_B, 0, s>>>(fixed_dev, n_nodes, grad_dev, nullptr, 1.0, delta_dev, w.r, w.z, w.p[0], w.p[1], part,
+                                              record_dev);
+    int rc = pg_loops_apply(n_nodes, n_edges, n_loops, node_ptr_dev, node_edge_dev, chain_dev, lp, w.r, w.z, w, w.r, part, record_dev, s);
+    if (rc) return rc;
+    pg_solve_rz0_kernel<<<1, PG_B, 0, s>>>(part, nbc, record_dev);
+  }
+  for (int k = 0; k < iterations; ++k) {
+    const int cur = (first_iteration + k) & 1;
+    pg_matvec_kernel<<<nbn, PG_B, 0, s>>>(fixed_dev, n_nodes, edge_ij_dev, n_edges, node_ptr_dev, node_edge_dev, blocks_dev, diag_dev, lambda,
+                                          w.z, w.p[cur], w.p[cur ^ 1], w.q, part, record_dev);
+    pg_alpha_kernel<<<1, PG_B, 0, s>>>(part, nbn, record_dev);
+    pg_update_kernel<<<nbn, PG_B, 0, s>>>(n_nodes, w.p[cur ^ 1], w.q, nullptr, 1.0, delta_dev, w.r, w.z, part, record_dev);
+    int rc = pg_loops_apply(n_nodes, n_edges, n_loops, node_ptr_dev, node_edge_dev, chain_dev, lp, w.r, w.z, w, w.r, part, record_dev, s);
+    if (rc) return rc;
+    pg_beta_kernel<<<1, PG_B, 0, s>>>(part, nbc, rtol, record_dev);
+  }
+  OVN_HIP_CHECK(hipGetLastError());
+  return OVN_OK;
+}
+
+int ovn_pose_graph_precondition_loops(ovn_ctx* ctx, void* stream, int n_nodes, int n_edges, int n_loops, const int32_t* node_ptr_dev,
+                                      const int32_t* node_edge_dev, const double* chain_dev, double* loops_dev, const double* in_dev,
+                                      double* out_dev, double* ws_dev) {
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_pose_graph_precondition_loops: ctx is NULL");
+  PGL_REQUIRE_SHAPE("ovn_pose_graph_precondition_loops");
+  OVN_REQUIRE(node_ptr_dev && node_edge_dev && chain_dev && loops_dev && in_dev && out_dev && ws_dev, OVN_ERR_ARG,
+              "ovn_pose_graph_precondition_loops: NULL buffer");
+  OVN_ON_DEVICE(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  OVN_HIP_CHECK(hipMemsetAsync(out_dev, 0, 6 * sizeof(double), s));   // the fixed node 0
+  PgWs w(ws_dev, n_nodes, 0);
+  PgLoops lp(loops_dev, n_nodes, n_loops);
+  return pg_loops_apply(n_nodes, n_edges, n_loops, node_ptr_dev, node_edge_dev, chain_dev, lp, in_dev, out_dev, w, nullptr, nullptr, nullptr,
+                        s);
 }
 
 }  // extern "C"

@@ -1483,6 +1483,8 @@ class OvnEngine:
     POSE_GRAPH_RECORD = ("cost", "bad_edges", "cholesky_failures", "grad_max", "iterations", "relative_residual", "converged",
                          "breakdown", "rz", "rz0", "alpha", "beta", "delta_max")
     POSE_GRAPH_PRECONDITIONERS = {"jacobi": 0, "chain": 1}
+    POSE_GRAPH_LOOPS = 2                       # OVN_POSE_GRAPH_LOOPS: served by the ovn_pose_graph_*_loops entries
+    POSE_GRAPH_MAX_LOOPS = 256                 # OVN_POSE_GRAPH_MAX_LOOPS
 
     def _pg_tensor(self, what: str, t: Optional[torch.Tensor], dtype, shape, optional: bool = False):
         if t is None and optional:
@@ -1492,10 +1494,20 @@ class OvnEngine:
             raise _lib.OvnError("%s must be a contiguous %s %s tensor on %s" % (what, dtype, tuple(shape) if shape else "", self.device))
         return t
 
-    def pose_graph_buffers(self, n_nodes: int, n_edges: int, chain: bool = False) -> Dict[str, torch.Tensor]:
+    def pose_graph_buffers(self, n_nodes: int, n_edges: int, chain: bool = False, loops: int = 0) -> Dict[str, torch.Tensor]:
         """Every device buffer the pose-graph calls write, sized for n_nodes and n_edges: res, chi, weight, jac, blocks, grad, diag,
-        dinv, chain (when asked), delta, ws (ovn_pose_graph_workspace_bytes) and record."""
+        dinv, chain (when asked), delta, ws (ovn_pose_graph_workspace_bytes) and record.  loops=L > 0 adds chain and `loops`
+        (ovn_pose_graph_loops_bytes) for the chain-plus-loops inverse of a graph whose last L edges are its loop edges."""
         n, e = int(n_nodes), int(n_edges)
+        if int(loops) > 0:
+            nl = int(loops)
+            lbytes = int(self.lib.ovn_pose_graph_loops_bytes(n, nl))
+            if lbytes <= 0 or e != n - 1 + nl:
+                raise _lib.OvnError("pose graph of %d nodes, %d edges and %d loop edges: the chain-plus-loops inverse takes 1..%d loop "
+                                    "edges after the %d chain edges" % (n, e, nl, self.POSE_GRAPH_MAX_LOOPS, n - 1))
+            b = self.pose_graph_buffers(n, e, chain=True)
+            b["loops"] = torch.zeros(lbytes // 8, dtype=torch.float64, device=self.device)
+            return b
         nbytes = int(self.lib.ovn_pose_graph_workspace_bytes(n, e))
         if nbytes <= 0:
             raise _lib.OvnError("pose graph of %d nodes and %d edges is outside the library's limits" % (n, e))
@@ -1537,9 +1549,18 @@ class OvnEngine:
         """Enqueues `iterations` PCG iterations on the linearization in `buf` (ovn_pose_graph_solve); delta in buf["delta"], state in
         buf["ws"], status in the returned record tensor.  Never waits for the GPU."""
         n, e = int(fixed.shape[0]), int(edge_ij.shape[0])
+        if preconditioner in ("loops", self.POSE_GRAPH_LOOPS):
+            lp = self._pg_loops(buf, n, e - (n - 1), "pose_graph_solve")
+            with self._dev():
+                _lib.check(self.lib.ovn_pose_graph_solve_loops(
+                    self._h, self._stream(), _ptr(fixed), n, _ptr(edge_ij), e, _ptr(node_ptr), _ptr(node_edge), _ptr(buf["blocks"]),
+                    _ptr(buf["grad"]), _ptr(buf["diag"]), _ptr(buf["dinv"]), _ptr(buf.get("chain")), _ptr(lp), e - (n - 1), float(lam),
+                    float(rtol), int(first_iteration), int(iterations), _ptr(buf["delta"]), _ptr(buf["ws"]), _ptr(buf["record"])),
+                    "ovn_pose_graph_solve_loops")
+            return buf["record"]
         kind = self.POSE_GRAPH_PRECONDITIONERS.get(preconditioner, preconditioner)
         if not isinstance(kind, int):
-            raise _lib.OvnError("pose_graph_solve: no preconditioner %r (jacobi, chain)" % (preconditioner,))
+            raise _lib.OvnError("pose_graph_solve: no preconditioner %r (jacobi, chain, loops)" % (preconditioner,))
         with self._dev():
             _lib.check(self.lib.ovn_pose_graph_solve(
                 self._h, self._stream(), _ptr(fixed), n, _ptr(edge_ij), e, _ptr(node_ptr), _ptr(node_edge), _ptr(buf["blocks"]),
@@ -1547,15 +1568,69 @@ class OvnEngine:
                 int(first_iteration), int(iterations), _ptr(buf["delta"]), _ptr(buf["ws"]), _ptr(buf["record"])), "ovn_pose_graph_solve")
         return buf["record"]
 
+    def _pg_loops(self, buf: Dict[str, torch.Tensor], n: int, n_loops: int, what: str) -> torch.Tensor:
+        nbytes = int(self.lib.ovn_pose_graph_loops_bytes(n, n_loops))
+        if nbytes <= 0:
+            raise _lib.OvnError("%s: the chain-plus-loops inverse takes 1..%d loop edges after the chain, got %d"
+                                % (what, self.POSE_GRAPH_MAX_LOOPS, n_loops))
+        if buf.get("chain") is None or buf.get("loops") is None:
+            raise _lib.OvnError("%s: the buffers were not made with loops=%d (pose_graph_buffers)" % (what, n_loops))
+        return self._pg_tensor("%s: buf['loops']" % what, buf["loops"], torch.float64, (nbytes // 8,))
+
+    def pose_graph_loops_prepare(self, poses, edge_ij, info, buf: Dict[str, torch.Tensor],
+                                 record: Optional[torch.Tensor] = None, stages: int = 7) -> torch.Tensor:
+        """Gamma, C, the spans, S and its Cholesky factor of the chain-plus-loops inverse into buf["loops"], from the linearization
+        (with Jacobians) that `buf` holds for `poses` (ovn_pose_graph_loops_prepare).  Returns the record tensor: slot 13 counts
+        failed pivots, slot 14 the loop edges left out.  stages: 1 = scan, 2 = assembly, 4 = factorization, summed (a benchmark's knob)."""
+        f64, n, e = torch.float64, int(poses.shape[0]), int(edge_ij.shape[0])
+        self._pg_tensor("pose_graph_loops_prepare: poses", poses, f64, (n, 4, 4))
+        self._pg_tensor("pose_graph_loops_prepare: edge_ij", edge_ij, torch.int32, (e, 2))
+        self._pg_tensor("pose_graph_loops_prepare: info", info, f64, (e, 6, 6))
+        lp = self._pg_loops(buf, n, e - (n - 1), "pose_graph_loops_prepare")
+        self._pg_tensor("pose_graph_loops_prepare: buf['weight']", buf["weight"], f64, (e,))
+        self._pg_tensor("pose_graph_loops_prepare: buf['jac']", buf["jac"], f64, (e, 2, 6, 6))
+        self._pg_tensor("pose_graph_loops_prepare: buf['chain']", buf["chain"], f64, (n - 1, 2, 6, 6))
+        rec = self._pg_tensor("pose_graph_loops_prepare: record", buf["record"] if record is None else record, f64, (16,))
+        with self._dev():
+            _lib.check(self.lib.ovn_pose_graph_loops_prepare(
+                self._h, self._stream(), _ptr(poses), n, _ptr(edge_ij), _ptr(info), _ptr(buf["weight"]), _ptr(buf["jac"]), e, e - (n - 1),
+                _ptr(buf["chain"]), int(stages), _ptr(lp), _ptr(rec)), "ovn_pose_graph_loops_prepare")
+        return rec
+
+    def pose_graph_loops_views(self, buf: Dict[str, torch.Tensor], n_nodes: int, n_loops: int) -> Dict[str, torch.Tensor]:
+        """Views into buf["loops"] (ovn_pose_graph_loops_layout): gamma (N,6,6), C (L,6,6), winv (L,6,6), span (L,4), S (sp,sp),
+        factor (sp,sp), and the integers block and sp."""
+        n, nl = int(n_nodes), int(n_loops)
+        lay = (C.c_int64 * 8)()
+        _lib.check(self.lib.ovn_pose_graph_loops_layout(n, nl, lay), "ovn_pose_graph_loops_layout")
+        b, sp = int(lay[0]), int(lay[1])
+        lp = self._pg_loops(buf, n, nl, "pose_graph_loops_views")
+        v = lambda k, *s: lp[int(lay[k]):int(lay[k]) + int(np.prod(s))].view(*s)
+        return dict(block=b, sp=sp, gamma=v(2, n, 6, 6), C=v(3, nl, 6, 6), winv=v(4, nl, 6, 6), span=v(5, nl, 4), S=v(6, sp, sp),
+                    factor=v(7, sp, sp))
+
     def pose_graph_precondition(self, vec: torch.Tensor, buf: Dict[str, torch.Tensor], preconditioner="jacobi", lam: float = 0.0,
-                                out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """out (N,6) = M^-1 vec (N,6) for the preconditioner of the linearization in `buf` (ovn_pose_graph_precondition)."""
+                                out: Optional[torch.Tensor] = None, node_ptr: Optional[torch.Tensor] = None,
+                                node_edge: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """out (N,6) = M^-1 vec (N,6) for the preconditioner of the linearization in `buf` (ovn_pose_graph_precondition); "loops"
+        also takes the graph's incidence list node_ptr, node_edge (ovn_pose_graph_precondition_loops; lam is not used: the inverse
+        is that of the undamped Hessian)."""
         n = int(vec.shape[0])
         self._pg_tensor("pose_graph_precondition: vec", vec, torch.float64, (n, 6))
         out = torch.zeros_like(vec) if out is None else self._pg_tensor("pose_graph_precondition: out", out, torch.float64, (n, 6))
+        if preconditioner in ("loops", self.POSE_GRAPH_LOOPS):
+            self._pg_tensor("pose_graph_precondition: node_ptr", node_ptr, torch.int32, (n + 1,))
+            self._pg_tensor("pose_graph_precondition: node_edge", node_edge, torch.int32, None)
+            e = int(node_edge.shape[0]) // 2
+            lp = self._pg_loops(buf, n, e - (n - 1), "pose_graph_precondition")
+            with self._dev():
+                _lib.check(self.lib.ovn_pose_graph_precondition_loops(
+                    self._h, self._stream(), n, e, e - (n - 1), _ptr(node_ptr), _ptr(node_edge), _ptr(buf["chain"]), _ptr(lp), _ptr(vec),
+                    _ptr(out), _ptr(buf["ws"])), "ovn_pose_graph_precondition_loops")
+            return out
         kind = self.POSE_GRAPH_PRECONDITIONERS.get(preconditioner, preconditioner)
         if not isinstance(kind, int):
-            raise _lib.OvnError("pose_graph_precondition: no preconditioner %r (jacobi, chain)" % (preconditioner,))
+            raise _lib.OvnError("pose_graph_precondition: no preconditioner %r (jacobi, chain, loops)" % (preconditioner,))
         with self._dev():
             _lib.check(self.lib.ovn_pose_graph_precondition(self._h, self._stream(), n, kind, float(lam), _ptr(buf.get("dinv")),
                                                             _ptr(buf.get("chain")), _ptr(vec), _ptr(out), _ptr(buf["ws"])),

@@ -3,7 +3,9 @@
 `odometry` tracks scans into poses, `Infer.infer_top_k` proposes loop closures and `Infer.verify_top_k` checks them by ICP; this module
 distributes the loop error over the trajectory.  Nodes are poses (4,4) sensor to world; an edge (i, j, Z, Omega) measures
 T_i^-1 T_j with information Omega (6 x 6, twist order (v, omega)).  The statement -- residual, Jacobians, Huber weights, normal
-equations, preconditioners -- is in include/ovn_hip.h and DESIGN.md section 32; the kernels are csrc/pose_graph.hip.
+equations, preconditioners -- is in include/ovn_hip.h and DESIGN.md section 32; the kernels are csrc/pose_graph.hip.  A drive with
+many loop closures has a third preconditioner, "loops" (DESIGN.md section 33): the exact inverse of the undamped Hessian of the
+odometry chain plus up to MAX_LOOPS loop edges, prepared after every full linearization.
 
 The outer loop is Levenberg-Marquardt on the host and reads one 16-double record per step (plus one per chunk of conjugate-gradient
 iterations): lambda starts at 0 (Gauss-Newton); a trial step T Exp(delta) is accepted when the cost does not rise, then lambda <-
@@ -26,6 +28,15 @@ XTOL = 1e-10
 # a term of rank 6 L); with block-Jacobi they needed 2.9 N .. 7.8 N on the drives of tools/bench_pose_graph.py (N = 1024 .. 16384,
 # L = 1 .. 512; profiles/pose_graph.json).  The smallest measured figure is the estimate.
 JACOBI_ITERATIONS_PER_NODE = 2.9
+# "loops" / "auto+loops": the chain-plus-loops inverse takes at most MAX_LOOPS loop edges
+# (OVN_POSE_GRAPH_MAX_LOOPS).  On the drives of tools/bench_pose_graph_loops.py (N = 1024 .. 16384; profiles/pose_graph_loops.json) one
+# undamped outer step -- prepare plus solve -- took 0.7 / 0.9 .. 1.2 / 2.5 .. 3.1 / 5.5 .. 6.7 ms at L = 1 / 32 / 128 / 256, against
+# 1.9 .. 2.0 / 9 .. 177 / 23 .. 698 / 34 .. 1345 ms with the chain and 2.8 .. 49 / 5.4 .. 121 / 5.2 .. 111 / 5.5 .. 103 ms for the CPU's
+# sparse direct solve, and a whole optimize was faster than the chain's in all twelve cells; at L = 512 it took 13.3 ms against the
+# CPU's 6.0 ms at N = 1024, which is what set MAX_LOOPS.  So "auto+loops" takes it for every L in LOOPS_MIN .. MAX_LOOPS when the
+# chain precondition holds, and is "auto" otherwise.
+MAX_LOOPS = 256
+LOOPS_MIN = 1
 
 Result = collections.namedtuple("Result", "poses cost_initial cost_final outer_iterations cg_iterations converged chi2 weights")
 
@@ -75,6 +86,7 @@ class PoseGraph:
             f[int(v)] = True
         self.fixed = f
         self._ij, self._z, self._info = [], [], []
+        self.fallbacks = 0      # outer iterations of "loops" whose factorization broke down and which the chain solved instead
 
     # -- building ---------------------------------------------------------------------------------------------------------------------
     def add_edge(self, i: int, j: int, Z, information) -> int:
@@ -160,16 +172,33 @@ class PoseGraph:
             if roots[v] not in anchored:
                 raise ValueError("node %d lies in a component without a fixed node" % v)
 
+    @property
+    def loops(self) -> int:
+        """The number of edges after the N - 1 a chain would take."""
+        return len(self._ij) - (self.n - 1)
+
     def choose_preconditioner(self, preconditioner: str = "auto") -> str:
         if preconditioner == "jacobi":
             return "jacobi"
+        if preconditioner == "loops":
+            if not self.chain_available():
+                raise ValueError("the chain-plus-loops inverse needs edges 0 .. N - 2 to be the odometry steps (k, k + 1) in order and "
+                                 "node 0 to be the only fixed node")
+            if not 1 <= self.loops <= MAX_LOOPS:
+                raise ValueError("the chain-plus-loops inverse takes 1 .. %d loop edges after the chain, the graph has %d"
+                                 % (MAX_LOOPS, self.loops))
+            return "loops"
+        if preconditioner == "auto+loops":
+            if self.chain_available() and LOOPS_MIN <= self.loops <= MAX_LOOPS:
+                return "loops"
+            preconditioner = "auto"
         if preconditioner == "chain":
             if not self.chain_available():
                 raise ValueError("the chain preconditioner needs edges 0 .. N - 2 to be the odometry steps (k, k + 1) in order and node 0 "
                                  "to be the only fixed node")
             return "chain"
         if preconditioner != "auto":
-            raise ValueError("no preconditioner %r (auto, jacobi, chain)" % (preconditioner,))
+            raise ValueError("no preconditioner %r (auto, auto+loops, jacobi, chain, loops)" % (preconditioner,))
         loops = len(self._ij) - (self.n - 1)
         if self.chain_available() and 6 * loops + 1 < JACOBI_ITERATIONS_PER_NODE * self.n:
             return "chain"
@@ -202,9 +231,14 @@ class PoseGraph:
         fixed = up(self.fixed.astype(np.uint8))
         ptr, lst = (up(a) for a in incidence(self.n, self.edges))
         poses, trial = up(self.poses), torch.empty((self.n, 4, 4), dtype=torch.float64, device=dev)
-        buf = eng.pose_graph_buffers(self.n, e, chain=(kind == "chain"))
+        buf = eng.pose_graph_buffers(self.n, e, chain=(kind == "chain"), loops=(self.loops if kind == "loops" else 0))
         rec_trial = torch.zeros(16, dtype=torch.float64, device=dev)
-        lin = lambda p, **kw: eng.pose_graph_linearize(p, fixed, ij, meas, info, ptr, lst, k, buf, **kw).cpu().numpy()
+
+        def lin(p, **kw):
+            rec = eng.pose_graph_linearize(p, fixed, ij, meas, info, ptr, lst, k, buf, **kw)
+            if kind == "loops" and kw.get("jacobians", True):          # the inverse belongs to this linearization
+                rec = eng.pose_graph_loops_prepare(p, ij, info, buf)
+            return rec.cpu().numpy()
 
         def refuse(rec):
             if rec[2] != 0:
@@ -216,8 +250,12 @@ class PoseGraph:
         lam, outer, cg, converged = 0.0, 0, 0, False
         while outer < int(max_iterations) and lam <= LAMBDA_MAX and e > 0:
             done = 0
+            use = kind
+            if kind == "loops" and rec[13] != 0:                       # S has no Cholesky factor at this linearization
+                use = "chain"
+                self.fallbacks += 1
             while True:
-                r = eng.pose_graph_solve(fixed, ij, ptr, lst, buf, kind, lam, rtol, done, min(cg_chunk, max_cg - done)).cpu().numpy()
+                r = eng.pose_graph_solve(fixed, ij, ptr, lst, buf, use, lam, rtol, done, min(cg_chunk, max_cg - done)).cpu().numpy()
                 done += min(cg_chunk, max_cg - done)
                 if r[6] != 0 or r[7] != 0 or done >= max_cg:
                     break

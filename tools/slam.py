@@ -56,7 +56,7 @@ def parse(argv=None):
     ap.add_argument("--loop-sigma", type=float, nargs=2, required=True, metavar=("METRES", "RADIANS"))
     ap.add_argument("--huber", type=number_or_none, required=True)
     ap.add_argument("--max-iterations", type=int, default=30)
-    ap.add_argument("--preconditioner", default="auto", choices=("auto", "jacobi", "chain"))
+    ap.add_argument("--preconditioner", default="auto", choices=("auto", "auto+loops", "jacobi", "chain", "loops"))
     ap.add_argument("--voxel", type=float, default=0.2)
     ap.add_argument("--fov-up", type=float, default=3.0)
     ap.add_argument("--fov-down", type=float, default=-25.0)
