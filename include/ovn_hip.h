@@ -783,6 +783,37 @@ int ovn_pose_graph_precondition_loops(ovn_ctx* ctx, void* stream, int n_nodes, i
                                       const int32_t* node_edge_dev, const double* chain_dev, double* loops_dev, const double* in_dev,
                                       double* out_dev, double* ws_dev);
 
+/* Marginal pose covariances: the diagonal 6 x 6 blocks of the inverse of the undamped Hessian of a chain plus L >= 0 loop edges, for a
+ * list of nodes (csrc/pose_graph.hip; restated by tests/_pose_graph_marginals_ref.py).  The PRECONDITION is that
+ * of the chain-plus-loops inverse above.  For the left perturbation T_k <- Exp(eps_k) T_k, eps = (v, omega) in the world,
+ *   Sigma_world(k) = Gamma[k] - Y_k' Y_k,   L_S Y_k = V_k',   V_k = [ (Gamma[clamp(k, lo_a, hi_a)] - Gamma[lo_a]) sigma_a C_a' ]_a  (6 x 6 L)
+ * with S = L_S L_S' the factor ovn_pose_graph_loops_prepare left.  Everything is relative to the fixed node 0, whose block is all
+ * zeros, and uses the edge weights (Huber weights included) of the linearization it follows.  `frame`:
+ *   OVN_POSE_GRAPH_COV_LOCAL     the optimizer's own delta_k (T_k <- T_k Exp(delta_k)): Ad(T_k^-1) Sigma_world Ad(T_k^-1)'
+ *   OVN_POSE_GRAPH_COV_POSITION  (position in the world, rotation vector in the world): J Sigma_world J', J = [[I, -[p_k]x], [0, I]];
+ *                                its top-left 2 x 2 is the x, y covariance of a search ellipse
+ * cov_dev (n_query,6,6) row-major, every block symmetric to the bit; node_ids_dev (n_query) int32 in any order, repeats allowed.  An id
+ * outside [0, N) gives a block of NaNs and is counted in record [15].  For L >= 1 loops_dev comes from ovn_pose_graph_loops_prepare
+ * with OVN_POSE_GRAPH_LOOPS_ALL after the same linearization as chain_dev; for L == 0 it is not read (NULL) and Gamma is scanned from
+ * chain_dev into the workspace: dead-reckoning covariance propagation.  When record [2] (or, for L >= 1, [13]) is not 0 the call sets
+ * `breakdown` [7] and cov_dev is not touched; otherwise it clears [7].  It must not run between the chunks of a solve.
+ *
+ * The sweep walks the queried nodes in launches of at most 512 workgroups of 8 nodes, so ws_dev is bounded however many are asked for:
+ * ovn_pose_graph_marginals_bytes(N, L, K) is 8 bytes times  ceil(K / 256)  +  (L == 0 ? 36 N + 72 ceil((N - 1) / 256) : 0)  +
+ * min(ceil(K / 8), 512) * sp * 48  with sp = 6 L rounded up to 48 (each term rounded up to even), at most 302 MB for L = 256 and a
+ * few hundred bytes for L == 0, K <= 256.  It returns 0 for N outside 2 .. OVN_POSE_GRAPH_MAX_NODES, L outside 0 ..
+ * OVN_POSE_GRAPH_MAX_LOOPS or K outside 1 .. OVN_POSE_GRAPH_MAX_QUERY.
+ *
+ * OVN_ERR_ARG, before any launch and with every buffer as it was: a NULL ctx or buffer (loops_dev only for L >= 1), N < 2, L < 0,
+ * L > OVN_POSE_GRAPH_MAX_LOOPS, E != N - 1 + L, n_query outside 1 .. OVN_POSE_GRAPH_MAX_QUERY, an unknown frame. */
+#define OVN_POSE_GRAPH_COV_LOCAL 0
+#define OVN_POSE_GRAPH_COV_POSITION 1
+#define OVN_POSE_GRAPH_MAX_QUERY (1 << 22)
+int64_t ovn_pose_graph_marginals_bytes(int64_t n_nodes, int64_t n_loops, int64_t n_query);
+int ovn_pose_graph_marginals(ovn_ctx* ctx, void* stream, const double* poses_dev, int n_nodes, int n_edges, int n_loops,
+                             const double* chain_dev, const double* loops_dev, const int32_t* node_ids_dev, int64_t n_query, int frame,
+                             double* cov_dev, double* ws_dev, double* record_dev);
+
 /* The per-point part of range_projection alone (src/utils/utils.py:75-104), exactly as ovn_project's scatter kernel evaluates it:
  * for each of n float32 points (x,y,z,*) yaw = -np.arctan2(y, x), pitch = np.arcsin(z / depth) with NumPy's float32 results
  * (csrc/svml_f32.h) and the pixel py * proj_w + px the point falls into (-1 for a point the range filter drops).  Outputs may

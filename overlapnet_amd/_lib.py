@@ -94,6 +94,8 @@ SIGNATURES = {
     "ovn_pose_graph_solve_loops": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int] + [_vp] * 8 + [C.c_int, C.c_double, C.c_double, C.c_int,
                                              C.c_int, _vp, _vp, _vp]),
     "ovn_pose_graph_precondition_loops": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int] + [_vp] * 7),
+    "ovn_pose_graph_marginals_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
+    "ovn_pose_graph_marginals": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int64, C.c_int, _vp, _vp, _vp]),
     "ovn_projection_angles": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp]),
     "ovn_gt_range_images": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int64, _vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double,
                                       C.c_double, _vp, _vp]),

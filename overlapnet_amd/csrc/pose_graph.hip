@@ -1,7 +1,8 @@
 // SE(3) pose-graph optimization in fp64 (ovn_pose_graph_*; include/ovn_hip.h): linearization of the edges,
 // block-sparse preconditioned conjugate gradients with a block-Jacobi or an odometry-chain preconditioner, and the retraction; and the
 // chain-plus-loops inverse (ovn_pose_graph_loops_*; tests/_pose_graph_loops_ref.py): the exact inverse of the
-// undamped Hessian of a chain plus L loop edges, with a dense Cholesky factorization of order 6 L.
+// undamped Hessian of a chain plus L loop edges, with a dense Cholesky factorization of order 6 L; and the marginal covariances that
+// inverse's diagonal blocks are (ovn_pose_graph_marginals; tests/_pose_graph_marginals_ref.py).
 // No atomics: a node sums over its incidence list in list order, every dot product and maximum is a fixed tree (256 lanes, halving),
 // the scans are Hillis-Steele inside a workgroup and three launches across workgroups.  No workgroup waits on another inside a launch.
 // Built without FMA contraction: tests/_pose_graph_ref.py states the same operations one by one.
@@ -1488,6 +1489,251 @@ int pg_loops_apply(int N, int E, int L, const int32_t* ptr, const int32_t* lst, 
   return OVN_OK;
 }
 
+// ---- marginal covariances (ovn_pose_graph_marginals; tests/_pose_graph_marginals_ref.py) -----------------------------
+// Sigma_world(k) = Gamma[k] - Y_k' Y_k with L_S Y_k = V_k' and V_k = [(Gamma[clamp(k, lo_a, hi_a)] - Gamma[lo_a]) sigma_a C_a']_a: the
+// diagonal blocks of H^-1 = H_c^-1 - H_c^-1 J' S^-1 J H_c^-1 in world tangent coordinates.  A workgroup owns PGM_TN queried nodes, 48
+// columns, and walks the factor's block rows left-looking: X = V' block - sum_t F[kb][t] Y[t] (one subtraction of a 48-term sum in
+// index order per earlier block, in block order), then the diagonal block column by column as pgl_solve_kernel takes it.  Its Y tile
+// lives in the workspace; the 48 x 48 blocks go through LDS.
+constexpr int PGM_TN = 8;                 // queried nodes per workgroup: 6 * 8 = PGL_NB columns
+constexpr int PGM_CHUNK = 512;            // workgroups per launch: the Y tiles of one launch are what the workspace holds
+constexpr int PGM_TRI = 21;               // entries of a 6 x 6 lower triangle
+enum { R_MOUT = 15 };
+static_assert(6 * PGM_TN == PGL_NB, "a tile of queried nodes is one factor block wide");
+
+struct PgMarg {   // the caller's ws_dev of ovn_pose_graph_marginals, in doubles
+  double *gamma, *gsum, *Y, *part;
+  int64_t nbc, nbq, tiles, chunk, sp;
+  size_t total;
+  PgMarg(double* base, int64_t N, int64_t L, int64_t K) {
+    nbc = (N - 1 + PG_B - 1) / PG_B;
+    nbq = (K + PG_B - 1) / PG_B;
+    tiles = (K + PGM_TN - 1) / PGM_TN;
+    chunk = tiles < PGM_CHUNK ? tiles : PGM_CHUNK;
+    sp = (6 * L + PGL_NB - 1) / PGL_NB * PGL_NB;
+    size_t o = 0;
+    auto take = [&](size_t n) { double* q_ = base ? base + o : nullptr; o += (n + 1) & ~(size_t)1; return q_; };
+    part = take(nbq);                              // out-of-range ids per finishing workgroup
+    gamma = take(L == 0 ? 36 * N : 0);             // without loop edges nobody has scanned Gamma: a copy of its own
+    gsum = take(L == 0 ? 72 * nbc : 0);
+    Y = take((size_t)chunk * sp * PGL_NB);         // one (sp, 48) tile per workgroup of a launch
+    total = o;
+  }
+};
+
+// `breakdown` from the linearization's and the prepare's failed pivots, before anything touches cov; slot [15] starts at 0
+__global__ void pgm_reset_kernel(double* rec, int L) {
+  if (threadIdx.x != 0) return;
+  rec[R_BREAK] = (rec[R_CHOL] != 0.0 || (L > 0 && rec[R_LPIV] != 0.0)) ? 1.0 : 0.0;
+  rec[R_MOUT] = 0.0;
+}
+
+// the forward sweep of one launch: workgroup w owns queries q0 + 8 w .. q0 + 8 w + 7 and leaves the lower triangles of Y_k' Y_k in cov
+__global__ __launch_bounds__(PG_B) void pgm_sweep_kernel(int N, int L, int sp, int64_t q0, int64_t K, const int32_t* __restrict__ ids,
+                                                         const double* __restrict__ gamma, const double* __restrict__ C,
+                                                         const double* __restrict__ span, const double* __restrict__ F,
+                                                         double* __restrict__ Yws, double* __restrict__ cov, const double* rec) {
+  if (rec[R_BREAK] != 0.0) return;
+  __shared__ double A[PGL_NB][PGL_NB + 1], B[PGL_NB][PGL_NB + 1], Yd[PGL_NB][PGL_NB + 1];
+  __shared__ int node[PGM_TN];
+  __shared__ int fbs[PG_B];
+  const int tid = threadIdx.x, nbk = sp / PGL_NB;
+  const int64_t qb = q0 + (int64_t)blockIdx.x * PGM_TN;
+  if (tid < PGM_TN) {
+    int k = -1;
+    if (qb + tid < K) {
+      k = ids[qb + tid];
+      if (k < 0 || k >= N) k = -1;
+    }
+    node[tid] = k;
+  }
+  __syncthreads();
+  int kmax = -1;
+#pragma unroll
+  for (int n = 0; n < PGM_TN; ++n) kmax = max(kmax, node[n]);
+  // the first block row in which some edge's V block is not zero for this tile: V_k's block a is zero for k <= lo_a
+  int fb = nbk;
+  for (int a = tid; a < L; a += PG_B)
+    if (span[4 * a + 3] != 0.0 && (int)span[4 * a] < kmax) fb = min(fb, 6 * a / PGL_NB);
+  fbs[tid] = fb;
+  __syncthreads();
+  for (int h = PG_B / 2; h > 0; h >>= 1) {
+    if (tid < h) fbs[tid] = min(fbs[tid], fbs[tid + h]);
+    __syncthreads();
+  }
+  fb = fbs[0];
+  double* Yt = Yws + (size_t)blockIdx.x * sp * PGL_NB;
+  const int tr = tid / 16 * 3, tc = tid % 16 * 3;     // this thread's 3 x 3 entries of a 48 x 48 block: rows tr.., columns tc..
+  const int my = node[tc / 6], i0 = tc % 6;           // its three columns are rows i0 .. i0 + 2 of one node's V
+  const int sc = tid % PGL_NB, sg = tid / PGL_NB;     // diagonal solve: column sc, rows sg, sg + 4, ... (threads 0 .. 191)
+  int an = -1, ai = 0, aj = 0;                        // Y'Y: entry (ai, aj), ai >= aj, of node an (threads 0 .. 167)
+  if (tid < PGM_TN * PGM_TRI) {
+    an = tid / PGM_TRI;
+    const int p = tid % PGM_TRI;
+    while ((ai + 1) * (ai + 2) / 2 <= p) ++ai;
+    aj = p - ai * (ai + 1) / 2;
+  }
+  double acc = 0.0;
+  for (int kb = fb; kb < nbk; ++kb) {
+    double x[3][3];
+#pragma unroll
+    for (int u = 0; u < 3; ++u)
+#pragma unroll
+      for (int v = 0; v < 3; ++v) x[u][v] = 0.0;
+    const int r0 = kb * PGL_NB + tr, a = r0 / 6, qr = r0 % 6;   // its three rows are rows qr .. qr + 2 of edge a's C
+    if (a < L && my >= 0 && span[4 * a + 3] != 0.0) {
+      const int lo = (int)span[4 * a], hi = (int)span[4 * a + 1];
+      if (my > lo) {
+        const double* gh = gamma + (size_t)min(my, hi) * 36 + i0 * 6;
+        const double* gl = gamma + (size_t)lo * 36 + i0 * 6;
+        const double* cr = C + (size_t)a * 36 + qr * 6;
+        const double sgn = span[4 * a + 2];
+        double M[3][6];
+#pragma unroll
+        for (int v = 0; v < 3; ++v)
+#pragma unroll
+          for (int t = 0; t < 6; ++t) M[v][t] = gh[v * 6 + t] - gl[v * 6 + t];
+#pragma unroll
+        for (int u = 0; u < 3; ++u)
+#pragma unroll
+          for (int v = 0; v < 3; ++v) {
+            double s = M[v][0] * cr[u * 6];
+#pragma unroll
+            for (int t = 1; t < 6; ++t) s = s + M[v][t] * cr[u * 6 + t];
+            x[u][v] = sgn * s;
+          }
+      }
+    }
+    for (int t = fb; t < kb; ++t) {
+      __syncthreads();
+      for (int idx = tid; idx < PGL_NB * PGL_NB; idx += PG_B) {
+        const int r = idx / PGL_NB, c = idx % PGL_NB;
+        A[r][c] = F[((size_t)kb * PGL_NB + r) * sp + (size_t)t * PGL_NB + c];
+        B[r][c] = Yt[((size_t)t * PGL_NB + r) * PGL_NB + c];
+      }
+      __syncthreads();
+      double s[3][3];
+#pragma unroll
+      for (int u = 0; u < 3; ++u)
+#pragma unroll
+        for (int v = 0; v < 3; ++v) s[u][v] = A[tr + u][0] * B[0][tc + v];
+#pragma unroll 4
+      for (int c = 1; c < PGL_NB; ++c) {
+        double av[3], bv[3];
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {
+          av[u] = A[tr + u][c];
+          bv[u] = B[c][tc + u];
+        }
+#pragma unroll
+        for (int u = 0; u < 3; ++u)
+#pragma unroll
+          for (int v = 0; v < 3; ++v) s[u][v] = s[u][v] + av[u] * bv[v];
+      }
+#pragma unroll
+      for (int u = 0; u < 3; ++u)
+#pragma unroll
+        for (int v = 0; v < 3; ++v) x[u][v] = x[u][v] - s[u][v];
+    }
+    __syncthreads();
+    for (int idx = tid; idx < PGL_NB * PGL_NB; idx += PG_B) {
+      const int r = idx / PGL_NB, c = idx % PGL_NB;
+      A[r][c] = F[((size_t)kb * PGL_NB + r) * sp + (size_t)kb * PGL_NB + c];
+    }
+#pragma unroll
+    for (int u = 0; u < 3; ++u)
+#pragma unroll
+      for (int v = 0; v < 3; ++v) B[tr + u][tc + v] = x[u][v];
+    __syncthreads();
+    // the diagonal block: y_c = x_c / L_cc, then one subtraction per row below, column by column
+    for (int c = 0; c < PGL_NB; ++c) {
+      if (sg < 4) {
+        const double y = B[c][sc] / A[c][c];
+        if (c % 4 == sg) Yd[c][sc] = y;
+        for (int r = c + 1 + ((sg - c - 1) % 4 + 4) % 4; r < PGL_NB; r += 4) B[r][sc] = B[r][sc] - A[r][c] * y;
+      }
+      __syncthreads();
+    }
+    for (int idx = tid; idx < PGL_NB * PGL_NB; idx += PG_B) {
+      const int r = idx / PGL_NB, c = idx % PGL_NB;
+      Yt[((size_t)kb * PGL_NB + r) * PGL_NB + c] = Yd[r][c];
+    }
+    if (an >= 0) {
+#pragma unroll 4
+      for (int r = 0; r < PGL_NB; ++r) acc = acc + Yd[r][6 * an + ai] * Yd[r][6 * an + aj];
+    }
+  }
+  if (an >= 0 && qb + an < K) cov[(size_t)(qb + an) * 36 + ai * 6 + aj] = acc;
+}
+
+// one query per thread: Sigma_world = Gamma[k] - Y'Y on the lower triangle, mirrored; then A Sigma A' with A = Ad(T_k^-1) (local frame)
+// or [[I, -p^], [0, I]] (position frame), its lower triangle mirrored.  Node 0 is all zeros; an id outside [0, N) gives NaNs and is counted
+__global__ __launch_bounds__(PG_B) void pgm_finish_kernel(int N, int64_t K, int has_acc, int frame, const int32_t* __restrict__ ids,
+                                                          const double* __restrict__ poses, const double* __restrict__ chain,
+                                                          const double* __restrict__ gamma, double* __restrict__ cov,
+                                                          double* __restrict__ part, const double* rec) {
+  if (rec[R_BREAK] != 0.0) return;
+  __shared__ double sh[PG_B];
+  const int64_t q = (int64_t)blockIdx.x * PG_B + threadIdx.x;
+  double bad = 0.0;
+  if (q < K) {
+    const int k = ids[q];
+    double* out = cov + (size_t)q * 36;
+    if (k < 0 || k >= N) {
+      bad = 1.0;
+      const double nan = __longlong_as_double(0x7ff8000000000000LL);
+#pragma unroll
+      for (int e = 0; e < 36; ++e) out[e] = nan;
+    } else if (k == 0) {
+#pragma unroll
+      for (int e = 0; e < 36; ++e) out[e] = 0.0;
+    } else {
+      double Sg[36], Am[36], T[36];
+      const double* g = gamma + (size_t)k * 36;
+#pragma unroll
+      for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+          const double v = has_acc ? g[i * 6 + j] - out[i * 6 + j] : g[i * 6 + j];
+          Sg[i * 6 + j] = v;
+          Sg[j * 6 + i] = v;
+        }
+      if (frame == OVN_POSE_GRAPH_COV_LOCAL) {
+        ld36(chain + (size_t)(k - 1) * 72 + 36, Am);
+      } else {
+        const double* Tk = poses + (size_t)k * 16;
+        const double p[3] = {Tk[3], Tk[7], Tk[11]};
+        double H[9];
+        m3_hat(p, H);
+#pragma unroll
+        for (int e = 0; e < 36; ++e) Am[e] = (e % 7 == 0) ? 1.0 : 0.0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+          for (int j = 0; j < 3; ++j) Am[i * 6 + 3 + j] = -H[i * 3 + j];
+      }
+      m6_mul(Am, Sg, T);
+      m6_mult(T, Am, Sg);
+#pragma unroll
+      for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+          out[i * 6 + j] = Sg[i * 6 + j];
+          out[j * 6 + i] = Sg[i * 6 + j];
+        }
+    }
+  }
+  const double b = pg_wg_sum(bad, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = b;
+}
+// ONE workgroup: record [15], the ids outside [0, N)
+__global__ __launch_bounds__(PG_B) void pgm_record_kernel(const double* part, int nb, double* rec) {
+  if (rec[R_BREAK] != 0.0) return;
+  __shared__ double sh[PG_B];
+  const double b = pg_partial_sum(part, nb, 1, sh);
+  if (threadIdx.x == 0) rec[R_MOUT] = b;
+}
+
 }  // namespace
 
 // ---- C ABI --------------------------------------------------------------------------------------------------------------------------------
@@ -1763,6 +2009,55 @@ int ovn_pose_graph_precondition_loops(ovn_ctx* ctx, void* stream, int n_nodes, i
   PgLoops lp(loops_dev, n_nodes, n_loops);
   return pg_loops_apply(n_nodes, n_edges, n_loops, node_ptr_dev, node_edge_dev, chain_dev, lp, in_dev, out_dev, w, nullptr, nullptr, nullptr,
                         s);
+}
+
+// ---- marginal covariances ---------------------------------------------------------------------------------------------------------------
+int64_t ovn_pose_graph_marginals_bytes(int64_t n_nodes, int64_t n_loops, int64_t n_query) {
+  if (n_nodes < 2 || n_nodes > OVN_POSE_GRAPH_MAX_NODES || n_loops < 0 || n_loops > OVN_POSE_GRAPH_MAX_LOOPS || n_query < 1 ||
+      n_query > OVN_POSE_GRAPH_MAX_QUERY)
+    return 0;
+  return (int64_t)(PgMarg(nullptr, n_nodes, n_loops, n_query).total * sizeof(double));
+}
+
+int ovn_pose_graph_marginals(ovn_ctx* ctx, void* stream, const double* poses_dev, int n_nodes, int n_edges, int n_loops,
+                             const double* chain_dev, const double* loops_dev, const int32_t* node_ids_dev, int64_t n_query, int frame,
+                             double* cov_dev, double* ws_dev, double* record_dev) {
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_pose_graph_marginals: ctx is NULL");
+  OVN_REQUIRE(n_nodes >= 2 && n_nodes <= OVN_POSE_GRAPH_MAX_NODES && n_loops >= 0 && n_loops <= OVN_POSE_GRAPH_MAX_LOOPS &&
+                  (int64_t)n_edges == (int64_t)n_nodes - 1 + n_loops, OVN_ERR_ARG,
+              "ovn_pose_graph_marginals: %d nodes (2..%d), %d loop edges (0..%d), %d edges (must be nodes - 1 + loop edges)", n_nodes,
+              OVN_POSE_GRAPH_MAX_NODES, n_loops, OVN_POSE_GRAPH_MAX_LOOPS, n_edges);
+  OVN_REQUIRE(n_query >= 1 && n_query <= OVN_POSE_GRAPH_MAX_QUERY, OVN_ERR_ARG, "ovn_pose_graph_marginals: %lld queried nodes (1..%d)",
+              (long long)n_query, OVN_POSE_GRAPH_MAX_QUERY);
+  OVN_REQUIRE(frame == OVN_POSE_GRAPH_COV_LOCAL || frame == OVN_POSE_GRAPH_COV_POSITION, OVN_ERR_ARG,
+              "ovn_pose_graph_marginals: frame %d (0 = local, 1 = position)", frame);
+  OVN_REQUIRE(poses_dev && chain_dev && node_ids_dev && cov_dev && ws_dev && record_dev && (n_loops == 0 || loops_dev), OVN_ERR_ARG,
+              "ovn_pose_graph_marginals: NULL buffer");
+  OVN_ON_DEVICE(ctx->device);
+  hipStream_t s = (hipStream_t)stream;
+  PgMarg m(ws_dev, n_nodes, n_loops, n_query);
+  pgm_reset_kernel<<<1, 64, 0, s>>>(record_dev, n_loops);
+  const double* gamma = m.gamma;
+  if (n_loops == 0) {   // dead reckoning: Gamma alone, scanned here
+    const int n = n_nodes - 1, nbc = (int)m.nbc;
+    double* goff = m.gsum + (size_t)36 * nbc;
+    pgl_gamma_local_kernel<<<dim3(nbc, 6), PG_B, 0, s>>>(n, chain_dev, m.gamma, m.gsum);
+    pgl_gamma_sums_kernel<<<1, 64, 0, s>>>(nbc, m.gsum, goff);
+    pgl_gamma_add_kernel<<<dim3(nbc, 6), PG_B, 0, s>>>(n, goff, m.gamma);
+  } else {
+    PgLoops lp(const_cast<double*>(loops_dev), n_nodes, n_loops);
+    gamma = lp.gamma;
+    for (int64_t t0 = 0; t0 < m.tiles; t0 += PGM_CHUNK) {
+      const int64_t nt = m.tiles - t0 < PGM_CHUNK ? m.tiles - t0 : PGM_CHUNK;
+      pgm_sweep_kernel<<<(int)nt, PG_B, 0, s>>>(n_nodes, n_loops, (int)lp.sp, t0 * PGM_TN, n_query, node_ids_dev, lp.gamma, lp.C, lp.span,
+                                                lp.F, m.Y, cov_dev, record_dev);
+    }
+  }
+  pgm_finish_kernel<<<(int)m.nbq, PG_B, 0, s>>>(n_nodes, n_query, n_loops > 0, frame, node_ids_dev, poses_dev, chain_dev, gamma, cov_dev,
+                                                m.part, record_dev);
+  pgm_record_kernel<<<1, PG_B, 0, s>>>(m.part, (int)m.nbq, record_dev);
+  OVN_HIP_CHECK(hipGetLastError());
+  return OVN_OK;
 }
 
 }  // extern "C"

@@ -1637,6 +1637,46 @@ class OvnEngine:
                        "ovn_pose_graph_precondition")
         return out
 
+    POSE_GRAPH_COV_FRAMES = {"local": 0, "position": 1}      # OVN_POSE_GRAPH_COV_LOCAL, OVN_POSE_GRAPH_COV_POSITION
+
+    def pose_graph_marginals_bytes(self, n_nodes: int, n_loops: int, n_query: int) -> int:
+        """The size of the workspace of `pose_graph_marginals` (ovn_pose_graph_marginals_bytes); 0 outside the limits."""
+        return int(self.lib.ovn_pose_graph_marginals_bytes(int(n_nodes), int(n_loops), int(n_query)))
+
+    def pose_graph_marginals(self, poses: torch.Tensor, buf: Dict[str, torch.Tensor], node_ids: torch.Tensor, n_loops: int,
+                             frame: str = "position", cov: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None,
+                             record: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """cov (K,6,6): the marginal covariances of the nodes node_ids (K) int32 from the linearization (with chain) that `buf` holds
+        for `poses` and, for n_loops >= 1, the `pose_graph_loops_prepare` after it (ovn_pose_graph_marginals).
+        frame: "local" (the optimizer's delta_k) or "position" (position and rotation vector in the world).  Slot 15 of the record
+        counts the ids outside [0, N), whose blocks are NaN; slot 7 is set, and cov left as it was, when a pivot had failed."""
+        n, nl = int(poses.shape[0]), int(n_loops)
+        f64 = torch.float64
+        if frame not in self.POSE_GRAPH_COV_FRAMES:
+            raise _lib.OvnError("pose_graph_marginals: no frame %r (local, position)" % (frame,))
+        self._pg_tensor("pose_graph_marginals: poses", poses, f64, (n, 4, 4))
+        ids = self._pg_tensor("pose_graph_marginals: node_ids", node_ids, torch.int32, None)
+        if ids.dim() != 1 or ids.shape[0] < 1:
+            raise _lib.OvnError("pose_graph_marginals: node_ids must be (K,) with K >= 1, got %s" % (tuple(ids.shape),))
+        k = int(ids.shape[0])
+        nbytes = self.pose_graph_marginals_bytes(n, nl, k)
+        if nbytes == 0:
+            raise _lib.OvnError("pose_graph_marginals: %d nodes, %d loop edges, %d queried nodes are outside the limits" % (n, nl, k))
+        self._pg_tensor("pose_graph_marginals: buf['chain']", buf.get("chain"), f64, (n - 1, 2, 6, 6))
+        lp = self._pg_loops(buf, n, nl, "pose_graph_marginals") if nl > 0 else None
+        rec = self._pg_tensor("pose_graph_marginals: record", buf["record"] if record is None else record, f64, (16,))
+        cov = torch.zeros((k, 6, 6), dtype=f64, device=self.device) if cov is None else \
+            self._pg_tensor("pose_graph_marginals: cov", cov, f64, (k, 6, 6))
+        ws = torch.empty(nbytes // 8, dtype=f64, device=self.device) if ws is None else \
+            self._pg_tensor("pose_graph_marginals: ws", ws, f64, None)
+        if ws.numel() * 8 < nbytes:
+            raise _lib.OvnError("pose_graph_marginals: ws holds %d bytes, %d are needed" % (ws.numel() * 8, nbytes))
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.ovn_pose_graph_marginals(
+                self._h, self._stream(), _ptr(poses), n, n - 1 + nl, nl, _ptr(buf["chain"]), _ptr(lp), _ptr(ids), k,
+                self.POSE_GRAPH_COV_FRAMES[frame], _ptr(cov), _ptr(ws), _ptr(rec)), "ovn_pose_graph_marginals")
+        return cov
+
     def pose_graph_retract(self, poses: torch.Tensor, fixed: torch.Tensor, buf: Dict[str, torch.Tensor],
                            out: Optional[torch.Tensor] = None, record: Optional[torch.Tensor] = None) -> torch.Tensor:
         """out (N,4,4) = T_i Exp(delta_i) with delta = buf["delta"] (ovn_pose_graph_retract); |delta|_inf goes to slot 12 of the record."""

@@ -111,3 +111,34 @@ def detect_offline(infer, frames: Sequence[int], traj_xy: np.ndarray, traj_lengt
     refs = [list(gate_candidates(f, traj_xy, traj_length, ellipse, **gate_kw)) for f in frames]
     infer.cache_frames(max(frames) + 1)
     return infer.infer_best_match_batch(frames, refs, overlap_thres)
+
+
+# ---- the covariance file of demo3 ("generated from the SLAM or odometry methods", demo3_lcd.py:215-218) ------------------------------
+def write_covariances(path: str, cov) -> None:
+    """One line per frame: the 36 entries of its 6 x 6 pose covariance, row-major, separated by blanks, each written with `repr`
+    (the shortest text that reads back to the same float64).  `PoseGraph.marginals(frame="position")` is the producer."""
+    cov = np.asarray(cov, np.float64)
+    if cov.ndim != 3 or cov.shape[1:] != (6, 6):
+        raise ValueError("write_covariances: (n,6,6) covariances, got %s" % (cov.shape,))
+    with open(path, "w") as f:
+        for c in cov:
+            f.write(" ".join(repr(float(v)) for v in c.reshape(36)) + "\n")
+
+
+def read_covariances(path: str) -> np.ndarray:
+    """(n,6,6) float64 from the file `write_covariances` writes, read as demo3 reads it: split on blanks, 36 numbers per line."""
+    with open(path) as f:
+        rows = [line.replace("\n", "").split() for line in f.readlines()]
+    rows = [r for r in rows if r]
+    if any(len(r) != 36 for r in rows):
+        raise ValueError("%s: expected 36 numbers per line" % path)
+    return np.asarray(rows, dtype=float).reshape((-1, 6, 6))
+
+
+def ellipses_from_covariances(cov, nstd: float = 3.0) -> List[Tuple[float, float, float]]:
+    """Per frame the (width, height, angle_deg) that `covariance_ellipse` gives its covariance's top-left 2 x 2: the list
+    `gate_candidates` takes one entry of per frame."""
+    cov = np.asarray(cov, np.float64)
+    if cov.ndim != 3 or cov.shape[1] < 2 or cov.shape[2] < 2:
+        raise ValueError("ellipses_from_covariances: (n,6,6) covariances, got %s" % (cov.shape,))
+    return [covariance_ellipse(c, nstd) for c in cov]

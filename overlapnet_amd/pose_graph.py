@@ -5,7 +5,8 @@ distributes the loop error over the trajectory.  Nodes are poses (4,4) sensor to
 T_i^-1 T_j with information Omega (6 x 6, twist order (v, omega)).  The statement -- residual, Jacobians, Huber weights, normal
 equations, preconditioners -- is in include/ovn_hip.h and DESIGN.md section 32; the kernels are csrc/pose_graph.hip.  A drive with
 many loop closures has a third preconditioner, "loops" (DESIGN.md section 33): the exact inverse of the undamped Hessian of the
-odometry chain plus up to MAX_LOOPS loop edges, prepared after every full linearization.
+odometry chain plus up to MAX_LOOPS loop edges, prepared after every full linearization.  `PoseGraph.marginals` returns that
+inverse's diagonal blocks, the marginal pose covariances: the covariance file and search ellipses of `lcd`.
 
 The outer loop is Levenberg-Marquardt on the host and reads one 16-double record per step (plus one per chunk of conjugate-gradient
 iterations): lambda starts at 0 (Gauss-Newton); a trial step T Exp(delta) is accepted when the cost does not rise, then lambda <-
@@ -281,3 +282,50 @@ class PoseGraph:
         self.poses = poses.cpu().numpy()
         chi = buf["chi"].cpu().numpy()
         return Result(self.poses.copy(), cost0, cost, outer, cg, converged, chi * chi, buf["weight"].cpu().numpy())
+
+    # -- marginal covariances --------------------------------------------------------------------------------------------------------------
+    def marginals(self, nodes=None, frame: str = "position", huber: Optional[float] = None, poses=None) -> np.ndarray:
+        """(K,6,6): the marginal covariance of every node in `nodes` (None: all N, in order) -- the diagonal blocks of the inverse of
+        the undamped Hessian at self.poses (`optimize` leaves them at its result; poses= takes another (N,4,4) point), relative to the
+        fixed node 0, whose block is zero.  frame: "position" (position in the world, rotation vector in the
+        world; the top-left 2 x 2 is the x, y covariance of a search ellipse, `lcd.ellipses_from_covariances`) or "local" (the
+        optimizer's delta_k).  huber: the robust kernel whose weights the linearization takes, None = least squares.  The graph must
+        be a chain plus at most MAX_LOOPS loop edges; with no loop edge the result is dead-reckoning covariance propagation."""
+        if not self.chain_available():
+            raise ValueError("marginal covariances need edges 0 .. N - 2 to be the odometry steps (k, k + 1) in order and node 0 to be "
+                             "the only fixed node")
+        if self.loops > MAX_LOOPS:
+            raise ValueError("marginal covariances take at most %d loop edges after the chain, the graph has %d" % (MAX_LOOPS, self.loops))
+        if frame not in ("position", "local"):
+            raise ValueError("no frame %r (position, local)" % (frame,))
+        k = float("inf") if huber is None else float(huber)
+        if not k > 0.0:
+            raise ValueError("huber must be > 0 (None: least squares), got %r" % (huber,))
+        ids = np.arange(self.n, dtype=np.int32) if nodes is None else np.asarray(nodes).reshape(-1)
+        if ids.size < 1:
+            raise ValueError("marginals: no node asked for")
+        if not np.issubdtype(ids.dtype, np.integer) or ids.min() < 0 or ids.max() >= self.n:
+            raise ValueError("marginals: nodes must be integers in 0..%d" % (self.n - 1))
+        p = self.poses if poses is None else np.array(poses, np.float64)
+        if p.shape != (self.n, 4, 4):
+            raise ValueError("poses must be (%d,4,4), got %s" % (self.n, p.shape))
+        self._check()
+        eng, dev = self.engine, self.engine.device
+        e, nl = len(self._ij), self.loops
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        ij = up(self.edges)
+        meas = up(np.asarray(self._z, np.float64).reshape(e, 4, 4))
+        info = up(np.asarray(self._info, np.float64).reshape(e, 6, 6))
+        fixed = up(self.fixed.astype(np.uint8))
+        ptr, lst = (up(a) for a in incidence(self.n, self.edges))
+        pd = up(p)
+        buf = eng.pose_graph_buffers(self.n, e, chain=True, loops=nl)
+        rec = eng.pose_graph_linearize(pd, fixed, ij, meas, info, ptr, lst, k, buf)
+        if nl > 0:
+            rec = eng.pose_graph_loops_prepare(pd, ij, info, buf)
+        cov = eng.pose_graph_marginals(pd, buf, up(ids.astype(np.int32)), nl, frame=frame)
+        r = buf["record"].cpu().numpy()
+        if r[7] != 0:
+            raise _lib.OvnError("marginal covariances: %d diagonal blocks and %d pivots of the loop edges' factorization are not positive "
+                                "(an information matrix, or a free node no finite edge holds)" % (int(r[2]), int(r[13])))
+        return cov.cpu().numpy()

@@ -9,7 +9,9 @@
      `infer_top_k_batch` against the frames at least --min-gap frames earlier
   3  verification: `Infer.verify_top_k` for every frame that has a candidate: one ICP launch per frame
   4  graph: the odometry steps and the accepted loop closures, `PoseGraph.optimize`
-  5  --out: the optimized poses (`odometry.write_poses`); --mesh: the scans re-fused at them (`TsdfVolume`)
+  5  --out: the optimized poses (`odometry.write_poses`); --mesh: the scans re-fused at them (`TsdfVolume`); --covariances: the
+     optimized graph's marginal pose covariances (`PoseGraph.marginals`, `lcd.write_covariances`)
+--gate-sigma N narrows step 2 to the frames inside the N-sigma ellipse of dead reckoning's covariance; it has no default value.
 
 --overlap-thres, --min-fitness, --max-rms, --odom-sigma, --loop-sigma and --huber have no defaults: no acceptance threshold or noise
 level has been measured on real loop closures, so each is given or is explicitly `none` (thresholds and --huber; with both --min-fitness
@@ -62,9 +64,15 @@ def parse(argv=None):
     ap.add_argument("--fov-down", type=float, default=-25.0)
     ap.add_argument("--max-range", type=float, default=50.0)
     ap.add_argument("--batch", type=int, default=64, help="frames per `infer_top_k_batch` call")
+    ap.add_argument("--covariances", default=None, help="also write the optimized graph's marginal pose covariances (position frame), "
+                    "one line of 36 numbers per scan: the covariance file of the reference's loop-closure demo")
+    ap.add_argument("--gate-sigma", type=float, default=None, help="for frame k take only candidates inside the N-sigma x, y ellipse of "
+                    "the odometry-only graph's marginal covariance at k (with --min-gap); not given: every earlier frame")
     a = ap.parse_args(argv)
     if a.min_gap < 1 or a.top_k < 1 or a.batch < 1:
         ap.error("--min-gap, --top-k and --batch must be >= 1")
+    if a.gate_sigma is not None and not a.gate_sigma > 0.0:
+        ap.error("--gate-sigma must be > 0")
     return a
 
 
@@ -83,7 +91,7 @@ def main(argv=None):
     offsets[1:] = np.cumsum([c.shape[0] for c in scans])
     points = np.concatenate(scans)
 
-    from overlapnet_amd import odometry, pose_graph, tsdf
+    from overlapnet_amd import lcd, odometry, pose_graph, tsdf
     from overlapnet_amd.infer import Infer
     t0 = time.time()
     infer = Infer(cfg)
@@ -99,10 +107,21 @@ def main(argv=None):
 
     infer.cache_frames(n)
     queries = list(range(a.min_gap, n))
+    references = {c: np.arange(0, c - a.min_gap + 1) for c in queries}
+    if a.gate_sigma is not None:      # the search space of the reference's demo: the ellipse of dead reckoning's covariance at the frame
+        dead = pose_graph.PoseGraph(eng, poses)
+        dead.add_odometry(poses, pose_graph.information_from_sigmas(*a.odom_sigma))
+        ellipses = lcd.ellipses_from_covariances(dead.marginals(frame="position"), a.gate_sigma)
+        xy = poses[:, :2, 3]
+        length = lcd.travelled_distances(xy)
+        references = {c: lcd.gate_candidates(c, xy, length, ellipses[c], inactive_time_thres=a.min_gap - 1,
+                                             inactive_dist_thres=-np.inf) for c in queries}
+        queries = [c for c in queries if len(references[c])]
+        line["frames_with_gated_candidates"] = len(queries)
     with_candidates = []
     for s in range(0, len(queries), a.batch):
         cur = queries[s:s + a.batch]
-        found = infer.infer_top_k_batch(cur, [np.arange(0, c - a.min_gap + 1) for c in cur], k=a.top_k, overlap_thres=a.overlap_thres)
+        found = infer.infer_top_k_batch(cur, [references[c] for c in cur], k=a.top_k, overlap_thres=a.overlap_thres)
         with_candidates += [c for c, f in zip(cur, found) if f]
     graph = pose_graph.PoseGraph(eng, poses)
     graph.add_odometry(poses, pose_graph.information_from_sigmas(*a.odom_sigma))
@@ -110,7 +129,7 @@ def main(argv=None):
     thresholds = a.min_fitness is not None or a.max_rms is not None
     verified = 0
     for c in with_candidates:
-        checked = infer.verify_top_k(c, np.arange(0, c - a.min_gap + 1), k=a.top_k, overlap_thres=a.overlap_thres,
+        checked = infer.verify_top_k(c, references[c], k=a.top_k, overlap_thres=a.overlap_thres,
                                      min_fitness=a.min_fitness, max_rms=a.max_rms)
         verified += len(checked)
         graph.add_loop_closures(c, checked, loop_info, only_accepted=thresholds)
@@ -122,6 +141,9 @@ def main(argv=None):
     line.update(preconditioner=graph.choose_preconditioner(a.preconditioner), outer_iterations=res.outer_iterations,
                 cg_iterations=res.cg_iterations, converged=bool(res.converged), cost_initial=res.cost_initial, cost_final=res.cost_final,
                 loop_edges_turned_down=int((res.weights[n - 1:] < 1.0).sum()), largest_correction_m=float(moved.max()))
+    if a.covariances:
+        lcd.write_covariances(a.covariances, graph.marginals(frame="position", huber=a.huber))
+        line["covariances"] = a.covariances
     if a.mesh:
         lo, hi = odometry.bounds_from_poses(res.poses, a.max_range)
         vol = tsdf.TsdfVolume(eng, lo, hi, a.voxel)
