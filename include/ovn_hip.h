@@ -491,7 +491,10 @@ int ovn_mcl_resample(ovn_ctx* ctx, const float* particles_dev, int n_particles, 
  * (index among the points that pass the range filter, utils.py:117-118), normal (n,H,W,3), and
  * stacked (n,H,W,C) = the leg input assembled in the reference's channel order depth|normals|intensity
  * (ImagePairOverlapOrientationSequence.py:143-207) according to the use_* flags.  Empty pixels = -1.
- * max_points_per_scan bounds the per-scan launch (>= the largest scan). */
+ * max_points_per_scan bounds the per-scan launch (>= the largest scan).
+ * Limits, OVN_ERR_ARG before any launch: H*W <= 2^31 - 1 (a pixel's index inside its image is a 32-bit integer; indices into the
+ * batch are 64-bit), at most 65535 scans per call (the scatter's grid carries the scan in its y dimension), fewer than 2^32 points
+ * per scan. */
 int ovn_project(ovn_ctx* ctx, const float* points_dev, const int64_t* offsets_dev, int n_scans,
                 int64_t max_points_per_scan, int proj_h, int proj_w, double fov_up_deg, double fov_down_deg,
                 double max_range, float* range_dev, float* vertex_dev, float* intensity_dev,
@@ -512,7 +515,8 @@ int ovn_project(ovn_ctx* ctx, const float* points_dev, const int64_t* offsets_de
  * range / vertex / intensity / idx / normal are bit for bit what ovn_project writes at the same max_range, and so are the
  * depth / normal / intensity channels of stacked_dev.  One scatter serves both views: a pixel's nearest point under the semantic
  * filter is its nearest cue point when its depth is < max_range, and otherwise the pixel has no cue point.  OVN_ERR_ARG for
- * n_classes outside 1..OVN_SEMANTIC_CLASSES_MAX, a NULL probs_dev with a probability output, more than 65535 scans. */
+ * n_classes outside 1..OVN_SEMANTIC_CLASSES_MAX, a NULL probs_dev with a probability output, more than 65535 scans,
+ * H*W > 2^31 - 1. */
 #define OVN_SEMANTIC_CLASSES_MAX 64
 int ovn_project_semantic(ovn_ctx* ctx, const float* points_dev, const int64_t* offsets_dev, int n_scans,
                          int64_t max_points_per_scan, int proj_h, int proj_w, double fov_up_deg, double fov_down_deg,
@@ -521,7 +525,7 @@ int ovn_project_semantic(ovn_ctx* ctx, const float* points_dev, const int64_t* o
                          float* stacked_dev, int use_depth, int use_normals, int use_semantic, int use_intensity, void* stream);
 
 /* Normal map alone from given range (n,H,W) and vertex (n,H,W,4) images -> normal (n,H,W,3)
- * (src/utils/utils.py:137-186 gen_normal_map). */
+ * (src/utils/utils.py:137-186 gen_normal_map).  OVN_ERR_ARG before any launch for H*W > 2^31 - 1. */
 int ovn_normals(ovn_ctx* ctx, const float* range_dev, const float* vertex_dev, int n_scans, int proj_h, int proj_w,
                 float* normal_dev, void* stream);
 
@@ -817,7 +821,8 @@ int ovn_pose_graph_marginals(ovn_ctx* ctx, void* stream, const double* poses_dev
 /* The per-point part of range_projection alone (src/utils/utils.py:75-104), exactly as ovn_project's scatter kernel evaluates it:
  * for each of n float32 points (x,y,z,*) yaw = -np.arctan2(y, x), pitch = np.arcsin(z / depth) with NumPy's float32 results
  * (csrc/svml_f32.h) and the pixel py * proj_w + px the point falls into (-1 for a point the range filter drops).  Outputs may
- * be NULL.  A validation entry: lets a test compare the two angle functions with the reference's NumPy on millions of points. */
+ * be NULL.  A validation entry: lets a test compare the two angle functions with the reference's NumPy on millions of points.
+ * OVN_ERR_ARG before any launch for H*W > 2^31 - 1 (the pixel is a 32-bit integer). */
 int ovn_projection_angles(ovn_ctx* ctx, const float* points_dev, int64_t n_points, int proj_h, int proj_w, double fov_up_deg,
                           double fov_down_deg, double max_range, float* yaw_dev, float* pitch_dev, int32_t* pixel_dev,
                           void* stream);
@@ -828,7 +833,10 @@ int ovn_projection_angles(ovn_ctx* ctx, const float* points_dev, int64_t n_point
  *   points/offsets as in ovn_project; ref_poses_dev (n,4,4) f64 row-major or NULL (identity); inv_cur_pose_dev (4,4) f64 or
  *   NULL (identity) -- with both NULL this is the current frame's own range image (com_overlap_yaw.py:30-31).
  * ovn_gt_overlap_counts: counts_dev[s] = #{ref_range[s] > 0 and |ref_range[s] - cur_range| < 1} for s < n, and
- *   counts_dev[n] = #{cur_range > 0} (`valid_num`, :32-33): overlap[s] = counts[s] / counts[n] (:42-45). */
+ *   counts_dev[n] = #{cur_range > 0} (`valid_num`, :32-33): overlap[s] = counts[s] / counts[n] (:42-45).
+ * Limits, OVN_ERR_ARG before any launch: H*W <= 2^31 - 1 for both calls (a pixel's index inside its image is a 32-bit integer),
+ * at most 65535 scans per ovn_gt_range_images call (its grid carries the scan in the y dimension) and at most 2^31 - 2 per
+ * ovn_gt_overlap_counts call (one workgroup per scan and one more). */
 int ovn_gt_range_images(ovn_ctx* ctx, const float* points_dev, const int64_t* offsets_dev, int n_scans,
                         int64_t max_points_per_scan, const double* ref_poses_dev, const double* inv_cur_pose_dev, int proj_h,
                         int proj_w, double fov_up_deg, double fov_down_deg, double max_range, float* range_dev, void* stream);

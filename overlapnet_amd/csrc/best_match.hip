@@ -32,9 +32,10 @@ __global__ __launch_bounds__(BM_THREADS) void best_match_kernel(const float* __r
   __shared__ float sv[BM_THREADS / 64];
   __shared__ int sk[BM_THREADS / 64];
   Best b = {0.f, -1};
-  for (int k = threadIdx.x; k < n; k += BM_THREADS) {
+  // unsigned counter: the last k + BM_THREADS passes 2^31 - 1 when n is within BM_THREADS of it (n < 2^31 always)
+  for (uint32_t k = threadIdx.x; k < (uint32_t)n; k += BM_THREADS) {
     const float v = overlap[k];
-    if (v == v) b = better(b, Best{v, k});  // NaN scores never win
+    if (v == v) b = better(b, Best{v, (int)k});  // NaN scores never win
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {

@@ -156,12 +156,13 @@ __global__ __launch_bounds__(256) void gt_count_kernel(const float* __restrict__
   int c = 0;
   if (s < n) {
     const float* r = ref + (long long)s * npix;
-    for (int i = threadIdx.x; i < npix; i += 256) {
+    // unsigned counters: the last i + 256 passes 2^31 - 1 when npix is within 256 of it (npix <= 2^31 - 1 always)
+    for (uint32_t i = threadIdx.x; i < (uint32_t)npix; i += 256) {
       const float v = r[i];
       if (v > 0.0f && fabsf(v - cur[i]) < 1.0f) ++c;
     }
   } else {
-    for (int i = threadIdx.x; i < npix; i += 256)
+    for (uint32_t i = threadIdx.x; i < (uint32_t)npix; i += 256)
       if (cur[i] > 0.0f) ++c;
   }
 #pragma unroll

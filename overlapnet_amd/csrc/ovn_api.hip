@@ -1263,6 +1263,10 @@ int ovn_project(ovn_ctx* ctx, const float* points_dev, const int64_t* offsets_de
                 int64_t max_points_per_scan, int proj_h, int proj_w, double fov_up_deg, double fov_down_deg,
                 double max_range, float* range_dev, float* vertex_dev, float* intensity_dev, int32_t* idx_dev,
                 float* normal_dev, float* stacked_dev, int use_depth, int use_normals, int use_intensity, void* stream) {
+  // the kernels form H * W and a pixel's index in 32 bits, and the scatter's grid carries the scan in its y dimension
+  OVN_REQUIRE(proj_h <= 0 || proj_w <= 0 || (int64_t)proj_h * proj_w <= 2147483647ll, OVN_ERR_ARG,
+              "ovn_project: %d x %d pixels per image, at most 2^31 - 1 (H*W)", proj_h, proj_w);
+  OVN_REQUIRE(n_scans <= 65535, OVN_ERR_ARG, "ovn_project: %d scans, at most 65535 per call", n_scans);
   OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_project: ctx is NULL");
   OVN_REQUIRE(n_scans == 0 || (points_dev || max_points_per_scan == 0), OVN_ERR_ARG, "ovn_project: points is NULL");
   OVN_REQUIRE(n_scans == 0 || offsets_dev, OVN_ERR_ARG, "ovn_project: offsets is NULL");
@@ -1282,6 +1286,8 @@ int ovn_project_semantic(ovn_ctx* ctx, const float* points_dev, const int64_t* o
               "ovn_project_semantic: n_classes %d outside 1..%d", n_classes, OVN_SEMANTIC_CLASSES_MAX);
   OVN_REQUIRE(probs_dev || !(semantic_dev || (stacked_dev && use_semantic)), OVN_ERR_ARG,
               "ovn_project_semantic: probabilities requested but probs is NULL");
+  OVN_REQUIRE(proj_h <= 0 || proj_w <= 0 || (int64_t)proj_h * proj_w <= 2147483647ll, OVN_ERR_ARG,
+              "ovn_project_semantic: %d x %d pixels per image, at most 2^31 - 1 (H*W)", proj_h, proj_w);
   OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_project_semantic: ctx is NULL");
   OVN_REQUIRE(n_scans == 0 || (points_dev || max_points_per_scan == 0), OVN_ERR_ARG, "ovn_project_semantic: points is NULL");
   OVN_REQUIRE(n_scans == 0 || offsets_dev, OVN_ERR_ARG, "ovn_project_semantic: offsets is NULL");
@@ -1296,6 +1302,8 @@ int ovn_project_semantic(ovn_ctx* ctx, const float* points_dev, const int64_t* o
 int ovn_projection_angles(ovn_ctx* ctx, const float* points_dev, int64_t n_points, int proj_h, int proj_w, double fov_up_deg,
                           double fov_down_deg, double max_range, float* yaw_dev, float* pitch_dev, int32_t* pixel_dev,
                           void* stream) {
+  OVN_REQUIRE(proj_h <= 0 || proj_w <= 0 || (int64_t)proj_h * proj_w <= 2147483647ll, OVN_ERR_ARG,
+              "ovn_projection_angles: %d x %d pixels per image, at most 2^31 - 1 (H*W)", proj_h, proj_w);
   OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_projection_angles: ctx is NULL");
   OVN_REQUIRE(n_points >= 0 && proj_h > 0 && proj_w > 0, OVN_ERR_ARG, "ovn_projection_angles: bad sizes");
   if (n_points == 0) return OVN_OK;
@@ -1307,6 +1315,8 @@ int ovn_projection_angles(ovn_ctx* ctx, const float* points_dev, int64_t n_point
 
 int ovn_normals(ovn_ctx* ctx, const float* range_dev, const float* vertex_dev, int n_scans, int proj_h, int proj_w,
                 float* normal_dev, void* stream) {
+  OVN_REQUIRE(proj_h <= 0 || proj_w <= 0 || (int64_t)proj_h * proj_w <= 2147483647ll, OVN_ERR_ARG,
+              "ovn_normals: %d x %d pixels per image, at most 2^31 - 1 (H*W)", proj_h, proj_w);
   OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_normals: ctx is NULL");
   OVN_REQUIRE(n_scans >= 0 && proj_h > 0 && proj_w > 0, OVN_ERR_ARG, "ovn_normals: bad sizes");
   if (n_scans == 0) return OVN_OK;
@@ -1452,6 +1462,8 @@ int ovn_tsdf_bricks(ovn_ctx* ctx, void* stream, const float* weight_dev, int nx,
 int ovn_gt_range_images(ovn_ctx* ctx, const float* points_dev, const int64_t* offsets_dev, int n_scans,
                         int64_t max_points_per_scan, const double* ref_poses_dev, const double* inv_cur_pose_dev, int proj_h,
                         int proj_w, double fov_up_deg, double fov_down_deg, double max_range, float* range_dev, void* stream) {
+  OVN_REQUIRE(proj_h <= 0 || proj_w <= 0 || (int64_t)proj_h * proj_w <= 2147483647ll, OVN_ERR_ARG,
+              "ovn_gt_range_images: %d x %d pixels per image, at most 2^31 - 1 (H*W)", proj_h, proj_w);
   OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_gt_range_images: ctx is NULL");
   OVN_REQUIRE(n_scans >= 0 && proj_h > 0 && proj_w > 0 && max_points_per_scan >= 0, OVN_ERR_ARG, "ovn_gt_range_images: bad sizes");
   if (n_scans == 0) return OVN_OK;
@@ -1464,6 +1476,10 @@ int ovn_gt_range_images(ovn_ctx* ctx, const float* points_dev, const int64_t* of
 
 int ovn_gt_overlap_counts(ovn_ctx* ctx, const float* ref_ranges_dev, const float* cur_range_dev, int n_scans, int proj_h,
                           int proj_w, int32_t* counts_dev, void* stream) {
+  OVN_REQUIRE(proj_h <= 0 || proj_w <= 0 || (int64_t)proj_h * proj_w <= 2147483647ll, OVN_ERR_ARG,
+              "ovn_gt_overlap_counts: %d x %d pixels per image, at most 2^31 - 1 (H*W)", proj_h, proj_w);
+  OVN_REQUIRE(n_scans <= 2147483646, OVN_ERR_ARG, "ovn_gt_overlap_counts: %d scans, at most 2^31 - 2 (one workgroup each and one more)",
+              n_scans);
   OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_gt_overlap_counts: ctx is NULL");
   OVN_REQUIRE(n_scans >= 0 && proj_h > 0 && proj_w > 0, OVN_ERR_ARG, "ovn_gt_overlap_counts: bad sizes");
   OVN_REQUIRE(cur_range_dev && counts_dev && (ref_ranges_dev || n_scans == 0), OVN_ERR_ARG, "ovn_gt_overlap_counts: NULL buffer");

@@ -63,7 +63,8 @@ __device__ __forceinline__ void for_each_score(const float* __restrict__ overlap
     }
     tail = n4 << 2;
   }
-  for (int i = tail + threadIdx.x; i < n; i += TK_THREADS) f(i, p[i]);
+  // unsigned: tail + threadIdx.x and the last i + TK_THREADS pass 2^31 - 1 when n is within TK_THREADS of it (n < 2^31 always)
+  for (uint32_t i = (uint32_t)tail + threadIdx.x; i < (uint32_t)n; i += TK_THREADS) f((int)i, p[i]);
 }
 
 // SEG = false: ovn_top_k, one workgroup on overlap[0, n).  SEG = true: ovn_top_k_segments, workgroup b on segment b =

@@ -77,8 +77,10 @@ def angle_diff(a, b):
     return d - 2 * np.pi * np.rint(d / (2 * np.pi))
 
 
-def lookup(x, y, cell_frame, origin_x, origin_y, resolution, nx, ny, M):
-    """float32, operation for operation: the frame of every position, -1 off the grid / non-finite / empty cell / entry >= M."""
+def lookup(x, y, cell_frame, origin_x, origin_y, resolution, nx, ny, M, cell_offset=0):
+    """float32, operation for operation: the frame of every position, -1 off the grid / non-finite / empty cell / entry >= M.
+    cell_offset: `cell_frame` holds the cells from flat index cell_offset on (a far block of a grid too large for the host); a
+    position on the grid whose cell lies outside that block is an error.  0 with the whole grid is the statement itself."""
     x, y = np.asarray(x, np.float32), np.asarray(y, np.float32)
     inv = np.float32(1.0 / float(resolution))
     with np.errstate(invalid="ignore", over="ignore"):
@@ -87,7 +89,11 @@ def lookup(x, y, cell_frame, origin_x, origin_y, resolution, nx, ny, M):
         ok = (fx >= 0) & (fx < np.float32(2147483648.0)) & (fy >= 0) & (fy < np.float32(2147483648.0))
         ix, iy = np.where(ok, fx, 0).astype(np.int64), np.where(ok, fy, 0).astype(np.int64)
     ok &= (ix < nx) & (iy < ny)
-    f = np.where(ok, np.asarray(cell_frame)[np.where(ok, iy * nx + ix, 0)], -1)
+    cells = np.asarray(cell_frame)
+    flat = np.where(ok, iy * nx + ix - int(cell_offset), 0)
+    if np.any(flat < 0) or np.any(flat >= cells.size):
+        raise IndexError("a position's cell lies outside the block of cells given (cell_offset %d, %d cells)" % (cell_offset, cells.size))
+    f = np.where(ok, cells[flat], -1)
     return np.where((f < 0) | (f >= M), -1, f).astype(np.int32)
 
 

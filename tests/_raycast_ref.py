@@ -43,29 +43,41 @@ def _lerp(a, b, f):
     return a + f * (b - a)
 
 
-def _cell_valid(Wt, mw, fl, shape_xyz, mask):
-    """(in bounds, seen) of the cells with base corner `fl` ((m,3) floats, NaN allowed); `seen` holds for in-bounds cells only."""
+def _cell_valid(Wt, mw, fl, shape_xyz, mask, offset=(0, 0, 0)):
+    """(in bounds, seen) of the cells with base corner `fl` ((m,3) floats, NaN allowed); `seen` holds for in-bounds cells only.
+    offset (i0, j0, k0): Wt (and mask) hold the block of the volume `shape_xyz` that starts there; every sample outside the block is
+    unseen, the returned indices are the block's, and "in bounds" then means inside the block (the only cells whose weights
+    can sit on the threshold)."""
     nx, ny, nz = shape_xyz
     with np.errstate(invalid="ignore"):
         inb = ((fl[:, 0] >= 0) & (fl[:, 0] <= nx - 2) & (fl[:, 1] >= 0) & (fl[:, 1] <= ny - 2) & (fl[:, 2] >= 0) & (fl[:, 2] <= nz - 2))
-    c = np.where(inb[:, None], fl, 0).astype(np.int64)
+    c = np.where(inb[:, None], fl, 0).astype(np.int64) - np.asarray(offset, np.int64)[None, :]
+    bz, by, bx = Wt.shape
+    inblock = inb & (c[:, 0] >= 0) & (c[:, 0] <= bx - 2) & (c[:, 1] >= 0) & (c[:, 1] <= by - 2) & (c[:, 2] >= 0) & (c[:, 2] <= bz - 2)
+    c = np.where(inblock[:, None], c, 0)
     i, j, k = c[:, 0], c[:, 1], c[:, 2]
-    seen = inb.copy()
+    seen = inblock.copy()
     if mask is not None:
         seen &= mask[k >> 3, j >> 3, i >> 3] != 0
     for cn in range(8):
         seen &= Wt[k + (cn >> 2), j + ((cn >> 1) & 1), i + (cn & 1)] >= mw
-    return inb, seen, (i, j, k)
+    return inblock, seen, (i, j, k)
 
 
 def raycast(tsdf, weight, origin, voxel, poses, H, W, dtype=np.float32, min_range=0.5, max_range=R.MAX_RANGE, step=None,
-            min_weight=1.0, mask=None, fov_up=R.FOV_UP, fov_down=R.FOV_DOWN, ambiguous=False):
+            min_weight=1.0, mask=None, fov_up=R.FOV_UP, fov_down=R.FOV_DOWN, ambiguous=False, index_offset=(0, 0, 0),
+            full_shape=None):
     """-> dict(range (n,H,W) dtype, vertex (n,H,W,4) dtype, denom (n,H,W): F_p - F of a hit[, ambiguous (n,H,W) bool]).  dtype float32
-    is the definition itself; float64 is the reference.  mask: a brick mask (the route with bricks_dev) or None."""
+    is the definition itself; float64 is the reference.  mask: a brick mask (the route with bricks_dev) or None.
+    index_offset (i0, j0, k0) with full_shape (nx, ny, nz): `tsdf` / `weight` (and `mask`) are the block of a volume of full_shape
+    that starts at that sample (multiples of 8), the rest of which is unseen (weight below min_weight); the rays are marched through
+    the whole volume's index space.  (0, 0, 0) and None are the statement itself."""
     dt = np.dtype(dtype).type
     D, Wt = np.asarray(tsdf, F32), np.asarray(weight, F32)
     nz, ny, nx = D.shape
-    shape = (nx, ny, nz)
+    shape = (nx, ny, nz) if full_shape is None else tuple(int(v) for v in full_shape)
+    off = tuple(int(v) for v in index_offset)
+    assert all(v % BRICK == 0 for v in off)
     step = voxel if step is None else step
     K = sample_count(min_range, max_range, step)
     assert 1 <= K <= MAX_SAMPLES
@@ -93,7 +105,7 @@ def raycast(tsdf, weight, origin, voxel, poses, H, W, dtype=np.float32, min_rang
         with np.errstate(all="ignore"):
             g = g_o[alive] + t * g_d[alive]
             fl = np.floor(g)
-        inb, valid, (i, j, kk) = _cell_valid(Wt, mw, fl, shape, mask)
+        inb, valid, (i, j, kk) = _cell_valid(Wt, mw, fl, shape, mask, off)
         F = np.zeros(alive.size, dt)
         v = np.flatnonzero(valid)
         if v.size:
@@ -125,7 +137,7 @@ def raycast(tsdf, weight, origin, voxel, poses, H, W, dtype=np.float32, min_rang
                     if not todo.any():
                         continue
                     alt = np.where(use[todo], other[todo], fl[rows][todo])
-                    _, alt_valid, _ = _cell_valid(Wt, mw, alt, shape, None)
+                    _, alt_valid, _ = _cell_valid(Wt, mw, alt, shape, None, off)
                     a[rows[todo]] |= alt_valid != base_valid[todo]
             # a corner weight equal to min_weight
             ib = np.flatnonzero(inb)

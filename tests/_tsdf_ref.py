@@ -55,9 +55,11 @@ def _angles(q0, q1, s, dtype, trig):
 
 
 def integrate(tsdf, weight, origin, voxel, trunc, max_weight, ranges, poses, fov_up=R.FOV_UP, fov_down=R.FOV_DOWN,
-              max_range=R.MAX_RANGE, dtype=np.float32, trig="svml", ambiguous=False):
+              max_range=R.MAX_RANGE, dtype=np.float32, trig="svml", ambiguous=False, index_offset=(0, 0, 0)):
     """-> dict(tsdf, weight (nz,ny,nx) dtype, updated (n,nz,ny,nx) bool: the scans that changed each sample[, ambiguous (nz,ny,nx)]).
-    The inputs are rounded to float32 first in either dtype; `tsdf` and `weight` are not modified."""
+    The inputs are rounded to float32 first in either dtype; `tsdf` and `weight` are not modified.
+    index_offset (i0, j0, k0): `tsdf` / `weight` are the block of a larger volume that starts at sample (i0, j0, k0) of it -- its
+    sample (i, j, k) sits at origin + (i0 + i, j0 + j, k0 + k) * voxel.  (0, 0, 0) is the statement itself."""
     dt = np.dtype(dtype).type
     nz, ny, nx = tsdf.shape
     t, w = tsdf.astype(dt), weight.astype(dt)
@@ -69,7 +71,8 @@ def integrate(tsdf, weight, origin, voxel, trunc, max_weight, ranges, poses, fov
     fda, fov = dt(F32(abs(down))), dt(F32(abs(down) + abs(up)))
     with np.errstate(over="ignore", invalid="ignore"):
         P = np.asarray(poses, np.float64).astype(F32)
-    k, j, i = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+    i0, j0, k0 = (int(v) for v in index_offset)
+    k, j, i = np.meshgrid(np.arange(nz) + k0, np.arange(ny) + j0, np.arange(nx) + i0, indexing="ij")
     p = [org[a] + idx.astype(dt) * vox for a, idx in enumerate((i, j, k))]
     updated = np.zeros((n, nz, ny, nx), bool)
     amb = np.zeros((nz, ny, nx), bool)
@@ -136,13 +139,16 @@ def tet_triangle_count(inside4):
     return {0: 0, 1: 1, 2: 2, 3: 1, 4: 0}[n]
 
 
-def triangles(tsdf, weight, origin, voxel, min_weight=1.0):
-    """(T,3,3) float32 in contract order: ascending cell index (x fastest), tetrahedron order, triangle order."""
+def triangles(tsdf, weight, origin, voxel, min_weight=1.0, index_offset=(0, 0, 0)):
+    """(T,3,3) float32 in contract order: ascending cell index (x fastest), tetrahedron order, triangle order.
+    index_offset (i0, j0, k0): the block of a larger volume, as in `integrate`: vertex coordinates are those of the larger volume
+    (the cells of a block keep the larger volume's order: k, then j, then i)."""
     D = np.asarray(tsdf, F32)
     Wt = np.asarray(weight, F32)
     nz, ny, nx = D.shape
     org = np.asarray(origin, np.float64).astype(F32)
     vox = F32(voxel)
+    off = [int(v) for v in index_offset]
     corner = lambda a, c: a[(c >> 2):nz - 1 + (c >> 2), ((c >> 1) & 1):ny - 1 + ((c >> 1) & 1), (c & 1):nx - 1 + (c & 1)]
     seen = np.ones((nz - 1, ny - 1, nx - 1), bool)
     inside = np.zeros((8, nz - 1, ny - 1, nx - 1), bool)
@@ -170,8 +176,8 @@ def triangles(tsdf, weight, origin, voxel, min_weight=1.0):
                 f = dl / (dl - dh)
                 xyz = []
                 for x in range(3):
-                    pl = org[x] + il[x].astype(F32) * vox
-                    ph = org[x] + ih[x].astype(F32) * vox
+                    pl = org[x] + (il[x] + off[x]).astype(F32) * vox
+                    ph = org[x] + (ih[x] + off[x]).astype(F32) * vox
                     xyz.append(pl + (ph - pl) * f)
                 pts.append(np.stack(xyz, -1))
             for qn in range(len(edges) // 3):
