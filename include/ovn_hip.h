@@ -664,6 +664,64 @@ int ovn_tsdf_raycast(ovn_ctx* ctx, void* stream, const float* tsdf_dev, const fl
 int ovn_tsdf_bricks(ovn_ctx* ctx, void* stream, const float* weight_dev, int nx, int ny, int nz, double min_weight,
                     uint8_t* bricks_dev);
 
+/* A TSDF volume that follows the sensor: a window of fixed size over a lattice fixed in the world, stored as a ring in each axis
+ * (csrc/tsdf.hip, csrc/tsdf_raycast.hip, csrc/tsdf_window.hip).  `stream` is the SECOND parameter of the four
+ * calls, as for ovn_tsdf_raycast; tests/test_gpu_tsdf_window_stream.py runs them on a non-default stream.  Every call only enqueues
+ * work on `stream` and restores the caller's device.  The four calls are additions: no existing prototype or behaviour changes, and
+ * OVN_ABI_VERSION stays, as it did when the dense TSDF calls were added.
+ *   lattice   sample (I, J, K), integers of either sign, sits at p = anchor + (float)(I, J, K) * voxel: the arithmetic of
+ *             ovn_tsdf_integrate with origin = anchor.  anchor: 3 doubles on the HOST, rounded to f32
+ *   window    the samples base <= (I, J, K) < base + (nx, ny, nz).  base, old_base, new_base, box_lo, box_hi: 3 int32 on the HOST
+ *   storage   tsdf_dev, weight_dev (nz,ny,nx) f32, x fastest; sample I of an axis lives in slot I mod n (floor modulus), likewise J, K.
+ *             A fresh window is tsdf = 1, weight = 0 at any base
+ *   WINDOW    what every call requires of (nx, ny, nz, base), OVN_ERR_ARG before any launch otherwise: nx, ny, nz multiples of 8 and
+ *             >= 16, nx ny nz <= 2^31 - 1, every component of base a multiple of 8, and |I| <= 2^20 for every sample of the window
+ *             ((float)I is exact, and the "|p| < 10^6 voxels" of ovn_tsdf_integrate holds).  An aligned run of 8 slots is then 8
+ *             consecutive lattice samples: ovn_tsdf_bricks on weight_dev as it is stored gives the mask of the aligned lattice bricks
+ * A window sample has the bits the same calls give the sample with that lattice index in a dense volume with origin = anchor: no
+ * float operation depends on where a sample is stored.
+ *
+ * ovn_tsdf_window_integrate: steps 1-7 of ovn_tsdf_integrate for every sample of the window; each scan's box of reachable samples is
+ * clamped to the window.  A wave's 64 consecutive slots are one interval of lattice x, or two when the seam of the ring falls inside the
+ * run; the scan's box is tested against both.  One writer per sample, no atomics: the same arguments give the same bits, and two calls
+ * give the bits of one.  Every other argument, error and the no-op for n == 0 are those of ovn_tsdf_integrate. */
+int ovn_tsdf_window_integrate(ovn_ctx* ctx, void* stream, float* tsdf_dev, float* weight_dev, int nx, int ny, int nz, const double* anchor,
+                              const int32_t* base, double voxel, double trunc, double max_weight, const float* range_dev,
+                              const double* poses_dev, int64_t n_scans, int proj_h, int proj_w, double fov_up_deg, double fov_down_deg,
+                              double max_range);
+
+/* ovn_tsdf_window_raycast: steps 1-6 of ovn_tsdf_raycast with origin = anchor.  A sample is VALID when its base corner (i, j, k) =
+ * floor(g) has base <= i <= base + nx - 2 (likewise j, k; a NaN fails) and all eight corners have weight >= min_weight; each of the
+ * eight corners is wrapped into its slot on its own.  bricks_dev: NULL, or the mask of ovn_tsdf_bricks for weight_dev as it is stored;
+ * the byte read is the one of the base corner's slot.  Every other argument, output, error and the no-op for n == 0 are those of
+ * ovn_tsdf_raycast. */
+int ovn_tsdf_window_raycast(ovn_ctx* ctx, void* stream, const float* tsdf_dev, const float* weight_dev, int nx, int ny, int nz,
+                            const double* anchor, const int32_t* base, double voxel, double min_weight, const uint8_t* bricks_dev,
+                            const double* poses_dev, int64_t n_scans, int proj_h, int proj_w, const float* cos_az_dev,
+                            const float* sin_az_dev, const float* cos_pitch_dev, const float* sin_pitch_dev, double min_range,
+                            double max_range, double step, float* range_dev, float* vertex_dev, float* normal_dev, float* stacked_dev,
+                            int use_depth, int use_normals);
+
+/* ovn_tsdf_window_shift: the window moves from old_base to new_base.  Every slot whose sample under new_base was not in the old window
+ * becomes (tsdf 1, weight 0); no other slot is written, and a sample in both windows keeps its slot and its bits.  One launch per moved
+ * axis, over the slab of slots that change hands alone: |new_base - old_base| of that axis times the full extent of the other two.  A
+ * move of a whole window or more on any axis clears everything; new_base == old_base launches nothing.  The caller extracts what it
+ * wants to keep of the leaving samples BEFORE this call (ovn_tsdf_window_triangles under old_base).
+ * OVN_ERR_ARG, before any launch: a NULL buffer or base, WINDOW violated by old_base or by new_base. */
+int ovn_tsdf_window_shift(ovn_ctx* ctx, void* stream, float* tsdf_dev, float* weight_dev, int nx, int ny, int nz, const int32_t* old_base,
+                          const int32_t* new_base);
+
+/* ovn_tsdf_window_triangles: marching tetrahedra exactly as ovn_tsdf_triangles, over the cells whose low corner (I, J, K) lies in
+ * box_lo <= (I, J, K) < box_hi.  Triangles appear in ascending cell order WITHIN THE BOX, x fastest, then tetrahedron and triangle
+ * order; vertex coordinates are lattice positions, so a cell gives the bits it gives in a dense volume with origin = anchor.  An empty
+ * box (box_lo == box_hi on an axis) counts 0.  triangles_dev, capacity, n_triangles_dev: the count / capacity contract of
+ * ovn_tsdf_triangles.
+ * OVN_ERR_ARG, before any launch: what ovn_tsdf_triangles refuses, WINDOW violated, a NULL box, box_lo > box_hi on an axis, or a cell
+ * with a corner outside the window: box_lo < base or box_hi > base + n - 1 on an axis. */
+int ovn_tsdf_window_triangles(ovn_ctx* ctx, void* stream, const float* tsdf_dev, const float* weight_dev, int nx, int ny, int nz,
+                              const double* anchor, const int32_t* base, double voxel, double min_weight, const int32_t* box_lo,
+                              const int32_t* box_hi, float* triangles_dev, int64_t capacity, int64_t* n_triangles_dev);
+
 /* SE(3) pose-graph optimization, the back end behind the loop closures of ovn_top_k + ovn_icp_register (csrc/pose_graph.hip;
  * DESIGN.md section 32; restated in NumPy by tests/_pose_graph_ref.py).  Everything is fp64.  `stream` is the SECOND parameter of
  * these calls, as for ovn_tsdf_raycast; tests/test_gpu_pose_graph_stream.py runs them on a non-default stream.  Every call only

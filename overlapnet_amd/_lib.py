@@ -82,6 +82,15 @@ SIGNATURES = {
                                    C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp,
                                    C.c_int, C.c_int]),
     "ovn_tsdf_bricks": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_double, _vp]),
+    "ovn_tsdf_window_integrate": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), _i32p, C.c_double,
+                                            C.c_double, C.c_double, _vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_double,
+                                            C.c_double]),
+    "ovn_tsdf_window_raycast": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), _i32p, C.c_double,
+                                          C.c_double, _vp, _vp, C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_double, C.c_double,
+                                          C.c_double, _vp, _vp, _vp, _vp, C.c_int, C.c_int]),
+    "ovn_tsdf_window_shift": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _i32p, _i32p]),
+    "ovn_tsdf_window_triangles": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), _i32p, C.c_double,
+                                            C.c_double, _i32p, _i32p, _vp, C.c_int64, _vp]),
     "ovn_pose_graph_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "ovn_pose_graph_linearize": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_double] + [_vp] * 11),
     "ovn_pose_graph_solve": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int] + [_vp] * 7 + [C.c_int, C.c_double, C.c_double, C.c_int,

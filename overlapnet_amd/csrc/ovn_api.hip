@@ -1376,41 +1376,144 @@ bool tsdf_volume_ok(int nx, int ny, int nz, const double* origin, double voxel) 
     if (!std::isfinite((float)origin[a])) return false;
   return true;
 }
+
+// the window of ovn_tsdf_window_*: dimensions that are multiples of 8 and >= 16, a base of multiples of 8, every index within 2^20
+constexpr int WINDOW_MAX_INDEX = 1 << 20;
+bool tsdf_window_ok(int nx, int ny, int nz, const int* base, OvnRing* ring) {
+  const int n[3] = {nx, ny, nz};
+  if (!base) return false;
+  for (int a = 0; a < 3; ++a) {
+    if (n[a] < 16 || n[a] % 8 != 0 || base[a] % 8 != 0) return false;
+    if (base[a] < -WINDOW_MAX_INDEX || (int64_t)base[a] + n[a] - 1 > WINDOW_MAX_INDEX) return false;
+    const int m = base[a] % n[a];
+    ring->base[a] = base[a];
+    ring->slot0[a] = m < 0 ? m + n[a] : m;
+  }
+  return true;
+}
+#define OVN_WINDOW_TEXT "%s: window %d x %d x %d at base (%d, %d, %d): dimensions and base must be multiples of 8, dimensions >= 16, every " \
+                        "index within 2^20"
+
+// ovn_tsdf_integrate (ring NULL) and ovn_tsdf_window_integrate: `fn` names the caller in the messages
+int tsdf_integrate_checked(const char* fn, ovn_ctx* ctx, float* tsdf_dev, float* weight_dev, int nx, int ny, int nz, const double* origin,
+                           double voxel, double trunc, double max_weight, const float* range_dev, const double* poses_dev,
+                           int64_t n_scans, int proj_h, int proj_w, double fov_up_deg, double fov_down_deg, double max_range,
+                           void* stream, const int* base) {
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "%s: ctx is NULL", fn);
+  OVN_REQUIRE(tsdf_dev && weight_dev, OVN_ERR_ARG, "%s: NULL volume buffer", fn);
+  OVN_REQUIRE(tsdf_volume_ok(nx, ny, nz, origin, voxel), OVN_ERR_ARG,
+              "%s: volume %d x %d x %d (each >= 2, at most 2^31 - 1 samples) needs a finite origin and a voxel > 0", fn, nx, ny, nz);
+  OvnRing ring;
+  if (base) OVN_REQUIRE(tsdf_window_ok(nx, ny, nz, base, &ring), OVN_ERR_ARG, OVN_WINDOW_TEXT, fn, nx, ny, nz, base[0], base[1], base[2]);
+  OVN_REQUIRE((float)trunc > 0.0f && std::isfinite((float)trunc), OVN_ERR_ARG, "%s: trunc must be > 0", fn);
+  OVN_REQUIRE((float)max_weight > 0.0f, OVN_ERR_ARG, "%s: max_weight must be > 0", fn);
+  OVN_REQUIRE((float)max_range > 0.0f && std::isfinite((float)max_range), OVN_ERR_ARG, "%s: max_range must be > 0", fn);
+  OVN_REQUIRE(proj_h >= 1 && proj_w >= 1 && (int64_t)proj_h * proj_w <= 2147483647ll, OVN_ERR_ARG,
+              "%s: image %d x %d outside 1 .. 2^31 - 1 pixels", fn, proj_h, proj_w);
+  OVN_REQUIRE(n_scans >= 0 && n_scans <= 2147483646ll, OVN_ERR_ARG, "%s: bad n_scans %lld", fn, (long long)n_scans);
+  if (n_scans == 0) return OVN_OK;
+  OVN_REQUIRE(range_dev && poses_dev, OVN_ERR_ARG, "%s: NULL range images or poses", fn);
+  OVN_ON_DEVICE(ctx->device);
+  return ovn_tsdf_integrate_forward(ctx, tsdf_dev, weight_dev, nx, ny, nz, origin, voxel, trunc, max_weight, range_dev, poses_dev,
+                                    (int)n_scans, proj_h, proj_w, fov_up_deg, fov_down_deg, max_range, (hipStream_t)stream,
+                                    base ? &ring : nullptr);
+}
 }  // namespace
 
 int ovn_tsdf_integrate(ovn_ctx* ctx, float* tsdf_dev, float* weight_dev, int nx, int ny, int nz, const double* origin, double voxel,
                        double trunc, double max_weight, const float* range_dev, const double* poses_dev, int64_t n_scans, int proj_h,
                        int proj_w, double fov_up_deg, double fov_down_deg, double max_range, void* stream) {
-  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_tsdf_integrate: ctx is NULL");
-  OVN_REQUIRE(tsdf_dev && weight_dev, OVN_ERR_ARG, "ovn_tsdf_integrate: NULL volume buffer");
-  OVN_REQUIRE(tsdf_volume_ok(nx, ny, nz, origin, voxel), OVN_ERR_ARG,
-              "ovn_tsdf_integrate: volume %d x %d x %d (each >= 2, at most 2^31 - 1 samples) needs a finite origin and a voxel > 0", nx,
-              ny, nz);
-  OVN_REQUIRE((float)trunc > 0.0f && std::isfinite((float)trunc), OVN_ERR_ARG, "ovn_tsdf_integrate: trunc must be > 0");
-  OVN_REQUIRE((float)max_weight > 0.0f, OVN_ERR_ARG, "ovn_tsdf_integrate: max_weight must be > 0");
-  OVN_REQUIRE((float)max_range > 0.0f && std::isfinite((float)max_range), OVN_ERR_ARG, "ovn_tsdf_integrate: max_range must be > 0");
-  OVN_REQUIRE(proj_h >= 1 && proj_w >= 1 && (int64_t)proj_h * proj_w <= 2147483647ll, OVN_ERR_ARG,
-              "ovn_tsdf_integrate: image %d x %d outside 1 .. 2^31 - 1 pixels", proj_h, proj_w);
-  OVN_REQUIRE(n_scans >= 0 && n_scans <= 2147483646ll, OVN_ERR_ARG, "ovn_tsdf_integrate: bad n_scans %lld", (long long)n_scans);
-  if (n_scans == 0) return OVN_OK;
-  OVN_REQUIRE(range_dev && poses_dev, OVN_ERR_ARG, "ovn_tsdf_integrate: NULL range images or poses");
-  OVN_ON_DEVICE(ctx->device);
-  return ovn_tsdf_integrate_forward(ctx, tsdf_dev, weight_dev, nx, ny, nz, origin, voxel, trunc, max_weight, range_dev, poses_dev,
-                                    (int)n_scans, proj_h, proj_w, fov_up_deg, fov_down_deg, max_range, (hipStream_t)stream);
+  return tsdf_integrate_checked("ovn_tsdf_integrate", ctx, tsdf_dev, weight_dev, nx, ny, nz, origin, voxel, trunc, max_weight, range_dev,
+                                poses_dev, n_scans, proj_h, proj_w, fov_up_deg, fov_down_deg, max_range, stream, nullptr);
 }
+
+int ovn_tsdf_window_integrate(ovn_ctx* ctx, void* stream, float* tsdf_dev, float* weight_dev, int nx, int ny, int nz, const double* anchor,
+                              const int32_t* base, double voxel, double trunc, double max_weight, const float* range_dev,
+                              const double* poses_dev, int64_t n_scans, int proj_h, int proj_w, double fov_up_deg, double fov_down_deg,
+                              double max_range) {
+  OVN_REQUIRE(base != nullptr, OVN_ERR_ARG, "ovn_tsdf_window_integrate: base is NULL");
+  return tsdf_integrate_checked("ovn_tsdf_window_integrate", ctx, tsdf_dev, weight_dev, nx, ny, nz, anchor, voxel, trunc, max_weight,
+                                range_dev, poses_dev, n_scans, proj_h, proj_w, fov_up_deg, fov_down_deg, max_range, stream, base);
+}
+
+
+namespace {
+// ovn_tsdf_triangles (base NULL) and ovn_tsdf_window_triangles: `fn` names the caller in the messages
+int tsdf_triangles_checked(const char* fn, ovn_ctx* ctx, const float* tsdf_dev, const float* weight_dev, int nx, int ny, int nz,
+                           const double* origin, double voxel, double min_weight, float* triangles_dev, int64_t capacity,
+                           int64_t* n_triangles_dev, void* stream, const int* base, const int* box_lo, const int* box_hi) {
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "%s: ctx is NULL", fn);
+  OVN_REQUIRE(tsdf_dev && weight_dev && n_triangles_dev, OVN_ERR_ARG, "%s: NULL buffer", fn);
+  OVN_REQUIRE(tsdf_volume_ok(nx, ny, nz, origin, voxel), OVN_ERR_ARG,
+              "%s: volume %d x %d x %d (each >= 2, at most 2^31 - 1 samples) needs a finite origin and a voxel > 0", fn, nx, ny, nz);
+  OvnRing ring;
+  if (base) {
+    OVN_REQUIRE(tsdf_window_ok(nx, ny, nz, base, &ring), OVN_ERR_ARG, OVN_WINDOW_TEXT, fn, nx, ny, nz, base[0], base[1], base[2]);
+    OVN_REQUIRE(box_lo && box_hi, OVN_ERR_ARG, "%s: NULL box", fn);
+    const int n[3] = {nx, ny, nz};
+    for (int a = 0; a < 3; ++a)   // a cell's far corner is its low corner + 1: the low corners end at base + n - 1
+      OVN_REQUIRE(box_lo[a] <= box_hi[a] && box_lo[a] >= base[a] && (int64_t)box_hi[a] <= (int64_t)base[a] + n[a] - 1, OVN_ERR_ARG,
+                  "%s: cells %d .. %d of axis %d have corners outside the window %d .. %d", fn, box_lo[a], box_hi[a] - 1, a, base[a],
+                  base[a] + n[a] - 1);
+  }
+  OVN_REQUIRE(min_weight == min_weight, OVN_ERR_ARG, "%s: min_weight is NaN", fn);
+  OVN_REQUIRE(capacity >= 0, OVN_ERR_ARG, "%s: capacity %lld < 0", fn, (long long)capacity);
+  OVN_ON_DEVICE(ctx->device);
+  return ovn_tsdf_triangles_forward(ctx, tsdf_dev, weight_dev, nx, ny, nz, origin, voxel, min_weight, triangles_dev, capacity,
+                                    n_triangles_dev, (hipStream_t)stream, base ? &ring : nullptr, box_lo, box_hi);
+}
+
+// ovn_tsdf_raycast (base NULL) and ovn_tsdf_window_raycast
+int tsdf_raycast_checked(const char* fn, ovn_ctx* ctx, void* stream, const float* tsdf_dev, const float* weight_dev, int nx, int ny,
+                         int nz, const double* origin, const int* base, double voxel, double min_weight, const uint8_t* bricks_dev,
+                         const double* poses_dev, int64_t n_scans, int proj_h, int proj_w, const float* cos_az_dev,
+                         const float* sin_az_dev, const float* cos_pitch_dev, const float* sin_pitch_dev, double min_range,
+                         double max_range, double step, float* range_dev, float* vertex_dev, float* normal_dev, float* stacked_dev,
+                         int use_depth, int use_normals) {
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "%s: ctx is NULL", fn);
+  OVN_REQUIRE(tsdf_dev && weight_dev, OVN_ERR_ARG, "%s: NULL volume buffer", fn);
+  OVN_REQUIRE(tsdf_volume_ok(nx, ny, nz, origin, voxel), OVN_ERR_ARG,
+              "%s: volume %d x %d x %d (each >= 2, at most 2^31 - 1 samples) needs a finite origin and a voxel > 0", fn, nx, ny, nz);
+  OvnRing ring;
+  if (base) OVN_REQUIRE(tsdf_window_ok(nx, ny, nz, base, &ring), OVN_ERR_ARG, OVN_WINDOW_TEXT, fn, nx, ny, nz, base[0], base[1], base[2]);
+  OVN_REQUIRE(proj_h >= 1 && proj_w >= 1 && (int64_t)proj_h * proj_w <= 2147483647ll, OVN_ERR_ARG,
+              "%s: image %d x %d outside 1 .. 2^31 - 1 pixels", fn, proj_h, proj_w);
+  OVN_REQUIRE(n_scans >= 0 && n_scans <= 2147483647ll, OVN_ERR_ARG, "%s: bad n_scans %lld", fn, (long long)n_scans);
+  const float mn = (float)min_range, mx = (float)max_range, st = (float)step;
+  OVN_REQUIRE(mn > 0.0f && std::isfinite(mn) && mx > 0.0f && std::isfinite(mx) && st > 0.0f && std::isfinite(st), OVN_ERR_ARG,
+              "%s: min_range %g, max_range %g and step %g must be finite and > 0", fn, min_range, max_range, step);
+  OVN_REQUIRE(mn < mx, OVN_ERR_ARG, "%s: min_range %g is not below max_range %g", fn, min_range, max_range);
+  const long long K = ovn_tsdf_raycast_samples(min_range, max_range, step, OVN_RAYCAST_MAX_SAMPLES);
+  OVN_REQUIRE(K <= OVN_RAYCAST_MAX_SAMPLES, OVN_ERR_ARG, "%s: more than 2^20 samples per ray (range %g .. %g, step %g)", fn, min_range,
+              max_range, step);
+  OVN_REQUIRE(min_weight == min_weight, OVN_ERR_ARG, "%s: min_weight is NaN", fn);
+  OVN_REQUIRE(!vertex_dev || aligned16(vertex_dev), OVN_ERR_ARG, "%s: vertex_dev is not 16-byte aligned", fn);
+  use_depth = use_depth ? 1 : 0;
+  use_normals = use_normals ? 1 : 0;
+  OVN_REQUIRE(!stacked_dev || use_depth + use_normals > 0, OVN_ERR_ARG, "%s: stacked output requested with no channel enabled", fn);
+  if (n_scans == 0) return OVN_OK;
+  OVN_REQUIRE(poses_dev != nullptr, OVN_ERR_ARG, "%s: poses is NULL", fn);
+  OVN_REQUIRE(cos_az_dev && sin_az_dev && cos_pitch_dev && sin_pitch_dev, OVN_ERR_ARG, "%s: NULL direction table", fn);
+  OVN_ON_DEVICE(ctx->device);
+  return ovn_tsdf_raycast_forward(ctx, tsdf_dev, weight_dev, nx, ny, nz, origin, voxel, min_weight, bricks_dev, poses_dev, n_scans,
+                                  proj_h, proj_w, cos_az_dev, sin_az_dev, cos_pitch_dev, sin_pitch_dev, min_range, step, (int)K,
+                                  range_dev, vertex_dev, normal_dev, stacked_dev, use_depth, use_normals, (hipStream_t)stream,
+                                  base ? &ring : nullptr);
+}
+}  // namespace
 
 int ovn_tsdf_triangles(ovn_ctx* ctx, const float* tsdf_dev, const float* weight_dev, int nx, int ny, int nz, const double* origin,
                        double voxel, double min_weight, float* triangles_dev, int64_t capacity, int64_t* n_triangles_dev, void* stream) {
-  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_tsdf_triangles: ctx is NULL");
-  OVN_REQUIRE(tsdf_dev && weight_dev && n_triangles_dev, OVN_ERR_ARG, "ovn_tsdf_triangles: NULL buffer");
-  OVN_REQUIRE(tsdf_volume_ok(nx, ny, nz, origin, voxel), OVN_ERR_ARG,
-              "ovn_tsdf_triangles: volume %d x %d x %d (each >= 2, at most 2^31 - 1 samples) needs a finite origin and a voxel > 0", nx,
-              ny, nz);
-  OVN_REQUIRE(min_weight == min_weight, OVN_ERR_ARG, "ovn_tsdf_triangles: min_weight is NaN");
-  OVN_REQUIRE(capacity >= 0, OVN_ERR_ARG, "ovn_tsdf_triangles: capacity %lld < 0", (long long)capacity);
-  OVN_ON_DEVICE(ctx->device);
-  return ovn_tsdf_triangles_forward(ctx, tsdf_dev, weight_dev, nx, ny, nz, origin, voxel, min_weight, triangles_dev, capacity,
-                                    n_triangles_dev, (hipStream_t)stream);
+  return tsdf_triangles_checked("ovn_tsdf_triangles", ctx, tsdf_dev, weight_dev, nx, ny, nz, origin, voxel, min_weight, triangles_dev,
+                                capacity, n_triangles_dev, stream, nullptr, nullptr, nullptr);
+}
+
+int ovn_tsdf_window_triangles(ovn_ctx* ctx, void* stream, const float* tsdf_dev, const float* weight_dev, int nx, int ny, int nz,
+                              const double* anchor, const int32_t* base, double voxel, double min_weight, const int32_t* box_lo,
+                              const int32_t* box_hi, float* triangles_dev, int64_t capacity, int64_t* n_triangles_dev) {
+  OVN_REQUIRE(base != nullptr, OVN_ERR_ARG, "ovn_tsdf_window_triangles: base is NULL");
+  return tsdf_triangles_checked("ovn_tsdf_window_triangles", ctx, tsdf_dev, weight_dev, nx, ny, nz, anchor, voxel, min_weight,
+                                triangles_dev, capacity, n_triangles_dev, stream, base, box_lo, box_hi);
 }
 
 int ovn_tsdf_raycast(ovn_ctx* ctx, void* stream, const float* tsdf_dev, const float* weight_dev, int nx, int ny, int nz,
@@ -1418,34 +1521,35 @@ int ovn_tsdf_raycast(ovn_ctx* ctx, void* stream, const float* tsdf_dev, const fl
                      int64_t n_scans, int proj_h, int proj_w, const float* cos_az_dev, const float* sin_az_dev,
                      const float* cos_pitch_dev, const float* sin_pitch_dev, double min_range, double max_range, double step,
                      float* range_dev, float* vertex_dev, float* normal_dev, float* stacked_dev, int use_depth, int use_normals) {
-  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_tsdf_raycast: ctx is NULL");
-  OVN_REQUIRE(tsdf_dev && weight_dev, OVN_ERR_ARG, "ovn_tsdf_raycast: NULL volume buffer");
-  OVN_REQUIRE(tsdf_volume_ok(nx, ny, nz, origin, voxel), OVN_ERR_ARG,
-              "ovn_tsdf_raycast: volume %d x %d x %d (each >= 2, at most 2^31 - 1 samples) needs a finite origin and a voxel > 0", nx,
-              ny, nz);
-  OVN_REQUIRE(proj_h >= 1 && proj_w >= 1 && (int64_t)proj_h * proj_w <= 2147483647ll, OVN_ERR_ARG,
-              "ovn_tsdf_raycast: image %d x %d outside 1 .. 2^31 - 1 pixels", proj_h, proj_w);
-  OVN_REQUIRE(n_scans >= 0 && n_scans <= 2147483647ll, OVN_ERR_ARG, "ovn_tsdf_raycast: bad n_scans %lld", (long long)n_scans);
-  const float mn = (float)min_range, mx = (float)max_range, st = (float)step;
-  OVN_REQUIRE(mn > 0.0f && std::isfinite(mn) && mx > 0.0f && std::isfinite(mx) && st > 0.0f && std::isfinite(st), OVN_ERR_ARG,
-              "ovn_tsdf_raycast: min_range %g, max_range %g and step %g must be finite and > 0", min_range, max_range, step);
-  OVN_REQUIRE(mn < mx, OVN_ERR_ARG, "ovn_tsdf_raycast: min_range %g is not below max_range %g", min_range, max_range);
-  const long long K = ovn_tsdf_raycast_samples(min_range, max_range, step, OVN_RAYCAST_MAX_SAMPLES);
-  OVN_REQUIRE(K <= OVN_RAYCAST_MAX_SAMPLES, OVN_ERR_ARG, "ovn_tsdf_raycast: more than 2^20 samples per ray (range %g .. %g, step %g)",
-              min_range, max_range, step);
-  OVN_REQUIRE(min_weight == min_weight, OVN_ERR_ARG, "ovn_tsdf_raycast: min_weight is NaN");
-  OVN_REQUIRE(!vertex_dev || aligned16(vertex_dev), OVN_ERR_ARG, "ovn_tsdf_raycast: vertex_dev is not 16-byte aligned");
-  use_depth = use_depth ? 1 : 0;
-  use_normals = use_normals ? 1 : 0;
-  OVN_REQUIRE(!stacked_dev || use_depth + use_normals > 0, OVN_ERR_ARG,
-              "ovn_tsdf_raycast: stacked output requested with no channel enabled");
-  if (n_scans == 0) return OVN_OK;
-  OVN_REQUIRE(poses_dev != nullptr, OVN_ERR_ARG, "ovn_tsdf_raycast: poses is NULL");
-  OVN_REQUIRE(cos_az_dev && sin_az_dev && cos_pitch_dev && sin_pitch_dev, OVN_ERR_ARG, "ovn_tsdf_raycast: NULL direction table");
+  return tsdf_raycast_checked("ovn_tsdf_raycast", ctx, stream, tsdf_dev, weight_dev, nx, ny, nz, origin, nullptr, voxel, min_weight,
+                              bricks_dev, poses_dev, n_scans, proj_h, proj_w, cos_az_dev, sin_az_dev, cos_pitch_dev, sin_pitch_dev,
+                              min_range, max_range, step, range_dev, vertex_dev, normal_dev, stacked_dev, use_depth, use_normals);
+}
+
+int ovn_tsdf_window_raycast(ovn_ctx* ctx, void* stream, const float* tsdf_dev, const float* weight_dev, int nx, int ny, int nz,
+                            const double* anchor, const int32_t* base, double voxel, double min_weight, const uint8_t* bricks_dev,
+                            const double* poses_dev, int64_t n_scans, int proj_h, int proj_w, const float* cos_az_dev,
+                            const float* sin_az_dev, const float* cos_pitch_dev, const float* sin_pitch_dev, double min_range,
+                            double max_range, double step, float* range_dev, float* vertex_dev, float* normal_dev, float* stacked_dev,
+                            int use_depth, int use_normals) {
+  OVN_REQUIRE(base != nullptr, OVN_ERR_ARG, "ovn_tsdf_window_raycast: base is NULL");
+  return tsdf_raycast_checked("ovn_tsdf_window_raycast", ctx, stream, tsdf_dev, weight_dev, nx, ny, nz, anchor, base, voxel, min_weight,
+                              bricks_dev, poses_dev, n_scans, proj_h, proj_w, cos_az_dev, sin_az_dev, cos_pitch_dev, sin_pitch_dev,
+                              min_range, max_range, step, range_dev, vertex_dev, normal_dev, stacked_dev, use_depth, use_normals);
+}
+
+int ovn_tsdf_window_shift(ovn_ctx* ctx, void* stream, float* tsdf_dev, float* weight_dev, int nx, int ny, int nz, const int32_t* old_base,
+                          const int32_t* new_base) {
+  OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_tsdf_window_shift: ctx is NULL");
+  OVN_REQUIRE(tsdf_dev && weight_dev && old_base && new_base, OVN_ERR_ARG, "ovn_tsdf_window_shift: NULL buffer or base");
+  OVN_REQUIRE(nx >= 2 && ny >= 2 && nz >= 2 && (int64_t)nx * ny <= 2147483647ll && (int64_t)nx * ny * nz <= 2147483647ll, OVN_ERR_ARG,
+              "ovn_tsdf_window_shift: volume %d x %d x %d (each >= 2, at most 2^31 - 1 samples)", nx, ny, nz);
+  OvnRing ring;
+  for (const int32_t* base : {old_base, new_base})
+    OVN_REQUIRE(tsdf_window_ok(nx, ny, nz, base, &ring), OVN_ERR_ARG, OVN_WINDOW_TEXT, "ovn_tsdf_window_shift", nx, ny, nz, base[0],
+                base[1], base[2]);
   OVN_ON_DEVICE(ctx->device);
-  return ovn_tsdf_raycast_forward(ctx, tsdf_dev, weight_dev, nx, ny, nz, origin, voxel, min_weight, bricks_dev, poses_dev, n_scans,
-                                  proj_h, proj_w, cos_az_dev, sin_az_dev, cos_pitch_dev, sin_pitch_dev, min_range, step, (int)K,
-                                  range_dev, vertex_dev, normal_dev, stacked_dev, use_depth, use_normals, (hipStream_t)stream);
+  return ovn_tsdf_window_shift_forward(tsdf_dev, weight_dev, nx, ny, nz, old_base, new_base, (hipStream_t)stream);
 }
 
 int ovn_tsdf_bricks(ovn_ctx* ctx, void* stream, const float* weight_dev, int nx, int ny, int nz, double min_weight,

@@ -654,13 +654,36 @@ int ovn_normals_forward(const float* range, const float* vertex, int n_scans, in
 int ovn_normals_stack_forward(const float* range, const float* vertex, int n_scans, int H, int W, float* normal, float* stacked,
                               int use_depth, int use_normals, hipStream_t stream);
 
-// tsdf.hip: the arguments are those of ovn_tsdf_integrate / ovn_tsdf_triangles, validated there (n_scans >= 1)
+// A rolling window over the fixed lattice p = origin + (float)(I, J, K) voxel (ovn_tsdf_window_*): the storage
+// (nz,ny,nx) holds the samples base <= (I, J, K) < base + n, sample I in slot I mod n (floor modulus) on every axis.  slot0 = the slot of
+// `base`; n, base and so slot0 are multiples of 8.  The TSDF kernels are templated on this addressing: a NULL ring is the dense volume.
+struct OvnRing {
+  int base[3];
+  int slot0[3];
+};
+// the slot of lattice index I on an axis of n slots: a compare and a subtract, no division (base <= I < base + n)
+__host__ __device__ __forceinline__ int ovn_ring_slot(int I, int base, int slot0, int n) {
+  const int s = slot0 + (I - base);
+  return s >= n ? s - n : s;
+}
+// the lattice index that lives in slot s
+__host__ __device__ __forceinline__ int ovn_ring_index(int s, int base, int slot0, int n) {
+  return base + (s - slot0) + (s < slot0 ? n : 0);
+}
+
+// tsdf.hip: the arguments are those of ovn_tsdf_integrate / ovn_tsdf_triangles, validated there (n_scans >= 1).  With a ring they are
+// those of ovn_tsdf_window_integrate / ovn_tsdf_window_triangles: origin is the anchor, box_lo / box_hi the cells to extract
 int ovn_tsdf_integrate_forward(ovn_ctx* ctx, float* tsdf, float* weight, int nx, int ny, int nz, const double* origin, double voxel,
                                double trunc, double max_weight, const float* range, const double* poses, int n_scans, int H, int W,
-                               double fov_up_deg, double fov_down_deg, double max_range, hipStream_t stream);
+                               double fov_up_deg, double fov_down_deg, double max_range, hipStream_t stream,
+                               const OvnRing* ring = nullptr);
 int ovn_tsdf_triangles_forward(ovn_ctx* ctx, const float* tsdf, const float* weight, int nx, int ny, int nz, const double* origin,
                                double voxel, double min_weight, float* triangles, int64_t capacity, int64_t* n_triangles,
-                               hipStream_t stream);
+                               hipStream_t stream, const OvnRing* ring = nullptr, const int* box_lo = nullptr,
+                               const int* box_hi = nullptr);
+// tsdf_window.hip: the arguments are those of ovn_tsdf_window_shift, validated there
+int ovn_tsdf_window_shift_forward(float* tsdf, float* weight, int nx, int ny, int nz, const int* old_base, const int* new_base,
+                                  hipStream_t stream);
 
 // tsdf_raycast.hip: the arguments are those of ovn_tsdf_raycast / ovn_tsdf_bricks, validated there (n >= 1; K = the sample count of
 // ovn_tsdf_raycast_samples, which counts k with min_range + (float)k step < max_range in f32 up to cap + 1)
@@ -669,7 +692,7 @@ int ovn_tsdf_raycast_forward(ovn_ctx* ctx, const float* tsdf, const float* weigh
                              double voxel, double min_weight, const uint8_t* bricks, const double* poses, int64_t n, int H, int W,
                              const float* cos_az, const float* sin_az, const float* cos_pitch, const float* sin_pitch, double min_range,
                              double step, int K, float* range, float* vertex, float* normal, float* stacked, int use_depth,
-                             int use_normals, hipStream_t stream);
+                             int use_normals, hipStream_t stream, const OvnRing* ring = nullptr);
 int ovn_tsdf_bricks_forward(const float* weight, int nx, int ny, int nz, double min_weight, uint8_t* bricks, hipStream_t stream);
 
 // render_mesh.hip: nodes / order NULL = every ray walks all T triangles; the arguments are those of ovn_render_scans, validated there

@@ -11,6 +11,13 @@
 // Extraction.  Marching tetrahedra over the cells in linear order, x fastest.  A workgroup owns XB consecutive cells.  Pass 1 writes one
 // triangle count per workgroup, one workgroup scans those counts, pass 2 recomputes the per-cell counts, scans them inside the
 // workgroup and every lane writes its cell's triangles at its offset: the order of the output is the order of the cells.
+//
+// Both kernels are templated on the addressing.  RING = false is the dense volume: slot (i, j, k) holds sample (i, j, k).  RING = true is
+// the rolling window of ovn_tsdf_window_* (OvnRing, ovn_internal.h): a slot's lattice index comes from a compare
+// and an add per axis, and every float32 operation on a sample is the dense one, so a window sample has the bits of the dense sample
+// with the same lattice index.
+#include <climits>
+
 #include "ovn_internal.h"
 #include "proj_pixel.h"
 
@@ -20,7 +27,7 @@ namespace {
 struct TsdfScan {
   float R[9];   // row-major rotation, float32
   float o[3];
-  int lo[3];    // the samples this scan can change: lo <= (i, j, k) <= hi
+  int lo[3];    // the samples this scan can change: lo <= (i, j, k) <= hi, lattice indices
   int hi[3];
   int ok;       // 0: a non-finite pose or an empty box
   int pad;
@@ -35,16 +42,22 @@ struct TsdfArgs {
   int nx, ny, nz, x_runs, n_scans;
   float ox, oy, oz, voxel, trunc, max_weight;
   ProjGeom gm;
+  OvnRing ring;             // RING only
 };
 
-// one thread per scan of the batch, one workgroup: the records, then the union of the boxes
-__global__ __launch_bounds__(256) void tsdf_prepare_kernel(const double* __restrict__ poses, int n_scans, int nx, int ny, int nz, float ox,
-                                                           float oy, float oz, float voxel, float trunc, float max_range,
+struct Int3 {
+  int v[3];
+};
+
+// one thread per scan of the batch, one workgroup: the records, then the union of the boxes.  The volume holds the lattice samples
+// base .. base + n - 1 on every axis (base = 0: the dense volume)
+__global__ __launch_bounds__(256) void tsdf_prepare_kernel(const double* __restrict__ poses, int n_scans, int nx, int ny, int nz, Int3 base,
+                                                           float ox, float oy, float oz, float voxel, float trunc, float max_range,
                                                            TsdfScan* __restrict__ scans) {
   __shared__ int ulo[3], uhi[3];
   if (threadIdx.x < 3) {
-    ulo[threadIdx.x] = 0x7fffffff;
-    uhi[threadIdx.x] = -1;
+    ulo[threadIdx.x] = INT_MAX;
+    uhi[threadIdx.x] = INT_MIN;
   }
   __syncthreads();
   const int dims[3] = {nx, ny, nz};
@@ -71,14 +84,15 @@ __global__ __launch_bounds__(256) void tsdf_prepare_kernel(const double* __restr
     for (int a = 0; a < 3; ++a) {
       int lo = 0, hi = -1;
       if (ok) {
-        const double l = floor((((double)rec.o[a] - reach) - org[a]) / (double)voxel) - 1.0;
-        const double h = ceil((((double)rec.o[a] + reach) - org[a]) / (double)voxel) + 1.0;
+        // counted from base: the clamp is the dense one
+        const double l = (floor((((double)rec.o[a] - reach) - org[a]) / (double)voxel) - 1.0) - (double)base.v[a];
+        const double h = (ceil((((double)rec.o[a] + reach) - org[a]) / (double)voxel) + 1.0) - (double)base.v[a];
         const double top = (double)(dims[a] - 1);
         lo = l < 0.0 ? 0 : (l > top ? dims[a] : (int)l);
         hi = h > top ? dims[a] - 1 : (h < 0.0 ? -1 : (int)h);
       }
-      rec.lo[a] = lo;
-      rec.hi[a] = hi;
+      rec.lo[a] = base.v[a] + lo;
+      rec.hi[a] = base.v[a] + hi;
       ok = ok && lo <= hi;
     }
     rec.ok = ok ? 1 : 0;
@@ -99,29 +113,52 @@ __global__ __launch_bounds__(256) void tsdf_prepare_kernel(const double* __restr
       u.lo[a] = ulo[a];
       u.hi[a] = uhi[a];
     }
-    u.ok = (uhi[0] >= 0) ? 1 : 0;
+    u.ok = (ulo[0] <= uhi[0]) ? 1 : 0;             // some scan had a box
     scans[n_scans] = u;
   }
 }
 
-// grid = ceil(n_waves / 4) workgroups of 4 waves; wave w owns samples (64 run .. 64 run + 63, j, k), w = (k ny + j) x_runs + run
+// grid = ceil(n_waves / 4) workgroups of 4 waves; wave w owns slots (64 run .. 64 run + 63, sj, sk), w = (sk ny + sj) x_runs + run.
+// RING: the run's slots are one interval of lattice x, or two when the window's seam (slot0) falls inside the run; a scan's box is
+// tested against both, wave-uniformly.  The dense run is the one interval i0 .. i0 + 63
+template <bool RING>
 __global__ __launch_bounds__(256) void tsdf_integrate_kernel(TsdfArgs a) {
   const long long wave = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (wave >= a.n_waves) return;
   const long long row = wave / a.x_runs;
   // wave-uniform by construction; readfirstlane lets the compiler keep them, and every test on them, in scalar registers
   const int run = __builtin_amdgcn_readfirstlane((int)(wave - row * a.x_runs));
-  const int k = __builtin_amdgcn_readfirstlane((int)(row / a.ny));
-  const int j = __builtin_amdgcn_readfirstlane((int)(row - (long long)k * a.ny));
+  const int sk = __builtin_amdgcn_readfirstlane((int)(row / a.ny));
+  const int sj = __builtin_amdgcn_readfirstlane((int)(row - (long long)sk * a.ny));
   const int i0 = run * 64;
+  int j = sj, k = sk;                            // lattice indices from here on
+  int lo1 = i0, hi1 = i0 + 63;                   // the run's lattice x, first interval
+  int lo2 = INT_MAX, hi2 = INT_MIN;              // and second: empty unless the seam is inside the run
+  if (RING) {
+    const OvnRing& r = a.ring;
+    j = ovn_ring_index(sj, r.base[1], r.slot0[1], a.ny);
+    k = ovn_ring_index(sk, r.base[2], r.slot0[2], a.nz);
+    const int last = i0 + 63 < a.nx ? i0 + 63 : a.nx - 1;
+    lo1 = ovn_ring_index(i0, r.base[0], r.slot0[0], a.nx);
+    if (r.slot0[0] > i0 && r.slot0[0] <= last) {
+      hi1 = r.base[0] + a.nx - 1;                // slots i0 .. slot0 - 1: the top of the window
+      lo2 = r.base[0];                           // slots slot0 .. last: its bottom
+      hi2 = r.base[0] + (last - r.slot0[0]);
+    } else {
+      hi1 = lo1 + (last - i0);
+    }
+  }
   const TsdfScan* __restrict__ scans = a.scans;
   {
     const TsdfScan& u = scans[a.n_scans];        // the union of the batch's boxes: most waves of a large volume end here
-    if (!u.ok || j < u.lo[1] || j > u.hi[1] || k < u.lo[2] || k > u.hi[2] || i0 + 63 < u.lo[0] || i0 > u.hi[0]) return;
+    if (!u.ok || j < u.lo[1] || j > u.hi[1] || k < u.lo[2] || k > u.hi[2] ||
+        ((hi1 < u.lo[0] || lo1 > u.hi[0]) && (hi2 < u.lo[0] || lo2 > u.hi[0])))
+      return;
   }
-  const int i = i0 + (int)(threadIdx.x & 63);
-  if (i >= a.nx) return;                         // nothing below crosses lanes
-  const long long idx = ((long long)k * a.ny + j) * a.nx + i;
+  const int si = i0 + (int)(threadIdx.x & 63);
+  if (si >= a.nx) return;                        // nothing below crosses lanes
+  const int i = RING ? ovn_ring_index(si, a.ring.base[0], a.ring.slot0[0], a.nx) : si;
+  const long long idx = ((long long)sk * a.ny + sj) * a.nx + si;
   float t = a.tsdf[idx], w = a.weight[idx];
   const float px = a.ox + (float)i * a.voxel;
   const float py = a.oy + (float)j * a.voxel;
@@ -130,7 +167,9 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(TsdfArgs a) {
   const float fH = (float)a.gm.H;
   for (int s = 0; s < a.n_scans; ++s) {
     const TsdfScan& sc = scans[s];
-    if (!sc.ok || j < sc.lo[1] || j > sc.hi[1] || k < sc.lo[2] || k > sc.hi[2] || i0 + 63 < sc.lo[0] || i0 > sc.hi[0]) continue;
+    if (!sc.ok || j < sc.lo[1] || j > sc.hi[1] || k < sc.lo[2] || k > sc.hi[2] ||
+        ((hi1 < sc.lo[0] || lo1 > sc.hi[0]) && (hi2 < sc.lo[0] || lo2 > sc.hi[0])))
+      continue;
     const float d0 = px - sc.o[0], d1 = py - sc.o[1], d2 = pz - sc.o[2];
     const float q0 = (sc.R[0] * d0 + sc.R[3] * d1) + sc.R[6] * d2;      // R^T d
     const float q1 = (sc.R[1] * d0 + sc.R[4] * d1) + sc.R[7] * d2;
@@ -174,8 +213,22 @@ struct ExtractArgs {
   long long* wg;             // one word per workgroup: its count (pass 1), then its exclusive prefix
   long long n_cells, capacity;
   int nx, ny, nz;
+  int cx, cy;                // the cells run over a box cx wide and cy deep, x fastest; dense: nx - 1, ny - 1
+  int lo[3];                 // the lattice index of cell 0's low corner; dense: 0
   float ox, oy, oz, voxel, min_weight;
+  OvnRing ring;              // RING only
 };
+
+// where lattice sample (i, j, k) is stored
+template <bool RING>
+__device__ __forceinline__ long long sample_at(const ExtractArgs& a, int i, int j, int k) {
+  if (RING) {
+    i = ovn_ring_slot(i, a.ring.base[0], a.ring.slot0[0], a.nx);
+    j = ovn_ring_slot(j, a.ring.base[1], a.ring.slot0[1], a.ny);
+    k = ovn_ring_slot(k, a.ring.base[2], a.ring.slot0[2], a.nz);
+  }
+  return ((long long)k * a.ny + j) * a.nx + i;
+}
 
 // exclusive prefix of v over the workgroup's XB lanes, and the workgroup's total
 __device__ __forceinline__ int block_exclusive(int v, int& total) {
@@ -199,21 +252,24 @@ __device__ __forceinline__ int block_exclusive(int v, int& total) {
   return base + incl - v;
 }
 
-template <bool WRITE>
+template <bool WRITE, bool RING>
 __global__ __launch_bounds__(XB) void tsdf_cells_kernel(ExtractArgs a) {
   const long long cell = (long long)blockIdx.x * XB + threadIdx.x;
-  const int cx = a.nx - 1, cy = a.ny - 1;
-  int count = 0, i = 0, j = 0, k = 0;
+  const int cx = a.cx, cy = a.cy;
+  int count = 0, i = 0, j = 0, k = 0;   // the cell's low corner, lattice indices
   unsigned inside = 0;           // bit c: corner c has tsdf < 0
   if (cell < a.n_cells) {
     const long long rowc = cell / cx;
     i = (int)(cell - rowc * cx);
     k = (int)(rowc / cy);
     j = (int)(rowc - (long long)k * cy);
+    i += a.lo[0];
+    j += a.lo[1];
+    k += a.lo[2];
     bool seen = true;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-      const long long s = ((long long)(k + (c >> 2)) * a.ny + (j + ((c >> 1) & 1))) * a.nx + (i + (c & 1));
+      const long long s = sample_at<RING>(a, i + (c & 1), j + ((c >> 1) & 1), k + (c >> 2));
       seen = seen && (a.weight[s] >= a.min_weight);
       inside |= (a.tsdf[s] < 0.0f ? 1u : 0u) << c;
     }
@@ -250,8 +306,8 @@ __global__ __launch_bounds__(XB) void tsdf_cells_kernel(ExtractArgs a) {
         const int cl = ca < cb ? ca : cb, ch = ca < cb ? cb : ca;   // the corner with the smaller sample index leads
         const int il[3] = {i + (cl & 1), j + ((cl >> 1) & 1), k + (cl >> 2)};
         const int ih[3] = {i + (ch & 1), j + ((ch >> 1) & 1), k + (ch >> 2)};
-        const float dl = a.tsdf[((long long)il[2] * a.ny + il[1]) * a.nx + il[0]];
-        const float dh = a.tsdf[((long long)ih[2] * a.ny + ih[1]) * a.nx + ih[0]];
+        const float dl = a.tsdf[sample_at<RING>(a, il[0], il[1], il[2])];
+        const float dh = a.tsdf[sample_at<RING>(a, ih[0], ih[1], ih[2])];
         const float f = dl / (dl - dh);          // the signs differ: dl - dh != 0
 #pragma unroll
         for (int x = 0; x < 3; ++x) {
@@ -318,7 +374,7 @@ struct TsdfCellScratch {
 
 int ovn_tsdf_integrate_forward(ovn_ctx* ctx, float* tsdf, float* weight, int nx, int ny, int nz, const double* origin, double voxel,
                                double trunc, double max_weight, const float* range, const double* poses, int n_scans, int H, int W,
-                               double fov_up_deg, double fov_down_deg, double max_range, hipStream_t stream) {
+                               double fov_up_deg, double fov_down_deg, double max_range, hipStream_t stream, const OvnRing* ring) {
   TsdfScanScratch sc;
   int rc = ovn_ws_layout(ctx, stream, &sc, (size_t)n_scans + 1);
   if (rc) return rc;
@@ -341,26 +397,42 @@ int ovn_tsdf_integrate_forward(ovn_ctx* ctx, float* tsdf, float* weight, int nx,
   a.trunc = (float)trunc;
   a.max_weight = (float)max_weight;
   a.gm = make_geom(H, W, fov_up_deg, fov_down_deg, max_range, ctx->proj_trig);
-  hipLaunchKernelGGL(tsdf_prepare_kernel, dim3(1), dim3(256), 0, stream, poses, n_scans, nx, ny, nz, a.ox, a.oy, a.oz, a.voxel, a.trunc,
-                     a.gm.max_range, sc.scans);
+  a.ring = ring ? *ring : OvnRing{};
+  const Int3 base = {{a.ring.base[0], a.ring.base[1], a.ring.base[2]}};
+  hipLaunchKernelGGL(tsdf_prepare_kernel, dim3(1), dim3(256), 0, stream, poses, n_scans, nx, ny, nz, base, a.ox, a.oy, a.oz, a.voxel,
+                     a.trunc, a.gm.max_range, sc.scans);
   const long long blocks = (a.n_waves + 3) / 4;   // <= 2^31 (1/64 + 1/nx) / 4 + ny nz / 4 < 2^31
-  hipLaunchKernelGGL(tsdf_integrate_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+  if (ring)
+    hipLaunchKernelGGL(tsdf_integrate_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+  else
+    hipLaunchKernelGGL(tsdf_integrate_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, a);
   OVN_HIP_CHECK(hipGetLastError());
   return OVN_OK;
 }
 
 int ovn_tsdf_triangles_forward(ovn_ctx* ctx, const float* tsdf, const float* weight, int nx, int ny, int nz, const double* origin,
                                double voxel, double min_weight, float* triangles, int64_t capacity, int64_t* n_triangles,
-                               hipStream_t stream) {
+                               hipStream_t stream, const OvnRing* ring, const int* box_lo, const int* box_hi) {
   ExtractArgs a;
   a.tsdf = tsdf;
   a.weight = weight;
   a.triangles = triangles;
-  a.n_cells = (long long)(nx - 1) * (ny - 1) * (nz - 1);
   a.capacity = capacity;
   a.nx = nx;
   a.ny = ny;
   a.nz = nz;
+  a.ring = ring ? *ring : OvnRing{};
+  int cz = nz - 1;
+  a.cx = nx - 1;
+  a.cy = ny - 1;
+  for (int x = 0; x < 3; ++x) a.lo[x] = 0;
+  if (ring) {                                    // the cells whose low corner lies in box_lo <= (I, J, K) < box_hi
+    for (int x = 0; x < 3; ++x) a.lo[x] = box_lo[x];
+    a.cx = box_hi[0] - box_lo[0];
+    a.cy = box_hi[1] - box_lo[1];
+    cz = box_hi[2] - box_lo[2];
+  }
+  a.n_cells = (long long)a.cx * a.cy * cz;
   a.ox = (float)origin[0];
   a.oy = (float)origin[1];
   a.oz = (float)origin[2];
@@ -368,13 +440,20 @@ int ovn_tsdf_triangles_forward(ovn_ctx* ctx, const float* tsdf, const float* wei
   a.min_weight = (float)min_weight;
   const long long n_wg = (a.n_cells + XB - 1) / XB;   // < 2^24
   TsdfCellScratch sc;
-  int rc = ovn_ws_layout(ctx, stream, &sc, (size_t)n_wg);
+  int rc = ovn_ws_layout(ctx, stream, &sc, (size_t)(n_wg > 0 ? n_wg : 1));
   if (rc) return rc;
   scratch_overwritten(ctx);
   a.wg = sc.wg;
-  hipLaunchKernelGGL(tsdf_cells_kernel<false>, dim3((unsigned)n_wg), dim3(XB), 0, stream, a);
-  hipLaunchKernelGGL(tsdf_scan_kernel, dim3(1), dim3(SCAN_T), 0, stream, sc.wg, n_wg, reinterpret_cast<long long*>(n_triangles));
-  if (triangles && capacity > 0) hipLaunchKernelGGL(tsdf_cells_kernel<true>, dim3((unsigned)n_wg), dim3(XB), 0, stream, a);
+  const bool write = triangles && capacity > 0;
+  if (ring) {                                    // an empty box has no cells: the scan alone writes the count 0
+    if (n_wg > 0) hipLaunchKernelGGL((tsdf_cells_kernel<false, true>), dim3((unsigned)n_wg), dim3(XB), 0, stream, a);
+    hipLaunchKernelGGL(tsdf_scan_kernel, dim3(1), dim3(SCAN_T), 0, stream, sc.wg, n_wg, reinterpret_cast<long long*>(n_triangles));
+    if (write && n_wg > 0) hipLaunchKernelGGL((tsdf_cells_kernel<true, true>), dim3((unsigned)n_wg), dim3(XB), 0, stream, a);
+  } else {
+    hipLaunchKernelGGL((tsdf_cells_kernel<false, false>), dim3((unsigned)n_wg), dim3(XB), 0, stream, a);
+    hipLaunchKernelGGL(tsdf_scan_kernel, dim3(1), dim3(SCAN_T), 0, stream, sc.wg, n_wg, reinterpret_cast<long long*>(n_triangles));
+    if (write) hipLaunchKernelGGL((tsdf_cells_kernel<true, false>), dim3((unsigned)n_wg), dim3(XB), 0, stream, a);
+  }
   OVN_HIP_CHECK(hipGetLastError());
   return OVN_OK;
 }

@@ -33,10 +33,15 @@ struct RaycastArgs {
   long long pose0;             // first pose of this launch
   int nx, ny, nz, bx, by, H, W, tiles_x, tiles_per_scan, K;
   float ox, oy, oz, inv, min_weight, min_range, step;
+  OvnRing ring;                // RING only
 };
 
 __device__ __forceinline__ float lerp1(float a, float b, float f) { return a + f * (b - a); }
 
+// RING = false is the dense volume.  RING = true is the rolling window of ovn_tsdf_window_raycast (OvnRing, ovn_internal.h; DESIGN.md
+// section 36): the base corner is valid in base .. base + n - 2, each of the eight corners is wrapped into its slot on its own, the
+// brick byte is the one of the base corner's slot; the float32 operations are the dense ones
+template <bool RING>
 __global__ __launch_bounds__(64) void tsdf_raycast_kernel(RaycastArgs a) {
   const long long tile = blockIdx.x;
   const long long scan_local = tile / a.tiles_per_scan;
@@ -67,7 +72,11 @@ __global__ __launch_bounds__(64) void tsdf_raycast_kernel(RaycastArgs a) {
   const float gdx = dwx * a.inv, gdy = dwy * a.inv, gdz = dwz * a.inv;
   // n - 2 as a float may round once n exceeds 2^24 (n < 2^30: the other two axes hold 2 samples at least); the float test keeps the
   // conversion to int defined, the int test below decides
-  const float topx = (float)(a.nx - 2), topy = (float)(a.ny - 2), topz = (float)(a.nz - 2);
+  // the window's bounds are exact as floats: |index| <= 2^20
+  const int bi = RING ? a.ring.base[0] : 0, bj = RING ? a.ring.base[1] : 0, bk = RING ? a.ring.base[2] : 0;
+  const int ti = bi + (a.nx - 2), tj = bj + (a.ny - 2), tk = bk + (a.nz - 2);
+  const float botx = (float)bi, boty = (float)bj, botz = (float)bk;
+  const float topx = (float)ti, topy = (float)tj, topz = (float)tk;
   const long long sy = a.nx, sz = (long long)a.nx * a.ny;
   bool have = false;           // the previous sample was valid and positive
   bool hit = false;
@@ -77,25 +86,35 @@ __global__ __launch_bounds__(64) void tsdf_raycast_kernel(RaycastArgs a) {
       const float t = a.min_range + (float)k * a.step;
       const float gx = gox + t * gdx, gy = goy + t * gdy, gz = goz + t * gdz;
       const float fx0 = floorf(gx), fy0 = floorf(gy), fz0 = floorf(gz);
-      bool valid = (fx0 >= 0.0f) && (fx0 <= topx) && (fy0 >= 0.0f) && (fy0 <= topy) && (fz0 >= 0.0f) && (fz0 <= topz);   // a NaN fails
+      bool valid = (fx0 >= botx) && (fx0 <= topx) && (fy0 >= boty) && (fy0 <= topy) && (fz0 >= botz) && (fz0 <= topz);   // a NaN fails
       float F = 0.0f;
       if (valid) {
-        const int i = (int)fx0, j = (int)fy0, kk = (int)fz0;
-        valid = (i <= a.nx - 2) && (j <= a.ny - 2) && (kk <= a.nz - 2);
+        int i = (int)fx0, j = (int)fy0, kk = (int)fz0;
+        valid = (i <= ti) && (j <= tj) && (kk <= tk);
+        // the corners' strides from the base corner: the next slot, or back to slot 0 from the last one
+        long long dx = 1, dy = sy, dz = sz;
+        if (RING && valid) {
+          i = ovn_ring_slot(i, bi, a.ring.slot0[0], a.nx);
+          j = ovn_ring_slot(j, bj, a.ring.slot0[1], a.ny);
+          kk = ovn_ring_slot(kk, bk, a.ring.slot0[2], a.nz);
+          if (i == a.nx - 1) dx = -(long long)(a.nx - 1);
+          if (j == a.ny - 1) dy = -(long long)(a.ny - 1) * sy;
+          if (kk == a.nz - 1) dz = -(long long)(a.nz - 1) * sz;
+        }
         if (valid && a.bricks) valid = a.bricks[((long long)(kk >> 3) * a.by + (j >> 3)) * a.bx + (i >> 3)] != 0;
         if (valid) {
           const long long base = (long long)kk * sz + (long long)j * sy + i;
           const float* w = a.weight + base;
-          const float w0 = w[0], w1 = w[1], w2 = w[sy], w3 = w[sy + 1], w4 = w[sz], w5 = w[sz + 1], w6 = w[sz + sy], w7 = w[sz + sy + 1];
+          const float w0 = w[0], w1 = w[dx], w2 = w[dy], w3 = w[dy + dx], w4 = w[dz], w5 = w[dz + dx], w6 = w[dz + dy], w7 = w[dz + dy + dx];
           const float mw = a.min_weight;
           valid = (w0 >= mw) && (w1 >= mw) && (w2 >= mw) && (w3 >= mw) && (w4 >= mw) && (w5 >= mw) && (w6 >= mw) && (w7 >= mw);
           if (valid) {
             const float* d = a.tsdf + base;
             const float fx = gx - fx0, fy = gy - fy0, fz = gz - fz0;
-            const float c00 = lerp1(d[0], d[1], fx);
-            const float c10 = lerp1(d[sy], d[sy + 1], fx);
-            const float c01 = lerp1(d[sz], d[sz + 1], fx);
-            const float c11 = lerp1(d[sz + sy], d[sz + sy + 1], fx);
+            const float c00 = lerp1(d[0], d[dx], fx);
+            const float c10 = lerp1(d[dy], d[dy + dx], fx);
+            const float c01 = lerp1(d[dz], d[dz + dx], fx);
+            const float c11 = lerp1(d[dz + dy], d[dz + dy + dx], fx);
             const float c0 = lerp1(c00, c10, fy), c1 = lerp1(c01, c11, fy);
             F = lerp1(c0, c1, fz);
             valid = (F == F);            // neither > 0 nor <= 0: a NaN
@@ -173,7 +192,7 @@ int ovn_tsdf_raycast_forward(ovn_ctx* ctx, const float* tsdf, const float* weigh
                              double voxel, double min_weight, const uint8_t* bricks, const double* poses, int64_t n, int H, int W,
                              const float* cos_az, const float* sin_az, const float* cos_pitch, const float* sin_pitch, double min_range,
                              double step, int K, float* range, float* vertex, float* normal, float* stacked, int use_depth,
-                             int use_normals, hipStream_t stream) {
+                             int use_normals, hipStream_t stream, const OvnRing* ring) {
   const bool want_post = normal || stacked;
   const bool need_vertex = normal || (stacked && use_normals);
   const long long HW = (long long)H * W;
@@ -203,6 +222,7 @@ int ovn_tsdf_raycast_forward(ovn_ctx* ctx, const float* tsdf, const float* weigh
   a.min_weight = (float)min_weight;
   a.min_range = (float)min_range;
   a.step = (float)step;
+  a.ring = ring ? *ring : OvnRing{};
   const long long scans_per_launch = (1ll << 30) / a.tiles_per_scan > 0 ? (1ll << 30) / a.tiles_per_scan : 1;
   // the normal kernel reads range and vertex images: the caller's, or scratch of one launch's scans when it wants neither
   const long long slab_scans = n < scans_per_launch ? n : scans_per_launch;
@@ -227,7 +247,10 @@ int ovn_tsdf_raycast_forward(ovn_ctx* ctx, const float* tsdf, const float* weigh
     a.range = tmp_range ? sc.range - s0 * HW : range;
     a.vertex = tmp_vertex ? sc.vertex - s0 * HW * 4 : vertex;
     a.pose0 = s0;
-    hipLaunchKernelGGL(tsdf_raycast_kernel, dim3((unsigned)(ns * a.tiles_per_scan)), dim3(64), 0, stream, a);
+    if (ring)
+      hipLaunchKernelGGL(tsdf_raycast_kernel<true>, dim3((unsigned)(ns * a.tiles_per_scan)), dim3(64), 0, stream, a);
+    else
+      hipLaunchKernelGGL(tsdf_raycast_kernel<false>, dim3((unsigned)(ns * a.tiles_per_scan)), dim3(64), 0, stream, a);
     OVN_HIP_CHECK(hipGetLastError());
     if (want_post) {
       int rc = ovn_normals_stack_forward(a.range + s0 * HW, a.vertex ? a.vertex + s0 * HW * 4 : nullptr, (int)ns, H, W,

@@ -1055,12 +1055,25 @@ class OvnEngine:
         nz, ny, nx = (int(v) for v in tsdf.shape)
         return nx, ny, nz, (C.c_double * 3)(*org)
 
+    @staticmethod
+    def _int3(what: str, name: str, v):
+        """3 int32 on the host for the library: a window's base or a box of cells."""
+        a = np.asarray(v).reshape(-1)
+        if a.shape[0] != 3 or not np.issubdtype(a.dtype, np.integer):
+            raise _lib.OvnError("%s: %s must hold 3 integers, got %r" % (what, name, v))
+        if np.any(np.abs(a.astype(np.int64)) >= 2 ** 31):
+            raise _lib.OvnError("%s: %s %s does not fit int32" % (what, name, a.tolist()))
+        return (C.c_int32 * 3)(*(int(x) for x in a))
+
     def tsdf_integrate(self, tsdf: torch.Tensor, weight: torch.Tensor, origin, voxel: float, trunc: float, max_weight: float,
-                       range_images: torch.Tensor, poses, fov_up: float = 3.0, fov_down: float = -25.0, max_range: float = 50.0) -> None:
+                       range_images: torch.Tensor, poses, fov_up: float = 3.0, fov_down: float = -25.0, max_range: float = 50.0,
+                       base=None) -> None:
         """Fuses `range_images` ((n,H,W) float32 device tensor, -1 = empty) taken at `poses` ((n,4,4) float64 sensor-to-world, host
         array or device tensor) into the volume tsdf / weight ((nz,ny,nx) float32 device tensors, updated in place) whose sample
-        (i,j,k) sits at origin + (i,j,k) * voxel (ovn_tsdf_integrate)."""
+        (i,j,k) sits at origin + (i,j,k) * voxel (ovn_tsdf_integrate).  With `base` (3 integers) the tensors are
+        the rolling window at that base and `origin` is its anchor (ovn_tsdf_window_integrate)."""
         nx, ny, nz, org = self._tsdf_volume_args("tsdf_integrate", tsdf, weight, origin)
+        b3 = None if base is None else self._int3("tsdf_integrate", "base", base)
         r = range_images
         if r.device != self.device or r.dtype != torch.float32 or not r.is_contiguous() or r.dim() != 3:
             raise _lib.OvnError("tsdf_integrate: range_images must be a contiguous float32 (n,H,W) tensor on %s" % self.device)
@@ -1072,17 +1085,30 @@ class OvnEngine:
         if tuple(p.shape) != (n, 4, 4):
             raise _lib.OvnError("tsdf_integrate: poses must be (%d,4,4) for %d range images, got %s" % (n, n, tuple(p.shape)))
         with self._dev():
+            if b3 is not None:
+                _lib.check(self.lib.ovn_tsdf_window_integrate(self._h, self._stream(), _ptr(tsdf), _ptr(weight), nx, ny, nz, org, b3,
+                                                              float(voxel), float(trunc), float(max_weight), _ptr(r), _ptr(p), n, h, w,
+                                                              float(fov_up), float(fov_down), float(max_range)),
+                           "ovn_tsdf_window_integrate")
+                return
             _lib.check(self.lib.ovn_tsdf_integrate(self._h, _ptr(tsdf), _ptr(weight), nx, ny, nz, org, float(voxel), float(trunc),
                                                    float(max_weight), _ptr(r), _ptr(p), n, h, w, float(fov_up), float(fov_down),
                                                    float(max_range), self._stream()),
                        "ovn_tsdf_integrate")
 
     def tsdf_triangles(self, tsdf: torch.Tensor, weight: torch.Tensor, origin, voxel: float, min_weight: float = 1.0,
-                       capacity: Optional[int] = None, out: Optional[torch.Tensor] = None):
+                       capacity: Optional[int] = None, out: Optional[torch.Tensor] = None, base=None, box=None):
         """The zero level set of a fused volume as a triangle soup (ovn_tsdf_triangles, marching tetrahedra).  capacity=None counts
         first and then writes every triangle; otherwise at most `capacity` triangles are written (0: count only), into `out`
-        ((capacity,3,3) float32) when given.  Returns (triangles (min(T, capacity),3,3) device tensor or None, T)."""
+        ((capacity,3,3) float32) when given.  Returns (triangles (min(T, capacity),3,3) device tensor or None, T).  With `base` the
+        tensors are the rolling window at that base, `origin` its anchor and box = (box_lo, box_hi) the cells to extract, by their
+        low corners' lattice indices (ovn_tsdf_window_triangles)."""
         nx, ny, nz, org = self._tsdf_volume_args("tsdf_triangles", tsdf, weight, origin)
+        if (base is None) != (box is None):
+            raise _lib.OvnError("tsdf_triangles: base and box come together (a window), or neither (a dense volume)")
+        if base is not None:
+            b3 = self._int3("tsdf_triangles", "base", base)
+            lo3, hi3 = self._int3("tsdf_triangles", "box_lo", box[0]), self._int3("tsdf_triangles", "box_hi", box[1])
         if out is not None:
             if (out.device != self.device or out.dtype != torch.float32 or not out.is_contiguous() or out.dim() != 3
                     or tuple(out.shape[1:]) != (3, 3)):
@@ -1095,9 +1121,15 @@ class OvnEngine:
 
         def call(buf, cap):
             with self._dev():
-                _lib.check(self.lib.ovn_tsdf_triangles(self._h, _ptr(tsdf), _ptr(weight), nx, ny, nz, org, float(voxel),
-                                                       float(min_weight), _ptr(buf), int(cap), _ptr(count), self._stream()),
-                           "ovn_tsdf_triangles")
+                if base is not None:
+                    _lib.check(self.lib.ovn_tsdf_window_triangles(self._h, self._stream(), _ptr(tsdf), _ptr(weight), nx, ny, nz, org, b3,
+                                                                  float(voxel), float(min_weight), lo3, hi3, _ptr(buf), int(cap),
+                                                                  _ptr(count)),
+                               "ovn_tsdf_window_triangles")
+                else:
+                    _lib.check(self.lib.ovn_tsdf_triangles(self._h, _ptr(tsdf), _ptr(weight), nx, ny, nz, org, float(voxel),
+                                                           float(min_weight), _ptr(buf), int(cap), _ptr(count), self._stream()),
+                               "ovn_tsdf_triangles")
             return int(count.item())
 
         if capacity is None:
@@ -1143,18 +1175,21 @@ class OvnEngine:
                      fov_up: float = 3.0, fov_down: float = -25.0, min_range: float = 0.5, max_range: float = 50.0,
                      step: Optional[float] = None, min_weight: float = 1.0, bricks: Optional[torch.Tensor] = None,
                      want: Sequence[str] = ("range", "normal"), stacked_flags: Optional[Tuple[bool, ...]] = None,
-                     stacked_out: Optional[torch.Tensor] = None, out: Optional[Dict[str, torch.Tensor]] = None):
+                     stacked_out: Optional[torch.Tensor] = None, out: Optional[Dict[str, torch.Tensor]] = None, base=None):
         """Views of the volume tsdf / weight ((nz,ny,nx) float32 device tensors, sample (i,j,k) at origin + (i,j,k) * voxel) from
         `poses` ((n,4,4) float64 sensor-to-world, host array or device tensor): one ray per pixel marched from min_range to max_range
         in steps of `step` (default: one voxel), the first crossing from positive to non-positive tsdf is the hit (ovn_tsdf_raycast;
         DESIGN.md section 31).  `want` selects outputs among range, vertex, normal; stacked_flags = (use_depth, use_normals)
         additionally assembles the (n,H,W,C) leg input (into `stacked_out` when given).  bricks: the mask of `tsdf_bricks` for this
         weight and min_weight, or None.  out: a dict name -> contiguous float32 tensor of that output's shape (a slice along the first
-        axis of a caller's buffer) to write into instead of a fresh tensor.  Returns a dict of device tensors."""
+        axis of a caller's buffer) to write into instead of a fresh tensor.  Returns a dict of device tensors.  With `base` the
+        tensors are the rolling window at that base, `origin` its anchor and `bricks` the mask of the storage as it stands
+        (ovn_tsdf_window_raycast)."""
         bad = [k for k in want if k not in ("range", "vertex", "normal")]
         if bad:
             raise _lib.OvnError("tsdf_raycast: no output %s (a ray-cast view has range, vertex, normal)" % bad)
         nx, ny, nz, org = self._tsdf_volume_args("tsdf_raycast", tsdf, weight, origin)
+        b3 = None if base is None else self._int3("tsdf_raycast", "base", base)
         if isinstance(poses, torch.Tensor):
             p = poses.to(self.device, torch.float64).contiguous()
         else:
@@ -1196,16 +1231,28 @@ class OvnEngine:
             else:
                 stk = torch.empty((n, proj_h, proj_w, max(c, 1)), dtype=torch.float32, device=dev)
         tabs = self._direction_tables(proj_h, proj_w, fov_up, fov_down)
+        tail = (float(voxel), float(min_weight), _ptr(bricks), _ptr(p), n, proj_h, proj_w, _ptr(tabs[0]), _ptr(tabs[1]), _ptr(tabs[2]),
+                _ptr(tabs[3]), float(min_range), float(max_range), float(voxel if step is None else step), _ptr(bufs.get("range")),
+                _ptr(bufs.get("vertex")), _ptr(bufs.get("normal")), _ptr(stk), ud, un)
         with self._dev():
-            _lib.check(self.lib.ovn_tsdf_raycast(self._h, self._stream(), _ptr(tsdf), _ptr(weight), nx, ny, nz, org, float(voxel),
-                                                 float(min_weight), _ptr(bricks), _ptr(p), n, proj_h, proj_w, _ptr(tabs[0]),
-                                                 _ptr(tabs[1]), _ptr(tabs[2]), _ptr(tabs[3]), float(min_range), float(max_range),
-                                                 float(voxel if step is None else step), _ptr(bufs.get("range")),
-                                                 _ptr(bufs.get("vertex")), _ptr(bufs.get("normal")), _ptr(stk), ud, un),
-                       "ovn_tsdf_raycast")
+            if b3 is not None:
+                _lib.check(self.lib.ovn_tsdf_window_raycast(self._h, self._stream(), _ptr(tsdf), _ptr(weight), nx, ny, nz, org, b3, *tail),
+                           "ovn_tsdf_window_raycast")
+            else:
+                _lib.check(self.lib.ovn_tsdf_raycast(self._h, self._stream(), _ptr(tsdf), _ptr(weight), nx, ny, nz, org, *tail),
+                           "ovn_tsdf_raycast")
         if stk is not None:
             bufs["stacked"] = stk
         return bufs
+
+    def tsdf_window_shift(self, tsdf: torch.Tensor, weight: torch.Tensor, old_base, new_base) -> None:
+        """The rolling window tsdf / weight moves from old_base to new_base (3 integers each): the slots whose samples leave become
+        (tsdf 1, weight 0) for the samples that enter, nothing else is written (ovn_tsdf_window_shift)."""
+        nx, ny, nz, _ = self._tsdf_volume_args("tsdf_window_shift", tsdf, weight, (0.0, 0.0, 0.0))
+        ob, nb = self._int3("tsdf_window_shift", "old_base", old_base), self._int3("tsdf_window_shift", "new_base", new_base)
+        with self._dev():
+            _lib.check(self.lib.ovn_tsdf_window_shift(self._h, self._stream(), _ptr(tsdf), _ptr(weight), nx, ny, nz, ob, nb),
+                       "ovn_tsdf_window_shift")
 
     def icp_register(self, vertex: torch.Tensor, normal: torch.Tensor, rng: torch.Tensor, src_idx: torch.Tensor,
                      tgt_idx: torch.Tensor, init_pose: torch.Tensor, iterations: int = 20, max_dist: float = 2.0,

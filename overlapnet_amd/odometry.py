@@ -4,6 +4,8 @@
     odo = TsdfOdometry(engine, lo, hi, voxel=0.2)                     # frame to MODEL: predict, ray-cast, register, fuse
     for scan in scans: result = odo.track(scan)
     poses, results, volume = estimate_poses(engine, points, offsets)  # both in a row; `volume.mesh()` is the map's mesh
+    odo = RollingTsdfOdometry(engine, extent=(120, 120, 20), voxel=0.2)   # the same tracker in a window that follows the sensor (section 36)
+    poses, results, volume = estimate_poses(engine, points, offsets, window=120.0)    # online: no first pass, any drive length
 
 The pieces are HIP kernels that exist on their own: `ovn_project` (range, vertex and normal images), `ovn_tsdf_raycast` (the model seen
 from the predicted pose), `ovn_icp_register` (the alignment of two such images) and `ovn_tsdf_integrate` (the model).  This module is
@@ -131,7 +133,7 @@ class TsdfOdometry(object):
         bad = [k for k in icp_params if k not in ("iterations", "max_dist", "cos_min", "huber", "min_inliers")]
         if bad:
             raise ValueError("unknown registration parameters %s" % bad)
-        self.volume = TsdfVolume(engine, lo, hi, voxel, trunc=trunc, max_weight=max_weight)     # refuses bad bounds before the GPU
+        self.volume = self._make_volume(engine, lo, hi, voxel, trunc, max_weight, float(max_range))   # refuses bad bounds before the GPU
         import torch
         self.engine = engine
         self.h, self.w = int(proj_h), int(proj_w)
@@ -150,6 +152,13 @@ class TsdfOdometry(object):
         self._offs = torch.zeros(2, dtype=torch.int64, device=dev)
         self.poses: List[np.ndarray] = []
         self.results: List[TrackResult] = []
+
+    def _make_volume(self, engine, lo, hi, voxel, trunc, max_weight, max_range):
+        from .tsdf import TsdfVolume
+        return TsdfVolume(engine, lo, hi, voxel, trunc=trunc, max_weight=max_weight)
+
+    def _before_view(self, pose: np.ndarray) -> None:
+        """Called with the pose a scan is expected at (the first pose, then every prediction) before the volume is read or written."""
 
     def _project(self, points) -> None:
         """The scan's images into slot 1 (an empty scan: every pixel empty, without a launch)."""
@@ -172,7 +181,8 @@ class TsdfOdometry(object):
     def _fuse(self, pose_dev) -> None:
         up, down, rmax = self.sensor
         v = self.volume
-        self.engine.tsdf_integrate(v.tsdf, v.weight, v.origin, v.voxel, v.trunc, v.max_weight, self.range[1:2], pose_dev, up, down, rmax)
+        self.engine.tsdf_integrate(v.tsdf, v.weight, v.origin, v.voxel, v.trunc, v.max_weight, self.range[1:2], pose_dev, up, down, rmax,
+                                   **v._window())
         v.n_scans += 1
 
     def track(self, points, first_pose=None) -> TrackResult:
@@ -191,6 +201,7 @@ class TsdfOdometry(object):
             if not np.isfinite(pose).all():
                 raise ValueError("first_pose is not finite")
             self._project(points)
+            self._before_view(pose)
             self._fuse(torch.from_numpy(pose[None]).to(dev))
             res = TrackResult(pose, SOURCE_FIRST, 0, 0.0, 0.0, 0)
         else:
@@ -198,11 +209,12 @@ class TsdfOdometry(object):
             t_pred = predict(self.poses[-2], t_last) if len(self.poses) > 1 else t_last.copy()
             self._project(points)
             both = torch.from_numpy(np.stack([t_pred, t_last])).to(dev)                      # what each registration's result multiplies
+            self._before_view(t_pred)
             v = self.volume
             mask = self.engine.tsdf_bricks(v.weight, self.min_weight) if self.use_bricks else None
             self.engine.tsdf_raycast(v.tsdf, v.weight, v.origin, v.voxel, both[0:1], self.h, self.w, up, down, self.min_range, rmax,
                                      v.voxel, self.min_weight, mask, want=(),
-                                     out=dict(range=self.range[0:1], vertex=self.vertex[0:1], normal=self.normal[0:1]))
+                                     out=dict(range=self.range[0:1], vertex=self.vertex[0:1], normal=self.normal[0:1]), **v._window())
             icp, stats = self.engine.icp_register(self.vertex, self.normal, self.range, self._src, self._tgt, self._init, fov_up=up,
                                                   fov_down=down, max_range=rmax, **self.icp_params)
             # pose candidates: prediction . model registration, last pose . frame registration, the prediction itself
@@ -227,18 +239,65 @@ class TsdfOdometry(object):
         return res
 
 
+class RollingTsdfOdometry(TsdfOdometry):
+    """`TsdfOdometry` against a volume that follows the sensor (`tsdf.RollingTsdfVolume`): online, with memory
+    and a frame's cost that do not depend on the length of the drive.
+
+    extent: the window's size in metres, 3 numbers or one for all axes; anchor: the lattice's fixed point; shift: the voxels the window
+    moves at a time, a multiple of 8.  Before a scan's view is cast -- before the first scan is fused -- the window follows the
+    predicted position; the cells that leave are meshed and go to on_leave(piece (T,3,3) float32), or into `volume.pieces` without one,
+    so that `volume.mesh()` is the whole drive's.  Refused: a window whose half extent in x or y is below max_range + trunc + voxel +
+    shift * voxel, what a scan can reach from a sensor that may stand `shift` voxels off the centre.  The z extent is the caller's to
+    choose, as `below` and `above` are for the fixed box: a sensor that looks along the ground does not reach max_range upwards."""
+
+    def __init__(self, engine, extent, voxel: float, trunc: Optional[float] = None, anchor=(0.0, 0.0, 0.0), shift: int = 8,
+                 on_leave=None, **tracker):
+        self._rolling = dict(extent=extent, anchor=anchor, shift=shift)
+        self.on_leave = on_leave
+        super().__init__(engine, None, None, voxel, trunc=trunc, **tracker)
+
+    def _make_volume(self, engine, lo, hi, voxel, trunc, max_weight, max_range):
+        from .tsdf import DEFAULT_TRUNC_VOXELS, RollingTsdfVolume, window_shape
+        shape = window_shape(self._rolling["extent"], voxel)
+        shift = self._rolling["shift"]
+        tr = DEFAULT_TRUNC_VOXELS * float(voxel) if trunc is None else float(trunc)
+        need = max_range + tr + float(voxel) + float(shift) * float(voxel)
+        half = min(shape[0], shape[1]) // 2 * float(voxel)
+        if not half >= need:
+            raise ValueError("a window of %d x %d samples at voxel %g m reaches %g m from its centre in x or y, below max_range + trunc + "
+                             "voxel + shift * voxel = %g m" % (shape[0], shape[1], voxel, half, need))
+        return RollingTsdfVolume(engine, self._rolling["extent"], voxel, trunc=trunc, max_weight=max_weight,
+                                 anchor=self._rolling["anchor"], shift=shift)
+
+    def _before_view(self, pose: np.ndarray) -> None:
+        self.volume.follow(np.asarray(pose, np.float64)[:3, 3], self.on_leave, self.min_weight)
+
+
 def estimate_poses(engine, points, offsets, voxel: float = 0.2, trunc: Optional[float] = None, proj_h: int = 64, proj_w: int = 900,
                    fov_up: float = 3.0, fov_down: float = -25.0, max_range: float = 50.0, min_range: float = 0.5, below: float = 5.0,
-                   above: float = 15.0, chunk: int = 64, min_fitness: Optional[float] = None, **icp_params):
+                   above: float = 15.0, chunk: int = 64, min_fitness: Optional[float] = None, window=None, shift: int = 8,
+                   **icp_params):
     """The poses of a drive from its scans: `frame_to_frame` gives a first trajectory, its `bounds_from_poses` the volume's box, and
     `TsdfOdometry` tracks the drive against the volume it builds.  A box over 2^31 - 1 samples is refused with `volume_shape`'s message,
-    which names the voxel that fits (the volume does not follow the sensor).  -> (poses (n,4,4), [TrackResult] * n, the TsdfVolume)."""
+    which names the voxel that fits (the volume does not follow the sensor).  -> (poses (n,4,4), [TrackResult] * n, the TsdfVolume).
+    window: metres, 3 numbers or one for x and y with below + above for z -- `RollingTsdfOdometry` tracks the drive in a window of
+    that size that follows the sensor, `shift` voxels at a time: no `frame_to_frame` pass, no limit on the drive's extent, and the
+    volume returned is the RollingTsdfVolume, whose `mesh()` is the whole drive's."""
     from .tsdf import volume_shape
     offs = _check_scans(points, offsets)
     n = offs.shape[0] - 1
     if n < 1:
         raise ValueError("estimate_poses needs at least one scan")
     sensor = dict(proj_h=proj_h, proj_w=proj_w, fov_up=fov_up, fov_down=fov_down, max_range=max_range)
+    if window is not None:
+        ext = np.asarray(window, np.float64).reshape(-1)
+        if ext.shape[0] == 1:
+            ext = np.array([ext[0], ext[0], float(below) + float(above)])
+        odo = RollingTsdfOdometry(engine, ext, voxel, trunc=trunc, shift=shift, min_range=min_range, min_fitness=min_fitness, **sensor,
+                                  **icp_params)
+        for s in range(n):
+            odo.track(points[int(offs[s]):int(offs[s + 1])])
+        return np.stack(odo.poses), odo.results, odo.volume
     first, _ = frame_to_frame(engine, points, offsets, chunk=chunk, **sensor, **icp_params)
     lo, hi = bounds_from_poses(first, max_range, below, above)
     volume_shape(lo, hi, voxel)

@@ -7,6 +7,8 @@ level set as a `mesh.TriangleMesh` (ovn_tsdf_integrate / ovn_tsdf_triangles, csr
     views = vol.render_scans(poses)                    # the volume itself seen from poses (ovn_tsdf_raycast)
 
 The volume is dense: (nz, ny, nx) float32 tsdf and weight, at most 2^31 - 1 samples.  Argument errors raise before a GPU is touched.
+`RollingTsdfVolume` is the same pair of arrays as a window that follows the sensor over a lattice fixed in the world (ovn_tsdf_window_*;
+DESIGN.md section 36).
 """
 from __future__ import annotations
 
@@ -108,6 +110,10 @@ class TsdfVolume(object):
     def n_samples(self) -> int:
         return self.nx * self.ny * self.nz
 
+    def _window(self) -> dict:
+        """What the engine's calls take beyond the dense volume's arguments: nothing (RollingTsdfVolume: its base)."""
+        return {}
+
     def reset(self) -> None:
         """Back to the fresh volume: tsdf = 1, weight = 0."""
         self.tsdf.fill_(1.0)
@@ -137,7 +143,7 @@ class TsdfVolume(object):
         else:
             r = torch.from_numpy(np.ascontiguousarray(range_images, np.float32)).to(self.engine.device)
         self.engine.tsdf_integrate(self.tsdf, self.weight, self.origin, self.voxel, self.trunc, self.max_weight, r, poses, fov_up,
-                                   fov_down, max_range)
+                                   fov_down, max_range, **self._window())
         self.n_scans += shape[0]
 
     def integrate_scans(self, points, offsets, poses, proj_h: int = 64, proj_w: int = 900, fov_up: float = 3.0,
@@ -168,7 +174,7 @@ class TsdfVolume(object):
             r = self.engine.project(pts, d_offs[a:b + 1], max_points, int(proj_h), int(proj_w), fov_up, fov_down, max_range,
                                     want=("range",))["range"]
             self.engine.tsdf_integrate(self.tsdf, self.weight, self.origin, self.voxel, self.trunc, self.max_weight, r, poses[a:b],
-                                       fov_up, fov_down, max_range)
+                                       fov_up, fov_down, max_range, **self._window())
         self.n_scans += n
 
     def bricks(self, min_weight: float = 1.0, out=None):
@@ -198,7 +204,8 @@ class TsdfVolume(object):
         elif bricks is not False and bricks is not None:
             mask = bricks
         return self.engine.tsdf_raycast(self.tsdf, self.weight, self.origin, self.voxel, poses, int(proj_h), int(proj_w), fov_up,
-                                        fov_down, min_range, max_range, step, min_weight, mask, want, stacked_flags, stacked_out, out)
+                                        fov_down, min_range, max_range, step, min_weight, mask, want, stacked_flags, stacked_out, out,
+                                        **self._window())
 
     def triangles(self, min_weight: float = 1.0):
         """(T,3,3) float32 device tensor of the triangle soup, in contract order: one counting call, then one writing call."""
@@ -217,3 +224,179 @@ class TsdfVolume(object):
         if t > MAX_TRIANGLES:
             raise OvnError("TsdfVolume.mesh: %d triangles exceed the 2^27 a TriangleMesh holds: use a larger voxel" % t)
         return TriangleMesh(tri.reshape(3 * t, 3).cpu().numpy(), np.arange(3 * t, dtype=np.int32).reshape(t, 3))
+
+
+# ---- a volume that follows the sensor ----------------------------------------------------------------------
+WINDOW_MAX_INDEX = 1 << 20       # |lattice index| of every sample of a window: (float)I is exact
+
+
+def window_shape(extent, voxel: float) -> Tuple[int, int, int]:
+    """(nx, ny, nz) of a window `extent` metres wide (3 numbers, or one for all axes): extent / voxel samples, rounded up to a multiple
+    of 8, at least 16 per axis.  Raises ValueError for an extent or voxel that is not finite and > 0 or a window over MAX_SAMPLES."""
+    ext = np.asarray(extent, np.float64).reshape(-1)
+    if ext.shape[0] == 1:
+        ext = np.repeat(ext, 3)
+    voxel = float(voxel)
+    if ext.shape[0] != 3 or not (np.isfinite(ext).all() and (ext > 0).all()):
+        raise ValueError("extent must be 1 or 3 finite numbers > 0, got %r" % (extent,))
+    if not (voxel > 0.0 and np.isfinite(voxel) and np.float32(voxel) > 0):
+        raise ValueError("voxel must be a finite number > 0, got %r" % (voxel,))
+    n = np.maximum(np.ceil(np.ceil(ext / voxel - 1e-9) / 8.0) * 8.0, 16.0)
+    if float(np.prod(n)) > MAX_SAMPLES:
+        raise ValueError("a window of %s m at voxel %g m has %.3g samples, over the limit of 2^31 - 1" % (ext.tolist(), voxel, np.prod(n)))
+    return int(n[0]), int(n[1]), int(n[2])
+
+
+def check_window(shape, base) -> None:
+    """Raises ValueError for what the ovn_tsdf_window_* calls refuse in a window's shape (nx, ny, nz) and base."""
+    shape, base = [int(v) for v in shape], [int(v) for v in base]
+    if len(shape) != 3 or len(base) != 3:
+        raise ValueError("a window has 3 dimensions and a base of 3 indices, got %r and %r" % (shape, base))
+    if any(n < 16 or n % 8 for n in shape):
+        raise ValueError("the dimensions of a window must be multiples of 8 and >= 16, got %s" % (shape,))
+    if shape[0] * shape[1] * shape[2] > MAX_SAMPLES:
+        raise ValueError("a window of %s samples is over the limit of 2^31 - 1" % (shape,))
+    if any(b % 8 for b in base):
+        raise ValueError("every component of a window's base must be a multiple of 8, got %s" % (base,))
+    if any(b < -WINDOW_MAX_INDEX or b + n - 1 > WINDOW_MAX_INDEX for b, n in zip(base, shape)):
+        raise ValueError("the window %s at base %s leaves the lattice indices -2^20 .. 2^20 (moving the anchor is not supported)"
+                         % (shape, base))
+
+
+def leaving_boxes(old_base, new_base, shape):
+    """The lattice points of the box old_base .. old_base + shape - 1 that the box of the same shape at new_base does not hold, as at
+    most three disjoint boxes [(lo, hi)], hi exclusive: what leaves along x; of the rest what leaves along y; of the rest along z."""
+    ob, nb, n = (np.asarray(v, np.int64).reshape(3) for v in (old_base, new_base, shape))
+    lo, hi = ob.copy(), ob + n                   # what is left of the old box
+    out = []
+    for a in range(3):
+        keep_lo, keep_hi = max(lo[a], nb[a]), min(hi[a], nb[a] + n[a])
+        if keep_lo >= keep_hi:                   # nothing of this axis stays: all that is left leaves
+            out.append((lo.copy(), hi.copy()))
+            break
+        for l, h in ((lo[a], keep_lo), (keep_hi, hi[a])):    # below the new box or above it: a shift leaves one of them empty
+            if l < h:
+                blo, bhi = lo.copy(), hi.copy()
+                blo[a], bhi[a] = l, h
+                out.append((blo, bhi))
+        lo[a], hi[a] = keep_lo, keep_hi
+    return [(tuple(int(v) for v in l), tuple(int(v) for v in h)) for l, h in out if np.all(np.asarray(l) < np.asarray(h))]
+
+
+class RollingTsdfVolume(TsdfVolume):
+    """A TSDF of fixed size whose window follows the sensor (ovn_tsdf_window_*).
+
+        vol = RollingTsdfVolume(engine, extent=(120, 120, 24), voxel=0.2)
+        vol.follow(position); vol.integrate(range_images, poses); views = vol.render_scans(poses)
+        mesh = vol.mesh()                                  # what left the window on the way, plus the window
+
+    The lattice is fixed: sample (I, J, K) sits at anchor + (I, J, K) * voxel.  The window holds base <= (I, J, K) < base + (nx, ny,
+    nz) in ring storage and starts centred on the anchor.  `follow` moves the base in multiples of `shift` voxels (a multiple of 8) and
+    meshes the cells that lose a corner before their slots are cleared.  A region the window comes back to is fresh."""
+
+    def __init__(self, engine, extent, voxel: float, trunc: float = None, max_weight: float = 64.0, anchor=(0.0, 0.0, 0.0),
+                 shift: int = 8):
+        self.nx, self.ny, self.nz = window_shape(extent, voxel)
+        self.voxel = float(voxel)
+        self.trunc = DEFAULT_TRUNC_VOXELS * self.voxel if trunc is None else float(trunc)
+        self.max_weight = float(max_weight)
+        if not (self.trunc > 0.0 and np.isfinite(self.trunc)):
+            raise ValueError("trunc must be a finite number > 0, got %r" % (trunc,))
+        if not self.max_weight > 0.0:
+            raise ValueError("max_weight must be > 0, got %r" % (max_weight,))
+        if int(shift) != shift or int(shift) < 8 or int(shift) % 8:
+            raise ValueError("shift must be a multiple of 8 voxels, got %r" % (shift,))
+        self.shift = int(shift)
+        self.origin = np.asarray(anchor, np.float64).reshape(-1).copy()      # the anchor: what the dense calls name origin
+        if self.origin.shape[0] != 3 or not np.isfinite(self.origin).all():
+            raise ValueError("anchor must be 3 finite numbers, got %r" % (anchor,))
+        self.base = tuple(-(n // 2) // 8 * 8 for n in self.shape)
+        check_window(self.shape, self.base)
+        self.engine = engine
+        import torch
+        self.tsdf = torch.ones((self.nz, self.ny, self.nx), dtype=torch.float32, device=engine.device)
+        self.weight = torch.zeros((self.nz, self.ny, self.nx), dtype=torch.float32, device=engine.device)
+        self.n_scans = 0
+        self.n_shifts = 0
+        self.pieces = []                 # (T,3,3) float32 host arrays: what `follow` meshed and no `on_leave` took
+
+    @property
+    def shape(self) -> Tuple[int, int, int]:
+        return self.nx, self.ny, self.nz
+
+    @property
+    def anchor(self) -> np.ndarray:
+        return self.origin
+
+    def _window(self) -> dict:
+        return dict(base=self.base)
+
+    def reset(self) -> None:
+        """Back to the fresh window at the base it has; the pieces kept so far are dropped."""
+        super().reset()
+        self.pieces = []
+
+    def cell_of(self, position) -> Tuple[int, int, int]:
+        """The lattice cell a point lies in: floor((position - anchor) / voxel) per axis."""
+        p = np.asarray(position, np.float64).reshape(-1)
+        if p.shape[0] != 3 or not np.isfinite(p).all():
+            raise ValueError("position must be 3 finite numbers, got %r" % (position,))
+        return tuple(int(v) for v in np.floor((p - self.origin) / self.voxel))
+
+    def next_base(self, position) -> Tuple[int, int, int]:
+        """The base `follow(position)` moves to: per axis, when the cell of `position` is `shift` voxels or more from the window's
+        centre base + n // 2, the base moves by that distance rounded towards zero to a multiple of `shift`."""
+        out = []
+        for c, b, n in zip(self.cell_of(position), self.base, self.shape):
+            d = c - (b + n // 2)
+            out.append(b + (abs(d) // self.shift) * self.shift * (1 if d >= 0 else -1))
+        return tuple(out)
+
+    def follow(self, position, on_leave=None, min_weight: float = 1.0) -> bool:
+        """Moves the window after the sensor at `position`; -> whether it moved.  Before the slots that change hands are cleared, the
+        cells with at least one corner among the leaving samples are meshed -- at most three boxes of cells, `leaving_boxes` -- and
+        every non-empty piece, an (T,3,3) float32 host array, goes to on_leave(piece), or into `self.pieces` without one."""
+        new = self.next_base(position)
+        if new == self.base:
+            return False
+        check_window(self.shape, new)
+        if self.n_scans > 0:                      # a window nothing was fused into has no surface to keep
+            for lo, hi in leaving_boxes(self.base, new, tuple(n - 1 for n in self.shape)):      # boxes of CELLS, by their low corners
+                tri = self.triangles(min_weight, box=(lo, hi))
+                if int(tri.shape[0]) > 0:
+                    piece = tri.cpu().numpy()
+                    if on_leave is not None:
+                        on_leave(piece)
+                    else:
+                        self.pieces.append(piece)
+        self.engine.tsdf_window_shift(self.tsdf, self.weight, self.base, new)
+        self.base = new
+        self.n_shifts += 1
+        return True
+
+    def triangles(self, min_weight: float = 1.0, box=None):
+        """(T,3,3) float32 device tensor, T >= 0: the triangles of the cells whose low corner lies in box = (lo, hi), hi exclusive, in
+        ascending cell order within the box; box=None is every cell of the window.  A cell needs all eight corners in the window."""
+        if np.isnan(float(min_weight)):
+            raise ValueError("min_weight is NaN")
+        top = tuple(b + n - 1 for b, n in zip(self.base, self.shape))
+        lo, hi = (self.base, top) if box is None else (tuple(int(v) for v in box[0]), tuple(int(v) for v in box[1]))
+        if len(lo) != 3 or len(hi) != 3 or any(l > h or l < b or h > t for l, h, b, t in zip(lo, hi, self.base, top)):
+            raise ValueError("the cells %s .. %s (exclusive) have corners outside the window %s .. %s" % (lo, hi, self.base, top))
+        tri, total = self.engine.tsdf_triangles(self.tsdf, self.weight, self.origin, self.voxel, min_weight, base=self.base, box=(lo, hi))
+        if total == 0:
+            import torch
+            return torch.zeros((0, 3, 3), dtype=torch.float32, device=self.engine.device)
+        return tri
+
+    def mesh(self, min_weight: float = 1.0) -> TriangleMesh:
+        """The pieces kept by `follow` in the order they left, then the window, as one TriangleMesh (a soup)."""
+        parts = list(self.pieces) + [self.triangles(min_weight).cpu().numpy()]
+        tri = np.concatenate(parts).astype(np.float32, copy=False)
+        t = int(tri.shape[0])
+        if t == 0:
+            raise OvnError("RollingTsdfVolume.mesh: no surface: no cell has all eight corners seen %g times and a sign change "
+                           "(%d scans fused)" % (min_weight, self.n_scans))
+        if t > MAX_TRIANGLES:
+            raise OvnError("RollingTsdfVolume.mesh: %d triangles exceed the 2^27 a TriangleMesh holds: use a larger voxel" % t)
+        return TriangleMesh(np.ascontiguousarray(tri.reshape(3 * t, 3)), np.arange(3 * t, dtype=np.int32).reshape(t, 3))

@@ -1,11 +1,12 @@
 """Raw scans -> the sensor poses the mapping tools take: LiDAR odometry on the GPU (`overlapnet_amd.odometry`).
 
     python tools/odometry.py --config network.json --scans sequences/07/velodyne --out poses.txt [--mesh site.ply] [--voxel 0.2] \\
-        [--frame-to-frame-only]
+        [--frame-to-frame-only] [--window 120]
 
 Every scan is registered onto its predecessor (one launch per chunk of pairs); that trajectory sizes a TSDF volume, and the drive is
 then tracked against the volume it builds: each scan is registered onto a ray-cast view of the model at its predicted pose and fused.
---frame-to-frame-only stops after the first pass.  The poses file holds one KITTI pose line per scan (12 numbers, sensor to world in the
+--frame-to-frame-only stops after the first pass.  --window M skips the first pass: the volume is a window M metres wide that follows the
+sensor, and what leaves it is meshed on the way.  The poses file holds one KITTI pose line per scan (12 numbers, sensor to world in the
 sensor frame, the first pose the identity): the file `tools/build_mesh.py --poses` reads without --calib.  --mesh also writes the tracked
 volume's zero level set.  The config is the `network.yml` dict `Infer` takes; its `model.inputShape` is the range image the scans are
 projected into.  Prints one JSON line."""
@@ -30,6 +31,8 @@ def main(argv=None):
     ap.add_argument("--mesh", default=None, help="also write the tracked volume's mesh, binary PLY")
     ap.add_argument("--voxel", type=float, default=0.2)
     ap.add_argument("--trunc", type=float, default=None, help="truncation distance in metres (default: 4 voxels)")
+    ap.add_argument("--window", type=float, default=None, metavar="M", help="track in a volume M metres wide (--below + --above metres "
+                    "high) that follows the sensor: no first pass, no limit on the drive's extent; --mesh writes the streamed mesh")
     ap.add_argument("--frame-to-frame-only", action="store_true")
     ap.add_argument("--min-fitness", type=float, default=None, help="a registration below it counts as failed (default: none)")
     ap.add_argument("--below", type=float, default=5.0, help="metres of volume below the lowest sensor position")
@@ -69,11 +72,13 @@ def main(argv=None):
             try:
                 poses, results, vol = odometry.estimate_poses(eng, points, offsets, voxel=a.voxel, trunc=a.trunc, min_range=a.min_range,
                                                               below=a.below, above=a.above, chunk=a.chunk, min_fitness=a.min_fitness,
-                                                              **sensor)
+                                                              window=a.window, **sensor)
             except ValueError as e:
                 raise SystemExit("odometry: %s" % e)
             line.update(mode="frame_to_model", volume=[vol.nx, vol.ny, vol.nz], voxel=vol.voxel,
                         sources={s: int(sum(r.source == s for r in results)) for s in ("first", "model", "frame", "prediction")})
+            if a.window is not None:
+                line.update(window_m=a.window, window_shifts=vol.n_shifts)
             if a.mesh:
                 mesh = vol.mesh()
                 mesh.to_ply(a.mesh)

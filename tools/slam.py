@@ -60,6 +60,8 @@ def parse(argv=None):
     ap.add_argument("--max-iterations", type=int, default=30)
     ap.add_argument("--preconditioner", default="auto", choices=("auto", "auto+loops", "jacobi", "chain", "loops"))
     ap.add_argument("--voxel", type=float, default=0.2)
+    ap.add_argument("--window", type=float, default=None, metavar="M", help="track (and mesh) in a TSDF window M metres wide that follows "
+                    "the sensor instead of a volume over the whole drive")
     ap.add_argument("--fov-up", type=float, default=3.0)
     ap.add_argument("--fov-down", type=float, default=-25.0)
     ap.add_argument("--max-range", type=float, default=50.0)
@@ -102,7 +104,7 @@ def main(argv=None):
         if poses.shape[0] != n:
             raise SystemExit("%s holds %d poses for %d scans" % (a.poses, poses.shape[0], n))
     else:
-        poses, _, _ = odometry.estimate_poses(eng, points, offsets, voxel=a.voxel, **sensor)
+        poses, _, _ = odometry.estimate_poses(eng, points, offsets, voxel=a.voxel, window=a.window, **sensor)
     line = {"out": a.out, "scans": n, "odometry_seconds": round(time.time() - t0, 3)}
 
     infer.cache_frames(n)
@@ -145,9 +147,16 @@ def main(argv=None):
         lcd.write_covariances(a.covariances, graph.marginals(frame="position", huber=a.huber))
         line["covariances"] = a.covariances
     if a.mesh:
-        lo, hi = odometry.bounds_from_poses(res.poses, a.max_range)
-        vol = tsdf.TsdfVolume(eng, lo, hi, a.voxel)
-        vol.integrate_scans(points, offsets, res.poses, **sensor)
+        if a.window is not None:      # the window follows the optimized poses; what leaves it is meshed on the way
+            vol = tsdf.RollingTsdfVolume(eng, (a.window, a.window, 20.0), a.voxel)
+            for s in range(n):
+                vol.follow(res.poses[s, :3, 3])
+                vol.integrate_scans(points[int(offsets[s]):int(offsets[s + 1])], [0, int(offsets[s + 1] - offsets[s])], res.poses[s:s + 1],
+                                    **sensor)
+        else:
+            lo, hi = odometry.bounds_from_poses(res.poses, a.max_range)
+            vol = tsdf.TsdfVolume(eng, lo, hi, a.voxel)
+            vol.integrate_scans(points, offsets, res.poses, **sensor)
         mesh = vol.mesh()
         mesh.to_ply(a.mesh)
         line.update(mesh=a.mesh, triangles=mesh.n_triangles)
