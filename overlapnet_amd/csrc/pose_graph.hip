@@ -3,8 +3,11 @@
 // chain-plus-loops inverse (ovn_pose_graph_loops_*; tests/_pose_graph_loops_ref.py): the exact inverse of the
 // undamped Hessian of a chain plus L loop edges, with a dense Cholesky factorization of order 6 L; and the marginal covariances that
 // inverse's diagonal blocks are (ovn_pose_graph_marginals; tests/_pose_graph_marginals_ref.py).
-// No atomics: a node sums over its incidence list in list order, every dot product and maximum is a fixed tree (256 lanes, halving),
-// the scans are Hillis-Steele inside a workgroup and three launches across workgroups.  No workgroup waits on another inside a launch.
+// No atomics, and no workgroup waits on another inside a launch.  A node sums over its incidence list in list order.
+// Reductions: every dot product and maximum over nodes is a fixed tree -- 256 lanes halving inside a workgroup (pg_wg_sum, pg_wg_max),
+// then ONE workgroup over the per-workgroup partials, lane t taking partials t, t + 256, ... in order (pg_partial_sum, pg_partial_max).
+// Scans: every prefix sum over the chain is the one scan of "the scan" below, three launches: Hillis-Steele inside blocks of 256
+// (pg_block_scan6), the block totals added in block order by one lane per component, and the offset added to every block but the first.
 // Built without FMA contraction: tests/_pose_graph_ref.py states the same operations one by one.
 #include "ovn_internal.h"
 
@@ -15,15 +18,25 @@ constexpr double PG_SERIES_X = 1e-2;   // theta^2 below which the coefficient se
 
 // record slots (OVN_POSE_GRAPH_RECORD doubles)
 enum { R_COST = 0, R_BAD = 1, R_CHOL = 2, R_GMAX = 3, R_ITER = 4, R_REL = 5, R_CONV = 6, R_BREAK = 7, R_RZ = 8, R_RZ0 = 9, R_ALPHA = 10,
-       R_BETA = 11, R_DMAX = 12 };
+       R_BETA = 11, R_DMAX = 12, R_LPIV = 13, R_LOUT = 14, R_MOUT = 15 };
+
+// the carve of the three workspace layouts below: the next n doubles (NULL when only measuring), rounded up to an even count
+struct PgTake {
+  double* base;
+  size_t o = 0;
+  double* operator()(size_t n) {
+    double* q = base ? base + o : nullptr;
+    o += (n + 1) & ~(size_t)1;
+    return q;
+  }
+};
 
 struct PgWs {   // the caller's workspace, in doubles
   double *eg, *part_e, *part_n, *part_c, *r, *z, *q, *p[2], *sa, *sb, *bsum;
   size_t total;
   PgWs(double* base, int64_t N, int64_t E) {
     const int64_t nbn = (N + PG_B - 1) / PG_B, nbe = (E + PG_B - 1) / PG_B;
-    size_t o = 0;
-    auto take = [&](size_t n) { double* q_ = base ? base + o : nullptr; o += (n + 1) & ~(size_t)1; return q_; };
+    PgTake take{base};
     part_n = take(2 * nbn);   // the node-sized parts first: their places do not depend on E
     part_c = take(nbn);
     r = take(6 * N);
@@ -36,7 +49,7 @@ struct PgWs {   // the caller's workspace, in doubles
     bsum = take(12 * nbn);
     part_e = take(2 * nbe);
     eg = take(12 * E);
-    total = o;
+    total = take.o;
   }
 };
 
@@ -238,6 +251,18 @@ __device__ __forceinline__ void pg_adjoint(const double* R, const double* t, dou
       Ad[(i + 3) * 6 + 3 + j] = R[i * 3 + j];
     }
 }
+// Ad(T^-1) of T = (R, t): T^-1 = (R', -(R' t))
+__device__ __forceinline__ void pg_adjoint_inv(const double* R, const double* t, double* Ad) {
+  double Rt[9], tt[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) Rt[a * 3 + b] = R[b * 3 + a];
+  m3_tvec(R, t, tt);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) tt[a] = -tt[a];
+  pg_adjoint(Rt, tt, Ad);
+}
 // inverse left Jacobian of SE(3) at xi = (rho, phi), closed form (Barfoot, State Estimation for Robotics, 7.85-7.86)
 __device__ __forceinline__ void pg_jl_inv(const double* xi, double* J) {
   const double* rho = xi;
@@ -398,15 +423,8 @@ __global__ __launch_bounds__(PG_B) void pg_edge_kernel(const double* __restrict_
         if (JAC) {
           const double nr[6] = {-r[0], -r[1], -r[2], -r[3], -r[4], -r[5]};
           pg_jl_inv(nr, B);                      // J_r^-1(r) = J_l^-1(-r)
-          double Rji[9], tji[3], Ad[36];
-#pragma unroll
-          for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int b = 0; b < 3; ++b) Rji[a * 3 + b] = Rij[b * 3 + a];
-          m3_tvec(Rij, tij, tji);
-#pragma unroll
-          for (int a = 0; a < 3; ++a) tji[a] = -tji[a];
-          pg_adjoint(Rji, tji, Ad);
+          double Ad[36];
+          pg_adjoint_inv(Rij, tij, Ad);          // Ad(T_ij^-1)
           m6_mul(B, Ad, A);
 #pragma unroll
           for (int q = 0; q < 36; ++q) A[q] = -A[q];
@@ -571,15 +589,7 @@ __global__ __launch_bounds__(PG_B) void pg_chain_kernel(const double* __restrict
     if (ok) {
       m6_mul(P, Wi, PW);
       m6_mult(PW, P, G);
-      double Rt[9], tt[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) Rt[a * 3 + b] = R[b * 3 + a];
-      m3_tvec(R, t, tt);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) tt[a] = -tt[a];
-      pg_adjoint(Rt, tt, Nm);
+      pg_adjoint_inv(R, t, Nm);
       double f = 0.0;
 #pragma unroll
       for (int q = 0; q < 36; ++q) f += (G[q] + Nm[q]) * 0.0;
@@ -623,12 +633,13 @@ __global__ void pg_set_record_kernel(double* rec, int first, int n, double value
 }
 
 // ---- the solver ---------------------------------------------------------------------------------------------------------------------------
-__global__ void pg_solve_reset_kernel(double* rec) {
+// the start of a solve: `breakdown` from the linearization's failed pivots and, with `loops`, the prepare's
+__global__ void pg_solve_reset_kernel(double* rec, int loops) {
   if (threadIdx.x != 0) return;
   rec[R_ITER] = 0.0;
   rec[R_REL] = 1.0;
   rec[R_CONV] = 0.0;
-  rec[R_BREAK] = rec[R_CHOL] != 0.0 ? 1.0 : 0.0;
+  rec[R_BREAK] = (rec[R_CHOL] != 0.0 || (loops && rec[R_LPIV] != 0.0)) ? 1.0 : 0.0;
   rec[R_RZ] = rec[R_RZ0] = rec[R_ALPHA] = rec[R_BETA] = 0.0;
 }
 
@@ -815,27 +826,10 @@ __global__ __launch_bounds__(PG_B) void pg_beta_kernel(const double* part, int n
   }
 }
 
-// ---- the chain preconditioner: z = N S G S' N' r, S = inclusive prefix sums over the chain edges ------------------------------------------
-// launch 1 of a scan over n 6-vectors (REV: from the last element down): the block-local inclusive scan and the block totals.
-// PRE: element m is N_m' in[m + 1] (`in` has a row per NODE); else it is in[m] (a row per chain edge)
-template <bool REV, bool PRE>
-__global__ __launch_bounds__(PG_B) void pg_scan_local_kernel(int n, const double* __restrict__ in, const double* __restrict__ chain,
-                                                             double* __restrict__ local, double* __restrict__ bsum, const double* rec) {
-  if (pg_stopped(rec)) return;
-  __shared__ double sh[2][PG_B][6];
-  const int l = blockIdx.x * PG_B + threadIdx.x;
-  const int m = REV ? n - 1 - l : l;
-  double v[6] = {0, 0, 0, 0, 0, 0};
-  if (l < n) {
-    if (PRE) {
-      double Nm[36], y[6];
-      ld36(chain + (size_t)m * 72 + 36, Nm);
-      ld6(in + (size_t)(m + 1) * 6, y);
-      m6_tvec(Nm, y, v);
-    } else {
-      ld6(in + (size_t)m * 6, v);
-    }
-  }
+// ---- the scan: inclusive prefix sums of n 6-vectors (REV: from the last element down) in `rows` rows, three launches ----------------------
+// Element l of the scan is element m = l (REV: n - 1 - l) of the data; block b holds the elements l = 256 b .. 256 b + 255.
+// The block-local Hillis-Steele scan of one 6-vector per thread; the result is sh[returned][threadIdx.x]
+__device__ __forceinline__ int pg_block_scan6(double (*sh)[PG_B][6], const double* v) {
   int cur = 0;
   st6(sh[0][threadIdx.x], v);
   __syncthreads();
@@ -848,54 +842,207 @@ __global__ __launch_bounds__(PG_B) void pg_scan_local_kernel(int n, const double
     cur ^= 1;
     __syncthreads();
   }
-  if (l < n) st6(local + (size_t)m * 6, sh[cur][threadIdx.x]);
-  const int last = min(n - blockIdx.x * PG_B, PG_B) - 1;
-  if ((int)threadIdx.x == last) st6(bsum + (size_t)blockIdx.x * 6, sh[cur][threadIdx.x]);
+  return cur;
 }
 
-// launch 2, ONE workgroup: off[b] = the totals of the blocks before b, added in block order
-__global__ void pg_scan_sums_kernel(int nb, const double* __restrict__ bsum, double* __restrict__ off, const double* rec) {
+// launch 1, grid (blocks, rows): load(m, row, v) gives element m of a row (v arrives as zeros); the block-local scan goes to
+// local[m * stride + 6 row], the block's total (written by its last live thread) to bsum
+template <bool REV, class Load>
+__global__ __launch_bounds__(PG_B) void pg_scan_local_kernel(int n, Load load, double* __restrict__ local, int stride,
+                                                             double* __restrict__ bsum, const double* rec) {
+  if (pg_stopped(rec)) return;
+  __shared__ double sh[2][PG_B][6];
+  const int l = blockIdx.x * PG_B + threadIdx.x, row = blockIdx.y;
+  const int m = REV ? n - 1 - l : l;
+  double v[6] = {0, 0, 0, 0, 0, 0};
+  if (l < n) load(m, row, v);
+  const int cur = pg_block_scan6(sh, v);
+  if (l < n) st6(local + (size_t)m * stride + row * 6, sh[cur][threadIdx.x]);
+  const int last = min(n - (int)blockIdx.x * PG_B, PG_B) - 1;
+  if ((int)threadIdx.x == last) st6(bsum + ((size_t)row * gridDim.x + blockIdx.x) * 6, sh[cur][threadIdx.x]);
+}
+// the loaders.  A plain row: in[m]
+struct PgLoadRow {
+  const double* in;
+  __device__ __forceinline__ void operator()(int m, int, double* v) const { ld6(in + (size_t)m * 6, v); }
+};
+// N_m' in[m + 1] (`in` has a row per NODE)
+struct PgLoadNt {
+  const double *in, *chain;
+  __device__ __forceinline__ void operator()(int m, int, double* v) const {
+    double Nm[36], y[6];
+    ld36(chain + (size_t)m * 72 + 36, Nm);
+    ld6(in + (size_t)(m + 1) * 6, y);
+    m6_tvec(Nm, y, v);
+  }
+};
+// row `row` of the 6 x 6 block G_m
+struct PgLoadG {
+  const double* chain;
+  __device__ __forceinline__ void operator()(int m, int row, double* v) const { ld6(chain + (size_t)m * 72 + row * 6, v); }
+};
+// chain edge m takes + sigma_a C_a' d_a for the loop edges whose lo is node m and - for those whose hi is node m, over node m's
+// incidence list in list order
+struct PgLoadLoopDiff {
+  int N, E, L;
+  const int32_t *ptr, *lst;
+  const double *C, *span, *d;
+  __device__ __forceinline__ void operator()(int m, int, double* v) const {
+    int b = ptr[m], en = ptr[m + 1];
+    b = b < 0 ? 0 : b;
+    en = en > 2 * E ? 2 * E : en;
+    for (int k = b; k < en; ++k) {
+      const int a = lst[k] - (N - 1);
+      if (a < 0 || a >= L || span[4 * a + 3] == 0.0) continue;
+      double Ca[36], da[6], t6[6];
+      ld36(C + (size_t)a * 36, Ca);
+      ld6(d + (size_t)a * 6, da);
+      m6_tvec(Ca, da, t6);
+      const double sg = span[4 * a + 2];
+      if ((int)span[4 * a] == m) {
+#pragma unroll
+        for (int q = 0; q < 6; ++q) v[q] = v[q] + sg * t6[q];
+      } else if ((int)span[4 * a + 1] == m) {
+#pragma unroll
+        for (int q = 0; q < 6; ++q) v[q] = v[q] - sg * t6[q];
+      }
+    }
+  }
+};
+
+// launch 2, ONE workgroup, one lane per component: off[b] = the totals of the blocks before b, added in block order
+__global__ void pg_scan_sums_kernel(int nb, int rows, const double* __restrict__ bsum, double* __restrict__ off, const double* rec) {
   if (pg_stopped(rec)) return;
   const int k = threadIdx.x;
-  if (k >= 6) return;
+  if (k >= 6 * rows) return;
+  const int row = k / 6, q = k % 6;
   double tot = 0.0;
   for (int b = 0; b < nb; ++b) {
-    off[(size_t)b * 6 + k] = tot;
-    tot = b ? tot + bsum[(size_t)b * 6 + k] : bsum[k];
+    const size_t at = ((size_t)row * nb + b) * 6 + q;
+    off[at] = tot;
+    tot = b ? tot + bsum[at] : bsum[at];
   }
 }
 
-// launch 3: the block offset added, then the element's transform.  POSTN: out[m + 1] = N_m (.), a row per node, with the partials
-// of r . z when `r` is given; else out[m] = G_m (.), a row per chain edge
-template <bool REV, bool POSTN>
-__global__ __launch_bounds__(PG_B) void pg_scan_apply_kernel(int n, const double* __restrict__ local, const double* __restrict__ off,
-                                                             const double* __restrict__ chain, double* __restrict__ out,
-                                                             const double* __restrict__ r, double* __restrict__ part, const double* rec) {
+// an element after launch 2: its block-local value and, past the first block, its block's offset
+__device__ __forceinline__ void pg_scan_read(const double* loc, const double* off, bool first_block, double* c) {
+  ld6(loc, c);
+  if (!first_block) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) c[k] = c[k] + off[k];
+  }
+}
+// c[m] of a forward scan of one row whose launch 3 has not run
+__device__ __forceinline__ void pgl_prefix_at(const double* local, const double* off, int m, double* c) {
+  pg_scan_read(local + (size_t)m * 6, off + (size_t)(m / PG_B) * 6, m < PG_B, c);
+}
+
+// launch 3, grid (blocks, rows): fin(m, row, first, v) finishes element m from its scanned value v (`first`: it is in the first
+// block, whose values have no offset; a finisher that works IN_PLACE on `local` gets no v there) and returns its term of the dot
+// product, summed per workgroup into fin.part where the finisher has one (Fin::DOT) and it is given.  The finishers' members cannot
+// say that they do not alias: each passes them to a `run` whose parameters can, as the kernels' parameters do
+template <bool REV, class Fin>
+__global__ __launch_bounds__(PG_B) void pg_scan_apply_kernel(int n, const double* local, int stride, const double* __restrict__ off, Fin fin,
+                                                             const double* rec) {
   if (pg_stopped(rec)) return;
-  __shared__ double sh[PG_B];
-  const int l = blockIdx.x * PG_B + threadIdx.x;
+  const int l = blockIdx.x * PG_B + threadIdx.x, row = blockIdx.y;
   const int m = REV ? n - 1 - l : l;
   double d = 0.0;
   if (l < n) {
-    double v[6], M[36], o[6];
-    ld6(local + (size_t)m * 6, v);
-    if (blockIdx.x > 0) {
-#pragma unroll
-      for (int k = 0; k < 6; ++k) v[k] = v[k] + off[(size_t)blockIdx.x * 6 + k];
+    const bool first = blockIdx.x == 0;
+    double v[6] = {0, 0, 0, 0, 0, 0};
+    if (!(Fin::IN_PLACE && first))
+      pg_scan_read(local + (size_t)m * stride + row * 6, off + ((size_t)row * gridDim.x + blockIdx.x) * 6, first, v);
+    d = fin(m, row, first, v);
+  }
+  if constexpr (Fin::DOT) {
+    if (fin.part) {
+      __shared__ double sh[PG_B];
+      const double s = pg_wg_sum(d, sh);
+      if (threadIdx.x == 0) fin.part[blockIdx.x] = s;
     }
-    ld36(chain + (size_t)m * 72 + (POSTN ? 36 : 0), M);
+  }
+}
+// the finishers.  out[m] = G_m v, a row per chain edge; v itself is kept in keep[m] when `keep` is given
+struct PgFinG {
+  static constexpr bool DOT = false, IN_PLACE = false;
+  const double* chain;
+  double *keep, *out;
+  static __device__ __forceinline__ void run(const double* __restrict__ chain, double* __restrict__ keep, double* __restrict__ out, int m,
+                                             const double* v) {
+    double M[36], o[6];
+    if (keep) st6(keep + (size_t)m * 6, v);
+    ld36(chain + (size_t)m * 72, M);
     m6_vec(M, v, o);
-    st6(out + (size_t)(POSTN ? m + 1 : m) * 6, o);
-    if (POSTN && r) {
-      double rv[6];
-      ld6(r + (size_t)(m + 1) * 6, rv);
-      d = v6_dot(rv, o);
+    st6(out + (size_t)m * 6, o);
+  }
+  __device__ __forceinline__ double operator()(int m, int, bool, const double* v) const {
+    run(chain, keep, out, m, v);
+    return 0.0;
+  }
+};
+// out[m] = G_m (s[m] - v)
+struct PgFinDiffG {
+  static constexpr bool DOT = false, IN_PLACE = false;
+  const double *chain, *s;
+  double* out;
+  __device__ __forceinline__ double operator()(int m, int, bool, const double* v) const {
+    double sv[6], M[36], o[6];
+    ld6(s + (size_t)m * 6, sv);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) sv[k] = sv[k] - v[k];
+    ld36(chain + (size_t)m * 72, M);
+    m6_vec(M, sv, o);
+    st6(out + (size_t)m * 6, o);
+    return 0.0;
+  }
+};
+// out[m + 1] = N_m v, a row per node, and its term of r . z when `r` is given
+struct PgFinN {
+  static constexpr bool DOT = true, IN_PLACE = false;
+  const double* chain;
+  double* out;
+  const double* r;
+  double* part;
+  static __device__ __forceinline__ double run(const double* __restrict__ chain, double* __restrict__ out, const double* __restrict__ r,
+                                               int m, const double* v) {
+    double M[36], o[6];
+    ld36(chain + (size_t)m * 72 + 36, M);
+    m6_vec(M, v, o);
+    st6(out + (size_t)(m + 1) * 6, o);
+    if (!r) return 0.0;
+    double rv[6];
+    ld6(r + (size_t)(m + 1) * 6, rv);
+    return v6_dot(rv, o);
+  }
+  __device__ __forceinline__ double operator()(int m, int, bool, const double* v) const { return run(chain, out, r, m, v); }
+};
+// Gamma in place: the block-local scan sits in Gamma[m + 1] already, so only the blocks past the first are written; Gamma[0] = 0
+struct PgFinGamma {
+  static constexpr bool DOT = false, IN_PLACE = true;
+  double* gamma;
+  __device__ __forceinline__ double operator()(int m, int row, bool first, const double* v) const {
+    if (m == 0) {
+#pragma unroll
+      for (int k = 0; k < 6; ++k) gamma[row * 6 + k] = 0.0;
     }
+    if (!first) st6(gamma + (size_t)(m + 1) * 36 + row * 6, v);
+    return 0.0;
   }
-  if (POSTN && part) {
-    const double s = pg_wg_sum(d, sh);
-    if (threadIdx.x == 0) part[blockIdx.x] = s;
-  }
+};
+
+// launches 1 and 2 of one scan; the offsets follow the block totals in `bsum` (12 * rows * blocks doubles)
+template <bool REV, class Load>
+void pg_scan_launch12(int n, int rows, Load load, double* local, int stride, double* bsum, const double* rec, hipStream_t stream) {
+  const int nb = (n + PG_B - 1) / PG_B;
+  pg_scan_local_kernel<REV><<<dim3(nb, rows), PG_B, 0, stream>>>(n, load, local, stride, bsum, rec);
+  pg_scan_sums_kernel<<<1, 64, 0, stream>>>(nb, rows, bsum, bsum + (size_t)6 * rows * nb, rec);
+}
+// Gamma[k] = sum_{m < k} G_m, (n + 1, 6, 6), as six rows of six
+void pg_gamma_scan(int n, const double* chain, double* gamma, double* gsum, hipStream_t stream) {
+  const int nb = (n + PG_B - 1) / PG_B;
+  pg_scan_launch12<false>(n, 6, PgLoadG{chain}, gamma + 36, 36, gsum, nullptr, stream);
+  pg_scan_apply_kernel<false><<<dim3(nb, 6), PG_B, 0, stream>>>(n, gamma + 36, 36, gsum + (size_t)36 * nb, PgFinGamma{gamma}, nullptr);
 }
 
 // z = Dinv r / (1 + lambda) alone (ovn_pose_graph_precondition)
@@ -907,22 +1054,6 @@ __global__ __launch_bounds__(PG_B) void pg_jacobi_apply_kernel(int N, const doub
   ld6(in + (size_t)v * 6, rv);
   (void)pg_jacobi_node(dinv + (size_t)v * 36, scale, rv, zv);
   st6(out + (size_t)v * 6, zv);
-}
-
-// six launches: out = M_chain^-1 in over the nodes 1 .. N - 1 (row 0 of `out` is not written: it is 0 from the start of a solve)
-int pg_chain_apply(int N, const double* chain, const double* in, double* out, const PgWs& w, const double* r_for_dot, double* part,
-                   const double* rec, hipStream_t stream) {
-  const int n = N - 1;
-  if (n < 1) return OVN_OK;
-  const int nb = (n + PG_B - 1) / PG_B;
-  pg_scan_local_kernel<true, true><<<nb, PG_B, 0, stream>>>(n, in, chain, w.sa, w.bsum, rec);
-  pg_scan_sums_kernel<<<1, 64, 0, stream>>>(nb, w.bsum, w.bsum + (size_t)6 * nb, rec);
-  pg_scan_apply_kernel<true, false><<<nb, PG_B, 0, stream>>>(n, w.sa, w.bsum + (size_t)6 * nb, chain, w.sb, nullptr, nullptr, rec);
-  pg_scan_local_kernel<false, false><<<nb, PG_B, 0, stream>>>(n, w.sb, chain, w.sa, w.bsum, rec);
-  pg_scan_sums_kernel<<<1, 64, 0, stream>>>(nb, w.bsum, w.bsum + (size_t)6 * nb, rec);
-  pg_scan_apply_kernel<false, true><<<nb, PG_B, 0, stream>>>(n, w.sa, w.bsum + (size_t)6 * nb, chain, out, r_for_dot, part, rec);
-  OVN_HIP_CHECK(hipGetLastError());
-  return OVN_OK;
 }
 
 // ---- retraction ---------------------------------------------------------------------------------------------------------------------------
@@ -974,7 +1105,6 @@ bool pg_finite(double v) { return v * 0.0 == 0.0; }
 constexpr int PGL_NB = 48;                                  // block size of the factorization: eight 6 x 6 blocks
 constexpr int PGL_TS = 1024;                                // threads of the one-workgroup triangular sweeps
 constexpr int PGL_MAX_SP = (6 * OVN_POSE_GRAPH_MAX_LOOPS + PGL_NB - 1) / PGL_NB * PGL_NB;
-enum { R_LPIV = 13, R_LOUT = 14 };
 
 struct PgLoops {   // the caller's loops_dev, in doubles
   double *gamma, *gsum, *C, *winv, *span, *s, *d, *part, *pf, *S, *F;
@@ -985,8 +1115,7 @@ struct PgLoops {   // the caller's loops_dev, in doubles
     nbl = (L + PG_B - 1) / PG_B;
     sp = (6 * L + PGL_NB - 1) / PGL_NB * PGL_NB;
     nbk = sp / PGL_NB;
-    size_t o = 0;
-    auto take = [&](size_t n) { double* q_ = base ? base + o : nullptr; o += (n + 1) & ~(size_t)1; return q_; };
+    PgTake take{base};
     gamma = take(36 * N);       // Gamma[k] = sum_{m < k} G_m
     C = take(36 * L);           // C_a = B_a Ad(T_j^-1), 0 for an edge that is left out
     winv = take(36 * L);        // (w_a Omega_a)^-1, the identity for an edge that is left out
@@ -998,63 +1127,43 @@ struct PgLoops {   // the caller's loops_dev, in doubles
     d = take(sp);
     part = take(2 * nbl);
     pf = take(nbk);
-    total = o;
+    total = take.o;
   }
 };
 
-// the Hillis-Steele scan of pg_scan_local_kernel over one value of six per thread; the result is sh[returned][threadIdx.x]
-__device__ __forceinline__ int pgl_block_scan6(double (*sh)[PG_B][6], const double* v) {
-  int cur = 0;
-  st6(sh[0][threadIdx.x], v);
-  __syncthreads();
-  for (int d = 1; d < PG_B; d <<= 1) {
+// the 48 x 48 block whose first entry is `a`, rows `lda` doubles apart, staged into LDS by the T threads of the workgroup; a second
+// block (TWO) goes along in the same pass, so that both loads of an entry are in flight together
+template <int T, bool TWO = false>
+__device__ __forceinline__ void pgl_stage_tile(double (*A)[PGL_NB + 1], const double* a, size_t lda, double (*B)[PGL_NB + 1] = nullptr,
+                                               const double* b = nullptr, size_t ldb = 0) {
+  for (int t = threadIdx.x; t < PGL_NB * PGL_NB; t += T) {
+    const int r = t / PGL_NB, c = t % PGL_NB;
+    A[r][c] = a[(size_t)r * lda + c];
+    if (TWO) B[r][c] = b[(size_t)r * ldb + c];
+  }
+}
+// 3 x 3 entries per thread of the product of two staged tiles: acc[u][v] = sum_t A[tr + u][t] B[t][tc + v] (BT: B[tc + v][t]); the
+// first term initialises, the rest are added in the order of t
+template <bool BT>
+__device__ __forceinline__ void pgl_tile_mul3(const double (*A)[PGL_NB + 1], const double (*B)[PGL_NB + 1], int tr, int tc,
+                                              double (*acc)[3]) {
 #pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      const double a = sh[cur][threadIdx.x][k];
-      sh[cur ^ 1][threadIdx.x][k] = (int)threadIdx.x >= d ? a + sh[cur][threadIdx.x - d][k] : a;
+  for (int u = 0; u < 3; ++u)
+#pragma unroll
+    for (int v = 0; v < 3; ++v) acc[u][v] = A[tr + u][0] * (BT ? B[tc + v][0] : B[0][tc + v]);
+#pragma unroll 4
+  for (int t = 1; t < PGL_NB; ++t) {
+    double av[3], bv[3];
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+      av[u] = A[tr + u][t];
+      bv[u] = BT ? B[tc + u][t] : B[t][tc + u];
     }
-    cur ^= 1;
-    __syncthreads();
-  }
-  return cur;
-}
-
-// Gamma, launch 1, grid (blocks, 6): row blockIdx.y of the 6 x 6 blocks G_m, scanned inside the block; Gamma[m + 1] gets the inclusive sum
-__global__ __launch_bounds__(PG_B) void pgl_gamma_local_kernel(int n, const double* __restrict__ chain, double* __restrict__ gamma,
-                                                               double* __restrict__ bsum) {
-  __shared__ double sh[2][PG_B][6];
-  const int m = blockIdx.x * PG_B + threadIdx.x, row = blockIdx.y;
-  double v[6] = {0, 0, 0, 0, 0, 0};
-  if (m < n) ld6(chain + (size_t)m * 72 + row * 6, v);
-  const int cur = pgl_block_scan6(sh, v);
-  if (m < n) st6(gamma + (size_t)(m + 1) * 36 + row * 6, sh[cur][threadIdx.x]);
-  const int last = min(n - (int)blockIdx.x * PG_B, PG_B) - 1;
-  if ((int)threadIdx.x == last) st6(bsum + ((size_t)row * gridDim.x + blockIdx.x) * 6, sh[cur][threadIdx.x]);
-}
-// launch 2, ONE workgroup of 36 lanes: the totals of the blocks before b, added in block order
-__global__ void pgl_gamma_sums_kernel(int nb, const double* __restrict__ bsum, double* __restrict__ off) {
-  const int k = threadIdx.x;
-  if (k >= 36) return;
-  const int row = k / 6, q = k % 6;
-  double tot = 0.0;
-  for (int b = 0; b < nb; ++b) {
-    const size_t at = ((size_t)row * nb + b) * 6 + q;
-    off[at] = tot;
-    tot = b ? tot + bsum[at] : bsum[at];
-  }
-}
-// launch 3: the block offset added; Gamma[0] = 0
-__global__ __launch_bounds__(PG_B) void pgl_gamma_add_kernel(int n, const double* __restrict__ off, double* __restrict__ gamma) {
-  const int m = blockIdx.x * PG_B + threadIdx.x, row = blockIdx.y;
-  if (m == 0) {
 #pragma unroll
-    for (int k = 0; k < 6; ++k) gamma[row * 6 + k] = 0.0;
-  }
-  if (m >= n || blockIdx.x == 0) return;
-  double* g = gamma + (size_t)(m + 1) * 36 + row * 6;
-  const double* o = off + ((size_t)row * gridDim.x + blockIdx.x) * 6;
+    for (int u = 0; u < 3; ++u)
 #pragma unroll
-  for (int k = 0; k < 6; ++k) g[k] = g[k] + o[k];
+      for (int v = 0; v < 3; ++v) acc[u][v] = acc[u][v] + av[u] * bv[v];
+  }
 }
 
 // one loop edge a = edge N - 1 + a per thread: C_a = B_a Ad(T_j^-1), (w_a Omega_a)^-1, lo, hi, sigma.  An edge of weight 0 is left out
@@ -1088,16 +1197,9 @@ __global__ __launch_bounds__(PG_B) void pgl_edge_kernel(const double* __restrict
       }
     }
     if (live) {
-      double R[9], t[3], Rt[9], tt[3], Ad[36], Bm[36];
+      double R[9], t[3], Ad[36], Bm[36];
       pg_load_pose(poses + (size_t)j * 16, R, t);
-#pragma unroll
-      for (int p = 0; p < 3; ++p)
-#pragma unroll
-        for (int q = 0; q < 3; ++q) Rt[p * 3 + q] = R[q * 3 + p];
-      m3_tvec(R, t, tt);
-#pragma unroll
-      for (int p = 0; p < 3; ++p) tt[p] = -tt[p];
-      pg_adjoint(Rt, tt, Ad);
+      pg_adjoint_inv(R, t, Ad);
       ld36(jac + e * 72 + 36, Bm);
       m6_mul(Bm, Ad, Ca);
     }
@@ -1185,10 +1287,7 @@ __global__ __launch_bounds__(64) void pgl_panel_kernel(int sp, int k, double* __
   __shared__ double A[PGL_NB][PGL_NB + 1];
   const int lane = threadIdx.x;
   const size_t base = (size_t)k * PGL_NB;
-  for (int t = lane; t < PGL_NB * PGL_NB; t += 64) {
-    const int r = t / PGL_NB, c = t % PGL_NB;
-    A[r][c] = F[(base + r) * sp + base + c];
-  }
+  pgl_stage_tile<64>(A, F + base * sp + base, sp);
   __syncthreads();
   double fails = 0.0;
   for (int c = 0; c < PGL_NB; ++c) {
@@ -1218,10 +1317,7 @@ __global__ __launch_bounds__(64) void pgl_panel_kernel(int sp, int k, double* __
 __global__ __launch_bounds__(PG_B) void pgl_trsm_kernel(int sp, int k, double* __restrict__ F) {
   __shared__ double Lk[PGL_NB][PGL_NB + 1];
   const size_t base = (size_t)k * PGL_NB;
-  for (int t = threadIdx.x; t < PGL_NB * PGL_NB; t += PG_B) {
-    const int r = t / PGL_NB, c = t % PGL_NB;
-    Lk[r][c] = F[(base + r) * sp + base + c];
-  }
+  pgl_stage_tile<PG_B>(Lk, F + base * sp + base, sp);
   __syncthreads();
   const size_t r = base + PGL_NB + (size_t)blockIdx.x * PG_B + threadIdx.x;
   if (r >= (size_t)sp) return;
@@ -1244,31 +1340,11 @@ __global__ __launch_bounds__(PG_B) void pgl_syrk_kernel(int sp, int k, double* _
   if (tj > ti) return;
   __shared__ double A[PGL_NB][PGL_NB + 1], B[PGL_NB][PGL_NB + 1];
   const size_t p0 = (size_t)k * PGL_NB, r0 = p0 + (size_t)(1 + ti) * PGL_NB, c0 = p0 + (size_t)(1 + tj) * PGL_NB;
-  for (int t = threadIdx.x; t < PGL_NB * PGL_NB; t += PG_B) {
-    const int r = t / PGL_NB, c = t % PGL_NB;
-    A[r][c] = F[(r0 + r) * sp + p0 + c];
-    B[r][c] = F[(c0 + r) * sp + p0 + c];
-  }
+  pgl_stage_tile<PG_B, true>(A, F + r0 * sp + p0, sp, B, F + c0 * sp + p0, sp);
   __syncthreads();
   const int tr = threadIdx.x / 16 * 3, tc = threadIdx.x % 16 * 3;
   double acc[3][3];
-#pragma unroll
-  for (int u = 0; u < 3; ++u)
-#pragma unroll
-    for (int v = 0; v < 3; ++v) acc[u][v] = A[tr + u][0] * B[tc + v][0];
-#pragma unroll 4
-  for (int t = 1; t < PGL_NB; ++t) {
-    double av[3], bv[3];
-#pragma unroll
-    for (int u = 0; u < 3; ++u) {
-      av[u] = A[tr + u][t];
-      bv[u] = B[tc + u][t];
-    }
-#pragma unroll
-    for (int u = 0; u < 3; ++u)
-#pragma unroll
-      for (int v = 0; v < 3; ++v) acc[u][v] = acc[u][v] + av[u] * bv[v];
-  }
+  pgl_tile_mul3<true>(A, B, tr, tc, acc);
 #pragma unroll
   for (int u = 0; u < 3; ++u)
 #pragma unroll
@@ -1289,45 +1365,6 @@ __global__ void pgl_record_kernel(const double* part, int nbl, const double* pf,
   for (int k = 0; k < nbk; ++k) fail = fail + pf[k];
   rec[R_LPIV] = fail;
   rec[R_LOUT] = out;
-}
-
-__global__ void pgl_solve_reset_kernel(double* rec) {
-  if (threadIdx.x != 0) return;
-  rec[R_ITER] = 0.0;
-  rec[R_REL] = 1.0;
-  rec[R_CONV] = 0.0;
-  rec[R_BREAK] = (rec[R_CHOL] != 0.0 || rec[R_LPIV] != 0.0) ? 1.0 : 0.0;
-  rec[R_RZ] = rec[R_RZ0] = rec[R_ALPHA] = rec[R_BETA] = 0.0;
-}
-
-// launch 3 of the suffix scan: s[m] = the scan with its block offset, kept for later, and out[m] = G_m s[m]
-__global__ __launch_bounds__(PG_B) void pgl_suffix_apply_kernel(int n, const double* __restrict__ local, const double* __restrict__ off,
-                                                                const double* __restrict__ chain, double* __restrict__ s_out,
-                                                                double* __restrict__ out, const double* rec) {
-  if (pg_stopped(rec)) return;
-  const int l = blockIdx.x * PG_B + threadIdx.x;
-  if (l >= n) return;
-  const int m = n - 1 - l;
-  double v[6], M[36], o[6];
-  ld6(local + (size_t)m * 6, v);
-  if (blockIdx.x > 0) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) v[k] = v[k] + off[(size_t)blockIdx.x * 6 + k];
-  }
-  st6(s_out + (size_t)m * 6, v);
-  ld36(chain + (size_t)m * 72, M);
-  m6_vec(M, v, o);
-  st6(out + (size_t)m * 6, o);
-}
-
-// c[m] of the forward scan whose launch 3 has not run: the block-local value and the block's offset
-__device__ __forceinline__ void pgl_prefix_at(const double* local, const double* off, int m, double* c) {
-  ld6(local + (size_t)m * 6, c);
-  const int b = m / PG_B;
-  if (b > 0) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) c[k] = c[k] + off[(size_t)b * 6 + k];
-  }
 }
 
 // ONE workgroup: v_a = sigma_a C_a (c[hi_a - 1] - c[lo_a - 1]), then d = S^-1 v by L y = v and L' d = y.  Block column by block
@@ -1361,10 +1398,7 @@ __global__ __launch_bounds__(PGL_TS) void pgl_solve_kernel(int L, int sp, const 
   const int nbk = sp / PGL_NB;
   for (int k = 0; k < nbk; ++k) {
     const size_t base = (size_t)k * PGL_NB;
-    for (int t = tid; t < PGL_NB * PGL_NB; t += PGL_TS) {
-      const int r = t / PGL_NB, c = t % PGL_NB;
-      D[r][c] = F[(base + r) * sp + base + c];
-    }
+    pgl_stage_tile<PGL_TS>(D, F + base * sp + base, sp);
     __syncthreads();
     if (tid < 64) {
       double xv = tid < PGL_NB ? x[base + tid] : 0.0;
@@ -1387,10 +1421,7 @@ __global__ __launch_bounds__(PGL_TS) void pgl_solve_kernel(int L, int sp, const 
   }
   for (int k = nbk - 1; k >= 0; --k) {
     const size_t base = (size_t)k * PGL_NB;
-    for (int t = tid; t < PGL_NB * PGL_NB; t += PGL_TS) {
-      const int r = t / PGL_NB, c = t % PGL_NB;
-      D[r][c] = F[(base + r) * sp + base + c];
-    }
+    pgl_stage_tile<PGL_TS>(D, F + base * sp + base, sp);
     __syncthreads();
     if (tid < 64) {
       double xv = tid < PGL_NB ? x[base + tid] : 0.0;
@@ -1414,78 +1445,89 @@ __global__ __launch_bounds__(PGL_TS) void pgl_solve_kernel(int L, int sp, const 
   for (int idx = tid; idx < sp; idx += PGL_TS) d[idx] = x[idx];
 }
 
-// launch 1 of the difference scan: chain edge m takes + sigma_a C_a' d_a for the loop edges whose lo is node m and - for those whose
-// hi is node m, over node m's incidence list in list order, then the block-local scan
-__global__ __launch_bounds__(PG_B) void pgl_diff_local_kernel(int n, int N, int E, int L, const int32_t* __restrict__ ptr,
-                                                              const int32_t* __restrict__ lst, const double* __restrict__ C,
-                                                              const double* __restrict__ span, const double* __restrict__ d,
-                                                              double* __restrict__ local, double* __restrict__ bsum, const double* rec) {
-  if (pg_stopped(rec)) return;
-  __shared__ double sh[2][PG_B][6];
-  const int m = blockIdx.x * PG_B + threadIdx.x;
-  double v[6] = {0, 0, 0, 0, 0, 0};
-  if (m < n) {
-    int b = ptr[m], en = ptr[m + 1];
-    b = b < 0 ? 0 : b;
-    en = en > 2 * E ? 2 * E : en;
-    for (int k = b; k < en; ++k) {
-      const int a = lst[k] - (N - 1);
-      if (a < 0 || a >= L || span[4 * a + 3] == 0.0) continue;
-      double Ca[36], da[6], t6[6];
-      ld36(C + (size_t)a * 36, Ca);
-      ld6(d + (size_t)a * 6, da);
-      m6_tvec(Ca, da, t6);
-      const double sg = span[4 * a + 2];
-      if ((int)span[4 * a] == m) {
-#pragma unroll
-        for (int q = 0; q < 6; ++q) v[q] = v[q] + sg * t6[q];
-      } else if ((int)span[4 * a + 1] == m) {
-#pragma unroll
-        for (int q = 0; q < 6; ++q) v[q] = v[q] - sg * t6[q];
-      }
-    }
+// ---- the preconditioners and the PCG loop they sit in ---------------------------------------------------------------------------------
+struct PgPrecond {        // what a solve applies as M^-1
+  const double* dj;       // block-Jacobi: dinv, applied inside the init and update kernels with `scale` = 1 / (1 + lambda); else NULL
+  double scale;
+  const double* chain;    // the chain (z = N S G S' N' r, S = inclusive prefix sums over the chain edges) and the loops; else NULL
+  const PgLoops* lp;      // the chain-plus-loops inverse of L loop edges; else NULL
+  int L;
+};
+
+// out = M^-1 in over the nodes 1 .. N - 1 (row 0 of `out` is not written: it is 0 from the start of a solve).  The chain alone is six
+// launches; with loops the suffix scan s is kept, and between the two forward scans S^-1 is applied and the loop edges' terms are
+// scanned and taken off s (out = H^-1 in, undamped): twelve launches
+int pg_precond_apply(int N, int E, const int32_t* ptr, const int32_t* lst, const PgPrecond& pc, const double* in, double* out,
+                     const PgWs& w, const double* r_for_dot, double* part, const double* rec, hipStream_t stream) {
+  const int n = N - 1;
+  if (n < 1) return OVN_OK;
+  const int nb = (n + PG_B - 1) / PG_B;
+  const double* chain = pc.chain;
+  double* off = w.bsum + (size_t)6 * nb;
+  pg_scan_launch12<true>(n, 1, PgLoadNt{in, chain}, w.sa, 6, w.bsum, rec, stream);
+  pg_scan_apply_kernel<true><<<nb, PG_B, 0, stream>>>(n, w.sa, 6, off, PgFinG{chain, pc.lp ? pc.lp->s : nullptr, w.sb}, rec);
+  pg_scan_launch12<false>(n, 1, PgLoadRow{w.sb}, w.sa, 6, w.bsum, rec, stream);
+  if (pc.lp) {
+    const PgLoops& lp = *pc.lp;
+    pgl_solve_kernel<<<1, PGL_TS, 0, stream>>>(pc.L, (int)lp.sp, w.sa, off, lp.C, lp.span, lp.F, lp.d, rec);
+    pg_scan_launch12<false>(n, 1, PgLoadLoopDiff{N, E, pc.L, ptr, lst, lp.C, lp.span, lp.d}, w.sa, 6, w.bsum, rec, stream);
+    pg_scan_apply_kernel<false><<<nb, PG_B, 0, stream>>>(n, w.sa, 6, off, PgFinDiffG{chain, lp.s, w.sb}, rec);
+    pg_scan_launch12<false>(n, 1, PgLoadRow{w.sb}, w.sa, 6, w.bsum, rec, stream);
   }
-  const int cur = pgl_block_scan6(sh, v);
-  if (m < n) st6(local + (size_t)m * 6, sh[cur][threadIdx.x]);
-  const int last = min(n - (int)blockIdx.x * PG_B, PG_B) - 1;
-  if ((int)threadIdx.x == last) st6(bsum + (size_t)blockIdx.x * 6, sh[cur][threadIdx.x]);
-}
-// launch 3 of the difference scan: e[m] = the scan with its block offset, out[m] = G_m (s[m] - e[m])
-__global__ __launch_bounds__(PG_B) void pgl_diff_apply_kernel(int n, const double* __restrict__ local, const double* __restrict__ off,
-                                                              const double* __restrict__ s, const double* __restrict__ chain,
-                                                              double* __restrict__ out, const double* rec) {
-  if (pg_stopped(rec)) return;
-  const int m = blockIdx.x * PG_B + threadIdx.x;
-  if (m >= n) return;
-  double e[6], sv[6], M[36], o[6];
-  pgl_prefix_at(local, off, m, e);
-  ld6(s + (size_t)m * 6, sv);
-#pragma unroll
-  for (int k = 0; k < 6; ++k) sv[k] = sv[k] - e[k];
-  ld36(chain + (size_t)m * 72, M);
-  m6_vec(M, sv, o);
-  st6(out + (size_t)m * 6, o);
+  pg_scan_apply_kernel<false><<<nb, PG_B, 0, stream>>>(n, w.sa, 6, off, PgFinN{chain, out, r_for_dot, part}, rec);
+  OVN_HIP_CHECK(hipGetLastError());
+  return OVN_OK;
 }
 
-// twelve launches: out = H^-1 in (undamped) over the nodes 1 .. N - 1; row 0 of `out` is not written
-int pg_loops_apply(int N, int E, int L, const int32_t* ptr, const int32_t* lst, const double* chain, const PgLoops& lp, const double* in,
-                   double* out, const PgWs& w, const double* r_for_dot, double* part, const double* rec, hipStream_t stream) {
-  const int n = N - 1;
-  const int nb = (n + PG_B - 1) / PG_B;
-  double* off = w.bsum + (size_t)6 * nb;
-  pg_scan_local_kernel<true, true><<<nb, PG_B, 0, stream>>>(n, in, chain, w.sa, w.bsum, rec);
-  pg_scan_sums_kernel<<<1, 64, 0, stream>>>(nb, w.bsum, off, rec);
-  pgl_suffix_apply_kernel<<<nb, PG_B, 0, stream>>>(n, w.sa, off, chain, lp.s, w.sb, rec);
-  pg_scan_local_kernel<false, false><<<nb, PG_B, 0, stream>>>(n, w.sb, chain, w.sa, w.bsum, rec);
-  pg_scan_sums_kernel<<<1, 64, 0, stream>>>(nb, w.bsum, off, rec);
-  pgl_solve_kernel<<<1, PGL_TS, 0, stream>>>(L, (int)lp.sp, w.sa, off, lp.C, lp.span, lp.F, lp.d, rec);
-  pgl_diff_local_kernel<<<nb, PG_B, 0, stream>>>(n, N, E, L, ptr, lst, lp.C, lp.span, lp.d, w.sa, w.bsum, rec);
-  pg_scan_sums_kernel<<<1, 64, 0, stream>>>(nb, w.bsum, off, rec);
-  pgl_diff_apply_kernel<<<nb, PG_B, 0, stream>>>(n, w.sa, off, lp.s, chain, w.sb, rec);
-  pg_scan_local_kernel<false, false><<<nb, PG_B, 0, stream>>>(n, w.sb, chain, w.sa, w.bsum, rec);
-  pg_scan_sums_kernel<<<1, 64, 0, stream>>>(nb, w.bsum, off, rec);
-  pg_scan_apply_kernel<false, true><<<nb, PG_B, 0, stream>>>(n, w.sa, off, chain, out, r_for_dot, part, rec);
+// `iterations` PCG iterations from iteration `first_iteration` (0: from the start) with the preconditioner `pc`
+int pg_pcg(const PgPrecond& pc, const uint8_t* fixed, int N, const int32_t* ij, int E, const int32_t* ptr, const int32_t* lst,
+           const double* blocks, const double* grad, const double* diag, double lambda, double rtol, int first_iteration, int iterations,
+           double* delta, const PgWs& w, double* rec, hipStream_t s) {
+  const int nbn = (N + PG_B - 1) / PG_B, nbc = (N - 1 + PG_B - 1) / PG_B;
+  const int nbz = pc.chain ? nbc : nbn;   // the partials of r . z: per block of chain edges after the scans, else per block of nodes
+  double* part = w.part_n;
+  if (first_iteration == 0) {
+    pg_solve_reset_kernel<<<1, 64, 0, s>>>(rec, pc.lp != nullptr);
+    pg_solve_init_kernel<<<nbn, PG_B, 0, s>>>(fixed, N, grad, pc.dj, pc.scale, delta, w.r, w.z, w.p[0], w.p[1], part, rec);
+    if (pc.chain) {
+      int rc = pg_precond_apply(N, E, ptr, lst, pc, w.r, w.z, w, w.r, part, rec, s);
+      if (rc) return rc;
+    }
+    pg_solve_rz0_kernel<<<1, PG_B, 0, s>>>(part, nbz, rec);
+  }
+  for (int k = 0; k < iterations; ++k) {
+    const int cur = (first_iteration + k) & 1;
+    pg_matvec_kernel<<<nbn, PG_B, 0, s>>>(fixed, N, ij, E, ptr, lst, blocks, diag, lambda, w.z, w.p[cur], w.p[cur ^ 1], w.q, part, rec);
+    pg_alpha_kernel<<<1, PG_B, 0, s>>>(part, nbn, rec);
+    pg_update_kernel<<<nbn, PG_B, 0, s>>>(N, w.p[cur ^ 1], w.q, pc.dj, pc.scale, delta, w.r, w.z, part, rec);
+    if (pc.chain) {
+      int rc = pg_precond_apply(N, E, ptr, lst, pc, w.r, w.z, w, w.r, part, rec, s);
+      if (rc) return rc;
+    }
+    pg_beta_kernel<<<1, PG_B, 0, s>>>(part, nbz, rtol, rec);
+  }
   OVN_HIP_CHECK(hipGetLastError());
+  return OVN_OK;
+}
+
+// the argument checks the entries share; `fn` names the caller in the messages
+int pg_check_lambda(const char* fn, double lambda) {
+  OVN_REQUIRE(pg_finite(lambda) && lambda >= 0.0, OVN_ERR_ARG, "%s: lambda must be finite and >= 0", fn);
+  return OVN_OK;
+}
+int pg_check_iterations(const char* fn, double lambda, double rtol, int first_iteration, int iterations) {
+  if (int rc = pg_check_lambda(fn, lambda)) return rc;
+  OVN_REQUIRE(pg_finite(rtol) && rtol >= 0.0, OVN_ERR_ARG, "%s: rtol must be finite and >= 0", fn);
+  OVN_REQUIRE(first_iteration >= 0 && iterations >= 0 && iterations <= OVN_POSE_GRAPH_MAX_CHUNK, OVN_ERR_ARG,
+              "%s: first_iteration %d (>= 0), iterations %d (0..%d)", fn, first_iteration, iterations, OVN_POSE_GRAPH_MAX_CHUNK);
+  return OVN_OK;
+}
+// a chain of n_nodes - 1 edges and then the loop edges, at least `min_loops` of them
+int pg_check_shape(const char* fn, int n_nodes, int n_edges, int n_loops, int min_loops) {
+  OVN_REQUIRE(n_nodes >= 2 && n_nodes <= OVN_POSE_GRAPH_MAX_NODES && n_loops >= min_loops && n_loops <= OVN_POSE_GRAPH_MAX_LOOPS &&
+                  (int64_t)n_edges == (int64_t)n_nodes - 1 + n_loops, OVN_ERR_ARG,
+              "%s: %d nodes (2..%d), %d loop edges (%d..%d), %d edges (must be nodes - 1 + loop edges)", fn, n_nodes,
+              OVN_POSE_GRAPH_MAX_NODES, n_loops, min_loops, OVN_POSE_GRAPH_MAX_LOOPS, n_edges);
   return OVN_OK;
 }
 
@@ -1493,12 +1535,13 @@ int pg_loops_apply(int N, int E, int L, const int32_t* ptr, const int32_t* lst, 
 // Sigma_world(k) = Gamma[k] - Y_k' Y_k with L_S Y_k = V_k' and V_k = [(Gamma[clamp(k, lo_a, hi_a)] - Gamma[lo_a]) sigma_a C_a']_a: the
 // diagonal blocks of H^-1 = H_c^-1 - H_c^-1 J' S^-1 J H_c^-1 in world tangent coordinates.  A workgroup owns PGM_TN queried nodes, 48
 // columns, and walks the factor's block rows left-looking: X = V' block - sum_t F[kb][t] Y[t] (one subtraction of a 48-term sum in
-// index order per earlier block, in block order), then the diagonal block column by column as pgl_solve_kernel takes it.  Its Y tile
-// lives in the workspace; the 48 x 48 blocks go through LDS.
+// index order per earlier block, in block order), then the diagonal block column by column, one subtraction per column in column
+// order.  Its Y tile lives in the workspace; the 48 x 48 blocks go through LDS.
+// The diagonal-block solve shares no code with pgl_solve_kernel's: there one wave holds one vector in registers and shuffles, here
+// four row groups work on 48 columns through LDS, and one form would change who computes what.
 constexpr int PGM_TN = 8;                 // queried nodes per workgroup: 6 * 8 = PGL_NB columns
 constexpr int PGM_CHUNK = 512;            // workgroups per launch: the Y tiles of one launch are what the workspace holds
 constexpr int PGM_TRI = 21;               // entries of a 6 x 6 lower triangle
-enum { R_MOUT = 15 };
 static_assert(6 * PGM_TN == PGL_NB, "a tile of queried nodes is one factor block wide");
 
 struct PgMarg {   // the caller's ws_dev of ovn_pose_graph_marginals, in doubles
@@ -1511,13 +1554,12 @@ struct PgMarg {   // the caller's ws_dev of ovn_pose_graph_marginals, in doubles
     tiles = (K + PGM_TN - 1) / PGM_TN;
     chunk = tiles < PGM_CHUNK ? tiles : PGM_CHUNK;
     sp = (6 * L + PGL_NB - 1) / PGL_NB * PGL_NB;
-    size_t o = 0;
-    auto take = [&](size_t n) { double* q_ = base ? base + o : nullptr; o += (n + 1) & ~(size_t)1; return q_; };
+    PgTake take{base};
     part = take(nbq);                              // out-of-range ids per finishing workgroup
     gamma = take(L == 0 ? 36 * N : 0);             // without loop edges nobody has scanned Gamma: a copy of its own
     gsum = take(L == 0 ? 72 * nbc : 0);
     Y = take((size_t)chunk * sp * PGL_NB);         // one (sp, 48) tile per workgroup of a launch
-    total = o;
+    total = take.o;
   }
 };
 
@@ -1606,40 +1648,18 @@ __global__ __launch_bounds__(PG_B) void pgm_sweep_kernel(int N, int L, int sp, i
     }
     for (int t = fb; t < kb; ++t) {
       __syncthreads();
-      for (int idx = tid; idx < PGL_NB * PGL_NB; idx += PG_B) {
-        const int r = idx / PGL_NB, c = idx % PGL_NB;
-        A[r][c] = F[((size_t)kb * PGL_NB + r) * sp + (size_t)t * PGL_NB + c];
-        B[r][c] = Yt[((size_t)t * PGL_NB + r) * PGL_NB + c];
-      }
+      pgl_stage_tile<PG_B, true>(A, F + (size_t)kb * PGL_NB * sp + (size_t)t * PGL_NB, sp,
+                                 B, Yt + (size_t)t * PGL_NB * PGL_NB, PGL_NB);
       __syncthreads();
       double s[3][3];
-#pragma unroll
-      for (int u = 0; u < 3; ++u)
-#pragma unroll
-        for (int v = 0; v < 3; ++v) s[u][v] = A[tr + u][0] * B[0][tc + v];
-#pragma unroll 4
-      for (int c = 1; c < PGL_NB; ++c) {
-        double av[3], bv[3];
-#pragma unroll
-        for (int u = 0; u < 3; ++u) {
-          av[u] = A[tr + u][c];
-          bv[u] = B[c][tc + u];
-        }
-#pragma unroll
-        for (int u = 0; u < 3; ++u)
-#pragma unroll
-          for (int v = 0; v < 3; ++v) s[u][v] = s[u][v] + av[u] * bv[v];
-      }
+      pgl_tile_mul3<false>(A, B, tr, tc, s);
 #pragma unroll
       for (int u = 0; u < 3; ++u)
 #pragma unroll
         for (int v = 0; v < 3; ++v) x[u][v] = x[u][v] - s[u][v];
     }
     __syncthreads();
-    for (int idx = tid; idx < PGL_NB * PGL_NB; idx += PG_B) {
-      const int r = idx / PGL_NB, c = idx % PGL_NB;
-      A[r][c] = F[((size_t)kb * PGL_NB + r) * sp + (size_t)kb * PGL_NB + c];
-    }
+    pgl_stage_tile<PG_B>(A, F + (size_t)kb * PGL_NB * sp + (size_t)kb * PGL_NB, sp);
 #pragma unroll
     for (int u = 0; u < 3; ++u)
 #pragma unroll
@@ -1799,11 +1819,7 @@ int ovn_pose_graph_solve(ovn_ctx* ctx, void* stream, const uint8_t* fixed_dev, i
               OVN_POSE_GRAPH_MAX_EDGES);
   OVN_REQUIRE(preconditioner == OVN_POSE_GRAPH_JACOBI || preconditioner == OVN_POSE_GRAPH_CHAIN, OVN_ERR_ARG,
               "ovn_pose_graph_solve: preconditioner %d (0 = block-Jacobi, 1 = odometry chain)", preconditioner);
-  OVN_REQUIRE(pg_finite(lambda) && lambda >= 0.0, OVN_ERR_ARG, "ovn_pose_graph_solve: lambda must be finite and >= 0");
-  OVN_REQUIRE(pg_finite(rtol) && rtol >= 0.0, OVN_ERR_ARG, "ovn_pose_graph_solve: rtol must be finite and >= 0");
-  OVN_REQUIRE(first_iteration >= 0 && iterations >= 0 && iterations <= OVN_POSE_GRAPH_MAX_CHUNK, OVN_ERR_ARG,
-              "ovn_pose_graph_solve: first_iteration %d (>= 0), iterations %d (0..%d)", first_iteration, iterations,
-              OVN_POSE_GRAPH_MAX_CHUNK);
+  if (int rc = pg_check_iterations("ovn_pose_graph_solve", lambda, rtol, first_iteration, iterations)) return rc;
   OVN_REQUIRE(record_dev != nullptr, OVN_ERR_ARG, "ovn_pose_graph_solve: record_dev is NULL");
   OVN_ON_DEVICE(ctx->device);
   hipStream_t s = (hipStream_t)stream;
@@ -1817,34 +1833,9 @@ int ovn_pose_graph_solve(ovn_ctx* ctx, void* stream, const uint8_t* fixed_dev, i
                   ws_dev, OVN_ERR_ARG, "ovn_pose_graph_solve: NULL buffer");
   const bool chain = preconditioner == OVN_POSE_GRAPH_CHAIN;
   OVN_REQUIRE(!chain || chain_dev, OVN_ERR_ARG, "ovn_pose_graph_solve: the chain preconditioner needs chain_dev");
-  PgWs w(ws_dev, n_nodes, n_edges);
-  const int nbn = (n_nodes + PG_B - 1) / PG_B, nbc = (n_nodes - 1 + PG_B - 1) / PG_B;
-  const double scale = 1.0 / (1.0 + lambda);
-  const double* dj = chain ? nullptr : dinv_dev;
-  double* part = w.part_n;
-  if (first_iteration == 0) {
-    pg_solve_reset_kernel<<<1, 64, 0, s>>>(record_dev);
-    pg_solve_init_kernel<<<nbn, PG_B, 0, s>>>(fixed_dev, n_nodes, grad_dev, dj, scale, delta_dev, w.r, w.z, w.p[0], w.p[1], part, record_dev);
-    if (chain) {
-      int rc = pg_chain_apply(n_nodes, chain_dev, w.r, w.z, w, w.r, part, record_dev, s);
-      if (rc) return rc;
-    }
-    pg_solve_rz0_kernel<<<1, PG_B, 0, s>>>(part, chain ? nbc : nbn, record_dev);
-  }
-  for (int k = 0; k < iterations; ++k) {
-    const int cur = (first_iteration + k) & 1;
-    pg_matvec_kernel<<<nbn, PG_B, 0, s>>>(fixed_dev, n_nodes, edge_ij_dev, n_edges, node_ptr_dev, node_edge_dev, blocks_dev, diag_dev, lambda,
-                                          w.z, w.p[cur], w.p[cur ^ 1], w.q, part, record_dev);
-    pg_alpha_kernel<<<1, PG_B, 0, s>>>(part, nbn, record_dev);
-    pg_update_kernel<<<nbn, PG_B, 0, s>>>(n_nodes, w.p[cur ^ 1], w.q, dj, scale, delta_dev, w.r, w.z, part, record_dev);
-    if (chain) {
-      int rc = pg_chain_apply(n_nodes, chain_dev, w.r, w.z, w, w.r, part, record_dev, s);
-      if (rc) return rc;
-    }
-    pg_beta_kernel<<<1, PG_B, 0, s>>>(part, chain ? nbc : nbn, rtol, record_dev);
-  }
-  OVN_HIP_CHECK(hipGetLastError());
-  return OVN_OK;
+  const PgPrecond pc = {chain ? nullptr : dinv_dev, 1.0 / (1.0 + lambda), chain ? chain_dev : nullptr, nullptr, 0};
+  return pg_pcg(pc, fixed_dev, n_nodes, edge_ij_dev, n_edges, node_ptr_dev, node_edge_dev, blocks_dev, grad_dev, diag_dev, lambda, rtol,
+                first_iteration, iterations, delta_dev, PgWs(ws_dev, n_nodes, n_edges), record_dev, s);
 }
 
 int ovn_pose_graph_precondition(ovn_ctx* ctx, void* stream, int n_nodes, int preconditioner, double lambda, const double* dinv_dev,
@@ -1854,7 +1845,7 @@ int ovn_pose_graph_precondition(ovn_ctx* ctx, void* stream, int n_nodes, int pre
               OVN_POSE_GRAPH_MAX_NODES);
   OVN_REQUIRE(preconditioner == OVN_POSE_GRAPH_JACOBI || preconditioner == OVN_POSE_GRAPH_CHAIN, OVN_ERR_ARG,
               "ovn_pose_graph_precondition: preconditioner %d (0 = block-Jacobi, 1 = odometry chain)", preconditioner);
-  OVN_REQUIRE(pg_finite(lambda) && lambda >= 0.0, OVN_ERR_ARG, "ovn_pose_graph_precondition: lambda must be finite and >= 0");
+  if (int rc = pg_check_lambda("ovn_pose_graph_precondition", lambda)) return rc;
   const bool chain = preconditioner == OVN_POSE_GRAPH_CHAIN;
   OVN_REQUIRE(in_dev && out_dev && ws_dev && (chain ? chain_dev != nullptr : dinv_dev != nullptr), OVN_ERR_ARG,
               "ovn_pose_graph_precondition: NULL buffer");
@@ -1866,8 +1857,8 @@ int ovn_pose_graph_precondition(ovn_ctx* ctx, void* stream, int n_nodes, int pre
     return OVN_OK;
   }
   OVN_HIP_CHECK(hipMemsetAsync(out_dev, 0, 6 * sizeof(double), s));   // the fixed node 0
-  PgWs w(ws_dev, n_nodes, 0);
-  return pg_chain_apply(n_nodes, chain_dev, in_dev, out_dev, w, nullptr, nullptr, nullptr, s);
+  const PgPrecond pc = {nullptr, 1.0, chain_dev, nullptr, 0};
+  return pg_precond_apply(n_nodes, 0, nullptr, nullptr, pc, in_dev, out_dev, PgWs(ws_dev, n_nodes, 0), nullptr, nullptr, nullptr, s);
 }
 
 int ovn_pose_graph_retract(ovn_ctx* ctx, void* stream, const double* poses_dev, const uint8_t* fixed_dev, const double* delta_dev,
@@ -1887,12 +1878,6 @@ int ovn_pose_graph_retract(ovn_ctx* ctx, void* stream, const double* poses_dev, 
 }
 
 // ---- the chain-plus-loops inverse -------------------------------------------------------------------------------------------------------
-#define PGL_REQUIRE_SHAPE(what)                                                                                                          \
-  OVN_REQUIRE(n_nodes >= 2 && n_nodes <= OVN_POSE_GRAPH_MAX_NODES && n_loops >= 1 && n_loops <= OVN_POSE_GRAPH_MAX_LOOPS &&              \
-                  (int64_t)n_edges == (int64_t)n_nodes - 1 + n_loops, OVN_ERR_ARG,                                                       \
-              what ": %d nodes (2..%d), %d loop edges (1..%d), %d edges (must be nodes - 1 + loop edges)", n_nodes,                      \
-              OVN_POSE_GRAPH_MAX_NODES, n_loops, OVN_POSE_GRAPH_MAX_LOOPS, n_edges)
-
 int64_t ovn_pose_graph_loops_bytes(int64_t n_nodes, int64_t n_loops) {
   if (n_nodes < 2 || n_nodes > OVN_POSE_GRAPH_MAX_NODES || n_loops < 1 || n_loops > OVN_POSE_GRAPH_MAX_LOOPS) return 0;
   return (int64_t)(PgLoops(nullptr, n_nodes, n_loops).total * sizeof(double));
@@ -1919,7 +1904,7 @@ int ovn_pose_graph_loops_prepare(ovn_ctx* ctx, void* stream, const double* poses
                                  const double* info_dev, const double* weight_dev, const double* jac_dev, int n_edges, int n_loops,
                                  const double* chain_dev, int stages, double* loops_dev, double* record_dev) {
   OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_pose_graph_loops_prepare: ctx is NULL");
-  PGL_REQUIRE_SHAPE("ovn_pose_graph_loops_prepare");
+  if (int rc = pg_check_shape("ovn_pose_graph_loops_prepare", n_nodes, n_edges, n_loops, 1)) return rc;
   OVN_REQUIRE(stages >= 1 && stages <= OVN_POSE_GRAPH_LOOPS_ALL, OVN_ERR_ARG, "ovn_pose_graph_loops_prepare: stages %d (a sum of 1 = scan, "
               "2 = assembly, 4 = factorization)", stages);
   OVN_REQUIRE(poses_dev && edge_ij_dev && info_dev && weight_dev && jac_dev && chain_dev && loops_dev && record_dev, OVN_ERR_ARG,
@@ -1927,13 +1912,8 @@ int ovn_pose_graph_loops_prepare(ovn_ctx* ctx, void* stream, const double* poses
   OVN_ON_DEVICE(ctx->device);
   hipStream_t s = (hipStream_t)stream;
   PgLoops lp(loops_dev, n_nodes, n_loops);
-  const int n = n_nodes - 1, nbc = (int)lp.nbc, nbl = (int)lp.nbl, sp = (int)lp.sp, nbk = (int)lp.nbk, n6 = 6 * n_loops;
-  double* goff = lp.gsum + (size_t)36 * nbc;
-  if (stages & OVN_POSE_GRAPH_LOOPS_SCAN) {
-    pgl_gamma_local_kernel<<<dim3(nbc, 6), PG_B, 0, s>>>(n, chain_dev, lp.gamma, lp.gsum);
-    pgl_gamma_sums_kernel<<<1, 64, 0, s>>>(nbc, lp.gsum, goff);
-    pgl_gamma_add_kernel<<<dim3(nbc, 6), PG_B, 0, s>>>(n, goff, lp.gamma);
-  }
+  const int nbl = (int)lp.nbl, sp = (int)lp.sp, nbk = (int)lp.nbk, n6 = 6 * n_loops;
+  if (stages & OVN_POSE_GRAPH_LOOPS_SCAN) pg_gamma_scan(n_nodes - 1, chain_dev, lp.gamma, lp.gsum, s);
   if (stages & OVN_POSE_GRAPH_LOOPS_ASSEMBLE) {
     pgl_edge_kernel<<<nbl, PG_B, 0, s>>>(poses_dev, n_nodes, edge_ij_dev, info_dev, weight_dev, jac_dev, n_loops, lp.C, lp.winv, lp.span,
                                          lp.part);
@@ -1959,56 +1939,32 @@ int ovn_pose_graph_solve_loops(ovn_ctx* ctx, void* stream, const uint8_t* fixed_
                                double lambda, double rtol, int first_iteration, int iterations, double* delta_dev, double* ws_dev,
                                double* record_dev) {
   OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_pose_graph_solve_loops: ctx is NULL");
-  PGL_REQUIRE_SHAPE("ovn_pose_graph_solve_loops");
-  OVN_REQUIRE(pg_finite(lambda) && lambda >= 0.0, OVN_ERR_ARG, "ovn_pose_graph_solve_loops: lambda must be finite and >= 0");
-  OVN_REQUIRE(pg_finite(rtol) && rtol >= 0.0, OVN_ERR_ARG, "ovn_pose_graph_solve_loops: rtol must be finite and >= 0");
-  OVN_REQUIRE(first_iteration >= 0 && iterations >= 0 && iterations <= OVN_POSE_GRAPH_MAX_CHUNK, OVN_ERR_ARG,
-              "ovn_pose_graph_solve_loops: first_iteration %d (>= 0), iterations %d (0..%d)", first_iteration, iterations,
-              OVN_POSE_GRAPH_MAX_CHUNK);
+  if (int rc = pg_check_shape("ovn_pose_graph_solve_loops", n_nodes, n_edges, n_loops, 1)) return rc;
+  if (int rc = pg_check_iterations("ovn_pose_graph_solve_loops", lambda, rtol, first_iteration, iterations)) return rc;
   OVN_REQUIRE(fixed_dev && edge_ij_dev && node_ptr_dev && node_edge_dev && blocks_dev && grad_dev && diag_dev && dinv_dev && chain_dev &&
                   loops_dev && delta_dev && ws_dev && record_dev, OVN_ERR_ARG, "ovn_pose_graph_solve_loops: NULL buffer");
   OVN_ON_DEVICE(ctx->device);
   hipStream_t s = (hipStream_t)stream;
-  PgWs w(ws_dev, n_nodes, n_edges);
-  PgLoops lp(loops_dev, n_nodes, n_loops);
-  const int nbn = (n_nodes + PG_B - 1) / PG_B, nbc = (n_nodes - 1 + PG_B - 1) / PG_B;
-  double* part = w.part_n;
-  if (first_iteration == 0) {
-    pgl_solve_reset_kernel<<<1, 64, 0, s>>>(record_dev);
-    pg_solve_init_kernel<<<nbn, PG_B, 0, s>>>(fixed_dev, n_nodes, grad_dev, nullptr, 1.0, delta_dev, w.r, w.z, w.p[0], w.p[1], part,
-                                              record_dev);
-    int rc = pg_loops_apply(n_nodes, n_edges, n_loops, node_ptr_dev, node_edge_dev, chain_dev, lp, w.r, w.z, w, w.r, part, record_dev, s);
-    if (rc) return rc;
-    pg_solve_rz0_kernel<<<1, PG_B, 0, s>>>(part, nbc, record_dev);
-  }
-  for (int k = 0; k < iterations; ++k) {
-    const int cur = (first_iteration + k) & 1;
-    pg_matvec_kernel<<<nbn, PG_B, 0, s>>>(fixed_dev, n_nodes, edge_ij_dev, n_edges, node_ptr_dev, node_edge_dev, blocks_dev, diag_dev, lambda,
-                                          w.z, w.p[cur], w.p[cur ^ 1], w.q, part, record_dev);
-    pg_alpha_kernel<<<1, PG_B, 0, s>>>(part, nbn, record_dev);
-    pg_update_kernel<<<nbn, PG_B, 0, s>>>(n_nodes, w.p[cur ^ 1], w.q, nullptr, 1.0, delta_dev, w.r, w.z, part, record_dev);
-    int rc = pg_loops_apply(n_nodes, n_edges, n_loops, node_ptr_dev, node_edge_dev, chain_dev, lp, w.r, w.z, w, w.r, part, record_dev, s);
-    if (rc) return rc;
-    pg_beta_kernel<<<1, PG_B, 0, s>>>(part, nbc, rtol, record_dev);
-  }
-  OVN_HIP_CHECK(hipGetLastError());
-  return OVN_OK;
+  const PgLoops lp(loops_dev, n_nodes, n_loops);
+  const PgPrecond pc = {nullptr, 1.0, chain_dev, &lp, n_loops};
+  return pg_pcg(pc, fixed_dev, n_nodes, edge_ij_dev, n_edges, node_ptr_dev, node_edge_dev, blocks_dev, grad_dev, diag_dev, lambda, rtol,
+                first_iteration, iterations, delta_dev, PgWs(ws_dev, n_nodes, n_edges), record_dev, s);
 }
 
 int ovn_pose_graph_precondition_loops(ovn_ctx* ctx, void* stream, int n_nodes, int n_edges, int n_loops, const int32_t* node_ptr_dev,
                                       const int32_t* node_edge_dev, const double* chain_dev, double* loops_dev, const double* in_dev,
                                       double* out_dev, double* ws_dev) {
   OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_pose_graph_precondition_loops: ctx is NULL");
-  PGL_REQUIRE_SHAPE("ovn_pose_graph_precondition_loops");
+  if (int rc = pg_check_shape("ovn_pose_graph_precondition_loops", n_nodes, n_edges, n_loops, 1)) return rc;
   OVN_REQUIRE(node_ptr_dev && node_edge_dev && chain_dev && loops_dev && in_dev && out_dev && ws_dev, OVN_ERR_ARG,
               "ovn_pose_graph_precondition_loops: NULL buffer");
   OVN_ON_DEVICE(ctx->device);
   hipStream_t s = (hipStream_t)stream;
   OVN_HIP_CHECK(hipMemsetAsync(out_dev, 0, 6 * sizeof(double), s));   // the fixed node 0
-  PgWs w(ws_dev, n_nodes, 0);
-  PgLoops lp(loops_dev, n_nodes, n_loops);
-  return pg_loops_apply(n_nodes, n_edges, n_loops, node_ptr_dev, node_edge_dev, chain_dev, lp, in_dev, out_dev, w, nullptr, nullptr, nullptr,
-                        s);
+  const PgLoops lp(loops_dev, n_nodes, n_loops);
+  const PgPrecond pc = {nullptr, 1.0, chain_dev, &lp, n_loops};
+  return pg_precond_apply(n_nodes, n_edges, node_ptr_dev, node_edge_dev, pc, in_dev, out_dev, PgWs(ws_dev, n_nodes, 0), nullptr, nullptr,
+                          nullptr, s);
 }
 
 // ---- marginal covariances ---------------------------------------------------------------------------------------------------------------
@@ -2023,10 +1979,7 @@ int ovn_pose_graph_marginals(ovn_ctx* ctx, void* stream, const double* poses_dev
                              const double* chain_dev, const double* loops_dev, const int32_t* node_ids_dev, int64_t n_query, int frame,
                              double* cov_dev, double* ws_dev, double* record_dev) {
   OVN_REQUIRE(ctx != nullptr, OVN_ERR_ARG, "ovn_pose_graph_marginals: ctx is NULL");
-  OVN_REQUIRE(n_nodes >= 2 && n_nodes <= OVN_POSE_GRAPH_MAX_NODES && n_loops >= 0 && n_loops <= OVN_POSE_GRAPH_MAX_LOOPS &&
-                  (int64_t)n_edges == (int64_t)n_nodes - 1 + n_loops, OVN_ERR_ARG,
-              "ovn_pose_graph_marginals: %d nodes (2..%d), %d loop edges (0..%d), %d edges (must be nodes - 1 + loop edges)", n_nodes,
-              OVN_POSE_GRAPH_MAX_NODES, n_loops, OVN_POSE_GRAPH_MAX_LOOPS, n_edges);
+  if (int rc = pg_check_shape("ovn_pose_graph_marginals", n_nodes, n_edges, n_loops, 0)) return rc;
   OVN_REQUIRE(n_query >= 1 && n_query <= OVN_POSE_GRAPH_MAX_QUERY, OVN_ERR_ARG, "ovn_pose_graph_marginals: %lld queried nodes (1..%d)",
               (long long)n_query, OVN_POSE_GRAPH_MAX_QUERY);
   OVN_REQUIRE(frame == OVN_POSE_GRAPH_COV_LOCAL || frame == OVN_POSE_GRAPH_COV_POSITION, OVN_ERR_ARG,
@@ -2039,11 +1992,7 @@ int ovn_pose_graph_marginals(ovn_ctx* ctx, void* stream, const double* poses_dev
   pgm_reset_kernel<<<1, 64, 0, s>>>(record_dev, n_loops);
   const double* gamma = m.gamma;
   if (n_loops == 0) {   // dead reckoning: Gamma alone, scanned here
-    const int n = n_nodes - 1, nbc = (int)m.nbc;
-    double* goff = m.gsum + (size_t)36 * nbc;
-    pgl_gamma_local_kernel<<<dim3(nbc, 6), PG_B, 0, s>>>(n, chain_dev, m.gamma, m.gsum);
-    pgl_gamma_sums_kernel<<<1, 64, 0, s>>>(nbc, m.gsum, goff);
-    pgl_gamma_add_kernel<<<dim3(nbc, 6), PG_B, 0, s>>>(n, goff, m.gamma);
+    pg_gamma_scan(n_nodes - 1, chain_dev, m.gamma, m.gsum, s);
   } else {
     PgLoops lp(const_cast<double*>(loops_dev), n_nodes, n_loops);
     gamma = lp.gamma;

@@ -106,6 +106,8 @@ def test_prepare(eng, ref, name):
               % (name, k, fig, err, " (the same bits)" if np.array_equal(a, fwd[k]) else ""))
     for k, a in got.items():
         assert _rel(a, fwd[k]) <= 10 * _rel(rev[k], fwd[k]), k
+    G = d["buf"]["chain"][:, 0].cpu().numpy()                          # no libm between the G the GPU holds and its Gamma
+    assert np.array_equal(v["gamma"], LR.gamma(G)), "Gamma is the scan of G in the scans' order of additions, to the bit"
     assert np.array_equal(v["S"], v["S"].T), "S is symmetric by construction"
     assert np.all(np.triu(v["factor"], 1) == 0)
     pad = slice(6 * L, v["sp"])
