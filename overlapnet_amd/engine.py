@@ -3,6 +3,10 @@
 PyTorch-ROCm is used only as the owner of device memory and for the current HIP stream; every
 computation is a C-ABI call into the hand-written HIP kernels.  Nothing here falls back to torch
 math or to the CPU oracle.
+
+Every entry point is built from the same three pieces: `OvnEngine._check` refuses a tensor the library must not see, `_call` makes
+the native call on this engine's device and raises on its status, and `_image_outputs` allocates the per-pixel outputs of the calls
+that make images.  A new entry point is a row in `_lib.SIGNATURES`, a list of checks and one `_call`.
 """
 from __future__ import annotations
 
@@ -30,6 +34,11 @@ class _NoContext(object):
 
 _NO_CONTEXT = _NoContext()
 _MATCH_PENDING = 0x7FFFFFF0      # word 3 of a best-match record that the kernel has not written yet (it writes 0 or 1)
+_F32, _I32 = torch.float32, torch.int32
+# per-pixel outputs of the calls that make images, in the order the library takes them: name -> (trailing shape, dtype)
+_PROJECT_OUTPUTS = {"range": ((), _F32), "vertex": ((4,), _F32), "intensity": ((), _F32), "idx": ((), _I32), "normal": ((3,), _F32)}
+_RENDER_OUTPUTS = {"range": ((), _F32), "tri_id": ((), _I32), "vertex": ((4,), _F32), "normal": ((3,), _F32)}
+_RAYCAST_OUTPUTS = {"range": ((), _F32), "vertex": ((4,), _F32), "normal": ((3,), _F32)}
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -90,6 +99,56 @@ class OvnEngine:
         of a single query)."""
         return _NO_CONTEXT if torch.cuda.current_device() == self.device_index else torch.cuda.device(self.device)
 
+    # -- the pieces every entry point is made of ------------------------------------------------------
+    def _call(self, name: str, *args, what: Optional[str] = None) -> None:
+        """The native call `name(ctx, *args)` with this engine's GPU current; a status other than 0 raises with the library's message.
+        The stream is among `args`: second in the newer entry points, last in the older ones."""
+        with self._dev():
+            _lib.check(getattr(self.lib, name)(self._h, *args), what or name)
+
+    def _check(self, t: Optional[torch.Tensor], what: str, dtype=_F32, shape=None, numel: Optional[int] = None,
+               ndim: Optional[int] = None, optional: bool = False, pinned_ok: bool = False) -> Optional[torch.Tensor]:
+        """The one test of a tensor that goes to the library: contiguous, of `dtype`, on this device (pinned_ok: or pinned host memory,
+        which the device sees at the same address), and of the exact `shape`, `numel` elements or `ndim` dimensions where given.
+        `what` names the argument in the message, with the call in front ("call: name") where one is named.  Returns the tensor."""
+        if t is None and optional:
+            return None
+        if (t is None or t.dtype != dtype or not t.is_contiguous()
+                or not (t.device == self.device or (pinned_ok and t.device.type == "cpu" and t.is_pinned()))
+                or (shape is not None and tuple(t.shape) != tuple(shape)) or (numel is not None and t.numel() != numel)
+                or (ndim is not None and t.dim() != ndim)):
+            size = ("" if shape is None else " of shape %s" % (tuple(shape),)) + ("" if numel is None else " of %d elements" % numel) \
+                + ("" if ndim is None else " of %d dimensions" % ndim)
+            raise _lib.OvnError("%s must be a contiguous %s tensor%s on %s%s"
+                                % (what, dtype, size, self.device, " (or pinned host memory)" if pinned_ok else ""))
+        return t
+
+    def _poses64(self, poses) -> torch.Tensor:
+        """Poses (a tensor or a host array) as a contiguous float64 tensor on the device."""
+        if isinstance(poses, torch.Tensor):
+            return poses.to(self.device, torch.float64).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(poses, np.float64))).to(self.device)
+
+    def _image_outputs(self, n: int, h: int, w: int, table, want, channels: Optional[int] = None,
+                       stacked_out: Optional[torch.Tensor] = None, min_channels: int = 0, out=None, what: str = ""):
+        """The (n, h, w, ...) outputs of a call that makes images.  table: name -> (trailing shape, dtype) in the library's order.  An
+        output is the caller's tensor when `out` holds its name, a fresh one when `want` names it, and absent otherwise.  channels:
+        the stacked leg input's, None for a call that assembles none; it goes into `stacked_out` when given, which must have exactly
+        `channels`, and is else allocated with max(channels, min_channels).  Returns (dict of the outputs present, stacked or None)."""
+        bufs = {}
+        for name, (tail, dt) in table.items():
+            if out is not None and name in out:
+                bufs[name] = self._check(out[name], "%sout[%r]" % (what, name), dt, (n, h, w) + tail)
+            elif name in want:
+                bufs[name] = torch.empty((n, h, w) + tail, dtype=dt, device=self.device)
+        stk = None
+        if channels is not None:
+            if stacked_out is not None:
+                stk = self._check(stacked_out, "stacked_out", _F32, (n, h, w, channels))
+            else:
+                stk = torch.empty((n, h, w, max(channels, min_channels)), dtype=_F32, device=self.device)
+        return bufs, stk
+
     # -- weights ------------------------------------------------------------------------------------
     def load_weights(self, weights: Dict[str, np.ndarray], model_cfg: Optional[dict] = None) -> None:
         """Register leg + head weights given by Keras layer name (reference infer.py:117-120).  The optional model keys
@@ -110,22 +169,22 @@ class OvnEngine:
             for l in W.leg_layers(self.in_c, cfg):
                 k = torch.from_numpy(np.ascontiguousarray(weights[l.name + "/kernel"], np.float32)).to(self.device)
                 b = torch.from_numpy(np.ascontiguousarray(weights[l.name + "/bias"], np.float32)).to(self.device)
-                _lib.check(self.lib.ovn_add_leg_layer(self._h, l.name.encode(), _ptr(k), _ptr(b), l.kh, l.kw, l.cin,
-                                                      l.cout, l.sh, l.sw, st), "ovn_add_leg_layer(%s)" % l.name)
+                self._call("ovn_add_leg_layer", l.name.encode(), _ptr(k), _ptr(b), l.kh, l.kw, l.cin, l.cout, l.sh, l.sw, st,
+                           what="ovn_add_leg_layer(%s)" % l.name)
             fw = C.c_int(0)
-            _lib.check(self.lib.ovn_finalize(self._h, C.byref(fw)), "ovn_finalize")
+            self._call("ovn_finalize", C.byref(fw))
             self.feat_w = fw.value
             self._leg_ready = True
             self._leg_cfg = {k: cfg[k] for k in ("strides_layer1", "additional_unsymmetric_layer3a") if k in cfg}
             if self.conv1size != 15:   # any other value: the library's general fp32 Delta path (no Delta cache)
-                _lib.check(self.lib.ovn_set_head_geometry(self._h, self.conv1size), "ovn_set_head_geometry")
+                self._call("ovn_set_head_geometry", self.conv1size)
             names = ["c_conv1", "c_conv2", "c_conv3", "overlap_output"]
             ts = []
             for n in names:
                 k = np.ascontiguousarray(weights[n + "/kernel"], np.float32)
                 ts.append(torch.from_numpy(-k if (negate and n == "c_conv1") else k).to(self.device))
                 ts.append(torch.from_numpy(np.ascontiguousarray(weights[n + "/bias"], np.float32)).to(self.device))
-            _lib.check(self.lib.ovn_set_head_weights(self._h, *[_ptr(t) for t in ts], st), "ovn_set_head_weights")
+            self._call("ovn_set_head_weights", *[_ptr(t) for t in ts], st)
             self._head_ready = True
             self.negate_diffs = negate
             torch.cuda.synchronize(self.device)
@@ -135,17 +194,14 @@ class OvnEngine:
     # -- leg ----------------------------------------------------------------------------------------
     def leg(self, images: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """images (n, H, W, C) float32 on this device -> feature volumes (n, feat_w, 128)."""
-        if not self._leg_ready:
-            raise _lib.OvnError("leg weights not loaded")
-        if images.device != self.device or images.dtype != torch.float32 or not images.is_contiguous():
-            raise _lib.OvnError("leg input must be a contiguous float32 tensor on %s" % self.device)
+        self._require_leg()
+        self._check(images, "leg input")
         if tuple(images.shape[1:]) != (self.in_h, self.in_w, self.in_c):
             raise _lib.OvnError("leg input shape %s, expected (n,%d,%d,%d)" % (tuple(images.shape), self.in_h, self.in_w, self.in_c))
         n = images.shape[0]
         if out is None:
             out = torch.empty((n, self.feat_w, FEAT_C), dtype=torch.float32, device=self.device)
-        with self._dev():
-            _lib.check(self.lib.ovn_leg(self._h, _ptr(images), n, _ptr(out), self._stream()), "ovn_leg")
+        self._call("ovn_leg", _ptr(images), n, _ptr(out), self._stream())
         return out
 
     # -- heads --------------------------------------------------------------------------------------
@@ -159,11 +215,21 @@ class OvnEngine:
         """The spectral correlation head (`spectrum`, `corr_head_spectral`, spec_l / spec_r of `heads`) runs 360-column volumes only."""
         return self._fw == FEAT_W
 
-    def _check_feats(self, t: torch.Tensor, what: str) -> None:
-        if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous():
-            raise _lib.OvnError("%s must be a contiguous float32 tensor on %s" % (what, self.device))
-        if t.numel() % (self._fw * FEAT_C) != 0:
+    def _require_head(self) -> None:
+        if not self._head_ready:
+            raise _lib.OvnError("head weights not loaded")
+
+    def _require_spectrum(self) -> None:
+        if not self.has_spectrum:
+            raise _lib.OvnError("spectra exist for 360-column feature volumes only (this leg produces %d)" % self._fw)
+
+    def _check_feats(self, t: torch.Tensor, what: str) -> int:
+        """A stack of feature volumes; returns how many."""
+        self._check(t, what)
+        n, rest = divmod(t.numel(), self._fw * FEAT_C)
+        if rest:
             raise _lib.OvnError("%s is not a stack of %dx128 feature volumes" % (what, self._fw))
+        return n
 
     def _idx(self, idx, n: Optional[int], bound: Optional[int] = None, what: str = "pair index") -> Optional[torch.Tensor]:
         """Index list -> int32 device tensor.  Host lists / arrays are range-checked ON THE HOST before the upload (no device
@@ -208,6 +274,21 @@ class OvnEngine:
             raise _lib.OvnError("the right-hand side holds no feature volume")
         return li, ri, n
 
+    def _heads_outputs(self, n: int, want_logit: bool, want_corr: bool):
+        """(overlap (n) f32, yaw (n) i32, logit (n) f32 or None, corr (n, feat_w) f32 or None) for a call of both heads."""
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
+        return (f32(n), torch.empty(n, dtype=torch.int32, device=self.device), f32(n) if want_logit else None,
+                f32(n, self._fw) if want_corr else None)
+
+    @staticmethod
+    def _heads_result(overlap, yaw, logit, corr) -> Dict[str, torch.Tensor]:
+        out = {"overlap": overlap, "yaw": yaw}
+        if logit is not None:
+            out["logit"] = logit
+        if corr is not None:
+            out["corr"] = corr
+        return out
+
     def heads(self, feats_l: torch.Tensor, feats_r: torch.Tensor, lidx=None, ridx=None, n: Optional[int] = None,
               want_logit: bool = False, want_corr: bool = False, spec_l: Optional[torch.Tensor] = None,
               spec_r: Optional[torch.Tensor] = None, dcache_l: Optional[torch.Tensor] = None):
@@ -217,54 +298,25 @@ class OvnEngine:
         (`delta_cache`), used by 1-vs-N sweeps -- same results with or without it.
         Returns dict of device tensors: overlap (n) f32, yaw (n) i32 [, logit (n), corr (n, feat_w)].  At feat_w != 360 there are no
         spectra or Delta cache rows: spec_l / spec_r raise."""
-        if not self._head_ready:
-            raise _lib.OvnError("head weights not loaded")
-        self._check_feats(feats_l, "feats_l")
-        self._check_feats(feats_r, "feats_r")
-        nl = feats_l.numel() // (self._fw * FEAT_C)
-        nr = feats_r.numel() // (self._fw * FEAT_C)
+        self._require_head()
+        nl, nr = self._check_feats(feats_l, "feats_l"), self._check_feats(feats_r, "feats_r")
         li, ri, n = self._pairs(nl, nr, lidx, ridx, n)
-        overlap = torch.empty(n, dtype=torch.float32, device=self.device)
-        logit = torch.empty(n, dtype=torch.float32, device=self.device) if want_logit else None
-        if spec_l is not None or spec_r is not None:
-            # cached spectra given: Delta head on the features, correlation head in its HBM-bound spectral form
-            if spec_l is None or spec_r is None:
-                raise _lib.OvnError("spec_l and spec_r must be given together")
-            if not self.has_spectrum:
-                raise _lib.OvnError("spectra exist for 360-column feature volumes only (this leg produces %d)" % self._fw)
-            for t, what in ((spec_l, "spec_l"), (spec_r, "spec_r")):
-                if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous():
-                    raise _lib.OvnError("%s must be a contiguous float32 tensor on %s" % (what, self.device))
-            if spec_l.numel() != nl * FEAT_C * self.SPEC_W or spec_r.numel() != nr * FEAT_C * self.SPEC_W:
-                raise _lib.OvnError("spec_l / spec_r must hold one 128x368 spectrum per feature volume")
-            if dcache_l is not None:
-                if dcache_l.device != self.device or dcache_l.dtype != torch.float32 or not dcache_l.is_contiguous():
-                    raise _lib.OvnError("dcache_l must be a contiguous float32 tensor on %s" % self.device)
-                if dcache_l.numel() != nl * self.DELTA_CACHE_ELEMS:
-                    raise _lib.OvnError("dcache_l must hold one Delta cache row per left feature volume")
-            yaw = torch.empty(n, dtype=torch.int32, device=self.device)
-            corr = torch.empty((n, FEAT_W), dtype=torch.float32, device=self.device) if want_corr else None
-            with self._dev():
-                _lib.check(self.lib.ovn_heads_spectral(self._h, _ptr(feats_l), _ptr(spec_l), _ptr(dcache_l), _ptr(li), _ptr(feats_r),
-                                                       _ptr(spec_r), _ptr(ri), n, _ptr(overlap), _ptr(yaw), _ptr(logit), _ptr(corr),
-                                                       self._stream()), "ovn_heads_spectral")
-            out = {"overlap": overlap, "yaw": yaw}
-            if want_logit:
-                out["logit"] = logit
-            if want_corr:
-                out["corr"] = corr
-            return out
-        yaw = torch.empty(n, dtype=torch.int32, device=self.device)
-        corr = torch.empty((n, self._fw), dtype=torch.float32, device=self.device) if want_corr else None
-        with self._dev():
-            _lib.check(self.lib.ovn_heads(self._h, _ptr(feats_l), _ptr(li), _ptr(feats_r), _ptr(ri), n, _ptr(overlap),
-                                          _ptr(yaw), _ptr(logit), _ptr(corr), self._stream()), "ovn_heads")
-        out = {"overlap": overlap, "yaw": yaw}
-        if want_logit:
-            out["logit"] = logit
-        if want_corr:
-            out["corr"] = corr
-        return out
+        if spec_l is None and spec_r is None:
+            overlap, yaw, logit, corr = self._heads_outputs(n, want_logit, want_corr)
+            self._call("ovn_heads", _ptr(feats_l), _ptr(li), _ptr(feats_r), _ptr(ri), n, _ptr(overlap), _ptr(yaw), _ptr(logit), _ptr(corr),
+                       self._stream())
+            return self._heads_result(overlap, yaw, logit, corr)
+        # cached spectra given: Delta head on the features, correlation head in its HBM-bound spectral form
+        if spec_l is None or spec_r is None:
+            raise _lib.OvnError("spec_l and spec_r must be given together")
+        self._require_spectrum()
+        self._check(spec_l, "spec_l", numel=nl * FEAT_C * self.SPEC_W)        # one 128x368 spectrum per feature volume
+        self._check(spec_r, "spec_r", numel=nr * FEAT_C * self.SPEC_W)
+        self._check(dcache_l, "dcache_l", numel=nl * self.DELTA_CACHE_ELEMS, optional=True)     # one row per left feature volume
+        overlap, yaw, logit, corr = self._heads_outputs(n, want_logit, want_corr)
+        self._call("ovn_heads_spectral", _ptr(feats_l), _ptr(spec_l), _ptr(dcache_l), _ptr(li), _ptr(feats_r), _ptr(spec_r), _ptr(ri), n,
+                   _ptr(overlap), _ptr(yaw), _ptr(logit), _ptr(corr), self._stream())
+        return self._heads_result(overlap, yaw, logit, corr)
 
     def heads_segments(self, feats_pool: torch.Tensor, feats_q: torch.Tensor, cand_idx, query_idx, seg_offsets,
                        spec_pool: Optional[torch.Tensor] = None, spec_q: Optional[torch.Tensor] = None,
@@ -278,56 +330,30 @@ class OvnEngine:
         The library stages the table through one pinned buffer: a segmented call (this one or `top_k_segments`) made while the
         previous one's table copy is still pending on its stream waits on the host for that copy; otherwise the call only enqueues.
         Returns dict of flat device tensors in pair order: overlap (n) f32, yaw (n) i32 [, logit (n), corr (n, feat_w)]."""
-        if not self._head_ready:
-            raise _lib.OvnError("head weights not loaded")
-        self._check_feats(feats_pool, "feats_pool")
-        self._check_feats(feats_q, "feats_q")
-        npool = feats_pool.numel() // (self._fw * FEAT_C)
-        nq = feats_q.numel() // (self._fw * FEAT_C)
+        self._require_head()
+        npool, nq = self._check_feats(feats_pool, "feats_pool"), self._check_feats(feats_q, "feats_q")
         offs, q = segment_table(seg_offsets, query_idx, nq)
         n = int(offs[-1])
         ci = self._idx(cand_idx, n, npool, "candidate index")
         if (spec_pool is None) != (spec_q is None):
             raise _lib.OvnError("spec_pool and spec_q must be given together")
         if spec_pool is not None:
-            if not self.has_spectrum:
-                raise _lib.OvnError("spectra exist for 360-column feature volumes only (this leg produces %d)" % self._fw)
-            for t, what, m in ((spec_pool, "spec_pool", npool), (spec_q, "spec_q", nq)):
-                if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous():
-                    raise _lib.OvnError("%s must be a contiguous float32 tensor on %s" % (what, self.device))
-                if t.numel() != m * FEAT_C * self.SPEC_W:
-                    raise _lib.OvnError("%s must hold one 128x368 spectrum per feature volume" % what)
-        if dcache_pool is not None:
-            if dcache_pool.device != self.device or dcache_pool.dtype != torch.float32 or not dcache_pool.is_contiguous():
-                raise _lib.OvnError("dcache_pool must be a contiguous float32 tensor on %s" % self.device)
-            if dcache_pool.numel() != npool * self.DELTA_CACHE_ELEMS:
-                raise _lib.OvnError("dcache_pool must hold one Delta cache row per pool volume")
-        overlap = torch.empty(n, dtype=torch.float32, device=self.device)
-        yaw = torch.empty(n, dtype=torch.int32, device=self.device)
-        logit = torch.empty(n, dtype=torch.float32, device=self.device) if want_logit else None
-        corr = torch.empty((n, self._fw), dtype=torch.float32, device=self.device) if want_corr else None
-        with self._dev():
-            _lib.check(self.lib.ovn_heads_segments(
-                self._h, _ptr(feats_pool), _ptr(spec_pool), _ptr(dcache_pool), _ptr(ci), _ptr(feats_q), _ptr(spec_q),
-                q.ctypes.data_as(C.POINTER(C.c_int32)), offs.ctypes.data_as(C.POINTER(C.c_int64)), len(q), n, _ptr(overlap),
-                _ptr(yaw), _ptr(logit), _ptr(corr), self._stream()), "ovn_heads_segments")
-        out = {"overlap": overlap, "yaw": yaw}
-        if want_logit:
-            out["logit"] = logit
-        if want_corr:
-            out["corr"] = corr
-        return out
+            self._require_spectrum()
+            self._check(spec_pool, "spec_pool", numel=npool * FEAT_C * self.SPEC_W)     # one 128x368 spectrum per feature volume
+            self._check(spec_q, "spec_q", numel=nq * FEAT_C * self.SPEC_W)
+        self._check(dcache_pool, "dcache_pool", numel=npool * self.DELTA_CACHE_ELEMS, optional=True)     # one row per pool volume
+        overlap, yaw, logit, corr = self._heads_outputs(n, want_logit, want_corr)
+        self._call("ovn_heads_segments", _ptr(feats_pool), _ptr(spec_pool), _ptr(dcache_pool), _ptr(ci), _ptr(feats_q), _ptr(spec_q),
+                   q.ctypes.data_as(C.POINTER(C.c_int32)), offs.ctypes.data_as(C.POINTER(C.c_int64)), len(q), n, _ptr(overlap),
+                   _ptr(yaw), _ptr(logit), _ptr(corr), self._stream())
+        return self._heads_result(overlap, yaw, logit, corr)
 
     def corr_head(self, feats_l: torch.Tensor, feats_r: torch.Tensor, lidx=None, ridx=None, n: Optional[int] = None,
                   want_corr: bool = False):
-        self._check_feats(feats_l, "feats_l")
-        self._check_feats(feats_r, "feats_r")
-        li, ri, n = self._pairs(feats_l.numel() // (self._fw * FEAT_C), feats_r.numel() // (self._fw * FEAT_C), lidx, ridx, n)
+        li, ri, n = self._pairs(self._check_feats(feats_l, "feats_l"), self._check_feats(feats_r, "feats_r"), lidx, ridx, n)
         yaw = torch.empty(n, dtype=torch.int32, device=self.device)
         corr = torch.empty((n, self._fw), dtype=torch.float32, device=self.device) if want_corr else None
-        with self._dev():
-            _lib.check(self.lib.ovn_corr_head(self._h, _ptr(feats_l), _ptr(li), _ptr(feats_r), _ptr(ri), n, _ptr(yaw),
-                                              _ptr(corr), self._stream()), "ovn_corr_head")
+        self._call("ovn_corr_head", _ptr(feats_l), _ptr(li), _ptr(feats_r), _ptr(ri), n, _ptr(yaw), _ptr(corr), self._stream())
         return {"yaw": yaw, "corr": corr} if want_corr else {"yaw": yaw}
 
     # -- fitting the Delta head on frozen legs ---------------------------------------------------------
@@ -339,7 +365,7 @@ class OvnEngine:
     def head_param_sizes(self) -> List[int]:
         """Elements of the eight head tensors (HEAD_PARAMS order) for this engine's conv1size and feature width."""
         sizes = (C.c_int64 * 8)()
-        _lib.check(self.lib.ovn_head_param_sizes(self._h, sizes), "ovn_head_param_sizes")
+        self._call("ovn_head_param_sizes", sizes)
         return [int(v) for v in sizes]
 
     def head_param_shapes(self) -> List[Tuple[int, ...]]:
@@ -357,9 +383,29 @@ class OvnEngine:
             if t.device != self.device or t.dtype != torch.float32 or t.numel() != size:
                 raise _lib.OvnError("head tensors must be float32 on %s with %s elements" % (self.device, self.head_param_sizes()))
             ts.append(t.contiguous())
-        with self._dev():
-            _lib.check(self.lib.ovn_set_head_weights(self._h, *[_ptr(t) for t in ts], self._stream()), "ovn_set_head_weights")
+        self._call("ovn_set_head_weights", *[_ptr(t) for t in ts], self._stream())
         self._head_ready = True
+
+    def _grad_pairs(self, feats_l, feats_r, targets, lidx, ridx):
+        """The arguments the two gradient calls share: (targets (n) f32 on the device, lidx, ridx, n >= 1)."""
+        nl, nr = self._check_feats(feats_l, "feats_l"), self._check_feats(feats_r, "feats_r")
+        if not isinstance(targets, torch.Tensor):
+            targets = torch.from_numpy(np.ascontiguousarray(targets, np.float32))
+        t = targets.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+        li, ri, n = self._pairs(nl, nr, lidx, ridx, t.numel() if lidx is None else None)
+        if n < 1 or t.numel() != n:
+            raise _lib.OvnError("%d targets for %d pairs (at least one pair)" % (t.numel(), n))
+        return t, li, ri, n
+
+    def _head_grad_views(self, flat: torch.Tensor, sizes: List[int]) -> Dict[str, Dict[str, torch.Tensor]]:
+        """layer name -> {'kernel', 'bias'}: the eight head gradients in their Keras shapes, views of `flat`."""
+        grads: Dict[str, Dict[str, torch.Tensor]] = {}
+        off = 0
+        for name, size, shape in zip(self.HEAD_PARAMS, sizes, self.head_param_shapes()):
+            layer, kind = name.split("/")
+            grads.setdefault(layer, {})[kind] = flat[off:off + size].view(shape)
+            off += size
+        return grads
 
     def delta_head_grad(self, feats_l: torch.Tensor, feats_r: torch.Tensor, targets, lidx=None, ridx=None, loss: str = "sigmoid",
                         scale: float = 1.0, want_activations: bool = False):
@@ -367,22 +413,12 @@ class OvnEngine:
         (`ovn_delta_head_grad`; pairs as in `heads`: lidx None -> p, ridx None -> 0).  loss: 'sigmoid' (the reference's
         my_sigmoid_loss) or 'mse'.  Returns dict: grads (layer name -> {'kernel', 'bias'} device tensors in Keras shapes, views of
         the one buffer 'flat'), loss (1,), overlap (n) [, o2 (n, G, G, 128), o3 (n, G - 2, G - 2, 256)]."""
-        if not self._head_ready:
-            raise _lib.OvnError("head weights not loaded")
+        self._require_head()
         if loss not in self._LOSSES:
             raise ValueError("loss must be one of %s, got %r" % (sorted(self._LOSSES), loss))
         if not np.isfinite(float(scale)):
             raise ValueError("scale must be finite")
-        self._check_feats(feats_l, "feats_l")
-        self._check_feats(feats_r, "feats_r")
-        nl = feats_l.numel() // (self._fw * FEAT_C)
-        nr = feats_r.numel() // (self._fw * FEAT_C)
-        if not isinstance(targets, torch.Tensor):
-            targets = torch.from_numpy(np.ascontiguousarray(targets, np.float32))
-        t = targets.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
-        li, ri, n = self._pairs(nl, nr, lidx, ridx, t.numel() if lidx is None else None)
-        if n < 1 or t.numel() != n:
-            raise _lib.OvnError("%d targets for %d pairs (at least one pair)" % (t.numel(), n))
+        t, li, ri, n = self._grad_pairs(feats_l, feats_r, targets, lidx, ridx)
         sizes = self.head_param_sizes()
         flat = torch.empty(sum(sizes), dtype=torch.float32, device=self.device)
         lossv = torch.empty(1, dtype=torch.float32, device=self.device)
@@ -390,17 +426,9 @@ class OvnEngine:
         g = self._fw // self.conv1size
         o2 = torch.empty((n, g, g, 128), dtype=torch.float32, device=self.device) if want_activations else None
         o3 = torch.empty((n, g - 2, g - 2, 256), dtype=torch.float32, device=self.device) if want_activations else None
-        with self._dev():
-            _lib.check(self.lib.ovn_delta_head_grad(self._h, _ptr(feats_l), _ptr(li), _ptr(feats_r), _ptr(ri), n, _ptr(t),
-                                                    self._LOSSES[loss], float(scale), _ptr(flat), _ptr(lossv), _ptr(overlap),
-                                                    _ptr(o2), _ptr(o3), self._stream()), "ovn_delta_head_grad")
-        grads: Dict[str, Dict[str, torch.Tensor]] = {}
-        off = 0
-        for name, size, shape in zip(self.HEAD_PARAMS, sizes, self.head_param_shapes()):
-            layer, kind = name.split("/")
-            grads.setdefault(layer, {})[kind] = flat[off:off + size].view(shape)
-            off += size
-        out = {"grads": grads, "flat": flat, "loss": lossv, "overlap": overlap}
+        self._call("ovn_delta_head_grad", _ptr(feats_l), _ptr(li), _ptr(feats_r), _ptr(ri), n, _ptr(t), self._LOSSES[loss], float(scale),
+                   _ptr(flat), _ptr(lossv), _ptr(overlap), _ptr(o2), _ptr(o3), self._stream())
+        out = {"grads": self._head_grad_views(flat, sizes), "flat": flat, "loss": lossv, "overlap": overlap}
         if want_activations:
             out["o2"], out["o3"] = o2, o3
         return out
@@ -417,23 +445,13 @@ class OvnEngine:
         corr (n, W): the correlation logits z, always un-normalised, whatever `set_corr_normalization` holds (want_corr=False leaves
         them out; a call without a yaw part then runs no correlation at all) [, grads, flat as `delta_head_grad` returns them for
         scale = overlap_scale]."""
-        if not self._head_ready:
-            raise _lib.OvnError("head weights not loaded")
+        self._require_head()
         if loss not in self._LOSSES:
             raise ValueError("loss must be one of %s, got %r" % (sorted(self._LOSSES), loss))
         for name, v in (("overlap_scale", overlap_scale), ("yaw_scale", yaw_scale), ("min_overlap_for_angle", min_overlap_for_angle)):
             if not np.isfinite(float(v)):
                 raise ValueError("%s must be finite" % name)
-        self._check_feats(feats_l, "feats_l")
-        self._check_feats(feats_r, "feats_r")
-        nl = feats_l.numel() // (self._fw * FEAT_C)
-        nr = feats_r.numel() // (self._fw * FEAT_C)
-        if not isinstance(targets, torch.Tensor):
-            targets = torch.from_numpy(np.ascontiguousarray(targets, np.float32))
-        t = targets.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
-        li, ri, n = self._pairs(nl, nr, lidx, ridx, t.numel() if lidx is None else None)
-        if n < 1 or t.numel() != n:
-            raise _lib.OvnError("%d targets for %d pairs (at least one pair)" % (t.numel(), n))
+        t, li, ri, n = self._grad_pairs(feats_l, feats_r, targets, lidx, ridx)
         yb = None
         if yaw_bins is not None:
             if not isinstance(yaw_bins, torch.Tensor):
@@ -448,22 +466,14 @@ class OvnEngine:
         corr = torch.empty((n, self._fw), dtype=torch.float32, device=self.device) if want_corr else None
         sizes = self.head_param_sizes()
         flat = torch.empty(sum(sizes), dtype=torch.float32, device=self.device) if want_head_grads else None
-        with self._dev():
-            _lib.check(self.lib.ovn_heads_feature_grad(self._h, _ptr(feats_l), _ptr(li), _ptr(feats_r), _ptr(ri), n, _ptr(t), _ptr(yb),
-                                                       self._LOSSES[loss], float(overlap_scale), float(yaw_scale),
-                                                       float(min_overlap_for_angle), _ptr(dl), _ptr(dr), _ptr(flat), _ptr(lossv),
-                                                       _ptr(overlap), _ptr(corr), self._stream()), "ovn_heads_feature_grad")
+        self._call("ovn_heads_feature_grad", _ptr(feats_l), _ptr(li), _ptr(feats_r), _ptr(ri), n, _ptr(t), _ptr(yb), self._LOSSES[loss],
+                   float(overlap_scale), float(yaw_scale), float(min_overlap_for_angle), _ptr(dl), _ptr(dr), _ptr(flat), _ptr(lossv),
+                   _ptr(overlap), _ptr(corr), self._stream())
         out = {"dfeat_l": dl, "dfeat_r": dr, "loss": lossv, "loss_overlap": lossv[0], "loss_yaw": lossv[1], "overlap": overlap}
         if want_corr:
             out["corr"] = corr
         if want_head_grads:
-            grads: Dict[str, Dict[str, torch.Tensor]] = {}
-            off = 0
-            for name, size, shape in zip(self.HEAD_PARAMS, sizes, self.head_param_shapes()):
-                layer, kind = name.split("/")
-                grads.setdefault(layer, {})[kind] = flat[off:off + size].view(shape)
-                off += size
-            out["grads"], out["flat"] = grads, flat
+            out["grads"], out["flat"] = self._head_grad_views(flat, sizes), flat
         return out
 
     # -- training the legs ---------------------------------------------------------------------------------
@@ -486,9 +496,9 @@ class OvnEngine:
         self._require_leg()
         shapes = [s for _, k in self._leg_specs() for s in (k, (k[3],))]
         nl = C.c_int(0)
-        _lib.check(self.lib.ovn_leg_layer_count(self._h, C.byref(nl)), "ovn_leg_layer_count")
+        self._call("ovn_leg_layer_count", C.byref(nl))
         sizes = (C.c_int64 * (2 * nl.value))()
-        _lib.check(self.lib.ovn_leg_param_sizes(self._h, sizes), "ovn_leg_param_sizes")
+        self._call("ovn_leg_param_sizes", sizes)
         if [int(v) for v in sizes] != [int(np.prod(s)) for s in shapes]:
             raise _lib.OvnError("the library holds leg tensors of %s elements, the layer table says %s"
                                 % ([int(v) for v in sizes], shapes))
@@ -502,14 +512,13 @@ class OvnEngine:
             h, w = (h - l.kh) // l.sh + 1, (w - l.kw) // l.sw + 1
             shapes.append((h, w, l.cout))
         sizes = (C.c_int64 * len(shapes))()
-        _lib.check(self.lib.ovn_leg_activation_sizes(self._h, sizes), "ovn_leg_activation_sizes")
+        self._call("ovn_leg_activation_sizes", sizes)
         if [int(v) for v in sizes] != [a * b * c for a, b, c in shapes]:
             raise _lib.OvnError("the library's leg activations %s do not match the layer table %s" % ([int(v) for v in sizes], shapes))
         return shapes
 
     def _check_images(self, images: torch.Tensor) -> int:
-        if images.device != self.device or images.dtype != torch.float32 or not images.is_contiguous():
-            raise _lib.OvnError("leg input must be a contiguous float32 tensor on %s" % self.device)
+        self._check(images, "leg input")
         if images.dim() != 4 or tuple(images.shape[1:]) != (self.in_h, self.in_w, self.in_c) or images.shape[0] < 1:
             raise _lib.OvnError("leg input shape %s, expected (n >= 1,%d,%d,%d)" % (tuple(images.shape), self.in_h, self.in_w, self.in_c))
         return int(images.shape[0])
@@ -522,8 +531,7 @@ class OvnEngine:
         n = self._check_images(images)
         shapes = self.leg_activation_shapes()
         flat = torch.empty(n * sum(a * b * c for a, b, c in shapes), dtype=torch.float32, device=self.device)
-        with self._dev():
-            _lib.check(self.lib.ovn_leg_forward_train(self._h, _ptr(images), n, _ptr(flat), self._stream()), "ovn_leg_forward_train")
+        self._call("ovn_leg_forward_train", _ptr(images), n, _ptr(flat), self._stream())
         acts, off = [], 0
         for a, b, c in shapes:
             acts.append(flat[off:off + n * a * b * c].view(n, a, b, c))
@@ -541,21 +549,17 @@ class OvnEngine:
             raise _lib.OvnError("leg_backward takes the %d activations of leg_forward_train" % len(shapes))
         base = acts[0].data_ptr()
         off = 0
-        for t, (a, b, c) in zip(acts, shapes):
-            if (t.device != self.device or t.dtype != torch.float32 or tuple(t.shape) != (n, a, b, c) or not t.is_contiguous()
-                    or t.data_ptr() != base + 4 * off):
+        for i, (t, (a, b, c)) in enumerate(zip(acts, shapes)):
+            self._check(t, "leg_backward: acts[%d]" % i, shape=(n, a, b, c))
+            if t.data_ptr() != base + 4 * off:
                 raise _lib.OvnError("leg_backward: acts must be the list leg_forward_train returned for these %d scans" % n)
             off += n * a * b * c
-        if (dfeat.device != self.device or dfeat.dtype != torch.float32 or not dfeat.is_contiguous()
-                or dfeat.numel() != n * self.feat_w * FEAT_C):
-            raise _lib.OvnError("dfeat must be a contiguous float32 tensor of %d feature volumes on %s" % (n, self.device))
+        self._check(dfeat, "dfeat", numel=n * self.feat_w * FEAT_C)       # n feature volumes
         if int(slice_scans) < 0:
             raise ValueError("slice_scans must be >= 0")
         pshapes = self.leg_param_shapes()
         flat = torch.empty(sum(int(np.prod(s)) for s in pshapes), dtype=torch.float32, device=self.device)
-        with self._dev():
-            _lib.check(self.lib.ovn_leg_backward(self._h, _ptr(images), C.c_void_p(base), n, _ptr(dfeat), _ptr(flat), int(slice_scans),
-                                                 self._stream()), "ovn_leg_backward")
+        self._call("ovn_leg_backward", _ptr(images), C.c_void_p(base), n, _ptr(dfeat), _ptr(flat), int(slice_scans), self._stream())
         out: Dict[str, torch.Tensor] = {}
         off = 0
         for name, shape in zip(self.leg_param_names(), pshapes):
@@ -575,20 +579,18 @@ class OvnEngine:
             if len(params) != len(names):
                 raise _lib.OvnError("set_leg_weights takes the %d leg tensors" % len(names))
             params = dict(zip(names, params))
-        with self._dev():
-            for li, (layer, _) in enumerate(self._leg_specs()):
-                k, b = params.get(layer + "/kernel"), params.get(layer + "/bias")
-                if k is None and b is None:
-                    continue
-                if k is None or b is None:
-                    raise _lib.OvnError("set_leg_weights: layer %s needs its kernel and its bias" % layer)
-                for t, shape in ((k, shapes[2 * li]), (b, shapes[2 * li + 1])):
-                    if t.device != self.device or t.dtype != torch.float32 or t.numel() != int(np.prod(shape)):
-                        raise _lib.OvnError("set_leg_weights: %s tensors must be float32 on %s with shapes %s, %s"
-                                            % (layer, self.device, shapes[2 * li], shapes[2 * li + 1]))
-                k, b = k.contiguous(), b.contiguous()
-                _lib.check(self.lib.ovn_set_leg_layer_weights(self._h, li, _ptr(k), _ptr(b), self._stream()),
-                           "ovn_set_leg_layer_weights(%s)" % layer)
+        for li, (layer, _) in enumerate(self._leg_specs()):
+            k, b = params.get(layer + "/kernel"), params.get(layer + "/bias")
+            if k is None and b is None:
+                continue
+            if k is None or b is None:
+                raise _lib.OvnError("set_leg_weights: layer %s needs its kernel and its bias" % layer)
+            for t, shape in ((k, shapes[2 * li]), (b, shapes[2 * li + 1])):
+                if t.device != self.device or t.dtype != torch.float32 or t.numel() != int(np.prod(shape)):
+                    raise _lib.OvnError("set_leg_weights: %s tensors must be float32 on %s with shapes %s, %s"
+                                        % (layer, self.device, shapes[2 * li], shapes[2 * li + 1]))
+            k, b = k.contiguous(), b.contiguous()
+            self._call("ovn_set_leg_layer_weights", li, _ptr(k), _ptr(b), self._stream(), what="ovn_set_leg_layer_weights(%s)" % layer)
 
     # -- data-parallel training ------------------------------------------------------------------------------
     GRAD_REDUCE_MAX_WORLD = 64     # OVN_GRAD_REDUCE_MAX_WORLD of include/ovn_hip.h
@@ -601,8 +603,7 @@ class OvnEngine:
         read).  params / accum: flat float32 tensors of count <= stride elements, updated IN PLACE with
         g = float32(sum_r w_r G[r] in fp64, rank order); a += g g; p -= lr g / (sqrt(a) + eps); both None: reduce only (the first
         `count` elements of the rows, default all).  Returns the reduced gradient (count) when want_grad or when only reducing, else None."""
-        if grads.device != self.device or grads.dtype != torch.float32 or grads.dim() != 2 or not grads.is_contiguous():
-            raise _lib.OvnError("grads must be a contiguous (world, stride) float32 tensor on %s" % self.device)
+        self._check(grads, "grads (world, stride)", ndim=2)
         world, stride = int(grads.shape[0]), int(grads.shape[1])
         w = np.ascontiguousarray(np.asarray(rank_weights, np.float64).reshape(-1))
         if len(w) != world or not 1 <= world <= self.GRAD_REDUCE_MAX_WORLD:
@@ -614,17 +615,14 @@ class OvnEngine:
             if not 1 <= count <= stride:
                 raise _lib.OvnError("count %d for gradient rows of %d" % (count, stride))
         else:
-            for t in (params, accum):
-                if t.device != self.device or t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous():
-                    raise _lib.OvnError("params and accum must be flat contiguous float32 tensors on %s" % self.device)
+            self._check(params, "params", ndim=1)
+            self._check(accum, "accum", ndim=1)
             count = int(params.numel())
             if accum.numel() != count or not 1 <= count <= stride:
                 raise _lib.OvnError("params %d and accum %d elements for gradient rows of %d" % (count, accum.numel(), stride))
         out = torch.empty(count, dtype=torch.float32, device=self.device) if (want_grad or params is None) else None
-        with self._dev():
-            _lib.check(self.lib.ovn_grad_reduce_adagrad(self._h, _ptr(grads), world, stride, w.ctypes.data_as(C.POINTER(C.c_double)), count,
-                                                        _ptr(params), _ptr(accum), float(lr), float(eps), _ptr(out), self._stream()),
-                       "ovn_grad_reduce_adagrad")
+        self._call("ovn_grad_reduce_adagrad", _ptr(grads), world, stride, w.ctypes.data_as(C.POINTER(C.c_double)), count, _ptr(params),
+                   _ptr(accum), float(lr), float(eps), _ptr(out), self._stream())
         return out
 
     def debug_conv(self, layer: int, x: torch.Tensor) -> torch.Tensor:
@@ -633,8 +631,7 @@ class OvnEngine:
         l = W.leg_layers(self.in_c, self._leg_cfg)[layer]
         nb, h, w, _ = x.shape
         out = torch.empty((nb, (h - l.kh) // l.sh + 1, (w - l.kw) // l.sw + 1, l.cout), dtype=torch.float32, device=self.device)
-        with self._dev():
-            _lib.check(self.lib.ovn_debug_conv(self._h, int(layer), _ptr(x.contiguous()), nb, h, w, _ptr(out), self._stream()), "ovn_debug_conv")
+        self._call("ovn_debug_conv", int(layer), _ptr(x.contiguous()), nb, h, w, _ptr(out), self._stream())
         return out
 
     def debug_conv_grad(self, layer: int, x: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, want=("din", "dkernel", "dbias")):
@@ -646,9 +643,8 @@ class OvnEngine:
         if not 0 <= int(layer) < len(specs):
             raise IndexError("no leg layer %r" % (layer,))
         l = specs[int(layer)]
-        for t in (x, out, dout):
-            if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous():
-                raise _lib.OvnError("debug_conv_grad takes contiguous float32 tensors on %s" % self.device)
+        for t, name in ((x, "x"), (out, "out"), (dout, "dout")):
+            self._check(t, "debug_conv_grad: " + name)
         if x.dim() != 4 or x.shape[3] != l.cin or x.shape[0] < 1 or x.shape[1] < l.kh or x.shape[2] < l.kw:
             raise _lib.OvnError("debug_conv_grad: input shape %s for layer %s" % (tuple(x.shape), l.name))
         nb, h, w, _ = (int(v) for v in x.shape)
@@ -662,9 +658,8 @@ class OvnEngine:
             r["dkernel"] = torch.empty((l.kh, l.kw, l.cin, l.cout), dtype=torch.float32, device=self.device)
         if "dbias" in want:
             r["dbias"] = torch.empty(l.cout, dtype=torch.float32, device=self.device)
-        with self._dev():
-            _lib.check(self.lib.ovn_debug_conv_grad(self._h, int(layer), _ptr(x), _ptr(out), _ptr(dout), nb, h, w, _ptr(r.get("din")),
-                                                    _ptr(r.get("dkernel")), _ptr(r.get("dbias")), self._stream()), "ovn_debug_conv_grad")
+        self._call("ovn_debug_conv_grad", int(layer), _ptr(x), _ptr(out), _ptr(dout), nb, h, w, _ptr(r.get("din")), _ptr(r.get("dkernel")),
+                   _ptr(r.get("dbias")), self._stream())
         return r
 
     SPEC_W = 368
@@ -678,46 +673,36 @@ class OvnEngine:
     def delta_cache(self, feats: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """feature volumes (n,360,128) -> Delta cache rows (n, 49216): the candidate-side half of the Delta head's preparation
         (packed words, TT + b2, value range), cached next to the volume like its spectrum."""
-        if not self._head_ready:
-            raise _lib.OvnError("head weights not loaded")
+        self._require_head()
         if not self.has_delta_cache:
             raise _lib.OvnError("the Delta cache exists for conv1NetworkHead_conv1size=15 and 360-column feature volumes only")
-        self._check_feats(feats, "feats")
-        n = feats.numel() // (self._fw * FEAT_C)
+        n = self._check_feats(feats, "feats")
         if out is None:
             out = torch.empty((n, self.DELTA_CACHE_ELEMS), dtype=torch.float32, device=self.device)
-        with self._dev():
-            _lib.check(self.lib.ovn_delta_cache(self._h, _ptr(feats), n, _ptr(out), self._stream()), "ovn_delta_cache")
+        self._call("ovn_delta_cache", _ptr(feats), n, _ptr(out), self._stream())
         return out
 
     def spectrum(self, feats: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """feature volumes (n,360,128) -> cached spectra (n,128,368) for the spectral correlation head (360 columns only)."""
-        if not self.has_spectrum:
-            raise _lib.OvnError("spectra exist for 360-column feature volumes only (this leg produces %d)" % self._fw)
-        self._check_feats(feats, "feats")
-        n = feats.numel() // (FEAT_W * FEAT_C)
+        self._require_spectrum()
+        n = self._check_feats(feats, "feats")
         if out is None:
             out = torch.empty((n, FEAT_C, self.SPEC_W), dtype=torch.float32, device=self.device)
-        with self._dev():
-            _lib.check(self.lib.ovn_spectrum(self._h, _ptr(feats), n, _ptr(out), self._stream()), "ovn_spectrum")
+        self._call("ovn_spectrum", _ptr(feats), n, _ptr(out), self._stream())
         return out
 
     def corr_head_spectral(self, spec_l: torch.Tensor, spec_r: torch.Tensor, lidx=None, ridx=None,
                            n: Optional[int] = None, want_corr: bool = False):
         """Correlation head on cached spectra: dict(yaw (n) i32 [, corr (n,360)]); 360-column feature volumes only."""
-        if not self.has_spectrum:
-            raise _lib.OvnError("spectra exist for 360-column feature volumes only (this leg produces %d)" % self._fw)
+        self._require_spectrum()
         for t, what in ((spec_l, "spec_l"), (spec_r, "spec_r")):
-            if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous():
-                raise _lib.OvnError("%s must be a contiguous float32 tensor on %s" % (what, self.device))
+            self._check(t, what)
             if t.numel() % (FEAT_C * self.SPEC_W) != 0:
                 raise _lib.OvnError("%s is not a stack of 128x368 spectra" % what)
         li, ri, n = self._pairs(spec_l.numel() // (FEAT_C * self.SPEC_W), spec_r.numel() // (FEAT_C * self.SPEC_W), lidx, ridx, n)
         yaw = torch.empty(n, dtype=torch.int32, device=self.device)
         corr = torch.empty((n, FEAT_W), dtype=torch.float32, device=self.device) if want_corr else None
-        with self._dev():
-            _lib.check(self.lib.ovn_corr_head_spectral(self._h, _ptr(spec_l), _ptr(li), _ptr(spec_r), _ptr(ri), n,
-                                                       _ptr(yaw), _ptr(corr), self._stream()), "ovn_corr_head_spectral")
+        self._call("ovn_corr_head_spectral", _ptr(spec_l), _ptr(li), _ptr(spec_r), _ptr(ri), n, _ptr(yaw), _ptr(corr), self._stream())
         return {"yaw": yaw, "corr": corr} if want_corr else {"yaw": yaw}
 
     # -- ground-truth labels -------------------------------------------------------------------------
@@ -728,33 +713,24 @@ class OvnEngine:
         """Float64 range projection of scans moved by inv_cur_pose . ref_poses[s] (com_overlap_yaw.py:37-40):
         (n, H, W) f32 device tensor, -1 = empty.  points (total,4) f32, offsets (n+1) i64, poses float64 device tensors."""
         n = int(offsets.numel()) - 1
-        for t, what, dt in ((points, "points", torch.float32), (offsets, "offsets", torch.int64),
-                            (ref_poses, "ref_poses", torch.float64), (inv_cur_pose, "inv_cur_pose", torch.float64)):
-            if t is not None and (t.device != self.device or t.dtype != dt or not t.is_contiguous()):
-                raise _lib.OvnError("%s must be a contiguous %s tensor on %s" % (what, dt, self.device))
-        if ref_poses is not None and ref_poses.numel() != 16 * n:
-            raise _lib.OvnError("ref_poses must hold %d 4x4 matrices" % n)
-        if inv_cur_pose is not None and inv_cur_pose.numel() != 16:
-            raise _lib.OvnError("inv_cur_pose must be one 4x4 matrix")
+        self._check(points, "points")
+        self._check(offsets, "offsets", torch.int64)
+        self._check(ref_poses, "ref_poses (%d 4x4 matrices)" % n, torch.float64, numel=16 * n, optional=True)
+        self._check(inv_cur_pose, "inv_cur_pose (one 4x4 matrix)", torch.float64, numel=16, optional=True)
         out = torch.empty((n, proj_h, proj_w), dtype=torch.float32, device=self.device)
-        with self._dev():
-            _lib.check(self.lib.ovn_gt_range_images(self._h, _ptr(points), _ptr(offsets), n, int(max_points), _ptr(ref_poses),
-                                                    _ptr(inv_cur_pose), proj_h, proj_w, float(fov_up), float(fov_down),
-                                                    float(max_range), _ptr(out), self._stream()), "ovn_gt_range_images")
+        self._call("ovn_gt_range_images", _ptr(points), _ptr(offsets), n, int(max_points), _ptr(ref_poses), _ptr(inv_cur_pose), proj_h,
+                   proj_w, float(fov_up), float(fov_down), float(max_range), _ptr(out), self._stream())
         return out
 
     def gt_overlap_counts(self, ref_ranges: torch.Tensor, cur_range: torch.Tensor) -> torch.Tensor:
         """(n+1) int32: per reference scan the pixels with |ref - cur| < 1 (ref > 0); last entry = #{cur > 0}."""
         n, h, w = ref_ranges.shape
-        for t, what in ((ref_ranges, "ref_ranges"), (cur_range, "cur_range")):
-            if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous():
-                raise _lib.OvnError("%s must be a contiguous float32 tensor on %s" % (what, self.device))
+        self._check(ref_ranges, "ref_ranges")
+        self._check(cur_range, "cur_range")
         if tuple(cur_range.shape[-2:]) != (h, w) or cur_range.numel() != h * w:
             raise _lib.OvnError("cur_range must be one %dx%d image" % (h, w))
         counts = torch.empty(n + 1, dtype=torch.int32, device=self.device)
-        with self._dev():
-            _lib.check(self.lib.ovn_gt_overlap_counts(self._h, _ptr(ref_ranges), _ptr(cur_range), n, h, w, _ptr(counts),
-                                                      self._stream()), "ovn_gt_overlap_counts")
+        self._call("ovn_gt_overlap_counts", _ptr(ref_ranges), _ptr(cur_range), n, h, w, _ptr(counts), self._stream())
         return counts
 
     def gt_pair_counts(self, points: torch.Tensor, offsets: torch.Tensor, poses: torch.Tensor, inv_poses: torch.Tensor,
@@ -766,27 +742,30 @@ class OvnEngine:
         and inv_poses (n,4,4) f64, cur_ranges (n,H,W) f32 = `gt_range_images` without poses (rows of scans that are no frame are
         never read), frame_idx / ref_idx int32 device lists or None = all scans in order."""
         n = int(offsets.numel()) - 1
-        for t, what, dt in ((points, "points", torch.float32), (offsets, "offsets", torch.int64), (poses, "poses", torch.float64),
-                            (inv_poses, "inv_poses", torch.float64), (cur_ranges, "cur_ranges", torch.float32),
-                            (frame_idx, "frame_idx", torch.int32), (ref_idx, "ref_idx", torch.int32)):
-            if t is not None and (t.device != self.device or t.dtype != dt or not t.is_contiguous()):
-                raise _lib.OvnError("%s must be a contiguous %s tensor on %s" % (what, dt, self.device))
-        if poses.numel() != 16 * n or inv_poses.numel() != 16 * n:
-            raise _lib.OvnError("poses and inv_poses must hold %d 4x4 matrices each" % n)
-        if cur_ranges.dim() != 3 or cur_ranges.shape[0] != n:
+        self._check(points, "points")
+        self._check(offsets, "offsets", torch.int64)
+        self._check(poses, "poses (%d 4x4 matrices)" % n, torch.float64, numel=16 * n)
+        self._check(inv_poses, "inv_poses (%d 4x4 matrices)" % n, torch.float64, numel=16 * n)
+        self._check(cur_ranges, "cur_ranges", ndim=3)
+        self._check(frame_idx, "frame_idx", torch.int32, optional=True)
+        self._check(ref_idx, "ref_idx", torch.int32, optional=True)
+        if cur_ranges.shape[0] != n:
             raise _lib.OvnError("cur_ranges must be (%d, H, W), one own range image per scan" % n)
         h, w = int(cur_ranges.shape[1]), int(cur_ranges.shape[2])
         nf = n if frame_idx is None else int(frame_idx.numel())
         nr = n if ref_idx is None else int(ref_idx.numel())
         counts = torch.empty((nf, nr), dtype=torch.int32, device=self.device)
-        with self._dev():
-            _lib.check(self.lib.ovn_gt_pair_counts(self._h, _ptr(points), _ptr(offsets), n, _ptr(poses), _ptr(inv_poses),
-                                                   _ptr(cur_ranges), _ptr(frame_idx), nf, _ptr(ref_idx), nr, h, w, float(fov_up),
-                                                   float(fov_down), float(max_range), _ptr(counts), self._stream()),
-                       "ovn_gt_pair_counts")
+        self._call("ovn_gt_pair_counts", _ptr(points), _ptr(offsets), n, _ptr(poses), _ptr(inv_poses), _ptr(cur_ranges), _ptr(frame_idx),
+                   nf, _ptr(ref_idx), nr, h, w, float(fov_up), float(fov_down), float(max_range), _ptr(counts), self._stream())
         return counts
 
     # -- loop-closure decision -----------------------------------------------------------------------
+    def _check_scores(self, n: int, overlap: torch.Tensor, yaw: Optional[torch.Tensor], ids: Optional[torch.Tensor]) -> None:
+        """The scores of a sweep as the decision calls take them: overlap f32, yaw and ids int32 or None, n elements each."""
+        self._check(overlap, "overlap", torch.float32, numel=n)
+        self._check(yaw, "yaw", torch.int32, numel=n, optional=True)
+        self._check(ids, "ids", torch.int32, numel=n, optional=True)
+
     def best_match(self, overlap: torch.Tensor, yaw: Optional[torch.Tensor] = None, threshold: float = 0.3,
                    ids: Optional[torch.Tensor] = None, index_offset: int = 0, host: bool = False) -> torch.Tensor:
         """On-device `argmax overlap, > threshold` of demo3 (demo3_lcd.py:117-120).  Returns a 4 x int32 device
@@ -795,11 +774,7 @@ class OvnEngine:
         caller reads the decision without a device-to-host copy (one blit kernel and its hand-off less per query); the record comes back
         as a NumPy int32 array."""
         n = int(overlap.numel())
-        for t, what, dt in ((overlap, "overlap", torch.float32), (yaw, "yaw", torch.int32), (ids, "ids", torch.int32)):
-            if t is None:
-                continue
-            if t.device != self.device or t.dtype != dt or not t.is_contiguous() or t.numel() != n:
-                raise _lib.OvnError("%s must be a contiguous %s tensor of %d elements on %s" % (what, dt, n, self.device))
+        self._check_scores(n, overlap, yaw, ids)
         if host:
             if getattr(self, "_match_host", None) is None:
                 self._match_host = torch.empty(4, dtype=torch.int32).pin_memory()
@@ -808,19 +783,17 @@ class OvnEngine:
             view[3] = _MATCH_PENDING                                      # the kernel's one 16-byte store replaces it (0 or 1)
         else:
             out = torch.empty(4, dtype=torch.int32, device=self.device)
-        with self._dev():
-            _lib.check(self.lib.ovn_best_match(self._h, _ptr(overlap), _ptr(yaw), _ptr(ids), n, float(threshold),
-                                               int(index_offset), _ptr(out), self._stream()), "ovn_best_match")
-            if host:
-                # poll the record instead of waiting for the stream: the wake-up of a stream wait costs more than the kernel
-                spins = 0
-                while view[3] == _MATCH_PENDING:
-                    spins += 1
-                    if spins > 200000:                                    # (~20 ms) something is wrong: let the stream say what
-                        torch.cuda.current_stream(self.device).synchronize()
-                        if view[3] == _MATCH_PENDING:
-                            raise _lib.OvnError("best_match(host=True): the decision record never arrived")
-                return view.copy()            # (a NumPy record: `decode_match` takes it as it is)
+        self._call("ovn_best_match", _ptr(overlap), _ptr(yaw), _ptr(ids), n, float(threshold), int(index_offset), _ptr(out), self._stream())
+        if host:
+            # poll the record instead of waiting for the stream: the wake-up of a stream wait costs more than the kernel
+            spins = 0
+            while view[3] == _MATCH_PENDING:
+                spins += 1
+                if spins > 200000:                                    # (~20 ms) something is wrong: let the stream say what
+                    torch.cuda.current_stream(self.device).synchronize()
+                    if view[3] == _MATCH_PENDING:
+                        raise _lib.OvnError("best_match(host=True): the decision record never arrived")
+            return view.copy()            # (a NumPy record: `decode_match` takes it as it is)
         return out
 
     def top_k(self, overlap: torch.Tensor, yaw: Optional[torch.Tensor] = None, k: int = 5, threshold: float = 0.3,
@@ -830,19 +803,13 @@ class OvnEngine:
         {-1, 0, 0, 0} past the last non-NaN score.  k = 1 gives `best_match`'s record bit for bit.  Decode with `decode_top_k`.
         `out` (optional): a contiguous int32 device tensor of k x 4 elements, 16-byte aligned (the library checks)."""
         n = int(overlap.numel())
-        for t, what, dt in ((overlap, "overlap", torch.float32), (yaw, "yaw", torch.int32), (ids, "ids", torch.int32)):
-            if t is None:
-                continue
-            if t.device != self.device or t.dtype != dt or not t.is_contiguous() or t.numel() != n:
-                raise _lib.OvnError("%s must be a contiguous %s tensor of %d elements on %s" % (what, dt, n, self.device))
+        self._check_scores(n, overlap, yaw, ids)
         k = int(k)
         if out is None:
             out = torch.empty((max(k, 0), 4), dtype=torch.int32, device=self.device)
-        elif out.device != self.device or out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != 4 * k:
-            raise _lib.OvnError("out must be a contiguous int32 tensor of %d elements on %s" % (4 * k, self.device))
-        with self._dev():
-            _lib.check(self.lib.ovn_top_k(self._h, _ptr(overlap), _ptr(yaw), _ptr(ids), n, k, float(threshold), int(index_offset),
-                                          _ptr(out), self._stream()), "ovn_top_k")
+        else:
+            self._check(out, "out", torch.int32, numel=4 * k)
+        self._call("ovn_top_k", _ptr(overlap), _ptr(yaw), _ptr(ids), n, k, float(threshold), int(index_offset), _ptr(out), self._stream())
         return out
 
     def top_k_segments(self, overlap: torch.Tensor, seg_offsets, yaw: Optional[torch.Tensor] = None, k: int = 5,
@@ -854,19 +821,13 @@ class OvnEngine:
         offs, _ = segment_table(seg_offsets, None, None)
         k = check_top_k(k)
         n, B = int(offs[-1]), len(offs) - 1
-        for t, what, dt in ((overlap, "overlap", torch.float32), (yaw, "yaw", torch.int32), (ids, "ids", torch.int32)):
-            if t is None:
-                continue
-            if t.device != self.device or t.dtype != dt or not t.is_contiguous() or t.numel() != n:
-                raise _lib.OvnError("%s must be a contiguous %s tensor of %d elements on %s" % (what, dt, n, self.device))
+        self._check_scores(n, overlap, yaw, ids)
         if out is None:
             out = torch.empty((B, k, 4), dtype=torch.int32, device=self.device)
-        elif out.device != self.device or out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != 4 * k * B:
-            raise _lib.OvnError("out must be a contiguous int32 tensor of %d elements on %s" % (4 * k * B, self.device))
-        with self._dev():
-            _lib.check(self.lib.ovn_top_k_segments(self._h, _ptr(overlap), _ptr(yaw), _ptr(ids),
-                                                   offs.ctypes.data_as(C.POINTER(C.c_int64)), B, k, float(threshold), _ptr(out),
-                                                   self._stream()), "ovn_top_k_segments")
+        else:
+            self._check(out, "out", torch.int32, numel=4 * k * B)
+        self._call("ovn_top_k_segments", _ptr(overlap), _ptr(yaw), _ptr(ids), offs.ctypes.data_as(C.POINTER(C.c_int64)), B, k,
+                   float(threshold), _ptr(out), self._stream())
         return out
 
     # -- preprocessing ------------------------------------------------------------------------------
@@ -886,106 +847,51 @@ class OvnEngine:
         point's proj_idx, which indexes the unfiltered rows as in the reference), stacked_flags is
         (use_depth, use_normals, use_semantic, use_intensity) in the reference's channel order, and every other output is bit
         for bit the one of the call without probs.  n_points: offsets[-1] when the caller knows it (else read from the device)."""
-        if points.device != self.device or points.dtype != torch.float32 or not points.is_contiguous():
-            raise _lib.OvnError("points must be a contiguous float32 tensor on %s" % self.device)
+        self._check(points, "points")
         if offsets.device != self.device or offsets.dtype != torch.int64:
             raise _lib.OvnError("offsets must be an int64 tensor on %s" % self.device)
-        if probs is not None:
-            return self._project_semantic(points, offsets, max_points, proj_h, proj_w, fov_up, fov_down, max_range, want,
-                                          stacked_flags, stacked_out, probs, n_classes, n_points)
-        n = offsets.numel() - 1
-        dev = self.device
-        out = {}
-        mk = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)
-        rng = mk(n, proj_h, proj_w) if "range" in want else None
-        vtx = mk(n, proj_h, proj_w, 4) if "vertex" in want else None
-        itn = mk(n, proj_h, proj_w) if "intensity" in want else None
-        idx = mk(n, proj_h, proj_w, dt=torch.int32) if "idx" in want else None
-        nrm = mk(n, proj_h, proj_w, 3) if "normal" in want else None
-        stk = None
-        ud = un = ui = 0
-        if stacked_flags is not None:
-            ud, un, ui = (int(bool(v)) for v in stacked_flags)
-            if stacked_out is not None:
-                if (stacked_out.device != self.device or stacked_out.dtype != torch.float32 or not stacked_out.is_contiguous()
-                        or tuple(stacked_out.shape) != (n, proj_h, proj_w, ud + 3 * un + ui)):
-                    raise _lib.OvnError("stacked_out must be a contiguous float32 (%d,%d,%d,%d) tensor on %s"
-                                        % (n, proj_h, proj_w, ud + 3 * un + ui, self.device))
-                stk = stacked_out
-            else:
-                stk = mk(n, proj_h, proj_w, ud + 3 * un + ui)
-        with self._dev():
-            _lib.check(self.lib.ovn_project(self._h, _ptr(points), _ptr(offsets), n, int(max_points), proj_h, proj_w,
-                                            float(fov_up), float(fov_down), float(max_range), _ptr(rng), _ptr(vtx),
-                                            _ptr(itn), _ptr(idx), _ptr(nrm), _ptr(stk), ud, un, ui, self._stream()),
-                       "ovn_project")
-        for k, v in (("range", rng), ("vertex", vtx), ("intensity", itn), ("idx", idx), ("normal", nrm), ("stacked", stk)):
-            if v is not None:
-                out[k] = v
-        return out
-
-    def _project_semantic(self, points, offsets, max_points, proj_h, proj_w, fov_up, fov_down, max_range, want, stacked_flags,
-                          stacked_out, probs, n_classes, n_points):
-        n_classes = int(n_classes)
-        if not 1 <= n_classes <= SEMANTIC_CLASSES_MAX:
-            raise _lib.OvnError("n_classes must be in 1..%d, got %d" % (SEMANTIC_CLASSES_MAX, n_classes))
-        total = int(offsets[-1].item()) if n_points is None else int(n_points)
-        if (probs.device != self.device or probs.dtype != torch.float32 or not probs.is_contiguous()
-                or tuple(probs.shape) != (total, n_classes)):
-            raise _lib.OvnError("probs must be a contiguous float32 (%d, %d) tensor on %s (one row per point), got %s %s %s"
-                                % (total, n_classes, self.device, tuple(probs.shape), probs.dtype, probs.device))
-        if probs.numel() == 0:      # no points at all: nothing is read, but the library wants a buffer for a probability output
-            probs = torch.empty((1, n_classes), dtype=torch.float32, device=self.device)
-        n = offsets.numel() - 1
-        dev = self.device
-        mk = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)
-        rng = mk(n, proj_h, proj_w) if "range" in want else None
-        vtx = mk(n, proj_h, proj_w, 4) if "vertex" in want else None
-        itn = mk(n, proj_h, proj_w) if "intensity" in want else None
-        idx = mk(n, proj_h, proj_w, dt=torch.int32) if "idx" in want else None
-        nrm = mk(n, proj_h, proj_w, 3) if "normal" in want else None
-        sem = mk(n, proj_h, proj_w, n_classes) if "semantic" in want else None
-        sid = mk(n, proj_h, proj_w, dt=torch.int32) if "sem_idx" in want else None
-        stk = None
-        ud = un = us = ui = 0
-        if stacked_flags is not None:
-            if len(stacked_flags) != 4:
+        semantic = probs is not None
+        table = _PROJECT_OUTPUTS
+        if semantic:
+            n_classes = int(n_classes)
+            if not 1 <= n_classes <= SEMANTIC_CLASSES_MAX:
+                raise _lib.OvnError("n_classes must be in 1..%d, got %d" % (SEMANTIC_CLASSES_MAX, n_classes))
+            total = int(offsets[-1].item()) if n_points is None else int(n_points)
+            self._check(probs, "probs (one row per point)", shape=(total, n_classes))
+            if probs.numel() == 0:      # no points at all: nothing is read, but the library wants a buffer for a probability output
+                probs = torch.empty((1, n_classes), dtype=torch.float32, device=self.device)
+            if stacked_flags is not None and len(stacked_flags) != 4:
                 raise _lib.OvnError("with probs, stacked_flags is (use_depth, use_normals, use_semantic, use_intensity)")
-            ud, un, us, ui = (int(bool(v)) for v in stacked_flags)
-            c = ud + 3 * un + n_classes * us + ui
-            if stacked_out is not None:
-                if (stacked_out.device != self.device or stacked_out.dtype != torch.float32 or not stacked_out.is_contiguous()
-                        or tuple(stacked_out.shape) != (n, proj_h, proj_w, c)):
-                    raise _lib.OvnError("stacked_out must be a contiguous float32 (%d,%d,%d,%d) tensor on %s"
-                                        % (n, proj_h, proj_w, c, self.device))
-                stk = stacked_out
+            table = dict(_PROJECT_OUTPUTS, semantic=((n_classes,), _F32), sem_idx=((), _I32))
+        n = offsets.numel() - 1
+        ud = un = us = ui = 0
+        c = None
+        if stacked_flags is not None:
+            if semantic:
+                ud, un, us, ui = (int(bool(v)) for v in stacked_flags)
             else:
-                stk = mk(n, proj_h, proj_w, c)
-        with self._dev():
-            _lib.check(self.lib.ovn_project_semantic(self._h, _ptr(points), _ptr(offsets), n, int(max_points), proj_h, proj_w,
-                                                     float(fov_up), float(fov_down), float(max_range), _ptr(probs), n_classes,
-                                                     _ptr(rng), _ptr(vtx), _ptr(itn), _ptr(idx), _ptr(nrm), _ptr(sem), _ptr(sid),
-                                                     _ptr(stk), ud, un, us, ui, self._stream()),
-                       "ovn_project_semantic")
-        out = {}
-        for k, v in (("range", rng), ("vertex", vtx), ("intensity", itn), ("idx", idx), ("normal", nrm), ("semantic", sem),
-                     ("sem_idx", sid), ("stacked", stk)):
-            if v is not None:
-                out[k] = v
+                ud, un, ui = (int(bool(v)) for v in stacked_flags)
+            c = ud + 3 * un + ui + (n_classes if us else 0)
+        out, stk = self._image_outputs(n, proj_h, proj_w, table, want, c, stacked_out)
+        scans = (_ptr(points), _ptr(offsets), n, int(max_points), proj_h, proj_w, float(fov_up), float(fov_down), float(max_range))
+        images = [_ptr(out.get(k)) for k in table]
+        if semantic:
+            self._call("ovn_project_semantic", *scans, _ptr(probs), n_classes, *images, _ptr(stk), ud, un, us, ui, self._stream())
+        else:
+            self._call("ovn_project", *scans, *images, _ptr(stk), ud, un, ui, self._stream())
+        if stk is not None:
+            out["stacked"] = stk
         return out
 
     def normals(self, rng: torch.Tensor, vtx: torch.Tensor) -> torch.Tensor:
         """range (n,H,W) + vertex (n,H,W,4) device tensors -> normal map (n,H,W,3)."""
-        for t in (rng, vtx):
-            if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous():
-                raise _lib.OvnError("normals(): inputs must be contiguous float32 tensors on %s" % self.device)
+        self._check(rng, "normals(): range")
+        self._check(vtx, "normals(): vertex")
         n, h, w = rng.shape
         if tuple(vtx.shape) != (n, h, w, 4):
             raise _lib.OvnError("normals(): vertex shape %s does not match range %s" % (tuple(vtx.shape), tuple(rng.shape)))
         out = torch.empty((n, h, w, 3), dtype=torch.float32, device=self.device)
-        with self._dev():
-            _lib.check(self.lib.ovn_normals(self._h, _ptr(rng), _ptr(vtx), n, h, w, _ptr(out), self._stream()),
-                       "ovn_normals")
+        self._call("ovn_normals", _ptr(rng), _ptr(vtx), n, h, w, _ptr(out), self._stream())
         return out
 
     def render_scans(self, mesh, poses, proj_h: int = 64, proj_w: int = 900, fov_up: float = 3.0, fov_down: float = -25.0,
@@ -997,56 +903,35 @@ class OvnEngine:
         use_normals) additionally assembles the (n,H,W,C) leg input (into `stacked_out` when given); a third (intensity) or fourth
         (class probabilities) flag that is set is refused by the library: a rendered scan has neither.  exhaustive=True walks every
         triangle with every ray (the validation route) instead of the mesh's hierarchy.  Returns a dict of device tensors."""
-        bad = [k for k in want if k not in ("range", "tri_id", "vertex", "normal")]
+        bad = [k for k in want if k not in _RENDER_OUTPUTS]
         if bad:
             raise _lib.OvnError("render_scans: no output %s (a rendered scan has range, tri_id, vertex, normal)" % bad)
-        if isinstance(poses, torch.Tensor):
-            p = poses.to(self.device, torch.float64).contiguous()
-        else:
-            p = torch.from_numpy(np.ascontiguousarray(np.asarray(poses, np.float64))).to(self.device)
+        p = self._poses64(poses)
         if p.dim() != 3 or tuple(p.shape[1:]) != (4, 4):
             raise _lib.OvnError("render_scans: poses must be (n,4,4), got %s" % (tuple(p.shape),))
-        n, dev = p.shape[0], self.device
+        n = p.shape[0]
         proj_h, proj_w = int(proj_h), int(proj_w)
         tabs = self._direction_tables(proj_h, proj_w, fov_up, fov_down)
         md = mesh.device(self, with_bvh=not exhaustive)
         nodes, order, leaves = (None, None, 0) if exhaustive else (md["nodes"], md["order"], md["leaves"])
-        mk = lambda *shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)
-        rng = mk(n, proj_h, proj_w) if "range" in want else None
-        tid = mk(n, proj_h, proj_w, dt=torch.int32) if "tri_id" in want else None
-        vtx = mk(n, proj_h, proj_w, 4) if "vertex" in want else None
-        nrm = mk(n, proj_h, proj_w, 3) if "normal" in want else None
-        stk = None
         flags = [0, 0, 0, 0]
+        c = None
         if stacked_flags is not None:
             if not 1 <= len(stacked_flags) <= 4:
                 raise _lib.OvnError("render_scans: stacked_flags is (use_depth, use_normals[, use_intensity[, use_semantic]])")
             flags[:len(stacked_flags)] = [int(bool(v)) for v in stacked_flags]
             c = flags[0] + 3 * flags[1]
-            if stacked_out is not None:
-                if (stacked_out.device != dev or stacked_out.dtype != torch.float32 or not stacked_out.is_contiguous()
-                        or tuple(stacked_out.shape) != (n, proj_h, proj_w, c)):
-                    raise _lib.OvnError("stacked_out must be a contiguous float32 (%d,%d,%d,%d) tensor on %s" % (n, proj_h, proj_w, c, dev))
-                stk = stacked_out
-            else:
-                stk = mk(n, proj_h, proj_w, max(c, 1))
-        with self._dev():
-            _lib.check(self.lib.ovn_render_scans(self._h, _ptr(md["vertices"]), mesh.n_vertices, _ptr(md["triangles"]),
-                                                 mesh.n_triangles, _ptr(nodes), _ptr(order), int(leaves), _ptr(p), n, proj_h, proj_w,
-                                                 _ptr(tabs[0]), _ptr(tabs[1]), _ptr(tabs[2]), _ptr(tabs[3]), float(max_range),
-                                                 _ptr(rng), _ptr(tid), _ptr(vtx), _ptr(nrm), _ptr(stk), flags[0], flags[1], flags[2],
-                                                 flags[3], self._stream()),
-                       "ovn_render_scans")
-        out = {}
-        for k, v in (("range", rng), ("tri_id", tid), ("vertex", vtx), ("normal", nrm), ("stacked", stk)):
-            if v is not None:
-                out[k] = v
+        out, stk = self._image_outputs(n, proj_h, proj_w, _RENDER_OUTPUTS, want, c, stacked_out, min_channels=1)
+        self._call("ovn_render_scans", _ptr(md["vertices"]), mesh.n_vertices, _ptr(md["triangles"]), mesh.n_triangles, _ptr(nodes),
+                   _ptr(order), int(leaves), _ptr(p), n, proj_h, proj_w, _ptr(tabs[0]), _ptr(tabs[1]), _ptr(tabs[2]), _ptr(tabs[3]),
+                   float(max_range), *[_ptr(out.get(k)) for k in _RENDER_OUTPUTS], _ptr(stk), *flags, self._stream())
+        if stk is not None:
+            out["stacked"] = stk
         return out
 
     def _tsdf_volume_args(self, what: str, tsdf: torch.Tensor, weight: torch.Tensor, origin):
-        for t, name in ((tsdf, "tsdf"), (weight, "weight")):
-            if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 3:
-                raise _lib.OvnError("%s: %s must be a contiguous float32 (nz,ny,nx) tensor on %s" % (what, name, self.device))
+        self._check(tsdf, "%s: tsdf (nz,ny,nx)" % what, ndim=3)
+        self._check(weight, "%s: weight (nz,ny,nx)" % what, ndim=3)
         if tuple(weight.shape) != tuple(tsdf.shape):
             raise _lib.OvnError("%s: weight %s does not match tsdf %s" % (what, tuple(weight.shape), tuple(tsdf.shape)))
         org = np.asarray(origin, np.float64).reshape(-1)
@@ -1074,27 +959,18 @@ class OvnEngine:
         the rolling window at that base and `origin` is its anchor (ovn_tsdf_window_integrate)."""
         nx, ny, nz, org = self._tsdf_volume_args("tsdf_integrate", tsdf, weight, origin)
         b3 = None if base is None else self._int3("tsdf_integrate", "base", base)
-        r = range_images
-        if r.device != self.device or r.dtype != torch.float32 or not r.is_contiguous() or r.dim() != 3:
-            raise _lib.OvnError("tsdf_integrate: range_images must be a contiguous float32 (n,H,W) tensor on %s" % self.device)
-        if isinstance(poses, torch.Tensor):
-            p = poses.to(self.device, torch.float64).contiguous()
-        else:
-            p = torch.from_numpy(np.ascontiguousarray(np.asarray(poses, np.float64))).to(self.device)
+        r = self._check(range_images, "tsdf_integrate: range_images (n,H,W)", ndim=3)
+        p = self._poses64(poses)
         n, h, w = (int(v) for v in r.shape)
         if tuple(p.shape) != (n, 4, 4):
             raise _lib.OvnError("tsdf_integrate: poses must be (%d,4,4) for %d range images, got %s" % (n, n, tuple(p.shape)))
-        with self._dev():
-            if b3 is not None:
-                _lib.check(self.lib.ovn_tsdf_window_integrate(self._h, self._stream(), _ptr(tsdf), _ptr(weight), nx, ny, nz, org, b3,
-                                                              float(voxel), float(trunc), float(max_weight), _ptr(r), _ptr(p), n, h, w,
-                                                              float(fov_up), float(fov_down), float(max_range)),
-                           "ovn_tsdf_window_integrate")
-                return
-            _lib.check(self.lib.ovn_tsdf_integrate(self._h, _ptr(tsdf), _ptr(weight), nx, ny, nz, org, float(voxel), float(trunc),
-                                                   float(max_weight), _ptr(r), _ptr(p), n, h, w, float(fov_up), float(fov_down),
-                                                   float(max_range), self._stream()),
-                       "ovn_tsdf_integrate")
+        scans = (_ptr(r), _ptr(p), n, h, w, float(fov_up), float(fov_down), float(max_range))
+        if b3 is not None:
+            self._call("ovn_tsdf_window_integrate", self._stream(), _ptr(tsdf), _ptr(weight), nx, ny, nz, org, b3, float(voxel),
+                       float(trunc), float(max_weight), *scans)
+        else:
+            self._call("ovn_tsdf_integrate", _ptr(tsdf), _ptr(weight), nx, ny, nz, org, float(voxel), float(trunc), float(max_weight),
+                       *scans, self._stream())
 
     def tsdf_triangles(self, tsdf: torch.Tensor, weight: torch.Tensor, origin, voxel: float, min_weight: float = 1.0,
                        capacity: Optional[int] = None, out: Optional[torch.Tensor] = None, base=None, box=None):
@@ -1110,8 +986,8 @@ class OvnEngine:
             b3 = self._int3("tsdf_triangles", "base", base)
             lo3, hi3 = self._int3("tsdf_triangles", "box_lo", box[0]), self._int3("tsdf_triangles", "box_hi", box[1])
         if out is not None:
-            if (out.device != self.device or out.dtype != torch.float32 or not out.is_contiguous() or out.dim() != 3
-                    or tuple(out.shape[1:]) != (3, 3)):
+            self._check(out, "tsdf_triangles: out (capacity,3,3)", ndim=3)
+            if tuple(out.shape[1:]) != (3, 3):
                 raise _lib.OvnError("tsdf_triangles: out must be a contiguous float32 (capacity,3,3) tensor on %s" % self.device)
             if capacity is None:
                 capacity = int(out.shape[0])
@@ -1120,16 +996,12 @@ class OvnEngine:
         count = torch.zeros(1, dtype=torch.int64, device=self.device)
 
         def call(buf, cap):
-            with self._dev():
-                if base is not None:
-                    _lib.check(self.lib.ovn_tsdf_window_triangles(self._h, self._stream(), _ptr(tsdf), _ptr(weight), nx, ny, nz, org, b3,
-                                                                  float(voxel), float(min_weight), lo3, hi3, _ptr(buf), int(cap),
-                                                                  _ptr(count)),
-                               "ovn_tsdf_window_triangles")
-                else:
-                    _lib.check(self.lib.ovn_tsdf_triangles(self._h, _ptr(tsdf), _ptr(weight), nx, ny, nz, org, float(voxel),
-                                                           float(min_weight), _ptr(buf), int(cap), _ptr(count), self._stream()),
-                               "ovn_tsdf_triangles")
+            if base is not None:
+                self._call("ovn_tsdf_window_triangles", self._stream(), _ptr(tsdf), _ptr(weight), nx, ny, nz, org, b3, float(voxel),
+                           float(min_weight), lo3, hi3, _ptr(buf), int(cap), _ptr(count))
+            else:
+                self._call("ovn_tsdf_triangles", _ptr(tsdf), _ptr(weight), nx, ny, nz, org, float(voxel), float(min_weight), _ptr(buf),
+                           int(cap), _ptr(count), self._stream())
             return int(count.item())
 
         if capacity is None:
@@ -1158,17 +1030,14 @@ class OvnEngine:
     def tsdf_bricks(self, weight: torch.Tensor, min_weight: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The byte mask `tsdf_raycast` takes: (ceil(nz/8), ceil(ny/8), ceil(nx/8)) uint8, 1 where some sample of the 8 x 8 x 8 brick
         has weight >= min_weight (ovn_tsdf_bricks), written into `out` when given."""
-        if weight.device != self.device or weight.dtype != torch.float32 or not weight.is_contiguous() or weight.dim() != 3:
-            raise _lib.OvnError("tsdf_bricks: weight must be a contiguous float32 (nz,ny,nx) tensor on %s" % self.device)
+        self._check(weight, "tsdf_bricks: weight (nz,ny,nx)", ndim=3)
         nz, ny, nx = (int(v) for v in weight.shape)
         shape = tuple(-(-v // 8) for v in (nz, ny, nx))
         if out is None:
             out = torch.empty(shape, dtype=torch.uint8, device=self.device)
-        elif out.device != self.device or out.dtype != torch.uint8 or not out.is_contiguous() or tuple(out.shape) != shape:
-            raise _lib.OvnError("tsdf_bricks: out must be a contiguous uint8 %s tensor on %s" % (shape, self.device))
-        with self._dev():
-            _lib.check(self.lib.ovn_tsdf_bricks(self._h, self._stream(), _ptr(weight), nx, ny, nz, float(min_weight), _ptr(out)),
-                       "ovn_tsdf_bricks")
+        else:
+            self._check(out, "tsdf_bricks: out", torch.uint8, shape)
+        self._call("ovn_tsdf_bricks", self._stream(), _ptr(weight), nx, ny, nz, float(min_weight), _ptr(out))
         return out
 
     def tsdf_raycast(self, tsdf: torch.Tensor, weight: torch.Tensor, origin, voxel: float, poses, proj_h: int = 64, proj_w: int = 900,
@@ -1185,62 +1054,38 @@ class OvnEngine:
         axis of a caller's buffer) to write into instead of a fresh tensor.  Returns a dict of device tensors.  With `base` the
         tensors are the rolling window at that base, `origin` its anchor and `bricks` the mask of the storage as it stands
         (ovn_tsdf_window_raycast)."""
-        bad = [k for k in want if k not in ("range", "vertex", "normal")]
+        bad = [k for k in want if k not in _RAYCAST_OUTPUTS]
         if bad:
             raise _lib.OvnError("tsdf_raycast: no output %s (a ray-cast view has range, vertex, normal)" % bad)
         nx, ny, nz, org = self._tsdf_volume_args("tsdf_raycast", tsdf, weight, origin)
         b3 = None if base is None else self._int3("tsdf_raycast", "base", base)
-        if isinstance(poses, torch.Tensor):
-            p = poses.to(self.device, torch.float64).contiguous()
-        else:
-            p = torch.from_numpy(np.ascontiguousarray(np.asarray(poses, np.float64))).to(self.device)
+        p = self._poses64(poses)
         if p.dim() != 3 or tuple(p.shape[1:]) != (4, 4):
             raise _lib.OvnError("tsdf_raycast: poses must be (n,4,4), got %s" % (tuple(p.shape),))
-        n, dev = int(p.shape[0]), self.device
+        n = int(p.shape[0])
         proj_h, proj_w = int(proj_h), int(proj_w)
-        if bricks is not None:
-            shape = tuple(-(-v // 8) for v in (nz, ny, nx))
-            if bricks.device != dev or bricks.dtype != torch.uint8 or not bricks.is_contiguous() or tuple(bricks.shape) != shape:
-                raise _lib.OvnError("tsdf_raycast: bricks must be a contiguous uint8 %s tensor on %s" % (shape, dev))
+        self._check(bricks, "tsdf_raycast: bricks", torch.uint8, tuple(-(-v // 8) for v in (nz, ny, nx)), optional=True)
         out = dict(out or {})
-        unknown = [k for k in out if k not in ("range", "vertex", "normal")]
+        unknown = [k for k in out if k not in _RAYCAST_OUTPUTS]
         if unknown:
             raise _lib.OvnError("tsdf_raycast: out names %s; it takes range, vertex, normal" % unknown)
-        bufs = {}
-        for k, tail in (("range", ()), ("vertex", (4,)), ("normal", (3,))):
-            shape = (n, proj_h, proj_w) + tail
-            if k in out:
-                t = out[k]
-                if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape:
-                    raise _lib.OvnError("tsdf_raycast: out[%r] must be a contiguous float32 %s tensor on %s" % (k, shape, dev))
-                bufs[k] = t
-            elif k in want:
-                bufs[k] = torch.empty(shape, dtype=torch.float32, device=dev)
-        stk = None
         ud = un = 0
+        c = None
         if stacked_flags is not None:
             if len(stacked_flags) != 2:
                 raise _lib.OvnError("tsdf_raycast: stacked_flags is (use_depth, use_normals)")
             ud, un = (int(bool(v)) for v in stacked_flags)
             c = ud + 3 * un
-            if stacked_out is not None:
-                if (stacked_out.device != dev or stacked_out.dtype != torch.float32 or not stacked_out.is_contiguous()
-                        or tuple(stacked_out.shape) != (n, proj_h, proj_w, c)):
-                    raise _lib.OvnError("stacked_out must be a contiguous float32 (%d,%d,%d,%d) tensor on %s" % (n, proj_h, proj_w, c, dev))
-                stk = stacked_out
-            else:
-                stk = torch.empty((n, proj_h, proj_w, max(c, 1)), dtype=torch.float32, device=dev)
+        bufs, stk = self._image_outputs(n, proj_h, proj_w, _RAYCAST_OUTPUTS, want, c, stacked_out, min_channels=1, out=out,
+                                        what="tsdf_raycast: ")
         tabs = self._direction_tables(proj_h, proj_w, fov_up, fov_down)
         tail = (float(voxel), float(min_weight), _ptr(bricks), _ptr(p), n, proj_h, proj_w, _ptr(tabs[0]), _ptr(tabs[1]), _ptr(tabs[2]),
                 _ptr(tabs[3]), float(min_range), float(max_range), float(voxel if step is None else step), _ptr(bufs.get("range")),
                 _ptr(bufs.get("vertex")), _ptr(bufs.get("normal")), _ptr(stk), ud, un)
-        with self._dev():
-            if b3 is not None:
-                _lib.check(self.lib.ovn_tsdf_window_raycast(self._h, self._stream(), _ptr(tsdf), _ptr(weight), nx, ny, nz, org, b3, *tail),
-                           "ovn_tsdf_window_raycast")
-            else:
-                _lib.check(self.lib.ovn_tsdf_raycast(self._h, self._stream(), _ptr(tsdf), _ptr(weight), nx, ny, nz, org, *tail),
-                           "ovn_tsdf_raycast")
+        if b3 is not None:
+            self._call("ovn_tsdf_window_raycast", self._stream(), _ptr(tsdf), _ptr(weight), nx, ny, nz, org, b3, *tail)
+        else:
+            self._call("ovn_tsdf_raycast", self._stream(), _ptr(tsdf), _ptr(weight), nx, ny, nz, org, *tail)
         if stk is not None:
             bufs["stacked"] = stk
         return bufs
@@ -1250,9 +1095,7 @@ class OvnEngine:
         (tsdf 1, weight 0) for the samples that enter, nothing else is written (ovn_tsdf_window_shift)."""
         nx, ny, nz, _ = self._tsdf_volume_args("tsdf_window_shift", tsdf, weight, (0.0, 0.0, 0.0))
         ob, nb = self._int3("tsdf_window_shift", "old_base", old_base), self._int3("tsdf_window_shift", "new_base", new_base)
-        with self._dev():
-            _lib.check(self.lib.ovn_tsdf_window_shift(self._h, self._stream(), _ptr(tsdf), _ptr(weight), nx, ny, nz, ob, nb),
-                       "ovn_tsdf_window_shift")
+        self._call("ovn_tsdf_window_shift", self._stream(), _ptr(tsdf), _ptr(weight), nx, ny, nz, ob, nb)
 
     def icp_register(self, vertex: torch.Tensor, normal: torch.Tensor, rng: torch.Tensor, src_idx: torch.Tensor,
                      tgt_idx: torch.Tensor, init_pose: torch.Tensor, iterations: int = 20, max_dist: float = 2.0,
@@ -1265,8 +1108,7 @@ class OvnEngine:
         for t, what, dt in ((vertex, "vertex", torch.float32), (normal, "normal", torch.float32), (rng, "range", torch.float32),
                             (src_idx, "src_idx", torch.int32), (tgt_idx, "tgt_idx", torch.int32),
                             (init_pose, "init_pose", torch.float64)):
-            if t.device != self.device or t.dtype != dt or not t.is_contiguous():
-                raise _lib.OvnError("icp_register(): %s must be a contiguous %s tensor on %s" % (what, dt, self.device))
+            self._check(t, "icp_register(): " + what, dt)
         if rng.dim() != 3:
             raise _lib.OvnError("icp_register(): range must be (n, H, W), got %s" % (tuple(rng.shape),))
         n, h, w = (int(v) for v in rng.shape)
@@ -1280,26 +1122,14 @@ class OvnEngine:
         pose = torch.empty((p, 4, 4), dtype=torch.float64, device=self.device)
         stats = torch.empty((p, 8), dtype=torch.float64, device=self.device)
         system = torch.empty((p, 28), dtype=torch.float64, device=self.device) if want_system else None
-        with self._dev():
-            _lib.check(self.lib.ovn_icp_register(self._h, _ptr(vertex), _ptr(normal), _ptr(rng), n, h, w, float(fov_up),
-                                                 float(fov_down), float(max_range), _ptr(src_idx), _ptr(tgt_idx), p, _ptr(init_pose),
-                                                 int(iterations), float(max_dist), float(cos_min), float(huber), int(min_inliers),
-                                                 _ptr(pose), _ptr(stats), _ptr(system), self._stream()), "ovn_icp_register")
+        self._call("ovn_icp_register", _ptr(vertex), _ptr(normal), _ptr(rng), n, h, w, float(fov_up), float(fov_down), float(max_range),
+                   _ptr(src_idx), _ptr(tgt_idx), p, _ptr(init_pose), int(iterations), float(max_dist), float(cos_min), float(huber),
+                   int(min_inliers), _ptr(pose), _ptr(stats), _ptr(system), self._stream())
         return (pose, stats, system) if want_system else (pose, stats)
 
     # -- Monte Carlo localization (csrc/mcl.hip) -------------------------------------------------------
-    def _check_mcl(self, t: torch.Tensor, what: str, dtype, numel: Optional[int] = None, pinned_ok: bool = False) -> None:
-        """A buffer of the mcl_* calls: contiguous, of `dtype`, on this device (a record may instead be pinned host memory, which the
-        device sees at the same address), holding `numel` elements when given."""
-        on_dev = t.device == self.device or (pinned_ok and t.device.type == "cpu" and t.is_pinned())
-        if not on_dev or t.dtype != dtype or not t.is_contiguous():
-            raise _lib.OvnError("%s must be a contiguous %s tensor on %s%s" % (what, dtype, self.device,
-                                                                             " (or pinned host memory)" if pinned_ok else ""))
-        if numel is not None and t.numel() != numel:
-            raise _lib.OvnError("%s holds %d elements, expected %d" % (what, t.numel(), numel))
-
     def _mcl_particles(self, particles: torch.Tensor, what: str = "particles") -> int:
-        self._check_mcl(particles, what, torch.float32)
+        self._check(particles, what)
         if particles.dim() != 2 or particles.shape[1] != 4:
             raise _lib.OvnError("%s must be (P, 4) rows x, y, theta, w; got %s" % (what, tuple(particles.shape)))
         return int(particles.shape[0])
@@ -1314,7 +1144,8 @@ class OvnEngine:
         record = {U, particles off the map, 0, 1} may be a pinned host tensor (the caller synchronises before reading it)."""
         p = self._mcl_particles(particles)
         nx, ny, m = int(nx), int(ny), int(n_frames)
-        self._check_mcl(cell_frame, "cell_frame", torch.int32, max(nx, 0) * max(ny, 0))
+        i32 = torch.int32
+        self._check(cell_frame, "cell_frame", i32, numel=max(nx, 0) * max(ny, 0))
         if particle_frame is None:
             particle_frame = torch.empty(p, dtype=torch.int32, device=self.device)
         if frame_slot is None:
@@ -1323,17 +1154,15 @@ class OvnEngine:
             frame_list = torch.empty(max(m, 0), dtype=torch.int32, device=self.device)
         if record is None:
             record = torch.empty(4, dtype=torch.int32, device=self.device)
-        self._check_mcl(particle_frame, "particle_frame", torch.int32, p)
-        self._check_mcl(frame_slot, "frame_slot", torch.int32, max(m, 0))
-        self._check_mcl(frame_list, "frame_list", torch.int32, max(m, 0))
-        self._check_mcl(record, "record", torch.int32, 4, pinned_ok=True)
+        self._check(particle_frame, "particle_frame", i32, numel=p)
+        self._check(frame_slot, "frame_slot", i32, numel=max(m, 0))
+        self._check(frame_list, "frame_list", i32, numel=max(m, 0))
+        self._check(record, "record", i32, numel=4, pinned_ok=True)
         dx, dy, dth = (float(v) for v in odom)
         sx, sy, sth = (float(v) for v in sigma)
-        with self._dev():
-            _lib.check(self.lib.ovn_mcl_predict(self._h, _ptr(particles), p, dx, dy, dth, sx, sy, sth, int(seed) & (2 ** 64 - 1),
-                                                int(step) & (2 ** 64 - 1), _ptr(cell_frame), float(origin[0]), float(origin[1]),
-                                                float(resolution), nx, ny, m, _ptr(particle_frame), _ptr(frame_slot), _ptr(frame_list),
-                                                _ptr(record), self._stream()), "ovn_mcl_predict")
+        self._call("ovn_mcl_predict", _ptr(particles), p, dx, dy, dth, sx, sy, sth, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1),
+                   _ptr(cell_frame), float(origin[0]), float(origin[1]), float(resolution), nx, ny, m, _ptr(particle_frame),
+                   _ptr(frame_slot), _ptr(frame_list), _ptr(record), self._stream())
         return particle_frame, frame_slot, frame_list, record
 
     def mcl_update(self, particles: torch.Tensor, particle_frame: torch.Tensor, frame_slot: torch.Tensor, frame_yaw: torch.Tensor,
@@ -1345,25 +1174,23 @@ class OvnEngine:
         want_spread=True also the weighted rms distance from the mean position, a (1,) float64 device tensor."""
         p = self._mcl_particles(particles)
         m = int(frame_slot.numel())
-        self._check_mcl(particle_frame, "particle_frame", torch.int32, p)
-        self._check_mcl(frame_slot, "frame_slot", torch.int32)
-        self._check_mcl(frame_yaw, "frame_yaw", torch.float32, m)
+        self._check(particle_frame, "particle_frame", torch.int32, numel=p)
+        self._check(frame_slot, "frame_slot", torch.int32)
+        self._check(frame_yaw, "frame_yaw", torch.float32, numel=m)
         if (overlap is None) != (yaw is None):
             raise _lib.OvnError("mcl_update(): overlap and yaw must be given together")
         u = 0
         if overlap is not None:
             u = int(overlap.numel())
-            self._check_mcl(overlap, "overlap", torch.float32)
-            self._check_mcl(yaw, "yaw", torch.int32, u)
+            self._check(overlap, "overlap", torch.float32)
+            self._check(yaw, "yaw", torch.int32, numel=u)
         if estimate is None:
             estimate = torch.empty(8, dtype=torch.float64, device=self.device)
-        self._check_mcl(estimate, "estimate", torch.float64, 8)
+        self._check(estimate, "estimate", torch.float64, numel=8)
         spread = torch.empty(1, dtype=torch.float64, device=self.device) if want_spread else None
-        with self._dev():
-            _lib.check(self.lib.ovn_mcl_update(self._h, _ptr(particles), p, _ptr(particle_frame), _ptr(frame_slot), _ptr(frame_yaw), m,
-                                               _ptr(overlap) if u else None, _ptr(yaw) if u else None, u, float(sigma_yaw),
-                                               float(eps_yaw), float(overlap_min), _ptr(estimate), _ptr(spread), self._stream()),
-                       "ovn_mcl_update")
+        self._call("ovn_mcl_update", _ptr(particles), p, _ptr(particle_frame), _ptr(frame_slot), _ptr(frame_yaw), m,
+                   _ptr(overlap) if u else None, _ptr(yaw) if u else None, u, float(sigma_yaw), float(eps_yaw), float(overlap_min),
+                   _ptr(estimate), _ptr(spread), self._stream())
         return (estimate, spread) if want_spread else estimate
 
     def mcl_resample(self, particles: torch.Tensor, seed: int, step: int, n_out: Optional[int] = None,
@@ -1382,28 +1209,25 @@ class OvnEngine:
             ancestors = torch.empty(max(n_out, 0), dtype=torch.int32, device=self.device)
         if record is None:
             record = torch.empty(4, dtype=torch.int32, device=self.device)
-        self._check_mcl(ancestors, "ancestors", torch.int32, max(n_out, 0))
-        self._check_mcl(record, "record", torch.int32, 4, pinned_ok=True)
-        with self._dev():
-            _lib.check(self.lib.ovn_mcl_resample(self._h, _ptr(particles), p, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1),
-                                                 _ptr(out), n_out, _ptr(ancestors), _ptr(record), self._stream()), "ovn_mcl_resample")
+        self._check(ancestors, "ancestors", torch.int32, numel=max(n_out, 0))
+        self._check(record, "record", torch.int32, numel=4, pinned_ok=True)
+        self._call("ovn_mcl_resample", _ptr(particles), p, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), _ptr(out), n_out,
+                   _ptr(ancestors), _ptr(record), self._stream())
         return out, ancestors, record
 
     def projection_angles(self, points: torch.Tensor, proj_h: int = 64, proj_w: int = 900, fov_up: float = 3.0,
                           fov_down: float = -25.0, max_range: float = 50.0):
         """(yaw, pitch, pixel) of every point of an (n, 4) float32 device tensor as the projection kernel evaluates them
         (utils.py:75-104; pixel = -1 for points the range filter drops) -- validation entry, include/ovn_hip.h."""
-        if points.device != self.device or points.dtype != torch.float32 or not points.is_contiguous() or points.dim() != 2 \
-                or points.shape[1] != 4:
+        self._check(points, "projection_angles(): points (n, 4)", ndim=2)
+        if points.shape[1] != 4:
             raise _lib.OvnError("projection_angles(): points must be a contiguous (n, 4) float32 tensor on %s" % self.device)
         n = points.shape[0]
         yaw = torch.empty(n, dtype=torch.float32, device=self.device)
         pitch = torch.empty(n, dtype=torch.float32, device=self.device)
         pix = torch.empty(n, dtype=torch.int32, device=self.device)
-        with self._dev():
-            _lib.check(self.lib.ovn_projection_angles(self._h, _ptr(points), n, proj_h, proj_w, float(fov_up), float(fov_down),
-                                                      float(max_range), _ptr(yaw), _ptr(pitch), _ptr(pix), self._stream()),
-                       "ovn_projection_angles")
+        self._call("ovn_projection_angles", _ptr(points), n, proj_h, proj_w, float(fov_up), float(fov_down), float(max_range), _ptr(yaw),
+                   _ptr(pitch), _ptr(pix), self._stream())
         return yaw, pitch, pix
 
     def debug_head_activations(self, n: int):
@@ -1413,20 +1237,17 @@ class OvnEngine:
         g = self._fw // 15
         o2 = torch.empty((n, g, g, 128), dtype=torch.float32, device=self.device)
         o3 = torch.empty((n, g - 2, g - 2, 256), dtype=torch.float32, device=self.device)
-        with self._dev():
-            _lib.check(self.lib.ovn_debug_head_activations(self._h, n, _ptr(o2), _ptr(o3), self._stream()),
-                       "ovn_debug_head_activations")
+        self._call("ovn_debug_head_activations", n, _ptr(o2), _ptr(o3), self._stream())
         return o2, o3
 
     def set_head_pipeline(self, chunk_pairs: int = 1024, sub_chunk_pairs: int = 0, streams: int = 1, yaw_on_side_stream: bool = False):
         """Launch structure of the head calls (include/ovn_hip.h: ovn_set_head_pipeline); results do not depend on it."""
-        _lib.check(self.lib.ovn_set_head_pipeline(self._h, int(chunk_pairs), int(sub_chunk_pairs), int(streams),
-                                                  int(bool(yaw_on_side_stream))), "ovn_set_head_pipeline")
+        self._call("ovn_set_head_pipeline", int(chunk_pairs), int(sub_chunk_pairs), int(streams), int(bool(yaw_on_side_stream)))
 
     def head_pipeline(self):
         """(chunk_pairs, sub_chunk_pairs, streams, yaw_on_side_stream) currently in effect."""
         a, b, c, d = C.c_int64(), C.c_int64(), C.c_int(), C.c_int()
-        _lib.check(self.lib.ovn_get_head_pipeline(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)), "ovn_get_head_pipeline")
+        self._call("ovn_get_head_pipeline", C.byref(a), C.byref(b), C.byref(c), C.byref(d))
         return int(a.value), int(b.value), int(c.value), bool(d.value)
 
     def set_head_precision(self, mode: str) -> None:
@@ -1442,16 +1263,16 @@ class OvnEngine:
         table = {"f32": 0, "f16x3": 1, "bf16x3": 2}
         if mode not in table:
             raise ValueError("head precision must be one of %s" % sorted(table))
-        _lib.check(self.lib.ovn_set_head_precision(self._h, table[mode]), "ovn_set_head_precision")
+        self._call("ovn_set_head_precision", table[mode])
         self.head_precision = mode
 
     def set_head_width_split(self, on: bool) -> None:
         """Delta head at a feature width other than 360 (conv1size 15): False (default) = exact fp32 in every head precision, True =
         head precision 'f16x3' runs DeltaLayer + c_conv1 + c_conv2 in the scaled 3-term fp16 split (delta_head_w_f16x3.hip),
         several times the fp32 rate at the error of the 360 path.  No effect at 360 columns or in the other head precisions."""
-        _lib.check(self.lib.ovn_set_head_width_split(self._h, 1 if on else 0), "ovn_set_head_width_split")
+        self._call("ovn_set_head_width_split", 1 if on else 0)
         got = C.c_int()
-        _lib.check(self.lib.ovn_get_head_width_split(self._h, C.byref(got)), "ovn_get_head_width_split")
+        self._call("ovn_get_head_width_split", C.byref(got))
         self.head_width_split = bool(got.value)
 
     def set_corr_normalization(self, mode: str) -> None:
@@ -1461,19 +1282,19 @@ class OvnEngine:
         `spectrum` are valid for the mode they were built under; the Delta head is not affected."""
         if not isinstance(mode, str) or mode not in W.CORR_NORMALIZE_MODES:
             raise ValueError("correlation normalisation must be one of %s" % sorted(W.CORR_NORMALIZE_MODES))
-        _lib.check(self.lib.ovn_set_corr_normalization(self._h, W.CORR_NORMALIZE_MODES[mode]), "ovn_set_corr_normalization")
+        self._call("ovn_set_corr_normalization", W.CORR_NORMALIZE_MODES[mode])
 
     @property
     def corr_normalization(self) -> str:
         """The normalisation mode the library context holds (ovn_get_corr_normalization)."""
         m = C.c_int(-1)
-        _lib.check(self.lib.ovn_get_corr_normalization(self._h, C.byref(m)), "ovn_get_corr_normalization")
+        self._call("ovn_get_corr_normalization", C.byref(m))
         return {v: k for k, v in W.CORR_NORMALIZE_MODES.items()}[m.value]
 
     def set_head_compaction(self, on: bool) -> None:
         """1-vs-N sweeps drop the query's dead feature channels (zero in all 360 columns) from the Delta head's contraction (default on;
         exact -- include/ovn_hip.h: ovn_set_head_compaction).  Off: every pair walks all 128 channels, as indexed pairs always do."""
-        _lib.check(self.lib.ovn_set_head_compaction(self._h, int(bool(on))), "ovn_set_head_compaction")
+        self._call("ovn_set_head_compaction", int(bool(on)))
         self.head_compaction = bool(on)
 
     def head_walk_stats(self) -> dict:
@@ -1483,7 +1304,7 @@ class OvnEngine:
         groups 3 w .. 3 w + 2 and skips a slice when none of them walks it; a last slice of <= 16 live channels is packed tap-major
         into `packed_last_slice_steps` steps instead of 15 (csrc/delta_head_f16x3.hip)."""
         out = (C.c_int32 * 16)()
-        _lib.check(self.lib.ovn_head_walk_stats(self._h, out, self._stream()), "ovn_head_walk_stats")
+        self._call("ovn_head_walk_stats", out, self._stream())
         spp = [int(out[2 + p]) for p in range(12)]
         per_wave = [max(spp[(3 * w) // 2], spp[(3 * w + 2) // 2]) for w in range(8)]
         nsm, tail = int(out[0]), int(out[15])
@@ -1501,7 +1322,7 @@ class OvnEngine:
         table = {"numpy_avx512": 0, "rounded": 1}
         if mode not in table:
             raise ValueError("projection trig must be one of %s" % sorted(table))
-        _lib.check(self.lib.ovn_set_projection_trig(self._h, table[mode]), "ovn_set_projection_trig")
+        self._call("ovn_set_projection_trig", table[mode])
         self.projection_trig = mode
 
     def set_leg_precision(self, mode: str) -> None:
@@ -1509,21 +1330,20 @@ class OvnEngine:
         table = {"f32": 0, "f16x3": 1}
         if mode not in table:
             raise ValueError("leg precision must be one of %s" % sorted(table))
-        _lib.check(self.lib.ovn_set_leg_precision(self._h, table[mode]), "ovn_set_leg_precision")
+        self._call("ovn_set_leg_precision", table[mode])
         self.leg_precision = mode
 
     PROFILE_KINDS = ("leg_conv", "corr_head", "delta_c12", "c_conv3", "dense_sigmoid", "projection", "spectrum",
                      "corr_spectral", "delta_prep", "delta_c2")
 
     def profile_begin(self) -> None:
-        _lib.check(self.lib.ovn_profile_begin(self._h), "ovn_profile_begin")
+        self._call("ovn_profile_begin")
 
     def profile_end(self):
         """{kind: (total_ms, launches)} measured with HIP events on the launch stream."""
         ms = (C.c_double * len(self.PROFILE_KINDS))()
         cnt = (C.c_int64 * len(self.PROFILE_KINDS))()
-        with self._dev():
-            _lib.check(self.lib.ovn_profile_end(self._h, ms, cnt), "ovn_profile_end")
+        self._call("ovn_profile_end", ms, cnt)
         return {k: (float(ms[i]), int(cnt[i])) for i, k in enumerate(self.PROFILE_KINDS)}
 
     # -- pose-graph optimization (ovn_pose_graph_*; DESIGN.md section 32) -------------------------------------------
@@ -1532,14 +1352,6 @@ class OvnEngine:
     POSE_GRAPH_PRECONDITIONERS = {"jacobi": 0, "chain": 1}
     POSE_GRAPH_LOOPS = 2                       # OVN_POSE_GRAPH_LOOPS: served by the ovn_pose_graph_*_loops entries
     POSE_GRAPH_MAX_LOOPS = 256                 # OVN_POSE_GRAPH_MAX_LOOPS
-
-    def _pg_tensor(self, what: str, t: Optional[torch.Tensor], dtype, shape, optional: bool = False):
-        if t is None and optional:
-            return None
-        if (t is None or t.device != self.device or t.dtype != dtype or not t.is_contiguous()
-                or (shape is not None and tuple(t.shape) != tuple(shape))):
-            raise _lib.OvnError("%s must be a contiguous %s %s tensor on %s" % (what, dtype, tuple(shape) if shape else "", self.device))
-        return t
 
     def pose_graph_buffers(self, n_nodes: int, n_edges: int, chain: bool = False, loops: int = 0) -> Dict[str, torch.Tensor]:
         """Every device buffer the pose-graph calls write, sized for n_nodes and n_edges: res, chi, weight, jac, blocks, grad, diag,
@@ -1571,24 +1383,19 @@ class OvnEngine:
         Hessian blocks, gradient, diagonal blocks, their inverses and (when buf has "chain") the chain preconditioner's terms
         (ovn_pose_graph_linearize).  Returns the record tensor (buf["record"] unless another is given)."""
         f64, n, e = torch.float64, int(poses.shape[0]), int(edge_ij.shape[0])
-        self._pg_tensor("pose_graph_linearize: poses", poses, f64, (n, 4, 4))
-        self._pg_tensor("pose_graph_linearize: fixed", fixed, torch.uint8, (n,))
-        self._pg_tensor("pose_graph_linearize: edge_ij", edge_ij, torch.int32, (e, 2))
-        self._pg_tensor("pose_graph_linearize: meas", meas, f64, (e, 4, 4))
-        self._pg_tensor("pose_graph_linearize: info", info, f64, (e, 6, 6))
-        self._pg_tensor("pose_graph_linearize: node_ptr", node_ptr, torch.int32, (n + 1,))
-        self._pg_tensor("pose_graph_linearize: node_edge", node_edge, torch.int32, (2 * e,))
-        rec = self._pg_tensor("pose_graph_linearize: record", buf["record"] if record is None else record, f64, (16,))
+        for name, t, dt, shape in (("poses", poses, f64, (n, 4, 4)), ("fixed", fixed, torch.uint8, (n,)),
+                                   ("edge_ij", edge_ij, torch.int32, (e, 2)), ("meas", meas, f64, (e, 4, 4)), ("info", info, f64, (e, 6, 6)),
+                                   ("node_ptr", node_ptr, torch.int32, (n + 1,)), ("node_edge", node_edge, torch.int32, (2 * e,))):
+            self._check(t, "pose_graph_linearize: " + name, dt, shape)
+        rec = self._check(buf["record"] if record is None else record, "pose_graph_linearize: record", f64, (16,))
         for k, s in (("res", (e, 6)), ("chi", (e,)), ("weight", (e,)), ("jac", (e, 2, 6, 6)), ("blocks", (e, 3, 6, 6)), ("grad", (n, 6)),
                      ("diag", (n, 6, 6)), ("dinv", (n, 6, 6))):
-            self._pg_tensor("pose_graph_linearize: buf[%r]" % k, buf[k], f64, s)
-        ch = self._pg_tensor("pose_graph_linearize: buf['chain']", buf.get("chain"), f64, (max(n - 1, 0), 2, 6, 6), optional=True)
+            self._check(buf[k], "pose_graph_linearize: buf[%r]" % k, f64, s)
+        ch = self._check(buf.get("chain"), "pose_graph_linearize: buf['chain']", f64, (max(n - 1, 0), 2, 6, 6), optional=True)
         j = (lambda k: _ptr(buf[k])) if jacobians else (lambda k: None)
-        with self._dev():
-            _lib.check(self.lib.ovn_pose_graph_linearize(
-                self._h, self._stream(), _ptr(poses), _ptr(fixed), n, _ptr(edge_ij), _ptr(meas), _ptr(info), e, _ptr(node_ptr),
-                _ptr(node_edge), float(huber), _ptr(buf["res"]), _ptr(buf["chi"]), _ptr(buf["weight"]), j("jac"), j("blocks"), j("grad"),
-                j("diag"), j("dinv"), _ptr(ch) if jacobians else None, _ptr(buf["ws"]), _ptr(rec)), "ovn_pose_graph_linearize")
+        self._call("ovn_pose_graph_linearize", self._stream(), _ptr(poses), _ptr(fixed), n, _ptr(edge_ij), _ptr(meas), _ptr(info), e,
+                   _ptr(node_ptr), _ptr(node_edge), float(huber), _ptr(buf["res"]), _ptr(buf["chi"]), _ptr(buf["weight"]), j("jac"),
+                   j("blocks"), j("grad"), j("diag"), j("dinv"), _ptr(ch) if jacobians else None, _ptr(buf["ws"]), _ptr(rec))
         return rec
 
     def pose_graph_solve(self, fixed, edge_ij, node_ptr, node_edge, buf: Dict[str, torch.Tensor], preconditioner="jacobi",
@@ -1596,23 +1403,17 @@ class OvnEngine:
         """Enqueues `iterations` PCG iterations on the linearization in `buf` (ovn_pose_graph_solve); delta in buf["delta"], state in
         buf["ws"], status in the returned record tensor.  Never waits for the GPU."""
         n, e = int(fixed.shape[0]), int(edge_ij.shape[0])
+        system = (self._stream(), _ptr(fixed), n, _ptr(edge_ij), e, _ptr(node_ptr), _ptr(node_edge), _ptr(buf["blocks"]), _ptr(buf["grad"]),
+                  _ptr(buf["diag"]), _ptr(buf["dinv"]), _ptr(buf.get("chain")))
+        run = (float(lam), float(rtol), int(first_iteration), int(iterations), _ptr(buf["delta"]), _ptr(buf["ws"]), _ptr(buf["record"]))
         if preconditioner in ("loops", self.POSE_GRAPH_LOOPS):
             lp = self._pg_loops(buf, n, e - (n - 1), "pose_graph_solve")
-            with self._dev():
-                _lib.check(self.lib.ovn_pose_graph_solve_loops(
-                    self._h, self._stream(), _ptr(fixed), n, _ptr(edge_ij), e, _ptr(node_ptr), _ptr(node_edge), _ptr(buf["blocks"]),
-                    _ptr(buf["grad"]), _ptr(buf["diag"]), _ptr(buf["dinv"]), _ptr(buf.get("chain")), _ptr(lp), e - (n - 1), float(lam),
-                    float(rtol), int(first_iteration), int(iterations), _ptr(buf["delta"]), _ptr(buf["ws"]), _ptr(buf["record"])),
-                    "ovn_pose_graph_solve_loops")
+            self._call("ovn_pose_graph_solve_loops", *system, _ptr(lp), e - (n - 1), *run)
             return buf["record"]
         kind = self.POSE_GRAPH_PRECONDITIONERS.get(preconditioner, preconditioner)
         if not isinstance(kind, int):
             raise _lib.OvnError("pose_graph_solve: no preconditioner %r (jacobi, chain, loops)" % (preconditioner,))
-        with self._dev():
-            _lib.check(self.lib.ovn_pose_graph_solve(
-                self._h, self._stream(), _ptr(fixed), n, _ptr(edge_ij), e, _ptr(node_ptr), _ptr(node_edge), _ptr(buf["blocks"]),
-                _ptr(buf["grad"]), _ptr(buf["diag"]), _ptr(buf["dinv"]), _ptr(buf.get("chain")), kind, float(lam), float(rtol),
-                int(first_iteration), int(iterations), _ptr(buf["delta"]), _ptr(buf["ws"]), _ptr(buf["record"])), "ovn_pose_graph_solve")
+        self._call("ovn_pose_graph_solve", *system, kind, *run)
         return buf["record"]
 
     def _pg_loops(self, buf: Dict[str, torch.Tensor], n: int, n_loops: int, what: str) -> torch.Tensor:
@@ -1622,7 +1423,7 @@ class OvnEngine:
                                 % (what, self.POSE_GRAPH_MAX_LOOPS, n_loops))
         if buf.get("chain") is None or buf.get("loops") is None:
             raise _lib.OvnError("%s: the buffers were not made with loops=%d (pose_graph_buffers)" % (what, n_loops))
-        return self._pg_tensor("%s: buf['loops']" % what, buf["loops"], torch.float64, (nbytes // 8,))
+        return self._check(buf["loops"], "%s: buf['loops']" % what, torch.float64, (nbytes // 8,))
 
     def pose_graph_loops_prepare(self, poses, edge_ij, info, buf: Dict[str, torch.Tensor],
                                  record: Optional[torch.Tensor] = None, stages: int = 7) -> torch.Tensor:
@@ -1630,18 +1431,17 @@ class OvnEngine:
         (with Jacobians) that `buf` holds for `poses` (ovn_pose_graph_loops_prepare).  Returns the record tensor: slot 13 counts
         failed pivots, slot 14 the loop edges left out.  stages: 1 = scan, 2 = assembly, 4 = factorization, summed (a benchmark's knob)."""
         f64, n, e = torch.float64, int(poses.shape[0]), int(edge_ij.shape[0])
-        self._pg_tensor("pose_graph_loops_prepare: poses", poses, f64, (n, 4, 4))
-        self._pg_tensor("pose_graph_loops_prepare: edge_ij", edge_ij, torch.int32, (e, 2))
-        self._pg_tensor("pose_graph_loops_prepare: info", info, f64, (e, 6, 6))
+        what = "pose_graph_loops_prepare: "
+        self._check(poses, what + "poses", f64, (n, 4, 4))
+        self._check(edge_ij, what + "edge_ij", torch.int32, (e, 2))
+        self._check(info, what + "info", f64, (e, 6, 6))
         lp = self._pg_loops(buf, n, e - (n - 1), "pose_graph_loops_prepare")
-        self._pg_tensor("pose_graph_loops_prepare: buf['weight']", buf["weight"], f64, (e,))
-        self._pg_tensor("pose_graph_loops_prepare: buf['jac']", buf["jac"], f64, (e, 2, 6, 6))
-        self._pg_tensor("pose_graph_loops_prepare: buf['chain']", buf["chain"], f64, (n - 1, 2, 6, 6))
-        rec = self._pg_tensor("pose_graph_loops_prepare: record", buf["record"] if record is None else record, f64, (16,))
-        with self._dev():
-            _lib.check(self.lib.ovn_pose_graph_loops_prepare(
-                self._h, self._stream(), _ptr(poses), n, _ptr(edge_ij), _ptr(info), _ptr(buf["weight"]), _ptr(buf["jac"]), e, e - (n - 1),
-                _ptr(buf["chain"]), int(stages), _ptr(lp), _ptr(rec)), "ovn_pose_graph_loops_prepare")
+        self._check(buf["weight"], what + "buf['weight']", f64, (e,))
+        self._check(buf["jac"], what + "buf['jac']", f64, (e, 2, 6, 6))
+        self._check(buf["chain"], what + "buf['chain']", f64, (n - 1, 2, 6, 6))
+        rec = self._check(buf["record"] if record is None else record, what + "record", f64, (16,))
+        self._call("ovn_pose_graph_loops_prepare", self._stream(), _ptr(poses), n, _ptr(edge_ij), _ptr(info), _ptr(buf["weight"]),
+                   _ptr(buf["jac"]), e, e - (n - 1), _ptr(buf["chain"]), int(stages), _ptr(lp), _ptr(rec))
         return rec
 
     def pose_graph_loops_views(self, buf: Dict[str, torch.Tensor], n_nodes: int, n_loops: int) -> Dict[str, torch.Tensor]:
@@ -1663,25 +1463,22 @@ class OvnEngine:
         also takes the graph's incidence list node_ptr, node_edge (ovn_pose_graph_precondition_loops; lam is not used: the inverse
         is that of the undamped Hessian)."""
         n = int(vec.shape[0])
-        self._pg_tensor("pose_graph_precondition: vec", vec, torch.float64, (n, 6))
-        out = torch.zeros_like(vec) if out is None else self._pg_tensor("pose_graph_precondition: out", out, torch.float64, (n, 6))
+        what = "pose_graph_precondition: "
+        self._check(vec, what + "vec", torch.float64, (n, 6))
+        out = torch.zeros_like(vec) if out is None else self._check(out, what + "out", torch.float64, (n, 6))
         if preconditioner in ("loops", self.POSE_GRAPH_LOOPS):
-            self._pg_tensor("pose_graph_precondition: node_ptr", node_ptr, torch.int32, (n + 1,))
-            self._pg_tensor("pose_graph_precondition: node_edge", node_edge, torch.int32, None)
+            self._check(node_ptr, what + "node_ptr", torch.int32, (n + 1,))
+            self._check(node_edge, what + "node_edge", torch.int32)
             e = int(node_edge.shape[0]) // 2
             lp = self._pg_loops(buf, n, e - (n - 1), "pose_graph_precondition")
-            with self._dev():
-                _lib.check(self.lib.ovn_pose_graph_precondition_loops(
-                    self._h, self._stream(), n, e, e - (n - 1), _ptr(node_ptr), _ptr(node_edge), _ptr(buf["chain"]), _ptr(lp), _ptr(vec),
-                    _ptr(out), _ptr(buf["ws"])), "ovn_pose_graph_precondition_loops")
+            self._call("ovn_pose_graph_precondition_loops", self._stream(), n, e, e - (n - 1), _ptr(node_ptr), _ptr(node_edge),
+                       _ptr(buf["chain"]), _ptr(lp), _ptr(vec), _ptr(out), _ptr(buf["ws"]))
             return out
         kind = self.POSE_GRAPH_PRECONDITIONERS.get(preconditioner, preconditioner)
         if not isinstance(kind, int):
             raise _lib.OvnError("pose_graph_precondition: no preconditioner %r (jacobi, chain, loops)" % (preconditioner,))
-        with self._dev():
-            _lib.check(self.lib.ovn_pose_graph_precondition(self._h, self._stream(), n, kind, float(lam), _ptr(buf.get("dinv")),
-                                                            _ptr(buf.get("chain")), _ptr(vec), _ptr(out), _ptr(buf["ws"])),
-                       "ovn_pose_graph_precondition")
+        self._call("ovn_pose_graph_precondition", self._stream(), n, kind, float(lam), _ptr(buf.get("dinv")), _ptr(buf.get("chain")),
+                   _ptr(vec), _ptr(out), _ptr(buf["ws"]))
         return out
 
     POSE_GRAPH_COV_FRAMES = {"local": 0, "position": 1}      # OVN_POSE_GRAPH_COV_LOCAL, OVN_POSE_GRAPH_COV_POSITION
@@ -1699,50 +1496,46 @@ class OvnEngine:
         counts the ids outside [0, N), whose blocks are NaN; slot 7 is set, and cov left as it was, when a pivot had failed."""
         n, nl = int(poses.shape[0]), int(n_loops)
         f64 = torch.float64
+        what = "pose_graph_marginals: "
         if frame not in self.POSE_GRAPH_COV_FRAMES:
             raise _lib.OvnError("pose_graph_marginals: no frame %r (local, position)" % (frame,))
-        self._pg_tensor("pose_graph_marginals: poses", poses, f64, (n, 4, 4))
-        ids = self._pg_tensor("pose_graph_marginals: node_ids", node_ids, torch.int32, None)
+        self._check(poses, what + "poses", f64, (n, 4, 4))
+        ids = self._check(node_ids, what + "node_ids", torch.int32)
         if ids.dim() != 1 or ids.shape[0] < 1:
             raise _lib.OvnError("pose_graph_marginals: node_ids must be (K,) with K >= 1, got %s" % (tuple(ids.shape),))
         k = int(ids.shape[0])
         nbytes = self.pose_graph_marginals_bytes(n, nl, k)
         if nbytes == 0:
             raise _lib.OvnError("pose_graph_marginals: %d nodes, %d loop edges, %d queried nodes are outside the limits" % (n, nl, k))
-        self._pg_tensor("pose_graph_marginals: buf['chain']", buf.get("chain"), f64, (n - 1, 2, 6, 6))
+        self._check(buf.get("chain"), what + "buf['chain']", f64, (n - 1, 2, 6, 6))
         lp = self._pg_loops(buf, n, nl, "pose_graph_marginals") if nl > 0 else None
-        rec = self._pg_tensor("pose_graph_marginals: record", buf["record"] if record is None else record, f64, (16,))
-        cov = torch.zeros((k, 6, 6), dtype=f64, device=self.device) if cov is None else \
-            self._pg_tensor("pose_graph_marginals: cov", cov, f64, (k, 6, 6))
-        ws = torch.empty(nbytes // 8, dtype=f64, device=self.device) if ws is None else \
-            self._pg_tensor("pose_graph_marginals: ws", ws, f64, None)
+        rec = self._check(buf["record"] if record is None else record, what + "record", f64, (16,))
+        cov = torch.zeros((k, 6, 6), dtype=f64, device=self.device) if cov is None else self._check(cov, what + "cov", f64, (k, 6, 6))
+        ws = torch.empty(nbytes // 8, dtype=f64, device=self.device) if ws is None else self._check(ws, what + "ws", f64)
         if ws.numel() * 8 < nbytes:
             raise _lib.OvnError("pose_graph_marginals: ws holds %d bytes, %d are needed" % (ws.numel() * 8, nbytes))
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.ovn_pose_graph_marginals(
-                self._h, self._stream(), _ptr(poses), n, n - 1 + nl, nl, _ptr(buf["chain"]), _ptr(lp), _ptr(ids), k,
-                self.POSE_GRAPH_COV_FRAMES[frame], _ptr(cov), _ptr(ws), _ptr(rec)), "ovn_pose_graph_marginals")
+        self._call("ovn_pose_graph_marginals", self._stream(), _ptr(poses), n, n - 1 + nl, nl, _ptr(buf["chain"]), _ptr(lp), _ptr(ids), k,
+                   self.POSE_GRAPH_COV_FRAMES[frame], _ptr(cov), _ptr(ws), _ptr(rec))
         return cov
 
     def pose_graph_retract(self, poses: torch.Tensor, fixed: torch.Tensor, buf: Dict[str, torch.Tensor],
                            out: Optional[torch.Tensor] = None, record: Optional[torch.Tensor] = None) -> torch.Tensor:
         """out (N,4,4) = T_i Exp(delta_i) with delta = buf["delta"] (ovn_pose_graph_retract); |delta|_inf goes to slot 12 of the record."""
         n = int(poses.shape[0])
-        self._pg_tensor("pose_graph_retract: poses", poses, torch.float64, (n, 4, 4))
-        self._pg_tensor("pose_graph_retract: fixed", fixed, torch.uint8, (n,))
-        self._pg_tensor("pose_graph_retract: buf['delta']", buf["delta"], torch.float64, (n, 6))
-        out = torch.empty_like(poses) if out is None else self._pg_tensor("pose_graph_retract: out", out, torch.float64, (n, 4, 4))
+        what = "pose_graph_retract: "
+        self._check(poses, what + "poses", torch.float64, (n, 4, 4))
+        self._check(fixed, what + "fixed", torch.uint8, (n,))
+        self._check(buf["delta"], what + "buf['delta']", torch.float64, (n, 6))
+        out = torch.empty_like(poses) if out is None else self._check(out, what + "out", torch.float64, (n, 4, 4))
         if out.data_ptr() == poses.data_ptr():
             raise _lib.OvnError("pose_graph_retract: out must not be poses")
         rec = buf["record"] if record is None else record
-        with self._dev():
-            _lib.check(self.lib.ovn_pose_graph_retract(self._h, self._stream(), _ptr(poses), _ptr(fixed), _ptr(buf["delta"]), n,
-                                                       _ptr(out), _ptr(buf["ws"]), _ptr(rec)), "ovn_pose_graph_retract")
+        self._call("ovn_pose_graph_retract", self._stream(), _ptr(poses), _ptr(fixed), _ptr(buf["delta"]), n, _ptr(out), _ptr(buf["ws"]),
+                   _ptr(rec))
         return out
 
     def selftest(self) -> None:
-        with self._dev():
-            _lib.check(self.lib.ovn_selftest(self._h), "ovn_selftest")
+        self._call("ovn_selftest")
 
     def workspace_bytes(self) -> int:
         return int(self.lib.ovn_workspace_bytes(self._h))

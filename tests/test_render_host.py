@@ -268,8 +268,7 @@ def test_export_is_declared_bound_and_additive():
     code = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     assert re.search(r"\bint\s+ovn_render_scans\s*\(", code)
     assert re.search(r"#define\s+OVN_ABI_VERSION\s+11\b", code) and _lib.ABI_VERSION == 11
-    n_args = len(re.search(r"ovn_render_scans\s*\((.*?)\)\s*;", code, flags=re.S).group(1).split(","))
-    assert "ovn_render_scans" in _lib.SIGNATURES and len(_lib.SIGNATURES["ovn_render_scans"][1]) == n_args
+    assert "ovn_render_scans" in _lib.SIGNATURES          # (its types and arity against the header: tests/test_abi.py)
     _lib.build()
     lib = _lib.load()
     assert lib.ovn_abi_version() == 11 and hasattr(lib, "ovn_render_scans")
