@@ -1,4 +1,4 @@
-"""ctypes binding of libovn_hip.so (C ABI declared in include/ovn_hip.h).
+"""ctypes binding of libovn_hip.so (C ABI declared in include/ovn_hip.h, with additions in include/ovn_hip_deskew.h).
 
 There is NO fallback: if the shared library is missing or a call fails, an exception is raised.
 """
@@ -132,6 +132,11 @@ SIGNATURES = {
     "ovn_selftest": (C.c_int, [_vp]),
 }
 
+# additions declared in include/ovn_hip_deskew.h, one to one (tests/test_deskew_host.py); the ABI version is that of SIGNATURES
+EXT_SIGNATURES = {
+    "ovn_deskew": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, C.c_double, C.c_int, _vp, C.c_double, _vp]),
+}
+
 
 class OvnError(Exception):
     pass
@@ -165,7 +170,7 @@ def load() -> C.CDLL:
         raise OvnError("%s not found: the HIP extension is not built. Run `python -c 'import __graft_entry__ as g; "
                        "g.build()'` (or `make -C overlapnet_amd/csrc`). There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

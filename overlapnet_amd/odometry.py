@@ -6,6 +6,7 @@
     poses, results, volume = estimate_poses(engine, points, offsets)  # both in a row; `volume.mesh()` is the map's mesh
     odo = RollingTsdfOdometry(engine, extent=(120, 120, 20), voxel=0.2)   # the same tracker in a window that follows the sensor (section 36)
     poses, results, volume = estimate_poses(engine, points, offsets, window=120.0)    # online: no first pass, any drive length
+    odo = TsdfOdometry(engine, lo, hi, voxel=0.2, deskew=dict(t_ref=0.5)); odo.track(scan, times=fractions)   # raw sweeps (section 37)
 
 The pieces are HIP kernels that exist on their own: `ovn_project` (range, vertex and normal images), `ovn_tsdf_raycast` (the model seen
 from the predicted pose), `ovn_icp_register` (the alignment of two such images) and `ovn_tsdf_integrate` (the model).  This module is
@@ -118,12 +119,25 @@ class TsdfOdometry(object):
     The device buffers hold three images each: slot 0 the virtual scan, slot 1 the current scan, slot 2 the previous scan.  Both
     registrations of a frame run in one launch, the choice between them is made on the device, and a frame reads back one pose and one
     stats row.  use_bricks=True rebuilds the brick mask of `ovn_tsdf_bricks` before every view; for the single view of a frame that
-    costs more than it saves, so it is off by default."""
+    costs more than it saves, so it is off by default.
+
+    deskew: None (the default) takes every scan as a snapshot and makes the launches it always made.  A dict
+    (`deskew.check_config`: t_ref, and start_azimuth with clockwise when the scans come without per-point times) takes the scans as RAW
+    sweeps: scan k >= 2 is moved into the sensor frame of fraction t_ref of its sweep (`deskew.deskew_scans`) before it is projected,
+    under the twist xi = Log(T_{k-2}^-1 T_{k-1}), the step `predict` repeats.  Scans 0 and 1 have no motion estimate when they are
+    registered: they are registered and fused as they come.  When scan 2 arrives the first step is known, and before anything else the
+    model is rebuilt from scans 0 and 1 deskewed by it (the volume is reset and the two are fused again at their poses; their raw
+    points stay on the device until then).  Without that the model keeps a bent seed, and a deskewed scan registered onto a bent model
+    comes out WORSE than a bent scan on a bent model, which at least share their distortion (measured: DESIGN.md section 37).  The
+    pose of a scan is the sensor's pose at fraction t_ref of its sweep.  deskew_passes=2 deskews scan k >= 1 once more before it is
+    FUSED, by the step Log(T_{k-1}^-1 T_k) its registration just found, and projects it again; there is no second registration.  The
+    step comes from the pose the frame's one read-back brought (the read-back precedes the fusion), so a frame still reads back once;
+    the twist travels host to device."""
 
     def __init__(self, engine, lo, hi, voxel: float, trunc: Optional[float] = None, proj_h: int = 64, proj_w: int = 900,
                  fov_up: float = 3.0, fov_down: float = -25.0, max_range: float = 50.0, min_range: float = 0.5,
                  min_fitness: Optional[float] = None, max_weight: float = 64.0, min_weight: float = 1.0, use_bricks: bool = False,
-                 **icp_params):
+                 deskew: Optional[dict] = None, deskew_passes: int = 1, **icp_params):
         from .tsdf import TsdfVolume, check_march
         if int(proj_h) < 1 or int(proj_w) < 1:
             raise ValueError("proj_h and proj_w must be >= 1, got %r, %r" % (proj_h, proj_w))
@@ -133,6 +147,12 @@ class TsdfOdometry(object):
         bad = [k for k in icp_params if k not in ("iterations", "max_dist", "cos_min", "huber", "min_inliers")]
         if bad:
             raise ValueError("unknown registration parameters %s" % bad)
+        from .deskew import check_config
+        self.deskew = check_config(deskew)
+        if deskew_passes not in (1, 2):
+            raise ValueError("deskew_passes must be 1 or 2, got %r" % (deskew_passes,))
+        self.deskew_passes = int(deskew_passes)
+        self._seed: list = []                     # with deskew: (raw scan, times) of scans 0 and 1 on the device, until scan 2 arrives
         self.volume = self._make_volume(engine, lo, hi, voxel, trunc, max_weight, float(max_range))   # refuses bad bounds before the GPU
         import torch
         self.engine = engine
@@ -178,6 +198,32 @@ class TsdfOdometry(object):
         self.vertex[1].copy_(m["vertex"][0])
         self.normal[1].copy_(m["normal"][0])
 
+    def _deskewed(self, pts, times, t_from: np.ndarray, t_to: np.ndarray):
+        """The raw scan `pts` (a device tensor) under the twist of the step t_from -> t_to, as a new device tensor."""
+        import torch
+        from .deskew import deskew_scans, se3_log, source_of
+        xi = se3_log(np.linalg.inv(t_from) @ t_to)
+        self._offs[1] = int(pts.shape[0])
+        return deskew_scans(self.engine, pts, self._offs, torch.from_numpy(xi[None]).to(self.engine.device),
+                            t_ref=self.deskew["t_ref"], **source_of(self.deskew, times, "track"))
+
+    def _rebuild_seed(self) -> None:
+        """Before scan 2 is tracked: the model, which so far holds scans 0 and 1 as they came, is rebuilt from them deskewed by the
+        first step Log(T_0^-1 T_1), the motion estimate that now exists for both.  Left as they came they would bend the model every
+        deskewed scan is registered onto.  Slot 2 ends up holding scan 1 as it was fused."""
+        import torch
+        seed, self._seed = self._seed, []
+        fused = [r.source != SOURCE_PREDICTION for r in self.results[:2]]
+        self.volume.reset()
+        for (raw, times), pose, was_fused in zip(seed, self.poses[:2], fused):
+            if raw is None or not was_fused:
+                continue
+            self._project(self._deskewed(raw, times, self.poses[0], self.poses[1]))
+            self._fuse(torch.from_numpy(np.ascontiguousarray(pose[None])).to(self.engine.device))
+        if seed[1][0] is not None and fused[1]:
+            for t in (self.range, self.vertex, self.normal):
+                t[2].copy_(t[1])
+
     def _fuse(self, pose_dev) -> None:
         up, down, rmax = self.sensor
         v = self.volume
@@ -185,9 +231,10 @@ class TsdfOdometry(object):
                                    **v._window())
         v.n_scans += 1
 
-    def track(self, points, first_pose=None) -> TrackResult:
+    def track(self, points, first_pose=None, times=None) -> TrackResult:
         """One scan, (N,4) float32 sensor-frame points (host array or device tensor).  first_pose: the pose of the FIRST scan (the
-        identity by default); refused on a later one."""
+        identity by default); refused on a later one.  times: with `deskew`, the (N,) float32 time fraction of every point within
+        the sweep (host array or device tensor); without them the deskew dict's azimuth parameters give the times."""
         import torch
         shape = tuple(points.shape)
         if len(shape) != 2 or shape[1] != 4:
@@ -195,6 +242,22 @@ class TsdfOdometry(object):
         if self.poses and first_pose is not None:
             raise ValueError("first_pose belongs to the first scan; %d are tracked" % len(self.poses))
         dev = self.engine.device
+        raw = None                                   # with deskew: the raw scan on the device, for scans that have a motion estimate
+        if self.deskew is None:
+            if times is not None:
+                raise ValueError("times belong to a tracker built with deskew=")
+        else:
+            from .deskew import source_of, times_tensor
+            source_of(self.deskew, times, "track")                                       # refuses a scan without a time source
+            if times is not None:
+                times = times_tensor(self.engine, times, shape[0], "track")
+            if shape[0] > 0:
+                raw = points if isinstance(points, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(points, np.float32))
+                raw = raw.to(dev, torch.float32).contiguous()
+            if len(self.poses) < 2:
+                self._seed.append((raw, times))                                          # scans 0 and 1, kept until scan 2 arrives
+            elif len(self.poses) == 2:
+                self._rebuild_seed()
         up, down, rmax = self.sensor
         if not self.poses:
             pose = np.eye(4) if first_pose is None else np.array(first_pose, np.float64).reshape(4, 4)
@@ -207,6 +270,8 @@ class TsdfOdometry(object):
         else:
             t_last = self.poses[-1]
             t_pred = predict(self.poses[-2], t_last) if len(self.poses) > 1 else t_last.copy()
+            if raw is not None:
+                points = self._deskewed(raw, times, self.poses[-2], t_last) if len(self.poses) > 1 else raw
             self._project(points)
             both = torch.from_numpy(np.stack([t_pred, t_last])).to(dev)                      # what each registration's result multiplies
             self._before_view(t_pred)
@@ -231,6 +296,8 @@ class TsdfOdometry(object):
             valid = int(st[3])
             res = TrackResult(pose, _SOURCES[which], int(st[0]), (st[2] / valid) if valid > 0 else 0.0, float(st[4]), int(st[2]))
             if which != 2:
+                if raw is not None and self.deskew_passes == 2:
+                    self._project(self._deskewed(raw, times, t_last, pose))               # the images that are fused and kept in slot 2
                 self._fuse(chosen.reshape(1, 4, 4).contiguous())
         for t in (self.range, self.vertex, self.normal):
             t[2].copy_(t[1])
@@ -276,32 +343,42 @@ class RollingTsdfOdometry(TsdfOdometry):
 def estimate_poses(engine, points, offsets, voxel: float = 0.2, trunc: Optional[float] = None, proj_h: int = 64, proj_w: int = 900,
                    fov_up: float = 3.0, fov_down: float = -25.0, max_range: float = 50.0, min_range: float = 0.5, below: float = 5.0,
                    above: float = 15.0, chunk: int = 64, min_fitness: Optional[float] = None, window=None, shift: int = 8,
-                   **icp_params):
+                   deskew: Optional[dict] = None, times=None, deskew_passes: int = 1, **icp_params):
     """The poses of a drive from its scans: `frame_to_frame` gives a first trajectory, its `bounds_from_poses` the volume's box, and
     `TsdfOdometry` tracks the drive against the volume it builds.  A box over 2^31 - 1 samples is refused with `volume_shape`'s message,
     which names the voxel that fits (the volume does not follow the sensor).  -> (poses (n,4,4), [TrackResult] * n, the TsdfVolume).
     window: metres, 3 numbers or one for x and y with below + above for z -- `RollingTsdfOdometry` tracks the drive in a window of
     that size that follows the sensor, `shift` voxels at a time: no `frame_to_frame` pass, no limit on the drive's extent, and the
-    volume returned is the RollingTsdfVolume, whose `mesh()` is the whole drive's."""
+    volume returned is the RollingTsdfVolume, whose `mesh()` is the whole drive's.
+    deskew, deskew_passes: the trackers' (DESIGN.md section 37), with times (total,) float32, one fraction per row of `points`, where
+    the deskew dict names no azimuth parameters.  `frame_to_frame` does not deskew: its trajectory only sizes the box."""
     from .tsdf import volume_shape
     offs = _check_scans(points, offsets)
     n = offs.shape[0] - 1
     if n < 1:
         raise ValueError("estimate_poses needs at least one scan")
+    if times is not None:
+        if deskew is None:
+            raise ValueError("times belong to deskew=")
+        if tuple(times.shape) != (int(points.shape[0]),):
+            raise ValueError("times must hold one fraction per point, (%d,), got %s" % (int(points.shape[0]), tuple(times.shape)))
+    scan_times = lambda s: {} if times is None else dict(times=times[int(offs[s]):int(offs[s + 1])])
+    motion = dict(deskew=deskew, deskew_passes=deskew_passes)
     sensor = dict(proj_h=proj_h, proj_w=proj_w, fov_up=fov_up, fov_down=fov_down, max_range=max_range)
     if window is not None:
         ext = np.asarray(window, np.float64).reshape(-1)
         if ext.shape[0] == 1:
             ext = np.array([ext[0], ext[0], float(below) + float(above)])
         odo = RollingTsdfOdometry(engine, ext, voxel, trunc=trunc, shift=shift, min_range=min_range, min_fitness=min_fitness, **sensor,
-                                  **icp_params)
+                                  **motion, **icp_params)
         for s in range(n):
-            odo.track(points[int(offs[s]):int(offs[s + 1])])
+            odo.track(points[int(offs[s]):int(offs[s + 1])], **scan_times(s))
         return np.stack(odo.poses), odo.results, odo.volume
     first, _ = frame_to_frame(engine, points, offsets, chunk=chunk, **sensor, **icp_params)
     lo, hi = bounds_from_poses(first, max_range, below, above)
     volume_shape(lo, hi, voxel)
-    odo = TsdfOdometry(engine, lo, hi, voxel, trunc=trunc, min_range=min_range, min_fitness=min_fitness, **sensor, **icp_params)
+    odo = TsdfOdometry(engine, lo, hi, voxel, trunc=trunc, min_range=min_range, min_fitness=min_fitness, **sensor, **motion,
+                       **icp_params)
     for s in range(n):
-        odo.track(points[int(offs[s]):int(offs[s + 1])])
+        odo.track(points[int(offs[s]):int(offs[s + 1])], **scan_times(s))
     return np.stack(odo.poses), odo.results, odo.volume

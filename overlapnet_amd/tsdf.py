@@ -147,10 +147,22 @@ class TsdfVolume(object):
         self.n_scans += shape[0]
 
     def integrate_scans(self, points, offsets, poses, proj_h: int = 64, proj_w: int = 900, fov_up: float = 3.0,
-                        fov_down: float = -25.0, max_range: float = 50.0, chunk: int = 64) -> None:
+                        fov_down: float = -25.0, max_range: float = 50.0, chunk: int = 64, deskew=None, twists=None, times=None) -> None:
         """Projects raw scans -- `points` (total,4) float32 of concatenated scans, `offsets` (n+1) int64 -- with `engine.project` and
-        fuses them, `chunk` scans at a time."""
+        fuses them, `chunk` scans at a time.  deskew: None, or the dict of `deskew.check_config` -- the scans are raw sweeps and each
+        chunk is moved into the sensor frames of fraction t_ref (`deskew.deskew_scans`) ahead of its projection,
+        under `twists` (n,6), by default `deskew.twists_from_poses(poses)`; `poses` are then the sensor's at t_ref.  times: (total,)
+        float32, one fraction per row of `points`, where the dict names no azimuth parameters."""
         import torch
+        from . import deskew as _deskew
+        cfg = _deskew.check_config(deskew)
+        if cfg is None and (twists is not None or times is not None):
+            raise ValueError("twists and times belong to deskew=")
+        if cfg is not None:
+            source = _deskew.source_of(cfg, times, "integrate_scans")
+            if times is not None and tuple(times.shape) != (int(points.shape[0]),):
+                raise ValueError("integrate_scans: times must hold one fraction per point, (%d,), got %s"
+                                 % (int(points.shape[0]), tuple(times.shape)))
         self._check_sensor(max_range)
         offs = np.asarray(offsets.cpu() if isinstance(offsets, torch.Tensor) else offsets, np.int64).reshape(-1)
         n = offs.shape[0] - 1
@@ -168,9 +180,22 @@ class TsdfVolume(object):
         pts = pts.to(dev, torch.float32).contiguous()
         d_offs = torch.from_numpy(offs).to(dev)
         poses = poses if isinstance(poses, torch.Tensor) else np.asarray(poses, np.float64)
+        if cfg is not None:
+            if times is not None:
+                source = dict(times=_deskew.times_tensor(self.engine, times, int(pts.shape[0]), "integrate_scans"))
+            if twists is None:
+                twists = _deskew.twists_from_poses(poses.cpu().numpy() if isinstance(poses, torch.Tensor) else poses)
+            if not isinstance(twists, torch.Tensor):
+                twists = torch.from_numpy(np.ascontiguousarray(np.asarray(twists, np.float64)))
+            if tuple(twists.shape) != (n, 6):
+                raise ValueError("twists must be (%d,6) for the %d scans of offsets, got %s" % (n, n, tuple(twists.shape)))
+            twists = twists.to(dev, torch.float64).contiguous()
+            raw, pts = pts, torch.empty_like(pts)            # every chunk writes its own rows of `pts`, which is never the caller's tensor
         for a in range(0, n, int(chunk)):
             b = min(n, a + int(chunk))
             max_points = int(np.diff(offs[a:b + 1]).max())
+            if cfg is not None:
+                _deskew.deskew_scans(self.engine, raw, d_offs[a:b + 1], twists[a:b], t_ref=cfg["t_ref"], out=pts, **source)
             r = self.engine.project(pts, d_offs[a:b + 1], max_points, int(proj_h), int(proj_w), fov_up, fov_down, max_range,
                                     want=("range",))["range"]
             self.engine.tsdf_integrate(self.tsdf, self.weight, self.origin, self.voxel, self.trunc, self.max_weight, r, poses[a:b],

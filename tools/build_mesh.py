@@ -2,14 +2,17 @@
 distance volume on the GPU and its zero level set extracted (`overlapnet_amd.tsdf`).
 
     python tools/build_mesh.py --config network.json --scans sequences/07/velodyne --poses poses/07.txt --calib sequences/07/calib.txt \\
-        --voxel 0.2 --out site.ply [--bounds X0 Y0 Z0 X1 Y1 Z1] [--every N]
+        --voxel 0.2 --out site.ply [--bounds X0 Y0 Z0 X1 Y1 Z1] [--every N] [--deskew --times DIR | --deskew --start-azimuth DEG --clockwise]
 
 The config is the `network.yml` dict `Infer` takes (JSON, or YAML when PyYAML is installed): its `model.inputShape` is the range image
 the scans are projected into.  The poses file holds one pose per line (12 numbers, a 3 x 4 matrix) or is an npz of (n,4,4) matrices,
 read as `tools/build_training_set.py` reads it.  With --calib they are camera poses and are moved into the LiDAR frame of the first
 scan with the calibration's `Tr:` line; without it they are taken as sensor-to-world poses as they stand.  Without --bounds the
 volume is the poses' bounding box grown by --max-range (and by --below / --above in z); a volume over 2^31 - 1 samples is refused with
-the voxel size that would fit.  Prints one JSON line."""
+the voxel size that would fit.  --deskew takes the scans as RAW sweeps: each is moved into the sensor frame of fraction --t-ref of its
+sweep under the twist of the step that led to its pose (of ALL the poses, whatever --every says) before it is
+projected, and the poses are taken as the sensor's at that fraction, which is what `tools/odometry.py --deskew` writes.  Prints one JSON
+line."""
 import argparse
 import json
 import os
@@ -50,7 +53,10 @@ def main(argv=None):
     ap.add_argument("--fov-up", type=float, default=3.0)
     ap.add_argument("--fov-down", type=float, default=-25.0)
     ap.add_argument("--max-range", type=float, default=50.0)
+    from overlapnet_amd import deskew as motion
+    motion.add_arguments(ap)
     a = ap.parse_args(argv)
+    deskew = motion.config_from_args(ap, a)
 
     cfg = load_config(a.config)
     h, w = (int(v) for v in cfg["model"]["inputShape"][:2])
@@ -62,6 +68,7 @@ def main(argv=None):
         raise SystemExit("%d scans in %s but %d poses in %s" % (len(paths), a.scans, len(poses), a.poses))
     if a.every < 1 or a.chunk < 1:
         raise SystemExit("--every and --chunk must be >= 1")
+    twists = motion.twists_from_poses(poses)[::a.every] if deskew is not None else None
     paths, poses = paths[::a.every], poses[::a.every]
     if not paths:
         raise SystemExit("no .bin scans in %s" % a.scans)
@@ -81,8 +88,16 @@ def main(argv=None):
             scans = [np.fromfile(p, dtype=np.float32).reshape((-1, 4)) for p in paths[s:s + a.chunk]]
             offsets = np.zeros(len(scans) + 1, np.int64)
             offsets[1:] = np.cumsum([c.shape[0] for c in scans])
+            extra = {}
+            if deskew is not None:
+                extra = dict(deskew=deskew, twists=twists[s:s + a.chunk])
+                if a.times is not None:
+                    try:
+                        extra["times"] = motion.read_times(a.times, paths[s:s + a.chunk], [c.shape[0] for c in scans])
+                    except ValueError as e:
+                        raise SystemExit("build_mesh: %s" % e)
             vol.integrate_scans(np.concatenate(scans), offsets, poses[s:s + a.chunk], proj_h=h, proj_w=w, fov_up=a.fov_up,
-                                fov_down=a.fov_down, max_range=a.max_range, chunk=a.chunk)
+                                fov_down=a.fov_down, max_range=a.max_range, chunk=a.chunk, **extra)
         mesh = vol.mesh(a.min_weight)
         mesh.to_ply(a.out)
         print(json.dumps({"out": a.out, "scans": len(paths), "volume": [vol.nx, vol.ny, vol.nz], "voxel": vol.voxel, "trunc": vol.trunc,

@@ -1,7 +1,7 @@
 """Raw scans -> the sensor poses the mapping tools take: LiDAR odometry on the GPU (`overlapnet_amd.odometry`).
 
     python tools/odometry.py --config network.json --scans sequences/07/velodyne --out poses.txt [--mesh site.ply] [--voxel 0.2] \\
-        [--frame-to-frame-only] [--window 120]
+        [--frame-to-frame-only] [--window 120] [--deskew --times DIR | --deskew --start-azimuth DEG --clockwise] [--deskew-passes 2]
 
 Every scan is registered onto its predecessor (one launch per chunk of pairs); that trajectory sizes a TSDF volume, and the drive is
 then tracked against the volume it builds: each scan is registered onto a ray-cast view of the model at its predicted pose and fused.
@@ -9,7 +9,9 @@ then tracked against the volume it builds: each scan is registered onto a ray-ca
 sensor, and what leaves it is meshed on the way.  The poses file holds one KITTI pose line per scan (12 numbers, sensor to world in the
 sensor frame, the first pose the identity): the file `tools/build_mesh.py --poses` reads without --calib.  --mesh also writes the tracked
 volume's zero level set.  The config is the `network.yml` dict `Infer` takes; its `model.inputShape` is the range image the scans are
-projected into.  Prints one JSON line."""
+projected into.  --deskew takes the scans as RAW sweeps and undoes the sensor's motion within each while tracking (DESIGN.md section
+37); each pose is then the sensor's at fraction --t-ref of its sweep, and `tools/build_mesh.py --deskew` fuses the same scans at them.
+Prints one JSON line."""
 import argparse
 import json
 import os
@@ -42,7 +44,14 @@ def main(argv=None):
     ap.add_argument("--fov-down", type=float, default=-25.0)
     ap.add_argument("--max-range", type=float, default=50.0)
     ap.add_argument("--min-range", type=float, default=0.5, help="where a ray of the model's view starts")
+    from overlapnet_amd import deskew as motion
+    motion.add_arguments(ap)
+    ap.add_argument("--deskew-passes", type=int, default=1, choices=(1, 2), help="2: deskew each scan again, by the step its "
+                    "registration found, before it is fused")
     a = ap.parse_args(argv)
+    deskew = motion.config_from_args(ap, a)
+    if deskew is not None and a.frame_to_frame_only:
+        ap.error("--deskew belongs to the tracker: drop --frame-to-frame-only")
 
     cfg = load_config(a.config)
     h, w = (int(v) for v in cfg["model"]["inputShape"][:2])
@@ -57,6 +66,12 @@ def main(argv=None):
     offsets = np.zeros(len(scans) + 1, np.int64)
     offsets[1:] = np.cumsum([c.shape[0] for c in scans])
     points = np.concatenate(scans)
+    times = None
+    if a.times is not None:
+        try:
+            times = motion.read_times(a.times, paths, [c.shape[0] for c in scans])
+        except ValueError as e:
+            raise SystemExit("odometry: %s" % e)
 
     from overlapnet_amd import odometry
     from overlapnet_amd.engine import OvnEngine
@@ -72,11 +87,14 @@ def main(argv=None):
             try:
                 poses, results, vol = odometry.estimate_poses(eng, points, offsets, voxel=a.voxel, trunc=a.trunc, min_range=a.min_range,
                                                               below=a.below, above=a.above, chunk=a.chunk, min_fitness=a.min_fitness,
-                                                              window=a.window, **sensor)
+                                                              window=a.window, deskew=deskew, times=times,
+                                                              deskew_passes=a.deskew_passes, **sensor)
             except ValueError as e:
                 raise SystemExit("odometry: %s" % e)
             line.update(mode="frame_to_model", volume=[vol.nx, vol.ny, vol.nz], voxel=vol.voxel,
                         sources={s: int(sum(r.source == s for r in results)) for s in ("first", "model", "frame", "prediction")})
+            if deskew is not None:
+                line.update(deskew=dict(deskew, passes=a.deskew_passes, times=a.times))
             if a.window is not None:
                 line.update(window_m=a.window, window_shifts=vol.n_shifts)
             if a.mesh:

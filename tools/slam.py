@@ -2,7 +2,8 @@
 (`overlapnet_amd.pose_graph`).
 
     python tools/slam.py --config network.json --scans sequences/07/velodyne --out poses.txt [--poses odometry.txt] [--mesh site.ply] \\
-        --overlap-thres 0.3 --min-fitness 0.5 --max-rms none --odom-sigma 0.05 0.01 --loop-sigma 0.1 0.02 --huber 1.5
+        --overlap-thres 0.3 --min-fitness 0.5 --max-rms none --odom-sigma 0.05 0.01 --loop-sigma 0.1 0.02 --huber 1.5 \\
+        [--deskew --times DIR | --deskew --start-azimuth DEG --clockwise]
 
   1  poses: `odometry.estimate_poses` on the scans, or the KITTI pose lines of --poses (12 numbers per line, sensor frame)
   2  candidates: `Infer` on the raw scans (`scan_folder` = --scans, frames 000000.bin ...): `cache_frames`, then per frame
@@ -11,6 +12,8 @@
   4  graph: the odometry steps and the accepted loop closures, `PoseGraph.optimize`
   5  --out: the optimized poses (`odometry.write_poses`); --mesh: the scans re-fused at them (`TsdfVolume`); --covariances: the
      optimized graph's marginal pose covariances (`PoseGraph.marginals`, `lcd.write_covariances`)
+--deskew takes the scans as RAW sweeps: step 1 tracks with motion compensation, and --mesh deskews every scan
+by the optimized poses' own steps before it is fused.  Steps 2 and 3 see the scans as they are on disk.
 --gate-sigma N narrows step 2 to the frames inside the N-sigma ellipse of dead reckoning's covariance; it has no default value.
 
 --overlap-thres, --min-fitness, --max-rms, --odom-sigma, --loop-sigma and --huber have no defaults: no acceptance threshold or noise
@@ -70,7 +73,10 @@ def parse(argv=None):
                     "one line of 36 numbers per scan: the covariance file of the reference's loop-closure demo")
     ap.add_argument("--gate-sigma", type=float, default=None, help="for frame k take only candidates inside the N-sigma x, y ellipse of "
                     "the odometry-only graph's marginal covariance at k (with --min-gap); not given: every earlier frame")
+    from overlapnet_amd import deskew as motion
+    motion.add_arguments(ap)
     a = ap.parse_args(argv)
+    a.deskew_config = motion.config_from_args(ap, a)
     if a.min_gap < 1 or a.top_k < 1 or a.batch < 1:
         ap.error("--min-gap, --top-k and --batch must be >= 1")
     if a.gate_sigma is not None and not a.gate_sigma > 0.0:
@@ -93,7 +99,13 @@ def main(argv=None):
     offsets[1:] = np.cumsum([c.shape[0] for c in scans])
     points = np.concatenate(scans)
 
-    from overlapnet_amd import lcd, odometry, pose_graph, tsdf
+    from overlapnet_amd import deskew as motion, lcd, odometry, pose_graph, tsdf
+    times = None
+    if a.times is not None:
+        try:
+            times = motion.read_times(a.times, [os.path.join(a.scans, f) for f in names], [c.shape[0] for c in scans])
+        except ValueError as e:
+            raise SystemExit("slam: %s" % e)
     from overlapnet_amd.infer import Infer
     t0 = time.time()
     infer = Infer(cfg)
@@ -104,7 +116,8 @@ def main(argv=None):
         if poses.shape[0] != n:
             raise SystemExit("%s holds %d poses for %d scans" % (a.poses, poses.shape[0], n))
     else:
-        poses, _, _ = odometry.estimate_poses(eng, points, offsets, voxel=a.voxel, window=a.window, **sensor)
+        poses, _, _ = odometry.estimate_poses(eng, points, offsets, voxel=a.voxel, window=a.window, deskew=a.deskew_config, times=times,
+                                              **sensor)
     line = {"out": a.out, "scans": n, "odometry_seconds": round(time.time() - t0, 3)}
 
     infer.cache_frames(n)
@@ -147,16 +160,21 @@ def main(argv=None):
         lcd.write_covariances(a.covariances, graph.marginals(frame="position", huber=a.huber))
         line["covariances"] = a.covariances
     if a.mesh:
+        fuse = lambda lo, hi: {}
+        if a.deskew_config is not None:
+            twists = motion.twists_from_poses(res.poses)
+            fuse = lambda lo, hi: dict(deskew=a.deskew_config, twists=twists[lo:hi],
+                                       **({} if times is None else dict(times=times[int(offsets[lo]):int(offsets[hi])])))
         if a.window is not None:      # the window follows the optimized poses; what leaves it is meshed on the way
             vol = tsdf.RollingTsdfVolume(eng, (a.window, a.window, 20.0), a.voxel)
             for s in range(n):
                 vol.follow(res.poses[s, :3, 3])
                 vol.integrate_scans(points[int(offsets[s]):int(offsets[s + 1])], [0, int(offsets[s + 1] - offsets[s])], res.poses[s:s + 1],
-                                    **sensor)
+                                    **sensor, **fuse(s, s + 1))
         else:
             lo, hi = odometry.bounds_from_poses(res.poses, a.max_range)
             vol = tsdf.TsdfVolume(eng, lo, hi, a.voxel)
-            vol.integrate_scans(points, offsets, res.poses, **sensor)
+            vol.integrate_scans(points, offsets, res.poses, **sensor, **fuse(0, n))
         mesh = vol.mesh()
         mesh.to_ply(a.mesh)
         line.update(mesh=a.mesh, triangles=mesh.n_triangles)
