@@ -1,4 +1,5 @@
-"""ctypes binding of libovn_hip.so (C ABI declared in include/ovn_hip.h, with additions in include/ovn_hip_deskew.h).
+"""ctypes binding of libovn_hip.so (C ABI declared in include/ovn_hip.h, with additions in include/ovn_hip_deskew.h and
+include/ovn_hip_tsdf_store.h).
 
 There is NO fallback: if the shared library is missing or a call fails, an exception is raised.
 """
@@ -137,6 +138,14 @@ EXT_SIGNATURES = {
     "ovn_deskew": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, C.c_double, C.c_int, _vp, C.c_double, _vp]),
 }
 
+# additions declared in include/ovn_hip_tsdf_store.h, one to one (tests/test_tsdf_store_host.py): a third table, because
+# tests/test_deskew_host.py pins EXT_SIGNATURES to ovn_deskew alone
+STORE_SIGNATURES = {
+    "ovn_tsdf_window_brick_flags": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _vp]),
+    "ovn_tsdf_window_page_out": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _i32p, C.c_int, _vp, _vp, _vp]),
+    "ovn_tsdf_window_page_in": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _i32p, C.c_int, _vp, _vp, _vp]),
+}
+
 
 class OvnError(Exception):
     pass
@@ -170,7 +179,7 @@ def load() -> C.CDLL:
         raise OvnError("%s not found: the HIP extension is not built. Run `python -c 'import __graft_entry__ as g; "
                        "g.build()'` (or `make -C overlapnet_amd/csrc`). There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(STORE_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -315,11 +315,15 @@ class RollingTsdfOdometry(TsdfOdometry):
     predicted position; the cells that leave are meshed and go to on_leave(piece (T,3,3) float32), or into `volume.pieces` without one,
     so that `volume.mesh()` is the whole drive's.  Refused: a window whose half extent in x or y is below max_range + trunc + voxel +
     shift * voxel, what a scan can reach from a sensor that may stand `shift` voxels off the centre.  The z extent is the caller's to
-    choose, as `below` and `above` are for the fixed box: a sensor that looks along the ground does not reach max_range upwards."""
+    choose, as `below` and `above` are for the fixed box: a sensor that looks along the ground does not reach max_range upwards.
+    store: the volume's (`RollingTsdfVolume(store=)`) -- True or a `tsdf_store.TsdfBrickStore` keeps what leaves
+    the window and brings it back when the drive returns; nothing is meshed on the way, so on_leave is refused with it."""
 
     def __init__(self, engine, extent, voxel: float, trunc: Optional[float] = None, anchor=(0.0, 0.0, 0.0), shift: int = 8,
-                 on_leave=None, **tracker):
-        self._rolling = dict(extent=extent, anchor=anchor, shift=shift)
+                 on_leave=None, store=None, **tracker):
+        if store is not None and store is not False and on_leave is not None:
+            raise ValueError("on_leave and store= exclude each other: with a store nothing is meshed when it leaves")
+        self._rolling = dict(extent=extent, anchor=anchor, shift=shift, store=store)
         self.on_leave = on_leave
         super().__init__(engine, None, None, voxel, trunc=trunc, **tracker)
 
@@ -334,7 +338,7 @@ class RollingTsdfOdometry(TsdfOdometry):
             raise ValueError("a window of %d x %d samples at voxel %g m reaches %g m from its centre in x or y, below max_range + trunc + "
                              "voxel + shift * voxel = %g m" % (shape[0], shape[1], voxel, half, need))
         return RollingTsdfVolume(engine, self._rolling["extent"], voxel, trunc=trunc, max_weight=max_weight,
-                                 anchor=self._rolling["anchor"], shift=shift)
+                                 anchor=self._rolling["anchor"], shift=shift, store=self._rolling["store"])
 
     def _before_view(self, pose: np.ndarray) -> None:
         self.volume.follow(np.asarray(pose, np.float64)[:3, 3], self.on_leave, self.min_weight)
@@ -343,13 +347,14 @@ class RollingTsdfOdometry(TsdfOdometry):
 def estimate_poses(engine, points, offsets, voxel: float = 0.2, trunc: Optional[float] = None, proj_h: int = 64, proj_w: int = 900,
                    fov_up: float = 3.0, fov_down: float = -25.0, max_range: float = 50.0, min_range: float = 0.5, below: float = 5.0,
                    above: float = 15.0, chunk: int = 64, min_fitness: Optional[float] = None, window=None, shift: int = 8,
-                   deskew: Optional[dict] = None, times=None, deskew_passes: int = 1, **icp_params):
+                   deskew: Optional[dict] = None, times=None, deskew_passes: int = 1, keep: bool = False, **icp_params):
     """The poses of a drive from its scans: `frame_to_frame` gives a first trajectory, its `bounds_from_poses` the volume's box, and
     `TsdfOdometry` tracks the drive against the volume it builds.  A box over 2^31 - 1 samples is refused with `volume_shape`'s message,
     which names the voxel that fits (the volume does not follow the sensor).  -> (poses (n,4,4), [TrackResult] * n, the TsdfVolume).
     window: metres, 3 numbers or one for x and y with below + above for z -- `RollingTsdfOdometry` tracks the drive in a window of
     that size that follows the sensor, `shift` voxels at a time: no `frame_to_frame` pass, no limit on the drive's extent, and the
-    volume returned is the RollingTsdfVolume, whose `mesh()` is the whole drive's.
+    volume returned is the RollingTsdfVolume, whose `mesh()` is the whole drive's.  keep=True (with window) gives that volume a brick
+    store: what leaves the window is kept and comes back when the drive revisits it.
     deskew, deskew_passes: the trackers' (DESIGN.md section 37), with times (total,) float32, one fraction per row of `points`, where
     the deskew dict names no azimuth parameters.  `frame_to_frame` does not deskew: its trajectory only sizes the box."""
     from .tsdf import volume_shape
@@ -357,6 +362,8 @@ def estimate_poses(engine, points, offsets, voxel: float = 0.2, trunc: Optional[
     n = offs.shape[0] - 1
     if n < 1:
         raise ValueError("estimate_poses needs at least one scan")
+    if keep and window is None:
+        raise ValueError("keep=True belongs to window=: the fixed box forgets nothing")
     if times is not None:
         if deskew is None:
             raise ValueError("times belong to deskew=")
@@ -369,8 +376,8 @@ def estimate_poses(engine, points, offsets, voxel: float = 0.2, trunc: Optional[
         ext = np.asarray(window, np.float64).reshape(-1)
         if ext.shape[0] == 1:
             ext = np.array([ext[0], ext[0], float(below) + float(above)])
-        odo = RollingTsdfOdometry(engine, ext, voxel, trunc=trunc, shift=shift, min_range=min_range, min_fitness=min_fitness, **sensor,
-                                  **motion, **icp_params)
+        odo = RollingTsdfOdometry(engine, ext, voxel, trunc=trunc, shift=shift, min_range=min_range, min_fitness=min_fitness,
+                                  store=True if keep else None, **sensor, **motion, **icp_params)
         for s in range(n):
             odo.track(points[int(offs[s]):int(offs[s + 1])], **scan_times(s))
         return np.stack(odo.poses), odo.results, odo.volume

@@ -317,10 +317,18 @@ class RollingTsdfVolume(TsdfVolume):
 
     The lattice is fixed: sample (I, J, K) sits at anchor + (I, J, K) * voxel.  The window holds base <= (I, J, K) < base + (nx, ny,
     nz) in ring storage and starts centred on the anchor.  `follow` moves the base in multiples of `shift` voxels (a multiple of 8) and
-    meshes the cells that lose a corner before their slots are cleared.  A region the window comes back to is fresh."""
+    meshes the cells that lose a corner before their slots are cleared.  A region the window comes back to is fresh.
+
+    store: None (the default) is all of the above and makes the launches it always made.  True, or a
+    `tsdf_store.TsdfBrickStore` (one that `load` made continues a saved map; its voxel, anchor and trunc must be this volume's), keeps
+    what leaves: `follow` pages the non-empty 8 x 8 x 8 bricks of the leaving samples out to the store, shifts, and pages the stored
+    bricks of the entering samples back in, so a region the window comes back to holds what it held.  `follow` then meshes nothing and
+    `mesh()` sweeps window and store, every cell once."""
+
+    store = None                         # the TsdfBrickStore of a volume built with store=
 
     def __init__(self, engine, extent, voxel: float, trunc: float = None, max_weight: float = 64.0, anchor=(0.0, 0.0, 0.0),
-                 shift: int = 8):
+                 shift: int = 8, store=None):
         self.nx, self.ny, self.nz = window_shape(extent, voxel)
         self.voxel = float(voxel)
         self.trunc = DEFAULT_TRUNC_VOXELS * self.voxel if trunc is None else float(trunc)
@@ -344,6 +352,12 @@ class RollingTsdfVolume(TsdfVolume):
         self.n_scans = 0
         self.n_shifts = 0
         self.pieces = []                 # (T,3,3) float32 host arrays: what `follow` meshed and no `on_leave` took
+        if store is not None and store is not False:
+            from .tsdf_store import TsdfBrickStore
+            self.store = TsdfBrickStore(engine) if store is True else store
+            if not isinstance(self.store, TsdfBrickStore):
+                raise ValueError("store must be None, True or a TsdfBrickStore, got %r" % (store,))
+            self.store.bind(self)
 
     @property
     def shape(self) -> Tuple[int, int, int]:
@@ -357,9 +371,11 @@ class RollingTsdfVolume(TsdfVolume):
         return dict(base=self.base)
 
     def reset(self) -> None:
-        """Back to the fresh window at the base it has; the pieces kept so far are dropped."""
+        """Back to the fresh window at the base it has; the pieces kept so far are dropped, and so is every brick of the store."""
         super().reset()
         self.pieces = []
+        if self.store is not None:
+            self.store.clear()
 
     def cell_of(self, position) -> Tuple[int, int, int]:
         """The lattice cell a point lies in: floor((position - anchor) / voxel) per axis."""
@@ -380,11 +396,22 @@ class RollingTsdfVolume(TsdfVolume):
     def follow(self, position, on_leave=None, min_weight: float = 1.0) -> bool:
         """Moves the window after the sensor at `position`; -> whether it moved.  Before the slots that change hands are cleared, the
         cells with at least one corner among the leaving samples are meshed -- at most three boxes of cells, `leaving_boxes` -- and
-        every non-empty piece, an (T,3,3) float32 host array, goes to on_leave(piece), or into `self.pieces` without one."""
+        every non-empty piece, an (T,3,3) float32 host array, goes to on_leave(piece), or into `self.pieces` without one.  With a
+        store nothing is meshed (on_leave is refused): the leaving bricks are paged out, the window shifts, the entering bricks that
+        the store holds are paged in.  A page-out over the store's max_bytes raises with window, base and store as they were."""
+        if self.store is not None and on_leave is not None:
+            raise ValueError("on_leave and store= exclude each other: with a store nothing is meshed when it leaves")
         new = self.next_base(position)
         if new == self.base:
             return False
         check_window(self.shape, new)
+        if self.store is not None:
+            self.store.page_out(self, leaving_boxes(self.base, new, self.shape))          # boxes of SAMPLES: the full shape
+            self.engine.tsdf_window_shift(self.tsdf, self.weight, self.base, new)
+            old, self.base = self.base, new
+            self.store.page_in(self, leaving_boxes(new, old, self.shape))
+            self.n_shifts += 1
+            return True
         if self.n_scans > 0:                      # a window nothing was fused into has no surface to keep
             for lo, hi in leaving_boxes(self.base, new, tuple(n - 1 for n in self.shape)):      # boxes of CELLS, by their low corners
                 tri = self.triangles(min_weight, box=(lo, hi))
@@ -401,9 +428,13 @@ class RollingTsdfVolume(TsdfVolume):
 
     def triangles(self, min_weight: float = 1.0, box=None):
         """(T,3,3) float32 device tensor, T >= 0: the triangles of the cells whose low corner lies in box = (lo, hi), hi exclusive, in
-        ascending cell order within the box; box=None is every cell of the window.  A cell needs all eight corners in the window."""
+        ascending cell order within the box; box=None is every cell of the window.  A cell needs all eight corners in the window.
+        With a store, box=None is every cell of window and store, once, in the order of the sweep's tiles
+        (`TsdfBrickStore.triangles`)."""
         if np.isnan(float(min_weight)):
             raise ValueError("min_weight is NaN")
+        if self.store is not None and box is None:
+            return self.store.triangles(self, min_weight)
         top = tuple(b + n - 1 for b, n in zip(self.base, self.shape))
         lo, hi = (self.base, top) if box is None else (tuple(int(v) for v in box[0]), tuple(int(v) for v in box[1]))
         if len(lo) != 3 or len(hi) != 3 or any(l > h or l < b or h > t for l, h, b, t in zip(lo, hi, self.base, top)):
@@ -415,7 +446,8 @@ class RollingTsdfVolume(TsdfVolume):
         return tri
 
     def mesh(self, min_weight: float = 1.0) -> TriangleMesh:
-        """The pieces kept by `follow` in the order they left, then the window, as one TriangleMesh (a soup)."""
+        """The pieces kept by `follow` in the order they left, then the window, as one TriangleMesh (a soup).  With a store: the
+        sweep of window and store (`triangles`), no cell twice."""
         parts = list(self.pieces) + [self.triangles(min_weight).cpu().numpy()]
         tri = np.concatenate(parts).astype(np.float32, copy=False)
         t = int(tri.shape[0])

@@ -3,6 +3,7 @@ distance volume on the GPU and its zero level set extracted (`overlapnet_amd.tsd
 
     python tools/build_mesh.py --config network.json --scans sequences/07/velodyne --poses poses/07.txt --calib sequences/07/calib.txt \\
         --voxel 0.2 --out site.ply [--bounds X0 Y0 Z0 X1 Y1 Z1] [--every N] [--deskew --times DIR | --deskew --start-azimuth DEG --clockwise]
+    python tools/build_mesh.py --load-volume map.npz --out site.ply          # mesh what `tools/odometry.py --keep --save-volume` wrote
 
 The config is the `network.yml` dict `Infer` takes (JSON, or YAML when PyYAML is installed): its `model.inputShape` is the range image
 the scans are projected into.  The poses file holds one pose per line (12 numbers, a 3 x 4 matrix) or is an npz of (n,4,4) matrices,
@@ -11,7 +12,8 @@ scan with the calibration's `Tr:` line; without it they are taken as sensor-to-w
 volume is the poses' bounding box grown by --max-range (and by --below / --above in z); a volume over 2^31 - 1 samples is refused with
 the voxel size that would fit.  --deskew takes the scans as RAW sweeps: each is moved into the sensor frame of fraction --t-ref of its
 sweep under the twist of the step that led to its pose (of ALL the poses, whatever --every says) before it is
-projected, and the poses are taken as the sensor's at that fraction, which is what `tools/odometry.py --deskew` writes.  Prints one JSON
+projected, and the poses are taken as the sensor's at that fraction, which is what `tools/odometry.py --deskew` writes.  --load-volume
+meshes a saved brick store without scans: --config, --scans and --poses are then not needed.  Prints one JSON
 line."""
 import argparse
 import json
@@ -32,13 +34,31 @@ def default_bounds(poses: np.ndarray, max_range: float, below: float, above: flo
     return bounds_from_poses(poses, max_range, below, above)
 
 
+def mesh_saved_volume(a) -> None:
+    """--load-volume: the mesh of a saved brick store, every cell once."""
+    from overlapnet_amd.engine import OvnEngine
+    from overlapnet_amd.tsdf_store import TsdfBrickStore, mesh_from_store
+    t0 = time.time()
+    eng = OvnEngine()
+    try:
+        store = TsdfBrickStore.load(eng, a.load_volume)
+        mesh = mesh_from_store(store, min_weight=a.min_weight)
+        mesh.to_ply(a.out)
+        print(json.dumps({"out": a.out, "loaded_volume": a.load_volume, "bricks": len(store), "voxel": store.meta["voxel"],
+                          "trunc": store.meta["trunc"], "triangles": mesh.n_triangles, "seconds": round(time.time() - t0, 3)}))
+    finally:
+        eng.close()
+
+
 def main(argv=None):
     from tools.build_training_set import lidar_poses, read_calib, read_poses
     from tools.localize import load_config
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--config", required=True)
-    ap.add_argument("--scans", required=True, help="folder of .bin scans (sorted by name = frame order)")
-    ap.add_argument("--poses", required=True)
+    ap.add_argument("--config", default=None)
+    ap.add_argument("--scans", default=None, help="folder of .bin scans (sorted by name = frame order)")
+    ap.add_argument("--poses", default=None)
+    ap.add_argument("--load-volume", default=None, metavar="FILE.npz", help="mesh the brick store `tools/odometry.py --keep "
+                    "--save-volume` wrote, without scans")
     ap.add_argument("--calib", default=None, help="KITTI calib.txt: the poses are camera poses")
     ap.add_argument("--out", required=True, help="the mesh, binary PLY")
     ap.add_argument("--voxel", type=float, default=0.2)
@@ -57,6 +77,13 @@ def main(argv=None):
     motion.add_arguments(ap)
     a = ap.parse_args(argv)
     deskew = motion.config_from_args(ap, a)
+    if a.load_volume is not None:
+        if a.config or a.scans or a.poses or deskew is not None:
+            ap.error("--load-volume meshes a saved volume: it takes no --config, --scans, --poses or --deskew")
+        return mesh_saved_volume(a)
+    missing = [n for n in ("config", "scans", "poses") if getattr(a, n) is None]
+    if missing:
+        ap.error("the following arguments are required: %s" % ", ".join("--" + n for n in missing))
 
     cfg = load_config(a.config)
     h, w = (int(v) for v in cfg["model"]["inputShape"][:2])

@@ -1,12 +1,15 @@
 """Raw scans -> the sensor poses the mapping tools take: LiDAR odometry on the GPU (`overlapnet_amd.odometry`).
 
     python tools/odometry.py --config network.json --scans sequences/07/velodyne --out poses.txt [--mesh site.ply] [--voxel 0.2] \\
-        [--frame-to-frame-only] [--window 120] [--deskew --times DIR | --deskew --start-azimuth DEG --clockwise] [--deskew-passes 2]
+        [--frame-to-frame-only] [--window 120 [--keep [--save-volume map.npz]]] \\
+        [--deskew --times DIR | --deskew --start-azimuth DEG --clockwise] [--deskew-passes 2]
 
 Every scan is registered onto its predecessor (one launch per chunk of pairs); that trajectory sizes a TSDF volume, and the drive is
 then tracked against the volume it builds: each scan is registered onto a ray-cast view of the model at its predicted pose and fused.
 --frame-to-frame-only stops after the first pass.  --window M skips the first pass: the volume is a window M metres wide that follows the
-sensor, and what leaves it is meshed on the way.  The poses file holds one KITTI pose line per scan (12 numbers, sensor to world in the
+sensor, and what leaves it is meshed on the way.  --keep keeps what leaves in a brick store instead and brings it
+back when the drive returns; --save-volume writes window and store as one .npz that `tools/build_mesh.py
+--load-volume` meshes.  The poses file holds one KITTI pose line per scan (12 numbers, sensor to world in the
 sensor frame, the first pose the identity): the file `tools/build_mesh.py --poses` reads without --calib.  --mesh also writes the tracked
 volume's zero level set.  The config is the `network.yml` dict `Infer` takes; its `model.inputShape` is the range image the scans are
 projected into.  --deskew takes the scans as RAW sweeps and undoes the sensor's motion within each while tracking (DESIGN.md section
@@ -35,6 +38,9 @@ def main(argv=None):
     ap.add_argument("--trunc", type=float, default=None, help="truncation distance in metres (default: 4 voxels)")
     ap.add_argument("--window", type=float, default=None, metavar="M", help="track in a volume M metres wide (--below + --above metres "
                     "high) that follows the sensor: no first pass, no limit on the drive's extent; --mesh writes the streamed mesh")
+    ap.add_argument("--keep", action="store_true", help="with --window: keep what leaves the window in a brick store and bring it back "
+                    "when the drive returns")
+    ap.add_argument("--save-volume", default=None, metavar="FILE.npz", help="with --keep: write window and store as one file")
     ap.add_argument("--frame-to-frame-only", action="store_true")
     ap.add_argument("--min-fitness", type=float, default=None, help="a registration below it counts as failed (default: none)")
     ap.add_argument("--below", type=float, default=5.0, help="metres of volume below the lowest sensor position")
@@ -50,6 +56,12 @@ def main(argv=None):
                     "registration found, before it is fused")
     a = ap.parse_args(argv)
     deskew = motion.config_from_args(ap, a)
+    if a.keep and a.window is None:
+        ap.error("--keep belongs to --window")
+    if a.save_volume is not None and not a.keep:
+        ap.error("--save-volume belongs to --keep")
+    if a.keep and a.frame_to_frame_only:
+        ap.error("--keep belongs to the tracker: drop --frame-to-frame-only")
     if deskew is not None and a.frame_to_frame_only:
         ap.error("--deskew belongs to the tracker: drop --frame-to-frame-only")
 
@@ -87,7 +99,7 @@ def main(argv=None):
             try:
                 poses, results, vol = odometry.estimate_poses(eng, points, offsets, voxel=a.voxel, trunc=a.trunc, min_range=a.min_range,
                                                               below=a.below, above=a.above, chunk=a.chunk, min_fitness=a.min_fitness,
-                                                              window=a.window, deskew=deskew, times=times,
+                                                              window=a.window, keep=a.keep, deskew=deskew, times=times,
                                                               deskew_passes=a.deskew_passes, **sensor)
             except ValueError as e:
                 raise SystemExit("odometry: %s" % e)
@@ -97,6 +109,10 @@ def main(argv=None):
                 line.update(deskew=dict(deskew, passes=a.deskew_passes, times=a.times))
             if a.window is not None:
                 line.update(window_m=a.window, window_shifts=vol.n_shifts)
+            if a.keep:
+                line.update(stored_bricks=len(vol.store), stored_bytes=vol.store.bytes)
+                if a.save_volume is not None:
+                    line.update(saved_volume=a.save_volume, saved_bricks=vol.store.save(a.save_volume, window=vol))
             if a.mesh:
                 mesh = vol.mesh()
                 mesh.to_ply(a.mesh)

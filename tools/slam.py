@@ -65,6 +65,8 @@ def parse(argv=None):
     ap.add_argument("--voxel", type=float, default=0.2)
     ap.add_argument("--window", type=float, default=None, metavar="M", help="track (and mesh) in a TSDF window M metres wide that follows "
                     "the sensor instead of a volume over the whole drive")
+    ap.add_argument("--keep", action="store_true", help="with --window: keep what leaves the window in a brick store, for tracking and for "
+                    "the re-fusion at the optimized poses, so that a revisited street is one surface (DESIGN.md section 38)")
     ap.add_argument("--fov-up", type=float, default=3.0)
     ap.add_argument("--fov-down", type=float, default=-25.0)
     ap.add_argument("--max-range", type=float, default=50.0)
@@ -77,6 +79,8 @@ def parse(argv=None):
     motion.add_arguments(ap)
     a = ap.parse_args(argv)
     a.deskew_config = motion.config_from_args(ap, a)
+    if a.keep and a.window is None:
+        ap.error("--keep belongs to --window")
     if a.min_gap < 1 or a.top_k < 1 or a.batch < 1:
         ap.error("--min-gap, --top-k and --batch must be >= 1")
     if a.gate_sigma is not None and not a.gate_sigma > 0.0:
@@ -116,8 +120,8 @@ def main(argv=None):
         if poses.shape[0] != n:
             raise SystemExit("%s holds %d poses for %d scans" % (a.poses, poses.shape[0], n))
     else:
-        poses, _, _ = odometry.estimate_poses(eng, points, offsets, voxel=a.voxel, window=a.window, deskew=a.deskew_config, times=times,
-                                              **sensor)
+        poses, _, _ = odometry.estimate_poses(eng, points, offsets, voxel=a.voxel, window=a.window, keep=a.keep, deskew=a.deskew_config,
+                                              times=times, **sensor)
     line = {"out": a.out, "scans": n, "odometry_seconds": round(time.time() - t0, 3)}
 
     infer.cache_frames(n)
@@ -166,7 +170,7 @@ def main(argv=None):
             fuse = lambda lo, hi: dict(deskew=a.deskew_config, twists=twists[lo:hi],
                                        **({} if times is None else dict(times=times[int(offsets[lo]):int(offsets[hi])])))
         if a.window is not None:      # the window follows the optimized poses; what leaves it is meshed on the way
-            vol = tsdf.RollingTsdfVolume(eng, (a.window, a.window, 20.0), a.voxel)
+            vol = tsdf.RollingTsdfVolume(eng, (a.window, a.window, 20.0), a.voxel, store=True if a.keep else None)
             for s in range(n):
                 vol.follow(res.poses[s, :3, 3])
                 vol.integrate_scans(points[int(offsets[s]):int(offsets[s + 1])], [0, int(offsets[s + 1] - offsets[s])], res.poses[s:s + 1],
